@@ -13,9 +13,11 @@ the only collective is the one-time RCCL broadcast of the packed weights from ra
 `--config {0,2,3,4}` runs another BASELINE.json configuration instead (never the headline; configs[3] = the
 8-way sharded 4096 pairs is `--gpus 8 --config 3`, 512 pairs per GPU).
 
-The timed window (--steps steps between barrier + synchronize, max over ranks) is repeated --windows times (default 5) and
-the MEDIAN window is the reported value (`timing` lists them all).  Rank 0 prints ONE JSON line: metric keypoint-pairs/sec
-(whole job), plus
+Exactly --steps steps are timed, between barrier + synchronize, max over ranks: `ms_per_step` is their time over --steps.
+`--windows W` splits them into W windows of as equal a number of steps as possible and reports the MEDIAN window's time per
+step instead (`timing` lists every window; each window pays one pipeline fill and drain).  `--dump-outputs DIR` writes what the last timed step returned (rank 0's pairs) as
+DIR/<name>.npy; inputs and weights come from fixed seeds, so the same arguments give the same inputs in every run.
+Rank 0 prints ONE JSON line: metric keypoint-pairs/sec (whole job), plus
   roofline     - the dominant kernel class of the step against the f16 MFMA roofline (or HBM for Sinkhorn): algorithmic
                  FLOPs per launch over its average launch duration, measured live with HIP events on the launch stream
                  (mdgat_profile); `frac_executed` = the 3x split-f16 MFMA work the matrix cores actually run.  The library runs a
@@ -352,6 +354,29 @@ def pmc_traffic(config, kernel):
         return None, None
 
 
+DUMP_NAMES = ('matches0', 'matches1', 'matching_scores0', 'matching_scores1')     # MDGAT._run's return (its Z is None here)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: MDGAT._run's arrays as path/<name>.npy - integer matches as float64 (exact), float32 stays float32.
+    Over 64 MB in all, the same seeded sample of pairs is kept in every array and its indices go to sample_pairs.npy."""
+    import numpy as np
+    arrays = {}
+    for name, t in zip(DUMP_NAMES, outs):
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        B = arrays['matches0'].shape[0]
+        keep = np.sort(np.random.RandomState(0).choice(B, max(1, B * DUMP_LIMIT_BYTES // (total + 8 * B)), replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+        arrays['sample_pairs'] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` must produce N ranks or fail (the reference's multi-GPU is one line, test.py:158).  Started
     without a launcher and asked for more than one GPU, this process becomes the launcher: it re-executes the same command
@@ -385,8 +410,8 @@ def main():
     ap.add_argument('--batch', type=int, default=None, help='pairs per GPU per step (default: the configuration\'s)')
     ap.add_argument('--attention-dtype', default=None, choices=['fp32', 'f16'],
                     help="'f16': single-f16 attention products (BASELINE configs[2]; outside the parity bar, not the headline)")
-    ap.add_argument('--windows', type=int, default=5,
-                    help='the timed window of --steps steps is repeated this many times; value = the median window')
+    ap.add_argument('--windows', type=int, default=1,
+                    help='the --steps timed steps are split into this many windows; value = the median window\'s time per step')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-breakdown', action='store_true')
     ap.add_argument('--no-dict-api', action='store_true', help='skip the forward(dict) throughput leg')
@@ -395,7 +420,11 @@ def main():
                     help="'fp64': time the reference-exact mode (MDGAT(arithmetic='fp64')) as the step; never the headline")
     ap.add_argument('--no-exact-mode', action='store_true', help='skip the exact_mode block (reference-exact fp64 mode on a bounded batch)')
     ap.add_argument('--no-parity', action='store_true', help='skip the parity block (profiling runs: its 8-pair forwards would enter the per-kernel averages)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     self_launch(args)
 
     c = CONFIGS[args.config]
@@ -443,25 +472,31 @@ def main():
         sync()
         for _ in range(args.warmup):
             step()
-        # EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks: one window.  A window at
-        # B = 64 is 20 x 3.3 ms = 67 ms - a single sample on a box whose clocks move - so the window is repeated and the
-        # MEDIAN window is reported (all windows are listed in the line).
-        windows, own_windows = [], []
-        for _ in range(max(1, args.windows)):
+        # EXACTLY --steps timed steps in --windows windows, barrier + synchronize on both sides of each, max over ranks; the
+        # MEDIAN window's time per step is reported (all windows are listed in the line).  Every window pays one pipeline fill
+        # and drain (~0.3 ms at B = 64), so more windows of fewer steps read slower.
+        n_win = min(max(1, args.windows), args.steps)
+        window_steps = [args.steps // n_win + (i < args.steps % n_win) for i in range(n_win)]
+        windows, own_windows = [], []       # seconds per window
+        for k in window_steps:
             shard.barrier(world)
             sync()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                step()
+            for _ in range(k):
+                last = step()
             sync()
             own = time.perf_counter() - t0          # this rank's own time for the window (before it waits for the others)
             shard.barrier(world)
             windows.append(shard.max_over_ranks(time.perf_counter() - t0, dev, world))
             own_windows.append(own)
-    dt = sorted(windows)[len(windows) // 2]
+    per_step = [w / k for w, k in zip(windows, window_steps)]
+    dt = sorted(per_step)[len(per_step) // 2]      # seconds per step, median window
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     # every rank's pair count and own time per step (median window), gathered on all ranks: a straggler shows in the line,
     # and the partition must add up to the job
-    mine = torch.tensor([float(count), 1e3 * sorted(own_windows)[len(own_windows) // 2] / args.steps], dtype=torch.float64)
+    own_per_step = sorted(w / k for w, k in zip(own_windows, window_steps))
+    mine = torch.tensor([float(count), 1e3 * own_per_step[len(own_per_step) // 2]], dtype=torch.float64)
     per_rank = shard.gather_matches(mine[None].to(dev if not stub else 'cpu'), world).cpu()
     assert int(per_rank[:, 0].sum()) == B * world, (per_rank[:, 0].tolist(), B, world)
     # asynchronous status of the forwards timed above: an f16 range violation raises here (the outputs would be invalid)
@@ -474,7 +509,7 @@ def main():
     range_violation = shard.max_over_ranks(float(range_violation), dev if not stub else 'cpu', world) > 0
 
     if rank == 0:
-        pairs = B * world * args.steps
+        pairs = B * world           # per step
         parity = att == 'fp32'
         out = {
             'metric': 'keypoint-pairs/sec',
@@ -483,8 +518,8 @@ def main():
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
-            'ms_per_step': 1e3 * dt / args.steps,
-            'ms_per_pair': 1e3 * dt / args.steps / B,
+            'ms_per_step': 1e3 * dt,
+            'ms_per_pair': 1e3 * dt / B,
             'higher_is_better': True,
             'scaling': 'weak',
             'vs_baseline': None,
@@ -501,8 +536,9 @@ def main():
                        # what the communicator saw (RCCL when collectives == 'nccl'): must equal n_gpus
                        'rccl_world_size': torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
                        'pairs_per_rank': [int(v) for v in per_rank[:, 0].tolist()]},
-            'timing': {'windows': len(windows), 'value_is': 'median window', 'window_ms': [round(1e3 * w, 3) for w in windows],
-                       'best_pairs_per_s': pairs / min(windows), 'worst_pairs_per_s': pairs / max(windows),
+            'timing': {'windows': len(windows), 'value_is': 'median window (time per step)', 'window_steps': window_steps,
+                       'window_ms': [round(1e3 * w, 3) for w in windows],
+                       'best_pairs_per_s': pairs / min(per_step), 'worst_pairs_per_s': pairs / max(per_step),
                        'per_rank_ms_per_step': [round(v, 4) for v in per_rank[:, 1].tolist()]},
             # mdgat_async_status after the timed windows (the timed step is the asynchronous MDGAT._run)
             'status': {'sinkhorn_fallback': bool(status['sinkhorn_fallback']), 'range_violation': bool(range_violation)},

@@ -821,6 +821,35 @@ def test_bench_two_ranks_one_gpu():
     assert 'cpu_baseline' not in d                      # rank 0 at N = 1 only
 
 
+def test_bench_dump_outputs_are_the_timed_steps(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned: bit for bit what MDGAT._run gives in a fresh
+    process on the same seeded weights and inputs, and exactly --steps steps are timed."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '1', '--windows', '3', '--batch', '4',
+           '--dump-outputs', str(tmp_path), '--no-breakdown', '--no-exact-mode', '--no-parity', '--no-dict-api', '--no-latency',
+           '--no-cpu-baseline']
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][0])
+    assert d['steps'] == 7 and d['timing']['window_steps'] == [3, 2, 2] and d['ms_per_step'] > 0
+    cfg = synth.default_config(L=9, sinkhorn_iterations=100)
+    cfg.update(attention_dtype='fp32', arithmetic='fp32')
+    net = MDGAT(cfg).eval()
+    net.load_state_dict(synth.make_state_dict(L=9, seed=0, dtype=torch.float32))
+    data = synth.make_batch(4, 512, 512, dtype=torch.float32, device=DEV)
+    with torch.no_grad():
+        ref = net._run(data['keypoints0'], data['scores0'], data['descriptors0'], data['keypoints1'], data['scores1'],
+                       data['descriptors1'])
+    for name, t, dtype in zip(('matches0', 'matches1', 'matching_scores0', 'matching_scores1'), ref,
+                              (np.float64, np.float64, np.float32, np.float32)):
+        a = np.load(os.path.join(tmp_path, name + '.npy'))
+        assert a.dtype == dtype and a.shape == tuple(t.shape), name
+        np.testing.assert_array_equal(a, t.cpu().numpy().astype(dtype), err_msg=name)
+
+
 def test_fuzz_checkpoint_short():
     """15 s of tools/fuzz_checkpoint.py - the forward-level robustness sweep standing in for the checkpoint the reference tree
     does not hold (pre-trained/best_model.pth is a missing blob): function-preserving rescalings of q against k, v against

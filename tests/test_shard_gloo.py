@@ -260,7 +260,7 @@ def test_bench_eight_ranks_gloo_stub(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '8', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'tests', 'bench_stub_runner.py'), '--gpus', '8', '--config', '3',
-           '--steps', '3', '--warmup', '1', '--windows', '2']
+           '--steps', '3', '--warmup', '1', '--windows', '2', '--dump-outputs', str(tmp_path / 'out')]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -271,7 +271,10 @@ def test_bench_eight_ranks_gloo_stub(tmp_path):
     assert c['rccl_world_size'] == 8 and c['collectives'] == 'gloo' and c['pairs_per_rank'] == [512] * 8 and c['baseline_config'] == 3
     t = d['timing']
     assert len(t['per_rank_ms_per_step']) == 8 and max(range(8), key=lambda r: t['per_rank_ms_per_step'][r]) == 3     # the straggler
-    assert abs(d['value'] - 4096 * 3 / (sorted(t['window_ms'])[len(t['window_ms']) // 2] * 1e-3)) < 1e-3 * d['value']      # (window_ms is rounded)
+    assert t['window_steps'] == [2, 1]                                   # exactly --steps timed steps, split into the windows
+    per_step = sorted(w / k for w, k in zip(t['window_ms'], t['window_steps']))
+    assert abs(d['value'] - 4096 / (per_step[len(per_step) // 2] * 1e-3)) < 1e-3 * d['value']      # (window_ms is rounded)
+    assert abs(d['ms_per_step'] - per_step[len(per_step) // 2]) < 1e-3 * d['ms_per_step']
     assert d['ms_per_step'] >= max(t['per_rank_ms_per_step']) * 0.999        # the whole job waits for its slowest rank
     assert d['status']['sinkhorn_fallback'] is False and d['status']['range_violation'] is False
     # the parity fields are COMPUTED in the run (here on the recorder's zeros: presence and shape, not values)
@@ -282,13 +285,18 @@ def test_bench_eight_ranks_gloo_stub(tmp_path):
         assert isinstance(mode['max_abs_dZ'], float) and isinstance(mode['max_abs_d_mscores'], float)
         assert mode['arg_maxes'] == 40 * 1024 and mode['matches_differing'] >= 0
     assert d['status']['literal_1e-4_pairs'] == {m: f"{pm[m]['pairs_within_1e-4']}/40" for m in pm} and 'measured' in d['status']['parity_source']
-    # every rank ran its own 512 pairs, and only those: 8 + warmup + windows x steps forwards of 512 x 512 x 512
+    # every rank ran its own 512 pairs, and only those: 8 + warmup + steps forwards of 512 x 512 x 512
     for r in range(8):
         calls = open(f'{log}.{r}').read().split('\n')[:-1]
-        timed = calls[:8 + 1 + 2 * 3]
-        assert timed and set(timed) == {'512 512 512'} and len(timed) == 8 + 1 + 2 * 3, (r, len(calls))
+        timed = calls[:8 + 1 + 3]
+        assert timed and set(timed) == {'512 512 512'} and len(timed) == 8 + 1 + 3, (r, len(calls))
         # behind them, on rank 0 only: the parity block's two forwards over the 40 reference-held pairs (one per arithmetic mode)
         assert calls[len(timed):] == (['40 512 512'] * 2 if r == 0 else []), (r, calls[len(timed):])
+    # --dump-outputs: rank 0's outputs of the last timed step (the recorder's zeros), integer matches as float64
+    for name, dtype in (('matches0', np.float64), ('matches1', np.float64), ('matching_scores0', np.float32),
+                        ('matching_scores1', np.float32)):
+        a = np.load(tmp_path / 'out' / f'{name}.npy')
+        assert a.dtype == dtype and a.shape == (512, 512) and not a.any(), name
 
 
 def test_bench_plain_form_starts_its_own_ranks(tmp_path):
