@@ -14,12 +14,17 @@
  *   - all tensors are owned by the caller (PyTorch); the library keeps only its packed weights;
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - return 0 on success, a negative mdgat_status otherwise; mdgat_last_error() gives the text;
- *   - a handle is bound to one device.  Thread safety: mdgat_forward / mdgat_forward_frames on ONE handle may be called from
+ *   - a handle is bound to one device: the forward entry points make it current for the length of the call and restore the
+ *     caller's device after it, so they may be called with any device current.  The per-op entry points (mdgat_sinkhorn_f64,
+ *     mdgat_attention, ...) run on the current device.  Device indices 0 .. 63 are supported (mdgat_create refuses others).
+ *   - thread safety: mdgat_forward / mdgat_forward_frames on ONE handle may be called from
  *     several host threads (and streams) - the library serialises the enqueue of a call internally (a mutex in the handle: the
  *     second lane's stream, its fork / join events and the profiling state are per handle); the device work of calls issued on
  *     different streams overlaps as far as those streams allow, but the halves that run on the handle's second lane queue on
  *     that one stream in call order.  Each call needs its own workspace while it is in flight.  mdgat_set_lanes,
- *     mdgat_load_weights, mdgat_profile and mdgat_destroy must not race with a forward on the same handle.
+ *     mdgat_load_weights, mdgat_profile and mdgat_destroy must not race with a forward on the same handle.  Exact-mode
+ *     (MDGAT_ARITH_FP64) forwards and the fp64 Sinkhorn entry points additionally enqueue one call at a time per device, across
+ *     handles: their kernels whose workgroups wait for each other run one launch at a time per device, whatever the stream.
  *
  * Layouts (fp32, row-major, innermost last)
  *   keypoints  kpts  [B][N][3]      saliency sigma [B][N]      FPFH fpfh [B][N][33]
@@ -120,8 +125,8 @@ size_t mdgat_topk_sel_words(int B, int N, int M);
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
 
-/* MDGAT(config).to(device) (test.py:156, 172).  Fails with MDGAT_ERR_UNSUPPORTED unless the
- * device is gfx950. */
+/* MDGAT(config).to(device) (test.py:156, 172).  Fails with MDGAT_ERR_BAD_ARG for a device index outside
+ * 0 .. 63, with MDGAT_ERR_UNSUPPORTED unless the device is gfx950. */
 int mdgat_create(const mdgat_config* cfg, int device, mdgat_handle** out);
 
 /* net.load_state_dict(...) (test.py:159) after host-side packing (BN folded into the convs, heads

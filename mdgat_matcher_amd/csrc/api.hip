@@ -110,6 +110,7 @@ extern "C" int mdgat_create(const mdgat_config* cfg, int device, mdgat_handle** 
     if (cfg->extract_mode < 0 || cfg->extract_mode > 3) { mdgat_set_error("mdgat_create: bad extract_mode %d", cfg->extract_mode); return MDGAT_ERR_BAD_ARG; }
     for (int i = 0; i < 2 * cfg->L; ++i)
         if (cfg->topk[i] < 0) { mdgat_set_error("mdgat_create: topk[%d] < 0", i); return MDGAT_ERR_BAD_ARG; }
+    if (device < 0 || device >= MDGAT_MAX_DEVICES) { mdgat_set_error("mdgat_create: device %d outside 0 .. %d", device, MDGAT_MAX_DEVICES - 1); return MDGAT_ERR_BAD_ARG; }
     hipDeviceProp_t prop;
     if (int rc = mdgat_check_hip(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties")) return rc;
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
@@ -467,7 +468,8 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
         const size_t Rz = (size_t)R;
         // (the forward's launches of kernels whose workgroups wait for each other - clustered layer tails, the resident fp64 Sinkhorn - as
         // one group of the device's chain: coop_chain.hpp)
-        CoopGroup coop_group(h->device, s, true);
+        CoopGroup coop_group;
+        if ((rc = coop_group.open(h->device, s))) return rc;
         auto gemm = [&](const double* A0, int lda0, int K0, const double* A1, int lda1, size_t wofs, size_t bofs, int relu, const double* Rs, double* C, int ldc,
                         int cout, int K) {
             GemmF64Args g{A0, lda0, K0, A1, lda1, w64 + wofs, K, w64 + bofs, Rs, ldc, C, ldc, R, cout, K, relu, status_dev + MDGAT_STATUS_RANGE};
@@ -548,7 +550,7 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
                 const LayerF64Args t{ws.x64, ws.msg64, lf + WF64_W1, w64 + lo + bl.mlp1_b, lf + WF64_W2, w64 + lo + bl.mlp2_b,
                                      last ? nullptr : lf + layer_f64_frag_doubles() + WF64_QKV, last ? nullptr : w64 + lo + bl.layer_stride + bl.qkv_b,
                                      ws.qkv64, last ? ws.x : nullptr, R, status_dev + MDGAT_STATUS_RANGE, ws.hid64};
-                if ((rc = launch_layer_tail_f64(t, s))) return rc;
+                if ((rc = launch_layer_tail_f64(t, coop_group))) return rc;
                 handed_over = last;
             } else {
                 if ((rc = gemm(ws.x64, 128, 128, ws.msg64, 128, lo + bl.mlp1_w, lo + bl.mlp1_b, 1, nullptr, ws.hid64, 256, 256, 256))) return rc;
@@ -582,7 +584,7 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
             const SkExtract ex64{h->cfg.extract_mode, h->cfg.match_threshold, matches0, matches1, mscores0, mscores1, defer_alldust,
                                  status_dev + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
             if ((rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, h->cfg.sinkhorn_iters, nullptr, Z, h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, ri, rv, ci, cv,
-                                          ws.sk64, kb, status_dev + MDGAT_STATUS_RANGE, s, w64 + bl.bin_score))) return rc;
+                                          ws.sk64, kb, status_dev + MDGAT_STATUS_RANGE, coop_group, w64 + bl.bin_score))) return rc;
             if ((rc = launch_extract_from_bests(B, N, M, &ex64, ri, rv, ci, cv, s))) return rc;
             mark(MDGAT_PROF_SINKHORN);
             return MDGAT_OK;
@@ -738,6 +740,14 @@ static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in
                            const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
     LanePlan p{1, B, 1, 0};
     if (!h) { mdgat_set_error("mdgat_forward: null handle"); return MDGAT_ERR_BAD_ARG; }
+    // the handle's device is current for the whole call, the caller's restored after it: everything below works on the current device
+    struct DeviceScope {
+        int prev = -1, dev;
+        hipError_t set = hipSuccess;
+        explicit DeviceScope(int d) : dev(d) { (void)hipGetDevice(&prev); if (prev != dev) set = hipSetDevice(dev); }
+        ~DeviceScope() { if (prev != dev) (void)hipSetDevice(prev); }
+    } scope(h->device);
+    if (int rc = mdgat_check_hip(scope.set, "hipSetDevice")) return rc;
     std::lock_guard<std::mutex> serialise(h->enqueue);
     if (++h->match_token == 0) h->match_token = 1;      // this call's token (mdgat_matched_any): every slice / lane of the call writes the same one
     if (!taps && B > 0 && N > 0 && M > 0 && matches0 && matches1 && mscores0 && mscores1) p = lane_plan(h->lanes, B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64);

@@ -44,14 +44,32 @@ __device__ __forceinline__ constexpr int mfma32_row(int r, int hi) { return (r &
 
 void mdgat_set_error(const char* fmt, ...);
 int mdgat_check_hip(hipError_t e, const char* what);
+
+// Per-device state (launch chains, CU counts, LDS opt-ins) is kept for device indices 0 .. MDGAT_MAX_DEVICES - 1;
+// mdgat_create refuses the others.  The launchers work on the CURRENT device: the forward makes the handle's current.
+constexpr int MDGAT_MAX_DEVICES = 64;
+inline int mdgat_current_device() {
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MDGAT_MAX_DEVICES ? dev : -1;
+}
+// compute units of the current device (asked once per device; 256, the MI355X's, if the runtime cannot tell)
+inline int mdgat_cu_count() {
+    static std::atomic<int> cached[MDGAT_MAX_DEVICES];
+    const int dev = mdgat_current_device();
+    int n = dev >= 0 ? cached[dev].load(std::memory_order_relaxed) : 0;
+    if (n > 0) return n;
+    if (dev < 0 || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
+    cached[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
 // Opt a kernel in to `lds` bytes of dynamic LDS, once per device (`done` = the caller's static bitmap of devices;
 // one process may drive several GPUs from several threads: torch.nn.DataParallel).
+static_assert(MDGAT_MAX_DEVICES <= 64, "one bit per device in mdgat_lds_optin's bitmap");
 inline int mdgat_lds_optin(const void* kern, size_t lds, std::atomic<unsigned long long>& done, const char* what) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;       // (bit 63: never cached)
-    if (dev < 63 && ((done.load(std::memory_order_acquire) >> dev) & 1ull)) return MDGAT_OK;
+    const int dev = mdgat_current_device();       // (-1: not cached)
+    if (dev >= 0 && ((done.load(std::memory_order_acquire) >> dev) & 1ull)) return MDGAT_OK;
     if (int rc = mdgat_check_hip(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what)) return rc;
-    if (dev < 63) done.fetch_or(1ull << dev, std::memory_order_release);
+    if (dev >= 0) done.fetch_or(1ull << dev, std::memory_order_release);
     return MDGAT_OK;
 }
 

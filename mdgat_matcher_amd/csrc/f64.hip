@@ -843,18 +843,6 @@ __global__ void mfma64_probe_fill(double* p, int n) {
 }  // namespace
 
 // ================================================================================================ launchers
-// compute units of the current device (asked once per device)
-static int f64_cu_count() {
-    static std::atomic<int> cached[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-    int n = cached[dev].load(std::memory_order_relaxed);
-    if (n > 0) return n;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev].store(n, std::memory_order_relaxed);
-    return n;
-}
-
 int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return MDGAT_OK;
     static std::atomic<unsigned long long> done2{0}, done4{0}, done2f{0}, done4f{0}, done2d{0};
@@ -866,7 +854,7 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     static const int wn_env = [] { const char* e = getenv("MDGAT_F64_GEMM_WN"); return e ? atoi(e) : 0; }();      // (measurements)
     int wn = 2;
     if (a.N > 64) {
-        const int cus = f64_cu_count();
+        const int cus = mdgat_cu_count();
         const long tiles_m64 = (long)((a.M + G_BM - 1) / G_BM) * (a.batch > 1 ? a.batch : 1);
         const long tw = tiles_m64 * ((a.N + 127) / 128), tn = tiles_m64 * ((a.N + 63) / 64);
         const long rw = (tw + 3 * cus - 1) / (3 * cus), rn = (tn + 4 * cus - 1) / (4 * cus);
@@ -881,7 +869,7 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     // at K = 256, the one-pair forward 1.54 -> 1.48 ms; from eight pairs on the shallower chunks' third resident workgroup wins)
     static const bool deep_off = [] { const char* e = getenv("MDGAT_F64_GEMM_DEEP"); return e && atoi(e) == 0; }();      // (measurements)
     const bool deep = !deep_off && fast && wn == 2 && a.K % 64 == 0 && (a.K0 >= a.K || a.K0 % 64 == 0) &&
-                      (long)((a.M + G_BM - 1) / G_BM) * ((a.N + 63) / 64) * (a.batch > 1 ? a.batch : 1) <= (long)f64_cu_count();
+                      (long)((a.M + G_BM - 1) / G_BM) * ((a.N + 63) / 64) * (a.batch > 1 ? a.batch : 1) <= (long)mdgat_cu_count();
     const size_t lds = (size_t)(G_BM + bn) * ((deep ? 64 : G_KC) + 2) * sizeof(double);
     const dim3 grid((a.M + G_BM - 1) / G_BM, (a.N + bn - 1) / bn, a.batch > 1 ? a.batch : 1);
     auto go = [&](auto kern, std::atomic<unsigned long long>& done) -> int {
@@ -975,9 +963,9 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
         // forces it at every size (tests: ragged frames, one pair), (0) never
         const int form = f64_attention_form();
         const long solo_wgs = 8L * ((nk_max + 127) / 128) * ugroups;
-        const bool solo = qb_env == 0 && (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)f64_cu_count()));
+        const bool solo = qb_env == 0 && (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)mdgat_cu_count()));
         if (solo) return go(attention_f64_kernel<false, 2, false, false, true>, 128, false, 0, std::integral_constant<int, 6>());
-        const bool small = 8L * ((nk_max + 31) / 32) * ugroups < 2L * f64_cu_count();
+        const bool small = 8L * ((nk_max + 31) / 32) * ugroups < 2L * mdgat_cu_count();
         if (qb_env == 1 || (qb_env != 2 && small)) return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
         return go(attention_f64_kernel<false, 2, false>, 32, false, 0, std::integral_constant<int, 1>());
     }
@@ -1019,9 +1007,7 @@ extern "C" int mdgat_mfma_f64_probe(int reps, void* workspace, size_t workspace_
         return MDGAT_ERR_BAD_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0, num_cu = 0;
-    if (int rc = mdgat_check_hip(hipGetDevice(&dev), "hipGetDevice")) return rc;
-    if (int rc = mdgat_check_hip(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute")) return rc;
+    const int num_cu = mdgat_cu_count();
     double* src = static_cast<double*>(workspace);
     double* sink = src + 512 * 16;
     long long* ticks = reinterpret_cast<long long*>(sink + 512);

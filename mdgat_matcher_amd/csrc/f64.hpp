@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+class CoopGroup;      // coop_chain.hpp
+
 // C[M][N] = act(A W^T + bias) (+ R); the K input columns come from A0 (columns [0, K0)) and A1 (columns [K0, K)).  No alignment
 // beyond 8 bytes is assumed of any operand (the FPFH rows are 33 doubles).
 struct GemmF64Args {
@@ -61,7 +63,7 @@ struct LayerF64Args {
     unsigned* guard;           // as GemmF64Args::guard
     double* hid = nullptr;     // optional scratch [R][256]: with it, launches of few 16-row blocks may run the clustered kernel (layer_f64.hip)
 };
-int launch_layer_tail_f64(const LayerF64Args& a, hipStream_t s);
+int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group);      // on the group's stream (coop_chain.hpp)
 // both encoders, their sum and layer 0's q | k | v as one launch (mdgat.py:184-188, 152-155, 392-393, 227-232); weights in fragment order
 struct EncoderF64Args {
     const double *in4, *in33;                  // [R][4] x y z saliency, [R][33] FPFH (launch_assemble_f64)

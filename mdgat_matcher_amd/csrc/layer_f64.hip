@@ -339,7 +339,8 @@ __global__ __launch_bounds__(64 * LF_WAVES) void layer_tail_f64_kernel(LayerF64A
 // raises its flag, polls its partners' flags and fetches their channels with L1-bypassing loads.  Same operand roles, same order over
 // k, every channel block by exactly one wave: BIT-IDENTICAL to the kernel above (and to the three-launch form).
 // Flags: 64-bit words in a buffer the library owns per device, set to the launch's number (CoopChain::epoch) - nothing to clear per
-// launch; launches of waiting kernels are chained one at a time per device (coop_chain.hpp), graph capture takes the kernel above.
+// launch; the launcher takes the forward's CoopGroup, which admits launches of waiting kernels one at a time per device
+// (coop_chain.hpp); a group that is not chained (graph capture) takes the kernel above.
 constexpr int LC_RANKS = 4;
 constexpr int LC_WORDS = 4;             // per rank: XCC id word | hidden-layer flag | x flag | pad
 
@@ -570,46 +571,32 @@ extern "C" int mdgat_set_f64_layer_fusion(int mode) {
     return prev < 0 ? fusion_default() : prev;
 }
 
-static int lf_cu_count() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    static std::atomic<int> cached[16];
-    if (dev >= 0 && dev < 16 && (n = cached[dev].load(std::memory_order_relaxed)) > 0) return n;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    if (dev >= 0 && dev < 16) cached[dev].store(n, std::memory_order_relaxed);
-    return n;
-}
-
-int launch_layer_tail_f64(const LayerF64Args& a, hipStream_t s) {
+int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group) {
     if (a.R <= 0) return MDGAT_OK;
+    const hipStream_t s = group.stream();
     // Rows per workgroup.  32 (two workgroups per CU, four waves per SIMD) from a round of the device on; 16 below - one pair of 512
     // keypoints is 64 workgroups instead of 32, and a workgroup's chain of products half as long (mdgat_set_f64_layer_fusion(16 | 32 |
     // 64) forces one).
-    int tm = (long)((a.R + 31) / 32) >= 2L * lf_cu_count() ? 32 : 16;
+    int tm = (long)((a.R + 31) / 32) >= 2L * mdgat_cu_count() ? 32 : 16;
     if (fusion_mode() >= 16) tm = fusion_mode();
     // Launches of at most a quarter of the CUs in 16-row blocks (one pair of 512 keypoints: 64): four workgroups per block
     // (layer_tail_f64_cluster_kernel; bit-identical).  Not under graph capture (its flags count launches), not without the scratch,
     // not when a tile height is forced or mdgat_set_f64_layer_fusion(2) asks for the one-workgroup-per-block kernel.
     const int nblk = (a.R + 15) / 16;
-    if (fusion_mode() == 1 && a.hid && LC_RANKS * nblk <= lf_cu_count() && !coop_stream_capturing(s)) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        CoopChain& ch = coop_chain_of(dev);
-        std::lock_guard<std::recursive_mutex> lock(ch.m);
-        constexpr size_t flag_bytes = (size_t)256 * LC_RANKS * LC_WORDS * sizeof(unsigned long long);      // up to 256 clusters
+    constexpr int max_clusters = 256;
+    if (fusion_mode() == 1 && a.hid && LC_RANKS * nblk <= mdgat_cu_count() && nblk <= max_clusters && group.chained()) {
+        CoopChain& ch = group.chain();
+        constexpr size_t flag_bytes = (size_t)max_clusters * LC_RANKS * LC_WORDS * sizeof(unsigned long long);
         if (!ch.cluster_flags) {
             void* p = nullptr;
             if (int rc = mdgat_check_hip(hipMalloc(&p, flag_bytes), "layer_tail_f64 cluster flags")) return rc;
             if (int rc = mdgat_check_hip(hipMemset(p, 0, flag_bytes), "layer_tail_f64 cluster flags (clear)")) { (void)hipFree(p); return rc; }
             ch.cluster_flags = static_cast<unsigned long long*>(p);
         }
-        if (nblk <= 256) {
-            if (int rc = mdgat_check_hip(coop_chain_wait(ch, s), "layer_tail_f64: wait for the previous waiting launch")) return rc;
-            const size_t lds = (size_t)16 * LF_LD * sizeof(double);
-            hipLaunchKernelGGL(layer_tail_f64_cluster_kernel, dim3((unsigned)(((nblk + 7) / 8) * 32)), dim3(64 * LF_WAVES), lds, s, a, ch.cluster_flags, ++ch.epoch);
-            if (int rc = mdgat_check_hip(hipGetLastError(), "layer_tail_f64 (clustered) launch")) return rc;
-            return mdgat_check_hip(coop_chain_record(ch, s), "layer_tail_f64: record");
-        }
+        if (int rc = group.admit()) return rc;
+        const size_t lds = (size_t)16 * LF_LD * sizeof(double);
+        hipLaunchKernelGGL(layer_tail_f64_cluster_kernel, dim3((unsigned)(((nblk + 7) / 8) * 32)), dim3(64 * LF_WAVES), lds, s, a, ch.cluster_flags, ++ch.epoch);
+        return mdgat_check_hip(hipGetLastError(), "layer_tail_f64 (clustered) launch");
     }
     const size_t lds = (size_t)tm * LF_LD * sizeof(double);
     const dim3 grid((a.R + tm - 1) / tm);
@@ -627,7 +614,7 @@ int launch_layer_tail_f64(const LayerF64Args& a, hipStream_t s) {
 
 int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s) {
     if (a.R <= 0) return MDGAT_OK;
-    int tm = (long)((a.R + 31) / 32) >= 2L * lf_cu_count() ? 32 : 16;
+    int tm = (long)((a.R + 31) / 32) >= 2L * mdgat_cu_count() ? 32 : 16;
     if (fusion_mode() == 16 || fusion_mode() == 32) tm = fusion_mode();
     const size_t lds = (size_t)tm * LF_LD * sizeof(double);
     const dim3 grid((a.R + tm - 1) / tm);

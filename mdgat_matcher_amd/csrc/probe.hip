@@ -57,9 +57,7 @@ extern "C" int mdgat_mfma_probe(int reps, void* workspace, size_t workspace_byte
         return MDGAT_ERR_BAD_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int dev = 0, num_cu = 0;
-    if (int rc = mdgat_check_hip(hipGetDevice(&dev), "hipGetDevice")) return rc;
-    if (int rc = mdgat_check_hip(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev), "CU count")) return rc;
+    const int num_cu = mdgat_cu_count();
     _Float16* src = static_cast<_Float16*>(workspace);
     float* sink = reinterpret_cast<float*>(src + halves);
     long long* ticks = reinterpret_cast<long long*>(reinterpret_cast<char*>(sink) + 512 * 4 + ((256 - (512 * 4) % 256) % 256));

@@ -1303,9 +1303,7 @@ int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_s
     if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
     const size_t need = sinkhorn_cluster_workspace_bytes(B, N, M);
     if (need && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0) {
-        int dev = 0, num_cu = 0;
-        if (int rc = mdgat_check_hip(hipGetDevice(&dev), "hipGetDevice")) return rc;
-        if (int rc = mdgat_check_hip(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev), "CU count")) return rc;
+        const int num_cu = mdgat_cu_count();
         const int rpw = sk_rpw(B, N, M);
         if (rpw == 4) return launch_scaling<4>(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
         if (rpw == 8) return launch_scaling<8>(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);

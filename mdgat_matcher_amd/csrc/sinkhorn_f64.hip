@@ -682,8 +682,9 @@ static int launch_sinkhorn_f64_wide(int B, int N, int M, const double* scores, d
 
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
                         float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
-                        hipStream_t s, const double* alpha_dev) {
+                        CoopGroup& group, const double* alpha_dev) {
     if (B <= 0) return MDGAT_OK;
+    const hipStream_t s = group.stream();
     if (!sinkhorn_f64_supported(N, M)) { mdgat_set_error("fp64 Sinkhorn: %d x %d keypoints > %d supported", N, M, 128 * W64_NC2MAX - 1); return MDGAT_ERR_UNSUPPORTED; }
     if (!workspace || workspace_bytes < sinkhorn_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
         mdgat_set_error("fp64 Sinkhorn: workspace too small or not 256-byte aligned");
@@ -708,19 +709,14 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     int* sidx = reinterpret_cast<int*>(w);
     a.cslab_idx = cbest_idx ? sidx : nullptr; a.cslab_val = cbest_idx ? sval : nullptr;
     a.error_word = error_word;
-    // ONE launch of this kernel at a time per device: a launch waits (on its own stream) for the previous one, whatever stream that was on.
-    // The workgroups of a pair wait for each other, and a workgroup that waits holds its CU.  Within one launch that is safe - an XCD gets
-    // its pairs in order, each as a contiguous run of workgroups, so at most one pair per XCD is partly resident and the other slots hold
-    // a complete pair that finishes - and other kernels that occupy CUs are finite.  But three launches in flight can each hold a partly
-    // resident pair on an XCD (3 x 15 of its 32 slots) with no slot left for any of them: measured - four streams, launches of 20 and
-    // 40 pairs: every spin ran into its bound and the results were garbage.  (Streams being captured into a graph are left alone.)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    CoopChain& sr = coop_chain_of(dev);                 // (shared with the clustered fp64 layer tail: coop_chain.hpp)
-    std::lock_guard<std::recursive_mutex> lock(sr.m);
-    const bool chain = !coop_stream_capturing(s);
-    if (chain)
-        if (int rc = mdgat_check_hip(coop_chain_wait(sr, s), "fp64 Sinkhorn: wait for the previous launch")) return rc;
+    // ONE launch of this kernel at a time per device: the caller's CoopGroup admits it after the previous waiting launch, whatever stream
+    // that was on (coop_chain.hpp; shared with the clustered fp64 layer tail).  The workgroups of a pair wait for each other, and a
+    // workgroup that waits holds its CU.  Within one launch that is safe - an XCD gets its pairs in order, each as a contiguous run of
+    // workgroups, so at most one pair per XCD is partly resident and the other slots hold a complete pair that finishes - and other
+    // kernels that occupy CUs are finite.  But three launches in flight can each hold a partly resident pair on an XCD (3 x 15 of its 32
+    // slots) with no slot left for any of them: measured - four streams, launches of 20 and 40 pairs: every spin ran into its bound and
+    // the results were garbage.  (A group on a stream being captured into a graph admits it unchained.)
+    if (int rc = group.admit()) return rc;
     if (int rc = mdgat_check_hip(hipMemsetAsync(a.flags, 0, (size_t)B * 3 * G * sizeof(unsigned), s), "memset(fp64 Sinkhorn flags)")) return rc;
     const int groups = (B + 7) / 8;
     const size_t lds = s64_lds_bytes(waves);
@@ -728,8 +724,6 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8>), lds, optin8, "sinkhorn_f64 LDS")) return rc;
     hipLaunchKernelGGL(sinkhorn_f64_kernel<8>, dim3(groups * 8 * G), dim3(512), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
-    if (chain)
-        if (int rc = mdgat_check_hip(coop_chain_record(sr, s), "fp64 Sinkhorn: record")) return rc;
     if (cbest_idx) {
         const size_t total = (size_t)B * M;
         hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, G, M,
@@ -751,8 +745,9 @@ extern "C" int mdgat_sinkhorn_f64(int B, int N, int M, const double* scores, dou
                                   size_t workspace_bytes, void* stream) {
     if (!scores || !Z) { mdgat_set_error("mdgat_sinkhorn_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("mdgat_sinkhorn_f64: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    return launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, nullptr,
-                               static_cast<hipStream_t>(stream));
+    CoopGroup group;
+    if (int rc = group.open(mdgat_current_device(), static_cast<hipStream_t>(stream))) return rc;
+    return launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, nullptr, group);
 }
 
 extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double bin_score, int iters, int mode, float match_threshold,
@@ -771,9 +766,13 @@ extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* sco
     int* ci = reinterpret_cast<int*>(w); w += s64_align((size_t)B * M * 4);
     float* cv = reinterpret_cast<float*>(w);
     const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
-    if (int rc = launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, nullptr, Z_or_null, inner, ri, rv, ci, cv, workspace, sinkhorn_f64_workspace_bytes(B, N, M),
-                                     nullptr, s))
-        return rc;
+    {
+        CoopGroup group;
+        if (int rc = group.open(mdgat_current_device(), s)) return rc;
+        if (int rc = launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, nullptr, Z_or_null, inner, ri, rv, ci, cv, workspace,
+                                         sinkhorn_f64_workspace_bytes(B, N, M), nullptr, group))
+            return rc;
+    }
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
     return launch_extract_from_bests(B, N, M, &ex, ri, rv, ci, cv, s);
 }

@@ -71,6 +71,13 @@ def test_create_rejects_bad_config_before_touching_a_device():
         h = C.c_void_p()
         assert lib.mdgat_create(C.byref(c), 0, C.byref(h)) == _lib.ERR_BAD_ARG, field
         assert not h.value and lib.mdgat_last_error()
+    # device indices beyond the library's per-device tables (MDGAT_MAX_DEVICES = 64) would alias another device's state
+    c = _lib.MdgatConfig()
+    c.L = 1
+    for device in (-1, 64, 1 << 20):
+        h = C.c_void_p()
+        assert lib.mdgat_create(C.byref(c), device, C.byref(h)) == _lib.ERR_BAD_ARG, device
+        assert not h.value and b'device' in lib.mdgat_last_error()
 
 
 def test_no_cpu_fallback():
