@@ -256,8 +256,8 @@ int mdgat_set_layer_split_tiles(int tiles);
  * launch per layer with the hidden activation kept on chip (csrc/layer_f64.hip) - launches of at most a quarter of the compute
  * units in 16-keypoint blocks (one pair per call) with FOUR workgroups per block that split the output channels and exchange the
  * hidden layer and the new x through L2; 2: the same, one workgroup per block at every launch size; 0: three launches of the fp64
- * product kernel (csrc/f64.hip); 16 / 32 / 64: one launch with that many keypoints per workgroup (default: by launch size);
- * mode < 0: back to the default.  Process-wide; the results are bit-identical either way.  Returns the previous value. */
+ * product kernel (csrc/f64.hip); 16 / 32: one launch with that many keypoints per workgroup (default: by launch size); any other
+ * mode > 0: 1; mode < 0: back to the default.  Process-wide; the results are bit-identical either way.  Returns the previous value. */
 int mdgat_set_f64_layer_fusion(int mode);
 
 /* MDGAT_ARITH_FP64: how full attention (models/mdgat.py:190-194) is launched.  -1 (default; MDGAT_F64_ATTENTION_FORM in the

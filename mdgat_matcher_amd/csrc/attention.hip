@@ -451,11 +451,10 @@ __device__ __forceinline__ void topk_break_ties(f32x16 (&S)[NBLK], float thr, in
 // NBLK  = 32-key blocks per chunk (16 NBLK row registers); full attention walks the keys chunk by chunk
 //         with an online softmax (running max / sum, the output rescaled between chunks), dynamic
 //         attention needs the whole row at once and therefore a single chunk.
-// EXACT = the key count is a multiple of 32 NBLK: no per-block conditions, one basic block per chunk.
 // LARGE = more than 512 keys (full attention only): LDS holds a window of 512 keys that is re-staged for
 //         every query pass; the online softmax carries across windows.
 // Threads: 512 (two waves per SIMD, <= 256 registers) for NBLK <= 8, else 256 (one wave per SIMD).
-template <bool TOPK, int NBLK, bool EXACT, bool LARGE, bool TAP = false>
+template <bool TOPK, int NBLK, bool LARGE, bool TAP = false>
 __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void attention_kernel(AttnArgs a) {
     static_assert(TOPK || !TAP, "the selection tap belongs to the dynamic layers");
     static_assert(!(TOPK && LARGE), "dynamic attention needs the whole row in one chunk");
@@ -568,7 +567,7 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
                 f32x16 S[NBLK];
 #pragma unroll
                 for (int jb = 0; jb < NBLK; ++jb) {
-                    if (EXACT || c0 + jb < wnb) {
+                    if (c0 + jb < wnb) {
                         const _Float16* kp = Ks + ((c0 + jb) * 32 + krow) * KROWH + 8 * hi;
                         const f16x8 kh0 = *reinterpret_cast<const f16x8*>(kp);
                         const f16x8 kh1 = *reinterpret_cast<const f16x8*>(kp + 16);
@@ -587,7 +586,7 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
                         acx = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl1, qh[1], acx, 0, 0, 0);
 #pragma unroll
                         for (int r = 0; r < 16; ++r) acc[r] += acx[r];
-                        if (!EXACT && last_partial && wb0 + c0 + jb == nblk - 1) {   // wave-uniform
+                        if (last_partial && wb0 + c0 + jb == nblk - 1) {   // wave-uniform
 #pragma unroll
                             for (int r = 0; r < 16; ++r)
                                 if (16 * (r >> 3) + (r & 7) >= last_lim) acc[r] = NEG_INF;
@@ -611,7 +610,7 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
                 float thr = NEG_INF;
                 if (TOPK) {
                     WaveComm comm;
-                    thr = topk_threshold<NBLK, EXACT>(S, m, a.topk, nk, a.zq, comm);
+                    thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, a.zq, comm);
                     if (TAP) {      // the TAP build counts first, so that the selection it records is final
                         int c = 0;
 #pragma unroll
@@ -660,7 +659,7 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
                 f32x2 kept = {0.f, 0.f};
 #pragma unroll
                 for (int jb = 0; jb < NBLK; ++jb) {
-                    if (EXACT || c0 + jb < wnb) {
+                    if (c0 + jb < wnb) {
 #pragma unroll
                         for (int t = 0; t < 2; ++t) {
                             float p[8], s8[8];
@@ -1404,7 +1403,7 @@ int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv,
         if (int rc = mdgat_check_hip(hipMemsetAsync(sel, dyn ? 0 : 0xff, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
         if (dyn) a.sel = sel;
     }
-    if (!dyn && attention_stream_supported(N, M) && !getenv("MDGAT_ATTN_NOSTREAM")) return launch_attention_stream(B, N, M, cross, qkv, msg, s, mode);
+    if (!dyn && attention_stream_supported(N, M)) return launch_attention_stream(B, N, M, cross, qkv, msg, s, mode);
     // one workgroup per (pair, frame, head) loops over its query tiles; split the tiles over more
     // workgroups only when there are too few (pair, frame, head) units to fill the chip twice
     auto go = [&](auto kern, int threads) {
@@ -1417,7 +1416,6 @@ int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv,
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kern, dim3(qsplit, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
     };
-    const bool mult32 = (N % 32 == 0) && (M % 32 == 0);
     // exactly 512 (or 256) keys in both frames: one wave = 16 queries, the row in four lanes
     auto launch16 = [&](auto nkc) {
         constexpr int NKEY = decltype(nkc)::value;
@@ -1442,22 +1440,19 @@ int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv,
         // the whole row in one chunk
         if (N == 256 && M == 256) launch16(std::integral_constant<int, 256>{});
         else if (a.sel && !(N == 512 && M == 512) && nblk <= 16) {
-            if (nblk <= 4) go(attention_kernel<true, 4, false, false, true>, 512);
-            else if (nblk <= 8) go(attention_kernel<true, 8, false, false, true>, 512);
-            else go(attention_kernel<true, 16, false, false, true>, 256);
-        } else if (nblk <= 4) go(attention_kernel<true, 4, false, false>, 512);
-        else if (nblk <= 8) go(attention_kernel<true, 8, false, false>, 512);
+            if (nblk <= 4) go(attention_kernel<true, 4, false, true>, 512);
+            else if (nblk <= 8) go(attention_kernel<true, 8, false, true>, 512);
+            else go(attention_kernel<true, 16, false, true>, 256);
+        } else if (nblk <= 4) go(attention_kernel<true, 4, false>, 512);
+        else if (nblk <= 8) go(attention_kernel<true, 8, false>, 512);
         else if (N == 512 && M == 512) launch16(std::integral_constant<int, 512>{});
-        else if (nblk <= 16) go(attention_kernel<true, 16, false, false>, 256);
+        else if (nblk <= 16) go(attention_kernel<true, 16, false>, 256);
         else return launch_attention_topk_wide(a, B, nk_max, s);
     } else {
         // chunks of 8 blocks (256 keys), two waves per SIMD
-        if (nblk <= 4) go(attention_kernel<false, 4, false, false>, 512);
-        else if (nblk > 16) {
-            if (mult32 && N % 256 == 0 && M % 256 == 0) go(attention_kernel<false, 8, true, true>, 512);
-            else go(attention_kernel<false, 8, false, true>, 512);
-        } else if (mult32 && N % 256 == 0 && M % 256 == 0) go(attention_kernel<false, 8, true, false>, 512);
-        else go(attention_kernel<false, 8, false, false>, 512);
+        if (nblk <= 4) go(attention_kernel<false, 4, false>, 512);
+        else if (nblk > 16) go(attention_kernel<false, 8, true>, 512);
+        else go(attention_kernel<false, 8, false>, 512);
     }
     return mdgat_check_hip(hipGetLastError(), "attention launch");
 }

@@ -851,7 +851,6 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     // CUs, not by its inner loop: one pair of 512 keypoints is 16 row tiles - 48 wide workgroups on 256 CUs for the q|k|v product,
     // 96 narrow ones, 20 -> 17 us; 8192 rows x 128 outputs 31 -> 21 us (profiles/NOTES_r5.md section 9).  The narrow tile is taken
     // when its rounds of resident workgroups, priced at 0.55 of a wide round, come out below the wide tile's.
-    static const int wn_env = [] { const char* e = getenv("MDGAT_F64_GEMM_WN"); return e ? atoi(e) : 0; }();      // (measurements)
     int wn = 2;
     if (a.N > 64) {
         const int cus = mdgat_cu_count();
@@ -859,7 +858,6 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
         const long tw = tiles_m64 * ((a.N + 127) / 128), tn = tiles_m64 * ((a.N + 63) / 64);
         const long rw = (tw + 3 * cus - 1) / (3 * cus), rn = (tn + 4 * cus - 1) / (4 * cus);
         wn = (tw <= 6L * cus && rn * 55 < rw * 100) ? 2 : 4;
-        if (wn_env == 2 || wn_env == 4) wn = wn_env;
     }
     const int bn = 32 * wn;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
@@ -867,8 +865,7 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
                       (a.K0 >= a.K || (a.lda1 % 2 == 0 && al16(a.A1))) && (a.batch <= 1 || (a.sA % 2 == 0 && a.sW % 2 == 0));
     // (chunks of 64 for whole-tile launches of at most one 64 x 64 tile per CU: one or two pairs of 512 keypoints - 19.0 -> 17.8 us
     // at K = 256, the one-pair forward 1.54 -> 1.48 ms; from eight pairs on the shallower chunks' third resident workgroup wins)
-    static const bool deep_off = [] { const char* e = getenv("MDGAT_F64_GEMM_DEEP"); return e && atoi(e) == 0; }();      // (measurements)
-    const bool deep = !deep_off && fast && wn == 2 && a.K % 64 == 0 && (a.K0 >= a.K || a.K0 % 64 == 0) &&
+    const bool deep = fast && wn == 2 && a.K % 64 == 0 && (a.K0 >= a.K || a.K0 % 64 == 0) &&
                       (long)((a.M + G_BM - 1) / G_BM) * ((a.N + 63) / 64) * (a.batch > 1 ? a.batch : 1) <= (long)mdgat_cu_count();
     const size_t lds = (size_t)(G_BM + bn) * ((deep ? 64 : G_KC) + 2) * sizeof(double);
     const dim3 grid((a.M + G_BM - 1) / G_BM, (a.N + bn - 1) / bn, a.batch > 1 ? a.batch : 1);
@@ -956,17 +953,15 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
     // fp64 logits stay in registers between the passes (KEEP), beyond that the rounding images of 32 rows would not fit the LDS
     if (!dyn) {
         // (fewer than two workgroups per CU with 32 queries each - a pair or two of 512 keypoints: 16 queries per workgroup, the
-        // same arithmetic per row; MDGAT_F64_ATT_QB=1|2 forces one for measurements.  64 queries per workgroup - 234 registers, two
-        // waves per SIMD - lose: 236 -> 289 us at batch 32)
-        static const int qb_env = [] { const char* e = getenv("MDGAT_F64_ATT_QB"); return e ? atoi(e) : 0; }();
+        // same arithmetic per row.  64 queries per workgroup - 234 registers, two waves per SIMD - lose: 236 -> 289 us at batch 32)
         // one wave per 32 queries (SOLO) from F64_SOLO_MIN_WG_PER_CU workgroups of four such waves per CU on; mdgat_set_f64_attention_form(1)
         // forces it at every size (tests: ragged frames, one pair), (0) never
         const int form = f64_attention_form();
         const long solo_wgs = 8L * ((nk_max + 127) / 128) * ugroups;
-        const bool solo = qb_env == 0 && (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)mdgat_cu_count()));
+        const bool solo = form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)mdgat_cu_count());
         if (solo) return go(attention_f64_kernel<false, 2, false, false, true>, 128, false, 0, std::integral_constant<int, 6>());
         const bool small = 8L * ((nk_max + 31) / 32) * ugroups < 2L * mdgat_cu_count();
-        if (qb_env == 1 || (qb_env != 2 && small)) return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
+        if (small) return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
         return go(attention_f64_kernel<false, 2, false>, 32, false, 0, std::integral_constant<int, 1>());
     }
     if (nk_max <= 512) return a.sel ? go(attention_f64_kernel<true, 1, true, true>, 16, true, 512, std::integral_constant<int, 2>())

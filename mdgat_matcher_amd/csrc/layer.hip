@@ -676,8 +676,7 @@ int launch_layer(const LayerLaunch& p, hipStream_t s) {
     // whose eight waves share the output channels; bit-identical results (mdgat_set_layer_split_tiles: tuning / A-B hook)
     if ((p.R + 127) / 128 <= g_split_tiles.load(std::memory_order_relaxed)) return launch_layer_split(a, p.do_mlp, p.mode3, s);
     // small launches (fewer 128-keypoint tiles than half the CUs of the part): 64-keypoint workgroups, one wave per SIMD
-    static const int small_tiles = [] { const char* e = getenv("MDGAT_LAYER_SMALL_TILES"); return e ? atoi(e) : 128; }();
-    if ((p.R + 127) / 128 <= small_tiles) {
+    if ((p.R + 127) / 128 <= MDGAT_LAYER_TILE64_TILES) {
         if (p.do_mlp) return p.mode3 != 1 ? launch_layer_t<1, 2, 0, 4>(a, s) : launch_layer_t<1, 1, 0, 4>(a, s);
         return p.mode3 != 1 ? launch_layer_t<0, 2, 0, 4>(a, s) : launch_layer_t<0, 1, 0, 4>(a, s);
     }

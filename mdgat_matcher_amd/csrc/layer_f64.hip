@@ -226,10 +226,9 @@ __global__ __launch_bounds__(64 * LF_WAVES) void layer_tail_f64_kernel(LayerF64A
     const int row0 = blockIdx.x * TM;
     bool bad = false;
     constexpr bool EARLY = NRB == 1;        // the first weights of a product requested before the barrier in front of it (registers: one-pair tiles only)
-    constexpr int PF3 = NRB >= 4 ? 2 : 4;
     // (deeper weight prefetch at one row block per workgroup - 8 / 16 pairs of k-steps for mlp.0 / mlp.3 - changes nothing: B = 1, 2, 8
     // within 0.5 % either way; the chain of 576 matrix instructions per SIMD is 15 us of its 26)
-    constexpr int PF1 = 4, PF2 = 4;
+    constexpr int PF1 = 4, PF2 = 4, PF3 = 4;
     f64x2 wb1[PF1][2], wb2[PF2][1], wb3[PF3][3];
     if (EARLY) lf_prefetch<2, 32, PF1>(a.w1f + (size_t)(2 * wave) * 32 * 128, lane, wb1);
 
@@ -556,17 +555,17 @@ int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s) {
 }
 
 // 0: three launches per layer tail (gemm_f64_kernel); 1: the fused kernels, form and rows per workgroup chosen by the launch (default);
-// 2: the same without the clustered form of small launches; 16 / 32 / 64: the one-workgroup-per-block kernel with that many rows per
-// workgroup (tests, measurements).  MDGAT_F64_LAYER_FUSION in the environment.
+// 2: the same without the clustered form of small launches; 16 / 32: the one-workgroup-per-block kernel with that many rows per
+// workgroup (tests); other positive values: 1.  MDGAT_F64_LAYER_FUSION in the environment.
 static std::atomic<int> g_fusion{-1};
 static int fusion_default() {
-    static const int v = [] { const char* e = getenv("MDGAT_F64_LAYER_FUSION"); const int m = e ? atoi(e) : 1; return (m == 16 || m == 32 || m == 64 || m == 2) ? m : (m != 0); }();
+    static const int v = [] { const char* e = getenv("MDGAT_F64_LAYER_FUSION"); const int m = e ? atoi(e) : 1; return (m == 16 || m == 32 || m == 2) ? m : (m != 0); }();
     return v;
 }
 static int fusion_mode() { const int v = g_fusion.load(std::memory_order_relaxed); return v < 0 ? fusion_default() : v; }
 bool layer_f64_fused() { return fusion_mode() != 0; }
 extern "C" int mdgat_set_f64_layer_fusion(int mode) {
-    const int m = mode < 0 ? -1 : (mode == 16 || mode == 32 || mode == 64 || mode == 2) ? mode : (mode != 0);
+    const int m = mode < 0 ? -1 : (mode == 16 || mode == 32 || mode == 2) ? mode : (mode != 0);
     const int prev = g_fusion.exchange(m, std::memory_order_relaxed);
     return prev < 0 ? fusion_default() : prev;
 }
@@ -575,8 +574,8 @@ int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group) {
     if (a.R <= 0) return MDGAT_OK;
     const hipStream_t s = group.stream();
     // Rows per workgroup.  32 (two workgroups per CU, four waves per SIMD) from a round of the device on; 16 below - one pair of 512
-    // keypoints is 64 workgroups instead of 32, and a workgroup's chain of products half as long (mdgat_set_f64_layer_fusion(16 | 32 |
-    // 64) forces one).
+    // keypoints is 64 workgroups instead of 32, and a workgroup's chain of products half as long (mdgat_set_f64_layer_fusion(16 | 32)
+    // forces one).
     int tm = (long)((a.R + 31) / 32) >= 2L * mdgat_cu_count() ? 32 : 16;
     if (fusion_mode() >= 16) tm = fusion_mode();
     // Launches of at most a quarter of the CUs in 16-row blocks (one pair of 512 keypoints: 64): four workgroups per block
@@ -608,8 +607,7 @@ int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group) {
         return mdgat_check_hip(hipGetLastError(), "layer_tail_f64 launch");
     };
     if (tm == 16) return go(layer_tail_f64_kernel<1>, std::integral_constant<int, 1>());
-    if (tm == 32) return go(layer_tail_f64_kernel<2>, std::integral_constant<int, 2>());
-    return go(layer_tail_f64_kernel<4>, std::integral_constant<int, 4>());
+    return go(layer_tail_f64_kernel<2>, std::integral_constant<int, 2>());
 }
 
 int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s) {

@@ -29,4 +29,6 @@ struct LayerArgs {
 
 // layer_split.hip: the same layer for launches of a few tiles (one pair, small batches)
 constexpr int MDGAT_LAYER_SPLIT_TILES_DEFAULT = 64;   // measured (tools/split_threshold.sh, N = M = 512): wins up to 64 tiles (B = 8), ties at 96-128, loses beyond
+// layer.hip: launches of at most this many 128-keypoint tiles (fewer than half the CUs of the part) use 64-keypoint workgroups
+constexpr int MDGAT_LAYER_TILE64_TILES = 128;
 int launch_layer_split(const LayerArgs& a, int do_mlp, int mode3, hipStream_t s);

@@ -256,26 +256,6 @@ __device__ __forceinline__ float wave_sum16(float (&acc)[16], int lane) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(16 * lane, __builtin_bit_cast(int, w)));
 }
 
-// Eight wave-wide sums at once (the same scheme one stage shorter): returns, in lane r (< 8), the wave total of row r.
-__device__ __forceinline__ float wave_sum8(float (&acc)[8], int lane) {
-    float s[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { float x = acc[r], y = acc[r + 4]; swap_halves32(x, y); s[r] = x + y; }   // lanes < 32: row r, others row r + 4
-    float t[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { float x = s[r], y = s[r + 2]; swap_rows16(x, y); t[r] = x + y; }      // 16-lane row q: row r + 2 q
-    const bool b3 = (lane & 8) != 0;
-    const float keep = b3 ? t[1] : t[0], give = b3 ? t[0] : t[1];
-    float w = keep + dpp_bank_move<0x128, 0xf>(0.f, give);             // row_ror:8: lanes 16 q + 0..7 row 2 q, lanes 16 q + 8..15 row 2 q + 1
-    float o = dpp_bank_move<0x104, 0x5>(0.f, w);                       // the value of lane ^ 4
-    o = dpp_bank_move<0x114, 0xa>(o, w);
-    w += o;
-    w += dpp_bank_move<0xb1, 0xf>(0.f, w);                             // quad_perm [1, 0, 3, 2]
-    w += dpp_bank_move<0x4e, 0xf>(0.f, w);                             // quad_perm [2, 3, 0, 1]
-    // lanes 8 q .. 8 q + 7 hold the total of row q: bring it to lane q
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(32 * lane, __builtin_bit_cast(int, w)));
-}
-
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 // cache policy of the polling loads: agent scope (served by the L2, never by a CU's L1).  "nt" measures the same and had
 // been used until round 3; "sc0" alone hits stale L1 lines (partners time out).
@@ -433,8 +413,9 @@ __device__ __forceinline__ void poll_partners(gu64* base, size_t stride, int n, 
 // thread that finalises column t keeps its own copies.  Row sums cross the GC column slabs, column sums the GR row slabs
 // (TWO_D = more than one column slab: N, M up to 2048).
 // GMAX = compile-time bound on the row slabs (4: N <= 512, 16: N <= 2048)
-template <int RPW, bool TWO_D, int GMAX>
+template <bool TWO_D, int GMAX>
 __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArgs a) {
+    constexpr int RPW = 16;               // rows per wave
     __shared__ __attribute__((aligned(16))) float lds[SKS_LDS_FLOATS];
     float* bvec = lds;                    // [512] column scalings of the slab, [512] = dustbin column
     float* colp = lds + 520;              // [8 waves][512] per-wave column sums
@@ -630,7 +611,7 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
             // ---- row update (mdgat.py:283): a_i = mu_i / sum_j K_ij b_j ----
             SK_TP(0);
             float psum = 0.f;
-            if (RPW == 16) {
+            {
                 float racc[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -642,26 +623,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                 SK_TP(1);
                 psum = wave_sum16(racc, lane);                 // lane r: row r (lanes >= 16 are not used)
                 psum = lane < 16 ? psum : 0.f;
-            } else if (RPW == 8) {
-                float racc[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    float acc = K[r][0] * b[0];
-#pragma unroll
-                    for (int c = 1; c < 8; ++c) acc = fmaf(K[r][c], b[c], acc);
-                    racc[r] = acc;
-                }
-                psum = wave_sum8(racc, lane);                  // lane r: row r
-                psum = lane < 8 ? psum : 0.f;
-            } else {
-#pragma unroll
-                for (int r = 0; r < RPW; ++r) {
-                    float acc = K[r][0] * b[0];
-#pragma unroll
-                    for (int c = 1; c < 8; ++c) acc = fmaf(K[r][c], b[c], acc);
-                    const float tot = wave_sum_dpp(acc);          // wave-uniform
-                    psum = (lane == r) ? tot : psum;
-                }
             }
             {
                 float pd = kr[0] * b[0];
@@ -1151,47 +1112,25 @@ int launch_sk(const SkArgs& a, int B, hipStream_t s) {
 
 }  // namespace
 
-// rows per wave for launches of few pairs (see sk_rpw); 16 = the throughput shape everywhere until measured otherwise
-static int mdgat_sk_small_rpw(int B, int N, int M) { (void)B; (void)N; (void)M; return 16; }
-// tiling of a pair: GR row slabs of 8 RPW rows (RPW rows per wave: 16) x GC column slabs of 512 columns, one workgroup each
-static void sk_tiling(int N, int M, int& GR, int& GC, int rpw = 16) { GR = (N + 8 * rpw - 1) / (8 * rpw); GC = (M + 511) / 512; }
-// Rows per wave of a launch.  16 (128-row slabs) is the throughput shape.  Few pairs leave most of the part idle - one pair of
-// 512 keypoints is 4 workgroups on 256 CUs - and thinner slabs (RPW = 8, 4: 8 / 16 workgroups per pair, an iteration's
-// issue-bound row and column passes 2x / 4x shorter, 7 / 15 partners to poll instead of 3) trade that idleness for exchange:
-// MDGAT_SK_RPW (measurements) forces a value where the shape allows it (one column slab, at most 16 row slabs).
-static int sk_rpw(int B, int N, int M) {
-    static const int forced = [] { const char* e = getenv("MDGAT_SK_RPW"); return e ? atoi(e) : 0; }();
-    int rpw = 16;
-    if (forced == 4 || forced == 8) rpw = forced;
-    else if (forced == 0) rpw = mdgat_sk_small_rpw(B, N, M);
-    if (rpw != 16 && (M > 512 || (N + 8 * rpw - 1) / (8 * rpw) > 16)) rpw = 16;
-    return rpw;
-}
-// (sizes are taken for the thinnest slabs a shape may run with: the layout inside is the launch's own)
-static int sk_max_groups(int N, int M, int rpw = 16) {      // pairs in flight on a 256-CU part (upper bound used for sizing)
+// tiling of a pair: GR row slabs of 128 rows (16 rows per wave) x GC column slabs of 512 columns, one workgroup each
+static void sk_tiling(int N, int M, int& GR, int& GC) { GR = (N + 127) / 128; GC = (M + 511) / 512; }
+static int sk_max_groups(int N, int M) {      // pairs in flight on a 256-CU part (upper bound used for sizing)
     int GR, GC;
-    sk_tiling(N, M, GR, GC, rpw);
+    sk_tiling(N, M, GR, GC);
     int g = 256 / (GR * GC);
     return g > 64 ? 64 : (g < 1 ? 1 : g);
 }
-static size_t slots_bytes_rpw(int N, int M, int rpw) {
-    int GR, GC;
-    sk_tiling(N, M, GR, GC, rpw);
-    const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
-    return (256 + per_group * sk_max_groups(N, M, rpw) + 255) & ~(size_t)255;
-}
 static size_t slots_bytes(int N, int M) {
-    size_t b = slots_bytes_rpw(N, M, 16);
-    for (int rpw : {8, 4})
-        if (M <= 512 && (N + 8 * rpw - 1) / (8 * rpw) <= 16) { const size_t x = slots_bytes_rpw(N, M, rpw); b = x > b ? x : b; }
-    return b;
+    int GR, GC;
+    sk_tiling(N, M, GR, GC);
+    const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
+    return (256 + per_group * sk_max_groups(N, M) + 255) & ~(size_t)255;
 }
 static size_t flags_bytes(int B) { return ((size_t)B * sizeof(unsigned) + 255) & ~(size_t)255; }
 size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M) {
     if (N > 2048 || M > 2048) return 0;
     int GR, GC;
     sk_tiling(N, M, GR, GC);
-    if (M <= 512 && (N + 31) / 32 <= 16) GR = (N + 31) / 32;       // (the thinnest slabs the shape may run with: sk_rpw)
     // exchange slots + per-pair range flags + fused arg-max scratch: row bests [B][GC][N] (int + float), column bests [B][GR][M] (int + float)
     return slots_bytes(N, M) + flags_bytes(B) + ((size_t)B * GC * N * 2 + (size_t)B * GR * M * 2) * sizeof(float);
 }
@@ -1214,23 +1153,21 @@ static int launch_streaming(const SkArgs& a, int B, hipStream_t s) {
 
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return (N > 2048 || M > 2048) ? 0 : slots_bytes(N, M) + flags_bytes(B); }
 
-template <int RPW>
 static int launch_scaling(int B, int N, int M, const float* scores, const float* alpha_dev, float alpha_host, int iters,
                           float* Z, void* ws, int num_cu, const SkExtract* ex, unsigned* status, float* Zfb, bool slots_cleared, hipStream_t s) {
     int GR, GC;
-    sk_tiling(N, M, GR, GC, RPW);
+    sk_tiling(N, M, GR, GC);
     const int P = GR * GC;                         // workgroups per pair, one per CU
     int ngroups = num_cu / P;
-    if (ngroups > sk_max_groups(N, M, RPW)) ngroups = sk_max_groups(N, M, RPW);
+    if (ngroups > sk_max_groups(N, M)) ngroups = sk_max_groups(N, M);
     if (ngroups > B) ngroups = B;
     // Placement: the workgroups of a pair exchange through L2 every iteration, which is fast and steady only inside one XCD
     // (workgroup i runs on XCD i % 8): group g takes the workgroups with blockIdx % 8 == g % 8, and the grid is padded to a
     // multiple of 8 groups - the surplus workgroups leave at once.  (Before: only batches that are multiples of 8 were placed,
     // others ran their partners on four different XCDs - 1.0 ms against an erratic 1.0 ... 3.5 ms per forward at B = 2 ... 4 -
     // and a batch of 12 ran as 8 + 4.)  A pair's workgroups must fit the 32 CUs of an XCD next to the other groups placed there.
-    static const bool cooperative = getenv("MDGAT_SK_COOPERATIVE") != nullptr;
     const int ng8 = (ngroups + 7) & ~7;
-    const bool xcd_map = P * (ng8 / 8) <= num_cu / 8 && (!cooperative || ngroups == ng8);
+    const bool xcd_map = P * (ng8 / 8) <= num_cu / 8;
     const int grid = xcd_map ? ng8 * P : ngroups * P;
     if (ngroups < 1) { mdgat_set_error("sinkhorn: %d workgroups per pair do not fit the device", P); return MDGAT_ERR_UNSUPPORTED; }
     const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
@@ -1254,12 +1191,9 @@ static int launch_scaling(int B, int N, int M, const float* scores, const float*
         a.cbest_val = reinterpret_cast<float*>(p);
     }
     void* args[] = {&a};
-    const void* kern;
-    if constexpr (RPW == 16)
-        kern = GC > 1 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<RPW, true, 16>)
-             : GR > 4 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<RPW, false, 16>)
-                      : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<RPW, false, 4>);
-    else kern = reinterpret_cast<const void*>(sinkhorn_scaling_kernel<RPW, false, 16>);      // (one column slab, up to 16 row slabs: sk_rpw)
+    const void* kern = GC > 1 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<true, 16>)
+                     : GR > 4 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 16>)
+                              : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 4>);
     // The workgroups of a pair wait for each other, so all of them must become resident.  A workgroup takes a whole CU
     // (512 threads x 256 registers), and ngroups * P <= num_cu by construction: every workgroup gets a CU as soon as the
     // stragglers of earlier launches leave.  A plain launch therefore suffices when this launch has the device to itself, and
@@ -1269,12 +1203,11 @@ static int launch_scaling(int B, int N, int M, const float* scores, const float*
     // streams, other processes) could leave every CU with a workgroup whose partners cannot be dispatched.  The spins are
     // therefore bounded, a workgroup that gives up raises the launch's error word, and the streaming kernel launched right
     // behind (gated on that word: it leaves at once otherwise, ~3 us) redoes the launch one workgroup per pair - slow, never
-    // wrong.  Without a fallback buffer (no Z and none lent) or with MDGAT_SK_COOPERATIVE=1 the launch is cooperative: the
-    // runtime then checks co-residency.
+    // wrong.  Without a fallback buffer (no Z and none lent) the launch is cooperative: the runtime then checks co-residency.
     float* zfb = Z ? Z : Zfb;
     const bool can_fall_back = zfb != nullptr && streaming_supported(N, M);
     hipError_t e;
-    if (cooperative || !can_fall_back || ngroups * P > num_cu) e = hipLaunchCooperativeKernel(kern, dim3(grid), dim3(SKS_THREADS), args, 0, s);
+    if (!can_fall_back || ngroups * P > num_cu) e = hipLaunchCooperativeKernel(kern, dim3(grid), dim3(SKS_THREADS), args, 0, s);
     else e = hipLaunchKernel(kern, dim3(grid), dim3(SKS_THREADS), args, 0, s);
     if (int rc = mdgat_check_hip(e, "sinkhorn scaling launch")) return rc;
     if (can_fall_back) {
@@ -1304,10 +1237,7 @@ int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_s
     const size_t need = sinkhorn_cluster_workspace_bytes(B, N, M);
     if (need && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0) {
         const int num_cu = mdgat_cu_count();
-        const int rpw = sk_rpw(B, N, M);
-        if (rpw == 4) return launch_scaling<4>(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
-        if (rpw == 8) return launch_scaling<8>(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
-        return launch_scaling<16>(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
+        return launch_scaling(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
     }
     if (!Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
     SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr};

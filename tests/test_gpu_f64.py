@@ -596,7 +596,7 @@ def test_f64_fused_layer_tail_equals_three_launches(B, n, m, L, k):
     fragment order straight from L2) against the three gemm_f64_kernel launches it replaces - and the fused encoder launch (both
     encoders, their sum, layer 0's q | k | v) against the seven it replaces: every accumulator walks k in the same order, so EVERY
     output bit is the same - matches, scores, Z, and the fp32 taps of the encoder output and of every layer's descriptors - for each
-    tile height (16 / 32 / 64 keypoints per workgroup), ragged keypoint counts, one pair, a batch large enough to run in slices, and
+    tile height (16 / 32 keypoints per workgroup), ragged keypoint counts, one pair, a batch large enough to run in slices, and
     a network without a dynamic layer (encoders only in fp64: the encoder launch hands over)."""
     from mdgat_matcher_amd import _lib
     lib = _lib.load()
@@ -618,10 +618,10 @@ def test_f64_fused_layer_tail_equals_three_launches(B, n, m, L, k):
             return out, t
         finally:
             lib.mdgat_set_f64_layer_fusion(-1)
-            assert prev in (0, 1, 2, 16, 32, 64)
+            assert prev in (0, 1, 2, 16, 32)
     for taps in (False, True):          # (taps run the whole batch unsliced)
         ref, rt = run(0, taps)
-        for mode in (1, 2, 16, 32, 64):     # (1: launches of few 16-row blocks take the clustered kernel - four workgroups per block; 2: never)
+        for mode in (1, 2, 16, 32):     # (1: launches of few 16-row blocks take the clustered kernel - four workgroups per block; 2: never)
             out, ot = run(mode, taps)
             for a, b, what in zip(ref, out, ('matches0', 'matches1', 'mscores0', 'mscores1', 'Z')):
                 assert torch.equal(a, b), (mode, taps, what)

@@ -1,6 +1,6 @@
 """Exact mode (a float64 module): the fused layer tail (csrc/layer_f64.hip) against the three-launch form, per batch size -
 forward time (one lane, then the default two lanes) and the time of the fp64 product class (HIP events on the launch stream,
-mdgat_profile).  GPU box:  python tools/f64_fusion_time.py [modes ...]   (modes: 0 = three launches, 1 = fused, 16 / 32 / 64 = fused
+mdgat_profile).  GPU box:  python tools/f64_fusion_time.py [modes ...]   (modes: 0 = three launches, 1 = fused, 16 / 32 = fused
 with that many keypoints per workgroup)"""
 import os
 import sys
@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 from mdgat_matcher_amd import MDGAT, _lib, synth  # noqa: E402
 
 DEV = 'cuda:0'
-modes = [int(x) for x in sys.argv[1:]] or [0, 1, 16, 32, 64]
+modes = [int(x) for x in sys.argv[1:]] or [0, 1, 16, 32]
 lib = _lib.load()
 L, S = 9, 100
 net = MDGAT(synth.default_config(L=L, sinkhorn_iterations=S)).double()
