@@ -155,7 +155,8 @@ const char* mdgat_last_error(void);
 /* Scratch the caller must provide to mdgat_forward for a batch of B pairs with N / M keypoints. */
 size_t mdgat_workspace_bytes(const mdgat_handle* h, int B, int N, int M);
 
-/* MDGAT.forward (mdgat.py:369-483) for descriptor == 'FPFH', loss excluded.
+/* MDGAT.forward (mdgat.py:369-483) for descriptor == 'FPFH' without the loss (mdgat_forward_loss with a NULL request; the
+ * evaluation loss of mdgat.py:486-594 is computed by mdgat_forward_loss below).
  * Z (optional, may be NULL) receives log_optimal_transport's output [B][N+1][M+1]. */
 int mdgat_forward(mdgat_handle* h, int B, int N, int M,
                   const float* kpts0, const float* sigma0, const float* fpfh0,
@@ -187,6 +188,52 @@ int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* fram
                          int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                          float* Z, const mdgat_taps* taps,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- evaluation loss (mdgat.py:486-594; no backward: the library is inference only) ------------------------------------- */
+
+/* config['loss_method'] of the loss: superglue (487-511), triplet_loss (512-546), gap_loss (547-594) */
+typedef enum { MDGAT_LOSS_SUPERGLUE = 0, MDGAT_LOSS_TRIPLET = 1, MDGAT_LOSS_GAP = 2 } mdgat_loss_method;
+
+/* What the forward's loss needs besides Z: gt0 [B][N] / gt1 [B][M] int64 ground-truth matches (-1 = unmatched: the dustbin column
+ * M / row N), gamma = config['triplet_loss_gamma'], loss [B] fp64 receives one value per pair - superglue: the pair's
+ * (-tp - tn) / (xx + M), triplet: the mean of the pair's N + M terms (the module's loss is the mean over pairs of either), gap: the
+ * pair's loss.  superglue and triplet need N == M (the reference's index tensors do not broadcast otherwise).  A gt0 value outside
+ * [-1, M] or (triplet, gap) a gt1 value outside [-1, N] is an indexing error in the reference: that pair's loss is NaN and bit 0 of
+ * *bad_index (device memory, optional; the caller clears it) is set.  The gts are not rewritten (the reference's in-place -1 -> M / N
+ * rewrite is left to the caller). */
+typedef struct {
+    int32_t method;            /* mdgat_loss_method */
+    double gamma;
+    const int64_t* gt0;
+    const int64_t* gt1;
+    double* loss;
+    unsigned* bad_index;
+} mdgat_loss_request;
+
+/* The loss on a caller-supplied Z [B][N+1][M+1] (fp32 or fp64; the arithmetic is fp64 either way).  workspace: 256-byte aligned,
+ * mdgat_loss_workspace_bytes.  Reads Z once; no allocation, no synchronisation. */
+int mdgat_loss(int B, int N, int M, const float* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma, double* loss,
+               unsigned* bad_index, void* workspace, size_t workspace_bytes, void* stream);
+int mdgat_loss_f64(int B, int N, int M, const double* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma, double* loss,
+                   unsigned* bad_index, void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_loss_workspace_bytes(int B, int N, int M);
+
+/* mdgat_forward / mdgat_forward_f64 and the loss of `req` on the forward's own Z: the fp64 Z of the exact mode's fp64 tail, else the
+ * fp32 Z.  Outputs, workspace alignment and everything else as the forwards without the loss; req == NULL is exactly those.  The
+ * workspace is larger (Z is always materialised: in fp64 on a MDGAT_ARITH_FP64 handle): mdgat_forward_loss_workspace_bytes. */
+int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M,
+                       const float* kpts0, const float* sigma0, const float* fpfh0,
+                       const float* kpts1, const float* sigma1, const float* fpfh1,
+                       int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                       float* Z, const mdgat_taps* taps, const mdgat_loss_request* req,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int mdgat_forward_f64_loss(mdgat_handle* h, int B, int N, int M,
+                           const double* kpts0, const double* sigma0, const double* fpfh0,
+                           const double* kpts1, const double* sigma1, const double* fpfh1,
+                           int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                           float* Z, const mdgat_taps* taps, const mdgat_loss_request* req,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_forward_loss_workspace_bytes(const mdgat_handle* h, int B, int N, int M);
 
 /* Asynchronous status of the handle's forwards since the last call with clear != 0 (read it after synchronising the
  * stream: the forward itself never synchronises).  *range_violation != 0: an activation left the f16 operand range

@@ -20,6 +20,11 @@ EXTRACT_THRESHOLD_MUTUAL = 3
 PROF_CLASSES = ('encoder', 'layer', 'attention_full', 'attention_topk', 'scores', 'sinkhorn', 'extract', 'layer_first', 'layer_last',
                 'f64_gemm', 'f64_attention_full', 'f64_attention_topk', 'f64_other')
 
+LOSS_SUPERGLUE = 0
+LOSS_TRIPLET = 1
+LOSS_GAP = 2
+LOSS_METHODS = {'superglue': LOSS_SUPERGLUE, 'triplet_loss': LOSS_TRIPLET, 'gap_loss': LOSS_GAP}     # config['loss_method'] -> mdgat_loss_method
+
 ARITH_FP32 = 0
 ARITH_FP64 = 1
 F64_ENCODERS_ONLY = -1
@@ -53,6 +58,11 @@ class MdgatTaps(C.Structure):
 TAP_NAMES = ('x_enc', 'x_layers', 'mdesc', 'scores', 'topk_sel')
 
 
+class MdgatLossRequest(C.Structure):
+    _fields_ = [('method', C.c_int32), ('gamma', C.c_double), ('gt0', C.c_void_p), ('gt1', C.c_void_p), ('loss', C.c_void_p),
+                ('bad_index', C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/mdgat_hip.h declares
 SIGNATURES = {
     'mdgat_create': (C.c_int, [C.POINTER(MdgatConfig), C.c_int, C.POINTER(C.c_void_p)]),
@@ -70,6 +80,16 @@ SIGNATURES = {
                           [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_forward_frames': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
                              [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_forward_loss': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p] * 4 +
+                           [C.c_void_p, C.POINTER(MdgatTaps), C.POINTER(MdgatLossRequest), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_forward_f64_loss': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p] * 4 +
+                               [C.c_void_p, C.POINTER(MdgatTaps), C.POINTER(MdgatLossRequest), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_forward_loss_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'mdgat_loss': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_loss_f64': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_loss_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_async_status': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     'mdgat_last_token': (C.c_uint, [C.c_void_p]),
     'mdgat_matched_any': (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_uint)]),

@@ -10,6 +10,7 @@
 #include "f64.hpp"
 #include "sinkhorn_f64.hpp"
 #include "coop_chain.hpp"
+#include "loss.hpp"
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -334,6 +335,12 @@ Workspace carve(float* base, int B, int N, int M, bool f64) {
     w.total = o;
     return w;
 }
+// A forward with a loss request (mdgat_forward_loss) needs, behind its carve, the loss kernels' workspace and - on an exact-mode
+// handle, whose fp64 tail hands the loss the fp64 Z - room for that Z.
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+size_t loss_extra_bytes(int B, int N, int M, bool f64) {
+    return al256(loss_workspace_bytes(B, N, M)) + (f64 ? al256((size_t)B * (N + 1) * (M + 1) * sizeof(double)) : 0);
+}
 }  // namespace
 
 
@@ -375,7 +382,8 @@ static int f64_layer_count(const mdgat_config& cfg) {
 
 static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
                         int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
-                        const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream, int defer_alldust = 0, int lane = 0) {
+                        const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream, int defer_alldust = 0, int lane = 0,
+                        const mdgat_loss_request* loss_req = nullptr) {
     const float *kpts0 = in.kpts0, *sigma0 = in.sigma0, *fpfh0 = in.fpfh0, *kpts1 = in.kpts1, *sigma1 = in.sigma1, *fpfh1 = in.fpfh1;
     const float *rec0 = in.rec0, *rec1 = in.rec1;
     const int normalize_fpfh = in.normalize_fpfh;
@@ -407,7 +415,9 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
         mdgat_set_error("mdgat_forward: null pointer argument");
         return MDGAT_ERR_BAD_ARG;
     }
-    const size_t need = carve(nullptr, B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64).total * sizeof(float);
+    const bool f64h = h->cfg.arithmetic == MDGAT_ARITH_FP64;
+    const size_t carved = al256(carve(nullptr, B, N, M, f64h).total * sizeof(float));
+    const size_t need = loss_req ? carved + loss_extra_bytes(B, N, M, f64h) : carved;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
     const int L2 = 2 * h->cfg.L;
@@ -422,6 +432,10 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
     const BlobLayout& bl = h->bl;
     const float* w = h->weights;
     Workspace ws = carve(static_cast<float*>(workspace), B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64);
+    // the loss (mdgat_forward_loss): its workspace and the exact mode's fp64 Z behind the carve
+    char* loss_ws = static_cast<char*>(workspace) + carved;
+    const size_t loss_ws_bytes = al256(loss_workspace_bytes(B, N, M));
+    double* Z64 = loss_req && f64h ? reinterpret_cast<double*>(loss_ws + loss_ws_bytes) : nullptr;
     const int P = N + M;
     const int R = B * P;
     int rc;
@@ -580,10 +594,16 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
             float* cv = reinterpret_cast<float*>(bw);
             const SkExtract ex64{h->cfg.extract_mode, h->cfg.match_threshold, matches0, matches1, mscores0, mscores1, defer_alldust,
                                  status_dev + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
-            if ((rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, h->cfg.sinkhorn_iters, nullptr, Z, h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, ri, rv, ci, cv,
+            if ((rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, h->cfg.sinkhorn_iters, Z64, Z, h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, ri, rv, ci, cv,
                                           ws.sk64, kb, status_dev + MDGAT_STATUS_RANGE, coop_group, w64 + bl.bin_score))) return rc;
             if ((rc = launch_extract_from_bests(B, N, M, &ex64, ri, rv, ci, cv, s))) return rc;
             mark(MDGAT_PROF_SINKHORN);
+            if (loss_req) {
+                // the loss (mdgat.py:486-594) on the fp64 Z; its time is attributed to no class
+                if ((rc = launch_loss(B, N, M, static_cast<const double*>(Z64), loss_req->gt0, loss_req->gt1, loss_req->method, loss_req->gamma,
+                                      loss_req->loss, loss_req->bad_index, loss_ws, loss_ws_bytes, s))) return rc;
+                mark(-1);
+            }
             return MDGAT_OK;
         }
         // hand-over: nothing behind the last dynamic layer is discontinuous
@@ -640,14 +660,20 @@ static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
         if ((rc = mdgat_check_hip(hipMemcpyAsync(taps->scores, ws.scores, (size_t)B * N * M * sizeof(float), hipMemcpyDeviceToDevice, s), "tap scores"))) return rc;
 
     // ---- optimal transport (mdgat.py:434-436) and match extraction (441-483) ----
-    // (Z is only materialised when the caller asks for it or the streaming Sinkhorn needs it for the extraction)
+    // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
     const bool fused = ws.sk_bytes != 0;   // N, M <= 2048: the cluster kernel, arg-maxes fused
-    float* Zout = Z ? Z : (fused ? nullptr : ws.Z);
+    float* Zout = Z ? Z : (fused && !loss_req ? nullptr : ws.Z);
     const SkExtract ex{h->cfg.extract_mode, h->cfg.match_threshold, matches0, matches1, mscores0, mscores1, defer_alldust,
                        status_dev + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
     if ((rc = launch_sinkhorn(B, N, M, ws.scores, w + bl.bin_score, 0.f, h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, s, status_dev,
                               Z ? Z : ws.Z, sk_clear != 0))) return rc;
     mark(MDGAT_PROF_SINKHORN);
+    if (loss_req) {
+        // the loss (mdgat.py:486-594) on the fp32 Z, widened to fp64; its time is attributed to no class
+        if ((rc = launch_loss(B, N, M, static_cast<const float*>(Zout), loss_req->gt0, loss_req->gt1, loss_req->method, loss_req->gamma,
+                              loss_req->loss, loss_req->bad_index, loss_ws, loss_ws_bytes, s))) return rc;
+        mark(-1);
+    }
     return MDGAT_OK;
 }
 
@@ -687,7 +713,7 @@ static int prof_collect(mdgat_handle* h) {
 // Taps (whole-batch layouts) run unsliced; mdgat_set_lanes(h, 1) / MDGAT_FORWARD_LANES=1 keeps everything on the caller's stream
 // (slices of 65 536 keypoints beyond 1.5 x that).
 struct LanePlan { int nslices, per, lanes; size_t lane_bytes; };
-static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64) {
+static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss = false) {
     static const long env_points = [] { const char* e = getenv("MDGAT_FORWARD_SLICE_POINTS"); return e ? atol(e) : -1L; }();   // unset: defaults; 0: never slice
     LanePlan p{1, B, 1, 0};
     const long per_pair = (long)N + M;
@@ -711,19 +737,23 @@ static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64) {
         p.per = (int)((B + n - 1) / n);
         p.nslices = (B + p.per - 1) / p.per;
     }
-    p.lane_bytes = (carve(nullptr, p.per, N, M, f64).total * sizeof(float) + 255) & ~size_t(255);
+    p.lane_bytes = al256(carve(nullptr, p.per, N, M, f64).total * sizeof(float)) + (loss ? loss_extra_bytes(p.per, N, M, f64) : 0);
     return p;
 }
 
-extern "C" size_t mdgat_workspace_bytes(const mdgat_handle* h, int B, int N, int M) {
+static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool loss) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     // (taps run unsliced: the whole batch's workspace is the lower bound in every case)
     const bool f64 = h && h->cfg.arithmetic == MDGAT_ARITH_FP64;
-    const size_t whole = carve(nullptr, B, N, M, f64).total * sizeof(float);
-    const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64);
+    const size_t carved = carve(nullptr, B, N, M, f64).total * sizeof(float);
+    const size_t whole = loss ? al256(carved) + loss_extra_bytes(B, N, M, f64) : carved;
+    const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
 }
+
+extern "C" size_t mdgat_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, false); }
+extern "C" size_t mdgat_forward_loss_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, true); }
 
 extern "C" int mdgat_set_lanes(mdgat_handle* h, int lanes) {
     if (!h || lanes < 1 || lanes > 2) { mdgat_set_error("mdgat_set_lanes: lanes must be 1 or 2"); return MDGAT_ERR_BAD_ARG; }
@@ -733,9 +763,20 @@ extern "C" int mdgat_set_lanes(mdgat_handle* h, int lanes) {
 
 static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
                            int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
-                           const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
+                           const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream,
+                           const mdgat_loss_request* loss_req = nullptr) {
     LanePlan p{1, B, 1, 0};
     if (!h) { mdgat_set_error("mdgat_forward: null handle"); return MDGAT_ERR_BAD_ARG; }
+    if (loss_req) {
+        // refused before anything is enqueued
+        const int lm = loss_req->method;
+        if (lm != MDGAT_LOSS_SUPERGLUE && lm != MDGAT_LOSS_TRIPLET && lm != MDGAT_LOSS_GAP) { mdgat_set_error("mdgat_forward_loss: bad method %d", lm); return MDGAT_ERR_BAD_ARG; }
+        if (!loss_req->gt0 || !loss_req->gt1 || !loss_req->loss) { mdgat_set_error("mdgat_forward_loss: null pointer in the loss request"); return MDGAT_ERR_BAD_ARG; }
+        if (lm != MDGAT_LOSS_GAP && N != M) {
+            mdgat_set_error("mdgat_forward_loss: the superglue and triplet losses need N == M (N=%d M=%d), as the reference's do", N, M);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    }
     // the handle's device is current for the whole call, the caller's restored after it: everything below works on the current device
     struct DeviceScope {
         int prev = -1, dev;
@@ -746,9 +787,10 @@ static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in
     if (int rc = mdgat_check_hip(scope.set, "hipSetDevice")) return rc;
     std::lock_guard<std::mutex> serialise(h->enqueue);
     if (++h->match_token == 0) h->match_token = 1;      // this call's token (mdgat_matched_any): every slice / lane of the call writes the same one
-    if (!taps && B > 0 && N > 0 && M > 0 && matches0 && matches1 && mscores0 && mscores1) p = lane_plan(h->lanes, B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64);
+    if (!taps && B > 0 && N > 0 && M > 0 && matches0 && matches1 && mscores0 && mscores1)
+        p = lane_plan(h->lanes, B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64, loss_req != nullptr);
     if (p.nslices <= 1) {
-        const int rc = forward_impl(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+        const int rc = forward_impl(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, 0, 0, loss_req);
         return rc ? rc : prof_collect(h);
     }
     if (!workspace || workspace_bytes < p.lane_bytes * (size_t)p.lanes) {
@@ -768,10 +810,17 @@ static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in
         const int b = B - c < p.per ? B - c : p.per;
         const size_t c_ = (size_t)c;
         const int lane = p.lanes == 2 ? (slice & 1) : 0;
+        mdgat_loss_request lr{};
+        if (loss_req) {
+            lr = *loss_req;
+            lr.gt0 += c_ * N;
+            lr.gt1 += c_ * M;
+            lr.loss += c_;
+        }
         rc = forward_impl(h, b, N, M, in.from(c_, N, M),
                           matches0 + c_ * N, matches1 + c_ * M, mscores0 + c_ * N, mscores1 + c_ * M,
                           Z ? Z + c_ * (N + 1) * (M + 1) : nullptr, nullptr, static_cast<char*>(workspace) + (size_t)lane * p.lane_bytes,
-                          p.lane_bytes, lane ? static_cast<void*>(h->lane_stream) : stream, 1, lane);
+                          p.lane_bytes, lane ? static_cast<void*>(h->lane_stream) : stream, 1, lane, loss_req ? &lr : nullptr);
     }
     if (p.lanes == 2) {
         // (joined even after a failed launch: the caller's stream must not run ahead of what the second lane was given)
@@ -800,6 +849,24 @@ extern "C" int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M, const dou
     if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_f64: null input pointer"); return MDGAT_ERR_BAD_ARG; }
     const FwdIn in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1};
     return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
+                                  const float* fpfh0, const float* kpts1, const float* sigma1, const float* fpfh1,
+                                  int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
+                                  const mdgat_taps* taps, const mdgat_loss_request* req, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_loss: null input pointer"); return MDGAT_ERR_BAD_ARG; }
+    const FwdIn in{kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
+}
+
+extern "C" int mdgat_forward_f64_loss(mdgat_handle* h, int B, int N, int M, const double* kpts0, const double* sigma0,
+                                      const double* fpfh0, const double* kpts1, const double* sigma1, const double* fpfh1,
+                                      int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
+                                      const mdgat_taps* taps, const mdgat_loss_request* req, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_f64_loss: null input pointer"); return MDGAT_ERR_BAD_ARG; }
+    const FwdIn in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1};
+    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
 }
 
 extern "C" int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* frames0, const float* frames1,

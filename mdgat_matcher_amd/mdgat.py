@@ -19,8 +19,9 @@ Host-side mirror of ``/root/reference/models/mdgat.py:315-603`` (class ``MDGAT``
   results are cast to the module's dtype either way.
 
 All arithmetic happens in ``libmdgat_hip.so``; PyTorch only owns device memory and streams.  There is no
-CPU path: tensors that are not on a gfx950 device raise.  Training (loss / backward) is out of scope:
-``loss`` is returned as a zero scalar and ``train()`` mode raises in ``forward``.
+CPU path: tensors that are not on a gfx950 device raise.  Training (backward) is out of scope: ``train()`` mode raises in
+``forward``.  The loss VALUE is what the reference's validation loop reads (``train.py:263-299``): with ``config['eval_loss']``
+(or ``MDGAT_EVAL_LOSS=1``) ``forward`` computes it on the device (``csrc/loss.hip``); otherwise ``loss`` is a zero scalar.
 """
 from __future__ import annotations
 
@@ -169,6 +170,11 @@ class MDGAT(nn.Module):
         self.arithmetic = str(self.config.get('arithmetic') or os.environ.get('MDGAT_ARITHMETIC') or 'auto')
         if self.arithmetic not in ('auto', 'fp32', 'fp64'):
             raise ValueError(f"arithmetic={self.arithmetic!r}: expected 'auto', 'fp32' or 'fp64'")
+        # not a reference key: compute the loss of mdgat.py:486-594 in forward (csrc/loss.hip) from data['gt_matches0/1'] - the value
+        # the reference's validation loop (train.py:263-299) averages to choose a checkpoint - instead of returning a zero scalar.
+        # MDGAT_EVAL_LOSS=1 in the environment replaces the default (off) for modules whose config does not carry the key.
+        ev = self.config.get('eval_loss')
+        self.eval_loss = bool(ev) if ev is not None else os.environ.get('MDGAT_EVAL_LOSS') == '1'
         f64_layers = self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -422,8 +428,10 @@ class MDGAT(nn.Module):
         if self.training:
             raise NotImplementedError('mdgat_matcher_amd implements inference only: call .eval() (training, the '
                                       'losses of mdgat.py:486-594 and backward are out of scope)')
+        loss_req = self._loss_request(data, kpts0, kpts1) if getattr(self, 'eval_loss', False) else None
         token = [0]
-        res = self._run(kpts0, data['scores0'], data['descriptors0'], kpts1, data['scores1'], data['descriptors1'], token_out=token)
+        res = self._run(kpts0, data['scores0'], data['descriptors0'], kpts1, data['scores1'], data['descriptors1'], token_out=token,
+                        loss=loss_req)
         m0, m1, s0, s1 = res[:4]
         s0, s1 = s0.to(out_dtype), s1.to(out_dtype)
         if self.loss_method != 'superglue':
@@ -439,13 +447,44 @@ class MDGAT(nn.Module):
                 s0, s1 = torch.zeros_like(m0), torch.zeros_like(m1)
         else:
             self.check(m0.device)                           # the dict API reports on the failing call in every branch
+        loss = m0.new_zeros((), dtype=out_dtype) if loss_req is None else self._finish_loss(loss_req, out_dtype)
         return {
             'matches0': m0,
             'matches1': m1,
             'matching_scores0': s0,
             'matching_scores1': s1,
-            'loss': m0.new_zeros((), dtype=out_dtype),     # losses are training-only: not computed
+            'loss': loss,
         }
+
+    def _loss_request(self, data, kpts0, kpts1):
+        """The loss inputs of mdgat.py:486-594, checked before anything is launched."""
+        gt0, gt1 = data['gt_matches0'], data['gt_matches1']            # KeyError when absent, as in the reference (mdgat.py:438-439)
+        method = _lib.LOSS_METHODS.get(self.loss_method)
+        if method is None:
+            raise ValueError(f"loss_method={self.loss_method!r}: the loss is defined for 'superglue', 'triplet_loss' and 'gap_loss'")
+        B, N, M = kpts0.shape[0], kpts0.shape[1], kpts1.shape[1]
+        if tuple(gt0.shape) != (B, N) or tuple(gt1.shape) != (B, M):
+            raise ValueError(f'gt_matches0 {tuple(gt0.shape)} / gt_matches1 {tuple(gt1.shape)}: expected [{B}, {N}] / [{B}, {M}]')
+        if method != _lib.LOSS_GAP and N != M:
+            raise ValueError(f'loss_method={self.loss_method!r} needs frames of equal size (N={N}, M={M}): the reference\'s index '
+                             "tensors do not broadcast otherwise; 'gap_loss' takes ragged pairs")
+        dev = kpts0.device
+        return {'method': method, 'gt': (gt0, gt1), 'N': N, 'M': M,
+                'g0': gt0.to(device=dev, dtype=torch.int64).contiguous(), 'g1': gt1.to(device=dev, dtype=torch.int64).contiguous(),
+                'loss': torch.empty(B, dtype=torch.float64, device=dev), 'bad': torch.zeros(1, dtype=torch.int32, device=dev)}
+
+    def _finish_loss(self, req, out_dtype):
+        """After the forward's synchronisation: the bad-index word, the reference's in-place rewrite of the gts, the loss."""
+        if int(req['bad'].item()):
+            raise IndexError(f"gt_matches0 holds a value outside [-1, {req['M']}] or gt_matches1 one outside [-1, {req['N']}]")
+        if req['method'] != _lib.LOSS_SUPERGLUE:
+            # mdgat.py:519-520, 554-555 rewrite the caller's tensors in place (test.py:237-238 undoes it)
+            gt0, gt1 = req['gt']
+            gt0[gt0 == -1] = req['M']
+            gt1[gt1 == -1] = req['N']
+        per_pair = req['loss']
+        # gap: one loss per pair [B] (mdgat.py:594); superglue / triplet: the mean (511, 546), 0-d
+        return per_pair.to(out_dtype) if req['method'] == _lib.LOSS_GAP else per_pair.mean().to(out_dtype)
 
     def _matched_any(self, device, token=0) -> bool:
         """Did the forward that carried ``token`` on ``device`` (already synchronised by the caller) match any frame-0 keypoint?
@@ -495,10 +534,12 @@ class MDGAT(nn.Module):
     def _f32(t, device):
         return t.to(device=device, dtype=torch.float32).contiguous()
 
-    def _run(self, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, want_Z=False, taps=None, frames=None, normalize=True, token_out=None):
+    def _run(self, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, want_Z=False, taps=None, frames=None, normalize=True, token_out=None,
+             loss=None):
         """One forward through the library on the current stream.  Either six arrays (keypoints / saliency / FPFH per
         frame) or ``frames=(records0, records1)`` raw [B, N, 37] loader records.  Asynchronous; returns device tensors
-        ``(matches0, matches1, mscores0, mscores1, Z or None)``."""
+        ``(matches0, matches1, mscores0, mscores1, Z or None)``.  ``loss`` (six arrays only): a request of ``_loss_request``
+        whose ``loss`` / ``bad`` tensors the forward fills."""
         probe = frames[0] if frames is not None else kpts0
         if not probe.is_cuda:
             raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP '
@@ -520,7 +561,8 @@ class MDGAT(nn.Module):
         lib = _lib.load()
         with torch.cuda.device(dev), st.lock:
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, B, N, M), dev)
+            need = lib.mdgat_forward_loss_workspace_bytes(st.handle, B, N, M) if loss is not None else lib.mdgat_workspace_bytes(st.handle, B, N, M)
+            ws = st.workspace_for(stream, need, dev)
             m0 = torch.empty((B, N), dtype=torch.int64, device=dev)
             m1 = torch.empty((B, M), dtype=torch.int64, device=dev)
             s0 = torch.empty((B, N), dtype=torch.float32, device=dev)
@@ -534,7 +576,12 @@ class MDGAT(nn.Module):
                     setattr(tap_struct, name, t.data_ptr() if t is not None else None)
             outs = (m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None,
                     C.byref(tap_struct) if tap_struct is not None else None, ws.data_ptr(), ws.numel(), stream)
-            if frames is not None:
+            if loss is not None:
+                req = _lib.MdgatLossRequest(loss['method'], float(self.triplet_loss_gamma), loss['g0'].data_ptr(), loss['g1'].data_ptr(),
+                                            loss['loss'].data_ptr(), loss['bad'].data_ptr())
+                fn = lib.mdgat_forward_f64_loss if f64 else lib.mdgat_forward_loss
+                rc = fn(st.handle, B, N, M, *[t.data_ptr() for t in ins], *outs[:6], C.byref(req), *outs[6:])
+            elif frames is not None:
                 rc = lib.mdgat_forward_frames(st.handle, B, N, M, ins[0].data_ptr(), ins[1].data_ptr(), int(bool(normalize)), *outs)
             elif f64:
                 rc = lib.mdgat_forward_f64(st.handle, B, N, M, *[t.data_ptr() for t in ins], *outs)

@@ -301,3 +301,36 @@ def mfma_f64_probe(device, reps: int = 2000):
         _lib.check(_lib.load().mdgat_mfma_f64_probe(int(reps), ws.data_ptr(), ws.numel(), C.byref(ms), C.byref(fl), C.byref(tk),
                                                     torch.cuda.current_stream(dev).cuda_stream), 'mdgat_mfma_f64_probe')
     return ms.value, fl.value, tk.value
+
+
+def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method='triplet_loss', gamma: float = 0.5) -> torch.Tensor:
+    """The evaluation loss of MDGAT.forward (mdgat.py:486-594; csrc/loss.hip) on Z [B, N+1, M+1] (float32 or float64; the arithmetic is
+    fp64 either way) and ground-truth matches gt0 [B, N] / gt1 [B, M] (any integer dtype, -1 = unmatched; not rewritten).  ``method``:
+    ``'superglue'``, ``'triplet_loss'`` or ``'gap_loss'`` (config['loss_method']); ``gamma``: config['triplet_loss_gamma'].  Returns
+    the per-pair values [B] float64 - superglue / triplet: the pair's ratio / mean (the module's loss is their mean), gap: the pair's
+    loss.  Synchronises: a gt index outside [-1, M] / [-1, N] raises IndexError, as indexing does in the reference."""
+    _need_cuda(Z)
+    m = _lib.LOSS_METHODS[method] if isinstance(method, str) else int(method)
+    f64 = Z.dtype == torch.float64
+    z = Z.to(torch.float64 if f64 else torch.float32).contiguous()
+    B, N1, M1 = z.shape
+    N, M = N1 - 1, M1 - 1
+    if tuple(gt0.shape) != (B, N) or tuple(gt1.shape) != (B, M):
+        raise ValueError(f'gt0 {tuple(gt0.shape)} / gt1 {tuple(gt1.shape)} do not fit Z {tuple(z.shape)}: expected [{B}, {N}] / [{B}, {M}]')
+    if m != _lib.LOSS_GAP and N != M:
+        raise ValueError(f'the {method} loss needs N == M (N={N}, M={M}), as the reference\'s does')
+    g0 = gt0.to(device=z.device, dtype=torch.int64).contiguous()
+    g1 = gt1.to(device=z.device, dtype=torch.int64).contiguous()
+    loss = torch.empty(B, dtype=torch.float64, device=z.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=z.device)
+    lib = _lib.load()
+    with torch.cuda.device(z.device):
+        need = lib.mdgat_loss_workspace_bytes(B, N, M)
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=z.device)
+        off = (-ws.data_ptr()) % 256
+        fn = lib.mdgat_loss_f64 if f64 else lib.mdgat_loss
+        _lib.check(fn(B, N, M, z.data_ptr(), g0.data_ptr(), g1.data_ptr(), m, float(gamma), loss.data_ptr(), bad.data_ptr(),
+                      ws.data_ptr() + off, need, _stream(z)), 'mdgat_loss_f64' if f64 else 'mdgat_loss')
+    if int(bad.item()):
+        raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1)')
+    return loss
