@@ -77,8 +77,11 @@ typedef enum { MDGAT_ATTENTION_FP32 = 0, MDGAT_ATTENTION_F16 = 1 } mdgat_attenti
  * MDGAT_ARITH_FP64: the reference's own arithmetic (the reference runs net.double(), test.py:193) where it decides anything
  * discontinuous: the encoders (mdgat.py:392-393) and the propagation layers up to and including the LAST dynamic layer
  * (mdgat.py:259-276 with dynamic_attention 196-210) run in fp64 on v_mfma_f64_16x16x4_f64 from fp64 inputs and fp64 weights
- * (mdgat_load_weights_f64, mdgat_forward_f64; csrc/f64.hip), so that logits.topk(k) selects what the reference selects; the
- * layers behind it, final_proj, the score matrix and Sinkhorn are continuous and stay on the fp32-class kernels. */
+ * (mdgat_load_weights_f64, mdgat_forward_f64; csrc/f64.hip), so that logits.topk(k) selects what the reference selects.  By
+ * default (mdgat_config.f64_sinkhorn) the tail runs in fp64 as well up to 2175 keypoints: every layer, final_proj, the score
+ * matrix and Sinkhorn, the extraction's arg-maxes decided on the fp64 Z (csrc/sinkhorn_f64.hip).  Beyond that, or with
+ * f64_layers != 0 or MDGAT_F64_SINKHORN_OFF, the layers behind the fp64 ones, final_proj, the score matrix and Sinkhorn run on
+ * the fp32-class kernels. */
 typedef enum { MDGAT_ARITH_FP32 = 0, MDGAT_ARITH_FP64 = 1 } mdgat_arithmetic;
 
 /* Replaces the config dict of MDGAT.__init__ (mdgat.py:325-367) for descriptor == 'FPFH'. */
@@ -167,8 +170,9 @@ int mdgat_forward(mdgat_handle* h, int B, int N, int M,
 
 /* The same forward in the reference's arithmetic (handle created with MDGAT_ARITH_FP64, both blobs loaded): inputs in fp64 as
  * the reference receives them (test.py:194-199 moves the loader's float64 tensors to the device; layouts as above), outputs as
- * mdgat_forward (Z and the matching scores come from the fp32 Sinkhorn: within 1e-4 of the reference's fp64 values).  The taps
- * receive fp32 roundings of the fp64 stages. */
+ * mdgat_forward.  With the fp64 tail (mdgat_arithmetic, mdgat_config.f64_sinkhorn) Z and the matching scores are fp32 roundings
+ * of the fp64 Sinkhorn's values and the matches are decided on them in fp64; with the fp32-class tail they come from the fp32
+ * Sinkhorn (within 1e-4 of the reference's fp64 values).  The taps receive fp32 roundings of the fp64 stages. */
 int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
                       const double* kpts0, const double* sigma0, const double* fpfh0,
                       const double* kpts1, const double* sigma1, const double* fpfh1,

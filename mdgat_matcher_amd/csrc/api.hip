@@ -145,7 +145,7 @@ extern "C" int mdgat_create(const mdgat_config* cfg, int device, mdgat_handle** 
     if (!rc) rc = mdgat_check_hip(hipMalloc(&h->weights, h->bl.total * sizeof(float)), "hipMalloc(weights)");
     if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64) rc = mdgat_check_hip(hipMalloc(&h->weights64, h->bl.total * sizeof(double)), "hipMalloc(fp64 weights)");
     if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64)
-        rc = mdgat_check_hip(hipMalloc(&h->wfrag64, (layer_f64_frag_doubles() * (size_t)(2 * cfg->L) + encoder_f64_frag_doubles()) * sizeof(double)),
+        rc = mdgat_check_hip(hipMalloc(&h->wfrag64, (layer_f64_frag_doubles() * (size_t)(2 * cfg->L) + encoder_f64_frags().total) * sizeof(double)),
                              "hipMalloc(fp64 weight fragments)");
     if (!rc) rc = mdgat_check_hip(hipMalloc(&h->wsplit, (wsplit_halves(cfg->L) + wfrag_halves(cfg->L)) * sizeof(_Float16)), "hipMalloc(split weights)");
     if (!rc) rc = mdgat_check_hip(hipMemset(h->wsplit, 0, (wsplit_halves(cfg->L) + wfrag_halves(cfg->L)) * sizeof(_Float16)), "hipMemset(split weights)");
@@ -265,17 +265,12 @@ extern "C" int mdgat_load_weights_f64(mdgat_handle* h, const double* blob, size_
         if (!rc) rc = launch_frag64(lw + bl.mlp2_w, lf + WF64_W2, 128, 256, nullptr);
         if (!rc) rc = launch_frag64(lw + bl.qkv_w, lf + WF64_QKV, 384, 128, nullptr);
     }
-    {
-        // the encoder matrices behind the layers': kenc.0 | denc.0 | kenc.3 | kenc.6 | denc.3 | last layers summed (EncFrag below)
-        double* ef = h->wfrag64 + layer_f64_frag_doubles() * (size_t)(2 * h->cfg.L);
-        const double* w = h->weights64;
-        const struct { size_t src; int n, k; } enc[6] = {{bl.kenc0_w, 32, 4}, {bl.denc0_w, 64, 33}, {bl.kenc1_w, 64, 32}, {bl.kenc2_w, 128, 64},
-                                                         {bl.denc1_w, 128, 64}, {bl.encl_w, 128, 256}};
-        for (int j = 0; j < 6 && !rc; ++j) {
-            rc = launch_frag64(w + enc[j].src, ef, enc[j].n, enc[j].k, nullptr);
-            ef += frag64_doubles(enc[j].n, enc[j].k);
-        }
-    }
+    // the encoder matrices behind the layers' (encoder_f64_frags)
+    const EncoderF64Frags ef = encoder_f64_frags();
+    double* efrag = h->wfrag64 + layer_f64_frag_doubles() * (size_t)(2 * h->cfg.L);
+    const struct { Frag64 m; size_t src; } enc[6] = {{ef.k0, bl.kenc0_w}, {ef.d0, bl.denc0_w}, {ef.k1, bl.kenc1_w}, {ef.k2, bl.kenc2_w},
+                                                     {ef.d1, bl.denc1_w}, {ef.l, bl.encl_w}};
+    for (int j = 0; j < 6 && !rc; ++j) rc = launch_frag64(h->weights64 + enc[j].src, efrag + enc[j].m.ofs, enc[j].m.n, enc[j].m.k, nullptr);
     if (!rc) rc = mdgat_check_hip(hipDeviceSynchronize(), "fp64 weight fragments");
     (void)hipSetDevice(prev);
     if (rc) return rc;
@@ -301,60 +296,50 @@ extern "C" void mdgat_destroy(mdgat_handle* h) {
 // ---------------------------------------------------------------------------------- workspace
 namespace {
 struct Workspace {
-    float *x, *qkv, *hid, *msg, *scores, *Z, *sk;
+    float *x, *qkv, *hid, *msg, *scores, *Z; _Float16* qkv16;
+    char* sk; size_t sk_bytes;             // the fp32 Sinkhorn's workspace (0: the shape is beyond its cluster kernel)
     double *x64, *qkv64, *hid64, *msg64;   // MDGAT_ARITH_FP64 only: the residual stream, q|k|v, hidden layer and message of the fp64 layers
     double* scores64;                      // ... the fp64 score matrix [B][N][M]: q | k | v's room where it fits, its own beyond (frames past ~770 keypoints)
-    float* sk64; size_t sk64_bytes;        // ... and the workspace of the fp64 Sinkhorn + its arg-max arrays (0: the shape is beyond that kernel)
-    _Float16* qkv16;
-    size_t sk_bytes;
-    size_t total;   // floats
+    char* sk64; size_t sk64_bytes;         // ... and the workspace of the fp64 Sinkhorn (0: the shape is beyond that kernel), its arg-max arrays behind it
+    char* loss; size_t loss_bytes;         // a forward with a loss request (mdgat_forward_loss): the loss kernels' workspace ...
+    double* Z64;                           // ... and on an exact-mode handle, whose fp64 tail hands the loss the fp64 Z, room for that Z
+    size_t total;   // bytes
 };
-Workspace carve(float* base, int B, int N, int M, bool f64) {
+Workspace carve(void* base, int B, int N, int M, bool f64, bool loss) {
     const size_t R = (size_t)B * (N + M);
     Workspace w{};
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o += (n + 63) & ~size_t(63); return base ? base + r : nullptr; };
-    w.x = take(R * 128);
-    w.qkv = take(R * 384);   // qkv and hid are contiguous: the encoder uses them as one scratch area
-    w.hid = take(R * 256);
-    w.msg = take(R * 128);
-    w.scores = take((size_t)B * N * M);
-    w.Z = take((size_t)B * (N + 1) * (M + 1));
+    WsCarver c{static_cast<char*>(base)};
+    c.take(w.x, R * 128);
+    c.take(w.qkv, R * 384);   // qkv and hid are contiguous: the encoder uses them as one scratch area
+    c.take(w.hid, R * 256);
+    c.take(w.msg, R * 128);
+    c.take(w.scores, (size_t)B * N * M);
+    c.take(w.Z, (size_t)B * (N + 1) * (M + 1));
     w.sk_bytes = mdgat_sinkhorn_ws_bytes_impl(B, N, M);
-    w.sk = take((w.sk_bytes + 3) / 4);
-    w.qkv16 = reinterpret_cast<_Float16*>(take((mdgat_qkv16_halves(B, N, M) + 1) / 2));
+    c.take(w.sk, w.sk_bytes);
+    c.take(w.qkv16, mdgat_qkv16_halves(B, N, M));
     if (f64) {
-        w.x64 = reinterpret_cast<double*>(take(R * 128 * 2));
-        w.qkv64 = reinterpret_cast<double*>(take(R * 384 * 2));     // qkv64 and hid64 are contiguous: the encoder stages live there
-        w.hid64 = reinterpret_cast<double*>(take(R * 256 * 2));
-        w.msg64 = reinterpret_cast<double*>(take(R * 128 * 2));
-        w.sk64_bytes = sinkhorn_f64_supported(N, M) ? sinkhorn_f64_workspace_bytes(B, N, M) + sinkhorn_f64_bests_bytes(B, N, M) : 0;
-        w.sk64 = take((w.sk64_bytes + 3) / 4);
-        w.scores64 = (size_t)N * M <= (size_t)384 * (N + M) || !w.sk64_bytes ? w.qkv64 : reinterpret_cast<double*>(take((size_t)B * N * M * 2));
+        c.take(w.x64, R * 128);
+        c.take(w.qkv64, R * 384);     // qkv64 and hid64 are contiguous: the encoder stages live there
+        c.take(w.hid64, R * 256);
+        c.take(w.msg64, R * 128);
+        w.sk64_bytes = sinkhorn_f64_supported(N, M) ? sinkhorn_f64_workspace_bytes(B, N, M) : 0;
+        c.take(w.sk64, w.sk64_bytes ? w.sk64_bytes + sinkhorn_f64_bests(nullptr, B, N, M).bytes : 0);
+        if ((size_t)N * M <= (size_t)384 * (N + M) || !w.sk64_bytes) w.scores64 = w.qkv64;
+        else c.take(w.scores64, (size_t)B * N * M);
     }
-    w.total = o;
+    if (loss) {
+        w.loss_bytes = loss_workspace_bytes(B, N, M);
+        c.take(w.loss, w.loss_bytes);
+        if (f64) c.take(w.Z64, (size_t)B * (N + 1) * (M + 1));
+    }
+    w.total = c.bytes;
     return w;
-}
-// A forward with a loss request (mdgat_forward_loss) needs, behind its carve, the loss kernels' workspace and - on an exact-mode
-// handle, whose fp64 tail hands the loss the fp64 Z - room for that Z.
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t loss_extra_bytes(int B, int N, int M, bool f64) {
-    return al256(loss_workspace_bytes(B, N, M)) + (f64 ? al256((size_t)B * (N + 1) * (M + 1) * sizeof(double)) : 0);
 }
 }  // namespace
 
 
 // ---------------------------------------------------------------------------------- forward
-static GemmArgs pointwise(const float* A, int lda, int K, const float* W, const float* bias, int relu, float* C, int ldc,
-                          int rows, int cout) {
-    GemmArgs g{};
-    g.A0 = A; g.lda0 = lda; g.K0 = K; g.A1 = nullptr; g.lda1 = 0;
-    g.W = W; g.ldw = K; g.bias = bias; g.R = nullptr; g.ldr = 0;
-    g.C = C; g.ldc = ldc; g.M = rows; g.N = cout; g.K = K; g.relu = relu; g.scale = 1.f;
-    g.batch = 1; g.sA = g.sW = g.sC = 0;
-    return g;
-}
-
 // inputs of a forward: six fp32 arrays, or raw 37-float frame records, or (MDGAT_ARITH_FP64) six fp64 arrays
 struct FwdIn {
     const float *kpts0, *sigma0, *fpfh0, *kpts1, *sigma1, *fpfh1;
@@ -370,6 +355,22 @@ struct FwdIn {
     }
 };
 
+// outputs of a forward: matches, matching scores, Z (optional) and the loss (mdgat_forward_loss)
+struct FwdOut {
+    int64_t *matches0, *matches1;
+    float *mscores0, *mscores1, *Z;
+    bool loss;
+    mdgat_loss_request lr;
+    // the same outputs from pair c on
+    FwdOut from(size_t c, int N, int M) const {
+        FwdOut o = *this;
+        o.matches0 += c * N; o.matches1 += c * M; o.mscores0 += c * N; o.mscores1 += c * M;
+        if (Z) o.Z += c * (N + 1) * (M + 1);
+        if (loss) { o.lr.gt0 += c * N; o.lr.gt1 += c * M; o.lr.loss += c; }
+        return o;
+    }
+};
+
 // MDGAT_ARITH_FP64: the number of leading propagation layers that run in fp64 (mdgat_config.f64_layers)
 static int f64_layer_count(const mdgat_config& cfg) {
     if (cfg.f64_layers > 0) return cfg.f64_layers;
@@ -378,324 +379,6 @@ static int f64_layer_count(const mdgat_config& cfg) {
     for (int i = 0; i < 2 * cfg.L; ++i)
         if (cfg.topk[i] > 0) n = i + 1;
     return n;
-}
-
-static int forward_impl(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
-                        int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
-                        const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream, int defer_alldust = 0, int lane = 0,
-                        const mdgat_loss_request* loss_req = nullptr) {
-    const float *kpts0 = in.kpts0, *sigma0 = in.sigma0, *fpfh0 = in.fpfh0, *kpts1 = in.kpts1, *sigma1 = in.sigma1, *fpfh1 = in.fpfh1;
-    const float *rec0 = in.rec0, *rec1 = in.rec1;
-    const int normalize_fpfh = in.normalize_fpfh;
-    if (!h) { mdgat_set_error("mdgat_forward: null handle"); return MDGAT_ERR_BAD_ARG; }
-    // fp64 inputs, or raw float32 records on a handle that computes in fp64 (the loader's own sequence: float32 records, FPFH
-    // normalised in float32, widened to double - load_data.py:146-165, 290-295)
-    const bool f64 = in.dk0 != nullptr || (in.rec0 != nullptr && h->cfg.arithmetic == MDGAT_ARITH_FP64);
-    if (!h->loaded) { mdgat_set_error("mdgat_forward: weights not loaded"); return MDGAT_ERR_NO_WEIGHTS; }
-    if (f64 && (h->cfg.arithmetic != MDGAT_ARITH_FP64 || !h->loaded64)) {
-        mdgat_set_error("mdgat_forward_f64: the handle needs MDGAT_ARITH_FP64 and mdgat_load_weights_f64");
-        return h->cfg.arithmetic != MDGAT_ARITH_FP64 ? MDGAT_ERR_BAD_ARG : MDGAT_ERR_NO_WEIGHTS;
-    }
-    if (!f64 && h->cfg.arithmetic == MDGAT_ARITH_FP64) {
-        mdgat_set_error("mdgat_forward: this handle computes in fp64 (MDGAT_ARITH_FP64): call mdgat_forward_f64 with fp64 inputs");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    if (static_cast<volatile unsigned*>(h->host_error)[MDGAT_STATUS_RANGE]) {
-        // the forward is asynchronous: what an earlier launch found surfaces here unless the caller asked first
-        // (mdgat_async_status after its own synchronisation - MDGAT.forward does)
-        h->host_error[MDGAT_STATUS_RANGE] = 0;
-        mdgat_set_error("mdgat_forward: a previous call on this handle met activations outside the f16 operand range (|v| >= 6e4; fp64 "
-                        "layers of the exact mode: |v| >= 2^500) or non-finite values; its outputs are invalid");
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    if (B <= 0 || N <= 0 || M <= 0) { mdgat_set_error("mdgat_forward: empty batch/keypoints (B=%d N=%d M=%d) must be handled by the caller", B, N, M); return MDGAT_ERR_BAD_ARG; }
-    const bool arrays = kpts0 && sigma0 && fpfh0 && kpts1 && sigma1 && fpfh1;
-    const bool arrays64 = in.dk0 && in.ds0 && in.df0 && in.dk1 && in.ds1 && in.df1;
-    if ((!arrays && !(rec0 && rec1) && !arrays64) || !matches0 || !matches1 || !mscores0 || !mscores1 || !workspace) {
-        mdgat_set_error("mdgat_forward: null pointer argument");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    const bool f64h = h->cfg.arithmetic == MDGAT_ARITH_FP64;
-    const size_t carved = al256(carve(nullptr, B, N, M, f64h).total * sizeof(float));
-    const size_t need = loss_req ? carved + loss_extra_bytes(B, N, M, f64h) : carved;
-    if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
-    const int L2 = 2 * h->cfg.L;
-    for (int i = 0; i < L2; ++i) {
-        const int k = h->cfg.topk[i];
-        if (k > 0 && (k > N || k > M)) {   // torch.topk raises (mdgat.py:202)
-            mdgat_set_error("layer %d: dynamic attention k=%d exceeds the number of keys (N=%d, M=%d)", i, k, N, M);
-            return MDGAT_ERR_BAD_ARG;
-        }
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const BlobLayout& bl = h->bl;
-    const float* w = h->weights;
-    Workspace ws = carve(static_cast<float*>(workspace), B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64);
-    // the loss (mdgat_forward_loss): its workspace and the exact mode's fp64 Z behind the carve
-    char* loss_ws = static_cast<char*>(workspace) + carved;
-    const size_t loss_ws_bytes = al256(loss_workspace_bytes(B, N, M));
-    double* Z64 = loss_req && f64h ? reinterpret_cast<double*>(loss_ws + loss_ws_bytes) : nullptr;
-    const int P = N + M;
-    const int R = B * P;
-    int rc;
-    unsigned* status_dev = nullptr;
-    if ((rc = mdgat_check_hip(hipHostGetDevicePointer(reinterpret_cast<void**>(&status_dev), h->host_error, 0), "hipHostGetDevicePointer"))) return rc;
-
-    // profiling (off by default): an event after every launch on this lane's stream; the intervals are attributed to the
-    // kernel classes after the whole batch has been enqueued (prof_collect), which then ends with a synchronisation
-    mdgat_handle::ProfLane& pl = h->prof[lane];
-    auto mark = [&](int cls) {
-        if (!h->prof_on) return;
-        if (pl.n == pl.ev.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            pl.ev.push_back(e);
-        }
-        (void)hipEventRecord(pl.ev[pl.n++], s);
-        pl.cls.push_back(cls);
-    };
-    mark(-1);
-
-    const Qkv16 q16 = mdgat_qkv16_carve(ws.qkv16, B, N, M);
-    if ((N & 31) || (M & 31))   // the attention kernel reads V^T in whole 32-key blocks: pad columns must be zero
-        if ((rc = mdgat_check_hip(hipMemsetAsync(q16.vt16, 0, (size_t)B * 256 * q16.PP * sizeof(_Float16), s), "memset(V^T pads)"))) return rc;
-    int first = 0;              // the first propagation layer the fp32-class kernels run
-    bool tail64 = false;        // MDGAT_ARITH_FP64: final_proj, scores, Sinkhorn and the extraction's arg-maxes in fp64 too
-    if (!f64) {
-        // ---- encoders (mdgat.py:392-393), one fused launch ----
-        EncoderLaunch e{};
-        e.kpts0 = kpts0; e.sigma0 = sigma0; e.fpfh0 = fpfh0; e.kpts1 = kpts1; e.sigma1 = sigma1; e.fpfh1 = fpfh1;
-        e.rec0 = rec0; e.rec1 = rec1; e.normalize = normalize_fpfh;
-        e.w = w; e.bl = &bl; e.es = h->wsplit + WS_LAYER * (size_t)L2 + WS_FINAL;
-        e.x = ws.x; e.B = B; e.N = N; e.M = M;
-        if ((rc = launch_encoder(e, s))) return rc;
-        mark(MDGAT_PROF_ENCODER);
-        if (taps && taps->x_enc)
-            if ((rc = mdgat_check_hip(hipMemcpyAsync(taps->x_enc, ws.x, (size_t)R * 128 * sizeof(float), hipMemcpyDeviceToDevice, s), "tap x_enc"))) return rc;
-    } else {
-        // ---- MDGAT_ARITH_FP64 (f64.hip): encoders and the layers up to the last dynamic one in the reference's arithmetic ----
-        const double* w64 = h->weights64;
-        const size_t Rz = (size_t)R;
-        // (the forward's launches of kernels whose workgroups wait for each other - clustered layer tails, the resident fp64 Sinkhorn - as
-        // one group of the device's chain: coop_chain.hpp)
-        CoopGroup coop_group;
-        if ((rc = coop_group.open(h->device, s))) return rc;
-        auto gemm = [&](const double* A0, int lda0, int K0, const double* A1, int lda1, size_t wofs, size_t bofs, int relu, const double* Rs, double* C, int ldc,
-                        int cout, int K) {
-            GemmF64Args g{A0, lda0, K0, A1, lda1, w64 + wofs, K, w64 + bofs, Rs, ldc, C, ldc, R, cout, K, relu, status_dev + MDGAT_STATUS_RANGE};
-            return launch_gemm_f64(g, s);
-        };
-        // the assembled inputs at the END of the hidden area (the fused encoder writes layer 0's q | k | v while other workgroups still
-        // read their inputs); the stages of the one-product-per-launch form in the (contiguous) q|k|v + hidden area in front of them:
-        // 32 + 64 + 128 + 64 + 128 = 416 of the 603 doubles per point there
-        double* in4 = ws.hid64 + Rz * (256 - 37);
-        double* in33 = in4 + Rz * 4;
-        double* hk1 = ws.qkv64;
-        double* hk2 = hk1 + Rz * 32;
-        double* hk3 = hk2 + Rz * 64;
-        double* hd1 = hk3 + Rz * 128;
-        double* hd2 = hd1 + Rz * 64;
-        if (in.rec0) rc = launch_assemble_frames_f64(B, N, M, in.rec0, in.rec1, normalize_fpfh, in4, in33, status_dev + MDGAT_STATUS_RANGE, s);
-        else rc = launch_assemble_f64(B, N, M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, status_dev + MDGAT_STATUS_RANGE, s);
-        if (rc) return rc;
-        mark(MDGAT_PROF_F64_OTHER);
-        first = f64_layer_count(h->cfg);
-        // The TAIL in fp64 as well (mdgat_config.f64_sinkhorn; round 6): every layer, final_proj, the score matrix and the optimal
-        // transport in the reference's own arithmetic, every arg-max of the extraction decided on the fp64 Z (sinkhorn_f64.hip).  With
-        // the fp32-class tail Z is good to 7e-6 - inside the bar of 1e-4, but among 40 960 arg-maxes of a reference-held batch one had
-        // its two candidates 1.3e-6 apart and fell the other way (profiles/NOTES_r6.md section 11).
-        if (h->cfg.f64_sinkhorn > 0 && !ws.sk64_bytes) {
-            mdgat_set_error("mdgat_forward_f64: f64_sinkhorn = 1 and %d x %d keypoints are beyond the fp64 Sinkhorn kernels (2175)", N, M);
-            return MDGAT_ERR_UNSUPPORTED;
-        }
-        tail64 = h->cfg.f64_sinkhorn >= 0 && ws.sk64_bytes != 0 && h->cfg.f64_layers == 0;
-        if (tail64) first = L2;
-        // The tail of a layer - mlp.0 + ReLU, mlp.3 + residual (mdgat.py:246-248, 274) - and the NEXT layer's q | k | v projection
-        // (227-232) run as one launch (layer_f64.hip), the hidden activation never leaving the chip, and so do the two encoders with
-        // layer 0's projection; the last fp64 launch also writes the fp32 rounding of x, the hand-over.  mdgat_set_f64_layer_fusion(0)
-        // keeps the one-product-per-launch form (bit-identical).
-        const bool fused = layer_f64_fused() && h->wfrag64;
-        bool handed_over = false;
-        // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
-        if (fused) {
-            const double* ef = h->wfrag64 + layer_f64_frag_doubles() * (size_t)L2;
-            const double* f_k0 = ef;
-            const double* f_d0 = f_k0 + frag64_doubles(32, 4);
-            const double* f_k1 = f_d0 + frag64_doubles(64, 33);
-            const double* f_k2 = f_k1 + frag64_doubles(64, 32);
-            const double* f_d1 = f_k2 + frag64_doubles(128, 64);
-            const double* f_l = f_d1 + frag64_doubles(128, 64);
-            const EncoderF64Args e{in4, in33, f_k0, w64 + bl.kenc0_b, f_d0, w64 + bl.denc0_b, f_k1, w64 + bl.kenc1_b, f_k2, w64 + bl.kenc2_b,
-                                   f_d1, w64 + bl.denc1_b, f_l, w64 + bl.encl_b,
-                                   first > 0 ? h->wfrag64 + WF64_QKV : nullptr, first > 0 ? w64 + bl.layer0 + bl.qkv_b : nullptr,
-                                   ws.x64, ws.qkv64,
-                                   first == 0 ? ws.x : nullptr, R, status_dev + MDGAT_STATUS_RANGE};
-            if ((rc = launch_encoder_f64(e, s))) return rc;
-            handed_over = first == 0;
-        } else {
-            if ((rc = gemm(in4, 4, 4, nullptr, 0, bl.kenc0_w, bl.kenc0_b, 1, nullptr, hk1, 32, 32, 4))) return rc;
-            if ((rc = gemm(hk1, 32, 32, nullptr, 0, bl.kenc1_w, bl.kenc1_b, 1, nullptr, hk2, 64, 64, 32))) return rc;
-            if ((rc = gemm(hk2, 64, 64, nullptr, 0, bl.kenc2_w, bl.kenc2_b, 1, nullptr, hk3, 128, 128, 64))) return rc;
-            if ((rc = gemm(in33, 33, 33, nullptr, 0, bl.denc0_w, bl.denc0_b, 1, nullptr, hd1, 64, 64, 33))) return rc;
-            if ((rc = gemm(hd1, 64, 64, nullptr, 0, bl.denc1_w, bl.denc1_b, 1, nullptr, hd2, 128, 128, 64))) return rc;
-            if ((rc = gemm(hd2, 128, 128, hk3, 128, bl.encl_w, bl.encl_b, 0, nullptr, ws.x64, 128, 128, 256))) return rc;
-        }
-        mark(MDGAT_PROF_F64_GEMM);
-        if (taps && taps->x_enc)
-            if ((rc = launch_f64_to_f32(ws.x64, taps->x_enc, Rz * 128, nullptr, s))) return rc;
-        for (int i = 0; i < first; ++i) {
-            const size_t lo = bl.layer0 + (size_t)i * bl.layer_stride;
-            // MultiHeadedAttention (mdgat.py:223-237; merge is folded into mlp.0 by pack.py), attention / dynamic_attention (190-210)
-            if (!fused) {
-                if ((rc = gemm(ws.x64, 128, 128, nullptr, 0, lo + bl.qkv_w, lo + bl.qkv_b, 0, nullptr, ws.qkv64, 384, 384, 128))) return rc;
-                mark(MDGAT_PROF_F64_GEMM);
-            }
-            uint32_t* sel = (taps && taps->topk_sel) ? taps->topk_sel + (size_t)i * mdgat_topk_sel_words(B, N, M) : nullptr;
-            if ((rc = launch_attention_f64(B, N, M, i & 1, h->cfg.topk[i], ws.qkv64, ws.msg64, sel, s, status_dev + MDGAT_STATUS_RANGE))) return rc;
-            mark(h->cfg.topk[i] > 0 ? MDGAT_PROF_F64_ATTENTION_TOPK : MDGAT_PROF_F64_ATTENTION_FULL);
-            // AttentionalPropagation + residual (mdgat.py:246-248, 274)
-            if (fused) {
-                const double* lf = h->wfrag64 + layer_f64_frag_doubles() * (size_t)i;
-                const bool last = i + 1 == first;
-                const LayerF64Args t{ws.x64, ws.msg64, lf + WF64_W1, w64 + lo + bl.mlp1_b, lf + WF64_W2, w64 + lo + bl.mlp2_b,
-                                     last ? nullptr : lf + layer_f64_frag_doubles() + WF64_QKV, last ? nullptr : w64 + lo + bl.layer_stride + bl.qkv_b,
-                                     ws.qkv64, last ? ws.x : nullptr, R, status_dev + MDGAT_STATUS_RANGE, ws.hid64};
-                if ((rc = launch_layer_tail_f64(t, coop_group))) return rc;
-                handed_over = last;
-            } else {
-                if ((rc = gemm(ws.x64, 128, 128, ws.msg64, 128, lo + bl.mlp1_w, lo + bl.mlp1_b, 1, nullptr, ws.hid64, 256, 256, 256))) return rc;
-                if ((rc = gemm(ws.hid64, 256, 256, nullptr, 0, lo + bl.mlp2_w, lo + bl.mlp2_b, 0, ws.x64, ws.x64, 128, 128, 256))) return rc;
-            }
-            mark(MDGAT_PROF_F64_GEMM);
-            if (taps && taps->x_layers)
-                if ((rc = launch_f64_to_f32(ws.x64, taps->x_layers + (size_t)i * Rz * 128, Rz * 128, nullptr, s))) return rc;
-        }
-        if (tail64) {
-            // final_proj (mdgat.py:397), the score matrix (430-431), the optimal transport (434-436) and the extraction (441-483)
-            double* mdesc64 = ws.msg64;          // (the message and q | k | v of the last layer are dead)
-            double* scores64 = ws.scores64;      // [B][N][M]: in q | k | v's room while N M <= 384 (N + M)
-            if ((rc = gemm(ws.x64, 128, 128, nullptr, 0, bl.final_w, bl.final_b, 0, nullptr, mdesc64, 128, 128, 128))) return rc;
-            if (taps && taps->mdesc)
-                if ((rc = launch_f64_to_f32(mdesc64, taps->mdesc, Rz * 128, nullptr, s))) return rc;
-            GemmF64Args sg{mdesc64, 128, 128, nullptr, 0, mdesc64 + (size_t)N * 128, 128, nullptr, nullptr, 0, scores64, M, N, M, 128, 0, status_dev + MDGAT_STATUS_RANGE};
-            sg.scale = 0.08838834764831845;      // 1 / sqrt(128)
-            sg.batch = B; sg.sA = sg.sW = (long long)(N + M) * 128; sg.sC = (long long)N * M;
-            if ((rc = launch_gemm_f64(sg, s))) return rc;
-            mark(MDGAT_PROF_F64_GEMM);
-            if (taps && taps->scores)
-                if ((rc = launch_f64_to_f32(scores64, taps->scores, (size_t)B * N * M, nullptr, s))) return rc;
-            const size_t kb = sinkhorn_f64_workspace_bytes(B, N, M);
-            char* bw = reinterpret_cast<char*>(ws.sk64) + kb;
-            auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-            int* ri = reinterpret_cast<int*>(bw); bw += al((size_t)B * N * 4);
-            float* rv = reinterpret_cast<float*>(bw); bw += al((size_t)B * N * 4);
-            int* ci = reinterpret_cast<int*>(bw); bw += al((size_t)B * M * 4);
-            float* cv = reinterpret_cast<float*>(bw);
-            const SkExtract ex64{h->cfg.extract_mode, h->cfg.match_threshold, matches0, matches1, mscores0, mscores1, defer_alldust,
-                                 status_dev + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
-            if ((rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, h->cfg.sinkhorn_iters, Z64, Z, h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, ri, rv, ci, cv,
-                                          ws.sk64, kb, status_dev + MDGAT_STATUS_RANGE, coop_group, w64 + bl.bin_score))) return rc;
-            if ((rc = launch_extract_from_bests(B, N, M, &ex64, ri, rv, ci, cv, s))) return rc;
-            mark(MDGAT_PROF_SINKHORN);
-            if (loss_req) {
-                // the loss (mdgat.py:486-594) on the fp64 Z; its time is attributed to no class
-                if ((rc = launch_loss(B, N, M, static_cast<const double*>(Z64), loss_req->gt0, loss_req->gt1, loss_req->method, loss_req->gamma,
-                                      loss_req->loss, loss_req->bad_index, loss_ws, loss_ws_bytes, s))) return rc;
-                mark(-1);
-            }
-            return MDGAT_OK;
-        }
-        // hand-over: nothing behind the last dynamic layer is discontinuous
-        if (!handed_over) {
-            if ((rc = launch_f64_to_f32(ws.x64, ws.x, Rz * 128, status_dev + MDGAT_STATUS_RANGE, s))) return rc;
-            mark(MDGAT_PROF_F64_OTHER);
-        }
-    }
-
-    // ---- 2L attentional propagation layers (mdgat.py:259-276) ----
-    // launch i: [attention of layer i] -> [mlp + residual of layer i | q/k/v of layer i + 1 (or final_proj)]
-    float* mdesc = ws.hid;
-    const _Float16* wfinal = h->wsplit + WS_LAYER * (size_t)L2;
-    const _Float16* wfrag = h->wsplit + wsplit_halves(h->cfg.L);      // fragment-order copies (layer_split.hip)
-    const _Float16* ffinal = wfrag + WF_LAYER * (size_t)L2;
-    {
-        LayerLaunch p{};
-        p.x = ws.x; p.R = R; p.N = N; p.M = M; p.out = q16; p.mdesc = mdesc; p.do_mlp = 0; p.guard = status_dev + MDGAT_STATUS_RANGE;
-        if (first < L2) { p.mode3 = 1; p.w3s = h->wsplit + WS_LAYER * (size_t)first + WS_QKV; p.w3f = wfrag + WF_LAYER * (size_t)first + WF_QKV; p.b3 = w + bl.layer0 + (size_t)first * bl.layer_stride + bl.qkv_b; }
-        else { p.mode3 = 2; p.w3s = wfinal; p.w3f = ffinal; p.b3 = w + bl.final_b; }
-        if ((rc = launch_layer(p, s))) return rc;
-        mark(MDGAT_PROF_LAYER_FIRST);
-    }
-    for (int i = first; i < L2; ++i) {
-        const float* lw = w + bl.layer0 + (size_t)i * bl.layer_stride;
-        const _Float16* ls = h->wsplit + WS_LAYER * (size_t)i;
-        const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
-        uint32_t* sel = (taps && taps->topk_sel) ? taps->topk_sel + (size_t)i * mdgat_topk_sel_words(B, N, M) : nullptr;
-        const int kk = h->cfg.topk[i];
-        if ((rc = launch_attention(B, N, M, cross, kk, q16, ws.msg, s, h->cfg.attention_mode, sel))) return rc;
-        mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
-        LayerLaunch p{};
-        p.x = ws.x; p.msg = ws.msg; p.R = R; p.N = N; p.M = M; p.out = q16; p.mdesc = mdesc; p.do_mlp = 1; p.guard = status_dev + MDGAT_STATUS_RANGE;
-        p.w1s = ls + WS_W1; p.b1 = lw + bl.mlp1_b; p.w2s = ls + WS_W2; p.b2 = lw + bl.mlp2_b;
-        const _Float16* lf = wfrag + WF_LAYER * (size_t)i;
-        p.w1f = lf + WF_W1; p.w2f = lf + WF_W2;
-        if (i + 1 < L2) { p.mode3 = 1; p.w3s = ls + WS_LAYER + WS_QKV; p.w3f = lf + WF_LAYER + WF_QKV; p.b3 = lw + bl.layer_stride + bl.qkv_b; }
-        else { p.mode3 = 2; p.w3s = wfinal; p.w3f = ffinal; p.b3 = w + bl.final_b; }
-        if ((rc = launch_layer(p, s))) return rc;
-        mark(i + 1 < L2 ? MDGAT_PROF_LAYER : MDGAT_PROF_LAYER_LAST);
-        if (taps && taps->x_layers)
-            if ((rc = mdgat_check_hip(hipMemcpyAsync(taps->x_layers + (size_t)i * R * 128, ws.x, (size_t)R * 128 * sizeof(float), hipMemcpyDeviceToDevice, s), "tap x_layers"))) return rc;
-    }
-
-    // ---- final projection (mdgat.py:397, computed by the last launch above) and score matrix (430-431) ----
-    if (taps && taps->mdesc)
-        if ((rc = mdgat_check_hip(hipMemcpyAsync(taps->mdesc, mdesc, (size_t)R * 128 * sizeof(float), hipMemcpyDeviceToDevice, s), "tap mdesc"))) return rc;
-    // (the score kernel also clears the exchange slots of the Sinkhorn kernel that follows: no memset launch in between)
-    const size_t sk_clear = ws.sk_bytes ? sinkhorn_slots_clear_bytes(B, N, M) : 0;
-    if ((rc = launch_scores(B, N, M, mdesc, ws.scores, 0.08838834764831845f /* 1 / sqrt(128) */, s, sk_clear ? ws.sk : nullptr, sk_clear,
-                            status_dev + MDGAT_STATUS_RANGE))) return rc;
-    mark(MDGAT_PROF_SCORES);
-    if (taps && taps->scores)
-        if ((rc = mdgat_check_hip(hipMemcpyAsync(taps->scores, ws.scores, (size_t)B * N * M * sizeof(float), hipMemcpyDeviceToDevice, s), "tap scores"))) return rc;
-
-    // ---- optimal transport (mdgat.py:434-436) and match extraction (441-483) ----
-    // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
-    const bool fused = ws.sk_bytes != 0;   // N, M <= 2048: the cluster kernel, arg-maxes fused
-    float* Zout = Z ? Z : (fused && !loss_req ? nullptr : ws.Z);
-    const SkExtract ex{h->cfg.extract_mode, h->cfg.match_threshold, matches0, matches1, mscores0, mscores1, defer_alldust,
-                       status_dev + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
-    if ((rc = launch_sinkhorn(B, N, M, ws.scores, w + bl.bin_score, 0.f, h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, s, status_dev,
-                              Z ? Z : ws.Z, sk_clear != 0))) return rc;
-    mark(MDGAT_PROF_SINKHORN);
-    if (loss_req) {
-        // the loss (mdgat.py:486-594) on the fp32 Z, widened to fp64; its time is attributed to no class
-        if ((rc = launch_loss(B, N, M, static_cast<const float*>(Zout), loss_req->gt0, loss_req->gt1, loss_req->method, loss_req->gamma,
-                              loss_req->loss, loss_req->bad_index, loss_ws, loss_ws_bytes, s))) return rc;
-        mark(-1);
-    }
-    return MDGAT_OK;
-}
-
-// profiling: wait for the events of both lanes and add the intervals between consecutive ones to their kernel classes
-// (an interval that starts at a -1 mark - the beginning of a forward_impl call - is counted, one that ends there is not)
-static int prof_collect(mdgat_handle* h) {
-    if (!h->prof_on) return MDGAT_OK;
-    for (auto& pl : h->prof) {
-        if (pl.n > 1) {
-            if (int rc = mdgat_check_hip(hipEventSynchronize(pl.ev[pl.n - 1]), "profile sync")) return rc;
-            for (size_t i = 1; i < pl.n; ++i) {
-                float ms = 0.f;
-                if (pl.cls[i] >= 0 && hipEventElapsedTime(&ms, pl.ev[i - 1], pl.ev[i]) == hipSuccess) {
-                    h->prof_ms[pl.cls[i]] += ms;
-                    h->prof_launches[pl.cls[i]] += 1;
-                }
-            }
-        }
-        pl.n = 0;
-        pl.cls.clear();
-    }
-    return MDGAT_OK;
 }
 
 // Batches run in slices on two lanes.  Pairs are independent.  (i) A slice of ~64 pairs fills the part (512 tiles of the
@@ -713,7 +396,7 @@ static int prof_collect(mdgat_handle* h) {
 // Taps (whole-batch layouts) run unsliced; mdgat_set_lanes(h, 1) / MDGAT_FORWARD_LANES=1 keeps everything on the caller's stream
 // (slices of 65 536 keypoints beyond 1.5 x that).
 struct LanePlan { int nslices, per, lanes; size_t lane_bytes; };
-static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss = false) {
+static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss) {
     static const long env_points = [] { const char* e = getenv("MDGAT_FORWARD_SLICE_POINTS"); return e ? atol(e) : -1L; }();   // unset: defaults; 0: never slice
     LanePlan p{1, B, 1, 0};
     const long per_pair = (long)N + M;
@@ -737,7 +420,7 @@ static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss = 
         p.per = (int)((B + n - 1) / n);
         p.nslices = (B + p.per - 1) / p.per;
     }
-    p.lane_bytes = al256(carve(nullptr, p.per, N, M, f64).total * sizeof(float)) + (loss ? loss_extra_bytes(p.per, N, M, f64) : 0);
+    p.lane_bytes = carve(nullptr, p.per, N, M, f64, loss).total;
     return p;
 }
 
@@ -745,8 +428,7 @@ static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool l
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     // (taps run unsliced: the whole batch's workspace is the lower bound in every case)
     const bool f64 = h && h->cfg.arithmetic == MDGAT_ARITH_FP64;
-    const size_t carved = carve(nullptr, B, N, M, f64).total * sizeof(float);
-    const size_t whole = loss ? al256(carved) + loss_extra_bytes(B, N, M, f64) : carved;
+    const size_t whole = carve(nullptr, B, N, M, f64, loss).total;
     const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
@@ -761,22 +443,352 @@ extern "C" int mdgat_set_lanes(mdgat_handle* h, int lanes) {
     return MDGAT_OK;
 }
 
-static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
-                           int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
-                           const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream,
-                           const mdgat_loss_request* loss_req = nullptr) {
-    LanePlan p{1, B, 1, 0};
+// How a call runs, decided once for all its slices.
+struct Path {
+    bool f64;         // MDGAT_ARITH_FP64 (f64.hip): the inputs, encoders and leading layers in the reference's arithmetic
+    int first;        // the first propagation layer the fp32-class kernels run (2L: none)
+    bool tail64;      // MDGAT_ARITH_FP64: final_proj, scores, Sinkhorn and the extraction's arg-maxes in fp64 too
+    bool fused64;     // the fp64 encoders and layer tails as fused launches, the last one writing the hand-over to fp32
+    bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
+    LanePlan lanes;
+};
+
+// Every check of a forward call, before anything is enqueued, and its Path.
+static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, const FwdOut& out, const mdgat_taps* taps,
+                        const void* workspace, size_t workspace_bytes, Path& p) {
     if (!h) { mdgat_set_error("mdgat_forward: null handle"); return MDGAT_ERR_BAD_ARG; }
-    if (loss_req) {
-        // refused before anything is enqueued
-        const int lm = loss_req->method;
+    if (out.loss) {
+        const int lm = out.lr.method;
         if (lm != MDGAT_LOSS_SUPERGLUE && lm != MDGAT_LOSS_TRIPLET && lm != MDGAT_LOSS_GAP) { mdgat_set_error("mdgat_forward_loss: bad method %d", lm); return MDGAT_ERR_BAD_ARG; }
-        if (!loss_req->gt0 || !loss_req->gt1 || !loss_req->loss) { mdgat_set_error("mdgat_forward_loss: null pointer in the loss request"); return MDGAT_ERR_BAD_ARG; }
+        if (!out.lr.gt0 || !out.lr.gt1 || !out.lr.loss) { mdgat_set_error("mdgat_forward_loss: null pointer in the loss request"); return MDGAT_ERR_BAD_ARG; }
         if (lm != MDGAT_LOSS_GAP && N != M) {
             mdgat_set_error("mdgat_forward_loss: the superglue and triplet losses need N == M (N=%d M=%d), as the reference's do", N, M);
             return MDGAT_ERR_BAD_ARG;
         }
     }
+    // fp64 inputs, or raw float32 records on a handle that computes in fp64 (the loader's own sequence: float32 records, FPFH
+    // normalised in float32, widened to double - load_data.py:146-165, 290-295); past these checks, exactly on an exact-mode handle
+    const bool f64 = in.dk0 != nullptr || (in.rec0 != nullptr && h->cfg.arithmetic == MDGAT_ARITH_FP64);
+    if (!h->loaded) { mdgat_set_error("mdgat_forward: weights not loaded"); return MDGAT_ERR_NO_WEIGHTS; }
+    if (f64 && (h->cfg.arithmetic != MDGAT_ARITH_FP64 || !h->loaded64)) {
+        mdgat_set_error("mdgat_forward_f64: the handle needs MDGAT_ARITH_FP64 and mdgat_load_weights_f64");
+        return h->cfg.arithmetic != MDGAT_ARITH_FP64 ? MDGAT_ERR_BAD_ARG : MDGAT_ERR_NO_WEIGHTS;
+    }
+    if (!f64 && h->cfg.arithmetic == MDGAT_ARITH_FP64) {
+        mdgat_set_error("mdgat_forward: this handle computes in fp64 (MDGAT_ARITH_FP64): call mdgat_forward_f64 with fp64 inputs");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    if (static_cast<volatile unsigned*>(h->host_error)[MDGAT_STATUS_RANGE]) {
+        // the forward is asynchronous: what an earlier launch found surfaces here unless the caller asked first
+        // (mdgat_async_status after its own synchronisation - MDGAT.forward does)
+        h->host_error[MDGAT_STATUS_RANGE] = 0;
+        mdgat_set_error("mdgat_forward: a previous call on this handle met activations outside the f16 operand range (|v| >= 6e4; fp64 "
+                        "layers of the exact mode: |v| >= 2^500) or non-finite values; its outputs are invalid");
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (B <= 0 || N <= 0 || M <= 0) { mdgat_set_error("mdgat_forward: empty batch/keypoints (B=%d N=%d M=%d) must be handled by the caller", B, N, M); return MDGAT_ERR_BAD_ARG; }
+    const bool arrays = in.kpts0 && in.sigma0 && in.fpfh0 && in.kpts1 && in.sigma1 && in.fpfh1;
+    const bool arrays64 = in.dk0 && in.ds0 && in.df0 && in.dk1 && in.ds1 && in.df1;
+    if ((!arrays && !(in.rec0 && in.rec1) && !arrays64) || !out.matches0 || !out.matches1 || !out.mscores0 || !out.mscores1 || !workspace) {
+        mdgat_set_error("mdgat_forward: null pointer argument");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    p.lanes = taps ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
+    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss).total;
+    if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
+    const int L2 = 2 * h->cfg.L;
+    for (int i = 0; i < L2; ++i) {
+        const int k = h->cfg.topk[i];
+        if (k > 0 && (k > N || k > M)) {   // torch.topk raises (mdgat.py:202)
+            mdgat_set_error("layer %d: dynamic attention k=%d exceeds the number of keys (N=%d, M=%d)", i, k, N, M);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    }
+    // The TAIL in fp64 as well (mdgat_config.f64_sinkhorn; round 6): every layer, final_proj, the score matrix and the optimal
+    // transport in the reference's own arithmetic, every arg-max of the extraction decided on the fp64 Z (sinkhorn_f64.hip).  With
+    // the fp32-class tail Z is good to 7e-6 - inside the bar of 1e-4, but among 40 960 arg-maxes of a reference-held batch one had
+    // its two candidates 1.3e-6 apart and fell the other way (profiles/NOTES_r6.md section 11).
+    if (f64 && h->cfg.f64_sinkhorn > 0 && !sinkhorn_f64_supported(N, M)) {
+        mdgat_set_error("mdgat_forward_f64: f64_sinkhorn = 1 and %d x %d keypoints are beyond the fp64 Sinkhorn kernels (2175)", N, M);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    p.f64 = f64;
+    p.tail64 = f64 && h->cfg.f64_sinkhorn >= 0 && sinkhorn_f64_supported(N, M) && h->cfg.f64_layers == 0;
+    p.first = p.tail64 ? L2 : f64 ? f64_layer_count(h->cfg) : 0;
+    // The tail of a layer - mlp.0 + ReLU, mlp.3 + residual (mdgat.py:246-248, 274) - and the NEXT layer's q | k | v projection
+    // (227-232) run as one launch (layer_f64.hip), the hidden activation never leaving the chip, and so do the two encoders with
+    // layer 0's projection; the last fp64 launch also writes the fp32 rounding of x, the hand-over.  mdgat_set_f64_layer_fusion(0)
+    // keeps the one-product-per-launch form (bit-identical).
+    p.fused64 = f64 && layer_f64_fused() && h->wfrag64;
+    p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
+    return MDGAT_OK;
+}
+
+// What the stages of one forward share: a slice of the call on one lane.
+struct Fwd {
+    const mdgat_handle* h;
+    const Path& p;
+    int B, N, M, R;
+    Workspace ws;
+    Qkv16 q16;               // ws.qkv16 in the attention kernel's layout
+    hipStream_t s;
+    unsigned* status;        // the handle's status words (device view)
+    mdgat_taps taps;         // all null when the call has none
+    mdgat_handle::ProfLane& pl;
+    int defer_alldust;       // a slice: the batch-wide rule is applied after the last one
+    unsigned* guard() const { return status + MDGAT_STATUS_RANGE; }
+    // profiling (off by default): an event after every launch on this lane's stream; the intervals are attributed to the
+    // kernel classes after the whole batch has been enqueued (prof_collect), which then ends with a synchronisation
+    void mark(int cls) {
+        if (!h->prof_on) return;
+        if (pl.n == pl.ev.size()) {
+            hipEvent_t e;
+            if (hipEventCreate(&e) != hipSuccess) return;
+            pl.ev.push_back(e);
+        }
+        (void)hipEventRecord(pl.ev[pl.n++], s);
+        pl.cls.push_back(cls);
+    }
+    // a tap (to == nullptr: not asked for): fp32 stages copied, fp64 ones rounded to fp32
+    int tap(float* to, const float* from, size_t n, const char* what) const { return to ? mdgat_check_hip(hipMemcpyAsync(to, from, n * sizeof(float), hipMemcpyDeviceToDevice, s), what) : MDGAT_OK; }
+    int tap(float* to, const double* from, size_t n) const { return to ? launch_f64_to_f32(from, to, n, nullptr, s) : MDGAT_OK; }
+    float* x_tap(int layer) const { return taps.x_layers ? taps.x_layers + (size_t)layer * R * 128 : nullptr; }
+    uint32_t* sel_tap(int layer) const { return taps.topk_sel ? taps.topk_sel + (size_t)layer * mdgat_topk_sel_words(B, N, M) : nullptr; }
+    SkExtract extract(const FwdOut& o) const {
+        return SkExtract{h->cfg.extract_mode, h->cfg.match_threshold, o.matches0, o.matches1, o.mscores0, o.mscores1, defer_alldust,
+                         status + MDGAT_STATUS_MATCHED + (h->match_token % MDGAT_MATCH_SLOTS), h->match_token};
+    }
+    // the loss (mdgat.py:486-594) on the tail's Z, fp64 or fp32 widened to fp64, if the call asked for it; its time is attributed to no class
+    template <typename T> int loss(const FwdOut& o, const T* Z) {
+        if (!o.loss) return MDGAT_OK;
+        if (int rc = launch_loss(B, N, M, Z, o.lr.gt0, o.lr.gt1, o.lr.method, o.lr.gamma, o.lr.loss, o.lr.bad_index, ws.loss, ws.loss_bytes, s)) return rc;
+        mark(-1);
+        return MDGAT_OK;
+    }
+    // an fp64 product over all R rows with the blob's weights at wofs / bofs (GemmF64Args)
+    int gemm64(const double* A0, int lda0, int K0, const double* A1, int lda1, size_t wofs, size_t bofs, int relu, const double* Rs, double* C,
+               int ldc, int cout, int K) const {
+        const GemmF64Args g{A0, lda0, K0, A1, lda1, h->weights64 + wofs, K, h->weights64 + bofs, Rs, ldc, C, ldc, R, cout, K, relu, guard()};
+        return launch_gemm_f64(g, s);
+    }
+};
+
+// ---- encoders (mdgat.py:392-393), one fused launch ----
+static int encoders32(Fwd& f, const FwdIn& in) {
+    EncoderLaunch e{};
+    e.kpts0 = in.kpts0; e.sigma0 = in.sigma0; e.fpfh0 = in.fpfh0; e.kpts1 = in.kpts1; e.sigma1 = in.sigma1; e.fpfh1 = in.fpfh1;
+    e.rec0 = in.rec0; e.rec1 = in.rec1; e.normalize = in.normalize_fpfh;
+    e.w = f.h->weights; e.bl = &f.h->bl; e.es = f.h->wsplit + WS_LAYER * (size_t)(2 * f.h->cfg.L) + WS_FINAL;
+    e.x = f.ws.x; e.B = f.B; e.N = f.N; e.M = f.M;
+    if (int rc = launch_encoder(e, f.s)) return rc;
+    f.mark(MDGAT_PROF_ENCODER);
+    return f.tap(f.taps.x_enc, f.ws.x, (size_t)f.R * 128, "tap x_enc");
+}
+
+// ---- MDGAT_ARITH_FP64 (f64.hip): the inputs, the encoders and the layers before p.first in the reference's arithmetic ----
+static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
+    const Workspace& ws = f.ws;
+    const BlobLayout& bl = f.h->bl;
+    const double* w64 = f.h->weights64;
+    const size_t Rz = (size_t)f.R;
+    const int first = f.p.first;
+    // the assembled inputs at the END of the hidden area (the fused encoder writes layer 0's q | k | v while other workgroups still
+    // read their inputs); the stages of the one-product-per-launch form in the (contiguous) q|k|v + hidden area in front of them:
+    // 32 + 64 + 128 + 64 + 128 = 416 of the 603 doubles per point there
+    double* in4 = ws.hid64 + Rz * (256 - 37);
+    double* in33 = in4 + Rz * 4;
+    if (int rc = in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
+                         : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s)) return rc;
+    f.mark(MDGAT_PROF_F64_OTHER);
+    // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
+    if (f.p.fused64) {
+        const EncoderF64Frags ef = encoder_f64_frags();
+        const double* fr = f.h->wfrag64 + layer_f64_frag_doubles() * (size_t)(2 * f.h->cfg.L);
+        const EncoderF64Args e{in4, in33, fr + ef.k0.ofs, w64 + bl.kenc0_b, fr + ef.d0.ofs, w64 + bl.denc0_b, fr + ef.k1.ofs, w64 + bl.kenc1_b,
+                               fr + ef.k2.ofs, w64 + bl.kenc2_b, fr + ef.d1.ofs, w64 + bl.denc1_b, fr + ef.l.ofs, w64 + bl.encl_b,
+                               first > 0 ? f.h->wfrag64 + WF64_QKV : nullptr, first > 0 ? w64 + bl.layer0 + bl.qkv_b : nullptr,
+                               ws.x64, ws.qkv64, first == 0 ? ws.x : nullptr, f.R, f.guard()};
+        if (int rc = launch_encoder_f64(e, f.s)) return rc;
+    } else {
+        double *hk1 = ws.qkv64, *hk2 = hk1 + Rz * 32, *hk3 = hk2 + Rz * 64;      // the keypoint encoder's stages
+        double *hd1 = hk3 + Rz * 128, *hd2 = hd1 + Rz * 64;                       // the descriptor encoder's
+        if (int rc = f.gemm64(in4, 4, 4, nullptr, 0, bl.kenc0_w, bl.kenc0_b, 1, nullptr, hk1, 32, 32, 4)) return rc;
+        if (int rc = f.gemm64(hk1, 32, 32, nullptr, 0, bl.kenc1_w, bl.kenc1_b, 1, nullptr, hk2, 64, 64, 32)) return rc;
+        if (int rc = f.gemm64(hk2, 64, 64, nullptr, 0, bl.kenc2_w, bl.kenc2_b, 1, nullptr, hk3, 128, 128, 64)) return rc;
+        if (int rc = f.gemm64(in33, 33, 33, nullptr, 0, bl.denc0_w, bl.denc0_b, 1, nullptr, hd1, 64, 64, 33)) return rc;
+        if (int rc = f.gemm64(hd1, 64, 64, nullptr, 0, bl.denc1_w, bl.denc1_b, 1, nullptr, hd2, 128, 128, 64)) return rc;
+        if (int rc = f.gemm64(hd2, 128, 128, hk3, 128, bl.encl_w, bl.encl_b, 0, nullptr, ws.x64, 128, 128, 256)) return rc;
+    }
+    f.mark(MDGAT_PROF_F64_GEMM);
+    if (int rc = f.tap(f.taps.x_enc, ws.x64, Rz * 128)) return rc;
+    for (int i = 0; i < first; ++i) {
+        const size_t lo = bl.layer0 + (size_t)i * bl.layer_stride;
+        // MultiHeadedAttention (mdgat.py:223-237; merge is folded into mlp.0 by pack.py), attention / dynamic_attention (190-210)
+        if (!f.p.fused64) {
+            if (int rc = f.gemm64(ws.x64, 128, 128, nullptr, 0, lo + bl.qkv_w, lo + bl.qkv_b, 0, nullptr, ws.qkv64, 384, 384, 128)) return rc;
+            f.mark(MDGAT_PROF_F64_GEMM);
+        }
+        const int kk = f.h->cfg.topk[i];
+        if (int rc = launch_attention_f64(f.B, f.N, f.M, i & 1, kk, ws.qkv64, ws.msg64, f.sel_tap(i), f.s, f.guard())) return rc;
+        f.mark(kk > 0 ? MDGAT_PROF_F64_ATTENTION_TOPK : MDGAT_PROF_F64_ATTENTION_FULL);
+        // AttentionalPropagation + residual (mdgat.py:246-248, 274)
+        if (f.p.fused64) {
+            const double* lf = f.h->wfrag64 + layer_f64_frag_doubles() * (size_t)i;
+            const bool last = i + 1 == first;
+            const LayerF64Args t{ws.x64, ws.msg64, lf + WF64_W1, w64 + lo + bl.mlp1_b, lf + WF64_W2, w64 + lo + bl.mlp2_b,
+                                 last ? nullptr : lf + layer_f64_frag_doubles() + WF64_QKV, last ? nullptr : w64 + lo + bl.layer_stride + bl.qkv_b,
+                                 ws.qkv64, last ? ws.x : nullptr, f.R, f.guard(), ws.hid64};
+            if (int rc = launch_layer_tail_f64(t, coop)) return rc;
+        } else {
+            if (int rc = f.gemm64(ws.x64, 128, 128, ws.msg64, 128, lo + bl.mlp1_w, lo + bl.mlp1_b, 1, nullptr, ws.hid64, 256, 256, 256)) return rc;
+            if (int rc = f.gemm64(ws.hid64, 256, 256, nullptr, 0, lo + bl.mlp2_w, lo + bl.mlp2_b, 0, ws.x64, ws.x64, 128, 128, 256)) return rc;
+        }
+        f.mark(MDGAT_PROF_F64_GEMM);
+        if (int rc = f.tap(f.x_tap(i), ws.x64, Rz * 128)) return rc;
+    }
+    return MDGAT_OK;
+}
+
+// ---- p.tail64: final_proj (mdgat.py:397), the score matrix (430-431), the optimal transport (434-436), the extraction (441-483)
+// and the loss in fp64 ----
+static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
+    const Workspace& ws = f.ws;
+    const int B = f.B, N = f.N, M = f.M;
+    double* mdesc64 = ws.msg64;          // (the message and q | k | v of the last layer are dead)
+    double* scores64 = ws.scores64;      // [B][N][M]: in q | k | v's room while N M <= 384 (N + M)
+    if (int rc = f.gemm64(ws.x64, 128, 128, nullptr, 0, f.h->bl.final_w, f.h->bl.final_b, 0, nullptr, mdesc64, 128, 128, 128)) return rc;
+    if (int rc = f.tap(f.taps.mdesc, mdesc64, (size_t)f.R * 128)) return rc;
+    const GemmF64Args sg{mdesc64, 128, 128, nullptr, 0, mdesc64 + (size_t)N * 128, 128, nullptr, nullptr, 0, scores64, M, N, M, 128, 0, f.guard(),
+                         0.08838834764831845 /* 1 / sqrt(128) */, B, (long long)(N + M) * 128, (long long)(N + M) * 128, (long long)N * M};
+    if (int rc = launch_gemm_f64(sg, f.s)) return rc;
+    f.mark(MDGAT_PROF_F64_GEMM);
+    if (int rc = f.tap(f.taps.scores, scores64, (size_t)B * N * M)) return rc;
+    const Sk64Bests b = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
+    const SkExtract ex = f.extract(o);
+    if (int rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
+                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->weights64 + f.h->bl.bin_score)) return rc;
+    if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s)) return rc;
+    f.mark(MDGAT_PROF_SINKHORN);
+    return f.loss(o, static_cast<const double*>(ws.Z64));
+}
+
+// ---- the hand-over to the fp32-class kernels (nothing behind p.first is discontinuous); the fused fp64 launches write it on the side ----
+static int hand_over(Fwd& f) {
+    if (f.p.fused64) return MDGAT_OK;
+    const int rc = launch_f64_to_f32(f.ws.x64, f.ws.x, (size_t)f.R * 128, f.guard(), f.s);
+    if (!rc) f.mark(MDGAT_PROF_F64_OTHER);
+    return rc;
+}
+
+// ---- the attentional propagation layers from p.first on (mdgat.py:259-276) ----
+// launch i: [attention of layer i] -> [mlp + residual of layer i | q/k/v of layer i + 1 (or final_proj into ws.hid)]
+static int layers32(Fwd& f) {
+    const mdgat_handle* h = f.h;
+    const BlobLayout& bl = h->bl;
+    const float* w = h->weights;
+    const int L2 = 2 * h->cfg.L;
+    const _Float16* wfrag = h->wsplit + wsplit_halves(h->cfg.L);      // fragment-order copies (layer_split.hip)
+    // a layer launch whose projection is layer j's q | k | v, or final_proj behind the last layer (j == 2L)
+    auto launch = [&](LayerLaunch p, int j, int cls) {
+        p.x = f.ws.x; p.R = f.R; p.N = f.N; p.M = f.M; p.out = f.q16; p.mdesc = f.ws.hid; p.guard = f.guard();
+        if (j < L2) { p.mode3 = 1; p.w3s = h->wsplit + WS_LAYER * (size_t)j + WS_QKV; p.w3f = wfrag + WF_LAYER * (size_t)j + WF_QKV; p.b3 = w + bl.layer0 + (size_t)j * bl.layer_stride + bl.qkv_b; }
+        else { p.mode3 = 2; p.w3s = h->wsplit + WS_LAYER * (size_t)L2; p.w3f = wfrag + WF_LAYER * (size_t)L2; p.b3 = w + bl.final_b; }
+        const int rc = launch_layer(p, f.s);
+        if (!rc) f.mark(cls);
+        return rc;
+    };
+    if (int rc = launch(LayerLaunch{}, f.p.first, MDGAT_PROF_LAYER_FIRST)) return rc;
+    for (int i = f.p.first; i < L2; ++i) {
+        const float* lw = w + bl.layer0 + (size_t)i * bl.layer_stride;
+        const _Float16* ls = h->wsplit + WS_LAYER * (size_t)i;
+        const _Float16* lf = wfrag + WF_LAYER * (size_t)i;
+        const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
+        const int kk = h->cfg.topk[i];
+        if (int rc = launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
+        f.mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
+        LayerLaunch p{};
+        p.msg = f.ws.msg; p.do_mlp = 1;
+        p.w1s = ls + WS_W1; p.w1f = lf + WF_W1; p.b1 = lw + bl.mlp1_b; p.w2s = ls + WS_W2; p.w2f = lf + WF_W2; p.b2 = lw + bl.mlp2_b;
+        if (int rc = launch(p, i + 1, i + 1 < L2 ? MDGAT_PROF_LAYER : MDGAT_PROF_LAYER_LAST)) return rc;
+        if (int rc = f.tap(f.x_tap(i), f.ws.x, (size_t)f.R * 128, "tap x_layers")) return rc;
+    }
+    return MDGAT_OK;
+}
+
+// ---- score matrix (mdgat.py:430-431) of the final projection (397, in ws.hid), optimal transport (434-436), match extraction
+// (441-483) and the loss ----
+static int tail32(Fwd& f, const FwdOut& o) {
+    const Workspace& ws = f.ws;
+    const int B = f.B, N = f.N, M = f.M;
+    const float* mdesc = ws.hid;
+    if (int rc = f.tap(f.taps.mdesc, mdesc, (size_t)f.R * 128, "tap mdesc")) return rc;
+    // (the score kernel also clears the exchange slots of the Sinkhorn kernel that follows: no memset launch in between)
+    const size_t sk_clear = f.p.cluster32 ? sinkhorn_slots_clear_bytes(B, N, M) : 0;
+    if (int rc = launch_scores(B, N, M, mdesc, ws.scores, 0.08838834764831845f /* 1 / sqrt(128) */, f.s, sk_clear ? ws.sk : nullptr, sk_clear,
+                            f.guard())) return rc;
+    f.mark(MDGAT_PROF_SCORES);
+    if (int rc = f.tap(f.taps.scores, ws.scores, (size_t)B * N * M, "tap scores")) return rc;
+    // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
+    float* Zout = o.Z ? o.Z : (f.p.cluster32 && !o.loss ? nullptr : ws.Z);
+    const SkExtract ex = f.extract(o);
+    if (int rc = launch_sinkhorn(B, N, M, ws.scores, f.h->weights + f.h->bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
+                              f.status, o.Z ? o.Z : ws.Z, sk_clear != 0)) return rc;
+    f.mark(MDGAT_PROF_SINKHORN);
+    return f.loss(o, static_cast<const float*>(Zout));
+}
+
+// one slice of a call (checked by plan_forward) on one lane
+static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
+                        void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
+    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss);
+    Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust};
+    f.mark(-1);
+    int rc;
+    if ((N & 31) || (M & 31))   // the attention kernel reads V^T in whole 32-key blocks: pad columns must be zero
+        if ((rc = mdgat_check_hip(hipMemsetAsync(f.q16.vt16, 0, (size_t)B * 256 * f.q16.PP * sizeof(_Float16), s), "memset(V^T pads)"))) return rc;
+    if (!p.f64) {
+        if ((rc = encoders32(f, in))) return rc;
+    } else {
+        // (the forward's launches of kernels whose workgroups wait for each other - clustered layer tails, the resident fp64 Sinkhorn - as
+        // one group of the device's chain: coop_chain.hpp)
+        CoopGroup coop;
+        if ((rc = coop.open(h->device, s)) || (rc = head64(f, in, coop))) return rc;
+        if (p.tail64) return tail64(f, o, coop);
+        if ((rc = hand_over(f))) return rc;
+    }
+    if ((rc = layers32(f))) return rc;
+    return tail32(f, o);
+}
+
+// profiling: wait for the events of both lanes and add the intervals between consecutive ones to their kernel classes
+// (an interval that starts at a -1 mark - the beginning of a forward_impl call - is counted, one that ends there is not)
+static int prof_collect(mdgat_handle* h) {
+    if (!h->prof_on) return MDGAT_OK;
+    for (auto& pl : h->prof) {
+        if (pl.n > 1) {
+            if (int rc = mdgat_check_hip(hipEventSynchronize(pl.ev[pl.n - 1]), "profile sync")) return rc;
+            for (size_t i = 1; i < pl.n; ++i) {
+                float ms = 0.f;
+                if (pl.cls[i] >= 0 && hipEventElapsedTime(&ms, pl.ev[i - 1], pl.ev[i]) == hipSuccess) {
+                    h->prof_ms[pl.cls[i]] += ms;
+                    h->prof_launches[pl.cls[i]] += 1;
+                }
+            }
+        }
+        pl.n = 0;
+        pl.cls.clear();
+    }
+    return MDGAT_OK;
+}
+
+static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in,
+                           int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
+                           const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream,
+                           const mdgat_loss_request* loss_req = nullptr) {
+    const FwdOut out{matches0, matches1, mscores0, mscores1, Z, loss_req != nullptr, loss_req ? *loss_req : mdgat_loss_request{}};
+    Path p{};
+    if (int rc = plan_forward(h, B, N, M, in, out, taps, workspace, workspace_bytes, p)) return rc;
     // the handle's device is current for the whole call, the caller's restored after it: everything below works on the current device
     struct DeviceScope {
         int prev = -1, dev;
@@ -787,49 +799,31 @@ static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in
     if (int rc = mdgat_check_hip(scope.set, "hipSetDevice")) return rc;
     std::lock_guard<std::mutex> serialise(h->enqueue);
     if (++h->match_token == 0) h->match_token = 1;      // this call's token (mdgat_matched_any): every slice / lane of the call writes the same one
-    if (!taps && B > 0 && N > 0 && M > 0 && matches0 && matches1 && mscores0 && mscores1)
-        p = lane_plan(h->lanes, B, N, M, h->cfg.arithmetic == MDGAT_ARITH_FP64, loss_req != nullptr);
-    if (p.nslices <= 1) {
-        const int rc = forward_impl(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, 0, 0, loss_req);
-        return rc ? rc : prof_collect(h);
-    }
-    if (!workspace || workspace_bytes < p.lane_bytes * (size_t)p.lanes) {
-        mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, p.lane_bytes * (size_t)p.lanes);
-        return MDGAT_ERR_BAD_ARG;
-    }
+    unsigned* status = nullptr;
+    if (int rc = mdgat_check_hip(hipHostGetDevicePointer(reinterpret_cast<void**>(&status), h->host_error, 0), "hipHostGetDevicePointer")) return rc;
     hipStream_t s0 = static_cast<hipStream_t>(stream);
+    const LanePlan& lp = p.lanes;
+    const bool sliced = lp.nslices > 1;
     int rc = MDGAT_OK;
-    if (p.lanes == 2) {
+    if (lp.lanes == 2) {
         // (both lanes start together: a second lane started one to five launches behind the first - complementary kernels
         // side by side - pays the delay as a tail: 20 900 -> 20 300 ... 19 700 pairs/s at B = 64)
         if ((rc = mdgat_check_hip(hipEventRecord(h->ev_fork, s0), "fork record"))) return rc;
         if ((rc = mdgat_check_hip(hipStreamWaitEvent(h->lane_stream, h->ev_fork, 0), "fork wait"))) return rc;
     }
-    int slice = 0;
-    for (int c = 0; c < B && !rc; c += p.per, ++slice) {
-        const int b = B - c < p.per ? B - c : p.per;
-        const size_t c_ = (size_t)c;
-        const int lane = p.lanes == 2 ? (slice & 1) : 0;
-        mdgat_loss_request lr{};
-        if (loss_req) {
-            lr = *loss_req;
-            lr.gt0 += c_ * N;
-            lr.gt1 += c_ * M;
-            lr.loss += c_;
-        }
-        rc = forward_impl(h, b, N, M, in.from(c_, N, M),
-                          matches0 + c_ * N, matches1 + c_ * M, mscores0 + c_ * N, mscores1 + c_ * M,
-                          Z ? Z + c_ * (N + 1) * (M + 1) : nullptr, nullptr, static_cast<char*>(workspace) + (size_t)lane * p.lane_bytes,
-                          p.lane_bytes, lane ? static_cast<void*>(h->lane_stream) : stream, 1, lane, loss_req ? &lr : nullptr);
+    for (int c = 0, slice = 0; c < B && !rc; c += lp.per, ++slice) {
+        const int lane = lp.lanes == 2 ? (slice & 1) : 0;
+        rc = forward_impl(h, p, B - c < lp.per ? B - c : lp.per, N, M, in.from(c, N, M), out.from(c, N, M), taps,
+                          static_cast<char*>(workspace) + (size_t)lane * lp.lane_bytes, lane ? h->lane_stream : s0, status, lane, sliced);
     }
-    if (p.lanes == 2) {
+    if (lp.lanes == 2) {
         // (joined even after a failed launch: the caller's stream must not run ahead of what the second lane was given)
         const int rj = mdgat_check_hip(hipEventRecord(h->ev_join, h->lane_stream), "join record");
         const int rw = mdgat_check_hip(hipStreamWaitEvent(s0, h->ev_join, 0), "join wait");
         if (!rc) rc = rj ? rj : rw;
     }
     if (rc) return rc;
-    if ((rc = launch_alldust_fixup(B, N, M, h->cfg.extract_mode, matches0, mscores1, s0))) return rc;
+    if (sliced && (rc = launch_alldust_fixup(B, N, M, h->cfg.extract_mode, out.matches0, out.mscores1, s0))) return rc;
     return prof_collect(h);
 }
 
@@ -989,8 +983,7 @@ extern "C" int mdgat_attention_qk_probe_sets(int B, int N, int M, int cross, int
 extern "C" int mdgat_pointwise(int M, int N, int K, const float* A, int lda, const float* W, int ldw, const float* bias,
                                int relu, const float* R, int ldr, float* C, int ldc, void* stream) {
     if (!A || !W || !C) { mdgat_set_error("mdgat_pointwise: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    GemmArgs g = pointwise(A, lda, K, W, bias, relu, C, ldc, M, N);
-    g.ldw = ldw; g.R = R; g.ldr = ldr;
+    const GemmArgs g{A, lda, K, nullptr, 0, W, ldw, bias, R, ldr, C, ldc, M, N, K, relu, 1.f, 1, 0, 0, 0};
     return launch_gemm(g, static_cast<hipStream_t>(stream));
 }
 

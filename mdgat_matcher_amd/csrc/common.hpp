@@ -45,6 +45,18 @@ __device__ __forceinline__ constexpr int mfma32_row(int r, int hi) { return (r &
 void mdgat_set_error(const char* fmt, ...);
 int mdgat_check_hip(hipError_t e, const char* what);
 
+// Workspaces are laid out in regions of whole 256-byte units.  A carve function runs the same takes with a null base for the byte
+// count and with the caller's base for the pointers: take(p, n) points p at the next n elements (nullptr for a null base).
+inline size_t mdgat_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+struct WsCarver {
+    char* base;
+    size_t bytes = 0;
+    template <typename T> void take(T*& p, size_t n) {
+        p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+        bytes += mdgat_align256(n * sizeof(T));
+    }
+};
+
 // Per-device state (launch chains, CU counts, LDS opt-ins) is kept for device indices 0 .. MDGAT_MAX_DEVICES - 1;
 // mdgat_create refuses the others.  The launchers work on the CURRENT device: the forward makes the handle's current.
 constexpr int MDGAT_MAX_DEVICES = 64;

@@ -541,10 +541,13 @@ __global__ __launch_bounds__(256) void frag64_kernel(const double* W, double* ou
 
 size_t layer_f64_frag_doubles() { return (size_t)256 * 256 + 128 * 256 + 384 * 128; }
 
-size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }
-// the six encoder matrices: kenc.0 | denc.0 | kenc.3 | kenc.6 | denc.3 | last layers summed
-size_t encoder_f64_frag_doubles() {
-    return frag64_doubles(32, 4) + frag64_doubles(64, 33) + frag64_doubles(64, 32) + frag64_doubles(128, 64) + frag64_doubles(128, 64) + frag64_doubles(128, 256);
+static size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }
+
+EncoderF64Frags encoder_f64_frags() {
+    EncoderF64Frags f{};
+    auto take = [&](Frag64& m, int n, int k) { m = Frag64{f.total, n, k}; f.total += frag64_doubles(n, k); };
+    take(f.k0, 32, 4); take(f.d0, 64, 33); take(f.k1, 64, 32); take(f.k2, 128, 64); take(f.d1, 128, 64); take(f.l, 128, 256);
+    return f;
 }
 
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s) {

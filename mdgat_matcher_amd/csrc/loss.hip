@@ -41,14 +41,13 @@ size_t tiles_of(int N) { return (size_t)(N + 1 + LOSS_TR - 1) / LOSS_TR; }
 struct LossWs { double *rowterm, *slab, *tpos; int *cols, *A; size_t total; };
 LossWs carve_loss(void* base, int B, int N, int M) {
     LossWs w{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return static_cast<char*>(base) + r; };
-    w.rowterm = reinterpret_cast<double*>(take((size_t)B * N * sizeof(double)));
-    w.slab = reinterpret_cast<double*>(take((size_t)B * tiles_of(N) * M * sizeof(double)));
-    w.tpos = reinterpret_cast<double*>(take((size_t)B * M * sizeof(double)));
-    w.cols = reinterpret_cast<int*>(take((size_t)B * M * sizeof(int)));
-    w.A = reinterpret_cast<int*>(take((size_t)B * (N + 2) * sizeof(int)));
-    w.total = o;
+    WsCarver c{static_cast<char*>(base)};
+    c.take(w.rowterm, (size_t)B * N);
+    c.take(w.slab, (size_t)B * tiles_of(N) * M);
+    c.take(w.tpos, (size_t)B * M);
+    c.take(w.cols, (size_t)B * M);
+    c.take(w.A, (size_t)B * (N + 2));
+    w.total = c.bytes;
     return w;
 }
 constexpr int LOSS_GAP_MAX_ROWS = 15000;     // the prologue holds N + 2 row counters in LDS (at most 64 KB per workgroup)

@@ -597,7 +597,6 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a
 
 }  // namespace
 
-static size_t s64_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static size_t s64_lds_bytes(int waves) { return ((size_t)waves * S64_SLOT + S64_SLOT) * sizeof(double) + (size_t)waves * S64_SLOT * sizeof(int); }
 
 static bool s64_resident_supported(int N, int M) { return N >= 1 && M >= 1 && M + 1 <= 64 * S64_NC && N <= 32 * S64_GMAX; }
@@ -619,22 +618,54 @@ extern "C" int mdgat_set_f64_sinkhorn_form(int mode) {
 }
 static bool s64_use_wide(int N, int M) { return !s64_resident_supported(N, M) || (s64_form() == 1 && s64_wide_supported(N, M)); }
 
-static size_t s64_wide_bytes(int B, int N, int M) {
+// the streaming form's workspace (a null base: its size only); sval / sidx: the column slabs of the extraction's arg-maxes
+struct Wk64Ws { double *K, *rmax, *av, *P, *bvec, *sval; int* sidx; size_t bytes; };
+static Wk64Ws s64_wide_carve(void* base, int B, int N, int M) {
     const size_t Mp = ((size_t)M + 1 + 127) & ~(size_t)127, G = ((size_t)N + W64_ROWS - 1) / W64_ROWS;
-    return s64_align((size_t)B * N * Mp * sizeof(double)) + s64_align((size_t)B * N * sizeof(double)) + s64_align((size_t)B * (N + 1) * sizeof(double)) +
-           s64_align((size_t)B * 2 * G * Mp * sizeof(double)) + s64_align((size_t)B * Mp * sizeof(double)) + s64_align((size_t)B * G * M * sizeof(double)) + s64_align((size_t)B * G * M * sizeof(int));
+    Wk64Ws w{};
+    WsCarver c{static_cast<char*>(base)};
+    c.take(w.K, (size_t)B * N * Mp); c.take(w.rmax, (size_t)B * N); c.take(w.av, (size_t)B * (N + 1));
+    c.take(w.P, (size_t)B * 2 * G * Mp); c.take(w.bvec, (size_t)B * Mp);
+    c.take(w.sval, (size_t)B * G * M); c.take(w.sidx, (size_t)B * G * M);
+    w.bytes = c.bytes;
+    return w;
 }
 
-// (the register-resident form sized for the eight-wave workgroups: the larger slab count)
-size_t sinkhorn_f64_workspace_bytes(int B, int N, int M) {
-    if (B <= 0) return 0;
-    if (s64_use_wide(N, M)) return s64_wide_bytes(B, N, M);
+// the register-resident form's workspace, sized for the eight-wave workgroups (the larger slab count)
+struct Sk64Ws { double* slots; unsigned* flags; double* sval; int* sidx; size_t bytes; };
+static Sk64Ws s64_resident_carve(void* base, int B, int N, int M) {
     const size_t G = (N + 31) / 32;
-    return s64_align((size_t)B * 2 * G * S64_SLOT * sizeof(double)) + s64_align((size_t)B * 3 * G * sizeof(unsigned)) +
-           s64_align((size_t)B * G * M * sizeof(double)) + s64_align((size_t)B * G * M * sizeof(int));
+    Sk64Ws w{};
+    WsCarver c{static_cast<char*>(base)};
+    c.take(w.slots, (size_t)B * 2 * G * S64_SLOT); c.take(w.flags, (size_t)B * 3 * G);
+    c.take(w.sval, (size_t)B * G * M); c.take(w.sidx, (size_t)B * G * M);
+    w.bytes = c.bytes;
+    return w;
+}
+
+size_t sinkhorn_f64_workspace_bytes(int B, int N, int M) {
+    return B <= 0 ? 0 : s64_use_wide(N, M) ? s64_wide_carve(nullptr, B, N, M).bytes : s64_resident_carve(nullptr, B, N, M).bytes;
+}
+
+Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M) {
+    Sk64Bests b{};
+    WsCarver c{static_cast<char*>(base)};
+    c.take(b.ri, (size_t)B * N); c.take(b.rv, (size_t)B * N);
+    c.take(b.ci, (size_t)B * M); c.take(b.cv, (size_t)B * M);
+    b.bytes = c.bytes;
+    return b;
 }
 
 bool sinkhorn_f64_supported(int N, int M) { return s64_resident_supported(N, M) || s64_wide_supported(N, M); }
+
+// both forms: the column arg-maxes of the G row slabs merged in fp64, if the caller asked for them
+static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val, hipStream_t s) {
+    if (!cbest_idx) return MDGAT_OK;
+    const size_t total = (size_t)B * M;
+    hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, G, M,
+                       cbest_idx, cbest_val);
+    return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch");
+}
 
 template <int NC2>
 static int s64_wide_launches(const Wk64Args& a0, hipStream_t s) {
@@ -659,25 +690,13 @@ static int launch_sinkhorn_f64_wide(int B, int N, int M, const double* scores, d
     a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.inner = inner;
     a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
     a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val;
-    char* w = static_cast<char*>(workspace);
-    a.K = reinterpret_cast<double*>(w); w += s64_align((size_t)B * N * a.Mp * sizeof(double));
-    a.rmax = reinterpret_cast<double*>(w); w += s64_align((size_t)B * N * sizeof(double));
-    a.av = reinterpret_cast<double*>(w); w += s64_align((size_t)B * (N + 1) * sizeof(double));
-    a.P = reinterpret_cast<double*>(w); w += s64_align((size_t)B * 2 * a.G * a.Mp * sizeof(double));
-    a.bvec = reinterpret_cast<double*>(w); w += s64_align((size_t)B * a.Mp * sizeof(double));
-    double* sval = reinterpret_cast<double*>(w); w += s64_align((size_t)B * a.G * M * sizeof(double));
-    int* sidx = reinterpret_cast<int*>(w);
-    a.cslab_idx = cbest_idx ? sidx : nullptr; a.cslab_val = cbest_idx ? sval : nullptr;
+    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
+    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
+    a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
     const int nc2 = a.Mp >> 7;
     int rc = nc2 <= 5 ? s64_wide_launches<5>(a, s) : nc2 <= 9 ? s64_wide_launches<9>(a, s) : s64_wide_launches<W64_NC2MAX>(a, s);
     if (rc) return rc;
-    if (cbest_idx) {
-        const size_t total = (size_t)B * M;
-        hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, a.G, M,
-                           cbest_idx, cbest_val);
-        if (int rc2 = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch")) return rc2;
-    }
-    return MDGAT_OK;
+    return s64_merge_columns(w.sidx, w.sval, B, a.G, M, cbest_idx, cbest_val, s);
 }
 
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
@@ -698,16 +717,11 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     // code generation that turned to garbage under a harmless edit (profiles/NOTES_r6.md section 12): not kept.
     constexpr int waves = 8;
     const int G = (N + 4 * waves - 1) / (4 * waves);
-    char* w = static_cast<char*>(workspace);
+    const Sk64Ws w = s64_resident_carve(workspace, B, N, M);
     Sk64Args a{};
     a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.G = G; a.inner = inner;
     a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val;
-    const size_t Gmax = (N + 31) / 32;
-    a.slots = reinterpret_cast<double*>(w); w += s64_align((size_t)B * 2 * Gmax * S64_SLOT * sizeof(double));
-    a.flags = reinterpret_cast<unsigned*>(w); w += s64_align((size_t)B * 3 * Gmax * sizeof(unsigned));
-    double* sval = reinterpret_cast<double*>(w); w += s64_align((size_t)B * Gmax * M * sizeof(double));
-    int* sidx = reinterpret_cast<int*>(w);
-    a.cslab_idx = cbest_idx ? sidx : nullptr; a.cslab_val = cbest_idx ? sval : nullptr;
+    a.slots = w.slots; a.flags = w.flags; a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
     a.error_word = error_word;
     // ONE launch of this kernel at a time per device: the caller's CoopGroup admits it after the previous waiting launch, whatever stream
     // that was on (coop_chain.hpp; shared with the clustered fp64 layer tail).  The workgroups of a pair wait for each other, and a
@@ -724,21 +738,13 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8>), lds, optin8, "sinkhorn_f64 LDS")) return rc;
     hipLaunchKernelGGL(sinkhorn_f64_kernel<8>, dim3(groups * 8 * G), dim3(512), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
-    if (cbest_idx) {
-        const size_t total = (size_t)B * M;
-        hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, G, M,
-                           cbest_idx, cbest_val);
-        if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch")) return rc;
-    }
-    return MDGAT_OK;
+    return s64_merge_columns(w.sidx, w.sval, B, G, M, cbest_idx, cbest_val, s);
 }
 
 // ---- per-op entry points (include/mdgat_hip.h) ----
-size_t sinkhorn_f64_bests_bytes(int B, int N, int M) { return s64_align((size_t)B * N * 4) * 2 + s64_align((size_t)B * M * 4) * 2; }
-
 extern "C" size_t mdgat_sinkhorn_f64_workspace_bytes(int B, int N, int M) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
-    return sinkhorn_f64_workspace_bytes(B, N, M) + sinkhorn_f64_bests_bytes(B, N, M);
+    return sinkhorn_f64_workspace_bytes(B, N, M) + sinkhorn_f64_bests(nullptr, B, N, M).bytes;
 }
 
 extern "C" int mdgat_sinkhorn_f64(int B, int N, int M, const double* scores, double bin_score, int iters, double* Z, void* workspace,
@@ -760,19 +766,15 @@ extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* sco
         return MDGAT_ERR_BAD_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace) + sinkhorn_f64_workspace_bytes(B, N, M);
-    int* ri = reinterpret_cast<int*>(w); w += s64_align((size_t)B * N * 4);
-    float* rv = reinterpret_cast<float*>(w); w += s64_align((size_t)B * N * 4);
-    int* ci = reinterpret_cast<int*>(w); w += s64_align((size_t)B * M * 4);
-    float* cv = reinterpret_cast<float*>(w);
+    const size_t kb = sinkhorn_f64_workspace_bytes(B, N, M);
+    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, N, M);
     const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
     {
         CoopGroup group;
         if (int rc = group.open(mdgat_current_device(), s)) return rc;
-        if (int rc = launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, nullptr, Z_or_null, inner, ri, rv, ci, cv, workspace,
-                                         sinkhorn_f64_workspace_bytes(B, N, M), nullptr, group))
+        if (int rc = launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv, workspace, kb, nullptr, group))
             return rc;
     }
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    return launch_extract_from_bests(B, N, M, &ex, ri, rv, ci, cv, s);
+    return launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, s);
 }

@@ -14,4 +14,6 @@ bool sinkhorn_f64_supported(int N, int M);
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
                         float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
                         CoopGroup& group, const double* alpha_dev = nullptr);      // on the group's stream; alpha_dev: the bin score on the device (replaces alpha)
-size_t sinkhorn_f64_bests_bytes(int B, int N, int M);      // room for rbest / cbest (idx + val each) behind the kernel's own workspace
+// rbest / cbest (idx + val each) for the extraction, carved behind the kernel's own workspace (a null base: their size only)
+struct Sk64Bests { int* ri; float* rv; int* ci; float* cv; size_t bytes; };
+Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M);
