@@ -345,6 +345,17 @@ int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double
                                int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of log_optimal_transport (mdgat.py:279-308) in fp64: given scores [B][N][M] fp64, the bin score and dZ = dL/dZ
+ * [B][N+1][M+1] fp64 (contiguous), writes dscores [B][N][M] and dbin [B] (the bin score's gradient PER PAIR: the sum of dL/dC over
+ * the pair's dustbin row and column; a caller with one shared bin score sums them).  N, M <= 2175 (else MDGAT_ERR_UNSUPPORTED),
+ * iters >= 0 (0: dscores = dZ[:, :N, :M]), B >= 0.  The forward's potentials are recomputed (the streaming fp64 iterations with their
+ * history kept), then T reverse iterations and one fp64 GEMM (csrc/sinkhorn_grad.hip).  A pair's result does not depend on the
+ * batch it travels in.  workspace: mdgat_sinkhorn_backward_workspace_bytes, 256-byte aligned (about 8 (B N (M + 128) + 2 T B
+ * (N + M + 192)) bytes).  Asynchronous on `stream`. */
+int mdgat_sinkhorn_backward(int B, int N, int M, const double* scores, double bin_score, int iters, const double* dZ, double* dscores,
+                            double* dbin, void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_sinkhorn_backward_workspace_bytes(int B, int N, int M, int iters);
+
 /* match extraction (mdgat.py:441-483) from Z [B][N+1][M+1]. */
 int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold,
                   int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,

@@ -64,7 +64,12 @@ def dynamic_attention(query, key, value, k):
 
 
 def log_optimal_transport(scores, alpha, iters: int):
-    """mdgat.py:288-308: scores [B, N, M] -> log assignment matrix [B, N+1, M+1] (log-domain Sinkhorn)."""
+    """mdgat.py:288-308: scores [B, N, M] -> log assignment matrix [B, N+1, M+1] (log-domain Sinkhorn).  Differentiable, as the
+    reference's is: with grad enabled and ``scores`` or a tensor ``alpha`` requiring grad, the same forward (bit for bit) runs under
+    ``ops.log_optimal_transport``, whose backward is the fp64 kernel of csrc/sinkhorn_grad.hip."""
+    wants_grad = scores.requires_grad or (isinstance(alpha, torch.Tensor) and alpha.requires_grad)
+    if torch.is_grad_enabled() and wants_grad:
+        return _ops.log_optimal_transport(scores, alpha, int(iters), arithmetic='fp32')
     return _ops.sinkhorn(scores, float(alpha), int(iters)).to(scores.dtype)
 
 

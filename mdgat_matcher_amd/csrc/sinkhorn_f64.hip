@@ -393,6 +393,9 @@ struct Wk64Args {
     double* P;                 // [B][2][G][Mp]: column partials per slab, by iteration parity
     double* bvec;              // [B][Mp]: the column scalings the coming launch works with (sinkhorn_f64_wide_b_kernel)
     double* Z64; float* Z32; int* rbest_idx; float* rbest_val; int* cslab_idx; double* cslab_val;
+    // optional potential history for the backward (sinkhorn_grad.hip; null for the forward): a_{it+1} (a_N last) into row 2 it + 1 of
+    // hist_a [B][2 iters][hist_lda], b_it into row 2 it of hist_b [B][2 iters][Mp] (it < iters)
+    double* hist_a; double* hist_b; int hist_lda;
 };
 
 typedef double w64x2 __attribute__((ext_vector_type(2)));
@@ -437,6 +440,7 @@ __global__ __launch_bounds__(128) void sinkhorn_f64_wide_b_kernel(Wk64Args a) {
         }
     }
     a.bvec[(size_t)pair * Mp + j] = bv;
+    if (a.hist_b && a.it < a.iters) a.hist_b[((size_t)pair * 2 * a.iters + 2 * a.it) * Mp + j] = bv;
 }
 
 template <int NC2>
@@ -473,6 +477,7 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_iter_kernel(Wk64Args a)
             }
         const double ai = mu * recip_f64(wave_sum_f64(p));
         if (lane == 0) a.av[(size_t)pair * (N + 1) + row] = ai;
+        if (a.hist_a && lane == 0) a.hist_a[((size_t)pair * 2 * a.iters + 2 * a.it + 1) * a.hist_lda + row] = ai;
 #pragma unroll
         for (int c = 0; c < NC2; ++c) {
             acc[2 * c] = __builtin_fma(kv[c].x, ai, acc[2 * c]);
@@ -508,6 +513,7 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_iter_kernel(Wk64Args a)
         mine[j] = p;
     }
     if (last && tid == 0) a.av[(size_t)pair * (N + 1) + N] = aN;
+    if (last && tid == 0 && a.hist_a) a.hist_a[((size_t)pair * 2 * a.iters + 2 * a.it + 1) * a.hist_lda + N] = aN;
 }
 
 // Z = Z0 - r + log a + log b - norm and the arg-maxes, decided on the fp64 values (as the register-resident kernel's epilogue)
@@ -667,8 +673,9 @@ static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, 
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch");
 }
 
+// final: the last launch (Z, the arg-maxes); without it (the backward's history run) the launches stop at b_iters
 template <int NC2>
-static int s64_wide_launches(const Wk64Args& a0, hipStream_t s) {
+static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final = true) {
     Wk64Args a = a0;
     const size_t lds_it = (size_t)9 * a.Mp * sizeof(double), lds_fin = (size_t)a.Mp * (3 * sizeof(double) + sizeof(int));
     static std::atomic<unsigned long long> optin_it{0}, optin_fin{0};
@@ -680,7 +687,7 @@ static int s64_wide_launches(const Wk64Args& a0, hipStream_t s) {
         hipLaunchKernelGGL(sinkhorn_f64_wide_b_kernel, dim3((unsigned)(a.B * (a.Mp >> 7))), dim3(128), 0, s, a);
         if (it < a.iters) hipLaunchKernelGGL(sinkhorn_f64_wide_iter_kernel<NC2>, dim3((unsigned)(a.B * a.G)), dim3(512), lds_it, s, a);
     }
-    hipLaunchKernelGGL(sinkhorn_f64_wide_final_kernel<NC2>, dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
+    if (final) hipLaunchKernelGGL(sinkhorn_f64_wide_final_kernel<NC2>, dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming) launch");
 }
 
@@ -739,6 +746,26 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     hipLaunchKernelGGL(sinkhorn_f64_kernel<8>, dim3(groups * 8 * G), dim3(512), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
     return s64_merge_columns(w.sidx, w.sval, B, G, M, cbest_idx, cbest_val, s);
+}
+
+// ---- the streaming form's iterations with their potential history, for the backward (sinkhorn_grad.hip) ----
+Sk64Stream sinkhorn_f64_stream_carve(void* base, int B, int N, int M) {
+    const Wk64Ws w = s64_wide_carve(base, B, N, M);
+    return Sk64Stream{w.K, w.P, w.bvec, (M + 1 + 127) & ~127, (N + W64_ROWS - 1) / W64_ROWS, w.bytes};
+}
+
+int sinkhorn_f64_stream_history(int B, int N, int M, const double* scores, double alpha, int iters, double* hist_a, int hist_lda, double* hist_b,
+                                void* workspace, hipStream_t s) {
+    if (B <= 0) return MDGAT_OK;
+    if (!s64_wide_supported(N, M)) { mdgat_set_error("fp64 Sinkhorn (streaming): %d x %d keypoints > %d supported", N, M, 128 * W64_NC2MAX - 1); return MDGAT_ERR_UNSUPPORTED; }
+    Wk64Args a{};
+    a.scores = scores; a.alpha = alpha; a.B = B; a.N = N; a.M = M; a.iters = iters;
+    a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
+    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
+    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
+    a.hist_a = hist_a; a.hist_b = hist_b; a.hist_lda = hist_lda;
+    const int nc2 = a.Mp >> 7;
+    return nc2 <= 5 ? s64_wide_launches<5>(a, s, false) : nc2 <= 9 ? s64_wide_launches<9>(a, s, false) : s64_wide_launches<W64_NC2MAX>(a, s, false);
 }
 
 // ---- per-op entry points (include/mdgat_hip.h) ----

@@ -17,3 +17,11 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
 // rbest / cbest (idx + val each) for the extraction, carved behind the kernel's own workspace (a null base: their size only)
 struct Sk64Bests { int* ri; float* rv; int* ci; float* cv; size_t bytes; };
 Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M);
+// The streaming form's init and iterations alone, with the potential history written through (the backward, sinkhorn_grad.hip):
+// a_1 .. a_T (a_N last in each) into rows 1, 3, .. of hist_a [B][2T][hist_lda], b_0 .. b_{T-1} into rows 0, 2, .. of hist_b
+// [B][2T][Mp] (zero beyond column M).  Left in the workspace: K [B][N][Mp] (rows padded with zeros, the dustbin column at M; the
+// dustbin row, all ones, is not stored) and b_T [B][Mp].  P: [B][2][G][Mp] doubles the iterations are done with.  N, M <= 2175.
+struct Sk64Stream { double* K; double* P; double* bvec; int Mp, G; size_t bytes; };
+Sk64Stream sinkhorn_f64_stream_carve(void* base, int B, int N, int M);       // (a null base: its size only)
+int sinkhorn_f64_stream_history(int B, int N, int M, const double* scores, double alpha, int iters, double* hist_a, int hist_lda, double* hist_b,
+                                void* workspace, hipStream_t s);

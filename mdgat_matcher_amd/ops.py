@@ -77,6 +77,73 @@ def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mod
     return (m0, m1, s0, s1, Z) if want_Z else (m0, m1, s0, s1)
 
 
+def sinkhorn_backward(scores: torch.Tensor, bin_score, iters: int, dZ: torch.Tensor):
+    """Gradient of log_optimal_transport (mdgat.py:288-308; csrc/sinkhorn_grad.hip): scores [B, N, M] (float32 or float64), the bin
+    score, ``iters`` >= 0 and dZ = dL/dZ [B, N+1, M+1] (any dtype and strides) -> (dscores [B, N, M] in the scores' dtype, dbin [B]
+    float64: the bin score's gradient per pair).  The arithmetic is fp64 for both input dtypes.  N, M <= 2175."""
+    _need_cuda(scores, dZ)
+    if scores.dim() != 3:
+        raise ValueError(f'scores must be [B, N, M], got {tuple(scores.shape)}')
+    B, N, M = scores.shape
+    if tuple(dZ.shape) != (B, N + 1, M + 1):
+        raise ValueError(f'dZ {tuple(dZ.shape)} does not fit scores {tuple(scores.shape)}: expected [{B}, {N + 1}, {M + 1}]')
+    if dZ.device != scores.device:
+        raise ValueError(f'dZ is on {dZ.device}, scores on {scores.device}')
+    s = scores.to(torch.float64).contiguous()
+    g = dZ.to(torch.float64).contiguous()          # (Z.sum().backward() hands over an expanded, stride-0 tensor)
+    dscores = torch.empty((B, N, M), dtype=torch.float64, device=s.device)
+    dbin = torch.empty((B,), dtype=torch.float64, device=s.device)
+    lib = _lib.load()
+    with torch.cuda.device(s.device):
+        need = lib.mdgat_sinkhorn_backward_workspace_bytes(B, N, M, int(iters))
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
+        off = (-ws.data_ptr()) % 256
+        _lib.check(lib.mdgat_sinkhorn_backward(B, N, M, s.data_ptr(), float(bin_score), int(iters), g.data_ptr(), dscores.data_ptr(),
+                                               dbin.data_ptr(), ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_backward')
+    return dscores.to(scores.dtype), dbin
+
+
+_ARITHMETIC = ('auto', 'fp32', 'fp64')
+
+
+class _LogOptimalTransport(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, alpha, iters, arithmetic):
+        a = float(alpha)
+        f64 = arithmetic == 'fp64' or (arithmetic == 'auto' and scores.dtype == torch.float64)
+        Z = (sinkhorn_f64 if f64 else sinkhorn)(scores, a, iters).to(scores.dtype)
+        ctx.save_for_backward(scores)
+        ctx.alpha, ctx.iters = a, iters
+        ctx.alpha_like = alpha if isinstance(alpha, torch.Tensor) else None
+        return Z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dZ):
+        scores, = ctx.saved_tensors
+        dscores, dbin = sinkhorn_backward(scores, ctx.alpha, ctx.iters, dZ)
+        dalpha = None
+        if ctx.needs_input_grad[1]:
+            al = ctx.alpha_like
+            dalpha = dbin.sum().to(device=al.device, dtype=al.dtype).reshape(al.shape)
+        return (dscores if ctx.needs_input_grad[0] else None), dalpha, None, None
+
+
+def log_optimal_transport(scores: torch.Tensor, alpha, iters: int, arithmetic: str = 'auto') -> torch.Tensor:
+    """Differentiable log_optimal_transport (mdgat.py:288-308): scores [B, N, M] -> Z [B, N+1, M+1] in the scores' dtype.
+
+    The forward is ``sinkhorn_f64`` for float64 scores and ``sinkhorn`` for float32 ones (``arithmetic='fp32'`` / ``'fp64'`` pins one,
+    the vocabulary of MDGAT's ``arithmetic`` config key); the backward is the fp64 kernel of ``sinkhorn_backward`` for both.  Gradients
+    flow to ``scores`` and to ``alpha`` when it is a tensor that requires grad (summed over the batch, alpha's shape and dtype).
+    Not twice differentiable; N, M <= 2175 for the backward."""
+    if arithmetic not in _ARITHMETIC:
+        raise ValueError(f'arithmetic must be one of {_ARITHMETIC}, got {arithmetic!r}')
+    _need_cuda(scores)
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'scores must be float32 or float64, got {scores.dtype}')
+    return _LogOptimalTransport.apply(scores, alpha, int(iters), arithmetic)
+
+
 def extract(Z: torch.Tensor, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2):
     """Match extraction (mdgat.py:441-483) from Z [B, N+1, M+1]."""
     _need_cuda(Z)
