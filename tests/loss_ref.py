@@ -52,7 +52,8 @@ def pair_losses(Z, gt0, gt1, method, gamma=0.5):
             row = np.where(keep_r, clamp0(t(pos_r)[:, None] - tz[:n, :] + gamma), 0.0).sum(axis=1)
             # The column half is not per column of Z.  The reference lists the m positives Z[gt1(j), j] and the n m other entries of
             # Z[:, :m] each in ROW-MAJOR order and lays the second list out as an n x m matrix V: term c pairs the c-th positive in
-            # that order with column c of V.  (Per column of Z only when the positives' rows increase with j.)
+            # that order with column c of V.  (Per column of Z only when every positive lies in the dustbin row: positives' rows that
+            # increase with j put P in column order, but V's entries still shift by the positives taken out before them.)
             P = tz[:, :m][~keep_c]                       # t of the positives, row-major
             V = tz[:, :m][keep_c].reshape(n, m)          # t of the others, row-major, n x m
             col = clamp0(P[None, :] - V + gamma).sum(axis=0)
@@ -66,3 +67,45 @@ def module_loss(Z, gt0, gt1, method, gamma=0.5):
     """What the reference's forward returns as 'loss': 0-d mean for superglue / triplet, [B] for gap."""
     v = pair_losses(Z, gt0, gt1, method, gamma)
     return v if method == 'gap_loss' else np.float64(v.mean())
+
+
+# ---- ground-truth patterns for the kernel tests (tests/test_gpu_loss.py) ----
+GT_PATTERNS = ('partial', 'reversed', 'all_dustbin', 'non_injective', 'explicit_dustbin')
+
+
+def gt_pattern(name, n, m, rs):
+    """(gt0 [n], gt1 [m]) int64 of one pair.  rs: a numpy RandomState.
+    partial:          a random partial matching (3/5 of min(n, m) pairs), the rest -1;
+    reversed:         the first min(n, m) rows and columns matched in reverse (gt1[j] = k - 1 - j): the positives' rows fall with j,
+                      so gap's row-major P is the columns backwards;
+    all_dustbin:      every gt -1: all positives in the dustbin row / column;
+    non_injective:    gt1 sends the first half of the columns to row 0 and the rest to row n // 2 (one row holds >= m / 2 positives),
+                      gt0 random in [-1, m);
+    explicit_dustbin: partial, with about half of the unmatched entries given as the dustbin index itself (m in gt0, n in gt1)."""
+    g0 = np.full(n, -1, dtype=np.int64)
+    g1 = np.full(m, -1, dtype=np.int64)
+    if name in ('partial', 'explicit_dustbin'):
+        k = max(1, 3 * min(n, m) // 5)
+        rows, cols = rs.permutation(n)[:k], rs.permutation(m)[:k]
+        g0[rows], g1[cols] = cols, rows
+        if name == 'explicit_dustbin':
+            g0[(g0 == -1) & (rs.rand(n) < 0.5)] = m
+            g1[(g1 == -1) & (rs.rand(m) < 0.5)] = n
+    elif name == 'reversed':
+        k = min(n, m)
+        g0[:k] = np.arange(k - 1, -1, -1)
+        g1[:k] = np.arange(k - 1, -1, -1)
+    elif name == 'non_injective':
+        g1[:] = n // 2
+        g1[:m // 2] = 0
+        g0[:] = rs.randint(-1, m, n)
+    elif name != 'all_dustbin':
+        raise ValueError(name)
+    return g0, g1
+
+
+def gt_batch(names, n, m, seed):
+    """gt0 [B, n], gt1 [B, m]: pair b gets pattern names[b]."""
+    rs = np.random.RandomState(seed)
+    pairs = [gt_pattern(p, n, m, rs) for p in names]
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])

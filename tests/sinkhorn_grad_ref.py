@@ -74,6 +74,37 @@ def oracle_grad(scores, alpha, iters, dZ):
     return s.grad.detach(), al.grad.detach()
 
 
+# ---- which skg_reverse_kernel<NC2> a shape runs (the launcher of csrc/sinkhorn_grad.hip), for the coverage check of the GPU tests ----
+REVERSE_VARIANTS = (5, 9, 17)
+
+
+def reverse_dispatch(M):
+    """(Mp, nc2, variant) for M columns: Mp = M + 1 rounded up to 128, nc2 = Mp / 128 column pairs per lane, and the instantiation
+    skg_reverse_kernel<variant> the launcher picks (the first with nc2 <= variant).  Column pairs c >= nc2 are masked when nc2 < variant."""
+    Mp = (M + 1 + 127) // 128 * 128
+    nc2 = Mp // 128
+    for v in REVERSE_VARIANTS:
+        if nc2 <= v:
+            return Mp, nc2, v
+    raise ValueError(f'M = {M}: beyond the backward\'s {128 * REVERSE_VARIANTS[-1] - 1} columns')
+
+
+# (B, N, M, T) of tests/test_gpu_sinkhorn_grad.py::test_fp64_reverse_variants: every instantiation with and without masking, both sides
+# of each switch (M = 639 | 640, 1151 | 1152, 2047 | 2048), N + 1 and M + 1 on and off multiples of the coupling kernel's 64 x 64 tiles,
+# N on and off the 32-row slabs, odd and even T (2T = 2 mod 4: the coupling kernel's tail), one row, one column.
+# tests/test_sinkhorn_grad_ref.py::test_reverse_variant_cases_cover_every_path keeps this list honest.
+VARIANT_CASES = (
+    (2, 63, 639, 7),
+    (1, 64, 640, 20),
+    (1, 127, 1151, 1),
+    (1, 128, 1152, 100),
+    (1, 300, 2047, 7),
+    (1, 191, 2048, 200),
+    (1, 1, 2048, 5),
+    (1, 2175, 1, 20),
+)
+
+
 def max_rel(a, b):
     """max |a - b| / max |b| (1 where b is all zero and a is not)."""
     a = torch.as_tensor(a, dtype=torch.float64)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from loss_ref import pair_losses
+from loss_ref import GT_PATTERNS, gt_batch, pair_losses
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +95,125 @@ def test_matching_loss_refuses_bad_input(g):
         ops.matching_loss(Z, g0, g1, 'triplet_loss')
     with pytest.raises(ValueError):
         ops.matching_loss(Z, g0[:, :-1], g1, 'gap_loss')
+
+
+# ------------------------------------------------------------------------------------------------ the kernel at the shapes it runs
+def _rel(got, want):
+    """the largest |got - want| / |want| over the finite values (0 where there are none; inf where want is 0 and got is not)"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    fin = np.isfinite(want) & np.isfinite(got)
+    err, den = np.abs(got[fin] - want[fin]), np.abs(want[fin])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return float(np.max(np.where(err == 0, 0.0, err / den), initial=0.0))
+
+
+def _lp_Z(B, n, m, seed):
+    """log-probabilities as the module's Z: ops.sinkhorn_f64 of random scores, fp64 on the device (a spread of +-15 and a bin score of
+    0: the dustbin does not outweigh every inner entry, and every gt pattern gives every loss a nonzero value up to 2048 keypoints)"""
+    from mdgat_matcher_amd import ops
+    gen = torch.Generator().manual_seed(seed)
+    s = (torch.rand(B, n, m, generator=gen, dtype=torch.float64) * 2 - 1) * 15
+    return ops.sinkhorn_f64(s.to(DEV), 0.0, 20)
+
+
+def _check_methods(Z, g0, g1, methods, rtol64=1e-11, rtol32=1e-10):
+    """ops.matching_loss on Z (fp64, on the device) and on its fp32 rounding against pair_losses of the same values."""
+    from mdgat_matcher_amd import ops
+    t0, t1 = torch.from_numpy(g0).to(DEV), torch.from_numpy(g1).to(DEV)
+    Z32 = Z.to(torch.float32)
+    for meth in methods:
+        for Zd, rtol in ((Z, rtol64), (Z32, rtol32)):
+            got = ops.matching_loss(Zd, t0, t1, meth, 0.5).cpu().numpy()
+            want = pair_losses(Zd.cpu().double().numpy(), g0, g1, meth, 0.5)
+            assert np.all(want != 0), (meth, want)          # (a pattern whose loss is 0 would test little)
+            print(f'{meth} {str(Zd.dtype)[6:]} {_rel(got, want):.1e}', end='; ')
+            _close(got, want, rtol)
+    print()
+
+
+# one pair per gt pattern of loss_ref.gt_pattern: P's order across the 256-column chunks of loss_gap_order_kernel, a row with hundreds
+# of positives for nth_other, every positive in the dustbin row, explicit dustbin indices (superglue counts only a literal -1)
+@pytest.mark.parametrize('n', [255, 256, 257, 511, 2048])
+def test_matching_loss_square_frames(n):
+    g0, g1 = gt_batch(GT_PATTERNS, n, n, seed=n)
+    _check_methods(_lp_Z(len(GT_PATTERNS), n, n, seed=n), g0, g1, METHODS)
+
+
+# gap takes ragged pairs: N > M, N < M, one row, one column, and the tile kernel's 16-row tiles full (15 + the dustbin row) and with a
+# second tile of the dustbin row alone
+@pytest.mark.parametrize('n,m', [(700, 300), (300, 700), (1, 2048), (2048, 1), (15, 600), (16, 600)])
+def test_gap_loss_ragged_frames(n, m):
+    g0, g1 = gt_batch(GT_PATTERNS, n, m, seed=n + m)
+    _check_methods(_lp_Z(len(GT_PATTERNS), n, m, seed=n + m), g0, g1, ('gap_loss',))
+
+
+def test_matching_loss_planted_beyond_the_first_256_columns():
+    """Entries in exp's subnormal band and below its underflow in columns >= 256 (the second round of the tile kernel's column loop
+    and of gap's column pass): positives and negatives of rows and columns, and the dustbin row, as make_goldens_loss.plant does."""
+    from mdgat_matcher_amd import ops
+    n = m = 511
+    g0, g1 = gt_batch(GT_PATTERNS, n, m, seed=3)
+    Z = _lp_Z(len(GT_PATTERNS), n, m, seed=3).cpu().numpy()
+    rs = np.random.RandomState(3)
+    for b in range(len(GT_PATTERNS)):
+        p0, p1 = np.where(g0[b] == -1, m, g0[b]), np.where(g1[b] == -1, n, g1[b])
+        for i in range(0, n, 5):
+            if p0[i] >= 256:
+                Z[b, i, p0[i]] = rs.uniform(-740.0, -709.0)
+            Z[b, i, 256 + i % (m + 1 - 256)] = rs.uniform(-740.0, -709.0)
+        for j in range(257, m, 7):
+            Z[b, p1[j], j] = rs.uniform(-740.0, -709.0)
+            Z[b, (p1[j] + 3) % (n + 1), j] = rs.uniform(-760.0, -745.2)
+        Z[b, n, 257::9] = rs.uniform(-740.0, -709.0, Z[b, n, 257::9].shape[0])
+    assert ((Z[:, :, 256:] > -740) & (Z[:, :, 256:] < -709)).any() and (Z[:, :, 256:] < -745.2).any()
+    t0, t1 = torch.from_numpy(g0).to(DEV), torch.from_numpy(g1).to(DEV)
+    finite = 0
+    for z in (Z, Z.astype(np.float32)):
+        for meth in METHODS:
+            got = ops.matching_loss(torch.from_numpy(z).to(DEV), t0, t1, meth, 0.5).cpu().numpy()
+            want = pair_losses(z.astype(np.float64), g0, g1, meth, 0.5)
+            print(f'{meth} {z.dtype} {_rel(got, want):.1e}', end='; ')
+            # (the subnormal band of exp: device and host exp / log may round a subnormal differently)
+            _close(got, want, 1e-6)
+            finite += int(np.isfinite(want).sum())
+    print()
+    assert finite > 0
+
+
+def test_matching_loss_pairs_are_bitwise_batch_independent():
+    """Six pairs of 512, each with another gt pattern: every pair alone gives its row of the batch, every method, fp64 and fp32 Z."""
+    from mdgat_matcher_amd import ops
+    g0, g1 = gt_batch(GT_PATTERNS + ('partial',), 512, 512, seed=6)
+    t0, t1 = torch.from_numpy(g0).to(DEV), torch.from_numpy(g1).to(DEV)
+    Z = _lp_Z(6, 512, 512, seed=6)
+    worst = 0.0
+    for Zd in (Z, Z.to(torch.float32)):
+        for meth in METHODS:
+            batch = ops.matching_loss(Zd, t0, t1, meth, 0.5)
+            for b in range(6):
+                alone = ops.matching_loss(Zd[b:b + 1], t0[b:b + 1], t1[b:b + 1], meth, 0.5)
+                worst = max(worst, (alone - batch[b:b + 1]).abs().max().item())
+                assert torch.equal(alone, batch[b:b + 1]), (meth, Zd.dtype, b)
+    print(f'max |alone - batch| = {worst:.1e}')
+
+
+def test_gap_loss_at_its_row_limit():
+    """N = 15000 (loss_gap_order_kernel's N + 2 row counters in LDS: 60 KB) is computed; 15001 is refused; the next call is right."""
+    from mdgat_matcher_amd import ops
+    n, m = 15000, 3
+    rs = np.random.RandomState(15000)
+    Z = np.log(rs.uniform(1e-6, 1.0, (1, n + 1, m + 1))) - 6.0
+    g0, g1 = gt_batch(['explicit_dustbin'], n, m, seed=15000)
+    want = pair_losses(Z, g0, g1, 'gap_loss', 0.5)
+    args = (torch.from_numpy(Z).to(DEV), torch.from_numpy(g0).to(DEV), torch.from_numpy(g1).to(DEV), 'gap_loss', 0.5)
+    got = ops.matching_loss(*args).cpu().numpy()
+    print(f'N=15000: {_rel(got, want):.1e}')
+    _close(got, want, 1e-11)
+    with pytest.raises(RuntimeError, match='15000'):
+        ops.matching_loss(torch.zeros(1, n + 2, m + 1, dtype=torch.float64, device=DEV), torch.zeros(1, n + 1, dtype=torch.int64, device=DEV),
+                          torch.zeros(1, m, dtype=torch.int64, device=DEV), 'gap_loss', 0.5)
+    again = ops.matching_loss(*args).cpu().numpy()
+    assert np.array_equal(again, got)
 
 
 # ------------------------------------------------------------------------------------------------ the module, exact mode
@@ -233,6 +352,11 @@ def test_exact_mode_two_pairs_of_2048():
     assert torch.isfinite(loss).all() and int(req['bad'].item()) == 0
     # the fp32 rounding of the same Z: within what rounding Z to fp32 moves the loss
     np.testing.assert_allclose(loss.numpy(), z32.cpu().numpy(), rtol=1e-4)
+    # and the kernel on that Z against the restatement: the rounded Z's loss exactly, the forward's own within the rounding
+    want = pair_losses(Z.cpu().double().numpy(), d['gt_matches0'].cpu().numpy(), d['gt_matches1'].cpu().numpy(), 'gap_loss', 0.5)
+    print(f'Z {Z.dtype}: {_rel(z32.cpu().numpy(), want):.1e} against the restatement')
+    _close(z32.cpu().numpy(), want, 1e-10)
+    np.testing.assert_allclose(loss.numpy(), want, rtol=1e-4)
 
 
 # ------------------------------------------------------------------------------------------------ contract

@@ -1,6 +1,7 @@
 """The backward of log_optimal_transport (csrc/sinkhorn_grad.hip; ops.sinkhorn_backward, ops.log_optimal_transport and the drop-in
-models.mdgat.log_optimal_transport) against the reference's autograd gradients (tests/golden/sk_grad.npz) and against torch autograd
-of the fp64 oracle on the CPU."""
+models.mdgat.log_optimal_transport) against the reference's autograd gradients (tests/golden/sk_grad.npz), against torch autograd
+of the fp64 oracle on the CPU, and against the fp64 restatement (tests/sinkhorn_grad_ref.py) at the shapes of every kernel variant and
+of training."""
 import importlib
 import math
 import os
@@ -10,7 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-from sinkhorn_grad_ref import max_rel, oracle_grad
+from loss_ref import gt_batch
+from sinkhorn_grad_ref import VARIANT_CASES, max_rel, oracle_grad, reverse_dispatch, sinkhorn_grad
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +59,7 @@ def test_fp64_against_reference_goldens(golden_dir, case):
     (2, 33, 20, 100, 100.0, 1.0),
     (1, 50, 70, 100, 2.0, 6.0),
     (1, 600, 130, 3, 5.0, 1.0),
+    (1, 300, 700, 10, 4.0, 1.0),          # skg_reverse_kernel<9>: autograd, not the scaling form of the restatement
 ])
 def test_fp64_against_oracle_autograd(B, N, M, T, spread, alpha):
     gen = torch.Generator().manual_seed(N * 131 + M * 7 + T)
@@ -75,6 +78,104 @@ def test_fp64_at_the_streaming_limit():
     ds, da = _grads(s, 1.0, 5, dZ)
     ref_ds, ref_da = oracle_grad(s, 1.0, 5, dZ)
     _check(ds, da, ref_ds, ref_da, 1e-8)
+
+
+# ---- against the fp64 restatement (tests/sinkhorn_grad_ref.py) at the shapes and values the small cases above do not reach ----
+def _check_pairs(ds, dbin, ref_ds, ref_da, tol):
+    """d scores and every pair's d bin score of ops.sinkhorn_backward within tol of max|g| of the restatement's."""
+    e_s, e_a = max_rel(ds, ref_ds), max_rel(dbin, ref_da)
+    print(f'dscores {e_s:.2e} of max|g|, dalpha {e_a:.2e} of max|dalpha|')
+    assert torch.isfinite(ds).all() and torch.isfinite(dbin).all()
+    assert e_s < tol and e_a < tol, (e_s, e_a)
+
+
+def _against_restatement(s, alpha, T, dZ):
+    ds, dbin = _ops().sinkhorn_backward(s.to(DEV), alpha, T, dZ.to(DEV))
+    ref_ds, ref_da = sinkhorn_grad(s, alpha, T, dZ)
+    _check_pairs(ds.cpu(), dbin.cpu(), ref_ds, ref_da, 1e-8)
+
+
+def _uniform(B, N, M, spread, gen):
+    return (torch.rand(B, N, M, generator=gen, dtype=torch.float64) * 2 - 1) * spread
+
+
+def _model_scores(B, N, M, seed, D=64):
+    """Scores as the model forms them: the scaled dot product of descriptors (final_proj, / sqrt(D)), standard deviation 2: about +-10."""
+    gen = torch.Generator().manual_seed(seed)
+    d0 = torch.randn(B, D, N, generator=gen, dtype=torch.float64)
+    d1 = torch.randn(B, D, M, generator=gen, dtype=torch.float64)
+    return torch.einsum('bdn,bdm->bnm', d0, d1) / D ** .5 * 2.0
+
+
+def _superglue_dZ(B, N, M, seed):
+    """dL/dZ of the superglue loss (_superglue_loss below) for random partial matches: -1 / (unmatched columns + M) / B at every row's
+    gt entry (the dustbin column for an unmatched row) and at the dustbin row of every unmatched column, zero elsewhere."""
+    gt0, gt1 = (torch.from_numpy(g) for g in gt_batch(['partial'] * B, N, M, seed))
+    Z = torch.zeros(B, N + 1, M + 1, dtype=torch.float64, requires_grad=True)
+    _superglue_loss(Z, gt0, gt1).backward()
+    assert int((Z.grad != 0).sum()) == B * N + int((gt1 == -1).sum())
+    return Z.grad
+
+
+@pytest.mark.parametrize('B,N,M,T', VARIANT_CASES)
+def test_fp64_reverse_variants(B, N, M, T):
+    """skg_reverse_kernel<5 / 9 / 17> with and without masked column pairs, and the history-writing streaming forward in each
+    (the shape list and what it covers: sinkhorn_grad_ref.VARIANT_CASES, checked on the CPU by test_sinkhorn_grad_ref.py)."""
+    print(f'M={M}: Mp, nc2, variant = {reverse_dispatch(M)}', end='; ')
+    gen = torch.Generator().manual_seed(N * 7 + M * 131 + T)
+    _against_restatement(_uniform(B, N, M, 4.0, gen), 1.0, T, torch.randn(B, N + 1, M + 1, generator=gen, dtype=torch.float64))
+
+
+# a score spread of +-100, and dustbin-heavy pairs (alpha above every score), in <9> (900 columns: nc2 8) and <17> (1500: nc2 12)
+@pytest.mark.parametrize('B,N,M,T,spread,alpha', [
+    (1, 200, 900, 50, 100.0, 1.0),
+    (1, 200, 900, 50, 2.0, 6.0),
+    (2, 150, 1500, 30, 100.0, 1.0),
+    (1, 150, 1500, 30, 2.0, 6.0),
+])
+def test_fp64_hard_values_in_the_wide_variants(B, N, M, T, spread, alpha):
+    gen = torch.Generator().manual_seed(N + M + T + int(spread))
+    _against_restatement(_uniform(B, N, M, spread, gen), alpha, T, torch.randn(B, N + 1, M + 1, generator=gen, dtype=torch.float64))
+
+
+# BASELINE's training shapes: 64 pairs of 512 at T = 100 (eight of them here) and pairs of 2048 at T = 200
+@pytest.mark.parametrize('B,N,T', [(8, 512, 100), (1, 2048, 200)])
+@pytest.mark.parametrize('dz', ['dense', 'superglue'])
+def test_fp64_at_production_shapes(B, N, T, dz):
+    s = _model_scores(B, N, N, seed=N + T)
+    if dz == 'dense':
+        dZ = torch.randn(B, N + 1, N + 1, generator=torch.Generator().manual_seed(N), dtype=torch.float64)
+    else:
+        dZ = _superglue_dZ(B, N, N, seed=N)
+    _against_restatement(s, 1.0, T, dZ)
+
+
+def test_fp32_inputs_at_2048():
+    s = _model_scores(1, 2048, 2048, seed=2048).to(torch.float32)
+    dZ = torch.randn(1, 2049, 2049, generator=torch.Generator().manual_seed(1), dtype=torch.float32)
+    x = s.to(DEV).requires_grad_(True)
+    al = torch.tensor(1.0, dtype=torch.float32, device=DEV, requires_grad=True)
+    Z = _ops().log_optimal_transport(x, al, 100)
+    assert Z.dtype == torch.float32
+    Z.backward(dZ.to(DEV))
+    assert x.grad.dtype == torch.float32 and al.grad.dtype == torch.float32
+    ref_ds, ref_da = sinkhorn_grad(s.double(), 1.0, 100, dZ.double())
+    _check(x.grad.cpu().double(), al.grad.cpu().double(), ref_ds, ref_da.sum(), 1e-6)
+
+
+@pytest.mark.parametrize('N,M', [(700, 900), (300, 1500)])
+def test_wide_variants_are_bitwise_batch_independent(N, M):
+    """<9> (900 columns) and <17> (1500): every pair of a batch of three alone gives its slice's bits."""
+    gen = torch.Generator().manual_seed(N + M)
+    S = _uniform(3, N, M, 20.0, gen).to(DEV)
+    G = torch.randn(3, N + 1, M + 1, generator=gen, dtype=torch.float64).to(DEV)
+    ds3, db3 = _ops().sinkhorn_backward(S, 1.5, 30, G)
+    worst = 0.0
+    for b in range(3):
+        ds1, db1 = _ops().sinkhorn_backward(S[b:b + 1], 1.5, 30, G[b:b + 1])
+        worst = max(worst, (ds1 - ds3[b:b + 1]).abs().max().item(), (db1 - db3[b:b + 1]).abs().max().item())
+        assert torch.equal(ds1, ds3[b:b + 1]) and torch.equal(db1, db3[b:b + 1]), b
+    print(f'max |alone - batch| = {worst:.1e}')
 
 
 def test_gradcheck_scores_and_alpha():

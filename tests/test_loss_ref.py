@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from loss_ref import module_loss, pair_losses, t
+from loss_ref import GT_PATTERNS, clamp0, gt_batch, module_loss, pair_losses, t
 
 METHODS = ('superglue', 'triplet_loss', 'gap_loss')
 
@@ -97,3 +97,51 @@ def test_pair_losses_shapes():
     for meth in METHODS:
         assert pair_losses(Z, g0, g1, meth).shape == (3,)
     assert np.ndim(module_loss(Z, g0, g1, 'triplet_loss')) == 0
+
+
+def _gap_per_column(Z, gt0, gt1, gamma=0.5):
+    """gap_loss with its column half taken naively per column of Z (column j: its positive against the other rows of that column).  The
+    reference's row-major reordering comes to this when every positive lies in the dustbin row (V is then the inner rows of Z, P the
+    dustbin row in column order), not in general."""
+    out = []
+    for z, g0, g1 in zip(np.asarray(Z, dtype=np.float64), gt0, gt1):
+        n, m = z.shape[0] - 1, z.shape[1] - 1
+        p0, p1 = np.where(g0 == -1, m, g0), np.where(g1 == -1, n, g1)
+        tz = t(z)
+        keep_r = np.ones((n, m + 1), dtype=bool)
+        keep_r[np.arange(n), p0] = False
+        row = np.where(keep_r, clamp0(tz[np.arange(n), p0][:, None] - tz[:n] + gamma), 0.0).sum(axis=1)
+        keep_c = np.ones((n + 1, m), dtype=bool)
+        keep_c[p1, np.arange(m)] = False
+        col = np.where(keep_c, clamp0(tz[p1, np.arange(m)][None, :] - tz[:, :m] + gamma), 0.0).sum(axis=0)
+        out.append((np.mean(2 * np.log(row + 1)) + np.mean(2 * np.log(col + 1))) / 2)
+    return np.array(out)
+
+
+def test_gt_patterns_reach_gaps_reordering():
+    """The gt patterns of the kernel tests (loss_ref.gt_pattern, tests/test_gpu_loss.py) at 511 x 511: a per-column column half is far
+    from the reference's wherever the row-major reordering matters, P's order crosses the 256-column chunks of the kernel's stable
+    ranking, one row holds >= 256 positives - and with every positive in the dustbin row the two forms agree."""
+    from oracle import mdgat_oracle as O
+    n = m = 511
+    s = (torch.rand(len(GT_PATTERNS), n, m, generator=torch.Generator().manual_seed(511), dtype=torch.float64) * 2 - 1) * 15
+    Z = O.log_optimal_transport(s, torch.tensor(0.0, dtype=torch.float64), 20).numpy()   # (as test_gpu_loss._lp_Z)
+    g0, g1 = gt_batch(GT_PATTERNS, n, m, seed=511)
+    ref = pair_losses(Z, g0, g1, 'gap_loss')
+    naive = _gap_per_column(Z, g0, g1)
+    assert np.all(np.isfinite(ref)) and np.all(ref > 0)
+    for b, name in enumerate(GT_PATTERNS):
+        p1 = np.where(g1[b] == -1, n, g1[b])
+        order = np.argsort(p1, kind='stable')                      # the columns in P's (row-major) order
+        crosses = bool(np.any(order // 256 != np.arange(m) // 256))
+        rel = abs(naive[b] - ref[b]) / abs(ref[b])
+        if name == 'all_dustbin':
+            assert rel < 1e-12 and not crosses, (name, rel)
+        else:
+            assert rel > 1e-6, (name, rel)                          # the kernel tests hold the kernel to 1e-11
+        if name in ('partial', 'reversed', 'explicit_dustbin'):
+            assert crosses, name
+        if name == 'non_injective':
+            assert np.bincount(p1).max() >= 256
+        if name == 'explicit_dustbin':
+            assert (g0[b] == m).any() and (g0[b] == -1).any() and (g1[b] == n).any() and (g1[b] == -1).any()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from sinkhorn_grad_ref import max_rel, oracle_grad, sinkhorn_grad
+from sinkhorn_grad_ref import REVERSE_VARIANTS, VARIANT_CASES, max_rel, oracle_grad, reverse_dispatch, sinkhorn_grad
 
 CASES = ('b2n64m48', 'n120m180', 'n7m5')
 
@@ -45,3 +45,30 @@ def test_zero_iterations_is_the_identity_on_the_couplings():
     ds, da = sinkhorn_grad(s, 0.25, 0, dZ)
     assert torch.equal(ds, dZ[:, :4, :6])
     assert torch.allclose(da, dZ[:, 4, :].sum(1) + dZ[:, :4, 6].sum(1), rtol=0, atol=1e-14)
+
+
+def test_reverse_dispatch_mirrors_the_launcher():
+    assert reverse_dispatch(1) == (128, 1, 5)
+    assert reverse_dispatch(639) == (640, 5, 5) and reverse_dispatch(640) == (768, 6, 9)
+    assert reverse_dispatch(1151) == (1152, 9, 9) and reverse_dispatch(1152) == (1280, 10, 17)
+    assert reverse_dispatch(2047) == (2048, 16, 17) and reverse_dispatch(2175) == (2176, 17, 17)
+    with pytest.raises(ValueError):
+        reverse_dispatch(2176)
+
+
+def test_reverse_variant_cases_cover_every_path():
+    """The shapes of the GPU's test_fp64_reverse_variants reach every skg_reverse_kernel instantiation with and without its masked
+    column pairs, both sides of every switch, both tile-edge states of rows and columns, both slab states and both T parities."""
+    Ms = {M for _, _, M, _ in VARIANT_CASES}
+    paths = {(reverse_dispatch(M)[2], reverse_dispatch(M)[1] < reverse_dispatch(M)[2]) for M in Ms}
+    assert paths == {(v, masked) for v in REVERSE_VARIANTS for masked in (False, True)}, paths
+    # both sides of every switch (test_reverse_dispatch_mirrors_the_launcher): <5> | <9>, <9> | <17>, <17> masked | unmasked
+    assert {639, 640, 1151, 1152, 2047, 2048} <= Ms
+    assert {(N + 1) % 64 == 0 for _, N, _, _ in VARIANT_CASES} == {False, True}
+    assert {(M + 1) % 64 == 0 for _, _, M, _ in VARIANT_CASES} == {False, True}
+    assert {N % 32 == 0 for _, N, _, _ in VARIANT_CASES} == {False, True}
+    assert {(2 * T) % 4 for _, _, _, T in VARIANT_CASES} == {0, 2}
+    assert {1, 7, 20, 100, 200} <= {T for _, _, _, T in VARIANT_CASES}
+    assert (1, 1, 2048) in {(B, N, M) for B, N, M, _ in VARIANT_CASES}
+    assert (1, 2175, 1) in {(B, N, M) for B, N, M, _ in VARIANT_CASES}
+    assert any(B > 1 for B, _, _, _ in VARIANT_CASES)
