@@ -27,14 +27,6 @@
 #include "common.hpp"
 #include <cstdlib>
 
-#ifdef WIDE_TRACE
-__device__ long long g_wide_trace[4 * 8];
-extern "C" int mdgat_wide_trace_read(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wide_trace), n * sizeof(long long)); }
-#define WT(k) do { if (blockIdx.x == 8 * 5 + 3 && (threadIdx.x & 63) == 0 && ((threadIdx.x >> 6) == 0 || (threadIdx.x >> 6) == 7)) \
-    g_wide_trace[((threadIdx.x >> 6) == 7) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WT(k) do {} while (0)
-#endif
 namespace {
 
 constexpr int KROWH = 72;   // K row in LDS, halves: 32 hi | 32 lo | 8 pad (144 B = 9 x 16 B: conflict free)
@@ -1102,7 +1094,6 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
         // reloaded from scratch in front of each block's loads: a scratch reload waits for EVERY load in flight.  Keys a ragged
         // last block reaches beyond the frame are out of range and load as zeros (masked below).
         f16x8 kf[NBLK][4];
-        WT(0);
 #pragma unroll
         for (int jb = 0; jb < NBLK; ++jb) {
             const int gb = kw * NBLK + jb;
@@ -1141,16 +1132,13 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        WT(1);
         float m = NEG_INF;
 #pragma unroll
         for (int jb = 0; jb < NBLK; ++jb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) m = fmaxf(m, S[jb][r]);
-        WT(2);
         // (m goes in as this wave's part of the row maximum and comes back as the row's: it travels with the search's statistics)
         const float thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, a.zq, comm, whole);
-        WT(3);
         // Exact ties at the k-th place (topk_break_ties; about one tile in 10^4).  The pass below counts what it keeps (softmax8); the
         // counts travel to LDS with the output partials, every wave sums them for the rows of the workgroup's query groups, and only
         // a tile that kept too much drops the surplus in the registers and runs the pass once more.  (Until round 6 a counting pass
@@ -1179,7 +1167,6 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
                 }
         }
 
-        WT(4);
         const float m11 = m - 11.0f;
         bool redone = TAP;
 #pragma unroll 1
@@ -1220,7 +1207,6 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
                 }
             }
         }
-        WT(5);
         float l = l2[0] + l2[1];
         l += xor32(l);
         int kc = kept_count(kept);
@@ -1273,7 +1259,6 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
             }
         }
         __syncthreads();     // obuf is reused by the next pass
-        WT(7);
     }
 }
 

@@ -33,16 +33,6 @@
 #include "common.hpp"
 #include "f64.hpp"
 #include "f64_dev.hpp"
-#ifdef F64_TRACE
-// measurement build only (tools/ab_build.sh f64 trace -DF64_TRACE; tools/f64_trace.py): s_memtime at the phase boundaries of the
-// dynamic kernel, waves 0 and 3 of one workgroup in the middle of the grid
-__device__ long long g_f64_trace[2 * 32];
-extern "C" int mdgat_f64_trace_read(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_f64_trace), n * sizeof(long long)); }
-#define FT(k) do { if (blockIdx.x == gridDim.x / 2 + 3 && (threadIdx.x & 63) == 0 && ((threadIdx.x >> 6) == 0 || (threadIdx.x >> 6) == 3)) \
-    g_f64_trace[((threadIdx.x >> 6) == 3) * 32 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define FT(k) do {} while (0)
-#endif
 
 #include "row_search.hpp"
 #include "exp2_tab256.hpp"
@@ -451,7 +441,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             }
         }
     } else {
-        FT(0);
         // ---- dynamic attention, pass A: fp32 roundings of the logits -> LDS, row maxima ----
         f64x4 Sk[KEEP ? 8 : 1];
         if (KEEP) {
@@ -495,13 +484,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             }
             if (tid < QT) sm.lcount[tid] = 0;
         }
-        FT(1);
         __syncthreads();
-        FT(2);
         // ---- the exact k-th largest rounding of every row ----
         if (KEEP) {
             // at most 512 keys: the wave's four rows (4 wave .. 4 wave + 3) side by side, sixteen lanes each (row_search.hpp)
-#ifndef F64_KO_SEARCH
             const float* rows = sm.img + 4 * wave * imgld;
             const bool own_space = imgld >= RQ_HIST_INTS;
             int* hb = own_space ? reinterpret_cast<int*>(sm.img + 4 * wave * imgld) : sm.hist + wave * 4 * RQ_HIST_INTS;
@@ -514,24 +500,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             else if (r.c_ge - r.c_gt <= A_LIST) rs = RowSel{r.thr, 2, a.topk - r.c_gt, 0};
             else rs = RowSel{r.thr, 1, r.keylim, 0};
             if ((lane & 15) == 0) sm.sel[4 * wave + (lane >> 4)] = rs;
-#else
-            if (lane < 4) sm.sel[4 * wave + lane] = RowSel{0.f, 0, 0, 0};
-#endif
         } else
         for (int q = wave; q < QT; q += 4) {
             const float* row = sm.img + q * imgld;
             int* hist = sm.hist + wave * RS_HIST_INTS;
-#ifdef F64_KO_SEARCH
-            if (lane == 0) sm.sel[q] = RowSel{0.f, 0, 0, 0};
-            continue;
-#endif
             const RowSel rs = nk <= 512 ? f64_row_select<8>(row, nk, a.topk, a.zq, lane, hist)
                             : nk <= 1024 ? f64_row_select<16>(row, nk, a.topk, a.zq, lane, hist) : f64_row_select<32>(row, nk, a.topk, a.zq, lane, hist);
             if (lane == 0) sm.sel[q] = rs;
         }
-        FT(3);
         __syncthreads();
-        FT(4);
         // ---- pass B: the fp64 logits again, masked softmax against the row maximum, P.V ----
         RowSel rs[QB];
         uint32_t* tap[QB];
@@ -555,12 +532,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                 const int key = jb * 16 + g + 4 * r;
                 const float sf = (float)S[r];
                 bool keep = TIES ? sf > rs[qb].thr : sf >= rs[qb].thr;
-#ifdef F64_KO_TIES
-                keep = sf >= rs[qb].thr;
-                if (false) {
-#else
                 if (TIES && sf == rs[qb].thr) {
-#endif
                     if (rs[qb].mode == 0) keep = true;
                     else if (rs[qb].mode == 1) keep = key <= rs[qb].aux;
                     else if (key < nk) {
@@ -570,11 +542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                     }
                 }
                 keep = keep && key < nk;
-#ifdef F64_KO_EXP
-                p[r] = keep ? S[r] - mrun[qb] : 0.0;
-#else
                 p[r] = keep ? exp_fast(S[r] - mrun[qb], sm.tab, ec) : 0.0;
-#endif
                 bits |= (unsigned)keep << (4 * r);        // keys 16 jb + g + 4 r
             }
             if (TAP && bits && q0 + qb * 16 + l15 < nq) atomicOr(tap[qb] + (jb >> 1), bits << (16 * (jb & 1) + g));
@@ -618,7 +586,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         }
     }
 
-    if (TOPK) FT(5);
     if (SOLO) {
         // the wave's rows are complete: row sum over the row's four lanes, normalise, write (lane: dims 2 (g + 4 r), + 1 of query l15)
 #pragma unroll
@@ -702,7 +669,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                 l += p; o0 += p * v[0]; o1 += p * v[1];
             }
         }
-        if (TOPK) FT(6);
         const double inv = 1.0 / l;
         o0 *= inv; o1 *= inv;
         if (f64_out_of_range(o0) || f64_out_of_range(o1)) f64_raise(a.guard);

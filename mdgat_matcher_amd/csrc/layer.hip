@@ -38,26 +38,6 @@
 #include <cstdlib>
 #include "common.hpp"
 #include "layer_image.hpp"
-#ifdef LAYER_TRACE
-__device__ long long g_dbg[8192];
-extern "C" int mdgat_debug_read(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg), n * sizeof(long long)); }
-#define TRACE_OFF (5 * 17 * 1024 + (768 + 8 * 2112) * 4)
-__device__ __forceinline__ void trace_point(int slot) {
-    extern __shared__ __attribute__((aligned(16))) char tsm[];
-    if ((threadIdx.x & 63) == 0 && ((threadIdx.x >> 6) == 0 || (threadIdx.x >> 6) == 3)) {     // waves 0 and 3 only (LDS is nearly full)
-        long long* tl = reinterpret_cast<long long*>(tsm + TRACE_OFF) + ((threadIdx.x >> 6) == 3) * 256;
-        const int c = (int)tl[255];
-        tl[c] = ((long long)slot << 48) | (__builtin_amdgcn_s_memtime() & 0xffffffffffffLL);
-        tl[255] = c + 1;
-    }
-}
-#define TR(slot) trace_point(slot)
-#ifndef TRACE_MLP
-#define TRACE_MLP 1
-#endif
-#else
-#define TR(slot)
-#endif
 #include "mma_chain.hpp"
 namespace {
 
@@ -223,12 +203,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
     const int wave_pt0 = blockIdx.x * TILE_PTS + wave * WPTS;
     constexpr int NB3 = MODE3 == 1 ? 12 : 4;      // units of phase 3 (two per stage)
 
-#ifdef LAYER_TRACE
-    const bool trace_on = (blockIdx.x == 3 || blockIdx.x == gridDim.x - 2) && (wave == 0 || wave == 3) && DO_MLP == TRACE_MLP && MODE3 == 1;
-    const int tbase = ((blockIdx.x != 3) * 2 + (wave == 3)) * 256;
-    long long* tlds = reinterpret_cast<long long*>(reinterpret_cast<char*>(smem) + TRACE_OFF) + (wave == 3) * 256;
-    if (lane == 0 && (wave == 0 || wave == 3)) tlds[255] = 0;
-#endif
     // stages of the tile: 16 row blocks of W1, 8 of W2, then the units of W3
     constexpr int NSTAGE = (DO_MLP ? 24 : 0) + NB3;
     auto stage_src = [&](int h) __attribute__((always_inline)) -> const _Float16* {
@@ -240,7 +214,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
     auto copy_ahead = [&](int h, int i) __attribute__((always_inline)) {
         if (h + LOOKAHEAD < NSTAGE) stage_dma_slice<NW>(stage_src(h + LOOKAHEAD), ldsb(h + LOOKAHEAD), wave, lane, i);
     };
-    TR(0);
     // (unrolled: as run-time loops the 64-keypoint variant's two rounds of b3 went load / wait / store, one round trip each)
     if (DO_MLP) {
 #pragma unroll
@@ -500,9 +473,7 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
             guard_report(rows_guard(tx, gm));
         }
         for_units<4>([&](int ks) __attribute__((always_inline)) { tile_fragment(ks, ah[ks], al[ks]); });
-        TR(1);
         stage_wait<DMA_SLICES>();               // stages 0 and 1 have landed, stage 2 may be in flight
-        TR(2);
 
         // ---- phase 1: 8 units of W1 -> hidden fragments (k-step rb of phase 2) ----
         f16x8 hh[8], hl[8];
@@ -521,7 +492,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
         // K = 256 units have 48 slots: a step in every other one, the stage copies in slots 6 i + 1
         // end of stage h: the copies of stages h + 2 and h + 3 may still be in flight
         for_units<8>([&](int rb) __attribute__((always_inline)) {
-            TR(10);
             // slots 0 .. 23: row block P, 24 .. 47: row block Q; the pending epilogue in every other slot
             auto inter = [&](int h, int base) __attribute__((always_inline)) {
                 return [&, h, base](int slot) __attribute__((always_inline)) {
@@ -531,9 +501,7 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
             };
             block_mma16<8, ROWH256>(bufp(2 * rb), l15, g, ah, al, acc[rb & 1].pm, acc[rb & 1].px, inter(2 * rb, 0));
             block_mma16<8, ROWH256>(bufp(2 * rb + 1), l15, g, ah, al, acc[rb & 1].qm, acc[rb & 1].qx, inter(2 * rb + 1, 24));
-            TR(11);
             end_of_pair<NW>(2 * rb + 1, NSTAGE);
-            TR(12);
         });
 
         // ---- phase 2: 4 units of W2, residual, new x (fp32 into the tile, split fragments kept) ----
@@ -554,7 +522,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
         };
         for_units<4>([&](int ob) __attribute__((always_inline)) {
             constexpr int H0 = 16;
-            TR(20);
             auto inter = [&](int h, int base) __attribute__((always_inline)) {
                 return [&, h, base](int slot) __attribute__((always_inline)) {
                     if (slot % 4 == 1 && slot / 4 < DMA_SLICES) copy_ahead(h, slot / 4);
@@ -565,15 +532,11 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
             };
             block_mma16<8, ROWH256>(bufp(H0 + 2 * ob), l15, g, hh, hl, acc[ob & 1].pm, acc[ob & 1].px, inter(H0 + 2 * ob, 0));
             block_mma16<8, ROWH256>(bufp(H0 + 2 * ob + 1), l15, g, hh, hl, acc[ob & 1].qm, acc[ob & 1].qx, inter(H0 + 2 * ob + 1, 24));
-            TR(21);
             end_of_pair<NW>(H0 + 2 * ob + 1, NSTAGE);
-            TR(22);
         });
         // the epilogue of the last unit (set 1) is not overlapped: phase 3 needs all of the new x
         for_units<E_STEPS>([&](int u) __attribute__((always_inline)) { e2(3, acc[1], u); });
-        TR(23);
         tile_to_rows(a.x);                       // the tile is free afterwards
-        TR(24);
     } else {
         {
             f32x4 tx[8];
@@ -591,7 +554,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
     for_units<NB3>([&](int q) __attribute__((always_inline)) {
         constexpr int H0 = DO_MLP ? 24 : 0;
         const _Float16* cur = bufp(H0 + q);
-        TR(30);
         auto inter = [&](int slot) __attribute__((always_inline)) {
             if (slot % 4 == 1 && slot / 4 < DMA_SLICES) copy_ahead(H0 + q, slot / 4);
             if (q > 0) e3(q - 1, acc[(q - 1) & 1], slot);
@@ -599,10 +561,8 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
         };
         if (MODE3 == 1 && q >= 8) unit_mma16<4, false, ROWH128>(cur, l15, g, xnh, xnl, acc[q & 1], inter);
         else unit_mma16<4, true, ROWH128>(cur, l15, g, xnh, xnl, acc[q & 1], inter);
-        TR(32);
         if ((q & 1) && q + 1 < NB3) end_of_pair<NW>(H0 + q, NSTAGE);
         else if (VW && q >= 10) __syncthreads();       // the gather buffers change hands every unit from here on
-        TR(33);
     });
     if (VW) for_units<4>([&](int u) __attribute__((always_inline)) { vstore(NB3 - 2, u); });
     for_units<E_STEPS>([&](int u) __attribute__((always_inline)) { e3(NB3 - 1, acc[(NB3 - 1) & 1], u); });
@@ -611,10 +571,6 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
         for_units<4>([&](int u) __attribute__((always_inline)) { vstore(NB3 - 1, u); });
     }
     if (MODE3 != 1) tile_to_rows(a.mdesc);
-    TR(40);
-#ifdef LAYER_TRACE
-    if (trace_on && lane == 0) for (int i = 0; i < (int)tlds[255]; ++i) g_dbg[tbase + i] = tlds[i];
-#endif
 }
 
 // fp32 [rows][K] -> split image [rows][rowh] (hi plane | lo plane | pad), once per weight load.  The first `nperm`
@@ -639,11 +595,7 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* w, _Float1
 template <int DO_MLP, int MODE3, int VW, int NW>
 int launch_layer_t(const LayerArgs& a, hipStream_t s) {
     constexpr int NWAVE = NW;
-    const size_t lds = (size_t)NSLOT * SLOT_BYTES + (768 + NWAVE * TILE_FLOATS) * sizeof(float)
-#ifdef LAYER_TRACE
-        + 2 * 256 * 8
-#endif
-        ;
+    const size_t lds = (size_t)NSLOT * SLOT_BYTES + (768 + NWAVE * TILE_FLOATS) * sizeof(float);
     static std::atomic<unsigned long long> optin;        // (one per template instance)
     if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(layer_kernel<DO_MLP, MODE3, VW, NW>), lds, optin, "layer LDS attribute")) return rc;
     constexpr int TILE_PTS = WPTS * NWAVE;

@@ -6,9 +6,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.hpp"
-#ifndef FT
-#define FT(k) do {} while (0)
-#endif
 
 // monotone image of a float in the unsigned integers (larger float <-> larger integer; -inf below every finite value)
 __device__ __forceinline__ unsigned f2ord(float f) {
@@ -204,9 +201,7 @@ __device__ __forceinline__ int rq_suffix_sum(int v) {
 __device__ __forceinline__ unsigned rq_row_bits(unsigned long long ballot, int lane) { return (unsigned)(ballot >> (lane & 48)) & 0xffffu; }
 
 constexpr int RQ_HIST_INTS = 272;       // per row: 256 bins + one waste bin per lane
-#ifndef RQ_START_BELOW
-#define RQ_START_BELOW 0.25f
-#endif
+constexpr float RQ_START_BELOW = 0.25f;  // deviations below mean + zq sd where the select starts (topk_quad_search)
 // rows: the wave's four rows in LDS, `pitch` floats apart (row r of the wave = lanes 16 r .. 16 r + 15); hist: 4 x RQ_HIST_INTS ints of LDS
 // owned by this wave (it may be the rows' own storage: every value is in registers before the first histogram is cleared, and the
 // LDS serves a wave's accesses in order).  Every lane returns its row's answer.
@@ -240,7 +235,6 @@ __device__ RowSearch topk_quad_search(const float* rows_, int pitch, int nk, int
             if (i % 2 == 0) { const float g = (valid && f > -3.0e38f) ? f : 0.f; s1 += g; s2 = fmaf(g, g, s2); }
         }
     }
-    FT(8);
     omx = rq_max_u(omx);
     // the row's smallest value: only a row that restarts needs it (rare: computed there)
     auto row_min = [&]() {
@@ -276,11 +270,7 @@ __device__ RowSearch topk_quad_search(const float* rows_, int pitch, int nk, int
     }
     int above = 0, ceq = 0;
     unsigned width = 256u;
-    FT(9);
-    int ft_level = 0;                    // (only the -DF64_TRACE build reads it)
-    (void)ft_level;
     for (;;) {
-        FT(10 + 3 * min(ft_level, 2));
         typedef int rq_i4 __attribute__((ext_vector_type(4)));
         typedef __attribute__((address_space(3))) rq_i4 rq_lds_int4;
         rq_lds_int4* h4 = (rq_lds_int4*)hist;
@@ -294,7 +284,6 @@ __device__ RowSearch topk_quad_search(const float* rows_, int pitch, int nk, int
             const unsigned d = (o[i] >> sh) - bq;               // below the base: wraps far beyond the width
             __atomic_fetch_add(hist + (d < width ? (int)d : 256 + s), 1, __ATOMIC_RELAXED);
         }
-        FT(11 + 3 * min(ft_level, 2));
         // stage 1: this lane's sixteen bins (16 s .. 16 s + 15) as one count; the lane whose bins hold the k-th largest
         const rq_i4 ha = h4[4 * s], hb = h4[4 * s + 1], hc = h4[4 * s + 2], hd = h4[4 * s + 3];
         const int t = (ha.x + ha.y + ha.z + ha.w) + (hb.x + hb.y + hb.z + hb.w) + (hc.x + hc.y + hc.z + hc.w) + (hd.x + hd.y + hd.z + hd.w);
@@ -316,8 +305,6 @@ __device__ RowSearch topk_quad_search(const float* rows_, int pitch, int nk, int
         above = rq_sum(own1 ? a1 : 0);
         ceq = rq_sum(own1 ? h1 : 0);
         base += (unsigned)bin << sh;
-        FT(12 + 3 * min(ft_level, 2));
-        ++ft_level;
         if (sh == 0) break;                                          // the bin is one value: `ceq` values equal it
         if (ceq == 1) {                                              // one value left in play: it is the k-th largest
             const unsigned bb = base >> sh;
@@ -330,7 +317,6 @@ __device__ RowSearch topk_quad_search(const float* rows_, int pitch, int nk, int
         width = sh >= 8 ? 256u : 1u << sh;      // (the bin just chosen spans 2^sh values: the next level must not look beyond it)
         sh = sh > 8 ? sh - 8 : 0;
     }
-    FT(20);
     out.thr = ord2f(base); out.c_gt = above; out.c_ge = above + ceq;
     if (out.c_ge == k || ceq <= list_cap) return out;
     // more than list_cap values share the k-th place: the first k - c_gt of them in key order stay (key = s + 16 i)

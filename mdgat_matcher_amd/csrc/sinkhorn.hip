@@ -18,22 +18,6 @@
 #include "common.hpp"
 #include <cstdlib>
 
-#ifdef SK_TRACE
-// phase trace of the cluster kernel (tools/ab_build.sh sinkhorn sktrace -DSK_TRACE; tools/sinkhorn_trace.py): s_memtime stamps
-// of waves 0 and 7 of workgroup 0 in iterations 40-47, 11 points per iteration
-__device__ long long g_sk_trace[2 * 8 * 12];
-extern "C" int mdgat_sk_trace_read(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sk_trace), n * sizeof(long long)); }
-#define SK_TP(k) do { if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7) && it >= 40 && it < 48) \
-    g_sk_trace[((wave == 7) * 8 + (it - 40)) * 12 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-// coarse phases of the whole kernel (workgroup 0, waves 0 and 7; tools/sinkhorn_phases.py): start | scores loaded | row maxima
-// absorbed | XCD handshake | iterations done | Z rows + row arg-maxes | end
-__device__ long long g_sk_phase[2 * 8];
-extern "C" int mdgat_sk_phase_read(long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sk_phase), n * sizeof(long long)); }
-#define SK_PH(k) do { if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7)) g_sk_phase[(wave == 7) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SK_TP(k) do {} while (0)
-#define SK_PH(k) do {} while (0)
-#endif
 namespace {
 
 constexpr float NEG_BIG = -1.0e30f;   // finite stand-in for -inf (keeps a - b well defined)
@@ -482,7 +466,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
 
     for (int pair = group; pair < a.B; pair += a.ngroups) {
         const float* S = a.scores + (size_t)pair * N * M;
-        SK_PH(0);
         // ---- this lane's RPW x 8 block of scores (base-2 log units); invalid entries -> exp2 gives 0 ----
         float K[RPW][8];
         const bool vec_ok = (M & 3) == 0 && gcol0 + 8 <= M;
@@ -505,7 +488,7 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
             }
         } else if (gcol0 >= M) {
             // a lane whose eight columns all lie beyond M loads nothing (M = 256: half of every wave - as clamped scalar
-            // loads, 128 per lane, they cost the launch of one pair 10 us: tools/sinkhorn_phases.py)
+            // loads, 128 per lane, they cost the launch of one pair 10 us in a phase trace)
 #pragma unroll
             for (int r = 0; r < RPW; ++r)
 #pragma unroll
@@ -529,7 +512,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                 }
         }
         if (a.range_guard && gmax >= 0x7f800000u) __hip_atomic_store(a.range_guard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        SK_PH(1);
         // ---- absorb the row maximum (all column slabs, dustbin column included): every row of K has largest entry <= 1 ----
         float u0r = 0.f, kbr = 0.f, ar = 0.f;     // lane r: absorbed potential, dustbin-column entry, scaling of row r
         {
@@ -580,7 +562,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
         // state of the columns this thread finalises: local column tid (global 512 jc + tid); thread 0 also the dustbin column
         const bool tcol_valid = jc * 512 + tid < M;
         float krt = 1.f, v0t = 0.f, bt = 1.f;
-        SK_PH(2);
         __syncthreads();                  // previous pair's readers of the LDS vectors are done
         if (tid == 0) flags[0] = 0;
         // do all row-slab partners of this pair sit on one XCD?  (slot 513 of the parity-0 buffer, agent scope)
@@ -606,10 +587,8 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
             same_xcd = flags[1] != 0;
         }
 
-        SK_PH(3);
         for (int it = 0; it < a.iters; ++it) {
             // ---- row update (mdgat.py:283): a_i = mu_i / sum_j K_ij b_j ----
-            SK_TP(0);
             float psum = 0.f;
             {
                 float racc[16];
@@ -620,7 +599,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                     for (int c = 1; c < 8; ++c) acc = fmaf(K[r][c], b[c], acc);
                     racc[r] = acc;
                 }
-                SK_TP(1);
                 psum = wave_sum16(racc, lane);                 // lane r: row r (lanes >= 16 are not used)
                 psum = lane < 16 ? psum : 0.f;
             }
@@ -638,7 +616,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
             }
             ar = my_row_valid ? mu * __builtin_amdgcn_rcpf(fmaf(kbr, bM, psum)) : 0.f;
             const float dsum = wave_sum_dpp(kbr * ar);
-            SK_TP(2);
             // ---- column update, wave-local part (mdgat.py:284): sum_i K_ij a_i over this wave's rows ----
             float q[8];
 #pragma unroll
@@ -649,16 +626,13 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
 #pragma unroll
                 for (int c = 0; c < 8; ++c) q[c] = fmaf(K[r][c], arr, q[c]);
             }
-            SK_TP(3);
             {
                 f32x4* qw = reinterpret_cast<f32x4*>(colp + wave * 512 + col0);
                 qw[0] = f32x4{q[0], q[1], q[2], q[3]};
                 qw[1] = f32x4{q[4], q[5], q[6], q[7]};
                 if (lane == 0) pdust[wave] = dsum;
             }
-            SK_TP(4);
             __syncthreads();
-            SK_TP(5);
             // ---- merge the 8 waves, exchange with the row-slab partners, new column scalings ----
             ++cep;
             {
@@ -687,12 +661,10 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                     for (int pp = 0; pp < GMAX; ++pp) vals[pp] = 0.f;
                     if (GR > 1) {
                         xstore(base + (size_t)jr * SLOT_STRIDE + tid, tagbits | __builtin_bit_cast(unsigned, loc), same_xcd);
-                        SK_TP(6);
                         const bool my_dust = wave == 7 && lane < GR && lane != jr;
                         poll_partners<GMAX>(base + tid, SLOT_STRIDE, GR, jr, cep, vals, failed, a.error_word, same_xcd,
                                             my_dust ? base + (size_t)lane * SLOT_STRIDE + 512 : nullptr, &dust_in);
                         have_dust = my_dust && !failed;
-                        SK_TP(7);
                     }
                     float total = 0.f;
 #pragma unroll
@@ -722,9 +694,7 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                     if (lane == 0) bvec[512] = nuM * __builtin_amdgcn_rcpf(fmaf(kc, aN, total));
                 }
             }
-            SK_TP(8);
             __syncthreads();
-            SK_TP(9);
             {
                 const f32x4 x0 = *reinterpret_cast<const f32x4*>(bvec + col0);
                 const f32x4 x1 = *reinterpret_cast<const f32x4*>(bvec + col0 + 4);
@@ -733,7 +703,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                 for (int c = 0; c < 8; ++c) if (gcol0 + c >= M) b[c] = 0.f;
                 bM = bvec[512];
             }
-            SK_TP(10);
             // ---- fold scalings that left [2^-40, 2^40] back into K and the absorbed potentials (rare) ----
             // (Measured: with the folds hoisted out of the iteration loop - an inner loop that only reads the block - the
             // 128 register copies per iteration disappear from the N <= 512 kernel, for -1 %; the two larger kernels spill
@@ -784,7 +753,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
             }
         }
 
-        SK_PH(4);
         // ---- Z = couplings + u + v - norm (mdgat.py:285, 307), natural-log units; fused arg-max ----
         float* Zp = a.Z ? a.Z + (size_t)pair * (N + 1) * (M + 1) : nullptr;
         const bool partner_lost = (__hip_atomic_load(a.error_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u) != 0 ||
@@ -877,7 +845,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                 }
             }
         }
-        SK_PH(5);
         const float UN = ran ? u0N + lg2(aN) : 0.f;
         const float zNt = (alpha + UN + (ran ? v0t + lg2(bt) + poison : 0.f)) * MDGAT_LN2 - norm;   // Z[N][512 jc + tid]
         if (last_r && Zp) {
@@ -910,7 +877,6 @@ __global__ __launch_bounds__(SKS_THREADS, 2) void sinkhorn_scaling_kernel(SksArg
                 a.cbest_idx[((size_t)pair * GR + jr) * M + jc * 512 + tid] = bi;
             }
         }
-        SK_PH(6);
     }
 }
 
