@@ -199,3 +199,59 @@ def test_free_functions_of_models_mdgat(models_mdgat, golden_dir):
         np.testing.assert_array_equal(models_mdgat.get_graph_feature(x, src, 9).cpu().numpy(), g[f'knn{Cc}_adj'])
     mlp = models_mdgat.MLP([4, 32, 64])
     assert [type(mm).__name__ for mm in mlp] == ['Conv1d', 'BatchNorm1d', 'ReLU', 'Conv1d']
+
+
+def test_free_functions_of_models_mdgat_in_float32(models_mdgat, golden_dir):
+    """The float32 route of the drop-in free functions (integration/models/mdgat.py): float32 q / k / v run the fp32-class kernels
+    through a CROSS layer of the library's layout - the queries are frame 0, zero rows pad it up to k (``_to_lib(min_rows=k)``), the
+    keys are frame 1.  Against the reference's outputs in tests/golden/op_vectors.npz cast to float32 (40 queries, 56 keys:
+    attention_kernel<true, 4>; k = 56 = every key: frame 0 padded to 56, the dispatcher's full-attention shortcut), then against
+    the fp64 oracle at lopsided shapes: k larger than the number of queries (zero-padded query rows; 900 keys:
+    attention_topk_wide_kernel<4>, 2048 keys: <8>), k equal to the number of keys (that side keeps every key), rows whose k-th and
+    (k+1)-th fp64 logits lie within 5e-6 excepted as in tests/test_gpu_ops.py.  Outputs are float32 in the reference's [B, dh, H, N]."""
+    from oracle import mdgat_oracle as O
+    g = np.load(os.path.join(golden_dir, 'op_vectors.npz'))
+    dev = 'cuda:0'
+    q, k, v = (torch.from_numpy(g[x]).float().to(dev) for x in ('att_q', 'att_k', 'att_v'))
+    msg, prob = models_mdgat.attention(q, k, v)
+    assert prob is None and msg.dtype == torch.float32 and tuple(msg.shape) == tuple(g['att_full'].shape)
+    assert np.abs(msg.cpu().double().numpy() - g['att_full']).max() < 1e-5
+    for kk in (1, 8, 56):
+        dyn, _ = models_mdgat.dynamic_attention(q, k, v, kk)
+        assert dyn.dtype == torch.float32 and tuple(dyn.shape) == tuple(g['att_full'].shape)
+        assert np.abs(dyn.cpu().double().numpy() - g[f'att_dyn{kk}']).max() < 1e-5, kk
+    with pytest.raises(RuntimeError):
+        models_mdgat.dynamic_attention(q, k, v, 57)
+    s = torch.from_numpy(g['sk_64x64_scores']).float().to(dev)
+    iters, alpha = g['sk_64x64_meta']
+    with torch.no_grad():
+        Z = models_mdgat.log_optimal_transport(s, torch.tensor(alpha, dtype=torch.float32), int(iters))
+    assert Z.dtype == torch.float32 and tuple(Z.shape) == tuple(g['sk_64x64_Z'].shape)
+    assert np.abs(Z.cpu().double().numpy() - g['sk_64x64_Z']).max() < 1e-5
+
+    rs = np.random.RandomState(17)
+    for B, N, M, kk in ((2, 100, 900, 128), (2, 300, 200, 200), (1, 130, 2048, 64), (2, 50, 600, 600), (2, 700, 300, 8)):
+        qd, kd, vd = (torch.from_numpy(rs.standard_normal((B, 32, 4, n)) * 1.3).float() for n in (N, M, M))
+        ref_full, _ = O.attention(qd.double(), kd.double(), vd.double())
+        full, _ = models_mdgat.attention(qd.to(dev), kd.to(dev), vd.to(dev))
+        assert full.dtype == torch.float32 and tuple(full.shape) == (B, 32, 4, N)
+        assert (full.cpu().double() - ref_full).abs().max() < 1e-5
+        dyn, _ = models_mdgat.dynamic_attention(qd.to(dev), kd.to(dev), vd.to(dev), kk)
+        assert dyn.dtype == torch.float32 and tuple(dyn.shape) == (B, 32, 4, N)
+        ref, _ = O.dynamic_attention(qd.double(), kd.double(), vd.double(), kk)
+        logits = torch.einsum('bdhn,bdhm->bhnm', qd.double(), kd.double()) / 32 ** 0.5
+        if kk < M:
+            top = logits.topk(kk + 1, dim=3).values
+            near_tie = (top[..., kk - 1] - top[..., kk]) < 5e-6                  # [B, H, N]
+        else:
+            near_tie = torch.zeros(logits.shape[:3], dtype=torch.bool)
+        assert near_tie.double().mean() < 2e-3
+        err = (dyn.cpu().double() - ref).abs().amax(1)                            # [B, H, N]
+        print(f'[dropin] float32 dynamic_attention {N} queries, {M} keys, k={kk}: near-tie rows {int(near_tie.sum())} of '
+              f'{near_tie.numel()}, worst error {float(err[~near_tie].max()):.2e}')
+        assert err[~near_tie].max() < 1e-5, (N, M, kk)
+    s = torch.from_numpy(rs.standard_normal((2, 300, 900)) * 4.0)
+    with torch.no_grad():
+        Z = models_mdgat.log_optimal_transport(s.float().to(dev), 0.7, 30)
+    assert Z.dtype == torch.float32 and tuple(Z.shape) == (2, 301, 901)
+    assert (Z.cpu().double() - O.log_optimal_transport(s.float().double(), 0.7, 30)).abs().max() < 1e-4

@@ -366,6 +366,43 @@ def test_literal_bar_on_every_reference_held_pair(golden_dir, name):
     assert torch.equal(plain[0], m0) and torch.equal(plain[1], m1) and torch.equal(plain[4], Z)
 
 
+@pytest.mark.parametrize('B,n,m,L,k', [(2, 512, 512, 2, [None, 128, 64, 64]), (2, 256, 256, 2, [None, 128, None, 32]),
+                                       (3, 100, 77, 2, [None, 16, 8, 77]), (1, 1500, 520, 2, [64, 64, None, 128])])
+def test_exact_mode_cross_dynamic_schedules_vs_oracle(B, n, m, L, k):
+    """Dynamic CROSS layers (odd layer indices) in the reference-exact mode, held to the UNFORCED fp64 oracle: the goldens' schedule
+    makes only self layers dynamic, and test_f64_fused_layer_tail_equals_three_launches compares cross-dynamic schedules only with
+    other kernel forms.  Here (k = 77 = the smaller frame of a lopsided cross layer; 1500 x 520 in the widest form): not one
+    top-k row selected differently from the oracle, identical matches, and Z the fp32 rounding of the oracle's fp64 Z."""
+    from parity_util import hip_forward_with_selection
+    cfg = synth.default_config(L=L, k=k, sinkhorn_iterations=20)
+    sd = synth.make_state_dict(L=L, seed=4)
+    net = MDGAT(cfg).double()                      # no 'arithmetic' key: the float64 module is the request
+    net.load_state_dict(sd)
+    net = net.double().eval().to(DEV)
+    assert net.exact()
+    data = synth.make_batch(B, n, m, first_pair=3)
+    dev = {kk: v.to(DEV) for kk, v in data.items()}
+    (m0, m1, s0, s1, Z), forced = hip_forward_with_selection(net, dev)
+    net.check(DEV)
+    assert len(forced) == sum(x is not None for x in k)
+    cap, capf = {}, {}
+    ref = O.mdgat_forward(sd, cfg, data, cap)
+    O.mdgat_forward(sd, cfg, data, capf, forced_topk=forced)
+    rows = sum(r['rows'] for reps in capf['topk_report'].values() for r in reps)
+    bad = sum(r['bad_count'] for reps in capf['topk_report'].values() for r in reps)
+    Zc, Zr = Z.cpu().double().numpy(), cap['Z'].numpy()
+    err = np.abs(Zc - Zr).max()
+    es = max((s0.cpu().double() - ref['matching_scores0']).abs().max().item(), (s1.cpu().double() - ref['matching_scores1']).abs().max().item())
+    print(f'[parity-f64] cross-dynamic {B}x{n}x{m} k={k}: top-k rows differing from the fp64 selection {rows}; max|dZ| vs the unforced '
+          f'oracle {err:.2e} (max|Z| {np.abs(Zr).max():.1f}); mscores {es:.2e}')
+    assert rows == 0 and bad == 0
+    assert torch.equal(m0.cpu(), ref['matches0']) and torch.equal(m1.cpu(), ref['matches1'])
+    assert err < 1.2e-7 * max(1.0, np.abs(Zr).max())
+    assert es < Z_TOL
+    plain = net._run(dev['keypoints0'], dev['scores0'], dev['descriptors0'], dev['keypoints1'], dev['scores1'], dev['descriptors1'], want_Z=True)
+    assert torch.equal(plain[0], m0) and torch.equal(plain[1], m1) and torch.equal(plain[4], Z)
+
+
 @pytest.mark.parametrize('tail', ['auto', 'fp32'])
 def test_literal_bar_on_a_reference_held_batch_that_runs_in_slices(golden_dir, tail):
     """tests/golden/cfg_n512_L9_S100_b40.npz: 40 pairs of the headline shape run through the REFERENCE as one batch.  Here they are

@@ -411,6 +411,29 @@ def test_large_frames(n, m, L, S, k):
         assert_plain_vs_oracle(res, cfg, sd, data, f'large {n}x{m} L={L} S={S}')
 
 
+CROSS_DYNAMIC = [(2, 512, 512, 2, [None, 128, 64, 64]), (2, 256, 256, 2, [None, 128, None, 32]), (3, 100, 77, 2, [None, 16, 8, 77]),
+                 (1, 1500, 520, 2, [64, 64, None, 128])]
+
+
+@pytest.mark.parametrize('B,n,m,L,k', CROSS_DYNAMIC)
+def test_cross_dynamic_schedules_vs_oracle(B, n, m, L, k):
+    """Top-k schedules with dynamic CROSS layers (odd layer indices; the reference's default schedule and the goldens make only
+    self layers dynamic) through the fp32-class forward: attention_topk16_kernel<512> and <256> in a cross layer, k equal to the
+    smaller frame of a lopsided cross layer (100 x 77, k = 77: frame 0's side keeps every key, frame 1's selects), and
+    attention_topk_wide_kernel<8> on 1500 x 520.  Against the fp64 oracle in the attributed form of parity_util.py, and
+    unconditionally against the unforced oracle."""
+    cfg = synth.default_config(L=L, k=k, sinkhorn_iterations=20)
+    sd = synth.make_state_dict(L=L, seed=4)
+    net = MDGAT(cfg).double()
+    net.load_state_dict(sd)
+    net = net.double().eval().to(DEV)
+    assert not net.exact()
+    data = synth.make_batch(B, n, m, first_pair=3)
+    res = attributed_parity(net, cfg, sd, data, DEV)
+    assert_attributed(res, f'cross-dynamic {B}x{n}x{m} k={k}')
+    assert_plain_vs_oracle(res, cfg, sd, data, f'cross-dynamic {B}x{n}x{m} k={k}')
+
+
 @pytest.mark.parametrize('B,n,m,k', [(3, 37, 53, []), (2, 130, 75, []), (5, 20, 44, [8, None]), (1, 1, 9, []), (2, 128, 256, [])])
 def test_ragged_shapes_vs_oracle(B, n, m, k):
     """Keypoint counts that are not multiples of anything (tiles of 128 / waves of 16 keypoints straddle frames and
@@ -582,6 +605,20 @@ def test_fuzz_short():
     spec.loader.exec_module(fz)
     cases, fails, worst = fz.run(15.0, seed=3, verbose=True)
     assert cases >= 20 and fails == 0 and worst <= 1e-4
+
+
+def test_fuzz_attention_short():
+    """15 s of tools/fuzz_attention.py: the per-op attention entry point on random self / cross layers, full or top-k with k
+    anywhere in 1 ... keys, N != M up to 2048 (the far end of attention_topk_wide_kernel<8>), operand scales 0.05 ... 6 - every
+    dynamic row keeps exactly k keys, the selection is the fp64 one up to near-ties, both kernel instantiations (with and without
+    the selection tap) within the stated bound of the oracle."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('fuzz_attention', os.path.join(root, 'tools', 'fuzz_attention.py'))
+    fz = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fz)
+    cases, fails = fz.run(15.0, seed=11)
+    assert cases >= 8 and fails == 0
 
 
 def test_repeatable_bitwise():

@@ -349,6 +349,170 @@ def test_attention_topk_unmeasured_bracket_ends(n):
             assert (out[:, lo:hi] - _ref_msg_to_lib(ref)).abs().max() < 1e-5
 
 
+def _frames(qkv, N, M, cross):
+    """(lo, hi, q, k, v) per side of the library layout: q [B, dh, H, n] of the side's own frame, k / v of its source frame
+    (the other one in a cross layer: attention.hip, ``src = cross ? 1 - side : side``)."""
+    out = []
+    for side, (lo, hi) in enumerate(((0, N), (N, N + M))):
+        slo, shi = ((N, N + M) if side == 0 else (0, N)) if cross else (lo, hi)
+        out.append((lo, hi, qkv[:, lo:hi, 0].permute(0, 3, 2, 1), qkv[:, slo:shi, 1].permute(0, 3, 2, 1),
+                    qkv[:, slo:shi, 2].permute(0, 3, 2, 1)))
+    return out
+
+
+def _check_topk_cross(qkv, N, M, k, tag):
+    """Both kernel instantiations (with and without the selection tap) of one dynamic cross layer against the fp64 oracle:
+    exactly k keys per row on both sides, the selection of torch.topk on the fp64 logits outside near-ties (< 2e-3 of the rows),
+    the message within 1e-5 of the oracle with the kernel's selection forced on every row and with the oracle's own selection on
+    the other rows, and the two instantiations within 1e-6 of each other."""
+    x = qkv.to(DEV)
+    out, sels = ops.attention(x, N, M, True, topk=k, return_selection=True)
+    shipped = ops.attention(x, N, M, True, topk=k)
+    d_tap = float((out - shipped).abs().max())
+    assert d_tap < 1e-6, (tag, d_tap)
+    out = out.cpu().double()
+    B = qkv.shape[0]
+    ties = rows = 0
+    worst = 0.0
+    for (lo, hi, q, kk, v), sel in zip(_frames(qkv, N, M, True), sels):
+        sel = sel.cpu()
+        n_keys = kk.shape[3]
+        cnt = sel.sum(-1)
+        assert (cnt == min(k, n_keys)).all(), (tag, lo, int(cnt.min()), int(cnt.max()))
+        logits = torch.einsum('bdhn,bdhm->bhnm', q, kk) / 32 ** 0.5
+        top = logits.topk(min(k + 1, n_keys), dim=3)
+        if k < n_keys:
+            near_tie = (top.values[..., k - 1] - top.values[..., k]) < 5e-6                      # [B, H, n]
+        else:
+            near_tie = torch.zeros(logits.shape[:3], dtype=torch.bool)
+        own = torch.zeros_like(logits, dtype=torch.bool).scatter_(3, top.indices[..., :k], True)
+        assert ((own != sel).any(-1) <= near_tie).all(), (tag, lo, int(((own != sel).any(-1) & ~near_tie).sum()))
+        ties += int(near_tie.sum())
+        rows += near_tie.numel()
+        rep = []
+        ref_f, _ = O.dynamic_attention(q, kk, v, k, forced=sel, report=rep)
+        assert rep[0]['bad_count'] == 0
+        err_f = float((out[:, lo:hi] - _ref_msg_to_lib(ref_f)).abs().max())
+        assert err_f < 1e-5, (tag, lo, err_f)
+        ref, _ = O.dynamic_attention(q, kk, v, k)
+        err = (out[:, lo:hi] - _ref_msg_to_lib(ref)).abs().reshape(B, hi - lo, 4, 32).amax(3)          # [B, n, H]
+        ok = ~near_tie.permute(0, 2, 1)
+        err_o = float(err[ok].max()) if ok.any() else 0.0
+        assert err_o < 1e-5, (tag, lo, err_o)
+        worst = max(worst, err_f, err_o)
+    assert ties < 2e-3 * rows, (tag, ties, rows)
+    print(f'[topk-cross] {tag}: near-tie rows {ties} of {rows}, worst message error {worst:.2e}, tap vs shipped {d_tap:.1e}')
+
+
+@pytest.mark.parametrize('N,M,k', [
+    (40, 100, 8), (100, 40, 40),                    # attention_kernel<true, 4>: max(N, M) <= 128
+    (200, 130, 64), (130, 256, 130),                # attention_kernel<true, 8>: <= 256 keys, not 256 x 256
+    (256, 256, 128), (256, 256, 1),                 # attention_topk16_kernel<256>: N = M = 256
+    (300, 500, 64), (500, 300, 300),                # attention_kernel<true, 16>: <= 512 keys, not 512 x 512
+    (512, 512, 128), (512, 512, 64),                # attention_topk16_kernel<512>: N = M = 512
+    (700, 600, 100), (1000, 513, 64),               # attention_topk_wide_kernel<4>: 513 ... 1024 keys
+    (1500, 520, 64), (2048, 700, 128), (130, 2048, 130)])   # attention_topk_wide_kernel<8>: 1025 ... 2048 keys
+def test_attention_topk_cross(N, M, k):
+    """Dynamic CROSS layers at every fp32-class top-k kernel form the dispatcher picks (launch_attention, from max(N, M) and the
+    tap).  With N != M a workgroup's query count (its side) differs from its key count (the other frame): a kernel that takes one
+    for the other - pass counts, the pad mask of the last key block, the "frame has only k keys" rule (kexp), the threshold search
+    on the smaller side (seeded from the quantile of max(N, M), a.zq) - keeps the wrong keys, which self layers (nq == nk) cannot
+    show.  Cases with k equal to the smaller frame ((100, 40, 40), (500, 300, 300), (130, 2048, 130)): one side keeps every key,
+    the other selects."""
+    rs = np.random.RandomState(N + 13 * M + k + 1)
+    B = 2 if max(N, M) <= 1024 else 1
+    qkv = torch.from_numpy(rs.standard_normal((B, N + M, 3, 4, 32)) * 1.3)
+    _check_topk_cross(qkv, N, M, k, f'{N}x{M} k={k}')
+
+
+def test_attention_topk_cross_k_equals_both_frames():
+    """k == N == M in a cross layer: the dispatcher's full-attention shortcut (launch_attention, ``dyn = ... && !(topk == N &&
+    topk == M)``) - the tap reports every key kept and the message is full attention over the other frame."""
+    N = M = k = 64
+    rs = np.random.RandomState(64)
+    qkv = torch.from_numpy(rs.standard_normal((2, N + M, 3, 4, 32)) * 1.3)
+    out, sels = ops.attention(qkv.to(DEV), N, M, True, topk=k, return_selection=True)
+    assert (out - ops.attention(qkv.to(DEV), N, M, True, topk=k)).abs().max() < 1e-6
+    out = out.cpu().double()
+    for (lo, hi, q, kk, v), sel in zip(_frames(qkv, N, M, True), sels):
+        assert sel.all()
+        ref, _ = O.attention(q, kk, v)
+        assert (out[:, lo:hi] - _ref_msg_to_lib(ref)).abs().max() < 1e-5
+
+
+@pytest.mark.parametrize('N,M,k,dups', [(200, 64, 16, 2), (200, 130, 64, 3), (500, 300, 128, 2), (900, 600, 100, 3),
+                                        (1500, 520, 64, 3)])
+def test_attention_topk_cross_with_ties(N, M, k, dups):
+    """test_attention_topk_with_ties in cross layers with N != M (attention_kernel<true, 4 / 8 / 16>, the wide kernel with four and
+    eight waves): a group of identical keys in frame 1 - the SOURCE of frame 0's queries - straddles the k-th place of some rows.
+    Every row keeps exactly k keys, a kept member of the group never follows a dropped one (ties towards the lowest key index),
+    and with the kernel's selection forced the oracle agrees to 1e-5 on every row of both sides."""
+    rs = np.random.RandomState(7 + N + M + k)
+    qkv = torch.from_numpy(rs.standard_normal((1, N + M, 3, 4, 32)))
+    group = [10 + 7 * i for i in range(dups)]                 # keys 10, 17, 24, ... of frame 1 identical
+    for g in group[1:]:
+        qkv[:, N + g, 1:] = qkv[:, N + group[0], 1:]
+    out, sels = ops.attention(qkv.to(DEV), N, M, True, topk=k, return_selection=True)
+    assert (out - ops.attention(qkv.to(DEV), N, M, True, topk=k)).abs().max() < 1e-6
+    out = out.cpu().double()
+    assert torch.isfinite(out).all()
+    for side, ((lo, hi, q, kk, v), sel) in enumerate(zip(_frames(qkv, N, M, True), sels)):
+        sel = sel.cpu()
+        assert (sel.sum(-1) == k).all(), (side, int(sel.sum(-1).min()), int(sel.sum(-1).max()))
+        rep = []
+        ref, _ = O.dynamic_attention(q, kk, v, k, forced=sel, report=rep)
+        assert (out[:, lo:hi] - _ref_msg_to_lib(ref)).abs().max() < 1e-5
+        assert rep[0]['bad_count'] == 0 and rep[0]['max_gap'] < 5e-6, rep[0]
+        if side == 0:
+            kept = sel[..., group].long()                                    # [1, 4, N, dups]
+            assert (kept[..., :-1] >= kept[..., 1:]).all()
+            partial = (kept.sum(-1) > 0) & (kept.sum(-1) < dups)
+            assert partial.any()                                             # the straddling case is exercised
+            ref_own, _ = O.dynamic_attention(q, kk, v, k)
+            err = (out[:, lo:hi] - _ref_msg_to_lib(ref_own)).abs().reshape(1, N, 4, 32).amax(3)
+            assert err[(~partial).permute(0, 2, 1)].max() < 1e-5
+
+
+@pytest.mark.parametrize('N,M', [(2048, 130), (130, 2048)])
+@pytest.mark.parametrize('cross', [False, True])
+@pytest.mark.parametrize('dist', ['bimodal', 'outliers', 'cauchy', 'two_clusters_at_k'])
+def test_attention_topk_count_on_hard_distributions_lopsided(N, M, cross, dist):
+    """test_attention_topk_count_on_hard_distributions on lopsided frames (attention_topk_wide_kernel<8>, k = 128): the threshold
+    search starts from the quantile of max(N, M) = 2048 keys (launch_attention, a.zq), far from the answer on the 130-key side of
+    a pair, whose rows keep 128 of 130 keys.  Every row of both sides must keep exactly k keys, self and cross."""
+    k = 128
+    rs = np.random.RandomState(N + 3 * M + len(dist) + 11 * cross)
+    P = N + M
+    local = np.concatenate([np.arange(N), np.arange(M)])[None]        # key index inside its frame
+    if dist == 'bimodal':
+        x = np.where(rs.uniform(size=(1, P)) < 0.1, 8 + rs.standard_normal((1, P)), -2 + 0.05 * rs.standard_normal((1, P)))
+    elif dist == 'outliers':
+        x = 0.01 * rs.standard_normal((1, P))
+        x[:, rs.choice(P, 12, replace=False)] = rs.uniform(-300, 300, 12)
+    elif dist == 'cauchy':
+        x = np.clip(rs.standard_cauchy((1, P)), -500, 500)
+    else:                            # the k-th place falls inside a tight cluster far from the mean
+        x = np.where(local < k - 3, 20 + rs.standard_normal((1, P)), 1e-3 * rs.standard_normal((1, P)))
+    qkv = np.zeros((1, P, 3, 4, 32))
+    qkv[:, :, 2] = rs.standard_normal((1, P, 4, 32))
+    qkv[:, :, 1, :, 0] = x[:, :, None]
+    qkv[:, :, 1, :, 1] = 0.3 * rs.standard_normal((1, P, 4))
+    qkv[:, :, 0, :, 0] = np.sqrt(32) * rs.uniform(0.5, 2.0, (1, P, 4)) * np.where(rs.uniform(size=(1, P, 4)) < 0.2, -1, 1)
+    qkv[:, :, 0, :, 1] = np.sqrt(32) * rs.uniform(-1, 1, (1, P, 4))
+    qkv = torch.from_numpy(qkv)
+    out, sels = ops.attention(qkv.to(DEV), N, M, cross, topk=k, return_selection=True)
+    out = out.cpu().double()
+    scale = max(1.0, float(np.abs(x).max()) * 2.5 / 10.0)
+    for (lo, hi, q, kk, v), sel in zip(_frames(qkv, N, M, cross), sels):
+        sel = sel.cpu()
+        cnt = sel.sum(-1)
+        assert (cnt == k).all(), (dist, lo, int(cnt.min()), int(cnt.max()))
+        rep = []
+        ref, _ = O.dynamic_attention(q, kk, v, k, forced=sel, report=rep)
+        assert (out[:, lo:hi] - _ref_msg_to_lib(ref)).abs().max() < 2e-5 * scale
+        assert rep[0]['max_gap'] < 5e-6 * scale and rep[0]['rows'] <= 4, rep[0]
+
+
 @pytest.mark.parametrize('tag', ['sk_7x5', 'sk_64x64', 'sk_48x64'])
 def test_sinkhorn_golden(golden_dir, tag):
     g = _g(golden_dir, 'op_vectors')

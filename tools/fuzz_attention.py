@@ -1,8 +1,8 @@
 """Randomised attention / dynamic-attention cases through the per-op entry point against the fp64 oracle (GPU box):
     python tools/fuzz_attention.py [seconds] [seed]
-Frames of 1 ... 1100 keypoints (ragged, N != M), self / cross, full or top-k with k anywhere in 1 ... keys, operand scales
-0.05 ... 6 (logits up to a few hundred).  Message rows must match the oracle to |v| (3e-6 + 2e-7 max|logit|) + 4e-8, rows
-whose k-th and (k+1)-th logit are closer than the arithmetic resolves excepted (and rare), every row must keep exactly k keys."""
+Frames of 1 ... 2048 keypoints (ragged, N != M; one pair when a frame has more than 1100), self / cross, full or top-k with k
+anywhere in 1 ... keys, operand scales 0.05 ... 6 (logits up to a few hundred).  Message rows must match the oracle to
+|v| (3e-6 + 2e-7 max|logit|) + 4e-8, rows whose k-th and (k+1)-th logit are closer than the arithmetic resolves excepted (and rare), every row must keep exactly k keys."""
 import os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,11 +18,13 @@ def lib(msg):
 
 def run(budget=60.0, seed=0):
     rs = np.random.RandomState(seed)
-    sizes = [1, 2, 17, 31, 64, 65, 100, 128, 200, 256, 257, 320, 512, 513, 600, 1024, 1100]
+    sizes = [1, 2, 17, 31, 64, 65, 100, 128, 200, 256, 257, 320, 512, 513, 600, 1024, 1100, 1500, 2048]
     t0, cases, fails, worst = time.time(), 0, 0, 0.0
     while time.time() - t0 < budget:
         B = int(rs.choice([1, 2, 3]))
         N, M = (int(x) for x in rs.choice(sizes, 2))
+        if max(N, M) > 1100:            # the far end of the 8-wave wide kernel: one pair keeps the oracle fast
+            B = 1
         cross = bool(rs.randint(2))
         sq, sk, sv = (float(x) for x in rs.choice([0.05, 0.5, 1.3, 3.0, 6.0], 3))
         nk_min = min(N, M)
