@@ -332,6 +332,15 @@ int mdgat_set_f64_sinkhorn_form(int mode);
 int mdgat_sinkhorn(int B, int N, int M, const float* scores, float bin_score, int iters,
                    float* Z, void* workspace, size_t workspace_bytes, void* stream);
 size_t mdgat_sinkhorn_workspace_bytes(int B, int N, int M);
+/* ... followed by the match extraction (mdgat.py:441-483), as the forward's score / Sinkhorn / extraction stage runs it: with the
+ * workspace of mdgat_sinkhorn_workspace_bytes (256-byte aligned) the cluster kernel decides the arg-maxes in its epilogue, on the
+ * registers it stores to Z, and the extraction kernel merges them; without one the streaming kernel writes Z and the extraction kernel
+ * scans it.  Z_or_null: Z [B][N+1][M+1] if wanted (required without a workspace).  Z_fallback_or_null: a buffer of Z's size lent to
+ * the cluster launch for pairs it hands to the streaming kernel (scores beyond the scaling form's range, a lost partner workgroup)
+ * when Z itself is not asked for - what the forward's workspace provides; with neither the launch is cooperative. */
+int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_score, int iters, int mode, float match_threshold,
+                           int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
+                           float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same in fp64 - the reference's own arithmetic (mdgat.py:279-308 run in float64, test.py:193) - on fp64 scores: Z [B][N+1][M+1]
  * fp64; N, M <= 2175.  Frames of at most 575 keypoints run in one launch with the couplings held in registers; larger ones stream them

@@ -921,6 +921,17 @@ extern "C" int mdgat_sinkhorn(int B, int N, int M, const float* scores, float bi
     return launch_sinkhorn(B, N, M, scores, nullptr, bin_score, iters, Z, workspace, workspace_bytes, nullptr, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_score, int iters, int mode, float match_threshold,
+                                      int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
+                                      float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_sinkhorn_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (mode < 0 || mode > 3) { mdgat_set_error("mdgat_sinkhorn_extract: bad mode %d", mode); return MDGAT_ERR_BAD_ARG; }
+    // the forward's call (tail32): the same launcher, the same SkExtract, the batch-wide rule applied inside the launch
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
+    return launch_sinkhorn(B, N, M, scores, nullptr, bin_score, iters, Z_or_null, workspace, workspace_bytes, &ex, static_cast<hipStream_t>(stream), nullptr,
+                           Z_or_null ? Z_or_null : Z_fallback_or_null);
+}
+
 extern "C" int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold, int64_t* matches0,
                              int64_t* matches1, float* mscores0, float* mscores1, void* stream) {
     if (!Z || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }

@@ -39,6 +39,31 @@ def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool
     return Z
 
 
+def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2,
+                     want_Z: bool = False, streaming: bool = False):
+    """fp32 Sinkhorn + match extraction as the forward runs them (launch_sinkhorn with an extraction request): (matches0, matches1,
+    mscores0, mscores1[, Z]).  On the cluster kernel (N, M <= 2048) the arg-maxes are decided in its epilogue and Z is written only
+    if wanted; ``streaming=True`` passes no workspace: the one-workgroup-per-pair kernel writes Z and the extraction kernel scans it."""
+    _need_cuda(scores)
+    s = scores.to(torch.float32).contiguous()
+    B, N, M = s.shape
+    m0 = torch.empty((B, N), dtype=torch.int64, device=s.device)
+    m1 = torch.empty((B, M), dtype=torch.int64, device=s.device)
+    s0 = torch.empty((B, N), dtype=torch.float32, device=s.device)
+    s1 = torch.empty((B, M), dtype=torch.float32, device=s.device)
+    Zbuf = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=s.device)     # Z, or the buffer lent for redone pairs
+    lib = _lib.load()
+    with torch.cuda.device(s.device):
+        need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
+        ws = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
+        z_out = want_Z or not need
+        _lib.check(lib.mdgat_sinkhorn_extract(B, N, M, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
+                                              m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Zbuf.data_ptr() if z_out else None,
+                                              None if z_out else Zbuf.data_ptr(), ws.data_ptr() if ws is not None else None, need, _stream(s)),
+                   'mdgat_sinkhorn_extract')
+    return (m0, m1, s0, s1, Zbuf) if want_Z else (m0, m1, s0, s1)
+
+
 def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64."""
     _need_cuda(scores)
