@@ -193,7 +193,7 @@ int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* fram
                          float* Z, const mdgat_taps* taps,
                          void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- evaluation loss (mdgat.py:486-594; no backward: the library is inference only) ------------------------------------- */
+/* ---- evaluation loss (mdgat.py:486-594) and its gradient with respect to Z (mdgat_loss_backward below) ------------------------- */
 
 /* config['loss_method'] of the loss: superglue (487-511), triplet_loss (512-546), gap_loss (547-594) */
 typedef enum { MDGAT_LOSS_SUPERGLUE = 0, MDGAT_LOSS_TRIPLET = 1, MDGAT_LOSS_GAP = 2 } mdgat_loss_method;
@@ -221,6 +221,22 @@ int mdgat_loss(int B, int N, int M, const float* Z, const int64_t* gt0, const in
 int mdgat_loss_f64(int B, int N, int M, const double* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma, double* loss,
                    unsigned* bad_index, void* workspace, size_t workspace_bytes, void* stream);
 size_t mdgat_loss_workspace_bytes(int B, int N, int M);
+
+/* The gradient autograd takes through the reference's loss code: dZ [B][N+1][M+1] fp64 = sum_b dloss[b] d loss[b] / dZ, with loss [B]
+ * the per-pair values of mdgat_loss and dloss [B] fp64 one upstream weight per pair (the mean over pairs of superglue / triplet is the
+ * caller's: dloss[b] = 1 / B).  Z fp32 or fp64, the arithmetic fp64 either way; every entry of dZ is written, each by one thread and
+ * without atomics on values, so a pair's gradient does not depend on the batch it travels in.  Conventions: a clamp argument that is
+ * exactly 0 passes the gradient (torch.clamp); t(z) = -log(exp(z)) is differentiated literally, (-g / e) * e with e = exp(z), which is
+ * -+inf or NaN where e is deep in its subnormal band or 0 (below about -745.1), as in the reference; ties between a row's or column's
+ * largest non-positive entries (triplet) take the lowest index.  A gt0 value outside [-1, M] or (triplet, gap) a gt1 value outside
+ * [-1, N]: that pair's dZ is NaN throughout and bit 0 of *bad (device memory, optional; the caller clears it) is set.  workspace:
+ * 256-byte aligned, mdgat_loss_backward_workspace_bytes.  Arguments and limits as mdgat_loss, and (N+1) (M+1) < 2^31.  Reads Z twice;
+ * no allocation, no synchronisation. */
+int mdgat_loss_backward(int B, int N, int M, const float* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma,
+                        const double* dloss, double* dZ, int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+int mdgat_loss_backward_f64(int B, int N, int M, const double* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma,
+                            const double* dloss, double* dZ, int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_loss_backward_workspace_bytes(int B, int N, int M);
 
 /* mdgat_forward / mdgat_forward_f64 and the loss of `req` on the forward's own Z: the fp64 Z of the exact mode's fp64 tail, else the
  * fp32 Z.  Outputs, workspace alignment and everything else as the forwards without the loss; req == NULL is exactly those.  The

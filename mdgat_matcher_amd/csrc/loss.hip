@@ -26,20 +26,15 @@
 
 namespace {
 
-constexpr int LOSS_TR = 16;        // rows per workgroup of the tile kernel
-constexpr int LOSS_THREADS = 256;
-
-__device__ inline double loss_t(double z) { return z < -708.0 ? -log(exp(z)) : -z; }
-// torch.clamp(x, min=0): NaN stays NaN
-__device__ inline double clamp0(double x) { return x < 0.0 ? 0.0 : x; }
-// gt index -> row / column of Z: -1 is the dustbin (`dust`), [0, dust] as is, anything else -1 (an indexing error in the reference)
-__device__ inline int gt_index(int64_t g, int dust) { return g == -1 ? dust : (g >= 0 && g <= dust ? (int)g : -1); }
-
-size_t tiles_of(int N) { return (size_t)(N + 1 + LOSS_TR - 1) / LOSS_TR; }
+// (the tile shape, t(z), clamp and the gt index rule: loss.hpp, shared with the gradient's dense pass)
+__device__ inline double clamp0(double x) { return loss_clamp0(x); }
+__device__ inline int gt_index(int64_t g, int dust) { return loss_gt_index(g, dust); }
+size_t tiles_of(int N) { return loss_tiles_of(N); }
 
 // the workspace: rowterm [B][N] | slab [B][tiles][M] | gap: tpos [B][M] (t of P) | cols [B][M] (the columns in P's order) | A [B][N+2]
-struct LossWs { double *rowterm, *slab, *tpos; int *cols, *A; size_t total; };
-LossWs carve_loss(void* base, int B, int N, int M) {
+// | the gradient's statistics pass (grad): rowaux [B][N] | slabaux [B][tiles][M]
+using LossWs = LossStats;
+LossWs carve_loss(void* base, int B, int N, int M, bool grad = false) {
     LossWs w{};
     WsCarver c{static_cast<char*>(base)};
     c.take(w.rowterm, (size_t)B * N);
@@ -47,10 +42,14 @@ LossWs carve_loss(void* base, int B, int N, int M) {
     c.take(w.tpos, (size_t)B * M);
     c.take(w.cols, (size_t)B * M);
     c.take(w.A, (size_t)B * (N + 2));
+    if (grad) {
+        c.take(w.rowaux, (size_t)B * N);
+        c.take(w.slabaux, (size_t)B * tiles_of(N) * M);
+    }
+    w.tiles = (int)tiles_of(N);
     w.total = c.bytes;
     return w;
 }
-constexpr int LOSS_GAP_MAX_ROWS = 15000;     // the prologue holds N + 2 row counters in LDS (at most 64 KB per workgroup)
 
 // the rank-th (0-based) column of a row that is not one of its a positive columns pos[0] < ... < pos[a-1]: rank + #{t : pos[t] - t <= rank}
 __device__ inline int nth_other(const int* pos, int a, int rank) {
@@ -137,16 +136,22 @@ __device__ inline double block_reduce(double v, double* red) {
 
 // GAP: row i accumulates sum_{j != pos} clamp(t(pos) - t(Z[i][j]) + gamma, 0) over the m+1 columns, column j the same over the
 // n+1 rows.  Else (triplet): row i the max of Z[i][j] over j != pos, column j the max over i != pos (the hard negative of topk(2)).
-template <typename T, bool GAP>
+// GRAD (the gradient's statistics pass, launch_loss_stats): the same walk, leaving the raw records of LossStats in place of the terms -
+// the sums with their active counts (a clamp argument >= 0 is active, as torch.clamp's backward has it), the maxima with their
+// index.  Ties take the LOWEST index, the rule of every arg-max of this library (torch.topk leaves the choice open).  GRAD = false is
+// the forward as it always was.
+template <typename T, bool GAP, bool GRAD>
 __global__ __launch_bounds__(LOSS_THREADS) void loss_tile_kernel(const T* __restrict__ Z, const int64_t* __restrict__ gt0,
                                                                 const int64_t* __restrict__ gt1, int N, int M, int tiles, double gamma,
                                                                 double* __restrict__ rowterm, double* __restrict__ slab,
                                                                 const double* __restrict__ tpos, const int* __restrict__ cols,
-                                                                const int* __restrict__ Arows) {
+                                                                const int* __restrict__ Arows, int* __restrict__ rowaux,
+                                                                int* __restrict__ slabaux) {
     __shared__ int s_pc[LOSS_TR];
     __shared__ int s_A[LOSS_TR + 1];
     __shared__ double s_tp[LOSS_TR];
     __shared__ double red[LOSS_THREADS / 64][LOSS_TR];
+    __shared__ int redaux[GRAD ? LOSS_THREADS / 64 : 1][LOSS_TR];
     const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const int i0 = tile * LOSS_TR;
     const size_t ld = (size_t)M + 1;
@@ -166,11 +171,13 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_tile_kernel(const T* __rest
     __syncthreads();
     int pc[LOSS_TR];
     double tp[LOSS_TR], acc[LOSS_TR];
+    int aux[GRAD ? LOSS_TR : 1];            // GRAD: the row's active count (gap) / the column of its maximum, -1 = none yet (triplet)
 #pragma unroll
     for (int r = 0; r < LOSS_TR; ++r) {
         pc[r] = s_pc[r];
         tp[r] = s_tp[r];
         acc[r] = GAP ? 0.0 : -INFINITY;
+        if (GRAD) aux[r] = GAP ? 0 : -1;
     }
     const int rows = N + 1 - i0 < LOSS_TR ? N + 1 - i0 : LOSS_TR;     // rows of Z in this tile (row N: the dustbin row)
     for (int j = threadIdx.x; j <= M; j += LOSS_THREADS) {
@@ -179,18 +186,30 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_tile_kernel(const T* __rest
 #pragma unroll
         for (int r = 0; r < LOSS_TR; ++r) z[r] = r < rows ? (double)Zb[(i0 + r) * ld + j] : 0.0;
         double c = -INFINITY;
+        int ci = -1;
 #pragma unroll
         for (int r = 0; r < LOSS_TR; ++r) {
             const int i = i0 + r;
             const bool row_term = i < N && j != pc[r];                  // (i < N: also false past the tile's last row)
             if (GAP) {
-                if (row_term) acc[r] += clamp0(tp[r] - loss_t(z[r]) + gamma);
+                if (row_term) {
+                    const double x = tp[r] - loss_t(z[r]) + gamma;
+                    acc[r] += clamp0(x);
+                    if (GRAD) aux[r] += x >= 0.0;
+                }
+            } else if (GRAD) {
+                // strict >: a thread's columns (and a tile's rows) come in increasing order, so the first of equals stays
+                if (row_term && (aux[r] < 0 || z[r] > acc[r])) { acc[r] = z[r]; aux[r] = j; }
+                if (r < rows && j < M && i != prow && (ci < 0 || z[r] > c)) { c = z[r]; ci = i; }
             } else {
                 if (row_term) acc[r] = fmax(acc[r], z[r]);
                 if (r < rows && j < M && i != prow) c = fmax(c, z[r]);
             }
         }
-        if (!GAP && j < M) slab[((size_t)b * tiles + tile) * M + j] = c;
+        if (!GAP && j < M) {
+            slab[((size_t)b * tiles + tile) * M + j] = c;
+            if (GRAD) slabaux[((size_t)b * tiles + tile) * M + j] = ci;
+        }
     }
     if (GAP) {
         // column c of V: from each row i of the tile the entry of rank (c + A_i) mod m among the row's non-positives, if it has one
@@ -208,26 +227,55 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_tile_kernel(const T* __rest
                 z[r] = has[r] ? (double)Zb[(i0 + r) * ld + j] : 0.0;
             }
             double v = 0.0;
+            int active = 0;
 #pragma unroll
             for (int r = 0; r < LOSS_TR; ++r)
-                if (has[r]) v += clamp0(tq - loss_t(z[r]) + gamma);
+                if (has[r]) {
+                    const double x = tq - loss_t(z[r]) + gamma;
+                    v += clamp0(x);
+                    if (GRAD) active += x >= 0.0;
+                }
             slab[((size_t)b * tiles + tile) * M + c] = v;
+            if (GRAD) slabaux[((size_t)b * tiles + tile) * M + c] = active;
         }
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int r = 0; r < LOSS_TR; ++r) {
         double v = acc[r];
+        int a = GRAD ? aux[r] : 0;
         for (int o = 32; o > 0; o >>= 1) {
             const double w = __shfl_xor(v, o, 64);
-            v = GAP ? v + w : fmax(v, w);
+            if (GRAD) {
+                const int wa = __shfl_xor(a, o, 64);
+                if (GAP) { v += w; a += wa; }
+                else if (wa >= 0 && (a < 0 || w > v || (w == v && wa < a))) { v = w; a = wa; }
+            } else {
+                v = GAP ? v + w : fmax(v, w);
+            }
         }
-        if (lane == 0) red[wv][r] = v;
+        if (lane == 0) {
+            red[wv][r] = v;
+            if (GRAD) redaux[wv][r] = a;
+        }
     }
     __syncthreads();
     if (threadIdx.x < LOSS_TR && i0 + (int)threadIdx.x < N) {
         const int r = threadIdx.x;
         double v = red[0][r];
+        if (GRAD) {
+            int a = redaux[0][r];
+            for (int k = 1; k < LOSS_THREADS / 64; ++k) {
+                const double w = red[k][r];
+                const int wa = redaux[k][r];
+                if (GAP) { v += w; a += wa; }
+                else if (wa >= 0 && (a < 0 || w > v || (w == v && wa < a))) { v = w; a = wa; }
+            }
+            // gap: S_i and its active count; triplet: the clamp argument and the negative's column
+            rowterm[(size_t)b * N + i0 + r] = GAP ? v : s_tp[r] - loss_t(v) + gamma;
+            rowaux[(size_t)b * N + i0 + r] = a;
+            return;
+        }
         for (int k = 1; k < LOSS_THREADS / 64; ++k) v = GAP ? v + red[k][r] : fmax(v, red[k][r]);
         // gap: 2 log(sum + 1) (mdgat.py:572); triplet: clamp(t(pos) - t(neg) + gamma, 0) (543-545)
         rowterm[(size_t)b * N + i0 + r] = GAP ? 2.0 * log(v + 1.0) : clamp0(s_tp[r] - loss_t(v) + gamma);
@@ -327,11 +375,11 @@ int launch_loss(int B, int N, int M, const T* Z, const int64_t* gt0, const int64
     if (method == MDGAT_LOSS_GAP) {
         hipLaunchKernelGGL((loss_gap_order_kernel<T>), dim3(B), dim3(LOSS_THREADS), (N + 2) * sizeof(int), s, Z, gt1, N, M, w.A, w.cols, w.tpos);
         if (int rc = mdgat_check_hip(hipGetLastError(), "loss_gap_order_kernel")) return rc;
-        hipLaunchKernelGGL((loss_tile_kernel<T, true>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
-                           rowterm, slab, w.tpos, w.cols, w.A);
+        hipLaunchKernelGGL((loss_tile_kernel<T, true, false>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
+                           rowterm, slab, w.tpos, w.cols, w.A, (int*)nullptr, (int*)nullptr);
     } else if (method == MDGAT_LOSS_TRIPLET) {
-        hipLaunchKernelGGL((loss_tile_kernel<T, false>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
-                           rowterm, slab, w.tpos, w.cols, w.A);
+        hipLaunchKernelGGL((loss_tile_kernel<T, false, false>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
+                           rowterm, slab, w.tpos, w.cols, w.A, (int*)nullptr, (int*)nullptr);
     }
     if (method != MDGAT_LOSS_SUPERGLUE)
         if (int rc = mdgat_check_hip(hipGetLastError(), "loss_tile_kernel")) return rc;
@@ -344,6 +392,28 @@ template int launch_loss<float>(int, int, int, const float*, const int64_t*, con
                                 hipStream_t);
 template int launch_loss<double>(int, int, int, const double*, const int64_t*, const int64_t*, int, double, double*, unsigned*, void*, size_t,
                                  hipStream_t);
+
+LossStats loss_stats_carve(void* base, int B, int N, int M) { return carve_loss(base, B, N, M, true); }
+
+// the caller (launch_loss_backward) has checked the arguments
+template <typename T>
+int launch_loss_stats(int B, int N, int M, const T* Z, const int64_t* gt0, const int64_t* gt1, int method, double gamma, const LossStats& w,
+                      hipStream_t s) {
+    const int tiles = w.tiles;
+    if (method == MDGAT_LOSS_GAP) {
+        hipLaunchKernelGGL((loss_gap_order_kernel<T>), dim3(B), dim3(LOSS_THREADS), (N + 2) * sizeof(int), s, Z, gt1, N, M, w.A, w.cols, w.tpos);
+        if (int rc = mdgat_check_hip(hipGetLastError(), "loss_gap_order_kernel")) return rc;
+        hipLaunchKernelGGL((loss_tile_kernel<T, true, true>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
+                           w.rowterm, w.slab, w.tpos, w.cols, w.A, w.rowaux, w.slabaux);
+    } else {
+        hipLaunchKernelGGL((loss_tile_kernel<T, false, true>), dim3((unsigned)B * tiles), dim3(LOSS_THREADS), 0, s, Z, gt0, gt1, N, M, tiles, gamma,
+                           w.rowterm, w.slab, w.tpos, w.cols, w.A, w.rowaux, w.slabaux);
+    }
+    return mdgat_check_hip(hipGetLastError(), "loss_tile_kernel (statistics)");
+}
+
+template int launch_loss_stats<float>(int, int, int, const float*, const int64_t*, const int64_t*, int, double, const LossStats&, hipStream_t);
+template int launch_loss_stats<double>(int, int, int, const double*, const int64_t*, const int64_t*, int, double, const LossStats&, hipStream_t);
 
 extern "C" size_t mdgat_loss_workspace_bytes(int B, int N, int M) { return loss_workspace_bytes(B, N, M); }
 

@@ -395,16 +395,11 @@ def mfma_f64_probe(device, reps: int = 2000):
     return ms.value, fl.value, tk.value
 
 
-def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method='triplet_loss', gamma: float = 0.5) -> torch.Tensor:
-    """The evaluation loss of MDGAT.forward (mdgat.py:486-594; csrc/loss.hip) on Z [B, N+1, M+1] (float32 or float64; the arithmetic is
-    fp64 either way) and ground-truth matches gt0 [B, N] / gt1 [B, M] (any integer dtype, -1 = unmatched; not rewritten).  ``method``:
-    ``'superglue'``, ``'triplet_loss'`` or ``'gap_loss'`` (config['loss_method']); ``gamma``: config['triplet_loss_gamma'].  Returns
-    the per-pair values [B] float64 - superglue / triplet: the pair's ratio / mean (the module's loss is their mean), gap: the pair's
-    loss.  Synchronises: a gt index outside [-1, M] / [-1, N] raises IndexError, as indexing does in the reference."""
+def _loss_args(Z, gt0, gt1, method):
+    """What both directions of the loss pass to the library: (method code, Z contiguous in its own precision, N, M, gt0, gt1 int64)."""
     _need_cuda(Z)
     m = _lib.LOSS_METHODS[method] if isinstance(method, str) else int(method)
-    f64 = Z.dtype == torch.float64
-    z = Z.to(torch.float64 if f64 else torch.float32).contiguous()
+    z = Z.to(torch.float64 if Z.dtype == torch.float64 else torch.float32).contiguous()
     B, N1, M1 = z.shape
     N, M = N1 - 1, M1 - 1
     if tuple(gt0.shape) != (B, N) or tuple(gt1.shape) != (B, M):
@@ -413,6 +408,12 @@ def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method=
         raise ValueError(f'the {method} loss needs N == M (N={N}, M={M}), as the reference\'s does')
     g0 = gt0.to(device=z.device, dtype=torch.int64).contiguous()
     g1 = gt1.to(device=z.device, dtype=torch.int64).contiguous()
+    return m, z, N, M, g0, g1
+
+
+def _matching_loss_values(Z, gt0, gt1, method, gamma):
+    m, z, N, M, g0, g1 = _loss_args(Z, gt0, gt1, method)
+    B, f64 = z.shape[0], z.dtype == torch.float64
     loss = torch.empty(B, dtype=torch.float64, device=z.device)
     bad = torch.zeros(1, dtype=torch.int32, device=z.device)
     lib = _lib.load()
@@ -426,3 +427,62 @@ def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method=
     if int(bad.item()):
         raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1)')
     return loss
+
+
+def matching_loss_backward(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method, gamma: float, dloss: torch.Tensor) -> torch.Tensor:
+    """Gradient of ``matching_loss`` with respect to Z (csrc/loss_grad.hip): Z [B, N+1, M+1] (float32 or float64), the gts and method
+    of the forward, and dloss [B] (any dtype and strides), one upstream weight per pair -> dZ [B, N+1, M+1] in Z's dtype, computed in
+    fp64: what autograd takes through the reference's loss code (mdgat.py:486-594), with its conventions - a clamp argument that is
+    exactly 0 passes the gradient, -log(exp(z)) is differentiated literally (non-finite where exp(z) underflows), ties between a
+    row's / column's largest non-positive entries (triplet) take the lowest index.  A pair's dZ is bitwise the same in any batch.
+    Synchronises: a gt index outside [-1, M] / [-1, N] raises IndexError."""
+    m, z, N, M, g0, g1 = _loss_args(Z, gt0, gt1, method)
+    B, f64 = z.shape[0], z.dtype == torch.float64
+    if dloss.device != z.device:
+        raise ValueError(f'dloss is on {dloss.device}, Z on {z.device}')
+    if tuple(dloss.shape) != (B,):
+        raise ValueError(f'dloss {tuple(dloss.shape)} does not fit Z {tuple(z.shape)}: expected [{B}]')
+    g = dloss.to(torch.float64).contiguous()
+    dZ = torch.empty(z.shape, dtype=torch.float64, device=z.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=z.device)
+    lib = _lib.load()
+    with torch.cuda.device(z.device):
+        need = lib.mdgat_loss_backward_workspace_bytes(B, N, M)
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=z.device)
+        off = (-ws.data_ptr()) % 256
+        fn = lib.mdgat_loss_backward_f64 if f64 else lib.mdgat_loss_backward
+        _lib.check(fn(B, N, M, z.data_ptr(), g0.data_ptr(), g1.data_ptr(), m, float(gamma), g.data_ptr(), dZ.data_ptr(), bad.data_ptr(),
+                      ws.data_ptr() + off, need, _stream(z)), 'mdgat_loss_backward_f64' if f64 else 'mdgat_loss_backward')
+    if int(bad.item()):
+        raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1)')
+    return dZ.to(Z.dtype)
+
+
+class _MatchingLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, gt0, gt1, method, gamma):
+        loss = _matching_loss_values(Z, gt0, gt1, method, gamma)
+        ctx.save_for_backward(Z, gt0, gt1)
+        ctx.method, ctx.gamma = method, gamma
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        Z, gt0, gt1 = ctx.saved_tensors
+        return matching_loss_backward(Z, gt0, gt1, ctx.method, ctx.gamma, dloss), None, None, None, None
+
+
+def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method='triplet_loss', gamma: float = 0.5) -> torch.Tensor:
+    """The evaluation loss of MDGAT.forward (mdgat.py:486-594; csrc/loss.hip) on Z [B, N+1, M+1] (float32 or float64; the arithmetic is
+    fp64 either way) and ground-truth matches gt0 [B, N] / gt1 [B, M] (any integer dtype, -1 = unmatched; not rewritten).  ``method``:
+    ``'superglue'``, ``'triplet_loss'`` or ``'gap_loss'`` (config['loss_method']); ``gamma``: config['triplet_loss_gamma'].  Returns
+    the per-pair values [B] float64 - superglue / triplet: the pair's ratio / mean (the module's loss is their mean), gap: the pair's
+    loss.  Synchronises: a gt index outside [-1, M] / [-1, N] raises IndexError, as indexing does in the reference.
+
+    Differentiable with respect to Z (``matching_loss_backward``; not twice): when Z requires grad and grad is enabled the result
+    carries a grad_fn, so ``matching_loss(log_optimal_transport(scores, bin_score, T), gt0, gt1, method).mean().backward()`` fills
+    ``scores.grad`` and ``bin_score.grad``.  The values, and without grad the kernels launched, are the same either way."""
+    if torch.is_grad_enabled() and isinstance(Z, torch.Tensor) and Z.requires_grad:
+        return _MatchingLoss.apply(Z, gt0, gt1, method, float(gamma))
+    return _matching_loss_values(Z, gt0, gt1, method, gamma)
