@@ -11,6 +11,7 @@
 #include "sinkhorn_f64.hpp"
 #include "coop_chain.hpp"
 #include "loss.hpp"
+#include "weights.hpp"
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -59,47 +60,28 @@ extern "C" size_t mdgat_blob_floats(int L) { return mdgat_blob_layout(L).total; 
 
 // ---------------------------------------------------------------------------------- handle
 struct mdgat_handle {
-    mdgat_config cfg;
-    int device;
-    BlobLayout bl;
-    float* weights;      // device, fp32 blob (pack.py layout)
-    _Float16* wsplit;    // device, split-f16 copies of the GNN / final_proj matrices (layer.hip)
-    double* weights64;   // device, the blob in fp64 (MDGAT_ARITH_FP64: f64.hip), else nullptr
-    double* wfrag64;     // device, per layer mlp.0 | mlp.3 | q|k|v once more in MFMA fragment order (layer_f64.hip), else nullptr
-    bool loaded, loaded64;
-    unsigned* host_error; // MDGAT_STATUS_WORDS host-mapped words the kernels set (common.hpp): Sinkhorn fallback taken, f16 range guard,
-                          // token of the last forward that matched a frame-0 keypoint
-    unsigned match_token; // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
+    mdgat_config cfg{};
+    int device = 0;
+    DeviceWeights w;     // the device copies of the checkpoint and their layout (weights.hpp)
+    bool loaded = false, loaded64 = false;
+    unsigned* host_error = nullptr; // MDGAT_STATUS_WORDS host-mapped words the kernels set (common.hpp): Sinkhorn fallback taken, f16 range guard,
+                                    // token of the last forward that matched a frame-0 keypoint
+    unsigned match_token = 0;       // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
     // Two lanes (forward_batched): the second lane's stream and the events that fork it off the caller's stream and join it again
-    int lanes;            // 1 or 2 (mdgat_set_lanes; default 2, MDGAT_FORWARD_LANES)
-    hipStream_t lane_stream;
-    hipEvent_t ev_fork, ev_join;
+    int lanes = 2;                  // 1 or 2 (mdgat_set_lanes; default 2, MDGAT_FORWARD_LANES)
+    hipStream_t lane_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // optional per-kernel-class timing of mdgat_forward (mdgat_profile): HIP events on the launch stream of each lane
-    bool prof_on;
+    bool prof_on = false;
     struct ProfLane { std::vector<hipEvent_t> ev; std::vector<int> cls; size_t n = 0; } prof[2];
-    double prof_ms[MDGAT_PROF_CLASSES];
-    long long prof_launches[MDGAT_PROF_CLASSES];
+    double prof_ms[MDGAT_PROF_CLASSES] = {};
+    long long prof_launches[MDGAT_PROF_CLASSES] = {};
     // One forward at a time per handle: the fork / join events, the second lane's stream and the profiling event lists are
     // per-handle state.  Two host threads calling mdgat_forward on one handle from two streams are serialised HERE (the enqueue
     // only - microseconds; the device work of the two calls still overlaps as far as their streams allow), so that one call's
     // lane can never fork off the other call's event record.  (The Python wrapper holds its own lock as well.)
     std::mutex enqueue;
 };
-
-// split-weight buffer: per layer the LDS images of layer.hip [w1 256 rows x 528 | w2 128 x 528 | qkv 384 x 272]
-// (row = hi plane | lo plane | 32 B pad, zero filled; output rows in the P/Q order of layer.hip except the v rows), then final_proj 128 x 272, then the encoder matrices.
-// The stage copies of layer.hip read whole KB: up to 512 B past a K = 256 block, hence the slack after final_proj.
-static constexpr size_t WS_ROW256 = 528, WS_ROW128 = 272;
-static constexpr size_t WS_W1 = 0, WS_W2 = 256 * WS_ROW256, WS_QKV = WS_W2 + 128 * WS_ROW256, WS_LAYER = WS_QKV + 384 * WS_ROW128;
-static constexpr size_t WS_FINAL = 128 * WS_ROW128 + 512;
-static size_t wsplit_halves(int L) { return WS_LAYER * (size_t)(2 * L) + WS_FINAL + MDGAT_ENC_SPLIT_HALVES; }
-// behind them, the same GNN / final_proj matrices once more in FRAGMENT order for layer_split.hip, whose waves load their
-// slice of the weights straight into registers: [row block of 16][k-step of 32][plane hi / lo][lane (row l15, column g)] x 16 B,
-// so that a wave's load instruction reads one contiguous KB (launch_frag_image; no pads)
-static constexpr size_t WF_W1 = 0, WF_W2 = 256 * 512, WF_QKV = WF_W2 + 128 * 512, WF_LAYER = WF_QKV + 384 * 256, WF_FINAL = 128 * 256;
-static size_t wfrag_halves(int L) { return WF_LAYER * (size_t)(2 * L) + WF_FINAL; }
-// fp64 fragment copies (layer_f64.hip: launch_frag64), per layer
-static constexpr size_t WF64_W1 = 0, WF64_W2 = 256 * 256, WF64_QKV = WF64_W2 + 128 * 256;
 
 extern "C" int mdgat_create(const mdgat_config* cfg, int device, mdgat_handle** out) {
     if (!cfg || !out) { mdgat_set_error("mdgat_create: null argument"); return MDGAT_ERR_BAD_ARG; }
@@ -122,33 +104,18 @@ extern "C" int mdgat_create(const mdgat_config* cfg, int device, mdgat_handle** 
     if (!h) { mdgat_set_error("mdgat_create: out of host memory"); return MDGAT_ERR_HIP; }
     h->cfg = *cfg;
     h->device = device;
-    h->bl = mdgat_blob_layout(cfg->L);
-    h->weights = nullptr;
-    h->wsplit = nullptr;
-    h->weights64 = nullptr;
-    h->wfrag64 = nullptr;
-    h->loaded = false;
-    h->loaded64 = false;
-    h->host_error = nullptr;
-    h->match_token = 0;
-    h->prof_on = false;
-    h->lane_stream = nullptr;
-    h->ev_fork = h->ev_join = nullptr;
-    {
-        const char* e = getenv("MDGAT_FORWARD_LANES");
-        h->lanes = (e && atoi(e) == 1) ? 1 : 2;
-    }
-    for (int c = 0; c < MDGAT_PROF_CLASSES; ++c) { h->prof_ms[c] = 0.0; h->prof_launches[c] = 0; }
+    DeviceWeights& w = h->w;
+    w.bl = mdgat_blob_layout(cfg->L);
+    w.im = mdgat_weight_images(w.bl, cfg->L);
+    if (const char* e = getenv("MDGAT_FORWARD_LANES")) h->lanes = atoi(e) == 1 ? 1 : 2;
     int prev = 0;
     (void)hipGetDevice(&prev);
     int rc = mdgat_check_hip(hipSetDevice(device), "hipSetDevice");
-    if (!rc) rc = mdgat_check_hip(hipMalloc(&h->weights, h->bl.total * sizeof(float)), "hipMalloc(weights)");
-    if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64) rc = mdgat_check_hip(hipMalloc(&h->weights64, h->bl.total * sizeof(double)), "hipMalloc(fp64 weights)");
-    if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64)
-        rc = mdgat_check_hip(hipMalloc(&h->wfrag64, (layer_f64_frag_doubles() * (size_t)(2 * cfg->L) + encoder_f64_frags().total) * sizeof(double)),
-                             "hipMalloc(fp64 weight fragments)");
-    if (!rc) rc = mdgat_check_hip(hipMalloc(&h->wsplit, (wsplit_halves(cfg->L) + wfrag_halves(cfg->L)) * sizeof(_Float16)), "hipMalloc(split weights)");
-    if (!rc) rc = mdgat_check_hip(hipMemset(h->wsplit, 0, (wsplit_halves(cfg->L) + wfrag_halves(cfg->L)) * sizeof(_Float16)), "hipMemset(split weights)");
+    if (!rc) rc = mdgat_check_hip(hipMalloc(&w.blob, w.bl.total * sizeof(float)), "hipMalloc(weights)");
+    if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64) rc = mdgat_check_hip(hipMalloc(&w.blob64, w.bl.total * sizeof(double)), "hipMalloc(fp64 weights)");
+    if (!rc && cfg->arithmetic == MDGAT_ARITH_FP64) rc = mdgat_check_hip(hipMalloc(&w.frag64, w.im.doubles * sizeof(double)), "hipMalloc(fp64 weight fragments)");
+    if (!rc) rc = mdgat_check_hip(hipMalloc(&w.split, w.im.halves * sizeof(_Float16)), "hipMalloc(split weights)");
+    if (!rc) rc = mdgat_check_hip(hipMemset(w.split, 0, w.im.halves * sizeof(_Float16)), "hipMemset(split weights)");
     if (!rc) rc = mdgat_check_hip(hipHostMalloc(reinterpret_cast<void**>(&h->host_error), MDGAT_STATUS_WORDS * sizeof(unsigned), hipHostMallocMapped), "hipHostMalloc(status words)");
     if (!rc) for (int i = 0; i < MDGAT_STATUS_WORDS; ++i) h->host_error[i] = 0;
     if (!rc) rc = mdgat_check_hip(hipStreamCreateWithFlags(&h->lane_stream, hipStreamNonBlocking), "hipStreamCreate(lane)");
@@ -173,12 +140,13 @@ __global__ __launch_bounds__(256) void blob_absmax_kernel(const float* w, size_t
 
 extern "C" int mdgat_load_weights(mdgat_handle* h, const float* blob, size_t n_floats, int on_device) {
     if (!h || !blob) { mdgat_set_error("mdgat_load_weights: null argument"); return MDGAT_ERR_BAD_ARG; }
-    if (n_floats != h->bl.total) {
-        mdgat_set_error("mdgat_load_weights: blob has %zu floats, expected %zu for L=%d", n_floats, h->bl.total, h->cfg.L);
+    const DeviceWeights& w = h->w;
+    if (n_floats != w.bl.total) {
+        mdgat_set_error("mdgat_load_weights: blob has %zu floats, expected %zu for L=%d", n_floats, w.bl.total, h->cfg.L);
         return MDGAT_ERR_BAD_ARG;
     }
-    if (blob != h->weights) {
-        if (int rc = mdgat_check_hip(hipMemcpy(h->weights, blob, n_floats * sizeof(float),
+    if (blob != w.blob) {
+        if (int rc = mdgat_check_hip(hipMemcpy(w.blob, blob, n_floats * sizeof(float),
                                                on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice),
                                      "hipMemcpy(weights)"))
             return rc;
@@ -187,18 +155,17 @@ extern "C" int mdgat_load_weights(mdgat_handle* h, const float* blob, size_t n_f
     int prev = 0;
     (void)hipGetDevice(&prev);
     int rc = mdgat_check_hip(hipSetDevice(h->device), "hipSetDevice");
-    const BlobLayout& bl = h->bl;
     h->loaded = false;
     if (!rc) {
         // f16 operand range of the WEIGHTS (the kernels guard activations): a weight beyond 6e4 would become an infinite f16 head,
         // and what that makes of the activations a ReLU can turn back into finite garbage (max(NaN, 0) = 0).  The packer brings
         // every rescalable channel to unit scale (pack.py: gauge fixing), so this only fires for checkpoints that are broken or
         // hold non-finite values.
-        unsigned* dmax = reinterpret_cast<unsigned*>(h->wsplit);       // (scratch: the split images are written below)
+        unsigned* dmax = reinterpret_cast<unsigned*>(w.split);       // (scratch: the split images are written below)
         rc = mdgat_check_hip(hipMemset(dmax, 0, sizeof(unsigned)), "hipMemset(weight range)");
         unsigned hmax = 0;
         if (!rc) {
-            hipLaunchKernelGGL(blob_absmax_kernel, dim3(256), dim3(256), 0, nullptr, h->weights, n_floats, dmax);
+            hipLaunchKernelGGL(blob_absmax_kernel, dim3(256), dim3(256), 0, nullptr, w.blob, n_floats, dmax);
             rc = mdgat_check_hip(hipMemcpy(&hmax, dmax, sizeof(unsigned), hipMemcpyDeviceToHost), "hipMemcpy(weight range)");
         }
         if (!rc && hmax >= __builtin_bit_cast(unsigned, MDGAT_F16_GUARD)) {
@@ -209,27 +176,12 @@ extern "C" int mdgat_load_weights(mdgat_handle* h, const float* blob, size_t n_f
         }
         if (!rc) rc = mdgat_check_hip(hipMemset(dmax, 0, sizeof(unsigned)), "hipMemset(weight range)");
     }
-    for (int i = 0; i < 2 * h->cfg.L && !rc; ++i) {
-        const float* lw = h->weights + bl.layer0 + (size_t)i * bl.layer_stride;
-        _Float16* ls = h->wsplit + WS_LAYER * (size_t)i;
-        rc = launch_split_rows(lw + bl.mlp1_w, ls + WS_W1, 256, 256, WS_ROW256, 256, nullptr);
-        if (!rc) rc = launch_split_rows(lw + bl.mlp2_w, ls + WS_W2, 128, 256, WS_ROW256, 128, nullptr);
-        if (!rc) rc = launch_split_rows(lw + bl.qkv_w, ls + WS_QKV, 384, 128, WS_ROW128, 256, nullptr);
-        _Float16* lf = h->wsplit + wsplit_halves(h->cfg.L) + WF_LAYER * (size_t)i;
-        if (!rc) rc = launch_frag_image(ls + WS_W1, lf + WF_W1, 256, 256, WS_ROW256, nullptr);
-        if (!rc) rc = launch_frag_image(ls + WS_W2, lf + WF_W2, 128, 256, WS_ROW256, nullptr);
-        if (!rc) rc = launch_frag_image(ls + WS_QKV, lf + WF_QKV, 384, 128, WS_ROW128, nullptr);
-    }
-    if (!rc) rc = launch_split_rows(h->weights + bl.final_w, h->wsplit + WS_LAYER * (size_t)(2 * h->cfg.L), 128, 128, WS_ROW128, 128, nullptr);
-    if (!rc) rc = launch_frag_image(h->wsplit + WS_LAYER * (size_t)(2 * h->cfg.L), h->wsplit + wsplit_halves(h->cfg.L) + WF_LAYER * (size_t)(2 * h->cfg.L),
-                                    128, 128, WS_ROW128, nullptr);
-    {
-        _Float16* es = h->wsplit + WS_LAYER * (size_t)(2 * h->cfg.L) + WS_FINAL;
-        if (!rc) rc = launch_split_rows(h->weights + bl.kenc1_w, es, 64, 32, 64, 0, nullptr);
-        if (!rc) rc = launch_split_rows(h->weights + bl.kenc2_w, es + 64 * 64, 128, 64, 128, 0, nullptr);
-        if (!rc) rc = launch_split_rows_pad(h->weights + bl.denc0_w, es + 64 * 64 + 128 * 128, 64, 33, 48, nullptr);
-        if (!rc) rc = launch_split_rows(h->weights + bl.denc1_w, es + 64 * 64 + 128 * 128 + 64 * 96, 128, 64, 128, 0, nullptr);
-        if (!rc) rc = launch_split_rows(h->weights + bl.encl_w, es + 64 * 64 + 128 * 128 + 64 * 96 + 128 * 128, 128, 256, 512, 0, nullptr);
+    // every matrix that has a row image (WeightImages), and its fragment image from that
+    for (const WeightMat& m : w.im.mats) {
+        if (rc || m.row == NO_IMAGE) continue;
+        rc = m.kpad ? launch_split_rows_pad(w.blob + m.w, w.split + m.row, m.rows, m.K, m.kpad, nullptr)
+                    : launch_split_rows(w.blob + m.w, w.split + m.row, m.rows, m.K, m.pitch, m.nperm, nullptr);
+        if (!rc && m.frag != NO_IMAGE) rc = launch_frag_image(w.split + m.row, w.split + m.frag, m.rows, m.K, m.pitch, nullptr);
     }
     if (!rc) rc = mdgat_check_hip(hipDeviceSynchronize(), "split weights");
     (void)hipSetDevice(prev);
@@ -238,39 +190,28 @@ extern "C" int mdgat_load_weights(mdgat_handle* h, const float* blob, size_t n_f
     return MDGAT_OK;
 }
 
-extern "C" float* mdgat_weights_device_ptr(mdgat_handle* h) { return h ? h->weights : nullptr; }
-extern "C" double* mdgat_weights_f64_device_ptr(mdgat_handle* h) { return h ? h->weights64 : nullptr; }
+extern "C" float* mdgat_weights_device_ptr(mdgat_handle* h) { return h ? h->w.blob : nullptr; }
+extern "C" double* mdgat_weights_f64_device_ptr(mdgat_handle* h) { return h ? h->w.blob64 : nullptr; }
 
 extern "C" int mdgat_load_weights_f64(mdgat_handle* h, const double* blob, size_t n_doubles, int on_device) {
     if (!h || !blob) { mdgat_set_error("mdgat_load_weights_f64: null argument"); return MDGAT_ERR_BAD_ARG; }
-    if (!h->weights64) { mdgat_set_error("mdgat_load_weights_f64: the handle was not created with MDGAT_ARITH_FP64"); return MDGAT_ERR_BAD_ARG; }
-    if (n_doubles != h->bl.total) {
-        mdgat_set_error("mdgat_load_weights_f64: blob has %zu doubles, expected %zu for L=%d", n_doubles, h->bl.total, h->cfg.L);
+    const DeviceWeights& w = h->w;
+    if (!w.blob64) { mdgat_set_error("mdgat_load_weights_f64: the handle was not created with MDGAT_ARITH_FP64"); return MDGAT_ERR_BAD_ARG; }
+    if (n_doubles != w.bl.total) {
+        mdgat_set_error("mdgat_load_weights_f64: blob has %zu doubles, expected %zu for L=%d", n_doubles, w.bl.total, h->cfg.L);
         return MDGAT_ERR_BAD_ARG;
     }
     h->loaded64 = false;
-    if (blob != h->weights64)
-        if (int rc = mdgat_check_hip(hipMemcpy(h->weights64, blob, n_doubles * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice),
+    if (blob != w.blob64)
+        if (int rc = mdgat_check_hip(hipMemcpy(w.blob64, blob, n_doubles * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice),
                                      "hipMemcpy(fp64 weights)"))
             return rc;
     // the layer-tail kernel's copies in fragment order (synchronous, like the copy above)
     int prev = 0;
     (void)hipGetDevice(&prev);
     int rc = mdgat_check_hip(hipSetDevice(h->device), "hipSetDevice");
-    const BlobLayout& bl = h->bl;
-    for (int i = 0; i < 2 * h->cfg.L && !rc; ++i) {
-        const double* lw = h->weights64 + bl.layer0 + (size_t)i * bl.layer_stride;
-        double* lf = h->wfrag64 + layer_f64_frag_doubles() * (size_t)i;
-        rc = launch_frag64(lw + bl.mlp1_w, lf + WF64_W1, 256, 256, nullptr);
-        if (!rc) rc = launch_frag64(lw + bl.mlp2_w, lf + WF64_W2, 128, 256, nullptr);
-        if (!rc) rc = launch_frag64(lw + bl.qkv_w, lf + WF64_QKV, 384, 128, nullptr);
-    }
-    // the encoder matrices behind the layers' (encoder_f64_frags)
-    const EncoderF64Frags ef = encoder_f64_frags();
-    double* efrag = h->wfrag64 + layer_f64_frag_doubles() * (size_t)(2 * h->cfg.L);
-    const struct { Frag64 m; size_t src; } enc[6] = {{ef.k0, bl.kenc0_w}, {ef.d0, bl.denc0_w}, {ef.k1, bl.kenc1_w}, {ef.k2, bl.kenc2_w},
-                                                     {ef.d1, bl.denc1_w}, {ef.l, bl.encl_w}};
-    for (int j = 0; j < 6 && !rc; ++j) rc = launch_frag64(h->weights64 + enc[j].src, efrag + enc[j].m.ofs, enc[j].m.n, enc[j].m.k, nullptr);
+    for (const WeightMat& m : w.im.mats)
+        if (!rc && m.frag64 != NO_IMAGE) rc = launch_frag64(w.blob64 + m.w, w.frag64 + m.frag64, m.rows, m.K, nullptr);
     if (!rc) rc = mdgat_check_hip(hipDeviceSynchronize(), "fp64 weight fragments");
     (void)hipSetDevice(prev);
     if (rc) return rc;
@@ -280,10 +221,8 @@ extern "C" int mdgat_load_weights_f64(mdgat_handle* h, const double* blob, size_
 
 extern "C" void mdgat_destroy(mdgat_handle* h) {
     if (!h) return;
-    if (h->weights) (void)hipFree(h->weights);
-    if (h->wsplit) (void)hipFree(h->wsplit);
-    if (h->weights64) (void)hipFree(h->weights64);
-    if (h->wfrag64) (void)hipFree(h->wfrag64);
+    for (void* p : {(void*)h->w.blob, (void*)h->w.split, (void*)h->w.blob64, (void*)h->w.frag64})
+        if (p) (void)hipFree(p);
     if (h->host_error) (void)hipHostFree(h->host_error);
     if (h->lane_stream) { (void)hipStreamSynchronize(h->lane_stream); (void)hipStreamDestroy(h->lane_stream); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -342,10 +281,16 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss) {
 // ---------------------------------------------------------------------------------- forward
 // inputs of a forward: six fp32 arrays, or raw 37-float frame records, or (MDGAT_ARITH_FP64) six fp64 arrays
 struct FwdIn {
-    const float *kpts0, *sigma0, *fpfh0, *kpts1, *sigma1, *fpfh1;
-    const float *rec0, *rec1;
-    int normalize_fpfh;
-    const double *dk0, *ds0, *df0, *dk1, *ds1, *df1;
+    const float *kpts0 = nullptr, *sigma0 = nullptr, *fpfh0 = nullptr, *kpts1 = nullptr, *sigma1 = nullptr, *fpfh1 = nullptr;
+    const float *rec0 = nullptr, *rec1 = nullptr;
+    int normalize_fpfh = 0;
+    const double *dk0 = nullptr, *ds0 = nullptr, *df0 = nullptr, *dk1 = nullptr, *ds1 = nullptr, *df1 = nullptr;
+    static FwdIn arrays(const float* k0, const float* s0, const float* f0, const float* k1, const float* s1, const float* f1) {
+        FwdIn in; in.kpts0 = k0; in.sigma0 = s0; in.fpfh0 = f0; in.kpts1 = k1; in.sigma1 = s1; in.fpfh1 = f1; return in;
+    }
+    static FwdIn arrays(const double* k0, const double* s0, const double* f0, const double* k1, const double* s1, const double* f1) {
+        FwdIn in; in.dk0 = k0; in.ds0 = s0; in.df0 = f0; in.dk1 = k1; in.ds1 = s1; in.df1 = f1; return in;
+    }
     // the same inputs from pair c on (slices of a batch)
     FwdIn from(size_t c, int N, int M) const {
         auto o = [](auto* q, size_t n) { return q ? q + n : q; };
@@ -520,7 +465,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     // (227-232) run as one launch (layer_f64.hip), the hidden activation never leaving the chip, and so do the two encoders with
     // layer 0's projection; the last fp64 launch also writes the fp32 rounding of x, the hand-over.  mdgat_set_f64_layer_fusion(0)
     // keeps the one-product-per-launch form (bit-identical).
-    p.fused64 = f64 && layer_f64_fused() && h->wfrag64;
+    p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
     p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
     return MDGAT_OK;
 }
@@ -566,21 +511,18 @@ struct Fwd {
         mark(-1);
         return MDGAT_OK;
     }
-    // an fp64 product over all R rows with the blob's weights at wofs / bofs (GemmF64Args)
-    int gemm64(const double* A0, int lda0, int K0, const double* A1, int lda1, size_t wofs, size_t bofs, int relu, const double* Rs, double* C,
-               int ldc, int cout, int K) const {
-        const GemmF64Args g{A0, lda0, K0, A1, lda1, h->weights64 + wofs, K, h->weights64 + bofs, Rs, ldc, C, ldc, R, cout, K, relu, guard()};
+    // an fp64 product over all R rows with matrix m of the fp64 blob: C [R][m.rows] = act([A0 (K0 columns) | A1] W^T + b) (+ Rs)
+    int gemm64(const WeightMat& m, const double* A0, int K0, const double* A1, int lda1, int relu, const double* Rs, double* C) const {
+        const double* w64 = h->w.blob64;
+        const GemmF64Args g{A0, K0, K0, A1, lda1, w64 + m.w, m.K, w64 + m.b, Rs, m.rows, C, m.rows, R, m.rows, m.K, relu, guard()};
         return launch_gemm_f64(g, s);
     }
 };
 
 // ---- encoders (mdgat.py:392-393), one fused launch ----
 static int encoders32(Fwd& f, const FwdIn& in) {
-    EncoderLaunch e{};
-    e.kpts0 = in.kpts0; e.sigma0 = in.sigma0; e.fpfh0 = in.fpfh0; e.kpts1 = in.kpts1; e.sigma1 = in.sigma1; e.fpfh1 = in.fpfh1;
-    e.rec0 = in.rec0; e.rec1 = in.rec1; e.normalize = in.normalize_fpfh;
-    e.w = f.h->weights; e.bl = &f.h->bl; e.es = f.h->wsplit + WS_LAYER * (size_t)(2 * f.h->cfg.L) + WS_FINAL;
-    e.x = f.ws.x; e.B = f.B; e.N = f.N; e.M = f.M;
+    const EncoderLaunch e{in.kpts0, in.sigma0, in.fpfh0, in.kpts1, in.sigma1, in.fpfh1, in.rec0, in.rec1, in.normalize_fpfh,
+                          f.h->w.encoder32(), f.ws.x, f.B, f.N, f.M};
     if (int rc = launch_encoder(e, f.s)) return rc;
     f.mark(MDGAT_PROF_ENCODER);
     return f.tap(f.taps.x_enc, f.ws.x, (size_t)f.R * 128, "tap x_enc");
@@ -589,8 +531,7 @@ static int encoders32(Fwd& f, const FwdIn& in) {
 // ---- MDGAT_ARITH_FP64 (f64.hip): the inputs, the encoders and the layers before p.first in the reference's arithmetic ----
 static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     const Workspace& ws = f.ws;
-    const BlobLayout& bl = f.h->bl;
-    const double* w64 = f.h->weights64;
+    const DeviceWeights& w = f.h->w;
     const size_t Rz = (size_t)f.R;
     const int first = f.p.first;
     // the assembled inputs at the END of the hidden area (the fused encoder writes layer 0's q | k | v while other workgroups still
@@ -603,30 +544,27 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     f.mark(MDGAT_PROF_F64_OTHER);
     // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
     if (f.p.fused64) {
-        const EncoderF64Frags ef = encoder_f64_frags();
-        const double* fr = f.h->wfrag64 + layer_f64_frag_doubles() * (size_t)(2 * f.h->cfg.L);
-        const EncoderF64Args e{in4, in33, fr + ef.k0.ofs, w64 + bl.kenc0_b, fr + ef.d0.ofs, w64 + bl.denc0_b, fr + ef.k1.ofs, w64 + bl.kenc1_b,
-                               fr + ef.k2.ofs, w64 + bl.kenc2_b, fr + ef.d1.ofs, w64 + bl.denc1_b, fr + ef.l.ofs, w64 + bl.encl_b,
-                               first > 0 ? f.h->wfrag64 + WF64_QKV : nullptr, first > 0 ? w64 + bl.layer0 + bl.qkv_b : nullptr,
+        const Mat64 k0 = w.mat64(&w.im.enc(ENC_K0)), d0 = w.mat64(&w.im.enc(ENC_D0)), k1 = w.mat64(&w.im.enc(ENC_K1)), k2 = w.mat64(&w.im.enc(ENC_K2)),
+                    d1 = w.mat64(&w.im.enc(ENC_D1)), l = w.mat64(&w.im.enc(ENC_L)), q = w.mat64(first > 0 ? &w.im.proj(0) : nullptr);
+        const EncoderF64Args e{in4, in33, k0.wf, k0.b, d0.wf, d0.b, k1.wf, k1.b, k2.wf, k2.b, d1.wf, d1.b, l.wf, l.b, q.wf, q.b,
                                ws.x64, ws.qkv64, first == 0 ? ws.x : nullptr, f.R, f.guard()};
         if (int rc = launch_encoder_f64(e, f.s)) return rc;
     } else {
         double *hk1 = ws.qkv64, *hk2 = hk1 + Rz * 32, *hk3 = hk2 + Rz * 64;      // the keypoint encoder's stages
         double *hd1 = hk3 + Rz * 128, *hd2 = hd1 + Rz * 64;                       // the descriptor encoder's
-        if (int rc = f.gemm64(in4, 4, 4, nullptr, 0, bl.kenc0_w, bl.kenc0_b, 1, nullptr, hk1, 32, 32, 4)) return rc;
-        if (int rc = f.gemm64(hk1, 32, 32, nullptr, 0, bl.kenc1_w, bl.kenc1_b, 1, nullptr, hk2, 64, 64, 32)) return rc;
-        if (int rc = f.gemm64(hk2, 64, 64, nullptr, 0, bl.kenc2_w, bl.kenc2_b, 1, nullptr, hk3, 128, 128, 64)) return rc;
-        if (int rc = f.gemm64(in33, 33, 33, nullptr, 0, bl.denc0_w, bl.denc0_b, 1, nullptr, hd1, 64, 64, 33)) return rc;
-        if (int rc = f.gemm64(hd1, 64, 64, nullptr, 0, bl.denc1_w, bl.denc1_b, 1, nullptr, hd2, 128, 128, 64)) return rc;
-        if (int rc = f.gemm64(hd2, 128, 128, hk3, 128, bl.encl_w, bl.encl_b, 0, nullptr, ws.x64, 128, 128, 256)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_K0), in4, 4, nullptr, 0, 1, nullptr, hk1)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_K1), hk1, 32, nullptr, 0, 1, nullptr, hk2)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_K2), hk2, 64, nullptr, 0, 1, nullptr, hk3)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_D0), in33, 33, nullptr, 0, 1, nullptr, hd1)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_D1), hd1, 64, nullptr, 0, 1, nullptr, hd2)) return rc;
+        if (int rc = f.gemm64(w.im.enc(ENC_L), hd2, 128, hk3, 128, 0, nullptr, ws.x64)) return rc;
     }
     f.mark(MDGAT_PROF_F64_GEMM);
     if (int rc = f.tap(f.taps.x_enc, ws.x64, Rz * 128)) return rc;
     for (int i = 0; i < first; ++i) {
-        const size_t lo = bl.layer0 + (size_t)i * bl.layer_stride;
         // MultiHeadedAttention (mdgat.py:223-237; merge is folded into mlp.0 by pack.py), attention / dynamic_attention (190-210)
         if (!f.p.fused64) {
-            if (int rc = f.gemm64(ws.x64, 128, 128, nullptr, 0, lo + bl.qkv_w, lo + bl.qkv_b, 0, nullptr, ws.qkv64, 384, 384, 128)) return rc;
+            if (int rc = f.gemm64(w.im.proj(i), ws.x64, 128, nullptr, 0, 0, nullptr, ws.qkv64)) return rc;
             f.mark(MDGAT_PROF_F64_GEMM);
         }
         const int kk = f.h->cfg.topk[i];
@@ -634,15 +572,13 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
         f.mark(kk > 0 ? MDGAT_PROF_F64_ATTENTION_TOPK : MDGAT_PROF_F64_ATTENTION_FULL);
         // AttentionalPropagation + residual (mdgat.py:246-248, 274)
         if (f.p.fused64) {
-            const double* lf = f.h->wfrag64 + layer_f64_frag_doubles() * (size_t)i;
             const bool last = i + 1 == first;
-            const LayerF64Args t{ws.x64, ws.msg64, lf + WF64_W1, w64 + lo + bl.mlp1_b, lf + WF64_W2, w64 + lo + bl.mlp2_b,
-                                 last ? nullptr : lf + layer_f64_frag_doubles() + WF64_QKV, last ? nullptr : w64 + lo + bl.layer_stride + bl.qkv_b,
-                                 ws.qkv64, last ? ws.x : nullptr, f.R, f.guard(), ws.hid64};
+            const Mat64 w1 = w.mat64(&w.im.layer(i, MAT_W1)), w2 = w.mat64(&w.im.layer(i, MAT_W2)), q = w.mat64(last ? nullptr : &w.im.proj(i + 1));
+            const LayerF64Args t{ws.x64, ws.msg64, w1.wf, w1.b, w2.wf, w2.b, q.wf, q.b, ws.qkv64, last ? ws.x : nullptr, f.R, f.guard(), ws.hid64};
             if (int rc = launch_layer_tail_f64(t, coop)) return rc;
         } else {
-            if (int rc = f.gemm64(ws.x64, 128, 128, ws.msg64, 128, lo + bl.mlp1_w, lo + bl.mlp1_b, 1, nullptr, ws.hid64, 256, 256, 256)) return rc;
-            if (int rc = f.gemm64(ws.hid64, 256, 256, nullptr, 0, lo + bl.mlp2_w, lo + bl.mlp2_b, 0, ws.x64, ws.x64, 128, 128, 256)) return rc;
+            if (int rc = f.gemm64(w.im.layer(i, MAT_W1), ws.x64, 128, ws.msg64, 128, 1, nullptr, ws.hid64)) return rc;
+            if (int rc = f.gemm64(w.im.layer(i, MAT_W2), ws.hid64, 256, nullptr, 0, 0, ws.x64, ws.x64)) return rc;
         }
         f.mark(MDGAT_PROF_F64_GEMM);
         if (int rc = f.tap(f.x_tap(i), ws.x64, Rz * 128)) return rc;
@@ -657,7 +593,7 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
     const int B = f.B, N = f.N, M = f.M;
     double* mdesc64 = ws.msg64;          // (the message and q | k | v of the last layer are dead)
     double* scores64 = ws.scores64;      // [B][N][M]: in q | k | v's room while N M <= 384 (N + M)
-    if (int rc = f.gemm64(ws.x64, 128, 128, nullptr, 0, f.h->bl.final_w, f.h->bl.final_b, 0, nullptr, mdesc64, 128, 128, 128)) return rc;
+    if (int rc = f.gemm64(f.h->w.im.proj(2 * f.h->cfg.L), ws.x64, 128, nullptr, 0, 0, nullptr, mdesc64)) return rc;
     if (int rc = f.tap(f.taps.mdesc, mdesc64, (size_t)f.R * 128)) return rc;
     const GemmF64Args sg{mdesc64, 128, 128, nullptr, 0, mdesc64 + (size_t)N * 128, 128, nullptr, nullptr, 0, scores64, M, N, M, 128, 0, f.guard(),
                          0.08838834764831845 /* 1 / sqrt(128) */, B, (long long)(N + M) * 128, (long long)(N + M) * 128, (long long)N * M};
@@ -667,7 +603,7 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
     const Sk64Bests b = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
     const SkExtract ex = f.extract(o);
     if (int rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
-                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->weights64 + f.h->bl.bin_score)) return rc;
+                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score)) return rc;
     if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const double*>(ws.Z64));
@@ -685,31 +621,23 @@ static int hand_over(Fwd& f) {
 // launch i: [attention of layer i] -> [mlp + residual of layer i | q/k/v of layer i + 1 (or final_proj into ws.hid)]
 static int layers32(Fwd& f) {
     const mdgat_handle* h = f.h;
-    const BlobLayout& bl = h->bl;
-    const float* w = h->weights;
     const int L2 = 2 * h->cfg.L;
-    const _Float16* wfrag = h->wsplit + wsplit_halves(h->cfg.L);      // fragment-order copies (layer_split.hip)
     // a layer launch whose projection is layer j's q | k | v, or final_proj behind the last layer (j == 2L)
     auto launch = [&](LayerLaunch p, int j, int cls) {
         p.x = f.ws.x; p.R = f.R; p.N = f.N; p.M = f.M; p.out = f.q16; p.mdesc = f.ws.hid; p.guard = f.guard();
-        if (j < L2) { p.mode3 = 1; p.w3s = h->wsplit + WS_LAYER * (size_t)j + WS_QKV; p.w3f = wfrag + WF_LAYER * (size_t)j + WF_QKV; p.b3 = w + bl.layer0 + (size_t)j * bl.layer_stride + bl.qkv_b; }
-        else { p.mode3 = 2; p.w3s = h->wsplit + WS_LAYER * (size_t)L2; p.w3f = wfrag + WF_LAYER * (size_t)L2; p.b3 = w + bl.final_b; }
+        p.proj = h->w.proj32(j);
         const int rc = launch_layer(p, f.s);
         if (!rc) f.mark(cls);
         return rc;
     };
     if (int rc = launch(LayerLaunch{}, f.p.first, MDGAT_PROF_LAYER_FIRST)) return rc;
     for (int i = f.p.first; i < L2; ++i) {
-        const float* lw = w + bl.layer0 + (size_t)i * bl.layer_stride;
-        const _Float16* ls = h->wsplit + WS_LAYER * (size_t)i;
-        const _Float16* lf = wfrag + WF_LAYER * (size_t)i;
         const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
         const int kk = h->cfg.topk[i];
         if (int rc = launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
         LayerLaunch p{};
-        p.msg = f.ws.msg; p.do_mlp = 1;
-        p.w1s = ls + WS_W1; p.w1f = lf + WF_W1; p.b1 = lw + bl.mlp1_b; p.w2s = ls + WS_W2; p.w2f = lf + WF_W2; p.b2 = lw + bl.mlp2_b;
+        p.msg = f.ws.msg; p.do_mlp = 1; p.mlp = h->w.layer32(i);
         if (int rc = launch(p, i + 1, i + 1 < L2 ? MDGAT_PROF_LAYER : MDGAT_PROF_LAYER_LAST)) return rc;
         if (int rc = f.tap(f.x_tap(i), f.ws.x, (size_t)f.R * 128, "tap x_layers")) return rc;
     }
@@ -732,7 +660,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
     // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
     float* Zout = o.Z ? o.Z : (f.p.cluster32 && !o.loss ? nullptr : ws.Z);
     const SkExtract ex = f.extract(o);
-    if (int rc = launch_sinkhorn(B, N, M, ws.scores, f.h->weights + f.h->bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
+    if (int rc = launch_sinkhorn(B, N, M, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
                               f.status, o.Z ? o.Z : ws.Z, sk_clear != 0)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const float*>(Zout));
@@ -827,40 +755,40 @@ static int forward_batched(mdgat_handle* h, int B, int N, int M, const FwdIn& in
     return prof_collect(h);
 }
 
+// the array entry points: `who` with its six input arrays, fp32 or fp64
+template <typename T> static int forward_arrays(const char* who, mdgat_handle* h, int B, int N, int M, const T* k0, const T* s0, const T* f0, const T* k1,
+                                                const T* s1, const T* f1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
+                                                const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream, const mdgat_loss_request* req = nullptr) {
+    if (!k0 || !s0 || !f0 || !k1 || !s1 || !f1) { mdgat_set_error("%s: null input pointer", who); return MDGAT_ERR_BAD_ARG; }
+    return forward_batched(h, B, N, M, FwdIn::arrays(k0, s0, f0, k1, s1, f1), matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
+}
+
 extern "C" int mdgat_forward(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
                              const float* fpfh0, const float* kpts1, const float* sigma1, const float* fpfh1,
                              int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
                              const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward: null input pointer"); return MDGAT_ERR_BAD_ARG; }
-    const FwdIn in{kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+    return forward_arrays("mdgat_forward", h, B, N, M, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M, const double* kpts0, const double* sigma0,
                                  const double* fpfh0, const double* kpts1, const double* sigma1, const double* fpfh1,
                                  int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
                                  const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_f64: null input pointer"); return MDGAT_ERR_BAD_ARG; }
-    const FwdIn in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1};
-    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+    return forward_arrays("mdgat_forward_f64", h, B, N, M, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
                                   const float* fpfh0, const float* kpts1, const float* sigma1, const float* fpfh1,
                                   int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
                                   const mdgat_taps* taps, const mdgat_loss_request* req, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_loss: null input pointer"); return MDGAT_ERR_BAD_ARG; }
-    const FwdIn in{kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
+    return forward_arrays("mdgat_forward_loss", h, B, N, M, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
 }
 
 extern "C" int mdgat_forward_f64_loss(mdgat_handle* h, int B, int N, int M, const double* kpts0, const double* sigma0,
                                       const double* fpfh0, const double* kpts1, const double* sigma1, const double* fpfh1,
                                       int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
                                       const mdgat_taps* taps, const mdgat_loss_request* req, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1) { mdgat_set_error("mdgat_forward_f64_loss: null input pointer"); return MDGAT_ERR_BAD_ARG; }
-    const FwdIn in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1};
-    return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
+    return forward_arrays("mdgat_forward_f64_loss", h, B, N, M, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream, req);
 }
 
 extern "C" int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* frames0, const float* frames1,
@@ -868,7 +796,8 @@ extern "C" int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const 
                                     float* mscores1, float* Z, const mdgat_taps* taps, void* workspace,
                                     size_t workspace_bytes, void* stream) {
     if (!frames0 || !frames1) { mdgat_set_error("mdgat_forward_frames: null frame pointer"); return MDGAT_ERR_BAD_ARG; }
-    const FwdIn in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, frames0, frames1, normalize_fpfh, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    FwdIn in;
+    in.rec0 = frames0; in.rec1 = frames1; in.normalize_fpfh = normalize_fpfh;
     return forward_batched(h, B, N, M, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
 }
 

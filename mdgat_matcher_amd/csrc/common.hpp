@@ -128,18 +128,20 @@ int launch_gemm(const GemmArgs& a, hipStream_t s);
 int launch_scores(int B, int N, int M, const float* mdesc, float* scores, float scale, hipStream_t s, void* zero = nullptr, size_t zero_bytes = 0,
                   unsigned* guard = nullptr);
 
-// fused encoders (encoder.hip).  es = split weights [kenc.3 64x2x32 | kenc.6 128x2x64 | denc.0 64x2x48 | denc.3 128x2x64 |
-// last convs 128x2x256]; inputs either as separate arrays or as raw 37-float frame records
+// fused encoders (encoder.hip); inputs either as separate arrays or as raw 37-float frame records
+struct Encoder32 {   // the encoder's weights (weights.hpp): kenc.0 and the biases in the fp32 blob, the other matrices as split row images
+    const float* w;
+    size_t kenc0_w, kenc0_b, denc0_b, kenc1_b, kenc2_b, denc1_b, encl_b;
+    const _Float16 *k1s, *k2s, *d0s, *d1s, *els;   // [rows][2][K]: 64x32, 128x64, 64x48, 128x64, 128x256
+};
 struct EncoderLaunch {
     const float *kpts0, *sigma0, *fpfh0, *kpts1, *sigma1, *fpfh1;
     const float *rec0, *rec1;
     int normalize;
-    const float* w; const BlobLayout* bl;
-    const _Float16* es;
+    Encoder32 enc;
     float* x;
     int B, N, M;
 };
-constexpr size_t MDGAT_ENC_SPLIT_HALVES = 64 * 64 + 128 * 128 + 64 * 96 + 128 * 128 + 128 * 512;
 int launch_encoder(const EncoderLaunch& p, hipStream_t s);
 int launch_split_rows_pad(const float* w, _Float16* out, int rows, int Kin, int Kpad, hipStream_t s);
 
@@ -164,16 +166,17 @@ int launch_attention_qk_probe(int B, int N, int M, int cross, const Qkv16& qkv, 
 int launch_qk_phase_probe(int B, int N, int M, int cross, int nq_sets, const Qkv16& qkv, float* msg, hipStream_t s);
 
 // fused layer tail (layer.hip): [mlp.0 -> mlp.3 -> residual] of one layer + q|k|v projection of the next
+// views (weights.hpp): ...s split row images [rows][hi K | lo K | 8 pad], ...f the same in fragment order (launch_frag_image; layer_split.hip)
+struct Layer32 { const _Float16 *w1s, *w2s, *w1f, *w2f; const float *b1, *b2; };
+struct Proj32 { const _Float16 *w3s, *w3f; const float* b3; int mode3; };   // mode3 1: q|k|v, 2: final_proj
 struct LayerLaunch {
     float* x; const float* msg;
-    const _Float16 *w1s, *w2s, *w3s;   // split weight images [rows][hi K | lo K | 8 pad]
-    const _Float16 *w1f, *w2f, *w3f;   // the same matrices in fragment order (launch_frag_image), read by layer_split.hip
-    const float *b1, *b2, *b3;
-    Qkv16 out;                         // mode3 == 1
-    float* mdesc;                      // mode3 == 2
+    Layer32 mlp;                       // do_mlp
+    Proj32 proj;
+    Qkv16 out;                         // proj.mode3 == 1
+    float* mdesc;                      // proj.mode3 == 2
     int R, N, M;
     int do_mlp;                        // 0: projection only
-    int mode3;                         // 1: q|k|v, 2: final_proj
     unsigned* guard;                   // optional (host-mapped): set to 1 when an input row holds a value outside the f16
                                        // operand range (|v| >= MDGAT_F16_GUARD) or a non-finite one
 };

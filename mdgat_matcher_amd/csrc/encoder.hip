@@ -253,10 +253,11 @@ int launch_encoder(const EncoderLaunch& p, hipStream_t s) {
     EncArgs a{};
     a.kpts0 = p.kpts0; a.sigma0 = p.sigma0; a.fpfh0 = p.fpfh0; a.kpts1 = p.kpts1; a.sigma1 = p.sigma1; a.fpfh1 = p.fpfh1;
     a.rec0 = p.rec0; a.rec1 = p.rec1; a.normalize = p.normalize;
-    a.w = p.w;
-    a.kenc0_w = p.bl->kenc0_w; a.kenc0_b = p.bl->kenc0_b; a.denc0_b = p.bl->denc0_b; a.kenc1_b = p.bl->kenc1_b;
-    a.kenc2_b = p.bl->kenc2_b; a.denc1_b = p.bl->denc1_b; a.encl_b = p.bl->encl_b;
-    a.k1s = p.es; a.k2s = a.k1s + 64 * 64; a.d0s = a.k2s + 128 * 128; a.d1s = a.d0s + 64 * 96; a.els = a.d1s + 128 * 128;
+    const Encoder32& e = p.enc;
+    a.w = e.w;
+    a.kenc0_w = e.kenc0_w; a.kenc0_b = e.kenc0_b; a.denc0_b = e.denc0_b; a.kenc1_b = e.kenc1_b;
+    a.kenc2_b = e.kenc2_b; a.denc1_b = e.denc1_b; a.encl_b = e.encl_b;
+    a.k1s = e.k1s; a.k2s = e.k2s; a.d0s = e.d0s; a.d1s = e.d1s; a.els = e.els;
     a.x = p.x; a.B = p.B; a.N = p.N; a.M = p.M; a.R = p.B * (p.N + p.M);
     const size_t lds = (size_t)OFF_END * sizeof(_Float16) + 672 * sizeof(float);
     static std::atomic<unsigned long long> optin;

@@ -78,12 +78,7 @@ struct EncoderF64Args {
     unsigned* guard;
 };
 int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s);
-// the encoder matrices in fragment order, behind the layers' (mdgat_load_weights_f64): kenc.0 | denc.0 | kenc.3 | kenc.6 | denc.3 | the
-// last layers summed; each an [n][k] matrix `ofs` doubles into the encoders' part
-struct Frag64 { size_t ofs; int n, k; };
-struct EncoderF64Frags { Frag64 k0, d0, k1, k2, d1, l; size_t total; };
-EncoderF64Frags encoder_f64_frags();
 // W [N][K] row-major -> the fragment order the kernels of layer_f64.hip load ([N / 16][ceil(K / 8)][64 lanes][2], zero beyond K); N % 16 == 0
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s);
-size_t layer_f64_frag_doubles();      // per layer: mlp.0 | mlp.3 | q|k|v
+inline size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }      // ... and its size (where the images are: weights.hpp)
 bool layer_f64_fused();               // mdgat_set_f64_layer_fusion / MDGAT_F64_LAYER_FUSION

@@ -620,19 +620,19 @@ int launch_layer(const LayerLaunch& p, hipStream_t s) {
     if (p.R <= 0) return MDGAT_OK;
     LayerArgs a{};
     a.x = p.x; a.msg = p.msg;
-    a.w1s = p.w1s; a.b1 = p.b1; a.w2s = p.w2s; a.b2 = p.b2; a.w3s = p.w3s; a.b3 = p.b3;
-    a.w1f = p.w1f; a.w2f = p.w2f; a.w3f = p.w3f;
+    a.w1s = p.mlp.w1s; a.b1 = p.mlp.b1; a.w2s = p.mlp.w2s; a.b2 = p.mlp.b2; a.w3s = p.proj.w3s; a.b3 = p.proj.b3;
+    a.w1f = p.mlp.w1f; a.w2f = p.mlp.w2f; a.w3f = p.proj.w3f;
     a.q16 = p.out.q16; a.k16 = p.out.k16; a.vt16 = p.out.vt16; a.mdesc = p.mdesc;
     a.R = p.R; a.N = p.N; a.M = p.M; a.Npad = p.out.Npad; a.PP = p.out.PP; a.guard = p.guard;
     // launches of a few tiles (one pair, small batches): the channel-split kernel of layer_split.hip - 32-keypoint workgroups
     // whose eight waves share the output channels; bit-identical results (mdgat_set_layer_split_tiles: tuning / A-B hook)
-    if ((p.R + 127) / 128 <= g_split_tiles.load(std::memory_order_relaxed)) return launch_layer_split(a, p.do_mlp, p.mode3, s);
+    if ((p.R + 127) / 128 <= g_split_tiles.load(std::memory_order_relaxed)) return launch_layer_split(a, p.do_mlp, p.proj.mode3, s);
     // small launches (fewer 128-keypoint tiles than half the CUs of the part): 64-keypoint workgroups, one wave per SIMD
     if ((p.R + 127) / 128 <= MDGAT_LAYER_TILE64_TILES) {
-        if (p.do_mlp) return p.mode3 != 1 ? launch_layer_t<1, 2, 0, 4>(a, s) : launch_layer_t<1, 1, 0, 4>(a, s);
-        return p.mode3 != 1 ? launch_layer_t<0, 2, 0, 4>(a, s) : launch_layer_t<0, 1, 0, 4>(a, s);
+        if (p.do_mlp) return p.proj.mode3 != 1 ? launch_layer_t<1, 2, 0, 4>(a, s) : launch_layer_t<1, 1, 0, 4>(a, s);
+        return p.proj.mode3 != 1 ? launch_layer_t<0, 2, 0, 4>(a, s) : launch_layer_t<0, 1, 0, 4>(a, s);
     }
-    const bool vw = p.mode3 == 1 && ((p.N | p.M) & 127) == 0;
-    if (p.do_mlp) return p.mode3 != 1 ? launch_layer_t<1, 2, 0, 8>(a, s) : vw ? launch_layer_t<1, 1, 1, 8>(a, s) : launch_layer_t<1, 1, 0, 8>(a, s);
-    return p.mode3 != 1 ? launch_layer_t<0, 2, 0, 8>(a, s) : vw ? launch_layer_t<0, 1, 1, 8>(a, s) : launch_layer_t<0, 1, 0, 8>(a, s);
+    const bool vw = p.proj.mode3 == 1 && ((p.N | p.M) & 127) == 0;
+    if (p.do_mlp) return p.proj.mode3 != 1 ? launch_layer_t<1, 2, 0, 8>(a, s) : vw ? launch_layer_t<1, 1, 1, 8>(a, s) : launch_layer_t<1, 1, 0, 8>(a, s);
+    return p.proj.mode3 != 1 ? launch_layer_t<0, 2, 0, 8>(a, s) : vw ? launch_layer_t<0, 1, 1, 8>(a, s) : launch_layer_t<0, 1, 0, 8>(a, s);
 }

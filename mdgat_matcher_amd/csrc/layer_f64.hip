@@ -539,17 +539,6 @@ __global__ __launch_bounds__(256) void frag64_kernel(const double* W, double* ou
 
 }  // namespace
 
-size_t layer_f64_frag_doubles() { return (size_t)256 * 256 + 128 * 256 + 384 * 128; }
-
-static size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }
-
-EncoderF64Frags encoder_f64_frags() {
-    EncoderF64Frags f{};
-    auto take = [&](Frag64& m, int n, int k) { m = Frag64{f.total, n, k}; f.total += frag64_doubles(n, k); };
-    take(f.k0, 32, 4); take(f.d0, 64, 33); take(f.k1, 64, 32); take(f.k2, 128, 64); take(f.d1, 128, 64); take(f.l, 128, 256);
-    return f;
-}
-
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s) {
     if (N % 16) { mdgat_set_error("launch_frag64: %d output channels are not whole fragments", N); return MDGAT_ERR_BAD_ARG; }
     const size_t total = frag64_doubles(N, K);
