@@ -381,6 +381,29 @@ int mdgat_sinkhorn_backward(int B, int N, int M, const double* scores, double bi
                             double* dbin, void* workspace, size_t workspace_bytes, void* stream);
 size_t mdgat_sinkhorn_backward_workspace_bytes(int B, int N, int M, int iters);
 
+/* The matching head (mdgat.py:397 final_proj = Conv1d(128, 128, 1) with one weight for both frames, 430-431 the score matrix) in
+ * fp64 as a call of its own: desc0 [B][N][128], desc1 [B][M][128] (point-major: the GNN's output descriptors, the reference's
+ * [B][128][N] transposed), W [128 out][128 in], bias [128] -> scores [B][N][M] = (desc0 W^T + b)(desc1 W^T + b)^T / sqrt(128).  The
+ * launches are the exact mode's (mdgat_forward_f64): the fp64 GEMM for final_proj - once per frame, the frames being separate arrays
+ * here - then the batched product with scale 1 / sqrt(128); the values are the exact mode's scores.  N, M <= 2175 (else
+ * MDGAT_ERR_UNSUPPORTED), B >= 0 (0: nothing is done).  workspace: mdgat_match_head_workspace_bytes, 256-byte aligned.  Asynchronous
+ * on `stream`. */
+int mdgat_match_head_f64(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
+                         double* scores, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the matching head in fp64: given the forward's inputs and dscores = dL/dscores [B][N][M] (contiguous), writes ddesc0
+ * [B][N][128], ddesc1 [B][M][128], dW [128][128] and dbias [128] - the sums over every point of every pair and both frames.  Each of
+ * the four may be NULL when the caller does not need it; with all four NULL, or B == 0, nothing is launched and nothing written.
+ * The projections are recomputed (the forward's launches), then dmd = s dscores md on fp64 matrix instructions with dscores read once
+ * per frame, ddesc = dmd W from the tile on chip, per-pair partials of dW / dbias, and their sum in pair order from pair 0's
+ * (csrc/head_grad.hip).  No atomics on values: the result is the same bit for bit from run to run, ddesc of a pair does not depend
+ * on the batch it travels in, and for B = 2 dW equals dW(pair 0 alone) + dW(pair 1 alone) exactly.  N, M <= 2175 (else
+ * MDGAT_ERR_UNSUPPORTED), B >= 0.  workspace: mdgat_match_head_workspace_bytes, 256-byte aligned (about 8 B (256 (N + M) + 16512)
+ * bytes).  Asynchronous on `stream`. */
+int mdgat_match_head_backward(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
+                              const double* dscores, double* ddesc0, double* ddesc1, double* dW, double* dbias,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_match_head_workspace_bytes(int B, int N, int M);      /* both calls; 0 for a shape they refuse */
+
 /* match extraction (mdgat.py:441-483) from Z [B][N+1][M+1]. */
 int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold,
                   int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,

@@ -956,6 +956,46 @@ extern "C" int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda
     return launch_gemm_f64(g, static_cast<hipStream_t>(stream));
 }
 
+// ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----
+constexpr int MATCH_HEAD_NMAX = 2175;             // the Sinkhorn backward's limit (sinkhorn_grad.hip), which the chain composes with
+static int match_head_shape(const char* who, int B, int N, int M) {
+    if (B < 0 || N <= 0 || M <= 0) { mdgat_set_error("%s: bad shape B=%d N=%d M=%d", who, B, N, M); return MDGAT_ERR_BAD_ARG; }
+    if (N > MATCH_HEAD_NMAX || M > MATCH_HEAD_NMAX) { mdgat_set_error("%s: %d x %d keypoints > %d supported", who, N, M, MATCH_HEAD_NMAX); return MDGAT_ERR_UNSUPPORTED; }
+    if ((long long)B * (N > M ? N : M) > (1 << 24)) { mdgat_set_error("%s: %d pairs of %d x %d keypoints: more than 2^24 rows", who, B, N, M); return MDGAT_ERR_UNSUPPORTED; }
+    return MDGAT_OK;
+}
+static int match_head_workspace(const char* who, int B, int N, int M, const void* workspace, size_t workspace_bytes) {
+    if (!workspace || workspace_bytes < match_head_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return MDGAT_OK;
+}
+
+extern "C" size_t mdgat_match_head_workspace_bytes(int B, int N, int M) {
+    if (B <= 0 || match_head_shape("mdgat_match_head_workspace_bytes", B, N, M)) return 0;
+    return match_head_f64_workspace_bytes(B, N, M);
+}
+
+extern "C" int mdgat_match_head_f64(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
+                                    double* scores, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = match_head_shape("mdgat_match_head_f64", B, N, M)) return rc;
+    if (B == 0) return MDGAT_OK;
+    if (!desc0 || !desc1 || !W || !bias || !scores) { mdgat_set_error("mdgat_match_head_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = match_head_workspace("mdgat_match_head_f64", B, N, M, workspace, workspace_bytes)) return rc;
+    return launch_match_head_f64(B, N, M, desc0, desc1, W, bias, scores, workspace, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_match_head_backward(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
+                                         const double* dscores, double* ddesc0, double* ddesc1, double* dW, double* dbias,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = match_head_shape("mdgat_match_head_backward", B, N, M)) return rc;
+    if (B == 0) return MDGAT_OK;
+    if (!desc0 || !desc1 || !W || !bias || !dscores) { mdgat_set_error("mdgat_match_head_backward: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = match_head_workspace("mdgat_match_head_backward", B, N, M, workspace, workspace_bytes)) return rc;
+    return launch_match_head_backward_f64(B, N, M, desc0, desc1, W, bias, dscores, ddesc0, ddesc1, dW, dbias, workspace, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
     if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (topk < 0) { mdgat_set_error("mdgat_attention_f64: topk < 0"); return MDGAT_ERR_BAD_ARG; }

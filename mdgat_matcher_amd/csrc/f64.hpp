@@ -82,3 +82,13 @@ int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s);
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s);
 inline size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }      // ... and its size (where the images are: weights.hpp)
 bool layer_f64_fused();               // mdgat_set_f64_layer_fusion / MDGAT_F64_LAYER_FUSION
+
+// ---- head_grad.hip: the matching head (final_proj and the score matrix, mdgat.py:397, 430-431) as a call of its own, and its backward ----
+// desc0 [B][N][128], desc1 [B][M][128], W [128][128], bias [128] -> scores [B][N][M] by tail64's launches; the arguments are the
+// caller's to check (api.hip); workspace: match_head_f64_workspace_bytes (both calls), 256-byte aligned
+size_t match_head_f64_workspace_bytes(int B, int N, int M);
+int launch_match_head_f64(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias, double* scores,
+                          void* workspace, hipStream_t s);
+// dscores [B][N][M] -> ddesc0, ddesc1, dW [128][128], dbias [128], each optional (nullptr: not wanted)
+int launch_match_head_backward_f64(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
+                                   const double* dscores, double* ddesc0, double* ddesc1, double* dW, double* dbias, void* workspace, hipStream_t s);

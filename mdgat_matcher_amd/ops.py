@@ -486,3 +486,92 @@ def matching_loss(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, method=
     if torch.is_grad_enabled() and isinstance(Z, torch.Tensor) and Z.requires_grad:
         return _MatchingLoss.apply(Z, gt0, gt1, method, float(gamma))
     return _matching_loss_values(Z, gt0, gt1, method, gamma)
+
+
+# ---- the matching head (mdgat.py:397 final_proj, 430-431 the score matrix; csrc/head_grad.hip) ----
+def _head_args(desc0, desc1, weight, bias):
+    """What both directions of the matching head pass to the library: (desc0, desc1, W [128, 128], b as contiguous float64, B, N, M)."""
+    _need_cuda(desc0, desc1, weight, bias)
+    if desc0.dim() != 3 or desc1.dim() != 3 or desc0.shape[2] != 128 or desc1.shape[2] != 128 or desc0.shape[0] != desc1.shape[0]:
+        raise ValueError(f'desc0 / desc1 must be [B, N, 128] / [B, M, 128], got {tuple(desc0.shape)} / {tuple(desc1.shape)}')
+    if tuple(weight.shape) not in ((128, 128), (128, 128, 1)):
+        raise ValueError(f'weight must be [128, 128] or the Conv1d\'s [128, 128, 1], got {tuple(weight.shape)}')
+    if tuple(bias.shape) != (128,):
+        raise ValueError(f'bias must be [128], got {tuple(bias.shape)}')
+    for t in (desc0, desc1, weight, bias):
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f'the matching head takes float32 or float64 tensors, got {t.dtype}')
+        if t.device != desc0.device:
+            raise ValueError(f'the matching head\'s tensors are on {t.device} and {desc0.device}')
+    f = lambda t: t.detach().to(torch.float64).contiguous()       # noqa: E731
+    return f(desc0), f(desc1), f(weight).reshape(128, 128), f(bias), desc0.shape[0], desc0.shape[1], desc1.shape[1]
+
+
+def _head_workspace(lib, B, N, M, device):
+    need = lib.mdgat_match_head_workspace_bytes(B, N, M)
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, need
+
+
+def _match_head_values(desc0, desc1, weight, bias):
+    d0, d1, w, b, B, N, M = _head_args(desc0, desc1, weight, bias)
+    scores = torch.empty((B, N, M), dtype=torch.float64, device=d0.device)
+    lib = _lib.load()
+    with torch.cuda.device(d0.device):
+        ws, base, need = _head_workspace(lib, B, N, M, d0.device)
+        _lib.check(lib.mdgat_match_head_f64(B, N, M, d0.data_ptr(), d1.data_ptr(), w.data_ptr(), b.data_ptr(), scores.data_ptr(), base, need,
+                                            _stream(d0)), 'mdgat_match_head_f64')
+    return scores.to(desc0.dtype)
+
+
+def match_head_backward(desc0: torch.Tensor, desc1: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, dscores: torch.Tensor,
+                        need=(True, True, True, True)):
+    """Gradient of ``match_head`` (csrc/head_grad.hip): the forward's inputs and dscores = dL/dscores [B, N, M] (any dtype and strides)
+    -> (ddesc0 [B, N, 128], ddesc1 [B, M, 128], dweight, dbias), each in the dtype (and, the weight, the shape) of its input, computed
+    in fp64.  dweight / dbias are the sums over every point of every pair and both frames, added in a fixed order: the same bits from
+    run to run, and ddesc of a pair does not depend on its batch.  ``need``: which of the four to compute (None for the others)."""
+    d0, d1, w, b, B, N, M = _head_args(desc0, desc1, weight, bias)
+    if tuple(dscores.shape) != (B, N, M):
+        raise ValueError(f'dscores {tuple(dscores.shape)} does not fit the descriptors: expected [{B}, {N}, {M}]')
+    if dscores.device != d0.device:
+        raise ValueError(f'dscores is on {dscores.device}, the descriptors on {d0.device}')
+    g = dscores.detach().to(torch.float64).contiguous()
+    shapes = ((B, N, 128), (B, M, 128), (128, 128), (128,))
+    # (zeros, not empty: an empty batch launches nothing and its sums are zero)
+    out = [(torch.zeros if B == 0 else torch.empty)(s, dtype=torch.float64, device=d0.device) if n else None for s, n in zip(shapes, need)]
+    ptr = [o.data_ptr() if o is not None else None for o in out]
+    lib = _lib.load()
+    with torch.cuda.device(d0.device):
+        ws, base, nbytes = _head_workspace(lib, B, N, M, d0.device)
+        _lib.check(lib.mdgat_match_head_backward(B, N, M, d0.data_ptr(), d1.data_ptr(), w.data_ptr(), b.data_ptr(), g.data_ptr(), ptr[0], ptr[1],
+                                                 ptr[2], ptr[3], base, nbytes, _stream(d0)), 'mdgat_match_head_backward')
+    like = (desc0, desc1, weight, bias)
+    return tuple(o.to(t.dtype).reshape(t.shape) if o is not None else None for o, t in zip(out, like))
+
+
+class _MatchHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, desc0, desc1, weight, bias):
+        scores = _match_head_values(desc0, desc1, weight, bias)
+        ctx.save_for_backward(desc0, desc1, weight, bias)
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dscores):
+        return match_head_backward(*ctx.saved_tensors, dscores, need=tuple(ctx.needs_input_grad))
+
+
+def match_head(desc0: torch.Tensor, desc1: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """The matching head of MDGAT.forward (mdgat.py:397, 430-431): desc0 [B, N, 128], desc1 [B, M, 128] - the GNN's output descriptors,
+    point-major (the reference's [B, 128, N] transposed) - ``final_proj``'s weight ([128, 128] or the Conv1d's [128, 128, 1]) and bias
+    [128] -> scores [B, N, M] = final_proj(desc0)^T final_proj(desc1) / sqrt(128), in desc0's dtype.  The arithmetic is fp64 for
+    float32 and float64 tensors alike, by the launches of the exact mode's forward.  N, M <= 2175.
+
+    Differentiable with respect to all four (``match_head_backward``; not twice): when one of them requires grad and grad is enabled
+    the result carries a grad_fn, so ``matching_loss(log_optimal_transport(match_head(desc0, desc1, W, b), bin_score, T), gt0, gt1,
+    method).mean().backward()`` fills ``desc0.grad``, ``desc1.grad``, ``W.grad``, ``b.grad`` and ``bin_score.grad``.  The values, and
+    without grad the kernels launched, are the same either way."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (desc0, desc1, weight, bias)):
+        return _MatchHead.apply(desc0, desc1, weight, bias)
+    return _match_head_values(desc0, desc1, weight, bias)
