@@ -459,6 +459,22 @@ int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda, const dou
                         int relu, const double* R, int ldr, double* C, int ldc, void* stream);
 int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream);
 
+/* Backward of mdgat_attention_f64 (csrc/attention_grad.hip): given the forward's qkv [B][N+M][384], its selection words `sel` (the
+ * `sel` output of the forward, layout of mdgat_taps.topk_sel; required when topk > 0, ignored when topk == 0) and dmsg = dL/dmsg
+ * [B][N+M][128] (channel = head * 32 + dim), writes dqkv [B][N+M][384].  The top-k selection is not differentiated and not decided
+ * again: a key the forward did not keep has a probability of exactly 0.0 and sends exactly 0.0 to dk / dv.  `cross` as in the forward:
+ * the queries of frame 0 read the keys and values of frame 1 and vice versa, so the rows of frame 0 receive dq from their own queries
+ * and dk / dv from frame 1's.  Two launches on fp64 matrix instructions: a row pass (per 64 queries: the row's log-sum-exp and
+ * D = sum_j P dP to the workspace, dq) and a column pass (per 64 keys: dk, dv).  No atomics on values: every element of dqkv is
+ * written exactly once and its terms are added in a fixed order, so the result is the same bit for bit from run to run and a pair's
+ * dqkv does not depend on the batch it travels in.  N, M <= 2048 and B (N + M) <= 2^24 rows (else MDGAT_ERR_UNSUPPORTED), 0 <= topk <= min(N, M), B >= 0
+ * (0: nothing is launched, nothing written).  topk > 0 with sel == NULL, or a workspace smaller than
+ * mdgat_attention_backward_workspace_bytes (16 bytes per pair, head and point) or not 256-byte aligned: MDGAT_ERR_BAD_ARG.
+ * Asynchronous on `stream`. */
+int mdgat_attention_backward_f64(int B, int N, int M, int cross, int topk, const double* qkv, const uint32_t* sel, const double* dmsg,
+                                 double* dqkv, void* workspace, size_t workspace_bytes, void* stream);
+size_t mdgat_attention_backward_workspace_bytes(int B, int N, int M);      /* 0 for a shape the call refuses */
+
 /* Conv1d(k=1)(+folded BN)(+ReLU) over points: C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (+R).
  * (MLP of mdgat.py:34-46 after folding.)  K must be a multiple of 32; lda/ldw/ldc multiples of 4. */
 int mdgat_pointwise(int M, int N, int K, const float* A, int lda, const float* W, int ldw,

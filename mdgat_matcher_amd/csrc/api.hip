@@ -1001,3 +1001,32 @@ extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, con
     if (topk < 0) { mdgat_set_error("mdgat_attention_f64: topk < 0"); return MDGAT_ERR_BAD_ARG; }
     return launch_attention_f64(B, N, M, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream));
 }
+
+// ---- the backward of mdgat_attention_f64: csrc/attention_grad.hip ----
+constexpr int ATTENTION_GRAD_NMAX = 2048;         // the forward's limit for dynamic layers
+static int attention_grad_shape(const char* who, int B, int N, int M) {
+    if (B < 0 || N <= 0 || M <= 0) { mdgat_set_error("%s: bad shape B=%d N=%d M=%d", who, B, N, M); return MDGAT_ERR_BAD_ARG; }
+    if (N > ATTENTION_GRAD_NMAX || M > ATTENTION_GRAD_NMAX) { mdgat_set_error("%s: %d x %d keypoints > %d supported", who, N, M, ATTENTION_GRAD_NMAX); return MDGAT_ERR_UNSUPPORTED; }
+    if ((long long)B * (N + M) > (1 << 24)) { mdgat_set_error("%s: %d pairs of %d + %d keypoints: more than 2^24 rows", who, B, N, M); return MDGAT_ERR_UNSUPPORTED; }
+    return MDGAT_OK;
+}
+
+extern "C" size_t mdgat_attention_backward_workspace_bytes(int B, int N, int M) {
+    if (B <= 0 || attention_grad_shape("mdgat_attention_backward_workspace_bytes", B, N, M)) return 0;
+    return attention_backward_f64_workspace_bytes(B, N, M);
+}
+
+extern "C" int mdgat_attention_backward_f64(int B, int N, int M, int cross, int topk, const double* qkv, const uint32_t* sel, const double* dmsg,
+                                            double* dqkv, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_attention_backward_f64";
+    if (int rc = attention_grad_shape(who, B, N, M)) return rc;
+    if (topk < 0 || topk > (N < M ? N : M)) { mdgat_set_error("%s: k=%d outside [0, %d], the number of keys", who, topk, N < M ? N : M); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (!qkv || !dmsg || !dqkv) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (topk > 0 && !sel) { mdgat_set_error("%s: topk=%d needs the forward's selection words (sel)", who, topk); return MDGAT_ERR_BAD_ARG; }
+    if (!workspace || workspace_bytes < attention_backward_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return launch_attention_backward_f64(B, N, M, cross, topk, qkv, sel, dmsg, dqkv, workspace, static_cast<hipStream_t>(stream));
+}

@@ -167,48 +167,7 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmF64Args a) {
 }
 
 // ================================================================================================ attention
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)u, m, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), m, 64);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// a value of the four lanes (q, q + 16, q + 32, q + 48) of a row combined
-__device__ __forceinline__ double quad_max(double v) { v = fmax(v, shfl_xor_f64(v, 16)); return fmax(v, shfl_xor_f64(v, 32)); }
-__device__ __forceinline__ double quad_sum(double v) { v += shfl_xor_f64(v, 16); return v + shfl_xor_f64(v, 32); }
-
-// exp(x) for the softmax numerators: x <= TAU_LAZY (x <= 0 except under the lazy reference of the full-attention loop), -inf for
-// masked keys.  Table-driven: x = (256 q + j) ln2 / 256 + r, |r| <= ln2 / 512 = 1.35e-3,
-//     exp(x) = 2^q T[j] (1 + r + r^2 / 2 + r^3 / 6 + r^4 / 24),      T[j] = 2^(j / 256) correctly rounded, 2 KB of LDS (exp2_tab256.hpp)
-// (truncation r^5 / 120 = 3.8e-17).  n = 256 q + j falls out of the low word of x (256 / ln 2) + 1.5 2^52, the reduction is ONE fma
-// against the correctly rounded ln2 / 256 (its rounding error acts like a relative perturbation of x by 2^-53: an ulp of the logit
-// itself), the polynomial is a product and three fmas with at most one scalar operand each, one fma scales the table entry and
-// v_ldexp_f64 applies 2^q.  Ten fp64 and three integer instructions and a ds_read_b64; the degree-12 polynomial this replaces ran 19 (+ a v_mov_b64 the compiler
-// rematerialised for the leading coefficient) - on this part an fp64 vector instruction issues in the slot of a sixteenth of a
-// v_mfma_f64_16x16x4 and the two share the pipe (profiles/NOTES_r5.md section 1), so the attention loops are their vector
-// instruction count.  Keys masked with -inf get exp(-700) = 1e-304 instead of 0: nothing against a row's largest term, which is 1.
-typedef __attribute__((address_space(3))) const double lds_cdouble;
-struct ExpConst { double magic; };        // 1.5 2^52 held in a vector register pair for the whole kernel (the fma that uses it has its one
-                                          // scalar slot taken by 256 / ln 2; left to the compiler the constant is rematerialised per call)
-__device__ __forceinline__ ExpConst exp_const() {
-    double m = 0x1.8p+52;
-    asm volatile("" : "+v"(m));
-    return ExpConst{m};
-}
-__device__ __forceinline__ double exp_fast(double x, const double* tab_, const ExpConst& ec) {
-    lds_cdouble* tab = (lds_cdouble*)tab_;
-    x = fmax(x, -700.0);
-    double tm, r, a, b, s;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(tm) : "v"(x), "s"(0x1.71547652b82fep+8), "v"(ec.magic));       // x 256 / ln 2 + 1.5 2^52
-    const int n = (int)(unsigned)__builtin_bit_cast(unsigned long long, tm);
-    const double nd = tm - ec.magic;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(nd), "s"(-0x1.62e42fefa39efp-9), "v"(x));              // x - n ln2 / 256
-    const double r2 = r * r;
-    asm("v_fma_f64 %0, %1, %2, 0.5" : "=v"(a) : "v"(r), "s"(0x1.5555555555555p-3));                        // 1/2 + r / 6
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(b) : "v"(r2), "s"(0x1.5555555555555p-5), "v"(a));               // ... + r^2 / 24
-    s = __builtin_fma(r2, b, r);                                                                          // exp(r) - 1
-    const double T = tab[n & 255];
-    return ldexp(__builtin_fma(T, s, T), n >> 8);       // (v_ashrrev + v_ldexp_f64; shift, mask and a 64-bit add into T's exponent field: one more, same time)
-}
+// (shfl_xor_f64, quad_max, quad_sum and the table-driven exp_fast: f64_dev.hpp, shared with attention_grad.hip)
 constexpr double TAU_LAZY = 8.0;          // full attention: the running reference of a row moves only when a logit exceeds it by this much
 
 constexpr int A_LIST = 32;        // logits tied (as fp32 roundings) at the k-th place that are ranked by their fp64 values; more: key order

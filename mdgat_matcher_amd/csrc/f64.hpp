@@ -92,3 +92,9 @@ int launch_match_head_f64(int B, int N, int M, const double* desc0, const double
 // dscores [B][N][M] -> ddesc0, ddesc1, dW [128][128], dbias [128], each optional (nullptr: not wanted)
 int launch_match_head_backward_f64(int B, int N, int M, const double* desc0, const double* desc1, const double* W, const double* bias,
                                    const double* dscores, double* ddesc0, double* ddesc1, double* dW, double* dbias, void* workspace, hipStream_t s);
+
+// ---- attention_grad.hip: the backward of launch_attention_f64 (sel: the forward's selection words, read when topk > 0) ----
+// the arguments are the caller's to check (api.hip); workspace: attention_backward_f64_workspace_bytes, 256-byte aligned
+size_t attention_backward_f64_workspace_bytes(int B, int N, int M);
+int launch_attention_backward_f64(int B, int N, int M, int cross, int topk, const double* qkv, const uint32_t* sel, const double* dmsg, double* dqkv,
+                                  void* workspace, hipStream_t s);

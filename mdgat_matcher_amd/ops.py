@@ -202,7 +202,8 @@ def topk_sel_to_masks(sel: torch.Tensor, B: int, N: int, M: int, cross: bool):
 
 def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False):
     """attention / dynamic_attention (mdgat.py:190-210).  qkv [B, N+M, 3, 4, 32] -> message [B, N+M, 128]
-    (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks)."""
+    (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks).
+    The fp32-class kernels have no backward: the result never carries a grad_fn (``attention_f64`` is the differentiable one)."""
     _need_cuda(qkv)
     x = qkv.to(torch.float32).contiguous()
     B, P = x.shape[0], x.shape[1]
@@ -367,18 +368,93 @@ def pointwise_f64(a: torch.Tensor, w: torch.Tensor, bias=None, relu: bool = Fals
     return out
 
 
-def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False):
-    """attention / dynamic_attention (mdgat.py:190-210) in fp64.  qkv [B, N+M, 3, 4, 32] float64 -> message [B, N+M, 128] float64
-    (with ``return_selection``: also the masks of the keys a dynamic layer kept, see topk_sel_to_masks)."""
+def _attention_f64_values(qkv, N, M, cross, topk, want_sel):
+    """The forward launch of ``attention_f64``: (message, the raw selection words or None)."""
     _need_cuda(qkv)
-    x = qkv.to(torch.float64).contiguous()
+    x = qkv.detach().to(torch.float64).contiguous()
     B, P = x.shape[0], x.shape[1]
     assert P == N + M and tuple(x.shape[2:]) == (3, 4, 32)
     msg = torch.empty((B, P, 128), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
-        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if return_selection else None
+        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if want_sel else None
         _lib.check(_lib.load().mdgat_attention_f64(B, N, M, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
                                                    sel.data_ptr() if sel is not None else None, _stream(x)), 'mdgat_attention_f64')
+    return msg, sel
+
+
+def attention_f64_backward(qkv: torch.Tensor, N: int, M: int, cross: bool, dmsg: torch.Tensor, topk: int = 0, selection=None) -> torch.Tensor:
+    """Gradient of ``attention_f64`` (csrc/attention_grad.hip): the forward's qkv [B, N+M, 3, 4, 32], dmsg = dL/dmessage [B, N+M, 128]
+    (any dtype and strides) and, for a dynamic layer (``topk`` > 0), ``selection`` - the forward's raw int32 selection words
+    (``mdgat_taps.topk_sel`` layout, what ``topk_sel_to_masks`` decodes) -> dqkv [B, N+M, 3, 4, 32] float64.  The top-k selection is not
+    differentiated and not decided again: keys the forward did not keep get exactly 0.0 in dk / dv.  No value atomics: the same bits
+    from run to run, and a pair's dqkv does not depend on its batch.  N, M <= 2048."""
+    _need_cuda(qkv, dmsg)
+    x = qkv.detach().to(torch.float64).contiguous()
+    B, P = x.shape[0], x.shape[1]
+    if P != N + M or tuple(x.shape[2:]) != (3, 4, 32):
+        raise ValueError(f'qkv must be [B, {N + M}, 3, 4, 32], got {tuple(qkv.shape)}')
+    if tuple(dmsg.shape) != (B, P, 128):
+        raise ValueError(f'dmsg {tuple(dmsg.shape)} does not fit qkv: expected [{B}, {P}, 128]')
+    if dmsg.device != x.device:
+        raise ValueError(f'dmsg is on {dmsg.device}, qkv on {x.device}')
+    topk = int(topk)
+    sel = None
+    if topk > 0:
+        if selection is None:
+            raise ValueError(f'topk={topk}: the backward of a dynamic layer needs the forward\'s selection words (selection=)')
+        _need_cuda(selection)
+        sel = selection.to(device=x.device, dtype=torch.int32).contiguous()
+        if sel.numel() != topk_sel_words(B, N, M):
+            raise ValueError(f'selection holds {sel.numel()} words, the forward writes {topk_sel_words(B, N, M)}')
+    g = dmsg.detach().to(torch.float64).contiguous()
+    dqkv = torch.empty_like(x)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        need = lib.mdgat_attention_backward_workspace_bytes(B, N, M)
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=x.device)
+        off = (-ws.data_ptr()) % 256
+        _lib.check(lib.mdgat_attention_backward_f64(B, N, M, int(bool(cross)), topk, x.data_ptr(), sel.data_ptr() if sel is not None else None,
+                                                    g.data_ptr(), dqkv.data_ptr(), ws.data_ptr() + off, need, _stream(x)),
+                   'mdgat_attention_backward_f64')
+    return dqkv
+
+
+class _AttentionF64(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, N, M, cross, topk, want_sel):
+        msg, sel = _attention_f64_values(qkv, N, M, cross, topk, want_sel)
+        ctx.save_for_backward(qkv, *((sel,) if topk > 0 else ()))
+        ctx.shape = (N, M, cross, topk)
+        if sel is None:
+            return msg
+        ctx.mark_non_differentiable(sel)
+        return msg, sel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmsg, *_):
+        qkv, *sel = ctx.saved_tensors
+        N, M, cross, topk = ctx.shape
+        dqkv = attention_f64_backward(qkv, N, M, cross, dmsg, topk, sel[0] if sel else None)
+        return dqkv.to(qkv.dtype), None, None, None, None, None
+
+
+def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False):
+    """attention / dynamic_attention (mdgat.py:190-210) in fp64.  qkv [B, N+M, 3, 4, 32] float64 -> message [B, N+M, 128] float64
+    (with ``return_selection``: also the masks of the keys a dynamic layer kept, see topk_sel_to_masks).
+
+    Differentiable with respect to qkv (``attention_f64_backward``; not twice): when qkv requires grad and grad is enabled the message
+    carries a grad_fn.  The launch and the values are the same either way; a dynamic layer then always asks for the selection words
+    and saves them for the backward (16 MB at 64 pairs of 512), which reads them instead of selecting again.  The masks are not
+    differentiable."""
+    B = qkv.shape[0]
+    topk = int(topk)
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        want_sel = topk > 0 or return_selection       # a dynamic layer always keeps its selection words
+        out = _AttentionF64.apply(qkv, N, M, bool(cross), topk, want_sel)
+        msg, sel = out if want_sel else (out, None)
+    else:
+        msg, sel = _attention_f64_values(qkv, N, M, cross, topk, return_selection)
     if return_selection:
         return msg, topk_sel_to_masks(sel, B, N, M, cross)
     return msg
