@@ -508,6 +508,63 @@ int mdgat_pose(int B, int N, int M, const float* kpts0, const float* kpts1, cons
 int mdgat_gt_matches(int B, int N, int M, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
                      double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream);
 
+/* ---- the evaluation scripts' per-pair record ------------------------------------------------------------------------------
+ * What test.py:212-296 and test_registration_metric.py:213-264 derive for one pair from the matcher's output, the ground-truth
+ * matches, the keypoints and T_gt.  In both scripts valid = matches0 > -1 (test.py:215) and, after the dustbin value M of gt0 has
+ * been rewritten to -1 (test.py:237-238), valid_gt = gt0 > -1 (:239); the sums run over the N frame-0 keypoints.  Counts are
+ * stored exactly; every ratio is one fp64 division of two exact integers, the value numpy's int64 / int64 gives, bit for bit. */
+typedef enum {
+    MDGAT_EVAL_N_VALID = 0,                 /* np.sum(valid): predicted matches = len(mkpts0) (test.py:215-216, 282) */
+    MDGAT_EVAL_N_VALID_GT,                  /* valid_num = np.sum(valid_gt) (test.py:241) */
+    MDGAT_EVAL_N_GT_NEGATIVE,               /* np.sum(matches_gt == -1) (test.py:288) */
+    MDGAT_EVAL_TRUE_POSITIVE,               /* tm: matches == matches_gt and valid (test.py:277, 284); `inlier` of
+                                               test_registration_metric.py:238, 251 */
+    MDGAT_EVAL_TRUE_NEGATIVE,               /* matches == matches_gt and not valid (test.py:278; test_registration_metric.py:240) */
+    MDGAT_EVAL_FALSE_POSITIVE,              /* fm: valid and matches_gt == -1 (test.py:279, 285) */
+    MDGAT_EVAL_N_VALID_AND_GT_POSITIVE,     /* valid and matches_gt > -1 (test.py:289) */
+    MDGAT_EVAL_FALSE_POSITIVE_REG,          /* valid and matches != matches_gt (test_registration_metric.py:239) */
+    MDGAT_EVAL_FALSE_NEGATIVE,              /* matches == -1 and matches_gt > -1 (test_registration_metric.py:241) */
+    MDGAT_EVAL_REPEATABILITY,               /* valid_num / all_num (test.py:241-244; test_registration_metric.py:235) */
+    MDGAT_EVAL_PRECISION,                   /* tp / n_valid if n_valid > 0 else 0 (test.py:282; test_registration_metric.py:243) */
+    MDGAT_EVAL_RECALL,                      /* tp / n_valid_gt if n_VALID > 0 else 0 (test.py:283; test_registration_metric.py:244) */
+    MDGAT_EVAL_MATCHING_SCORE,              /* tp / N (test.py:286) */
+    MDGAT_EVAL_ACCURACY,                    /* (tp + tn) / N (test.py:287) */
+    MDGAT_EVAL_FP_RATE,                     /* fp / n_gt_negative, unguarded (test.py:288) */
+    MDGAT_EVAL_TP_RATE,                     /* n_valid_and_gt_positive / n_valid_gt, unguarded (test.py:289) */
+    MDGAT_EVAL_TP_RATE2,                    /* tp / n_valid_gt, unguarded (test.py:290) */
+    MDGAT_EVAL_FP_RATE_REG,                 /* fp_reg / (fp_reg + tn), unguarded (test_registration_metric.py:247) */
+    MDGAT_EVAL_TP_RATE_REG,                 /* tp / (tp + fn), unguarded (test_registration_metric.py:248) */
+    MDGAT_EVAL_INLIERS,                     /* inlier (utils_test.py:61-62, via test.py:294) */
+    MDGAT_EVAL_INLIER_RATIO,                /* inlier / len(mkpts0) (utils_test.py:63) */
+    MDGAT_EVAL_TRANS_ERROR,                 /* trans_error (utils_test.py:66-67); rte of calculate_error2 (utils_test.py:34-35, via
+                                               test_registration_metric.py:256), the same number */
+    MDGAT_EVAL_ROT_ERROR,                   /* rot_error, radians, arccos unclamped (utils_test.py:68-70); rre (utils_test.py:36-38) */
+    MDGAT_EVAL_STATUS,                      /* mdgat_eval_status bits, as a number */
+    MDGAT_EVAL_COLS
+} mdgat_eval_column;
+
+/* The scripts `continue` (or skip an append) in these cases; the row is filled all the same and the caller decides. */
+typedef enum {
+    MDGAT_EVAL_BANNED = 1,                  /* valid_gt.sum() < len(matches_gt) * 0.1 (test.py:247; test_registration_metric.py:230) */
+    MDGAT_EVAL_TOO_FEW_MATCHES = 2,         /* len(mkpts0) < 4 (test.py:272) */
+    MDGAT_EVAL_REGISTRATION_FAIL = 4,       /* trans_error > 2 or rot_error > 5 or either is NaN (test.py:296) */
+    MDGAT_EVAL_RTE_OK = 8,                  /* rte < 2 (test_registration_metric.py:258) */
+    MDGAT_EVAL_RRE_OK = 16                  /* not isnan(rre) and rre < pi / 180 * 5 (test_registration_metric.py:261); RR counts
+                                               the pairs with both bits (:264) */
+} mdgat_eval_status;
+
+/* matches0 / gt0 [B][N], matches1 / gt1 [B][M] int64; kpts0 [B][N][3] / kpts1 [B][M][3] fp32 and T_gt [B][4][4] fp64 (optional:
+ * without it the errors are NaN and MDGAT_EVAL_REGISTRATION_FAIL is set) as mdgat_pose takes them, and the pose columns are
+ * mdgat_pose's arithmetic on matches0; T [B][4][4] receives the pose.  A pair without any match has no pose in the reference (the
+ * mean of an empty set): its T, inlier ratio and errors are NaN.  metrics [B][MDGAT_EVAL_COLS] fp64.  A gt0 value of -1 or M, a gt1
+ * value of -1 or N is "unmatched"; a gt0 value outside [-1, M], a gt1 value outside [-1, N], a matches0 value outside [-1, M) or a
+ * matches1 value outside [-1, N) is never used to index: that pair's row and T are NaN and bit 0 of *bad_index (device memory,
+ * optional; the caller clears it) is set.  matches1 and gt1 enter no column.  1 <= N, M <= 2175; B == 0 launches nothing.  One launch
+ * on `stream`; reads the matches once; no allocation, no synchronisation, no atomics on values. */
+int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
+                       const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
+                       unsigned* bad_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

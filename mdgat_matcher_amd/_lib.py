@@ -29,6 +29,16 @@ ARITH_FP32 = 0
 ARITH_FP64 = 1
 F64_ENCODERS_ONLY = -1
 
+# mdgat_eval_column (include/mdgat_hip.h), in order, and the mdgat_eval_status bits
+EVAL_COLUMNS = ('n_valid', 'n_valid_gt', 'n_gt_negative', 'true_positive', 'true_negative', 'false_positive', 'n_valid_and_gt_positive',
+                'false_positive_reg', 'false_negative', 'repeatability', 'precision', 'recall', 'matching_score', 'accuracy', 'fp_rate',
+                'tp_rate', 'tp_rate2', 'fp_rate_reg', 'tp_rate_reg', 'inliers', 'inlier_ratio', 'trans_error', 'rot_error', 'status')
+EVAL_BANNED = 1
+EVAL_TOO_FEW_MATCHES = 2
+EVAL_REGISTRATION_FAIL = 4
+EVAL_RTE_OK = 8
+EVAL_RRE_OK = 16
+
 OK = 0
 ERR_BAD_ARG = -1
 ERR_HIP = -2
@@ -141,6 +151,7 @@ SIGNATURES = {
                              C.c_void_p, C.c_void_p]),
     'mdgat_gt_matches': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mdgat_eval_metrics': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_double] + [C.c_void_p] * 4),
     'mdgat_knn': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_knn_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

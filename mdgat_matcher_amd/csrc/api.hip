@@ -949,6 +949,19 @@ extern "C" int mdgat_gt_matches(int B, int N, int M, const float* kpts0, const f
     return launch_gt_match(B, N, M, kpts0, kpts1, T0, T1, threshold, mutual, gt0, gt1, rep, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
+                                  const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
+                                  unsigned* bad_index, void* stream) {
+    if (B < 0) { mdgat_set_error("mdgat_eval_metrics: negative batch"); return MDGAT_ERR_BAD_ARG; }
+    if (N <= 0 || M <= 0) { mdgat_set_error("mdgat_eval_metrics: empty frame"); return MDGAT_ERR_BAD_ARG; }
+    if (B > 0 && (!matches0 || !matches1 || !gt0 || !gt1 || !kpts0 || !kpts1 || !metrics || !T)) {
+        mdgat_set_error("mdgat_eval_metrics: null pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return launch_eval_metrics(B, N, M, matches0, matches1, gt0, gt1, kpts0, kpts1, T_gt, inlier_dist, metrics, T, bad_index,
+                               static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda, const double* W, int ldw, const double* bias,
                                    int relu, const double* R, int ldr, double* C, int ldc, void* stream) {
     if (!A || !W || !C) { mdgat_set_error("mdgat_pointwise_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }

@@ -223,6 +223,10 @@ int launch_pose(int B, int N, int M, const float* kpts0, const float* kpts1, con
                 double inlier_dist, double* T, double* stats, hipStream_t s);
 int launch_gt_match(int B, int N, int M, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
                     double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, hipStream_t s);
+// the evaluation scripts' per-pair record (eval_metrics.hip)
+int launch_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
+                        const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
+                        unsigned* bad_index, hipStream_t s);
 
 // out[b][i][j] = scale <A[b][i], Bm[b][j]> - col_bias[b][j] over 128 channels, split-f16 products (scores.hip)
 int launch_dots(int B, int N, int M, const float* A, size_t strideA, const float* Bm, size_t strideB, float* out, float scale,

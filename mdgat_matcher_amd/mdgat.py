@@ -456,6 +456,20 @@ class MDGAT(nn.Module):
             'loss': loss,
         }
 
+    def evaluate(self, data):
+        """``forward(data)`` and then the evaluation scripts' per-pair record (test.py:212-296, test_registration_metric.py:213-264) of
+        the forward's own device outputs against ``data['gt_matches0/1']`` and ``data['T_gt']`` (optional): the forward's dict plus
+        ``'metrics'`` [B, len(ops.EvalColumns)] float64 and ``'T'`` [B, 4, 4], the pose from the matches.  The scripts' loop body
+        becomes ``meter.update(net.evaluate(pred))`` with an ``ops.EvalMeter``.  ``forward`` itself is unchanged."""
+        from . import ops
+        out = self.forward(data)
+        if out.get('skip_train'):                 # an empty frame: nothing to evaluate (mdgat.py:374-382)
+            return {**out, 'metrics': None, 'T': None}
+        dev = out['matches0'].device
+        metrics, T, _ = ops.evaluate_matches(out['matches0'], out['matches1'], data['gt_matches0'], data['gt_matches1'],
+                                             data['keypoints0'].to(dev), data['keypoints1'].to(dev), T_gt=data.get('T_gt'))
+        return {**out, 'metrics': metrics, 'T': T}
+
     def _loss_request(self, data, kpts0, kpts1):
         """The loss inputs of mdgat.py:486-594, checked before anything is launched."""
         gt0, gt1 = data['gt_matches0'], data['gt_matches1']            # KeyError when absent, as in the reference (mdgat.py:438-439)

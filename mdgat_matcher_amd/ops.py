@@ -349,6 +349,163 @@ def gt_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, T0=None, T1=None, thres
     return g0, g1, rep
 
 
+# ---- the evaluation scripts' per-pair record (csrc/eval_metrics.hip) ----
+class _EvalColumns(dict):
+    """Column name -> index of the table ``evaluate_matches`` returns (``mdgat_eval_column`` of include/mdgat_hip.h), also as
+    attributes (``EvalColumns.precision``), and the status bits (``mdgat_eval_status``)."""
+    BANNED = _lib.EVAL_BANNED
+    TOO_FEW_MATCHES = _lib.EVAL_TOO_FEW_MATCHES
+    REGISTRATION_FAIL = _lib.EVAL_REGISTRATION_FAIL
+    RTE_OK = _lib.EVAL_RTE_OK
+    RRE_OK = _lib.EVAL_RRE_OK
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+EvalColumns = _EvalColumns((name, i) for i, name in enumerate(_lib.EVAL_COLUMNS))
+
+
+def evaluate_matches(matches0: torch.Tensor, matches1: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, kpts0: torch.Tensor,
+                     kpts1: torch.Tensor, T_gt=None, inlier_dist: float = 1.0):
+    """What test.py:212-296 and test_registration_metric.py:213-264 derive per pair from the matcher's output, on the device:
+    matches0 / gt0 [B, N], matches1 / gt1 [B, M] (-1, or the dustbin value M / N in the gts, = unmatched), kpts [B, N, 3] / [B, M, 3]
+    and T_gt [B, 4, 4] as ``pose_from_matches`` takes them.  Returns (metrics [B, len(EvalColumns)] float64, T [B, 4, 4] float64,
+    EvalColumns): counts exact, every ratio bit for bit numpy's value (0/0 = NaN and x/0 = inf where the script does not guard), the
+    pose columns ``pose_from_matches``' arithmetic, and a status column with the scripts' skip rules as bits - the row is filled either
+    way (``EvalMeter`` applies the rules).  A gt outside [-1, M] / [-1, N] raises ``IndexError`` like the loss; the tensors are not
+    rewritten.  Reading the bad-index word synchronises, as in ``matching_loss``."""
+    _need_cuda(matches0, kpts0, kpts1)
+    dev = kpts0.device
+    k0 = kpts0.to(torch.float32).contiguous()
+    k1 = kpts1.to(device=dev, dtype=torch.float32).contiguous()
+    B, N, M = k0.shape[0], k0.shape[1], k1.shape[1]
+    m0, m1, g0, g1 = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (matches0, matches1, gt0, gt1))
+    for name, t, n in (('matches0', m0, N), ('gt0', g0, N), ('matches1', m1, M), ('gt1', g1, M)):
+        if tuple(t.shape) != (B, n):
+            raise ValueError(f'{name} {tuple(t.shape)}: expected [{B}, {n}]')
+    g = T_gt.to(device=dev, dtype=torch.float64).contiguous() if T_gt is not None else None
+    if g is not None and tuple(g.shape) != (B, 4, 4):
+        raise ValueError(f'T_gt {tuple(g.shape)}: expected [{B}, 4, 4]')
+    metrics = torch.empty((B, len(EvalColumns)), dtype=torch.float64, device=dev)
+    T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mdgat_eval_metrics(B, N, M, m0.data_ptr(), m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(),
+                                                  k1.data_ptr(), g.data_ptr() if g is not None else None, float(inlier_dist),
+                                                  metrics.data_ptr(), T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics')
+    if int(bad.item()):
+        raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1), or the matches one outside '
+                         f'[-1, {M}) / [-1, {N})')
+    return metrics, T, EvalColumns
+
+
+class _Average:
+    """utils/utils_test.py:6-25 as far as the scripts read it: a running sum in arrival order and its quotient by the count."""
+
+    def __init__(self):
+        self.sum, self.count, self.avg = 0.0, 0, 0
+
+    def update(self, val, n=1):
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+class EvalMeter:
+    """Host-side accumulator over the rows of ``evaluate_matches`` (one device-to-host copy of the table per batch), under the two
+    scripts' own rules, so that the aggregates equal theirs bit for bit when the rows do:
+
+    test.py:241-311 - repeatability is appended for every pair; a banned pair counts as banned and failed and is skipped; a pair with
+    fewer than 4 matches fails; so does one whose pose is off (trans_error > 2, rot_error > 5 or NaN); the others append to every list.
+    ``test_py()`` takes ``np.mean`` over those lists (:326-338) and reports ``fail`` and ``baned_data`` both as counts and divided by the
+    index of the last batch, which is what :340-342 print (``fail / i``: one less than the number of ``update`` calls).
+
+    test_registration_metric.py:230-269 - a banned pair is skipped; the others feed the running averages (the script's AverageMeter:
+    sums in arrival order), RTE / RRE only where they pass, RR with 1 or 0.  ``registration()`` reports what :282-286 print."""
+
+    _TEST_LISTS = ('precision', 'accuracy', 'recall', 'trans_error', 'rot_error', 'inliers', 'inlier_ratio', 'fp_rate', 'tp_rate',
+                   'tp_rate2', 'true_positive', 'false_positive')
+    _REG_NAMES = ('rep', 'rre', 'rte', 'inlier', 'inlier_ratio', 'recall', 'tp_rate', 'fp_rate', 'RR')
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.batches = 0
+        self.fail = 0
+        self.baned_data = 0
+        self.reg_baned_data = 0
+        self.lists = {name: [] for name in ('repeatability',) + self._TEST_LISTS}
+        self.reg = {name: _Average() for name in self._REG_NAMES}
+
+    def update(self, rows):
+        """``rows``: the metrics table ([B, COLS], a tensor on any device or an array), or the dict ``MDGAT.evaluate`` returns."""
+        if isinstance(rows, dict):
+            rows = rows['metrics']
+        if isinstance(rows, torch.Tensor):
+            rows = rows.detach().cpu().numpy()
+        c = EvalColumns
+        self.batches += 1
+        for r in rows:
+            status = int(r[c.status])
+            self._update_test_py(r, status)
+            self._update_registration(r, status)
+        return self
+
+    def _update_test_py(self, r, status):
+        c = EvalColumns
+        self.lists['repeatability'].append(r[c.repeatability])
+        if status & c.BANNED:
+            self.baned_data += 1
+            self.fail += 1
+            return
+        if status & (c.TOO_FEW_MATCHES | c.REGISTRATION_FAIL):
+            self.fail += 1
+            return
+        for name in self._TEST_LISTS:
+            self.lists[name].append(r[c[name]])
+
+    def _update_registration(self, r, status):
+        c, a = EvalColumns, self.reg
+        if status & c.BANNED:
+            self.reg_baned_data += 1
+            return
+        a['rep'].update(r[c.repeatability]), a['fp_rate'].update(r[c.fp_rate_reg]), a['tp_rate'].update(r[c.tp_rate_reg])
+        a['recall'].update(r[c.recall]), a['inlier_ratio'].update(r[c.precision]), a['inlier'].update(r[c.true_positive])
+        if status & c.RTE_OK:
+            a['rte'].update(r[c.trans_error])
+        if status & c.RRE_OK:
+            a['rre'].update(r[c.rot_error])
+        a['RR'].update(1 if (status & c.RTE_OK) and (status & c.RRE_OK) else 0)
+
+    def test_py(self):
+        """The aggregates test.py:326-342 prints.  An empty list averages to NaN there as well (numpy warns; silenced here)."""
+        import numpy as np
+        with np.errstate(invalid='ignore', divide='ignore'):
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)
+                out = {name + '_mean': np.mean(v) for name, v in self.lists.items()}
+            i = np.float64(self.batches - 1)
+            out.update(fail=self.fail, baned_data=self.baned_data, fail_rate=np.float64(self.fail) / i,
+                       baned_data_rate=np.float64(self.baned_data) / i)
+        return out
+
+    def registration(self):
+        """The aggregates test_registration_metric.py:282-286 prints."""
+        import numpy as np
+        out = {name: a.avg for name, a in self.reg.items()}
+        p, r = out['inlier_ratio'], out['recall']
+        with np.errstate(invalid='ignore', divide='ignore'):
+            out['F1'] = np.float64(2 * p * r) / np.float64(p + r)
+        out['baned_data'] = self.reg_baned_data
+        return out
+
+
 # ---- fp64 kernels of the reference-exact mode (csrc/f64.hip; MDGAT(arithmetic='fp64') launches the same ones) ----
 def pointwise_f64(a: torch.Tensor, w: torch.Tensor, bias=None, relu: bool = False, residual=None) -> torch.Tensor:
     """Conv1d(k=1) over points in fp64 (mdgat.py:34-46 after BN folding): a [M, K] x w [N, K]^T (+ bias)(ReLU)(+ residual)."""
