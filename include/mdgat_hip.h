@@ -404,6 +404,58 @@ int mdgat_match_head_backward(int B, int N, int M, const double* desc0, const do
                               void* workspace, size_t workspace_bytes, void* stream);
 size_t mdgat_match_head_workspace_bytes(int B, int N, int M);      /* both calls; 0 for a shape they refuse */
 
+/* The reference's MLP(channels) (mdgat.py:34-46) in fp64 with BatchNorm on the batch's own statistics, and its backward
+ * (csrc/mlp_grad.hip): n_conv Conv1d(k=1), each but the last followed by BatchNorm1d and ReLU.  Rows are points: x0 [R][K0] and the
+ * optional second source x1 [R][K1] are read side by side (the layer's cat([x, message]) is never materialised), the output is
+ * [R][C[n_conv - 1]].  W[l] is [C[l]][C_in] row-major as in the state_dict (C_in = K0 + K1 for l = 0, else C[l - 1]), bias[l] [C[l]];
+ * gamma / beta / running_mean / running_var [l] are [C[l]] and num_batches_tracked[l] one int64, all on the device, for
+ * l < n_conv - 1.  No alignment beyond 8 bytes is assumed of any of them.  Supported (else MDGAT_ERR_UNSUPPORTED): 1 to 4
+ * convolutions, every C[l] a multiple of 16 and at most 512, 1 <= K0 + K1 <= 512.  R >= 0 (0: nothing is launched); R == 1 with
+ * training != 0 and a BatchNorm in the stack is MDGAT_ERR_BAD_ARG, as in torch. */
+#define MDGAT_MLP_MAX_CONVS 4
+typedef struct {
+    int32_t n_conv;
+    int32_t R, K0, K1;
+    int32_t C[MDGAT_MLP_MAX_CONVS];
+    int32_t training;                                  /* != 0: batch statistics, the running buffers move; 0: the running buffers are read */
+    double eps[MDGAT_MLP_MAX_CONVS - 1], momentum[MDGAT_MLP_MAX_CONVS - 1];
+    const double* W[MDGAT_MLP_MAX_CONVS];
+    const double* bias[MDGAT_MLP_MAX_CONVS];
+    const double* gamma[MDGAT_MLP_MAX_CONVS - 1];
+    const double* beta[MDGAT_MLP_MAX_CONVS - 1];
+    double* running_mean[MDGAT_MLP_MAX_CONVS - 1];
+    double* running_var[MDGAT_MLP_MAX_CONVS - 1];
+    int64_t* num_batches_tracked[MDGAT_MLP_MAX_CONVS - 1];
+} mdgat_mlp_desc;
+/* the gradients the backward writes; NULL: not wanted, and a product only it needs is not formed */
+typedef struct {
+    double *dx0, *dx1;                                 /* [R][K0], [R][K1] */
+    double* dW[MDGAT_MLP_MAX_CONVS];
+    double* dbias[MDGAT_MLP_MAX_CONVS];
+    double* dgamma[MDGAT_MLP_MAX_CONVS - 1];
+    double* dbeta[MDGAT_MLP_MAX_CONVS - 1];
+} mdgat_mlp_grads;
+/* Forward.  Y_l = A_{l-1} W_l^T + b_l; per channel the mean and the biased variance over the R rows - per-row-block sum and centred
+ * M2, combined in block order by Chan's update, never E[y^2] - E[y]^2 - z = gamma (Y - mean) / sqrt(var + eps) + beta, A_l = max(z, 0).
+ * With training != 0 the same call moves running_mean = (1 - m) rm + m mean, running_var = (1 - m) rv + m var R / (R - 1) and adds 1
+ * to num_batches_tracked; with training == 0 the running statistics stand in for the batch's and are left alone.  `saved`
+ * (mdgat_mlp_workspace_bytes(d, 0), 256-byte aligned) receives what the backward needs beside the inputs: the pre-BN Y_l of every BN
+ * layer and mean / invstd per channel.  A_l is never stored: the normalisation and the ReLU are applied where the next product
+ * loads its A operand.  Asynchronous on `stream`. */
+int mdgat_mlp_forward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, double* out, void* saved, size_t saved_bytes,
+                          void* stream);
+/* Backward: the forward's descriptor, inputs and `saved` (with its size), and dout = dL/dout [R][C[n_conv - 1]] (contiguous).  From the last
+ * convolution to the first: db = colsum(dY), dW = dY^T A, dA = dY W, dz = dA [z > 0] (zero is not positive), dbeta = colsum(dz),
+ * dgamma = colsum(dz yhat), dY = gamma invstd (dz - dbeta / R - yhat dgamma / R) (training == 0: gamma invstd dz).  The sums over the
+ * rows run as one chain per element inside a slab of rows (512 for dW / db, 256 for dgamma / dbeta); the slabs' partials are added
+ * in slab order by a closing launch.  No atomics on values and no workgroup waits for another: two runs give the same bits.  The
+ * walk stops below the lowest gradient that is wanted.  workspace: mdgat_mlp_workspace_bytes(d, 1), 256-byte aligned.
+ * Asynchronous on `stream`. */
+int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, const void* saved, size_t saved_bytes,
+                           const double* dout, const mdgat_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+/* part 0: the forward's `saved`; part 1: the backward's workspace.  0 for a descriptor the calls refuse (and for R == 0) */
+size_t mdgat_mlp_workspace_bytes(const mdgat_mlp_desc* d, int part);
+
 /* match extraction (mdgat.py:441-483) from Z [B][N+1][M+1]. */
 int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold,
                   int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,

@@ -73,6 +73,24 @@ class MdgatLossRequest(C.Structure):
                 ('bad_index', C.c_void_p)]
 
 
+MLP_MAX_CONVS = 4
+
+
+class MdgatMlpDesc(C.Structure):
+    _fields_ = [('n_conv', C.c_int32), ('R', C.c_int32), ('K0', C.c_int32), ('K1', C.c_int32), ('C', C.c_int32 * MLP_MAX_CONVS),
+                ('training', C.c_int32),
+                ('eps', C.c_double * (MLP_MAX_CONVS - 1)), ('momentum', C.c_double * (MLP_MAX_CONVS - 1)),
+                ('W', C.c_void_p * MLP_MAX_CONVS), ('bias', C.c_void_p * MLP_MAX_CONVS),
+                ('gamma', C.c_void_p * (MLP_MAX_CONVS - 1)), ('beta', C.c_void_p * (MLP_MAX_CONVS - 1)),
+                ('running_mean', C.c_void_p * (MLP_MAX_CONVS - 1)), ('running_var', C.c_void_p * (MLP_MAX_CONVS - 1)),
+                ('num_batches_tracked', C.c_void_p * (MLP_MAX_CONVS - 1))]
+
+
+class MdgatMlpGrads(C.Structure):
+    _fields_ = [('dx0', C.c_void_p), ('dx1', C.c_void_p), ('dW', C.c_void_p * MLP_MAX_CONVS), ('dbias', C.c_void_p * MLP_MAX_CONVS),
+                ('dgamma', C.c_void_p * (MLP_MAX_CONVS - 1)), ('dbeta', C.c_void_p * (MLP_MAX_CONVS - 1))]
+
+
 # name -> (restype, argtypes); every symbol include/mdgat_hip.h declares
 SIGNATURES = {
     'mdgat_create': (C.c_int, [C.POINTER(MdgatConfig), C.c_int, C.POINTER(C.c_void_p)]),
@@ -124,6 +142,10 @@ SIGNATURES = {
     'mdgat_match_head_f64': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     'mdgat_match_head_backward': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]),
     'mdgat_match_head_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'mdgat_mlp_forward_f64': (C.c_int, [C.POINTER(MdgatMlpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_mlp_backward_f64': (C.c_int, [C.POINTER(MdgatMlpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(MdgatMlpGrads),
+                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_mlp_workspace_bytes': (C.c_size_t, [C.POINTER(MdgatMlpDesc), C.c_int]),
     'mdgat_sinkhorn': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
     'mdgat_sinkhorn_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

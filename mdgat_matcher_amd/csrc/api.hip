@@ -1009,6 +1009,71 @@ extern "C" int mdgat_match_head_backward(int B, int N, int M, const double* desc
     return launch_match_head_backward_f64(B, N, M, desc0, desc1, W, bias, dscores, ddesc0, ddesc1, dW, dbias, workspace, static_cast<hipStream_t>(stream));
 }
 
+// ---- the reference's MLP in training mode (Conv1d(k=1) + batch-statistics BatchNorm + ReLU) and its backward: csrc/mlp_grad.hip ----
+constexpr int MLP_CMAX = 512;
+static int mlp_shape(const char* who, const mdgat_mlp_desc* d) {
+    if (!d) { mdgat_set_error("%s: null descriptor", who); return MDGAT_ERR_BAD_ARG; }
+    if (d->R < 0 || d->K0 < 0 || d->K1 < 0) { mdgat_set_error("%s: bad shape R=%d K0=%d K1=%d", who, d->R, d->K0, d->K1); return MDGAT_ERR_BAD_ARG; }
+    if (d->n_conv < 1 || d->n_conv > MDGAT_MLP_MAX_CONVS) { mdgat_set_error("%s: %d convolutions, 1 to %d supported", who, d->n_conv, MDGAT_MLP_MAX_CONVS); return MDGAT_ERR_UNSUPPORTED; }
+    if (d->K0 < 1 || d->K0 + d->K1 > MLP_CMAX) { mdgat_set_error("%s: %d + %d input channels, 1 to %d supported", who, d->K0, d->K1, MLP_CMAX); return MDGAT_ERR_UNSUPPORTED; }
+    for (int l = 0; l < d->n_conv; ++l)
+        if (d->C[l] < 16 || d->C[l] > MLP_CMAX || d->C[l] % 16) {
+            mdgat_set_error("%s: convolution %d has %d output channels: a multiple of 16 up to %d is supported", who, l, d->C[l], MLP_CMAX);
+            return MDGAT_ERR_UNSUPPORTED;
+        }
+    if (d->R > (1 << 24)) { mdgat_set_error("%s: %d rows: more than 2^24", who, d->R); return MDGAT_ERR_UNSUPPORTED; }
+    if (d->R == 1 && d->training && d->n_conv > 1) {
+        mdgat_set_error("%s: batch statistics need more than one row (R = 1 in training mode)", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return MDGAT_OK;
+}
+static int mlp_pointers(const char* who, const mdgat_mlp_desc* d, const double* x0, const double* x1) {
+    bool ok = x0 && (d->K1 == 0 || x1);
+    for (int l = 0; l < d->n_conv; ++l) ok = ok && d->W[l] && d->bias[l];
+    for (int l = 0; l + 1 < d->n_conv; ++l)
+        ok = ok && d->gamma[l] && d->beta[l] && d->running_mean[l] && d->running_var[l] && (!d->training || d->num_batches_tracked[l]);
+    if (!ok) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    for (int l = 0; l + 1 < d->n_conv; ++l)
+        if (!(d->eps[l] >= 0.0) || (d->training && !(d->momentum[l] >= 0.0 && d->momentum[l] <= 1.0))) {
+            mdgat_set_error("%s: BatchNorm %d: eps=%g momentum=%g", who, l, d->eps[l], d->momentum[l]);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    return MDGAT_OK;
+}
+static int mlp_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
+    if (!p || have < need || (reinterpret_cast<uintptr_t>(p) & 255)) { mdgat_set_error("%s: %s too small or not 256-byte aligned", who, what); return MDGAT_ERR_BAD_ARG; }
+    return MDGAT_OK;
+}
+
+extern "C" size_t mdgat_mlp_workspace_bytes(const mdgat_mlp_desc* d, int part) {
+    if (mlp_shape("mdgat_mlp_workspace_bytes", d) || d->R == 0 || part < 0 || part > 1) return 0;
+    return part == 0 ? mlp_f64_saved_bytes(*d) : mlp_f64_backward_workspace_bytes(*d);
+}
+
+extern "C" int mdgat_mlp_forward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, double* out, void* saved, size_t saved_bytes,
+                                     void* stream) {
+    const char* who = "mdgat_mlp_forward_f64";
+    if (int rc = mlp_shape(who, d)) return rc;
+    if (d->R == 0) return MDGAT_OK;
+    if (int rc = mlp_pointers(who, d, x0, x1)) return rc;
+    if (!out) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = mlp_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
+    return launch_mlp_forward_f64(*d, x0, x1, out, saved, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, const void* saved, size_t saved_bytes,
+                                      const double* dout, const mdgat_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_mlp_backward_f64";
+    if (int rc = mlp_shape(who, d)) return rc;
+    if (d->R == 0) return MDGAT_OK;
+    if (int rc = mlp_pointers(who, d, x0, x1)) return rc;
+    if (!dout || !grads) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = mlp_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
+    if (int rc = mlp_buffer(who, "workspace", workspace, workspace_bytes, mlp_f64_backward_workspace_bytes(*d))) return rc;
+    return launch_mlp_backward_f64(*d, x0, x1, saved, dout, *grads, workspace, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
     if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (topk < 0) { mdgat_set_error("mdgat_attention_f64: topk < 0"); return MDGAT_ERR_BAD_ARG; }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "../../include/mdgat_hip.h"
 
 class CoopGroup;      // coop_chain.hpp
 
@@ -98,3 +99,12 @@ int launch_match_head_backward_f64(int B, int N, int M, const double* desc0, con
 size_t attention_backward_f64_workspace_bytes(int B, int N, int M);
 int launch_attention_backward_f64(int B, int N, int M, int cross, int topk, const double* qkv, const uint32_t* sel, const double* dmsg, double* dqkv,
                                   void* workspace, hipStream_t s);
+
+// ---- mlp_grad.hip: the reference's MLP (Conv1d(k=1) + batch-statistics BatchNorm + ReLU, mdgat.py:34-46) in training mode, and its backward ----
+// the descriptor is the caller's to check (api.hip); saved: what the forward keeps for the backward (mlp_f64_saved_bytes), workspace:
+// the backward's own (mlp_f64_backward_workspace_bytes), both 256-byte aligned
+size_t mlp_f64_saved_bytes(const mdgat_mlp_desc& d);
+size_t mlp_f64_backward_workspace_bytes(const mdgat_mlp_desc& d);
+int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, double* out, void* saved, hipStream_t s);
+int launch_mlp_backward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, const void* saved, const double* dout,
+                            const mdgat_mlp_grads& g, void* workspace, hipStream_t s);

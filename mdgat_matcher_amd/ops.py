@@ -808,3 +808,232 @@ def match_head(desc0: torch.Tensor, desc1: torch.Tensor, weight: torch.Tensor, b
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (desc0, desc1, weight, bias)):
         return _MatchHead.apply(desc0, desc1, weight, bias)
     return _match_head_values(desc0, desc1, weight, bias)
+
+
+# ---- the reference's MLP in training mode (mdgat.py:34-46: Conv1d(k=1), BatchNorm1d on batch statistics, ReLU; csrc/mlp_grad.hip) ----
+class MlpSaved:
+    """What ``mlp_f64_forward`` keeps for ``mlp_f64_backward`` beside the inputs: the pre-BN output of every BN layer and mean /
+    invstd per channel, in one device buffer laid out by the library."""
+    __slots__ = ('buffer', 'base', 'nbytes', 'training', 'rows')
+
+    def __init__(self, buffer, base, nbytes, training, rows):
+        self.buffer, self.base, self.nbytes, self.training, self.rows = buffer, base, nbytes, training, rows
+
+
+def _mlp_modules(seq):
+    """(convs, bns) of an nn.Sequential laid out as the reference's MLP lays it out, or of a bare nn.Conv1d."""
+    nn = torch.nn
+    if isinstance(seq, nn.Conv1d):
+        mods = [seq]
+    elif isinstance(seq, nn.Sequential):
+        mods = list(seq.children())
+    else:
+        raise ValueError(f'mlp_f64 takes an nn.Sequential laid out as the reference\'s MLP or an nn.Conv1d, got {type(seq).__name__}')
+    if not mods or (len(mods) - 1) % 3:
+        raise ValueError(f'mlp_f64: {len(mods)} modules are not Conv1d (BatchNorm1d ReLU Conv1d)*')
+    convs, bns = mods[0::3], mods[1::3]
+    if len(convs) > _lib.MLP_MAX_CONVS:
+        raise ValueError(f'mlp_f64: {len(convs)} convolutions, at most {_lib.MLP_MAX_CONVS} are supported')
+    for i, m in enumerate(mods):
+        want = (nn.Conv1d, nn.BatchNorm1d, nn.ReLU)[i % 3]
+        if not isinstance(m, want):
+            raise ValueError(f'mlp_f64: module {i} is {type(m).__name__}, the reference\'s MLP has {want.__name__} there')
+    for c in convs:
+        if c.kernel_size != (1,) or c.stride != (1,) or c.padding != (0,) or c.dilation != (1,) or c.groups != 1 or c.bias is None:
+            raise ValueError(f'mlp_f64: {c} is not a plain Conv1d(kernel_size=1) with bias')
+    for b in bns:
+        if not b.affine or b.weight is None:
+            raise ValueError('mlp_f64: BatchNorm1d without affine parameters is not supported')
+        if not b.track_running_stats or b.running_mean is None or b.running_var is None:
+            raise ValueError('mlp_f64: BatchNorm1d without running statistics is not supported')
+        if b.momentum is None:
+            raise ValueError('mlp_f64: BatchNorm1d(momentum=None) (cumulative average) is not supported')
+    for a, b in zip(convs[:-1], bns):
+        if b.num_features != a.out_channels:
+            raise ValueError(f'mlp_f64: {b} does not fit {a}')
+    for a, b in zip(convs[:-1], convs[1:]):
+        if b.in_channels != a.out_channels:
+            raise ValueError(f'mlp_f64: {b} does not follow {a}')
+    for c in convs:
+        if c.out_channels % 16 or not 16 <= c.out_channels <= 512:
+            raise ValueError(f'mlp_f64: {c.out_channels} output channels: the kernels take multiples of 16 up to 512')
+    if not 1 <= convs[0].in_channels <= 512:
+        raise ValueError(f'mlp_f64: {convs[0].in_channels} input channels: the kernels take 1 to 512')
+    return convs, bns
+
+
+def _mlp_rows(x, x1, cin):
+    """x [..., K0] (and x1 [..., K1]) -> contiguous rows [R, K0], [R, K1] or None, the leading shape."""
+    for t in (x,) if x1 is None else (x, x1):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError('mlp_f64 takes float64 tensors')
+    _need_cuda(x, *(() if x1 is None else (x1,)))
+    if x.dim() < 1 or (x1 is not None and (x1.shape[:-1] != x.shape[:-1] or x1.device != x.device)):
+        raise ValueError(f'mlp_f64: x {tuple(x.shape)} and x1 {None if x1 is None else tuple(x1.shape)} must share their leading shape and device')
+    k0, k1 = x.shape[-1], 0 if x1 is None else x1.shape[-1]
+    if k0 < 1 or (x1 is not None and k1 < 1) or k0 + k1 != cin:
+        raise ValueError(f'mlp_f64: {k0} + {k1} input channels (channel-last), the first convolution takes {cin}')
+    r0 = x.detach().reshape(-1, k0).contiguous()
+    r1 = None if x1 is None else x1.detach().reshape(-1, k1).contiguous()
+    return r0, r1, tuple(x.shape[:-1])
+
+
+def _mlp_desc(rows, k0, k1, training, ws, bs, gammas, betas, bufs, eps, momentum, device):
+    """The library's descriptor and the tensors it points into (to be kept alive as long as it)."""
+    d = _lib.MdgatMlpDesc()
+    d.n_conv, d.R, d.K0, d.K1, d.training = len(ws), rows, k0, k1, int(training)
+    keep = []
+
+    def ptr(t, inplace=False):
+        if t.dtype != torch.float64 or t.device != device:
+            raise ValueError(f'mlp_f64: parameters and buffers must be float64 on {device}, got {t.dtype} on {t.device}')
+        if inplace and not t.is_contiguous():
+            raise ValueError('mlp_f64: the running buffers must be contiguous')
+        t = t.detach().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+    for l, (w, b) in enumerate(zip(ws, bs)):
+        d.C[l], d.W[l], d.bias[l] = w.shape[0], ptr(w), ptr(b)
+    for l, (g, be, (rm, rv, nbt)) in enumerate(zip(gammas, betas, bufs)):
+        d.gamma[l], d.beta[l], d.running_mean[l], d.running_var[l] = ptr(g), ptr(be), ptr(rm, True), ptr(rv, True)
+        if nbt is not None:
+            if nbt.dtype != torch.int64 or nbt.device != device:
+                raise ValueError('mlp_f64: num_batches_tracked must be int64 on the device')
+            d.num_batches_tracked[l] = nbt.data_ptr()
+            keep.append(nbt)
+        d.eps[l], d.momentum[l] = float(eps[l]), float(momentum[l])
+    return d, keep
+
+
+def _mlp_buffer(lib, desc, part, device):
+    need = lib.mdgat_mlp_workspace_bytes(C.byref(desc), part)
+    buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return buf, buf.data_ptr() + (-buf.data_ptr()) % 256, need
+
+
+def _mlp_split(seq):
+    convs, bns = _mlp_modules(seq)
+    ws, bs = [c.weight for c in convs], [c.bias for c in convs]
+    gammas, betas = [b.weight for b in bns], [b.bias for b in bns]
+    bufs = [(b.running_mean, b.running_var, b.num_batches_tracked) for b in bns]
+    training = bool(seq.training)
+    if training and any(nbt is None for _, _, nbt in bufs):
+        raise ValueError('mlp_f64: BatchNorm1d without num_batches_tracked is not supported')
+    return ws, bs, gammas, betas, bufs, [b.eps for b in bns], [b.momentum for b in bns], training
+
+
+def _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training):
+    r0, r1, lead = _mlp_rows(x, x1, ws[0].shape[1])
+    rows, cout = r0.shape[0], ws[-1].shape[0]
+    if rows == 1 and training and gammas:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
+    out = torch.empty((rows, cout), dtype=torch.float64, device=r0.device)
+    if rows == 0:
+        return out.reshape(*lead, cout), MlpSaved(None, 0, 0, training, 0)
+    d, keep = _mlp_desc(rows, r0.shape[1], 0 if r1 is None else r1.shape[1], training, ws, bs, gammas, betas, bufs, eps, momentum, r0.device)
+    lib = _lib.load()
+    with torch.cuda.device(r0.device):
+        buf, base, need = _mlp_buffer(lib, d, 0, r0.device)
+        _lib.check(lib.mdgat_mlp_forward_f64(C.byref(d), r0.data_ptr(), None if r1 is None else r1.data_ptr(), out.data_ptr(), base, need,
+                                             _stream(r0)), 'mdgat_mlp_forward_f64')
+    del keep
+    return out.reshape(*lead, cout), MlpSaved(buf, base, need, training, rows)
+
+
+def _mlp_backward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, saved, dout, need):
+    """need: (dx, dx1, [dW...], [db...], [dgamma...], [dbeta...]) booleans -> the same structure of tensors / None."""
+    r0, r1, lead = _mlp_rows(x, x1, ws[0].shape[1])
+    rows, cout = r0.shape[0], ws[-1].shape[0]
+    if not isinstance(saved, MlpSaved) or saved.rows != rows:
+        raise ValueError('mlp_f64_backward: `saved` is not what mlp_f64_forward returned for these inputs')
+    if not isinstance(dout, torch.Tensor) or dout.dtype != torch.float64 or dout.device != r0.device or tuple(dout.shape) != lead + (cout,):
+        raise ValueError(f'mlp_f64_backward: dout must be float64 {lead + (cout,)} on {r0.device}')
+    g = dout.detach().reshape(-1, cout).contiguous()
+    new = (torch.zeros if rows == 0 else torch.empty)        # (an empty batch launches nothing and its sums are zero)
+    mk = lambda want, like: new(like.shape, dtype=torch.float64, device=r0.device) if want else None      # noqa: E731
+    dx = mk(need[0], r0)
+    dx1 = mk(need[1] and r1 is not None, r1 if r1 is not None else r0)
+    dW, db = [mk(n, w) for n, w in zip(need[2], ws)], [mk(n, b) for n, b in zip(need[3], bs)]
+    dga, dbe = [mk(n, t) for n, t in zip(need[4], gammas)], [mk(n, t) for n, t in zip(need[5], betas)]
+    if rows > 0 and any(t is not None for t in [dx, dx1, *dW, *db, *dga, *dbe]):
+        d, keep = _mlp_desc(rows, r0.shape[1], 0 if r1 is None else r1.shape[1], saved.training, ws, bs, gammas, betas, bufs, eps, momentum,
+                            r0.device)
+        gr = _lib.MdgatMlpGrads()
+        p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+        gr.dx0, gr.dx1 = p(dx), p(dx1)
+        for l in range(len(ws)):
+            gr.dW[l], gr.dbias[l] = p(dW[l]), p(db[l])
+        for l in range(len(gammas)):
+            gr.dgamma[l], gr.dbeta[l] = p(dga[l]), p(dbe[l])
+        lib = _lib.load()
+        with torch.cuda.device(r0.device):
+            buf, base, nbytes = _mlp_buffer(lib, d, 1, r0.device)
+            _lib.check(lib.mdgat_mlp_backward_f64(C.byref(d), r0.data_ptr(), None if r1 is None else r1.data_ptr(), saved.base, saved.nbytes, g.data_ptr(),
+                                                  C.byref(gr), base, nbytes, _stream(r0)), 'mdgat_mlp_backward_f64')
+        del keep
+    dx = None if dx is None else dx.reshape(x.shape)
+    dx1 = None if dx1 is None else dx1.reshape(x1.shape)
+    return dx, dx1, dW, db, dga, dbe
+
+
+def mlp_f64_forward(seq, x: torch.Tensor, x1: torch.Tensor = None):
+    """``mlp_f64`` without autograd: (out, saved), ``saved`` (``MlpSaved``) being what ``mlp_f64_backward`` needs beside the inputs.
+    In training mode the BatchNorm buffers of ``seq`` move, exactly once per call."""
+    return _mlp_forward(x, x1, *_mlp_split(seq))
+
+
+def mlp_f64_backward(seq, x: torch.Tensor, x1, saved: MlpSaved, dout: torch.Tensor, need=None):
+    """Gradient of ``mlp_f64`` (csrc/mlp_grad.hip): the forward's modules, inputs and ``saved``, and dout = dL/dout [..., C_L] ->
+    (dx, dx1, [dW per convolution], [dbias ...], [dgamma per BatchNorm], [dbeta ...]), float64, each in the shape of its tensor (the
+    weights [C_out, C_in, 1]).  ``need``: the same structure of booleans - which to compute (None for the others; default: all, dx1
+    only with an x1); a product that only an unwanted gradient needs is not formed.  The sums over the rows are added in a fixed
+    order: the same bits from run to run.  ``seq``'s parameters must be the forward's; its buffers are not touched."""
+    ws, bs, gammas, betas, bufs, eps, momentum, _ = _mlp_split(seq)
+    if need is None:
+        need = (True, x1 is not None, [True] * len(ws), [True] * len(ws), [True] * len(gammas), [True] * len(gammas))
+    return _mlp_backward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, saved, dout, need)
+
+
+class _MlpF64(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, meta, x, x1, *params):
+        n, nb, bufs, eps, momentum, training = meta
+        ws, bs, gammas, betas = params[:n], params[n:2 * n], params[2 * n:2 * n + nb], params[2 * n + nb:]
+        out, saved = _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training)
+        ctx.meta, ctx.saved = meta, saved
+        ctx.save_for_backward(x, x1, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        n, nb, bufs, eps, momentum, _ = ctx.meta
+        x, x1, *params = ctx.saved_tensors
+        ws, bs, gammas, betas = params[:n], params[n:2 * n], params[2 * n:2 * n + nb], params[2 * n + nb:]
+        want = ctx.needs_input_grad[1:]
+        need = (want[0], want[1], want[2:2 + n], want[2 + n:2 + 2 * n], want[2 + 2 * n:2 + 2 * n + nb], want[2 + 2 * n + nb:])
+        dx, dx1, dW, db, dga, dbe = _mlp_backward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, ctx.saved, dout, need)
+        return (None, dx, dx1, *dW, *db, *dga, *dbe)
+
+
+def mlp_f64(seq, x: torch.Tensor, x1: torch.Tensor = None) -> torch.Tensor:
+    """The reference's ``MLP`` (mdgat.py:34-46) in fp64 with BatchNorm as ``seq.training`` says - in training mode on the statistics of
+    this call's own rows, the gradient running through them (csrc/mlp_grad.hip).  ``seq``: an ``nn.Sequential`` laid out as the
+    reference lays it out - Conv1d(k=1), then BatchNorm1d and ReLU between convolutions - this package's encoder / layer modules, the
+    reference's own, or a bare ``nn.Conv1d``; 1 to 4 convolutions, output widths multiples of 16 up to 512, up to 512 inputs.
+    ``x`` [..., K0] channel-last float64 on the device (the reference's [B, K0, P] transposed); ``x1`` [..., K1] an optional second
+    source read beside it (the layer's ``cat([x, message])`` without the copy).  Returns [..., C_L].
+
+    Parameters and buffers are read from the modules.  In training mode ``running_mean``, ``running_var`` and ``num_batches_tracked``
+    are updated in place as torch updates them; in eval mode they are read and left alone.  More than one row is needed in training
+    mode (ValueError, as in torch).
+
+    Differentiable (``mlp_f64_backward``; not twice) when x, x1 or a parameter requires grad and grad is enabled: ``.backward()`` fills
+    ``x.grad``, ``x1.grad`` and the ``.grad`` of the modules' own parameters; a gradient nobody asked for is not computed.  Between
+    forward and backward only the inputs, the pre-BN output of every BN layer and mean / invstd per channel are kept."""
+    ws, bs, gammas, betas, bufs, eps, momentum, training = _mlp_split(seq)
+    params = (*ws, *bs, *gammas, *betas)
+    tensors = (x, *params) if x1 is None else (x, x1, *params)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        return _MlpF64.apply((len(ws), len(gammas), bufs, eps, momentum, training), x, x1, *params)
+    return _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training)[0]
