@@ -970,20 +970,21 @@ extern "C" int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda
 }
 
 // ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----
-constexpr int MATCH_HEAD_NMAX = 2175;             // the Sinkhorn backward's limit (sinkhorn_grad.hip), which the chain composes with
-static int match_head_shape(const char* who, int B, int N, int M) {
+// the shape and buffer checks of the gradient entries (this section and the two below)
+// nmax: keypoints per frame; rows: the rows the largest array of a pair holds
+static int grad_shape(const char* who, int B, int N, int M, int nmax, int rows) {
     if (B < 0 || N <= 0 || M <= 0) { mdgat_set_error("%s: bad shape B=%d N=%d M=%d", who, B, N, M); return MDGAT_ERR_BAD_ARG; }
-    if (N > MATCH_HEAD_NMAX || M > MATCH_HEAD_NMAX) { mdgat_set_error("%s: %d x %d keypoints > %d supported", who, N, M, MATCH_HEAD_NMAX); return MDGAT_ERR_UNSUPPORTED; }
-    if ((long long)B * (N > M ? N : M) > (1 << 24)) { mdgat_set_error("%s: %d pairs of %d x %d keypoints: more than 2^24 rows", who, B, N, M); return MDGAT_ERR_UNSUPPORTED; }
+    if (N > nmax || M > nmax) { mdgat_set_error("%s: %d x %d keypoints > %d supported", who, N, M, nmax); return MDGAT_ERR_UNSUPPORTED; }
+    if ((long long)B * rows > (1 << 24)) { mdgat_set_error("%s: B=%d N=%d M=%d: more than 2^24 rows (%d per pair)", who, B, N, M, rows); return MDGAT_ERR_UNSUPPORTED; }
     return MDGAT_OK;
 }
-static int match_head_workspace(const char* who, int B, int N, int M, const void* workspace, size_t workspace_bytes) {
-    if (!workspace || workspace_bytes < match_head_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
+static int grad_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
+    if (!p || have < need || (reinterpret_cast<uintptr_t>(p) & 255)) { mdgat_set_error("%s: %s too small or not 256-byte aligned", who, what); return MDGAT_ERR_BAD_ARG; }
     return MDGAT_OK;
 }
+
+constexpr int MATCH_HEAD_NMAX = 2175;             // the Sinkhorn backward's limit (sinkhorn_grad.hip), which the chain composes with
+static int match_head_shape(const char* who, int B, int N, int M) { return grad_shape(who, B, N, M, MATCH_HEAD_NMAX, N > M ? N : M); }
 
 extern "C" size_t mdgat_match_head_workspace_bytes(int B, int N, int M) {
     if (B <= 0 || match_head_shape("mdgat_match_head_workspace_bytes", B, N, M)) return 0;
@@ -995,7 +996,7 @@ extern "C" int mdgat_match_head_f64(int B, int N, int M, const double* desc0, co
     if (int rc = match_head_shape("mdgat_match_head_f64", B, N, M)) return rc;
     if (B == 0) return MDGAT_OK;
     if (!desc0 || !desc1 || !W || !bias || !scores) { mdgat_set_error("mdgat_match_head_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = match_head_workspace("mdgat_match_head_f64", B, N, M, workspace, workspace_bytes)) return rc;
+    if (int rc = grad_buffer("mdgat_match_head_f64", "workspace", workspace, workspace_bytes, match_head_f64_workspace_bytes(B, N, M))) return rc;
     return launch_match_head_f64(B, N, M, desc0, desc1, W, bias, scores, workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -1005,7 +1006,7 @@ extern "C" int mdgat_match_head_backward(int B, int N, int M, const double* desc
     if (int rc = match_head_shape("mdgat_match_head_backward", B, N, M)) return rc;
     if (B == 0) return MDGAT_OK;
     if (!desc0 || !desc1 || !W || !bias || !dscores) { mdgat_set_error("mdgat_match_head_backward: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = match_head_workspace("mdgat_match_head_backward", B, N, M, workspace, workspace_bytes)) return rc;
+    if (int rc = grad_buffer("mdgat_match_head_backward", "workspace", workspace, workspace_bytes, match_head_f64_workspace_bytes(B, N, M))) return rc;
     return launch_match_head_backward_f64(B, N, M, desc0, desc1, W, bias, dscores, ddesc0, ddesc1, dW, dbias, workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -1041,11 +1042,6 @@ static int mlp_pointers(const char* who, const mdgat_mlp_desc* d, const double* 
         }
     return MDGAT_OK;
 }
-static int mlp_buffer(const char* who, const char* what, const void* p, size_t have, size_t need) {
-    if (!p || have < need || (reinterpret_cast<uintptr_t>(p) & 255)) { mdgat_set_error("%s: %s too small or not 256-byte aligned", who, what); return MDGAT_ERR_BAD_ARG; }
-    return MDGAT_OK;
-}
-
 extern "C" size_t mdgat_mlp_workspace_bytes(const mdgat_mlp_desc* d, int part) {
     if (mlp_shape("mdgat_mlp_workspace_bytes", d) || d->R == 0 || part < 0 || part > 1) return 0;
     return part == 0 ? mlp_f64_saved_bytes(*d) : mlp_f64_backward_workspace_bytes(*d);
@@ -1058,7 +1054,7 @@ extern "C" int mdgat_mlp_forward_f64(const mdgat_mlp_desc* d, const double* x0, 
     if (d->R == 0) return MDGAT_OK;
     if (int rc = mlp_pointers(who, d, x0, x1)) return rc;
     if (!out) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = mlp_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
+    if (int rc = grad_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
     return launch_mlp_forward_f64(*d, x0, x1, out, saved, static_cast<hipStream_t>(stream));
 }
 
@@ -1069,8 +1065,8 @@ extern "C" int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0,
     if (d->R == 0) return MDGAT_OK;
     if (int rc = mlp_pointers(who, d, x0, x1)) return rc;
     if (!dout || !grads) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = mlp_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
-    if (int rc = mlp_buffer(who, "workspace", workspace, workspace_bytes, mlp_f64_backward_workspace_bytes(*d))) return rc;
+    if (int rc = grad_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
+    if (int rc = grad_buffer(who, "workspace", workspace, workspace_bytes, mlp_f64_backward_workspace_bytes(*d))) return rc;
     return launch_mlp_backward_f64(*d, x0, x1, saved, dout, *grads, workspace, static_cast<hipStream_t>(stream));
 }
 
@@ -1082,12 +1078,7 @@ extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, con
 
 // ---- the backward of mdgat_attention_f64: csrc/attention_grad.hip ----
 constexpr int ATTENTION_GRAD_NMAX = 2048;         // the forward's limit for dynamic layers
-static int attention_grad_shape(const char* who, int B, int N, int M) {
-    if (B < 0 || N <= 0 || M <= 0) { mdgat_set_error("%s: bad shape B=%d N=%d M=%d", who, B, N, M); return MDGAT_ERR_BAD_ARG; }
-    if (N > ATTENTION_GRAD_NMAX || M > ATTENTION_GRAD_NMAX) { mdgat_set_error("%s: %d x %d keypoints > %d supported", who, N, M, ATTENTION_GRAD_NMAX); return MDGAT_ERR_UNSUPPORTED; }
-    if ((long long)B * (N + M) > (1 << 24)) { mdgat_set_error("%s: %d pairs of %d + %d keypoints: more than 2^24 rows", who, B, N, M); return MDGAT_ERR_UNSUPPORTED; }
-    return MDGAT_OK;
-}
+static int attention_grad_shape(const char* who, int B, int N, int M) { return grad_shape(who, B, N, M, ATTENTION_GRAD_NMAX, N + M); }
 
 extern "C" size_t mdgat_attention_backward_workspace_bytes(int B, int N, int M) {
     if (B <= 0 || attention_grad_shape("mdgat_attention_backward_workspace_bytes", B, N, M)) return 0;
@@ -1102,9 +1093,6 @@ extern "C" int mdgat_attention_backward_f64(int B, int N, int M, int cross, int 
     if (B == 0) return MDGAT_OK;
     if (!qkv || !dmsg || !dqkv) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
     if (topk > 0 && !sel) { mdgat_set_error("%s: topk=%d needs the forward's selection words (sel)", who, topk); return MDGAT_ERR_BAD_ARG; }
-    if (!workspace || workspace_bytes < attention_backward_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
+    if (int rc = grad_buffer(who, "workspace", workspace, workspace_bytes, attention_backward_f64_workspace_bytes(B, N, M))) return rc;
     return launch_attention_backward_f64(B, N, M, cross, topk, qkv, sel, dmsg, dqkv, workspace, static_cast<hipStream_t>(stream));
 }

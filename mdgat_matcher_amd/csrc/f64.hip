@@ -19,7 +19,9 @@
 // launcher sizes its tiles by the launch (64 x 64 tiles, 64-deep chunks, 16-query workgroups for a pair or two: section 9).
 //
 //   gemm_f64_kernel       C = act(A W^T + b) (+ R): every Conv1d(k=1) of the path (mdgat.py:34-46 after BN folding; 152-155,
-//                         184-188, 227-232, 246-248, 274), 64 x 64 / 64 x 128 tiles, 32- (64-) deep K chunks through LDS.
+//                         184-188, 227-232, 246-248, 274), 64 x 64 / 64 x 128 tiles, 32- (64-) deep K chunks through LDS.  Also
+//                         the products of the training-mode MLP (mlp_grad.hip): behind a BatchNorm the A operand is
+//                         max(z, 0) of the stored convolution output, formed as it is loaded (BNT).
 //   attention_f64_kernel  attention / dynamic_attention (mdgat.py:190-210) for 16 (or 32) queries of a (pair, frame, head) per
 //                         workgroup, the KEYS split over the four waves: S^T = K Q^T puts a query's logits into the four lanes
 //                         (q, q + 16, q + 32, q + 48), the D fragment of a 16-key block is the B operand of the P.V product as
@@ -47,7 +49,9 @@ constexpr int G_BM = 64, G_KC = 32;      // row pitch KC + 2 doubles (34: 68 dwo
 // chunk, every one its own exec-masked branch)
 // KC: depth of a chunk.  32; 64 (FAST only) for launches of less than a round of workgroups, which are a chain of chunk round trips
 // (load -> registers -> LDS -> barrier, ~2 us each with nothing else on the CU to cover it): half as many.
-template <int WN, bool FAST, int KC = G_KC>      // 16-column blocks per wave: workgroup tile 64 x (32 WN)
+// BNT: the A operand is bn_relu of what is loaded (GemmF64Args::bn_*: the training-mode MLP's products behind a BatchNorm), formed between
+// the global load and the LDS store; a thread's channels are the same for every row of a chunk it loads.
+template <int WN, bool FAST, int KC = G_KC, bool BNT = false>      // 16-column blocks per wave: workgroup tile 64 x (32 WN)
 __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmF64Args a) {
     static_assert(KC == 32 || (KC == 64 && FAST), "chunk depth");
     if (a.batch > 1) { a.A0 += (size_t)blockIdx.z * a.sA; a.W += (size_t)blockIdx.z * a.sW; a.C += (size_t)blockIdx.z * a.sC; }
@@ -71,6 +75,12 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmF64Args a) {
                 const f64x2 v = *reinterpret_cast<const f64x2*>(src + (size_t)(row0 + r) * ld + c);
                 ra[2 * u] = v[0]; ra[2 * u + 1] = v[1];
             }
+            if (BNT) {
+                const int kk = k0 + (tid & RMASK) * 2;
+                const double m0 = a.bn_mean[kk], m1 = a.bn_mean[kk + 1], a0 = a.bn_a[kk], a1 = a.bn_a[kk + 1], b0 = a.bn_beta[kk], b1 = a.bn_beta[kk + 1];
+#pragma unroll
+                for (int u = 0; u < NA / 2; ++u) { ra[2 * u] = bn_relu(ra[2 * u], m0, a0, b0); ra[2 * u + 1] = bn_relu(ra[2 * u + 1], m1, a1, b1); }
+            }
 #pragma unroll
             for (int u = 0; u < NW / 2; ++u) {
                 const int idx = tid + 256 * u, r = idx >> RSH, c = (idx & RMASK) * 2;
@@ -79,12 +89,17 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmF64Args a) {
             }
             return;
         }
+        double bm = 0.0, ba = 0.0, bb = 0.0;
+        if (BNT && k0 + (tid & 31) < a.K) { const int kk = k0 + (tid & 31); bm = a.bn_mean[kk]; ba = a.bn_a[kk]; bb = a.bn_beta[kk]; }
 #pragma unroll
         for (int u = 0; u < NA; ++u) {
             const int idx = tid + 256 * u, r = idx >> 5, c = idx & 31;
             const int row = row0 + r, kk = k0 + c;
             double v = 0.0;
-            if (row < a.M && kk < a.K) v = kk < a.K0 ? a.A0[(size_t)row * a.lda0 + kk] : a.A1[(size_t)row * a.lda1 + (kk - a.K0)];
+            if (row < a.M && kk < a.K) {
+                v = kk < a.K0 ? a.A0[(size_t)row * a.lda0 + kk] : a.A1[(size_t)row * a.lda1 + (kk - a.K0)];
+                if (BNT) v = bn_relu(v, bm, ba, bb);      // (beyond the tile: 0, not max(beta, 0))
+            }
             ra[u] = v;
         }
 #pragma unroll
@@ -768,9 +783,25 @@ __global__ void mfma64_probe_fill(double* p, int n) {
 }  // namespace
 
 // ================================================================================================ launchers
+template <bool BNT>
+static int gemm_f64_go(const GemmF64Args& a, int wn, bool fast, bool deep, hipStream_t s) {
+    static std::atomic<unsigned long long> done2{0}, done4{0}, done2f{0}, done4f{0}, done2d{0};
+    const int bn = 32 * wn;
+    const size_t lds = (size_t)(G_BM + bn) * ((deep ? 64 : G_KC) + 2) * sizeof(double);
+    const dim3 grid((a.M + G_BM - 1) / G_BM, (a.N + bn - 1) / bn, a.batch > 1 ? a.batch : 1);
+    auto go = [&](auto kern, std::atomic<unsigned long long>& done) -> int {
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "gemm_f64 LDS")) return rc;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+        return MDGAT_OK;
+    };
+    if (wn == 4) return fast ? go(gemm_f64_kernel<4, true, G_KC, BNT>, done4f) : go(gemm_f64_kernel<4, false, G_KC, BNT>, done4);
+    if (deep) return go(gemm_f64_kernel<2, true, 64, BNT>, done2d);
+    return fast ? go(gemm_f64_kernel<2, true, G_KC, BNT>, done2f) : go(gemm_f64_kernel<2, false, G_KC, BNT>, done2);
+}
+
 int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return MDGAT_OK;
-    static std::atomic<unsigned long long> done2{0}, done4{0}, done2f{0}, done4f{0}, done2d{0};
+    if (a.bn_mean && a.K0 < a.K) { mdgat_set_error("gemm_f64: the BatchNorm operand transform takes a single source"); return MDGAT_ERR_BAD_ARG; }
     // Tile width.  64 x 128 tiles do a third more arithmetic per byte staged through LDS; 64 x 64 tiles are twice as many workgroups
     // (four resident per CU instead of three).  Up to a few rounds of workgroups the launch is bound by how evenly it fills the
     // CUs, not by its inner loop: one pair of 512 keypoints is 16 row tiles - 48 wide workgroups on 256 CUs for the q|k|v product,
@@ -792,17 +823,7 @@ int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
     // at K = 256, the one-pair forward 1.54 -> 1.48 ms; from eight pairs on the shallower chunks' third resident workgroup wins)
     const bool deep = fast && wn == 2 && a.K % 64 == 0 && (a.K0 >= a.K || a.K0 % 64 == 0) &&
                       (long)((a.M + G_BM - 1) / G_BM) * ((a.N + 63) / 64) * (a.batch > 1 ? a.batch : 1) <= (long)mdgat_cu_count();
-    const size_t lds = (size_t)(G_BM + bn) * ((deep ? 64 : G_KC) + 2) * sizeof(double);
-    const dim3 grid((a.M + G_BM - 1) / G_BM, (a.N + bn - 1) / bn, a.batch > 1 ? a.batch : 1);
-    auto go = [&](auto kern, std::atomic<unsigned long long>& done) -> int {
-        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "gemm_f64 LDS")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-        return MDGAT_OK;
-    };
-    int rc;
-    if (wn == 4) rc = fast ? go(gemm_f64_kernel<4, true>, done4f) : go(gemm_f64_kernel<4, false>, done4);
-    else if (deep) rc = go(gemm_f64_kernel<2, true, 64>, done2d);
-    else rc = fast ? go(gemm_f64_kernel<2, true>, done2f) : go(gemm_f64_kernel<2, false>, done2);
+    const int rc = a.bn_mean ? gemm_f64_go<true>(a, wn, fast, deep, s) : gemm_f64_go<false>(a, wn, fast, deep, s);
     if (rc) return rc;
     return mdgat_check_hip(hipGetLastError(), "gemm_f64 launch");
 }

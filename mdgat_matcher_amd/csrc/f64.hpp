@@ -23,6 +23,9 @@ struct GemmF64Args {
     double scale = 1.0;                // C = act(scale A W^T + bias) (+ R)   (the score matrix: 1 / sqrt(128), mdgat.py:431)
     int batch = 1;                     // independent products; A0, W, C of product z at + z sA, + z sW, + z sC (no second source, bias, residual shared)
     long long sA = 0, sW = 0, sC = 0;
+    const double *bn_mean = nullptr, *bn_a = nullptr, *bn_beta = nullptr;      // [K] each, single source (K0 >= K) only: the A operand is
+                                       // bn_relu(A0[row][k], mean[k], a[k], beta[k]) (f64_dev.hpp) - the training-mode MLP's BatchNorm + ReLU,
+                                       // formed as the operand is loaded
 };
 int launch_gemm_f64(const GemmF64Args& a, hipStream_t s);
 
@@ -83,6 +86,20 @@ int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s);
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s);
 inline size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }      // ... and its size (where the images are: weights.hpp)
 bool layer_f64_fused();               // mdgat_set_f64_layer_fusion / MDGAT_F64_LAYER_FUSION
+
+// ---- dw_f64.hip: dW = dY^T X [Cout][K0 + K1] and db = colsum(dY) [Cout] of a Conv1d(k=1) Y = X W^T + b, the rows cut into slabs ----
+struct DwF64Args {
+    const double* dY; int Cout;                  // [R][Cout], Cout a multiple of 16
+    const double* x0; int K0;                    // the convolution's input: [R][K0] | [R][K1] (x1: nullptr when K1 == 0)
+    const double* x1; int K1;
+    const double *bn_mean, *bn_a, *bn_beta;      // [K0]: X = bn_relu(x0) as it is loaded (K1 == 0), or nullptr
+    int R, slab;                                 // slab b owns the rows [b slab, min((b + 1) slab, R)): ONE chain per output element, rows ascending
+    double* P;                                   // the slabs' partials [ceil(R / slab)][Cout (K0 + K1) + Cout]: dW then db
+    double *dW, *db;                             // = P[0] + P[1] + ... in slab order; nullptr: not wanted (without dW no product is formed)
+};
+int launch_dw_f64(const DwF64Args& a, hipStream_t s);
+// the reduction alone, over partials [slabs][nW + nb] that the caller formed (head_grad.hip)
+int launch_dw_reduce_f64(const double* P, int slabs, int nW, int nb, double* dW, double* db, hipStream_t s);
 
 // ---- head_grad.hip: the matching head (final_proj and the score matrix, mdgat.py:397, 430-431) as a call of its own, and its backward ----
 // desc0 [B][N][128], desc1 [B][M][128], W [128][128], bias [128] -> scores [B][N][M] by tail64's launches; the arguments are the

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the fp64 kernels of the reference-exact mode (f64.hip, layer_f64.hip).
+// Device-side helpers shared by the fp64 kernels of the reference-exact mode (f64.hip, layer_f64.hip) and its backward units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,16 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 // v_mfma_f64_16x16x4_f64: A 16x4, B 4x16 one double per lane (row / col = lane & 15, k = lane >> 4); C/D col = lane & 15,
 // row = (lane >> 4) + 4 reg (cdna_hip_programming.md section 3)
 __device__ __forceinline__ f64x4 mfma64(double a, double b, f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+// BatchNorm + ReLU of the training-mode MLP (mlp_grad.hip), z = gamma (y - mean) invstd + beta with a = gamma invstd.  The one place z
+// is formed: every kernel that needs z or its sign calls this (the product behind a BN in f64.hip, dW's operand in dw_f64.hip, the
+// masks of mlp_grad.hip), so the sign of z is the same everywhere.  A NaN z gives 0 under either set of flags these units are
+// compiled with: as a compare and select (NaN > 0 is false) and as v_max_f64 (z comes out of an fma, hence is quiet).
+__device__ __forceinline__ double bn_z(double y, double mean, double a, double beta) { return __builtin_fma(y - mean, a, beta); }
+__device__ __forceinline__ double bn_relu(double y, double mean, double a, double beta) {
+    const double z = bn_z(y, mean, a, beta);
+    return z > 0.0 ? z : 0.0;
+}
 
 // Range guard of the exact mode, BETWEEN the layers: every output of an fp64 product (q | k | v, the hidden layer before its ReLU,
 // the residual stream, the encoder stages) and every message row is tested for "not finite, or |v| >= 2^500" by its exponent field,

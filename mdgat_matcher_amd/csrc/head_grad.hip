@@ -22,10 +22,12 @@
 //   2. hg_dw_kernel: per pair dW_pair = dmd^T desc over the pair's points, frame 0 then frame 1, points ascending - ONE chain per
 //      output element, no split of the contraction.  Both operands are contracted over their rows, so both fragments are coalesced
 //      loads from L2 and there is no LDS: sixteen waves of 32 x 32 per pair.  db_pair rides along: every lane adds up the A
-//      fragment values it loads (a quarter of the points each), the four quarters are combined as (0 + 1) + (2 + 3).
-//   3. hg_reduce_kernel: dW = pair 0's partial + pair 1's + ... in pair order, db likewise.  No value atomics and no workgroup
-//      waits for another: the bits are the same from run to run, ddesc of a pair does not depend on its batch, and for B = 2
-//      dW(batch) == dW(pair 0 alone) + dW(pair 1 alone).
+//      fragment values it loads (a quarter of the points each), the four quarters are combined as (0 + 1) + (2 + 3).  (The MLP's
+//      dw_f64_kernel, dw_f64.hip, is this kernel generalised - ragged tiles, two column sources, a BN in front; run here its
+//      per-load predicates cost 4 to 9 % of the backward, measured, so the head keeps the whole-tile kernel.)
+//   3. launch_dw_reduce_f64 (dw_f64.hip): dW = pair 0's partial + pair 1's + ... in pair order, db likewise.  No value atomics and
+//      no workgroup waits for another: the bits are the same from run to run, ddesc of a pair does not depend on its batch, and for
+//      B = 2 dW(batch) == dW(pair 0 alone) + dW(pair 1 alone).
 // Workspace: md0, md1, dmd0, dmd1 ([B][N + M][128] twice) and the per-pair partials [B][128 x 128 + 128].
 #include "common.hpp"
 #include "f64.hpp"
@@ -54,7 +56,6 @@ struct HgArgs {
     double *dmd0, *dmd1;              // workspace, or nullptr when neither dW nor db is wanted
     double *ddesc0, *ddesc1;          // or nullptr
     double* P;                        // [B][HG_PART]
-    double *dW, *db;                  // or nullptr
 };
 
 template <int FRAME>
@@ -240,16 +241,6 @@ __global__ __launch_bounds__(256) void hg_dw_kernel(HgArgs a) {
     }
 }
 
-// dW / db = the pairs' partials added in pair order, starting from pair 0's
-__global__ __launch_bounds__(256) void hg_reduce_kernel(HgArgs a) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= HG_PART) return;
-    double s = a.P[idx];
-    for (int b = 1; b < a.B; ++b) s += a.P[(size_t)b * HG_PART + idx];
-    if (idx < HG_D * HG_D) { if (a.dW) a.dW[idx] = s; }
-    else if (a.db) a.db[idx - HG_D * HG_D] = s;
-}
-
 struct HgWs { double *md0, *md1, *dmd0, *dmd1, *P; size_t bytes; };
 HgWs hg_carve(void* base, int B, int N, int M) {
     HgWs w{};
@@ -300,12 +291,10 @@ int launch_match_head_backward_f64(int B, int N, int M, const double* desc0, con
     if (f0) if (int rc = hg_project(desc1, W, bias, w.md1, B * M, s)) return rc;
     HgArgs a{};
     a.B = B; a.N = N; a.M = M; a.G = dscores; a.desc0 = desc0; a.desc1 = desc1; a.W = W; a.md0 = w.md0; a.md1 = w.md1;
-    a.dmd0 = red ? w.dmd0 : nullptr; a.dmd1 = red ? w.dmd1 : nullptr; a.ddesc0 = ddesc0; a.ddesc1 = ddesc1; a.P = w.P; a.dW = dW; a.db = dbias;
+    a.dmd0 = red ? w.dmd0 : nullptr; a.dmd1 = red ? w.dmd1 : nullptr; a.ddesc0 = ddesc0; a.ddesc1 = ddesc1; a.P = w.P;
     if (f0) if (int rc = hg_launch_dmd<0>(a, s)) return rc;
     if (f1) if (int rc = hg_launch_dmd<1>(a, s)) return rc;
-    if (red) {
-        hipLaunchKernelGGL(hg_dw_kernel, dim3((unsigned)B, 4), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(hg_reduce_kernel, dim3((HG_PART + 255) / 256), dim3(256), 0, s, a);
-    }
-    return mdgat_check_hip(hipGetLastError(), "matching head backward launch");
+    if (!red) return mdgat_check_hip(hipGetLastError(), "matching head backward launch");
+    hipLaunchKernelGGL(hg_dw_kernel, dim3((unsigned)B, 4), dim3(256), 0, s, a);
+    return launch_dw_reduce_f64(w.P, B, HG_D * HG_D, HG_D, dW, dbias, s);
 }

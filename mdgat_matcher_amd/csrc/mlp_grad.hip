@@ -7,13 +7,16 @@
 // [C_l][C_in] as in the state_dict, out [R][C_L].  Per convolution l:
 //      Y_l = A_{l-1} W_l^T + b_l;   mean_c, var_c (biased) over the rows;   z = gamma (Y - mean) invstd + beta;   A_l = max(z, 0)
 // What is kept for the backward is Y_l of every BN layer and mean / invstd / a = gamma invstd per channel.  A_l is NEVER stored:
-// z = fma(Y - mean, a, beta) is recomputed where the next product loads its A operand (mg_gemm_bn_kernel), where dW loads its B
-// operand (mg_dw_kernel) and where the backward masks (mg_bnbwd_*) - the same instruction everywhere, so the sign of z is the same
-// everywhere.  torch keeps the convolution output, the BN output and the ReLU output of every layer.
+// z = fma(Y - mean, a, beta) is recomputed where the next product loads its A operand (gemm_f64_kernel, f64.hip), where dW loads its B
+// operand (dw_f64_kernel, dw_f64.hip) and where the backward masks (mg_bnbwd_*) - the same function everywhere (bn_z / bn_relu,
+// f64_dev.hpp), so the sign of z is the same everywhere.  torch keeps the convolution output, the BN output and the ReLU output of
+// every layer.
 //
-// Forward launches.  Layer 0 is the exact mode's launch_gemm_f64 (two sources, no transform); the layers behind a BN run
-// mg_gemm_bn_kernel, that kernel's tile loop (64 x 64 / 64 x 128 tiles, chunks of 32 through LDS, the next chunk in flight in
-// registers) with the normalisation and the ReLU between the global load and the LDS store.  Batch statistics: mg_stats_kernel gives
+// Forward launches.  Every product is the exact mode's launch_gemm_f64: layer 0 with its two sources, the layers behind a BN with
+// the operand transform (GemmF64Args::bn_*: the normalisation and the ReLU between the global load and the LDS store); tile width
+// and chunk depth are that launcher's.  A NaN in Y: this file honours NaNs, so it stays a NaN through the statistics and reaches
+// every value of the layer through mean and a; in the operand of the next product a NaN z counts as 0, under f64.hip's flags as
+// under this file's (bn_relu).  Batch statistics: mg_stats_kernel gives
 // every slab of 256 rows its column sums and, around the SLAB's mean, the centred sums of squares M2 (two passes over rows that are
 // in cache after the first); mg_stats_final_kernel combines the slabs in slab order by Chan's update
 //      delta = mean_b - mean;  mean += delta n_b / n;  M2 += M2_b + delta^2 n_a n_b / n
@@ -21,10 +24,8 @@
 // running statistics stand in and nothing is written to them.
 //
 // Backward, from the last convolution to the first (dY_L = dout):
-//   mg_dw_kernel      dW_l = dY_l^T A_{l-1} and db_l = colsum(dY_l) over a slab of 512 rows: both operands are contracted over their
-//                     ROWS, so both fragments are coalesced loads and there is no LDS (hg_dw_kernel's shape); a wave owns 32 x 32 of
-//                     dW, ONE chain per element inside the slab; the B operand is A_{l-1} recomputed from Y_{l-1} as it is loaded.
-//   mg_reduce_kernel  the slabs' partials added in slab order.
+//   launch_dw_f64     dW_l = dY_l^T A_{l-1} and db_l = colsum(dY_l) (dw_f64.hip): slabs of 512 rows, ONE chain per element inside a
+//                     slab, the B operand A_{l-1} recomputed from Y_{l-1} as it is loaded; the slabs' partials added in slab order.
 //   dA_{l-1} = dY_l W_l: launch_gemm_f64 on W_l transposed into the workspace (mg_transpose_kernel; a weight is at most 2 MB); at
 //                     the first layer one launch per source writes dx0 / dx1 from the two row ranges of the transposed weight.
 //   mg_bnbwd_partial_kernel / _final_kernel   dz = dA [z > 0]; dbeta = colsum(dz), dgamma = colsum(dz yhat): slabs of 256 rows, their
@@ -41,131 +42,6 @@ namespace {
 
 constexpr int MG_SLAB = 256;        // rows per partial of a column statistic (mean / M2, dbeta / dgamma)
 constexpr int MG_DW_SLAB = 512;     // rows per partial of dW / db
-constexpr int MG_BM = 64, MG_KC = 32, MG_LD = MG_KC + 2;      // gemm_f64_kernel's tile: row pitch 34 doubles
-
-// the one place z is formed: every kernel that needs z or its sign calls this
-__device__ __forceinline__ double bn_z(double y, double mean, double a, double beta) { return __builtin_fma(y - mean, a, beta); }
-__device__ __forceinline__ double bn_relu(double y, double mean, double a, double beta) {
-    const double z = bn_z(y, mean, a, beta);
-    return z > 0.0 ? z : 0.0;
-}
-
-// ================================================================================================ forward product behind a BN
-struct MgGemmArgs {
-    const double* Y; int K;            // [M][K]: the previous convolution's output
-    const double *mean, *a, *beta;     // [K] each: its BN
-    const double* W;                   // [N][K]
-    const double* bias;                // [N]
-    double* C;                         // [M][N]
-    int M, N;
-};
-
-// FAST: whole tiles, K a multiple of 32, W 16-byte aligned: 16-byte loads without predicates (as gemm_f64_kernel's)
-template <int WN, bool FAST>
-__global__ __launch_bounds__(256) void mg_gemm_bn_kernel(MgGemmArgs p) {
-    constexpr int BN = 32 * WN;
-    extern __shared__ __attribute__((aligned(16))) double mg_lds[];
-    double* As = mg_lds;                      // [64][MG_LD]
-    double* Ws = mg_lds + MG_BM * MG_LD;      // [BN][MG_LD]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, g = lane >> 4;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int row0 = blockIdx.x * MG_BM, col0 = blockIdx.y * BN;
-    constexpr int NA = MG_BM * MG_KC / 256, NW = BN * MG_KC / 256;
-    double ra[NA], rw[NW];
-    auto fetch = [&](int k0) {
-        if (FAST) {
-            const int kk = k0 + (tid & 15) * 2;          // this thread's two channels of the chunk: the same for every row it loads
-            const double m0 = p.mean[kk], m1 = p.mean[kk + 1], a0 = p.a[kk], a1 = p.a[kk + 1], b0 = p.beta[kk], b1 = p.beta[kk + 1];
-#pragma unroll
-            for (int u = 0; u < NA / 2; ++u) {
-                const int r = (tid + 256 * u) >> 4;
-                const f64x2 v = *reinterpret_cast<const f64x2*>(p.Y + (size_t)(row0 + r) * p.K + kk);
-                ra[2 * u] = bn_relu(v[0], m0, a0, b0); ra[2 * u + 1] = bn_relu(v[1], m1, a1, b1);
-            }
-#pragma unroll
-            for (int u = 0; u < NW / 2; ++u) {
-                const int r = (tid + 256 * u) >> 4;
-                const f64x2 v = *reinterpret_cast<const f64x2*>(p.W + (size_t)(col0 + r) * p.K + kk);
-                rw[2 * u] = v[0]; rw[2 * u + 1] = v[1];
-            }
-            return;
-        }
-        const int kk = k0 + (tid & 31);
-        const bool ink = kk < p.K;
-        const double m = ink ? p.mean[kk] : 0.0, aa = ink ? p.a[kk] : 0.0, bb = ink ? p.beta[kk] : 0.0;
-#pragma unroll
-        for (int u = 0; u < NA; ++u) {
-            const int row = row0 + ((tid + 256 * u) >> 5);
-            ra[u] = (ink && row < p.M) ? bn_relu(p.Y[(size_t)row * p.K + kk], m, aa, bb) : 0.0;       // (beyond the tile: 0, not max(beta, 0))
-        }
-#pragma unroll
-        for (int u = 0; u < NW; ++u) {
-            const int n = col0 + ((tid + 256 * u) >> 5);
-            rw[u] = (ink && n < p.N) ? p.W[(size_t)n * p.K + kk] : 0.0;
-        }
-    };
-    auto stash = [&]() {
-        if (FAST) {
-#pragma unroll
-            for (int u = 0; u < NA / 2; ++u) { const int idx = tid + 256 * u; *reinterpret_cast<f64x2*>(As + (idx >> 4) * MG_LD + (idx & 15) * 2) = f64x2{ra[2 * u], ra[2 * u + 1]}; }
-#pragma unroll
-            for (int u = 0; u < NW / 2; ++u) { const int idx = tid + 256 * u; *reinterpret_cast<f64x2*>(Ws + (idx >> 4) * MG_LD + (idx & 15) * 2) = f64x2{rw[2 * u], rw[2 * u + 1]}; }
-            return;
-        }
-#pragma unroll
-        for (int u = 0; u < NA; ++u) { const int idx = tid + 256 * u; As[(idx >> 5) * MG_LD + (idx & 31)] = ra[u]; }
-#pragma unroll
-        for (int u = 0; u < NW; ++u) { const int idx = tid + 256 * u; Ws[(idx >> 5) * MG_LD + (idx & 31)] = rw[u]; }
-    };
-    f64x4 acc[2][WN];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
-    fetch(0);
-    stash();
-    __syncthreads();
-    const double* ap = As + (wm * 32 + l15) * MG_LD + g;
-    const double* wp = Ws + (wn * 16 * WN + l15) * MG_LD + g;
-    for (int k0 = 0; k0 < p.K; k0 += MG_KC) {
-        const bool more = k0 + MG_KC < p.K;
-        if (more) fetch(k0 + MG_KC);
-        const int rem = p.K - k0;
-        const int steps = rem >= MG_KC ? MG_KC / 4 : (rem + 3) >> 2;
-        for (int j = 0; j < steps; ++j) {
-            double fa[2], fw[WN];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = ap[i * 16 * MG_LD + 4 * j];
-#pragma unroll
-            for (int i = 0; i < WN; ++i) fw[i] = wp[i * 16 * MG_LD + 4 * j];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int n = 0; n < WN; ++n) acc[i][n] = mfma64(fa[i], fw[n], acc[i][n]);
-        }
-        if (more) {
-            __syncthreads();
-            stash();
-            __syncthreads();
-        }
-    }
-    // D: lane (column l15, g), register i -> row g + 4 i of the 16 x 16 block
-#pragma unroll
-    for (int nb = 0; nb < WN; ++nb) {
-        const int n = col0 + wn * 16 * WN + nb * 16 + l15;
-        if (n >= p.N) continue;
-        const double bias = p.bias[n];
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = row0 + wm * 32 + mb * 16 + g + 4 * i;
-                if (row < p.M) p.C[(size_t)row * p.N + n] = acc[mb][nb][i] + bias;
-            }
-    }
-}
-
 // ================================================================================================ batch statistics
 // a workgroup: 64 columns x one slab of rows; wave q walks rows q, q + 4, ...; the four waves are combined as (0 + 1) + (2 + 3)
 __device__ __forceinline__ double mg_quarters(double (*red)[64], double v, int q, int l) {
@@ -291,113 +167,6 @@ __global__ __launch_bounds__(256) void mg_bnbwd_apply_kernel(MgBnBwdArgs p) {
     }
 }
 
-// ================================================================================================ dW, db
-struct MgDwArgs {
-    const double* dY; int Cout;                     // [R][Cout]
-    const double* x0; int K0;                       // the convolution's input: [R][K0] | [R][K1]; behind a BN: x0 = Y_{l-1}
-    const double* x1; int K1;
-    const double *mean, *a, *beta;                  // the BN between (A = max(z, 0) is formed as it is loaded), or nullptr
-    int R;
-    double* P;                                      // [slabs][Cout (K0 + K1) + Cout]
-    int want_w;                                     // 0: only db is wanted - the waves of the first column tile add up their A fragments, no product is formed
-};
-__global__ __launch_bounds__(256) void mg_dw_kernel(MgDwArgs p) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l15 = lane & 15, g = lane >> 4;
-    const int Cin = p.K0 + p.K1, Cout = p.Cout;
-    const int tn = (Cin + 31) >> 5, tm = (Cout + 31) >> 5;
-    const int id = blockIdx.y * 4 + wave;
-    if (id >= tm * tn) return;
-    const int rt = id / tn, ct = id % tn;
-    const bool prod = p.want_w != 0;
-    if (!prod && ct != 0) return;
-    const int r0 = blockIdx.x * MG_DW_SLAB, cnt = min(MG_DW_SLAB, p.R - r0);
-    // A: row = output channel (l15), k = point (g); Cout is a multiple of 16: the first half of the 32 always exists
-    const bool oka1 = rt * 32 + 16 < Cout;
-    const double* ap = p.dY + (size_t)(r0 + g) * Cout + rt * 32 + l15;
-    // B: k = point, column = input channel
-    const double* bp[2] = {nullptr, nullptr};
-    int ldb[2] = {0, 0};
-    bool okb[2];
-    double mu[2] = {0.0, 0.0}, aa[2] = {0.0, 0.0}, be[2] = {0.0, 0.0};
-    const bool bn = p.mean != nullptr;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ci = ct * 32 + h * 16 + l15;
-        okb[h] = prod && ci < Cin;
-        if (!okb[h]) continue;
-        const bool first = ci < p.K0;
-        ldb[h] = first ? p.K0 : p.K1;
-        bp[h] = (first ? p.x0 + ci : p.x1 + (ci - p.K0)) + (size_t)(r0 + g) * ldb[h];
-        if (bn) { mu[h] = p.mean[ci]; aa[h] = p.a[ci]; be[h] = p.beta[ci]; }
-    }
-    auto ldA = [&](int r, int h, bool in) -> double { return (in && (h == 0 || oka1)) ? ap[(size_t)r * Cout + h * 16] : 0.0; };
-    auto ldB = [&](int r, int h, bool in) -> double {
-        if (!(in && okb[h])) return 0.0;
-        const double v = bp[h][(size_t)r * ldb[h]];
-        return bn ? bn_relu(v, mu[h], aa[h], be[h]) : v;
-    };
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[r][c] = f64x4{0.0, 0.0, 0.0, 0.0};
-    double s0 = 0.0, s1 = 0.0;
-    auto step = [&](double a0, double a1, double b0, double b1) {
-        if (prod) {
-            acc[0][0] = mfma64(a0, b0, acc[0][0]);
-            acc[0][1] = mfma64(a0, b1, acc[0][1]);
-            acc[1][0] = mfma64(a1, b0, acc[1][0]);
-            acc[1][1] = mfma64(a1, b1, acc[1][1]);
-        }
-        s0 += a0;
-        s1 += a1;
-    };
-    int r = 0;
-    for (; r + 16 <= cnt; r += 16) {          // sixteen loads in flight in front of sixteen products
-        double fa[4][2], fb[4][2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            fa[u][0] = ldA(r + 4 * u, 0, true); fa[u][1] = ldA(r + 4 * u, 1, true);
-            fb[u][0] = ldB(r + 4 * u, 0, true); fb[u][1] = ldB(r + 4 * u, 1, true);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) step(fa[u][0], fa[u][1], fb[u][0], fb[u][1]);
-    }
-    for (; r < cnt; r += 4) {
-        const bool in = r + g < cnt;
-        step(ldA(r, 0, in), ldA(r, 1, in), ldB(r, 0, in), ldB(r, 1, in));
-    }
-    double* Pp = p.P + (size_t)blockIdx.x * ((size_t)Cout * Cin + Cout);
-    if (prod)
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int co = rt * 32 + rr * 16 + g + 4 * i, ci = ct * 32 + c * 16 + l15;
-                if (co < Cout && ci < Cin) Pp[(size_t)co * Cin + ci] = acc[rr][c][i];
-            }
-    // db: the four quarters of the rows (k = g) as (0 + 1) + (2 + 3)
-    s0 = quad_sum(s0);
-    s1 = quad_sum(s1);
-    if (ct == 0 && g == 0) {
-        Pp[(size_t)Cout * Cin + rt * 32 + l15] = s0;
-        if (oka1) Pp[(size_t)Cout * Cin + rt * 32 + 16 + l15] = s1;
-    }
-}
-
-struct MgReduceArgs { const double* P; int slabs; int nW, nb; double *dW, *db; };      // dW == nullptr: the grid covers db alone
-__global__ __launch_bounds__(256) void mg_reduce_kernel(MgReduceArgs p) {
-    const int idx = blockIdx.x * 256 + threadIdx.x + (p.dW ? 0 : p.nW), part = p.nW + p.nb;
-    if (idx >= part) return;
-    double s = p.P[idx];
-    for (int b = 1; b < p.slabs; ++b) s += p.P[(size_t)b * part + idx];
-    if (idx < p.nW) { if (p.dW) p.dW[idx] = s; }
-    else if (p.db) p.db[idx - p.nW] = s;
-}
-
 // Wt [K][N] = W [N][K]^T
 __global__ __launch_bounds__(256) void mg_transpose_kernel(const double* W, double* Wt, int N, int K) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -445,21 +214,6 @@ MgWs mg_carve_ws(void* base, const mdgat_mlp_desc& d) {
     return w;
 }
 
-int mg_launch_gemm_bn(const MgGemmArgs& a, hipStream_t s) {
-    static std::atomic<unsigned long long> d2{0}, d4{0}, d2f{0}, d4f{0};
-    const int wn = a.N % 128 == 0 ? 4 : 2, bn = 32 * wn;
-    const bool fast = a.M % MG_BM == 0 && a.N % bn == 0 && a.K % MG_KC == 0 && (reinterpret_cast<uintptr_t>(a.W) & 15) == 0;
-    const size_t lds = (size_t)(MG_BM + bn) * MG_LD * sizeof(double);
-    const dim3 grid((a.M + MG_BM - 1) / MG_BM, (a.N + bn - 1) / bn);
-    auto go = [&](auto kern, std::atomic<unsigned long long>& done) -> int {
-        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "mlp forward LDS")) return rc;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
-        return MDGAT_OK;
-    };
-    if (wn == 4) return fast ? go(mg_gemm_bn_kernel<4, true>, d4f) : go(mg_gemm_bn_kernel<4, false>, d4);
-    return fast ? go(mg_gemm_bn_kernel<2, true>, d2f) : go(mg_gemm_bn_kernel<2, false>, d2);
-}
-
 }  // namespace
 
 size_t mlp_f64_saved_bytes(const mdgat_mlp_desc& d) { return mg_carve_saved(nullptr, d).bytes; }
@@ -472,14 +226,12 @@ int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const doub
     for (int l = 0; l < d.n_conv; ++l) {
         const int N = d.C[l], K = mg_cin(d, l);
         double* dst = l + 1 == d.n_conv ? out : sv.Y[l];
-        if (l == 0) {
-            const GemmF64Args g{x0, d.K0, d.K0, d.K1 > 0 ? x1 : nullptr, d.K1, d.W[0], K, d.bias[0], nullptr, 0, dst, N, R, N, K, 0, nullptr};
-            if (int rc = launch_gemm_f64(g, s)) return rc;
-        } else {
-            const double* S = sv.S[l - 1];
-            const MgGemmArgs g{sv.Y[l - 1], K, S, S + 2 * K, d.beta[l - 1], d.W[l], d.bias[l], dst, R, N};
-            if (int rc = mg_launch_gemm_bn(g, s)) return rc;
+        GemmF64Args g{x0, d.K0, d.K0, d.K1 > 0 ? x1 : nullptr, d.K1, d.W[l], K, d.bias[l], nullptr, 0, dst, N, R, N, K, 0, nullptr};
+        if (l > 0) {               // behind a BN: A = max(z, 0) of the previous convolution's output, formed as the operand is loaded
+            g.A0 = sv.Y[l - 1]; g.lda0 = g.K0 = K; g.A1 = nullptr; g.lda1 = 0;
+            g.bn_mean = sv.S[l - 1]; g.bn_a = sv.S[l - 1] + 2 * K; g.bn_beta = d.beta[l - 1];
         }
+        if (int rc = launch_gemm_f64(g, s)) return rc;
         if (l + 1 == d.n_conv) break;
         if (d.training) {
             const MgStatArgs st{dst, R, N, sv.P};
@@ -509,13 +261,11 @@ int launch_mlp_backward_f64(const mdgat_mlp_desc& d, const double* x0, const dou
     for (int l = L - 1; l >= 0; --l) {
         const int N = d.C[l], K = mg_cin(d, l);
         if (g.dW[l] || g.dbias[l]) {
+            // the convolution's input: x0 | x1, or behind a BN A_{l-1} recomputed from Y_{l-1} as it is loaded
             const double* S = l > 0 ? sv.S[l - 1] : nullptr;
-            const MgDwArgs a{dY, N, l > 0 ? sv.Y[l - 1] : x0, l > 0 ? K : d.K0, l > 0 ? nullptr : x1, l > 0 ? 0 : d.K1,
-                             S, S ? S + 2 * K : nullptr, l > 0 ? d.beta[l - 1] : nullptr, R, ws.Pw, g.dW[l] != nullptr};
-            const int slabs = mg_slabs(R, MG_DW_SLAB), waves = ((N + 31) / 32) * ((K + 31) / 32);
-            hipLaunchKernelGGL(mg_dw_kernel, dim3((unsigned)slabs, (unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
-            const MgReduceArgs r{ws.Pw, slabs, N * K, N, g.dW[l], g.dbias[l]};
-            hipLaunchKernelGGL(mg_reduce_kernel, dim3((unsigned)(((g.dW[l] ? N * K : 0) + N + 255) / 256)), dim3(256), 0, s, r);
+            const DwF64Args a{dY, N, l > 0 ? sv.Y[l - 1] : x0, l > 0 ? K : d.K0, l > 0 ? nullptr : x1, l > 0 ? 0 : d.K1,
+                              S, S ? S + 2 * K : nullptr, l > 0 ? d.beta[l - 1] : nullptr, R, MG_DW_SLAB, ws.Pw, g.dW[l], g.dbias[l]};
+            if (int rc = launch_dw_f64(a, s)) return rc;
         }
         if (!below[l]) break;
         hipLaunchKernelGGL(mg_transpose_kernel, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, s, d.W[l], ws.Wt, N, K);

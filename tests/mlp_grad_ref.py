@@ -53,7 +53,7 @@ U = 2.0 ** -53
 GOLDEN_FILES = {'kenc': ('mlp_grad_kenc',), 'denc': ('mlp_grad_denc',), 'denc_eval': ('mlp_grad_denc_eval',),
                 'layer': ('mlp_grad_layer_inputs', 'mlp_grad_layer_grads')}
 ALL_FILES = tuple(f for fs in GOLDEN_FILES.values() for f in fs)
-STACKS = {'kenc': (4, 32, 64, 128, 128), 'denc': (33, 64, 128, 128), 'layer': (256, 256, 128), 'conv128': (128, 128), 'conv384': (128, 384)}
+STACKS = {'kenc': (4, 32, 64, 128, 128), 'denc': (33, 64, 128, 128), 'layer': (256, 256, 128), 'conv128': (128, 128), 'conv384': (128, 384), 'ragged': (8, 48, 80, 16)}
 
 
 _DT = [np.float64]
@@ -264,7 +264,7 @@ def compare_grads(got, want, tol):
 
 # ---- the seeded inputs of the GPU tests (tests/test_gpu_mlp_grad.py), checked for the ReLU condition on the CPU ----
 GPU_ROWS = (2, 17, 64, 65, 1000, 1024)
-GPU_STACKS = ('kenc', 'denc', 'layer', 'conv128', 'conv384')
+GPU_STACKS = ('kenc', 'denc', 'layer', 'conv128', 'conv384', 'ragged')
 
 
 def gpu_case(stack, R, seed=None):

@@ -126,7 +126,7 @@ def test_kernel_agrees_with_restatement(stack):
         assert worst <= 1.0
 
 
-@pytest.mark.parametrize('stack', ['kenc', 'denc', 'layer'])
+@pytest.mark.parametrize('stack', ['kenc', 'denc', 'layer', 'ragged'])
 def test_eval_mode(stack):
     for rows in (17, 1000):
         worst, _, _ = _against_restatement(stack, rows, training=False)

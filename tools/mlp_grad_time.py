@@ -2,7 +2,8 @@
 """GPU box: forward + backward of the training-mode MLP through ops.mlp_f64 (csrc/mlp_grad.hip) next to what a user has without it:
 torch autograd of the same nn.Sequential on the same device in float64.  R = 64 x 512 rows (the rows of one frame of configs[1]), the
 three BN stacks (kenc 4-32-64-128-128, denc 33-64-128-128, layer 128+128-256-128 with two sources) and the bare 128 -> 384
-convolution: the median over windows of HIP-event time per call, after warm-up, and the peak of torch.cuda.max_memory_allocated above
+convolution: the median over windows of HIP-event time per call, after warm-up (also of the forward and the backward alone,
+ops.mlp_f64_forward / ops.mlp_f64_backward with every gradient asked for), and the peak of torch.cuda.max_memory_allocated above
 the inputs for both.  One JSON line per stack, with the ratios the conditions of DESIGN section 7.7 are stated on.
 
     python tools/mlp_grad_time.py [--windows 7] [--per-window 3] [--rows 32768]
@@ -82,7 +83,11 @@ def main():
             for s in srcs:
                 s.grad = None
 
+        raw = [t.detach() for t in srcs] + [None] * (2 - len(srcs))
+        saved = ops.mlp_f64_forward(mod, *raw)[1]
         rec = {'stack': stack, 'rows': args.rows,
+               'forward_ms': round(median_ms(lambda: ops.mlp_f64_forward(mod, *raw), args.windows, args.per_window), 4),
+               'backward_ms': round(median_ms(lambda: ops.mlp_f64_backward(mod, *raw, saved, g), args.windows, args.per_window), 4),
                'mlp_f64_ms': round(median_ms(ours, args.windows, args.per_window), 4),
                'torch_ms': round(median_ms(theirs, args.windows, args.per_window), 4)}
         clear()
