@@ -444,6 +444,12 @@ typedef struct {
  * loads its A operand.  Asynchronous on `stream`. */
 int mdgat_mlp_forward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, double* out, void* saved, size_t saved_bytes,
                           void* stream);
+/* The same forward with out = Y_L + residual: residual [R][C[n_conv - 1]] (contiguous, not NULL; may alias out) is added in the last
+ * product's epilogue - the layer's desc + delta (mdgat.py:274) and the encoders' denc(...) + kenc(...) (392-393) without a launch of
+ * their own.  `saved` is what mdgat_mlp_forward_f64 leaves; the backward is mdgat_mlp_backward_f64 unchanged, and dout is the
+ * residual's gradient as it stands. */
+int mdgat_mlp_forward_residual_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, const double* residual, double* out,
+                                   void* saved, size_t saved_bytes, void* stream);
 /* Backward: the forward's descriptor, inputs and `saved` (with its size), and dout = dL/dout [R][C[n_conv - 1]] (contiguous).  From the last
  * convolution to the first: db = colsum(dY), dW = dY^T A, dA = dY W, dz = dA [z > 0] (zero is not positive), dbeta = colsum(dz),
  * dgamma = colsum(dz yhat), dY = gamma invstd (dz - dbeta / R - yhat dgamma / R) (training == 0: gamma invstd dz).  The sums over the

@@ -143,6 +143,8 @@ SIGNATURES = {
     'mdgat_match_head_backward': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]),
     'mdgat_match_head_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_mlp_forward_f64': (C.c_int, [C.POINTER(MdgatMlpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_mlp_forward_residual_f64': (C.c_int, [C.POINTER(MdgatMlpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
     'mdgat_mlp_backward_f64': (C.c_int, [C.POINTER(MdgatMlpDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(MdgatMlpGrads),
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_mlp_workspace_bytes': (C.c_size_t, [C.POINTER(MdgatMlpDesc), C.c_int]),

@@ -1058,6 +1058,17 @@ extern "C" int mdgat_mlp_forward_f64(const mdgat_mlp_desc* d, const double* x0, 
     return launch_mlp_forward_f64(*d, x0, x1, out, saved, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int mdgat_mlp_forward_residual_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, const double* residual, double* out,
+                                              void* saved, size_t saved_bytes, void* stream) {
+    const char* who = "mdgat_mlp_forward_residual_f64";
+    if (int rc = mlp_shape(who, d)) return rc;
+    if (d->R == 0) return MDGAT_OK;
+    if (int rc = mlp_pointers(who, d, x0, x1)) return rc;
+    if (!out || !residual) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = grad_buffer(who, "saved", saved, saved_bytes, mlp_f64_saved_bytes(*d))) return rc;
+    return launch_mlp_forward_f64(*d, x0, x1, out, saved, static_cast<hipStream_t>(stream), residual);
+}
+
 extern "C" int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0, const double* x1, const void* saved, size_t saved_bytes,
                                       const double* dout, const mdgat_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "mdgat_mlp_backward_f64";

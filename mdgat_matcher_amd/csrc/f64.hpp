@@ -122,6 +122,7 @@ int launch_attention_backward_f64(int B, int N, int M, int cross, int topk, cons
 // the backward's own (mlp_f64_backward_workspace_bytes), both 256-byte aligned
 size_t mlp_f64_saved_bytes(const mdgat_mlp_desc& d);
 size_t mlp_f64_backward_workspace_bytes(const mdgat_mlp_desc& d);
-int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, double* out, void* saved, hipStream_t s);
+int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, double* out, void* saved, hipStream_t s,
+                           const double* residual = nullptr);      // residual [R][C_L] contiguous or nullptr (may alias out)
 int launch_mlp_backward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, const void* saved, const double* dout,
                             const mdgat_mlp_grads& g, void* workspace, hipStream_t s);

@@ -219,7 +219,8 @@ MgWs mg_carve_ws(void* base, const mdgat_mlp_desc& d) {
 size_t mlp_f64_saved_bytes(const mdgat_mlp_desc& d) { return mg_carve_saved(nullptr, d).bytes; }
 size_t mlp_f64_backward_workspace_bytes(const mdgat_mlp_desc& d) { return mg_carve_ws(nullptr, d).bytes; }
 
-int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, double* out, void* saved, hipStream_t s) {
+int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const double* x1, double* out, void* saved, hipStream_t s,
+                           const double* residual) {
     if (d.R <= 0) return MDGAT_OK;
     const MgSaved sv = mg_carve_saved(saved, d);
     const int R = d.R;
@@ -231,6 +232,7 @@ int launch_mlp_forward_f64(const mdgat_mlp_desc& d, const double* x0, const doub
             g.A0 = sv.Y[l - 1]; g.lda0 = g.K0 = K; g.A1 = nullptr; g.lda1 = 0;
             g.bn_mean = sv.S[l - 1]; g.bn_a = sv.S[l - 1] + 2 * K; g.bn_beta = d.beta[l - 1];
         }
+        if (l + 1 == d.n_conv && residual) { g.R = residual; g.ldr = N; }       // out = Y_L + residual, added in the last product's epilogue
         if (int rc = launch_gemm_f64(g, s)) return rc;
         if (l + 1 == d.n_conv) break;
         if (d.training) {

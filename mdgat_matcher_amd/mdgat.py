@@ -19,8 +19,9 @@ Host-side mirror of ``/root/reference/models/mdgat.py:315-603`` (class ``MDGAT``
   results are cast to the module's dtype either way.
 
 All arithmetic happens in ``libmdgat_hip.so``; PyTorch only owns device memory and streams.  There is no
-CPU path: tensors that are not on a gfx950 device raise.  Training (backward) is out of scope: ``train()`` mode raises in
-``forward``.  The loss VALUE is what the reference's validation loop reads (``train.py:263-299``): with ``config['eval_loss']``
+CPU path: tensors that are not on a gfx950 device raise.  Training: ``training_forward`` (``train.py``) is the differentiable fp64
+forward; ``forward`` in ``train()`` mode returns it with ``config['train_forward']`` (or ``MDGAT_TRAIN_FORWARD=1``) and raises
+otherwise.  The loss VALUE is what the reference's validation loop reads (``train.py:263-299``): with ``config['eval_loss']``
 (or ``MDGAT_EVAL_LOSS=1``) ``forward`` computes it on the device (``csrc/loss.hip``); otherwise ``loss`` is a zero scalar.
 """
 from __future__ import annotations
@@ -175,6 +176,10 @@ class MDGAT(nn.Module):
         # MDGAT_EVAL_LOSS=1 in the environment replaces the default (off) for modules whose config does not carry the key.
         ev = self.config.get('eval_loss')
         self.eval_loss = bool(ev) if ev is not None else os.environ.get('MDGAT_EVAL_LOSS') == '1'
+        # not a reference key: in train() mode forward returns training_forward(data) - the differentiable fp64 step (train.py) - instead of
+        # raising.  MDGAT_TRAIN_FORWARD=1 in the environment replaces the default (off) for modules whose config does not carry the key.
+        tf = self.config.get('train_forward')
+        self.train_forward = bool(tf) if tf is not None else os.environ.get('MDGAT_TRAIN_FORWARD') == '1'
         f64_layers = self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -425,6 +430,8 @@ class MDGAT(nn.Module):
                 'matching_scores1': kpts1.new_zeros(shape1, dtype=torch.float64)[0],
                 'skip_train': True,
             }
+        if self.training and getattr(self, 'train_forward', False):
+            return self.training_forward(data)
         if self.training:
             raise NotImplementedError('mdgat_matcher_amd implements inference only: call .eval() (training, the '
                                       'losses of mdgat.py:486-594 and backward are out of scope)')
@@ -455,6 +462,26 @@ class MDGAT(nn.Module):
             'matching_scores1': s1,
             'loss': loss,
         }
+
+    def training_forward(self, data):
+        """The reference's forward (mdgat.py:369-603, descriptor='FPFH') in fp64 with BatchNorm as ``self.training`` says, composed from the
+        differentiable device primitives (``mdgat_matcher_amd/train.py``): the reference's dict, whose ``loss`` (0-d for superglue /
+        triplet, [B] for gap) carries a grad_fn whenever grad is enabled and a parameter requires grad, so ``loss.mean().backward()``
+        fills the ``.grad`` of this module's own parameters.  In train() mode the BatchNorm buffers move as the reference's do (every
+        encoder once per frame, every layer's MLP for frame 0 and then frame 1); in eval() mode they are read and left alone.  Matches
+        and loss come from the same Z.  Needs a float64 module on one gfx950 device; CPU tensors raise RuntimeError (no CPU fallback), a
+        DataParallel replica NotImplementedError.  The parameters are read from the modules on every call, never from the packed
+        weights; the packed weights are dropped (train() mode: always, the buffers move; eval() mode: when a parameter changed in place
+        since the last look), but an ``optimizer.step()`` AFTER the last call is seen by nobody: call ``repack()`` before an ``eval()``
+        ``forward``.  ``forward`` calls this in train() mode when ``config['train_forward']`` (or
+        ``MDGAT_TRAIN_FORWARD=1``) is set."""
+        from . import train
+        if 'bin_score' in self._parameters:
+            if self.training:
+                self._invalidate()              # the kernels move the BatchNorm buffers behind autograd's version counters
+            else:
+                self._invalidate_if_changed()   # in-place optimizer updates since the last call: the packed weights are stale
+        return train.training_forward(self, data)
 
     def evaluate(self, data):
         """``forward(data)`` and then the evaluation scripts' per-pair record (test.py:212-296, test_registration_metric.py:213-264) of

@@ -922,11 +922,17 @@ def _mlp_split(seq):
     return ws, bs, gammas, betas, bufs, [b.eps for b in bns], [b.momentum for b in bns], training
 
 
-def _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training):
+def _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training, residual=None):
     r0, r1, lead = _mlp_rows(x, x1, ws[0].shape[1])
     rows, cout = r0.shape[0], ws[-1].shape[0]
     if rows == 1 and training and gammas:
         raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
+    res = None
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float64 or residual.device != r0.device or \
+                tuple(residual.shape) != lead + (cout,):
+            raise ValueError(f'mlp_f64: residual must be float64 {lead + (cout,)} on {r0.device}')
+        res = residual.detach().reshape(-1, cout).contiguous()
     out = torch.empty((rows, cout), dtype=torch.float64, device=r0.device)
     if rows == 0:
         return out.reshape(*lead, cout), MlpSaved(None, 0, 0, training, 0)
@@ -934,8 +940,12 @@ def _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training):
     lib = _lib.load()
     with torch.cuda.device(r0.device):
         buf, base, need = _mlp_buffer(lib, d, 0, r0.device)
-        _lib.check(lib.mdgat_mlp_forward_f64(C.byref(d), r0.data_ptr(), None if r1 is None else r1.data_ptr(), out.data_ptr(), base, need,
-                                             _stream(r0)), 'mdgat_mlp_forward_f64')
+        if res is not None:
+            _lib.check(lib.mdgat_mlp_forward_residual_f64(C.byref(d), r0.data_ptr(), None if r1 is None else r1.data_ptr(), res.data_ptr(),
+                                                          out.data_ptr(), base, need, _stream(r0)), 'mdgat_mlp_forward_residual_f64')
+        else:
+            _lib.check(lib.mdgat_mlp_forward_f64(C.byref(d), r0.data_ptr(), None if r1 is None else r1.data_ptr(), out.data_ptr(), base, need,
+                                                 _stream(r0)), 'mdgat_mlp_forward_f64')
     del keep
     return out.reshape(*lead, cout), MlpSaved(buf, base, need, training, rows)
 
@@ -1037,3 +1047,66 @@ def mlp_f64(seq, x: torch.Tensor, x1: torch.Tensor = None) -> torch.Tensor:
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
         return _MlpF64.apply((len(ws), len(gammas), bufs, eps, momentum, training), x, x1, *params)
     return _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training)[0]
+
+
+class _MlpTensorsF64(torch.autograd.Function):
+    """``_MlpF64`` with a residual operand: out = mlp(x | x1) + residual; dout reaches the residual unchanged."""
+
+    @staticmethod
+    def forward(ctx, meta, x, x1, residual, *params):
+        n, nb, bufs, eps, momentum, training = meta
+        ws, bs, gammas, betas = params[:n], params[n:2 * n], params[2 * n:2 * n + nb], params[2 * n + nb:]
+        out, saved = _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training, residual)
+        ctx.meta, ctx.saved = meta, saved
+        ctx.save_for_backward(x, x1, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        n, nb, bufs, eps, momentum, _ = ctx.meta
+        x, x1, *params = ctx.saved_tensors
+        ws, bs, gammas, betas = params[:n], params[n:2 * n], params[2 * n:2 * n + nb], params[2 * n + nb:]
+        want = ctx.needs_input_grad
+        p = want[4:]
+        need = (want[1], want[2], p[:n], p[n:2 * n], p[2 * n:2 * n + nb], p[2 * n + nb:])
+        dx, dx1, dW, db, dga, dbe = _mlp_backward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, ctx.saved, dout, need)
+        return (None, dx, dx1, dout if want[3] else None, *dW, *db, *dga, *dbe)
+
+
+def mlp_f64_tensors(x: torch.Tensor, weights, biases, bns=(), training: bool = True, x1: torch.Tensor = None,
+                    residual: torch.Tensor = None) -> torch.Tensor:
+    """``mlp_f64`` on weight TENSORS instead of modules, with an optional residual: the entry of a caller whose weights are computed
+    (rows or columns of a module's weight gathered into another channel order, several convolutions' weights stacked into one product)
+    and must stay in the autograd graph.  ``weights`` [C_l, C_in] or [C_l, C_in, 1] and ``biases`` [C_l], float64 on the device, one per
+    convolution; ``bns``: the ``nn.BatchNorm1d`` between them (one fewer; gamma, beta and the buffers are read from the modules, the
+    buffers move when ``training``).  ``residual`` [..., C_L] is added to the output in the last product's epilogue - out = mlp(x | x1) +
+    residual, the layer's ``desc + delta`` (mdgat.py:274) and the encoders' ``denc(...) + kenc(...)`` (392-393) - and receives dout
+    unchanged in the backward.  Everything else is ``mlp_f64``: the same launches, the same bits, the same limits."""
+    ws, bs, bns = list(weights), list(biases), list(bns)
+    if not ws or len(bs) != len(ws) or len(bns) != len(ws) - 1 or len(ws) > _lib.MLP_MAX_CONVS:
+        raise ValueError(f'mlp_f64_tensors: {len(ws)} weights, {len(bs)} biases, {len(bns)} BatchNorm1d: expected 1 to {_lib.MLP_MAX_CONVS} '
+                         'convolutions with one BatchNorm1d between each two')
+    for w, b in zip(ws, bs):
+        if not isinstance(w, torch.Tensor) or w.dim() not in (2, 3) or (w.dim() == 3 and w.shape[2] != 1) or tuple(b.shape) != (w.shape[0],):
+            raise ValueError('mlp_f64_tensors: weights are [C_out, C_in] or [C_out, C_in, 1], biases [C_out]')
+        if w.shape[0] % 16 or not 16 <= w.shape[0] <= 512:
+            raise ValueError(f'mlp_f64: {w.shape[0]} output channels: the kernels take multiples of 16 up to 512')
+    for a, b in zip(ws[:-1], ws[1:]):
+        if b.shape[1] != a.shape[0]:
+            raise ValueError(f'mlp_f64_tensors: a weight {tuple(b.shape)} does not follow {tuple(a.shape)}')
+    for w, b in zip(ws[:-1], bns):
+        if not isinstance(b, torch.nn.BatchNorm1d) or b.num_features != w.shape[0] or not b.affine or not b.track_running_stats or \
+                b.momentum is None or b.running_mean is None or (training and b.num_batches_tracked is None):
+            raise ValueError('mlp_f64_tensors: a BatchNorm1d with affine parameters, running statistics and a momentum is expected '
+                             'behind every convolution but the last')
+    if not 1 <= ws[0].shape[1] <= 512:
+        raise ValueError(f'mlp_f64: {ws[0].shape[1]} input channels: the kernels take 1 to 512')
+    gammas, betas = [b.weight for b in bns], [b.bias for b in bns]
+    bufs = [(b.running_mean, b.running_var, b.num_batches_tracked) for b in bns]
+    eps, momentum, training = [b.eps for b in bns], [b.momentum for b in bns], bool(training)
+    params = (*ws, *bs, *gammas, *betas)
+    tensors = [t for t in (x, x1, residual, *params) if isinstance(t, torch.Tensor)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return _MlpTensorsF64.apply((len(ws), len(gammas), bufs, eps, momentum, training), x, x1, residual, *params)
+    return _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training, residual)[0]
