@@ -179,6 +179,30 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
                       int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                       float* Z, const mdgat_taps* taps,
                       void* workspace, size_t workspace_bytes, void* stream);
+#define MDGAT_RAGGED_MAX_KEYPOINTS 575   /* keypoints per frame (and per padded slot) of a ragged batch: what the register-resident fp64 Sinkhorn holds */
+/* mdgat_forward_f64 on a RAGGED batch: B pairs of different sizes in one call (the evaluation scripts run one pair per call because no two
+ * frames hold the same number of keypoints - test.py:132; padding is no way out: padded keypoints change every softmax, every top-k and
+ * the optimal transport).  Pair b has counts0[b] x counts1[b] keypoints and is stored in a slot padded to Np x Mp: kpts0 [B][Np][3], sigma0
+ * [B][Np], fpfh0 [B][Np][33], frame 1 likewise with Mp; matches0 / mscores0 [B][Np], matches1 / mscores1 [B][Mp], Z [B][Np+1][Mp+1].
+ *   - Pair b's results are those of mdgat_forward_f64 on pair b alone (B = 1): its matches, its scores, its block Z[b][0 .. counts0[b]]
+ *     [0 .. counts1[b]] with the dustbin row at row counts0[b] and the dustbin column at column counts1[b]; the rule of mdgat.py:465-467
+ *     (nothing matched: all scores zero) is applied per pair.  Bit for bit under mdgat_set_f64_attention_form(0); to rounding where the
+ *     launch size selects another kernel form for the batch than for the pair.  One exception: a pair with counts0[b] == counts1[b] == k
+ *     for a dynamic layer's k runs that layer on the dynamic-attention kernel here and, alone, on the full-attention kernel (top-k of
+ *     k keys is all of them): the same keys are kept, the messages agree to fp64 rounding (1e-11), not bit for bit.
+ *   - Beyond a pair's counts: matches -1, scores 0, the rest of its Z slot 0.
+ *   - What the inputs hold beyond a pair's counts is never read: NaN there reaches no result and no guard.
+ *   - Uniform counts (all Np / Mp) give the bits of mdgat_forward_f64 (with the same exception: Np == Mp == a dynamic layer's k).
+ * counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same values in HOST memory - every check is made on them before
+ * anything is enqueued: 1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp, and every dynamic layer's k <= both (torch.topk raises), else
+ * MDGAT_ERR_BAD_ARG naming the first offending pair.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
+ * f64_sinkhorn not MDGAT_F64_SINKHORN_OFF, f64_layers automatic, mdgat_set_f64_sinkhorn_form not 1 (else MDGAT_ERR_UNSUPPORTED); an fp32
+ * handle is MDGAT_ERR_BAD_ARG.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
+ * There is no ragged mdgat_forward_frames and no ragged loss. */
+int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                             const int32_t* counts1_host, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
+                             const double* sigma1, const double* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                             float* Z, const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same forward fed with the loader's raw frame records instead of separate arrays: frames [B][N][37] fp32,
  * one record per keypoint = xyz(3) | saliency(1) | FPFH(33), the layout of the KITTI keypoint files that
@@ -370,6 +394,27 @@ int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double
                                int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* RAGGED batches: B pairs of different sizes in one call.  Pair b has counts0[b] x counts1[b] keypoints and is stored in a slot padded to
+ * Np x Mp (scores [B][Np][Mp], Z [B][Np+1][Mp+1], matches0 / mscores0 [B][Np], matches1 / mscores1 [B][Mp]); what the inputs hold beyond a
+ * pair's counts is never read.  Pair b's results are those of the pair run alone through the uniform entry above, bit for bit: its block
+ * Z[b][0 .. counts0[b]][0 .. counts1[b]] with the dustbin row at row counts0[b] and the dustbin column at column counts1[b], its matches
+ * (dustbin = no match), its scores, and the rule of mdgat.py:465-467 (no frame-0 keypoint matched: all scores zero) applied to the pair
+ * alone.  Beyond a pair's counts the outputs are fixed: the rest of its Z slot 0, matches -1, scores 0.
+ * counts0 / counts1: DEVICE int32 [B], read by the kernels; counts0_host / counts1_host: the same values in HOST memory, checked before
+ * anything is launched (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp, else MDGAT_ERR_BAD_ARG naming the first offending pair).  Np, Mp <=
+ * 575 (the register-resident form; else MDGAT_ERR_UNSUPPORTED, as under mdgat_set_f64_sinkhorn_form(1)).  workspace:
+ * mdgat_sinkhorn_f64_ragged_workspace_bytes, 256-byte aligned.  Unlike their uniform siblings these two entries hand the kernel an error
+ * word and read it back: they SYNCHRONISE `stream` before they return, and return MDGAT_ERR_HIP instead of numbers when a workgroup gave
+ * up waiting for its partners. */
+size_t mdgat_sinkhorn_f64_ragged_workspace_bytes(int B, int Np, int Mp);
+int mdgat_sinkhorn_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                              const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                      const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
+                                      float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                      float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of log_optimal_transport (mdgat.py:279-308) in fp64: given scores [B][N][M] fp64, the bin score and dZ = dL/dZ
  * [B][N+1][M+1] fp64 (contiguous), writes dscores [B][N][M] and dbin [B] (the bin score's gradient PER PAIR: the sum of dL/dC over
  * the pair's dustbin row and column; a caller with one shared bin score sums them).  N, M <= 2175 (else MDGAT_ERR_UNSUPPORTED),
@@ -516,6 +561,16 @@ int mdgat_mfma_f64_probe(int reps, void* workspace, size_t workspace_bytes, floa
 int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda, const double* W, int ldw, const double* bias,
                         int relu, const double* R, int ldr, double* C, int ldc, void* stream);
 int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream);
+/* The same on a RAGGED batch: pair b has counts0[b] / counts1[b] keypoints in slots padded to Np / Mp (qkv [B][Np+Mp][384], frame 1 from row
+ * Np on; msg and sel likewise, sel with the words of mdgat_topk_sel_words(B, Np, Mp)).  Queries and keys beyond a pair's counts take no part
+ * and are never read; their message rows and selection words are zero.  A pair's rows are those of mdgat_attention_f64 on the pair alone -
+ * bit for bit where both launches run the same kernel form (mdgat_set_f64_attention_form(0), and the larger frame of both launches on the
+ * same side of 512 keys for a dynamic layer), to rounding otherwise; the kept keys are the same always.  topk > 0 runs the dynamic kernel
+ * also where k equals a pair's key count.  counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same values in HOST
+ * memory, checked before the launch: 1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp and topk <= both (torch.topk raises), else
+ * MDGAT_ERR_BAD_ARG naming the first offending pair. */
+int mdgat_attention_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                               const int32_t* counts1_host, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream);
 
 /* Backward of mdgat_attention_f64 (csrc/attention_grad.hip): given the forward's qkv [B][N+M][384], its selection words `sel` (the
  * `sel` output of the forward, layout of mdgat_taps.topk_sel; required when topk > 0, ignored when topk == 0) and dmsg = dL/dmsg
@@ -622,6 +677,14 @@ typedef enum {
 int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
                        const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
                        unsigned* bad_index, void* stream);
+/* The same on a RAGGED batch (mdgat_forward_f64_ragged's outputs): pair b has counts0[b] x counts1[b] keypoints in slots padded to Np x Mp
+ * (matches0 / gt0 [B][Np], matches1 / gt1 [B][Mp], kpts0 [B][Np][3], kpts1 [B][Mp][3]); what lies beyond a pair's counts is not read, and
+ * its row and T are those of mdgat_eval_metrics on the pair alone, bit for bit.  counts0 / counts1: DEVICE int32 [B]; counts0_host /
+ * counts1_host: the same in HOST memory, checked before the launch (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp). */
+int mdgat_eval_metrics_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                              const int32_t* counts1_host, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0,
+                              const int64_t* gt1, const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist,
+                              double* metrics, double* T, unsigned* bad_index, void* stream);
 
 #ifdef __cplusplus
 }

@@ -285,6 +285,9 @@ struct FwdIn {
     const float *rec0 = nullptr, *rec1 = nullptr;
     int normalize_fpfh = 0;
     const double *dk0 = nullptr, *ds0 = nullptr, *df0 = nullptr, *dk1 = nullptr, *ds1 = nullptr, *df1 = nullptr;
+    // a ragged batch (mdgat_forward_f64_ragged): the pairs' own keypoint counts in slots of N / M - device int32 [B] for the kernels, the
+    // same values on the host for plan_forward's checks
+    const int *cnt0 = nullptr, *cnt1 = nullptr, *cnt0_host = nullptr, *cnt1_host = nullptr;
     static FwdIn arrays(const float* k0, const float* s0, const float* f0, const float* k1, const float* s1, const float* f1) {
         FwdIn in; in.kpts0 = k0; in.sigma0 = s0; in.fpfh0 = f0; in.kpts1 = k1; in.sigma1 = s1; in.fpfh1 = f1; return in;
     }
@@ -296,7 +299,8 @@ struct FwdIn {
         auto o = [](auto* q, size_t n) { return q ? q + n : q; };
         return FwdIn{o(kpts0, c * N * 3), o(sigma0, c * N), o(fpfh0, c * N * 33), o(kpts1, c * M * 3), o(sigma1, c * M), o(fpfh1, c * M * 33),
                      o(rec0, c * N * 37), o(rec1, c * M * 37), normalize_fpfh,
-                     o(dk0, c * N * 3), o(ds0, c * N), o(df0, c * N * 33), o(dk1, c * M * 3), o(ds1, c * M), o(df1, c * M * 33)};
+                     o(dk0, c * N * 3), o(ds0, c * N), o(df0, c * N * 33), o(dk1, c * M * 3), o(ds1, c * M), o(df1, c * M * 33),
+                     o(cnt0, c), o(cnt1, c), o(cnt0_host, c), o(cnt1_host, c)};
     }
 };
 
@@ -395,6 +399,7 @@ struct Path {
     bool tail64;      // MDGAT_ARITH_FP64: final_proj, scores, Sinkhorn and the extraction's arg-maxes in fp64 too
     bool fused64;     // the fp64 encoders and layer tails as fused launches, the last one writing the hand-over to fp32
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
+    int cnt_min;      // a ragged batch (FwdIn::cnt0): the smallest keypoint count of any frame; 0 otherwise
     LanePlan lanes;
 };
 
@@ -438,7 +443,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         mdgat_set_error("mdgat_forward: null pointer argument");
         return MDGAT_ERR_BAD_ARG;
     }
-    p.lanes = taps ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
+    p.lanes = (taps || in.cnt0) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
     const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
@@ -467,6 +472,35 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     // keeps the one-product-per-launch form (bit-identical).
     p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
     p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
+    p.cnt_min = 0;
+    if (in.cnt0) {
+        // The ragged plan: the kernels that take per-pair counts are the exact mode's with its fp64 tail on the register-resident Sinkhorn;
+        // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); every count is checked on its host copy, naming the first offending pair.
+        const char* who = "mdgat_forward_f64_ragged";
+        if (!in.cnt1 || !in.cnt0_host || !in.cnt1_host) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
+        if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || !sinkhorn_f64_ragged_supported(N, M)) {
+            mdgat_set_error("%s: ragged batches need the fp64 tail on the register-resident Sinkhorn: f64_sinkhorn not off, f64_layers automatic, "
+                            "mdgat_set_f64_sinkhorn_form not 1, and at most %d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_MAX_KEYPOINTS, N, M);
+            return MDGAT_ERR_UNSUPPORTED;
+        }
+        int cmin = N < M ? N : M;
+        for (int b = 0; b < B; ++b) {
+            const int n = in.cnt0_host[b], m = in.cnt1_host[b];
+            if (n < 1 || n > N || m < 1 || m > M) {
+                mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, n, m, N, M);
+                return MDGAT_ERR_BAD_ARG;
+            }
+            for (int i = 0; i < L2; ++i)
+                if (h->cfg.topk[i] > (n < m ? n : m)) {      // torch.topk raises (mdgat.py:202)
+                    mdgat_set_error("%s: pair %d (%d x %d keypoints): layer %d: dynamic attention k=%d exceeds the number of keys", who, b, n, m, i, h->cfg.topk[i]);
+                    return MDGAT_ERR_BAD_ARG;
+                }
+            cmin = n < cmin ? n : cmin;
+            cmin = m < cmin ? m : cmin;
+        }
+        p.cnt_min = cmin;
+    }
     return MDGAT_OK;
 }
 
@@ -482,6 +516,8 @@ struct Fwd {
     mdgat_taps taps;         // all null when the call has none
     mdgat_handle::ProfLane& pl;
     int defer_alldust;       // a slice: the batch-wide rule is applied after the last one
+    const int *cnt0, *cnt1;  // a ragged batch (FwdIn): null otherwise
+    int cnt_min;
     unsigned* guard() const { return status + MDGAT_STATUS_RANGE; }
     // profiling (off by default): an event after every launch on this lane's stream; the intervals are attributed to the
     // kernel classes after the whole batch has been enqueued (prof_collect), which then ends with a synchronisation
@@ -540,7 +576,7 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     double* in4 = ws.hid64 + Rz * (256 - 37);
     double* in33 = in4 + Rz * 4;
     if (int rc = in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
-                         : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s)) return rc;
+                         : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_F64_OTHER);
     // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
     if (f.p.fused64) {
@@ -568,7 +604,7 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
             f.mark(MDGAT_PROF_F64_GEMM);
         }
         const int kk = f.h->cfg.topk[i];
-        if (int rc = launch_attention_f64(f.B, f.N, f.M, i & 1, kk, ws.qkv64, ws.msg64, f.sel_tap(i), f.s, f.guard())) return rc;
+        if (int rc = launch_attention_f64(f.B, f.N, f.M, i & 1, kk, ws.qkv64, ws.msg64, f.sel_tap(i), f.s, f.guard(), f.cnt0, f.cnt1, f.cnt_min)) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_F64_ATTENTION_TOPK : MDGAT_PROF_F64_ATTENTION_FULL);
         // AttentionalPropagation + residual (mdgat.py:246-248, 274)
         if (f.p.fused64) {
@@ -603,8 +639,8 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
     const Sk64Bests b = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
     const SkExtract ex = f.extract(o);
     if (int rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
-                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score)) return rc;
-    if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s)) return rc;
+                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score, f.cnt0, f.cnt1)) return rc;
+    if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const double*>(ws.Z64));
 }
@@ -671,6 +707,7 @@ static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, con
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
     const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss);
     Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust};
+    f.cnt0 = in.cnt0; f.cnt1 = in.cnt1; f.cnt_min = p.cnt_min;
     f.mark(-1);
     int rc;
     if ((N & 31) || (M & 31))   // the attention kernel reads V^T in whole 32-key blocks: pad columns must be zero
@@ -775,6 +812,24 @@ extern "C" int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M, const dou
                                  int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
                                  const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream) {
     return forward_arrays("mdgat_forward_f64", h, B, N, M, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+}
+
+// A ragged batch in the exact mode: pairs of different sizes in slots padded to Np x Mp, one call.  The counts ride in FwdIn: plan_forward
+// makes every check - the uniform call's, and the counts' on their host copies - before anything is enqueued and plans the batch unsliced;
+// the kernels that take the counts (assemble, attention, Sinkhorn, extraction) get them, the row-wise launches in between run over the
+// padded rows, which the assemble kernel has zeroed.
+extern "C" int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
+                                        const int32_t* counts0_host, const int32_t* counts1_host, const double* kpts0, const double* sigma0,
+                                        const double* fpfh0, const double* kpts1, const double* sigma1, const double* fpfh1, int64_t* matches0,
+                                        int64_t* matches1, float* mscores0, float* mscores1, float* Z, const mdgat_taps* taps, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1 || !counts0 || !counts1 || !counts0_host || !counts1_host) {
+        mdgat_set_error("mdgat_forward_f64_ragged: null input pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    FwdIn in = FwdIn::arrays(kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1);
+    in.cnt0 = counts0; in.cnt1 = counts1; in.cnt0_host = counts0_host; in.cnt1_host = counts1_host;
+    return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
@@ -962,6 +1017,25 @@ extern "C" int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, 
                                static_cast<hipStream_t>(stream));
 }
 
+extern "C" int mdgat_eval_metrics_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                         const int32_t* counts1_host, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0,
+                                         const int64_t* gt1, const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist,
+                                         double* metrics, double* T, unsigned* bad_index, void* stream) {
+    if (B < 0) { mdgat_set_error("mdgat_eval_metrics_ragged: negative batch"); return MDGAT_ERR_BAD_ARG; }
+    if (Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_eval_metrics_ragged: empty frame"); return MDGAT_ERR_BAD_ARG; }
+    if (B > 0 && (!matches0 || !matches1 || !gt0 || !gt1 || !kpts0 || !kpts1 || !metrics || !T || !counts0 || !counts1 || !counts0_host || !counts1_host)) {
+        mdgat_set_error("mdgat_eval_metrics_ragged: null pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    for (int b = 0; b < B; ++b)
+        if (counts0_host[b] < 1 || counts0_host[b] > Np || counts1_host[b] < 1 || counts1_host[b] > Mp) {
+            mdgat_set_error("mdgat_eval_metrics_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, counts0_host[b], counts1_host[b], Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    return launch_eval_metrics(B, Np, Mp, matches0, matches1, gt0, gt1, kpts0, kpts1, T_gt, inlier_dist, metrics, T, bad_index,
+                               static_cast<hipStream_t>(stream), counts0, counts1);
+}
+
 extern "C" int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda, const double* W, int ldw, const double* bias,
                                    int relu, const double* R, int ldr, double* C, int ldc, void* stream) {
     if (!A || !W || !C) { mdgat_set_error("mdgat_pointwise_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
@@ -1085,6 +1159,28 @@ extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, con
     if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (topk < 0) { mdgat_set_error("mdgat_attention_f64: topk < 0"); return MDGAT_ERR_BAD_ARG; }
     return launch_attention_f64(B, N, M, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream));
+}
+
+// a ragged batch: the counts on the device for the kernel, on the host for the checks made before the launch
+extern "C" int mdgat_attention_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                          const int32_t* counts1_host, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
+    if (!qkv || !msg || !counts0 || !counts1 || !counts0_host || !counts1_host) { mdgat_set_error("mdgat_attention_f64_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_attention_f64_ragged: bad shape B=%d Np=%d Mp=%d topk=%d", B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
+    int cmin = Np < Mp ? Np : Mp;
+    for (int b = 0; b < B; ++b) {
+        const int n = counts0_host[b], m = counts1_host[b];
+        if (n < 1 || n > Np || m < 1 || m > Mp) {
+            mdgat_set_error("mdgat_attention_f64_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, n, m, Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        if (topk > (n < m ? n : m)) {      // torch.topk raises (mdgat.py:202)
+            mdgat_set_error("mdgat_attention_f64_ragged: pair %d: k=%d exceeds the number of keys (%d)", b, topk, n < m ? n : m);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        cmin = n < cmin ? n : cmin;
+        cmin = m < cmin ? m : cmin;
+    }
+    return launch_attention_f64(B, Np, Mp, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream), nullptr, counts0, counts1, cmin);
 }
 
 // ---- the backward of mdgat_attention_f64: csrc/attention_grad.hip ----

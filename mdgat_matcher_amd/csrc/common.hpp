@@ -216,8 +216,10 @@ size_t mdgat_sinkhorn_ws_bytes_impl(int B, int N, int M);
 
 int launch_extract(int B, int N, int M, const float* Z, int mode, float thr, int64_t* m0, int64_t* m1,
                    float* s0, float* s1, hipStream_t s);
+// cnt0 / cnt1 (optional, device int32 [B]): a ragged batch in slots of N x M - dustbins at a pair's own counts, the all-dustbin rule per pair,
+// matches -1 and scores 0 beyond the counts
 int launch_extract_from_bests(int B, int N, int M, const SkExtract* ex, const int* rbest_idx, const float* rbest_val, const int* cbest_idx,
-                              const float* cbest_val, hipStream_t s);
+                              const float* cbest_val, hipStream_t s, const int* cnt0 = nullptr, const int* cnt1 = nullptr);
 
 int launch_pose(int B, int N, int M, const float* kpts0, const float* kpts1, const int64_t* matches0, const double* T_gt,
                 double inlier_dist, double* T, double* stats, hipStream_t s);
@@ -226,7 +228,7 @@ int launch_gt_match(int B, int N, int M, const float* kpts0, const float* kpts1,
 // the evaluation scripts' per-pair record (eval_metrics.hip)
 int launch_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
                         const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
-                        unsigned* bad_index, hipStream_t s);
+                        unsigned* bad_index, hipStream_t s, const int* cnt0 = nullptr, const int* cnt1 = nullptr);      // cnt: a ragged batch in slots of N / M
 
 // out[b][i][j] = scale <A[b][i], Bm[b][j]> - col_bias[b][j] over 128 channels, split-f16 products (scores.hip)
 int launch_dots(int B, int N, int M, const float* A, size_t strideA, const float* Bm, size_t strideB, float* out, float scale,

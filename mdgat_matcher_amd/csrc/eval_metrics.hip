@@ -34,6 +34,8 @@ struct EvalArgs {
     unsigned* bad_index;       // or NULL
     int N, M;
     double inlier_dist;
+    const int* cnt0;           // optional (device int32 [B], both or neither): a ragged batch - pair b has cnt0[b] / cnt1[b] keypoints in slots
+    const int* cnt1;           // of N / M: the strides stay N / M, everything counted, scanned or divided by follows the pair's own counts
 };
 
 // workgroup-wide sums of the counters -> every thread gets the totals (red: [4][EVAL_NCOUNT])
@@ -55,9 +57,11 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(EvalArgs a) {
     __shared__ int red[4 * EVAL_NCOUNT];
     __shared__ double scratch[4 * 16];
     __shared__ double Rt[12];
-    const int b = blockIdx.x, tid = threadIdx.x, N = a.N, M = a.M;
-    const int64_t* m0 = a.matches0 + (size_t)b * N;
-    const int64_t* g0 = a.gt0 + (size_t)b * N;
+    const int b = blockIdx.x, tid = threadIdx.x, Ns = a.N, Ms = a.M;
+    int N = Ns, M = Ms;
+    if (a.cnt0) { N = a.cnt0[b]; M = a.cnt1[b]; }
+    const int64_t* m0 = a.matches0 + (size_t)b * Ns;
+    const int64_t* g0 = a.gt0 + (size_t)b * Ns;
 
     int c[EVAL_NCOUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = tid; i < N; i += 256) {
@@ -78,8 +82,8 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(EvalArgs a) {
         c[C_FN] += !valid && valid_gt;                          // test_registration_metric.py:241
     }
     {   // matches1 / gt1 enter no metric (the scripts only rewrite gt1's dustbin): their range is checked, nothing else
-        const int64_t* m1 = a.matches1 + (size_t)b * M;
-        const int64_t* g1 = a.gt1 + (size_t)b * M;
+        const int64_t* m1 = a.matches1 + (size_t)b * Ms;
+        const int64_t* g1 = a.gt1 + (size_t)b * Ms;
         for (int j = tid; j < M; j += 256) {
             const int64_t mr = m1[j], gr = g1[j];
             c[C_BAD] += (mr < -1 || mr >= N) || (gr < -1 || gr > N);
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(EvalArgs a) {
     block_sum_counts(c, red);          // (its barrier also publishes match[])
 
     double st[5];
-    pose_of_pair(a.kpts0 + (size_t)b * N * 3, a.kpts1 + (size_t)b * M * 3, [&](int i) { return (int64_t)match[i]; }, N, M,
+    pose_of_pair(a.kpts0 + (size_t)b * Ns * 3, a.kpts1 + (size_t)b * Ms * 3, [&](int i) { return (int64_t)match[i]; }, N, M,
                  a.T_gt ? a.T_gt + (size_t)b * 16 : nullptr, a.inlier_dist, a.T + (size_t)b * 16, scratch, Rt, st);
     if (tid != 0) return;
 
@@ -147,13 +151,14 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(EvalArgs a) {
 
 int launch_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
                         const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,
-                        unsigned* bad_index, hipStream_t s) {
+                        unsigned* bad_index, hipStream_t s, const int* cnt0, const int* cnt1) {
+    if ((cnt0 != nullptr) != (cnt1 != nullptr)) { mdgat_set_error("mdgat_eval_metrics: per-pair counts for one frame only"); return MDGAT_ERR_BAD_ARG; }
     if (N > EVAL_NMAX || M > EVAL_NMAX) {
         mdgat_set_error("mdgat_eval_metrics: %d x %d keypoints are beyond the fp64 tail's limit (%d)", N, M, EVAL_NMAX);
         return MDGAT_ERR_UNSUPPORTED;
     }
     if (B <= 0) return MDGAT_OK;
-    EvalArgs a{matches0, matches1, gt0, gt1, kpts0, kpts1, T_gt, metrics, T, bad_index, N, M, inlier_dist};
+    EvalArgs a{matches0, matches1, gt0, gt1, kpts0, kpts1, T_gt, metrics, T, bad_index, N, M, inlier_dist, cnt0, cnt1};
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(B), dim3(256), 0, s, a);
     return mdgat_check_hip(hipGetLastError(), "eval_metrics launch");
 }

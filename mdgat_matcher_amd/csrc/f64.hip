@@ -277,9 +277,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     if (unit >= a.units) return;
     const int head = unit & 3, side = (unit >> 2) & 1, b = unit >> 3;
     const int P = a.N + a.M;
-    const int nq = side ? a.M : a.N, q_off = side ? a.N : 0;
+    int cN = a.N, cM = a.M;                      // this pair's keypoint counts (a ragged batch: its own, in slots of N / M)
+    if (a.cnt0) { cN = __builtin_amdgcn_readfirstlane(a.cnt0[b]); cM = __builtin_amdgcn_readfirstlane(a.cnt1[b]); }
+    const int nq = side ? cM : cN, q_off = side ? a.N : 0;
     const int src = a.cross ? 1 - side : side;
-    const int nk = src ? a.M : a.N, k_off = src ? a.N : 0;
+    const int nk = src ? cM : cN, k_off = src ? a.N : 0;
     const int q0 = SOLO ? (tile * 4 + wave) * QT : tile * QT;
     if (!SOLO && q0 >= nq) return;
     sm.tab[tid] = MDGAT_EXP2_TAB256[tid];        // (256 threads)
@@ -662,7 +664,9 @@ __device__ __forceinline__ bool f32_bits_nonfinite(unsigned b) { return (b & 0x7
 // encoder inputs (mdgat.py:186-187, 154): in4 [R][4] = x y z saliency, in33 [R][33] = FPFH, rows pair-major (frame 0 then frame 1)
 __global__ __launch_bounds__(256) void assemble_f64_kernel(const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
                                                             const double* sigma1, const double* fpfh1, double* in4, double* in33, int B, int N, int M,
-                                                            unsigned* guard) {
+                                                            unsigned* guard, const int* cnt0, const int* cnt1) {
+    // cnt0 / cnt1 (optional): a ragged batch - rows beyond a pair's own counts are written as ZEROS and their inputs are not read (whatever
+    // they hold - NaN included - reaches neither a result nor the guard): the row-wise launches behind this one then run over them unchanged
     const int P = N + M;
     const size_t total = (size_t)B * P * 37;
     bool bad = false;
@@ -677,9 +681,10 @@ __global__ __launch_bounds__(256) void assemble_f64_kernel(const double* kpts0, 
         const double* fp = f1 ? fpfh1 : fpfh0;
         const size_t r = (size_t)b * cnt + n;
         typedef const unsigned long long* bits_p;
+        unsigned long long* dst = reinterpret_cast<unsigned long long*>(c < 4 ? in4 + row * 4 + c : in33 + row * 33 + (c - 4));
+        if (cnt0 && n >= (f1 ? cnt1[b] : cnt0[b])) { *dst = 0ull; continue; }
         const unsigned long long v = c < 3 ? bits_p(kp)[r * 3 + c] : c == 3 ? bits_p(sg)[r] : bits_p(fp)[r * 33 + (c - 4)];
         bad |= f64_bits_nonfinite(v);
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(c < 4 ? in4 + row * 4 + c : in33 + row * 33 + (c - 4));
         *dst = v;
     }
     if (bad) f64_raise(guard);
@@ -857,9 +862,13 @@ extern "C" int mdgat_set_f64_attention_form(int mode) {
     return prev;
 }
 
-int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard) {
+int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard,
+                         const int* cnt0, const int* cnt1, int cnt_min) {
     if (B <= 0 || N <= 0 || M <= 0) return MDGAT_OK;
-    const int nk_max = N > M ? N : M, nk_min = N < M ? N : M;
+    const bool ragged = cnt0 != nullptr;
+    if (ragged && (!cnt1 || cnt_min < 1 || cnt_min > (N < M ? N : M))) { mdgat_set_error("attention (fp64): bad per-pair counts"); return MDGAT_ERR_BAD_ARG; }
+    // (a ragged batch: the grid, the LDS and the choice of the kernel follow the padded sizes, the histograms' place the smallest count)
+    const int nk_max = N > M ? N : M, nk_min = ragged ? cnt_min : N < M ? N : M;
     if (topk > nk_min) {   // torch.topk raises (mdgat.py:202)
         mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", topk, nk_min);
         return MDGAT_ERR_BAD_ARG;
@@ -868,8 +877,11 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
         mdgat_set_error("dynamic attention (fp64): %d keys per frame > 2048 supported", nk_max);
         return MDGAT_ERR_UNSUPPORTED;
     }
-    const bool dyn = topk > 0 && !(topk == N && topk == M);
+    const bool dyn = topk > 0 && (ragged || !(topk == N && topk == M));
     AttnF64Args a{};
+    a.cnt0 = cnt0; a.cnt1 = cnt1;
+    // (the kernel writes the rows of a pair's own queries only)
+    if (ragged) if (int rc = mdgat_check_hip(hipMemsetAsync(msg, 0, (size_t)B * (N + M) * 128 * sizeof(double), s), "memset(ragged attention message)")) return rc;
     a.qkv = qkv; a.msg = msg; a.N = N; a.M = M; a.cross = cross; a.topk = dyn ? topk : 0;
     a.zq = dyn ? f64_normal_quantile_upper(((double)topk - 0.5) / (double)nk_max) : 0.f;
     a.selW = (nk_max + 31) / 32;
@@ -917,10 +929,11 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
 }
 
 int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
-                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s) {
+                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s, const int* cnt0,
+                        const int* cnt1) {
     const size_t total = (size_t)B * (N + M) * 37;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(assemble_f64_kernel, dim3(blocks), dim3(256), 0, s, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, in4, in33, B, N, M, guard);
+    hipLaunchKernelGGL(assemble_f64_kernel, dim3(blocks), dim3(256), 0, s, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, in4, in33, B, N, M, guard, cnt0, cnt1);
     return mdgat_check_hip(hipGetLastError(), "assemble_f64 launch");
 }
 

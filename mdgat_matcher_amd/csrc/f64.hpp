@@ -39,15 +39,22 @@ struct AttnF64Args {
     int units, tiles;      // B * 2 * 4 (pair, frame, head) units; query tiles per unit
     int hist_ints;         // dynamic attention: ints of LDS for the radix-select histograms (attn_hist_ints in f64.hip)
     unsigned* guard;       // as GemmF64Args::guard, for the message rows
+    const int* cnt0;       // optional (device int32 [B], both or neither): a ragged batch - pair b has cnt0[b] / cnt1[b] keypoints; N, M are then
+    const int* cnt1;       // the padded sizes: strides, grid and LDS follow them, queries and keys the pair's own counts
 };
 // attention (topk == 0) / dynamic_attention (mdgat.py:190-210) on fp64 q / k / v; sel: optional tap of the kept keys
 // mdgat_set_f64_attention_form / MDGAT_F64_ATTENTION_FORM: -1 full attention by launch size; 0 always the split-key form (results do not
 // depend on the batch a pair travels in); 1 the big-launch form at every size
 int f64_attention_form();
-int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard = nullptr);
+// cnt0 / cnt1: a ragged batch in slots padded to N / M (cnt_min: the smallest count of either frame, known to the caller on the host, who
+// has checked 1 <= cnt0[b] <= N, 1 <= cnt1[b] <= M).  A pair's message rows and selection words are those of the pair run alone wherever
+// the same instantiation runs it; message rows and selection words beyond its counts are zero.
+int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard = nullptr,
+                         const int* cnt0 = nullptr, const int* cnt1 = nullptr, int cnt_min = 0);
 // in4 [R][4] = x y z saliency, in33 [R][33] = FPFH; rows pair-major, frame 0 then frame 1
 int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
-                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s);
+                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s,
+                        const int* cnt0 = nullptr, const int* cnt1 = nullptr);      // cnt: a ragged batch - rows beyond a pair's counts are written as zeros, unread
 // the same from raw float32 records [B][N][37] (load_data.py:146-165; FPFH normalised as numpy does it in float32, 290-292)
 int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const float* rec1, int normalize, double* in4, double* in33, unsigned* guard,
                                hipStream_t s);

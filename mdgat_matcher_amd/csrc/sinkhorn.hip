@@ -902,50 +902,56 @@ struct ExArgs {
     // optional (host-mapped word): set to matched_token when a frame-0 keypoint of this pair is matched - what the host-side test
     // of mdgat.py:465 (`valid0.sum() == 0`) needs to know, without a reduction kernel and a copy (mdgat_matched_any)
     unsigned* matched; unsigned matched_token;
+    // optional (device int32 [B], both or neither; with the arg-maxes of sinkhorn_f64.hip's ragged launch): pair b has cnt0[b] x cnt1[b]
+    // keypoints in slots of N x M.  Its dustbins are the indices cnt1[b] / cnt0[b], the rule of mdgat.py:465-467 is applied to it alone (as
+    // when it is the only pair of the call), and beyond its counts matches are -1 and scores 0.
+    const int* cnt0; const int* cnt1;
 };
 
 __global__ __launch_bounds__(1024) void extract_kernel(ExArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int N = a.N, M = a.M;
+    const int Ns = a.N, Ms = a.M;                // the strides
+    int N = Ns, M = Ms;
+    if (a.cnt0) { N = a.cnt0[blockIdx.x]; M = a.cnt1[blockIdx.x]; }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // the cluster kernel lost a partner workgroup (bounded spin ran out): its fused arg-maxes are garbage; the gated streaming
     // kernel has recomputed Z since
     const bool redone = a.sk_error && ((__hip_atomic_load(a.sk_error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u) != 0 ||
                                        (a.pair_flags && __hip_atomic_load(a.pair_flags + blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0));
     const float* Zsrc = redone ? a.Zfb : a.Z;
-    const float* Z = Zsrc + (size_t)blockIdx.x * (N + 1) * (M + 1);
+    const float* Z = Zsrc + (size_t)blockIdx.x * (Ns + 1) * (Ms + 1);
     int* idx0 = reinterpret_cast<int*>(smem);   // [N]
-    int* idx1 = idx0 + N;                       // [M]
-    float* val0 = reinterpret_cast<float*>(idx1 + M);   // [N]
-    float* val1 = val0 + N;                     // [M]
+    int* idx1 = idx0 + Ns;                      // [M]
+    float* val0 = reinterpret_cast<float*>(idx1 + Ms);  // [N]
+    float* val1 = val0 + Ns;                    // [M]
     const bool inner = a.mode >= MDGAT_EXTRACT_THRESHOLD;   // arg-max over the inner N x M block only
     const int ncol = inner ? M : M + 1;   // columns scanned per row
     const int nrow = inner ? N : N + 1;   // rows scanned per column
     if (!Zsrc) {
         for (int i = tid; i < N; i += 1024) {
-            const size_t base = (size_t)blockIdx.x * a.GC * N + i;
+            const size_t base = (size_t)blockIdx.x * a.GC * Ns + i;
             float bv = a.rbest_val[base];
             int bi = a.rbest_idx[base];
             for (int g = 1; g < a.GC; ++g) {         // ascending column slabs, strict compare: first maximal column
-                const float v = a.rbest_val[base + (size_t)g * N];
-                if (v > bv) { bv = v; bi = a.rbest_idx[base + (size_t)g * N]; }
+                const float v = a.rbest_val[base + (size_t)g * Ns];
+                if (v > bv) { bv = v; bi = a.rbest_idx[base + (size_t)g * Ns]; }
             }
             idx0[i] = bi; val0[i] = bv;
         }
         for (int j = tid; j < M; j += 1024) {
-            const size_t base = (size_t)blockIdx.x * a.GR * M + j;
+            const size_t base = (size_t)blockIdx.x * a.GR * Ms + j;
             float bv = a.cbest_val[base];
             int bi = a.cbest_idx[base];
             for (int g = 1; g < a.GR; ++g) {         // ascending row slabs, strict compare: first maximal row
-                const float v = a.cbest_val[base + (size_t)g * M];
-                if (v > bv) { bv = v; bi = a.cbest_idx[base + (size_t)g * M]; }
+                const float v = a.cbest_val[base + (size_t)g * Ms];
+                if (v > bv) { bv = v; bi = a.cbest_idx[base + (size_t)g * Ms]; }
             }
             idx1[j] = bi; val1[j] = bv;
         }
     } else {
     // rows: first maximal index (torch.max semantics)
     for (int i = wave; i < N; i += 16) {
-        const float* zr = Z + (size_t)i * (M + 1);
+        const float* zr = Z + (size_t)i * (Ms + 1);
         float bv = -__builtin_inff();
         int bi = 0x7fffffff;
         for (int j = lane; j < ncol; j += 64) {
@@ -965,7 +971,7 @@ __global__ __launch_bounds__(1024) void extract_kernel(ExArgs a) {
         float bv = -__builtin_inff();
         int bi = 0;
         for (int i = 0; i < nrow; ++i) {
-            const float z = Z[(size_t)i * (M + 1) + j];
+            const float z = Z[(size_t)i * (Ms + 1) + j];
             if (z > bv) { bv = z; bi = i; }
         }
         idx1[j] = bi; val1[j] = bv;
@@ -973,10 +979,10 @@ __global__ __launch_bounds__(1024) void extract_kernel(ExArgs a) {
     }
     __syncthreads();
 
-    int64_t* m0 = a.m0 + (size_t)blockIdx.x * N;
-    int64_t* m1 = a.m1 + (size_t)blockIdx.x * M;
-    float* s0 = a.s0 + (size_t)blockIdx.x * N;
-    float* s1 = a.s1 + (size_t)blockIdx.x * M;
+    int64_t* m0 = a.m0 + (size_t)blockIdx.x * Ns;
+    int64_t* m1 = a.m1 + (size_t)blockIdx.x * Ms;
+    float* s0 = a.s0 + (size_t)blockIdx.x * Ns;
+    float* s1 = a.s1 + (size_t)blockIdx.x * Ms;
 
     int nmatch = 0;          // frame-0 keypoints of this thread with a match (matches0 >= 0)
     if (a.mode == MDGAT_EXTRACT_DUSTBIN || a.mode == MDGAT_EXTRACT_DUSTBIN_MUTUAL) {
@@ -1012,8 +1018,12 @@ __global__ __launch_bounds__(1024) void extract_kernel(ExArgs a) {
             __syncthreads();
             if (last) {                                                  // (s0 is zero already: no row was valid)
                 float* s1all = a.s1;
-                for (size_t i = tid; i < (size_t)a.B * M; i += 1024) s1all[i] = 0.f;
+                for (size_t i = tid; i < (size_t)a.B * Ms; i += 1024) s1all[i] = 0.f;
             }
+        } else if (a.cnt0) {
+            // a ragged batch: mdgat.py:465-467 for this pair alone (s0 is zero already; every thread rewrites the scores it stored)
+            if (!__syncthreads_or(nvalid > 0))
+                for (int j = tid; j < M; j += 1024) s1[j] = 0.f;
         }
     } else if (a.mode == MDGAT_EXTRACT_THRESHOLD) {
         for (int i = tid; i < N; i += 1024) {
@@ -1048,6 +1058,10 @@ __global__ __launch_bounds__(1024) void extract_kernel(ExArgs a) {
             m1[j] = valid1 ? i : -1;
             s1[j] = ms1;
         }
+    }
+    if (a.cnt0) {
+        for (int i = N + tid; i < Ns; i += 1024) { m0[i] = -1; s0[i] = 0.f; }
+        for (int j = M + tid; j < Ms; j += 1024) { m1[j] = -1; s1[j] = 0.f; }
     }
     if (a.matched) {
         const int any = __syncthreads_or(nmatch > 0);
@@ -1227,16 +1241,17 @@ static int launch_extract_impl(int B, int N, int M, ExArgs a, hipStream_t s, boo
     const size_t lds = (size_t)(2 * (N + M) + 4) * sizeof(float);
     hipLaunchKernelGGL(extract_kernel, dim3(B), dim3(1024), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "extract launch")) return rc;
-    if (defer_alldust || a.alldust_counters) return MDGAT_OK;      // (counters: the kernel applied the rule itself)
+    if (defer_alldust || a.alldust_counters || a.cnt0) return MDGAT_OK;      // (counters, or a ragged batch: the kernel applied the rule itself)
     return launch_alldust_fixup(B, N, M, a.mode, a.m0, a.s1, s);
 }
 
 // the extraction from arg-maxes another kernel has decided (sinkhorn_f64.hip: on the fp64 Z): rbest [B][N], cbest [B][M]
 int launch_extract_from_bests(int B, int N, int M, const SkExtract* ex, const int* rbest_idx, const float* rbest_val, const int* cbest_idx,
-                              const float* cbest_val, hipStream_t s) {
+                              const float* cbest_val, hipStream_t s, const int* cnt0, const int* cnt1) {
     if (B <= 0) return MDGAT_OK;
+    if ((cnt0 != nullptr) != (cnt1 != nullptr)) { mdgat_set_error("extract: per-pair counts for one frame only"); return MDGAT_ERR_BAD_ARG; }
     ExArgs xa{nullptr, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, rbest_idx, rbest_val, cbest_idx, cbest_val,
-              1, 1, ex->matched, ex->matched_token};
+              1, 1, ex->matched, ex->matched_token, cnt0, cnt1};
     return launch_extract_impl(B, N, M, xa, s, ex->defer_alldust != 0);
 }
 

@@ -46,6 +46,9 @@ struct Sk64Args {
     double* slots;             // [B][2][G][S64_SLOT]
     unsigned* flags;           // [B][3][G], zeroed per launch: two sets of iteration flags, then the partners' XCC ids + 1
     unsigned* error_word;      // bit 0: a workgroup gave up waiting for a partner
+    // RAGGED instantiation only: pair b has cnt0[b] x cnt1[b] keypoints; N, M above are then the launch's padded sizes - the strides of
+    // every array and what G is sized for - and everything the transport itself depends on comes from the pair's own counts
+    const int* cnt0; const int* cnt1;
 };
 
 // sum over the 64 lanes, the same bits in every lane: four rotations inside the DPP rows (no LDS crossbar), then the two steps across
@@ -125,7 +128,11 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
 }
 
 // S64_WAVES waves of four rows each per workgroup: 8 (32 rows) is what is launched - a pair of 512 keypoints is 16 workgroups on 16 CUs.
-template <int S64_WAVES>
+// RAGGED: per-pair keypoint counts in padded slots (Sk64Args::cnt0 / cnt1).  A pair then computes exactly what it computes alone: its
+// masks, marginals and norm come from its own counts, its dustbin row belongs to its OWN last slab (so the column sums associate as
+// when it runs alone - the slabs behind it publish +0.0), and all G workgroups of the launch's slab count take part in every exchange,
+// rows or none: a workgroup that left early would leave its partners spinning to their bound.
+template <int S64_WAVES, bool RAGGED>
 __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_kernel(Sk64Args a) {
     // (one workgroup per CU either way: eight waves at 168 registers, sixteen at 128.  Two eight-wave workgroups per CU - 128 registers,
     // 152 bytes of scratch - are no faster: 32 pairs 917 against 878 us, one pair 502 against 432: a CU's iteration time is its
@@ -139,19 +146,21 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
     __shared__ int dead, same_xcd_s;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, M = a.M, G = a.G;
+    const int Ns = a.N, Ms = a.M, G = a.G;               // the strides (RAGGED: the padded sizes)
     // blockIdx = (pair / 8) * (8 G) + g * 8 + pair % 8: the G workgroups of a pair share blockIdx % 8
     const int grp = blockIdx.x / (8 * G), rem = blockIdx.x % (8 * G);
     const int pair = grp * 8 + (rem & 7), g = rem >> 3;
     if (pair >= a.B) return;
+    int N = Ns, M = Ms;
+    if constexpr (RAGGED) { N = __builtin_amdgcn_readfirstlane(a.cnt0[pair]); M = __builtin_amdgcn_readfirstlane(a.cnt1[pair]); }
     if (tid == 0) dead = 0;
-    const double* sc = a.scores + (size_t)pair * N * M;
+    const double* sc = a.scores + (size_t)pair * Ns * Ms;
     const int row0 = g * S64_ROWS + wave * 4;            // this wave's rows row0 .. row0 + 3 (real rows: < N)
     const double nm = (double)(N + M);
     const double norm = -log(nm);
-    const bool last = g == G - 1;                        // the slab that also carries the dustbin row
+    const bool last = g == (RAGGED ? (N + S64_ROWS - 1) / S64_ROWS : G) - 1;      // the slab that also carries the dustbin row
     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
-    auto z0 = [&](int i, int j) -> double { return j < M ? sc[(size_t)i * M + j] : alpha; };      // (real rows only)
+    auto z0 = [&](int i, int j) -> double { return j < M ? sc[(size_t)i * Ms + j] : alpha; };      // (real rows only)
 
     // K = exp(Z0 - row maximum): 4 x 9 doubles per lane.  The DUSTBIN ROW needs no storage: its couplings are the bin score in every
     // column (mdgat.py:296-298), so K = 1 throughout - its row sum is the sum of b, its share of every column sum is a_N itself.
@@ -301,8 +310,8 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
             const int j = lane + 64 * c;
             if (j > M) continue;
             const double z = z0(row, j) + la + lb[c];
-            if (a.Z64) a.Z64[((size_t)pair * (N + 1) + row) * (M + 1) + j] = z;
-            if (a.Z32) a.Z32[((size_t)pair * (N + 1) + row) * (M + 1) + j] = (float)z;
+            if (a.Z64) a.Z64[((size_t)pair * (Ns + 1) + row) * (Ms + 1) + j] = z;
+            if (a.Z32) a.Z32[((size_t)pair * (Ns + 1) + row) * (Ms + 1) + j] = (float)z;
             if (j < jlim && z > best) { best = z; bj = j; }            // ascending j within the lane: the first maximum stays
             if (z > cb[c]) { cb[c] = z; ci[c] = row; }                 // ascending rows within the wave
         }
@@ -313,7 +322,7 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
                 const int oj = __shfl_xor(bj, s, 64);
                 if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }      // torch.max: the first of equal maxima
             }
-            if (lane == 0) { a.rbest_idx[(size_t)pair * N + row] = bj; a.rbest_val[(size_t)pair * N + row] = (float)best; }
+            if (lane == 0) { a.rbest_idx[(size_t)pair * Ns + row] = bj; a.rbest_val[(size_t)pair * Ns + row] = (float)best; }
         }
     }
     // the dustbin row of Z (row N: Z0 - r = 0), by the last slab's first wave
@@ -326,8 +335,8 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
             if (j > M) continue;
             const double z = laN + lb[c];
             bl[j] = z;
-            if (a.Z64) a.Z64[((size_t)pair * (N + 1) + N) * (M + 1) + j] = z;
-            if (a.Z32) a.Z32[((size_t)pair * (N + 1) + N) * (M + 1) + j] = (float)z;
+            if (a.Z64) a.Z64[((size_t)pair * (Ns + 1) + N) * (Ms + 1) + j] = z;
+            if (a.Z32) a.Z32[((size_t)pair * (Ns + 1) + N) * (Ms + 1) + j] = (float)z;
         }
     }
     if (a.cslab_idx) {
@@ -343,17 +352,20 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
             for (int w = 1; w < S64_WAVES; ++w)
                 if (colbuf[w][j] > bv) { bv = colbuf[w][j]; bi = cidx[w][j]; }
             if (last && !a.inner && bl[j] > bv) { bv = bl[j]; bi = N; }
-            a.cslab_val[((size_t)pair * G + g) * M + j] = bv;
-            a.cslab_idx[((size_t)pair * G + g) * M + j] = bi == 0x7fffffff ? 0 : bi;
+            a.cslab_val[((size_t)pair * G + g) * Ms + j] = bv;
+            a.cslab_idx[((size_t)pair * G + g) * Ms + j] = bi == 0x7fffffff ? 0 : bi;      // (RAGGED, a slab without rows: -inf, never taken)
         }
     }
 }
 
-// column arg-max over the G row slabs of a pair, in fp64: ascending slabs, strict compare (the first of equal maxima)
-__global__ __launch_bounds__(256) void sinkhorn_f64_merge_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val) {
+// column arg-max over the G row slabs of a pair, in fp64: ascending slabs, strict compare (the first of equal maxima).  cnt1 (optional):
+// the pairs' own column counts in slots of M - columns beyond a pair's count are left alone
+__global__ __launch_bounds__(256) void sinkhorn_f64_merge_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val,
+                                                                 const int* cnt1) {
     const size_t total = (size_t)B * M;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const size_t pair = e / M, j = e % M;
+        if (cnt1 && j >= (size_t)cnt1[pair]) continue;
         const size_t base = pair * G * M + j;
         double bv = sval[base];
         int bi = sidx[base];
@@ -663,13 +675,19 @@ Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M) {
 }
 
 bool sinkhorn_f64_supported(int N, int M) { return s64_resident_supported(N, M) || s64_wide_supported(N, M); }
+// (the resident kernel holds 576 rows and 575 columns; the ragged entries document and take one limit for both frames)
+static_assert(MDGAT_RAGGED_MAX_KEYPOINTS == 64 * S64_NC - 1 && MDGAT_RAGGED_MAX_KEYPOINTS <= 32 * S64_GMAX, "the ragged limit is the resident kernel's");
+bool sinkhorn_f64_ragged_supported(int N, int M) {
+    return s64_resident_supported(N, M) && N <= MDGAT_RAGGED_MAX_KEYPOINTS && M <= MDGAT_RAGGED_MAX_KEYPOINTS && s64_form() != 1;
+}
 
 // both forms: the column arg-maxes of the G row slabs merged in fp64, if the caller asked for them
-static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val, hipStream_t s) {
+static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val, hipStream_t s,
+                             const int* cnt1 = nullptr) {
     if (!cbest_idx) return MDGAT_OK;
     const size_t total = (size_t)B * M;
     hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, G, M,
-                       cbest_idx, cbest_val);
+                       cbest_idx, cbest_val, cnt1);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch");
 }
 
@@ -708,9 +726,15 @@ static int launch_sinkhorn_f64_wide(int B, int N, int M, const double* scores, d
 
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
                         float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
-                        CoopGroup& group, const double* alpha_dev) {
+                        CoopGroup& group, const double* alpha_dev, const int* cnt0, const int* cnt1) {
     if (B <= 0) return MDGAT_OK;
     const hipStream_t s = group.stream();
+    const bool ragged = cnt0 != nullptr;
+    if (ragged && (!cnt1 || !s64_resident_supported(N, M) || s64_form() == 1)) {
+        mdgat_set_error("fp64 Sinkhorn: per-pair counts run on the register-resident form only (padded sizes %d x %d, at most %d; form %d)", N, M,
+                        64 * S64_NC - 1, s64_form());
+        return cnt1 ? MDGAT_ERR_UNSUPPORTED : MDGAT_ERR_BAD_ARG;
+    }
     if (!sinkhorn_f64_supported(N, M)) { mdgat_set_error("fp64 Sinkhorn: %d x %d keypoints > %d supported", N, M, 128 * W64_NC2MAX - 1); return MDGAT_ERR_UNSUPPORTED; }
     if (!workspace || workspace_bytes < sinkhorn_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
         mdgat_set_error("fp64 Sinkhorn: workspace too small or not 256-byte aligned");
@@ -729,7 +753,7 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.G = G; a.inner = inner;
     a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val;
     a.slots = w.slots; a.flags = w.flags; a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
-    a.error_word = error_word;
+    a.error_word = error_word; a.cnt0 = cnt0; a.cnt1 = cnt1;
     // ONE launch of this kernel at a time per device: the caller's CoopGroup admits it after the previous waiting launch, whatever stream
     // that was on (coop_chain.hpp; shared with the clustered fp64 layer tail).  The workgroups of a pair wait for each other, and a
     // workgroup that waits holds its CU.  Within one launch that is safe - an XCD gets its pairs in order, each as a contiguous run of
@@ -741,11 +765,19 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     if (int rc = mdgat_check_hip(hipMemsetAsync(a.flags, 0, (size_t)B * 3 * G * sizeof(unsigned), s), "memset(fp64 Sinkhorn flags)")) return rc;
     const int groups = (B + 7) / 8;
     const size_t lds = s64_lds_bytes(waves);
-    static std::atomic<unsigned long long> optin8{0};
-    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8>), lds, optin8, "sinkhorn_f64 LDS")) return rc;
-    hipLaunchKernelGGL(sinkhorn_f64_kernel<8>, dim3(groups * 8 * G), dim3(512), lds, s, a);
+    static std::atomic<unsigned long long> optin8{0}, optin8r{0};
+    if (ragged) {
+        // (the kernel writes a pair's own block of Z only: the rest of every padded slot is zero)
+        if (Z64) if (int rc = mdgat_check_hip(hipMemsetAsync(Z64, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(double), s), "memset(fp64 Sinkhorn Z)")) return rc;
+        if (Z32) if (int rc = mdgat_check_hip(hipMemsetAsync(Z32, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(float), s), "memset(fp64 Sinkhorn Z32)")) return rc;
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8, true>), lds, optin8r, "sinkhorn_f64 (ragged) LDS")) return rc;
+        hipLaunchKernelGGL((sinkhorn_f64_kernel<8, true>), dim3(groups * 8 * G), dim3(512), lds, s, a);
+    } else {
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8, false>), lds, optin8, "sinkhorn_f64 LDS")) return rc;
+        hipLaunchKernelGGL((sinkhorn_f64_kernel<8, false>), dim3(groups * 8 * G), dim3(512), lds, s, a);
+    }
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
-    return s64_merge_columns(w.sidx, w.sval, B, G, M, cbest_idx, cbest_val, s);
+    return s64_merge_columns(w.sidx, w.sval, B, G, M, cbest_idx, cbest_val, s, cnt1);
 }
 
 // ---- the streaming form's iterations with their potential history, for the backward (sinkhorn_grad.hip) ----
@@ -804,4 +836,91 @@ extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* sco
     }
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
     return launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, s);
+}
+
+// ---- ragged batches (include/mdgat_hip.h): pairs of different sizes in slots padded to Np x Mp ----
+// The counts come twice: on the device for the kernels, and on the host for the checks made before anything is launched.
+static int s64_check_counts(const char* who, int B, int Np, int Mp, const int32_t* c0, const int32_t* c1, const int32_t* h0, const int32_t* h1) {
+    if (!c0 || !c1 || !h0 || !h1) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (!s64_resident_supported(Np, Mp) || Np > MDGAT_RAGGED_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_MAX_KEYPOINTS) {
+        mdgat_set_error("%s: padded sizes %d x %d: ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_MAX_KEYPOINTS);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    for (int b = 0; b < B; ++b)
+        if (h0[b] < 1 || h0[b] > Np || h1[b] < 1 || h1[b] > Mp) {
+            mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, h0[b], h1[b], Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    return MDGAT_OK;
+}
+// The error word sits behind the uniform entries' workspace.  Reading it back is the one synchronisation of these entries: a launch
+// whose workgroups gave up waiting for each other returns an error, not numbers.
+static size_t s64_ragged_word_offset(int B, int Np, int Mp) { return (mdgat_sinkhorn_f64_workspace_bytes(B, Np, Mp) + 255) & ~(size_t)255; }
+extern "C" size_t mdgat_sinkhorn_f64_ragged_workspace_bytes(int B, int Np, int Mp) {
+    if (B <= 0 || Np <= 0 || Mp <= 0 || !s64_resident_supported(Np, Mp) || Np > MDGAT_RAGGED_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_MAX_KEYPOINTS || s64_form() == 1) return 0;
+    return s64_ragged_word_offset(B, Np, Mp) + 256;
+}
+static int s64_ragged_finish(const char* who, unsigned* word, hipStream_t s) {
+    unsigned host = 0;
+    if (int rc = mdgat_check_hip(hipMemcpyAsync(&host, word, sizeof(unsigned), hipMemcpyDeviceToHost, s), "memcpy(fp64 Sinkhorn error word)")) return rc;
+    if (int rc = mdgat_check_hip(hipStreamSynchronize(s), "synchronize(fp64 Sinkhorn error word)")) return rc;
+    if (host & 1u) { mdgat_set_error("%s: a workgroup gave up waiting for its partners (is the device shared?): no result", who); return MDGAT_ERR_HIP; }
+    return MDGAT_OK;
+}
+
+extern "C" int mdgat_sinkhorn_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                         const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_sinkhorn_f64_ragged";
+    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (int rc = s64_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
+    if (s64_form() == 1) { mdgat_set_error("%s: the streaming form (mdgat_set_f64_sinkhorn_form(1)) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
+    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned* word = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + s64_ragged_word_offset(B, Np, Mp));
+    if (int rc = mdgat_check_hip(hipMemsetAsync(word, 0, 256, s), "memset(fp64 Sinkhorn error word)")) return rc;
+    {
+        CoopGroup group;
+        if (int rc = group.open(mdgat_current_device(), s)) return rc;
+        if (int rc = launch_sinkhorn_f64(B, Np, Mp, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace,
+                                         sinkhorn_f64_workspace_bytes(B, Np, Mp), word, group, nullptr, counts0, counts1)) return rc;
+    }
+    return s64_ragged_finish(who, word, s);
+}
+
+extern "C" int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                                 const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
+                                                 float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                                 float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_sinkhorn_f64_extract_ragged";
+    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
+    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (int rc = s64_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
+    if (s64_form() == 1) { mdgat_set_error("%s: the streaming form (mdgat_set_f64_sinkhorn_form(1)) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
+    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned* word = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + s64_ragged_word_offset(B, Np, Mp));
+    if (int rc = mdgat_check_hip(hipMemsetAsync(word, 0, 256, s), "memset(fp64 Sinkhorn error word)")) return rc;
+    const size_t kb = sinkhorn_f64_workspace_bytes(B, Np, Mp);
+    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, Np, Mp);
+    const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
+    {
+        CoopGroup group;
+        if (int rc = group.open(mdgat_current_device(), s)) return rc;
+        if (int rc = launch_sinkhorn_f64(B, Np, Mp, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv, workspace, kb, word, group,
+                                         nullptr, counts0, counts1)) return rc;
+    }
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
+    if (int rc = launch_extract_from_bests(B, Np, Mp, &ex, b.ri, b.rv, b.ci, b.cv, s, counts0, counts1)) return rc;
+    return s64_ragged_finish(who, word, s);
 }

@@ -9,11 +9,17 @@ class CoopGroup;      // coop_chain.hpp
 // (rbest [B][N]: per row over the columns - the inner M ones when `inner`, else including the dustbin; cbest [B][M] per column over the
 // rows, the slabs of a pair merged in fp64; both decided on the fp64 values, the values handed on as fp32).  workspace: 256-byte aligned,
 // sinkhorn_f64_workspace_bytes.  error_word: bit 0 raised when a workgroup gave up waiting for a partner (optional).
+// cnt0 / cnt1 (device int32 [B], both or neither): a RAGGED batch - pair b has cnt0[b] x cnt1[b] keypoints (1 <= cnt0[b] <= N, 1 <= cnt1[b] <= M,
+// checked by the caller) and is stored in slots padded to N x M, which are then the strides of every array here and must fit the
+// register-resident form (at most 575).  Pair b's block Z[b, :cnt0[b]+1, :cnt1[b]+1] and its arg-maxes have the bits of the pair run alone;
+// the rest of its Z slot is zero, rbest / cbest beyond its counts are not written.
 size_t sinkhorn_f64_workspace_bytes(int B, int N, int M);
 bool sinkhorn_f64_supported(int N, int M);
+bool sinkhorn_f64_ragged_supported(int N, int M);      // per-pair counts: the register-resident form only (padded sizes <= 575, form not forced to streaming)
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
                         float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
-                        CoopGroup& group, const double* alpha_dev = nullptr);      // on the group's stream; alpha_dev: the bin score on the device (replaces alpha)
+                        CoopGroup& group, const double* alpha_dev = nullptr,       // on the group's stream; alpha_dev: the bin score on the device (replaces alpha)
+                        const int* cnt0 = nullptr, const int* cnt1 = nullptr);
 // rbest / cbest (idx + val each) for the extraction, carved behind the kernel's own workspace (a null base: their size only)
 struct Sk64Bests { int* ri; float* rv; int* ci; float* cv; size_t bytes; };
 Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M);

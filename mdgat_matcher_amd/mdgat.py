@@ -463,6 +463,155 @@ class MDGAT(nn.Module):
             'loss': loss,
         }
 
+    RAGGED_MAX_KEYPOINTS = 575      # what the register-resident fp64 Sinkhorn holds (csrc/sinkhorn_f64.hip)
+
+    def _ragged_early_out(self, pair):
+        """the dict of mdgat.py:374-382 for a pair with an empty frame, as ``forward`` returns it"""
+        k0, k1 = (pair[k] if pair[k].dim() == 3 else pair[k][None] for k in ('keypoints0', 'keypoints1'))
+        shape0, shape1 = k0.shape[:-1], k1.shape[:-1]
+        return {
+            'matches0': k0.new_full(shape0, -1, dtype=torch.int)[0],
+            'matches1': k1.new_full(shape1, -1, dtype=torch.int)[0],
+            'matching_scores0': k0.new_zeros(shape0, dtype=torch.float64)[0],
+            'matching_scores1': k1.new_zeros(shape1, dtype=torch.float64)[0],
+            'skip_train': True,
+        }
+
+    def _ragged_checked(self, packed):
+        """Everything the library assumes of a packed ragged batch, checked before the call (as ``_run`` checks a uniform one): six
+        tensors [B, Np | Mp(, 3 | 33)] with one B, count vectors of B entries within the slots and the kernels' limits."""
+        h0, h1 = packed['counts0_host'], packed['counts1_host']
+        B = int(h0.numel())
+        if h0.dim() != 1 or tuple(h1.shape) != (B,) or tuple(packed['counts0'].shape) != (B,) or tuple(packed['counts1'].shape) != (B,):
+            raise ValueError(f'ragged batch: the four count vectors must hold one entry per pair (counts0_host {tuple(h0.shape)}, counts1_host '
+                             f"{tuple(h1.shape)}, counts0 {tuple(packed['counts0'].shape)}, counts1 {tuple(packed['counts1'].shape)})")
+        k0, k1 = packed['keypoints0'], packed['keypoints1']
+        if k0.dim() != 3 or k1.dim() != 3 or k0.shape[-1] != 3 or k1.shape[-1] != 3 or packed['descriptors0'].shape[-1] != 33 or \
+                packed['descriptors1'].shape[-1] != 33:
+            raise ValueError('expected keypoints [B, N, 3] and 33-D FPFH descriptors [B, N, 33]')
+        Np, Mp = int(k0.shape[1]), int(k1.shape[1])
+        for f, P in (('0', Np), ('1', Mp)):
+            for key, tail in (('keypoints', (3,)), ('scores', ()), ('descriptors', (33,))):
+                if tuple(packed[key + f].shape) != (B, P) + tail:
+                    raise ValueError(f'ragged batch: {key}{f} has shape {tuple(packed[key + f].shape)}: expected {(B, P) + tail} '
+                                     f'({B} pairs by the count vectors)')
+        kmax = max([int(k) for k in self._topk_schedule()] + [0])
+        for b in range(B):
+            n, m = int(h0[b]), int(h1[b])
+            if n > self.RAGGED_MAX_KEYPOINTS or m > self.RAGGED_MAX_KEYPOINTS:
+                raise ValueError(f'pair {b} has {n} x {m} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
+            if min(n, m) < max(kmax, 1):
+                raise ValueError(f'pair {b} has {n} x {m} keypoints: fewer than a dynamic layer keeps (k={kmax}; torch.topk raises in the reference)')
+            if n > Np or m > Mp:
+                raise ValueError(f'pair {b} has {n} x {m} keypoints in slots of {Np} x {Mp}')
+        if Np > self.RAGGED_MAX_KEYPOINTS or Mp > self.RAGGED_MAX_KEYPOINTS:
+            raise ValueError(f'slots of {Np} x {Mp} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
+        return B, Np, Mp
+
+    def _run_ragged(self, packed, return_Z):
+        """One ragged forward through the library: the PADDED device outputs (matches -1 and scores 0 beyond a pair's counts), the host
+        counts and - in the dustbin modes, with the call's one synchronisation - which pairs matched anything (mdgat.py:465, per pair)."""
+        from . import ops
+        if not self.exact() or self.bin_score.dtype != torch.float64:
+            raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'")
+        if self.training or getattr(self, 'eval_loss', False):
+            raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)')
+        B, Np, Mp = self._ragged_checked(packed)
+        probe = packed['keypoints0']
+        if not probe.is_cuda:
+            raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP device; there is no CPU fallback')
+        dev = probe.device
+        st = self._state_for(dev)
+        ins = [packed[k].to(device=dev, dtype=torch.float64).contiguous()
+               for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
+        d0, d1, h0, h1 = ops._ragged_counts(packed, B, dev)
+        lib = _lib.load()
+        with torch.cuda.device(dev), st.lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, B, Np, Mp), dev)
+            m0 = torch.empty((B, Np), dtype=torch.int64, device=dev)
+            m1 = torch.empty((B, Mp), dtype=torch.int64, device=dev)
+            s0 = torch.empty((B, Np), dtype=torch.float32, device=dev)
+            s1 = torch.empty((B, Mp), dtype=torch.float32, device=dev)
+            Z = torch.empty((B, Np + 1, Mp + 1), dtype=torch.float32, device=dev) if return_Z else None
+            _lib.check(lib.mdgat_forward_f64_ragged(st.handle, B, Np, Mp, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(),
+                                                    *[t.data_ptr() for t in ins], m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(),
+                                                    Z.data_ptr() if Z is not None else None, None, ws.data_ptr(), ws.numel(), stream),
+                       'mdgat_forward_f64_ragged')
+        dustbin = self.loss_method != 'superglue'
+        # the one synchronisation: which pairs matched nothing comes to the host with it
+        matched = (m0 >= 0).any(dim=1).cpu() if dustbin else None
+        self.check(dev, synchronize=not dustbin)
+        return m0, m1, s0, s1, Z, h0, h1, matched
+
+    def _ragged_dicts(self, padded, return_Z):
+        """the per-pair dicts of ``forward`` from the padded outputs of ``_run_ragged`` (views, no copies)"""
+        m0, m1, s0, s1, Z, h0, h1, matched = padded
+        out_dtype = self.bin_score.dtype
+        outs = []
+        for b in range(m0.shape[0]):
+            n, m = int(h0[b]), int(h1[b])
+            pm0, pm1 = m0[b:b + 1, :n], m1[b:b + 1, :m]
+            if matched is not None and not bool(matched[b]):
+                ps0, ps1 = torch.zeros_like(pm0), torch.zeros_like(pm1)       # INTEGER zeros, as the reference's torch.zeros_like(indices)
+            else:
+                ps0, ps1 = s0[b:b + 1, :n].to(out_dtype), s1[b:b + 1, :m].to(out_dtype)
+            d = {'matches0': pm0, 'matches1': pm1, 'matching_scores0': ps0, 'matching_scores1': ps1, 'loss': m0.new_zeros((), dtype=out_dtype)}
+            if return_Z:
+                d['Z'] = Z[b:b + 1, :n + 1, :m + 1]
+            outs.append(d)
+        return outs
+
+    @torch.no_grad()
+    def forward_ragged(self, pairs_or_packed, return_Z=False):
+        """``forward`` on B pairs of DIFFERENT sizes in one call of the library: a list of the reference's per-pair dicts, as its
+        ``batch_size=1`` loader yields them (test.py:132), or what ``ops.pack_ragged`` made of them.  Returns a list of B dicts, each
+        what ``forward`` returns for that pair alone - keys, dtypes, the leading batch axis of 1 (``matches0`` [1, N_b]), the integer-zero
+        scores of a pair that matched nothing (mdgat.py:464-467, per pair), bit for bit under ``mdgat_set_f64_attention_form(0)`` (but
+        for a pair with as many keypoints in both frames as a dynamic layer's k: to rounding, include/mdgat_hip.h) - plus ``'Z'``
+        [1, N_b + 1, M_b + 1] float32 with ``return_Z``.  A pair with an empty frame (list input only) gets the early-out dict
+        of mdgat.py:374-382 and is left out of the launch.  One call into the library and one synchronisation.
+
+        The exact mode only (a float64 module in eval() mode, no ``eval_loss``): ``NotImplementedError`` otherwise.  ``ValueError`` for a
+        frame of more than 575 keypoints or of fewer than a dynamic layer's k, and for tensors that are not [B, N, 3] / [B, N] /
+        [B, N, 33] with one B and count vectors of B entries."""
+        from . import ops
+        if isinstance(pairs_or_packed, dict):
+            return self._ragged_dicts(self._run_ragged(pairs_or_packed, return_Z), return_Z)
+        pairs = list(pairs_or_packed)
+        empty = [p['keypoints0'].shape[-2] == 0 or p['keypoints1'].shape[-2] == 0 for p in pairs]
+        results = [self._ragged_early_out(p) if e else None for p, e in zip(pairs, empty)]
+        order = [i for i, e in enumerate(empty) if not e]
+        if order:
+            packed = ops.pack_ragged([pairs[i] for i in order], device=self.bin_score.device)
+            for i, d in zip(order, self._ragged_dicts(self._run_ragged(packed, return_Z), return_Z)):
+                results[i] = d
+        return results
+
+    @torch.no_grad()
+    def evaluate_ragged(self, pairs_or_packed):
+        """``forward_ragged`` and then the evaluation scripts' per-pair record of every pair in ONE launch (``ops.evaluate_matches`` with
+        the pairs' counts, on the forward's own padded outputs) against their ``gt_matches0/1`` and ``T_gt`` (optional): ``{'pairs': the
+        forward's list of dicts, 'metrics': [B, len(ops.EvalColumns)] float64, 'T': [B, 4, 4]}``, rows and poses bit for bit
+        ``evaluate``'s on each pair alone - so the scripts' loop over a chunk of pairs becomes
+        ``meter.update(net.evaluate_ragged(chunk))``.  Pairs with an empty frame have nothing to evaluate (``evaluate`` returns None for
+        them): ``ValueError``."""
+        from . import ops
+        packed = pairs_or_packed if isinstance(pairs_or_packed, dict) else None
+        if packed is None:
+            pairs = list(pairs_or_packed)
+            if any(p['keypoints0'].shape[-2] == 0 or p['keypoints1'].shape[-2] == 0 for p in pairs):
+                raise ValueError('evaluate_ragged: a pair with an empty frame has nothing to evaluate (mdgat.py:374-382): leave it out')
+            packed = ops.pack_ragged(pairs, device=self.bin_score.device)
+        if 'gt_matches0' not in packed or 'gt_matches1' not in packed:
+            raise KeyError('gt_matches0')                  # as evaluate() on a dict without them
+        padded = self._run_ragged(packed, False)
+        m0, m1 = padded[0], padded[1]
+        dev = m0.device
+        metrics, T, _ = ops.evaluate_matches(m0, m1, packed['gt_matches0'], packed['gt_matches1'], packed['keypoints0'].to(dev),
+                                             packed['keypoints1'].to(dev), T_gt=packed.get('T_gt'), counts=packed)
+        return {'pairs': self._ragged_dicts(padded, False), 'metrics': metrics, 'T': T}
+
     def training_forward(self, data):
         """The reference's forward (mdgat.py:369-603, descriptor='FPFH') in fp64 with BatchNorm as ``self.training`` says, composed from the
         differentiable device primitives (``mdgat_matcher_amd/train.py``): the reference's dict, whose ``loss`` (0-d for superglue /

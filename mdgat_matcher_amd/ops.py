@@ -64,14 +64,101 @@ def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: i
     return (m0, m1, s0, s1, Zbuf) if want_Z else (m0, m1, s0, s1)
 
 
-def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int) -> torch.Tensor:
-    """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64."""
+_RAGGED_KEYS = (('keypoints', 2), ('scores', 1), ('descriptors', 2))      # per-frame inputs and their rank without a batch axis
+
+
+def pack_ragged(pairs, device=None) -> dict:
+    """A ragged batch from per-pair dicts, as the reference's ``batch_size=1`` loader yields them (test.py:132): ``keypoints0/1``
+    [N_b, 3], ``scores0/1`` [N_b], ``descriptors0/1`` [N_b, C], with or without a leading batch axis of 1, every pair with its own
+    keypoint counts.  Returns the float64 tensors padded with zeros to ``Np = max N_b`` / ``Mp = max M_b`` and stacked, ``counts0`` /
+    ``counts1`` (int32 [B], on the tensors' device) with their host copies ``counts0_host`` / ``counts1_host`` (CPU tensors: what the
+    library checks before it launches anything), and - where every pair carries them - ``gt_matches0/1`` (int64, padded with -1) and
+    ``T_gt`` [B, 4, 4].  Pure torch: it runs on CPU tensors too.  ``device``: where the result lives (default: where the first pair's
+    keypoints are)."""
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError('pack_ragged: no pairs')
+    if device is None:
+        device = pairs[0]['keypoints0'].device
+
+    def one(t, rank, what):
+        t = torch.as_tensor(t)
+        if t.dim() == rank + 1 and t.shape[0] == 1:
+            t = t[0]
+        if t.dim() != rank:
+            raise ValueError(f'pack_ragged: {what} has shape {tuple(t.shape)}: expected rank {rank}, or a leading axis of 1')
+        return t
+
+    B = len(pairs)
+    out, counts = {}, {}
+    for f in '01':
+        cols = {k: [one(p[k + f], r, k + f) for p in pairs] for k, r in _RAGGED_KEYS}
+        n = [int(t.shape[0]) for t in cols['keypoints']]
+        for k, _ in _RAGGED_KEYS:
+            for b, t in enumerate(cols[k]):
+                if int(t.shape[0]) != n[b] or t.shape[1:] != cols[k][0].shape[1:]:
+                    raise ValueError(f'pack_ragged: pair {b}: {k}{f} has shape {tuple(t.shape)}, keypoints{f} {n[b]} rows')
+        counts[f] = n
+        P = max(n)
+        for k, _ in _RAGGED_KEYS:
+            buf = torch.zeros((B, P) + tuple(cols[k][0].shape[1:]), dtype=torch.float64, device=device)
+            for b, t in enumerate(cols[k]):
+                buf[b, :n[b]] = t.to(device=device, dtype=torch.float64)
+            out[k + f] = buf
+        if all('gt_matches' + f in p for p in pairs):
+            gt = torch.full((B, P), -1, dtype=torch.int64, device=device)
+            for b, p in enumerate(pairs):
+                t = one(p['gt_matches' + f], 1, 'gt_matches' + f)
+                if int(t.shape[0]) != n[b]:
+                    raise ValueError(f'pack_ragged: pair {b}: gt_matches{f} has {int(t.shape[0])} entries, keypoints{f} {n[b]} rows')
+                gt[b, :n[b]] = t.to(device=device, dtype=torch.int64)
+            out['gt_matches' + f] = gt
+        host = torch.tensor(n, dtype=torch.int32)
+        out['counts' + f + '_host'] = host
+        out['counts' + f] = host.to(device)
+    if all('T_gt' in p for p in pairs):
+        out['T_gt'] = torch.stack([one(p['T_gt'], 2, 'T_gt').to(device=device, dtype=torch.float64) for p in pairs])
+    return out
+
+
+def _ragged_counts(counts, B, device):
+    """counts: a pack_ragged dict, or (counts0, counts1) as tensors or sequences -> device and host int32 copies of both."""
+    if isinstance(counts, dict):
+        h0, h1 = counts['counts0_host'], counts['counts1_host']
+    else:
+        h0, h1 = (torch.as_tensor(c).detach().to('cpu', torch.int32).contiguous() for c in counts)
+    h0, h1 = h0.to(torch.int32).contiguous(), h1.to(torch.int32).contiguous()
+    if h0.shape != (B,) or h1.shape != (B,):
+        raise ValueError(f'counts: expected two vectors of {B} entries, got {tuple(h0.shape)} / {tuple(h1.shape)}')
+    if isinstance(counts, dict) and counts['counts0'].device == device:
+        d0, d1 = counts['counts0'].contiguous(), counts['counts1'].contiguous()
+    else:
+        d0, d1 = h0.to(device), h1.to(device)
+    return d0, d1, h0, h1
+
+
+def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None) -> torch.Tensor:
+    """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64.
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b is ``scores[b, :counts0[b], :counts1[b]]``,
+    the rest of its slot is never read.  ``Z[b, :counts0[b]+1, :counts1[b]+1]`` then has the bits of the pair run alone (its dustbins at
+    row ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0.  N, M <= 575; the forward only."""
     _need_cuda(scores)
+    if counts is not None and scores.requires_grad:
+        raise RuntimeError('sinkhorn_f64(counts=): ragged batches run the forward only (no gradient)')
     s = scores.to(torch.float64).contiguous()
     B, N, M = s.shape
     Z = torch.empty((B, N + 1, M + 1), dtype=torch.float64, device=s.device)
     lib = _lib.load()
     with torch.cuda.device(s.device):
+        if counts is not None:
+            d0, d1, h0, h1 = _ragged_counts(counts, B, s.device)
+            need = lib.mdgat_sinkhorn_f64_ragged_workspace_bytes(B, N, M)
+            ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
+            off = (-ws.data_ptr()) % 256
+            _lib.check(lib.mdgat_sinkhorn_f64_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), s.data_ptr(), float(bin_score),
+                                                     int(iters), Z.data_ptr(), ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_f64_ragged')
+            return Z
         need = lib.mdgat_sinkhorn_f64_workspace_bytes(B, N, M)
         ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
         off = (-ws.data_ptr()) % 256
@@ -81,9 +168,14 @@ def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int) -> torch.Te
 
 
 def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2,
-                         want_Z: bool = False):
-    """fp64 Sinkhorn + match extraction with every arg-max decided on the fp64 Z: (matches0, matches1, mscores0, mscores1[, Z fp32])."""
+                         want_Z: bool = False, counts=None):
+    """fp64 Sinkhorn + match extraction with every arg-max decided on the fp64 Z: (matches0, matches1, mscores0, mscores1[, Z fp32]).
+
+    ``counts`` as in ``sinkhorn_f64``: pair b's matches and scores are those of the pair run alone (no match: -1; the rule of
+    mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0."""
     _need_cuda(scores)
+    if counts is not None and scores.requires_grad:
+        raise RuntimeError('sinkhorn_f64_extract(counts=): ragged batches run the forward only (no gradient)')
     s = scores.to(torch.float64).contiguous()
     B, N, M = s.shape
     m0 = torch.empty((B, N), dtype=torch.int64, device=s.device)
@@ -93,6 +185,16 @@ def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mod
     Z = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=s.device) if want_Z else None
     lib = _lib.load()
     with torch.cuda.device(s.device):
+        if counts is not None:
+            d0, d1, h0, h1 = _ragged_counts(counts, B, s.device)
+            need = lib.mdgat_sinkhorn_f64_ragged_workspace_bytes(B, N, M)
+            ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
+            off = (-ws.data_ptr()) % 256
+            _lib.check(lib.mdgat_sinkhorn_f64_extract_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), s.data_ptr(),
+                                                             float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
+                                                             m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None,
+                                                             ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_f64_extract_ragged')
+            return (m0, m1, s0, s1, Z) if want_Z else (m0, m1, s0, s1)
         need = lib.mdgat_sinkhorn_f64_workspace_bytes(B, N, M)
         ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
         off = (-ws.data_ptr()) % 256
@@ -370,14 +472,17 @@ EvalColumns = _EvalColumns((name, i) for i, name in enumerate(_lib.EVAL_COLUMNS)
 
 
 def evaluate_matches(matches0: torch.Tensor, matches1: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor, kpts0: torch.Tensor,
-                     kpts1: torch.Tensor, T_gt=None, inlier_dist: float = 1.0):
+                     kpts1: torch.Tensor, T_gt=None, inlier_dist: float = 1.0, counts=None):
     """What test.py:212-296 and test_registration_metric.py:213-264 derive per pair from the matcher's output, on the device:
     matches0 / gt0 [B, N], matches1 / gt1 [B, M] (-1, or the dustbin value M / N in the gts, = unmatched), kpts [B, N, 3] / [B, M, 3]
     and T_gt [B, 4, 4] as ``pose_from_matches`` takes them.  Returns (metrics [B, len(EvalColumns)] float64, T [B, 4, 4] float64,
     EvalColumns): counts exact, every ratio bit for bit numpy's value (0/0 = NaN and x/0 = inf where the script does not guard), the
     pose columns ``pose_from_matches``' arithmetic, and a status column with the scripts' skip rules as bits - the row is filled either
     way (``EvalMeter`` applies the rules).  A gt outside [-1, M] / [-1, N] raises ``IndexError`` like the loss; the tensors are not
-    rewritten.  Reading the bad-index word synchronises, as in ``matching_loss``."""
+    rewritten.  Reading the bad-index word synchronises, as in ``matching_loss``.
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch in padded slots - pair b's row and T are those of the pair
+    alone, what lies beyond its counts (the -1 padding of matches and gts, the zero keypoints) is not read."""
     _need_cuda(matches0, kpts0, kpts1)
     dev = kpts0.device
     k0 = kpts0.to(torch.float32).contiguous()
@@ -394,9 +499,16 @@ def evaluate_matches(matches0: torch.Tensor, matches1: torch.Tensor, gt0: torch.
     T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().mdgat_eval_metrics(B, N, M, m0.data_ptr(), m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(),
-                                                  k1.data_ptr(), g.data_ptr() if g is not None else None, float(inlier_dist),
-                                                  metrics.data_ptr(), T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics')
+        if counts is not None:
+            d0, d1, h0, h1 = _ragged_counts(counts, B, dev)
+            _lib.check(_lib.load().mdgat_eval_metrics_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), m0.data_ptr(),
+                                                             m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(), k1.data_ptr(),
+                                                             g.data_ptr() if g is not None else None, float(inlier_dist), metrics.data_ptr(),
+                                                             T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics_ragged')
+        else:
+            _lib.check(_lib.load().mdgat_eval_metrics(B, N, M, m0.data_ptr(), m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(),
+                                                      k1.data_ptr(), g.data_ptr() if g is not None else None, float(inlier_dist),
+                                                      metrics.data_ptr(), T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics')
     if int(bad.item()):
         raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1), or the matches one outside '
                          f'[-1, {M}) / [-1, {N})')
@@ -525,7 +637,7 @@ def pointwise_f64(a: torch.Tensor, w: torch.Tensor, bias=None, relu: bool = Fals
     return out
 
 
-def _attention_f64_values(qkv, N, M, cross, topk, want_sel):
+def _attention_f64_values(qkv, N, M, cross, topk, want_sel, counts=None):
     """The forward launch of ``attention_f64``: (message, the raw selection words or None)."""
     _need_cuda(qkv)
     x = qkv.detach().to(torch.float64).contiguous()
@@ -534,6 +646,12 @@ def _attention_f64_values(qkv, N, M, cross, topk, want_sel):
     msg = torch.empty((B, P, 128), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if want_sel else None
+        if counts is not None:
+            d0, d1, h0, h1 = _ragged_counts(counts, B, x.device)
+            _lib.check(_lib.load().mdgat_attention_f64_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), int(bool(cross)),
+                                                              int(topk), x.data_ptr(), msg.data_ptr(), sel.data_ptr() if sel is not None else None,
+                                                              _stream(x)), 'mdgat_attention_f64_ragged')
+            return msg, sel
         _lib.check(_lib.load().mdgat_attention_f64(B, N, M, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
                                                    sel.data_ptr() if sel is not None else None, _stream(x)), 'mdgat_attention_f64')
     return msg, sel
@@ -596,16 +714,25 @@ class _AttentionF64(torch.autograd.Function):
         return dqkv.to(qkv.dtype), None, None, None, None, None
 
 
-def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False):
+def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None):
     """attention / dynamic_attention (mdgat.py:190-210) in fp64.  qkv [B, N+M, 3, 4, 32] float64 -> message [B, N+M, 128] float64
     (with ``return_selection``: also the masks of the keys a dynamic layer kept, see topk_sel_to_masks).
 
     Differentiable with respect to qkv (``attention_f64_backward``; not twice): when qkv requires grad and grad is enabled the message
     carries a grad_fn.  The launch and the values are the same either way; a dynamic layer then always asks for the selection words
     and saves them for the backward (16 MB at 64 pairs of 512), which reads them instead of selecting again.  The masks are not
-    differentiable."""
+    differentiable.
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b has ``counts0[b]`` / ``counts1[b]`` keypoints in
+    slots padded to N / M (frame 1 from row N on).  Its rows are those of the pair run alone (bit for bit where both launches run the same
+    kernel form, the kept keys always); message rows and masks beyond its counts are zero / False.  The forward only."""
     B = qkv.shape[0]
     topk = int(topk)
+    if counts is not None:
+        if qkv.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError('attention_f64(counts=): ragged batches run the forward only (no gradient)')
+        msg, sel = _attention_f64_values(qkv, N, M, cross, topk, return_selection, counts)
+        return (msg, topk_sel_to_masks(sel, B, N, M, cross)) if return_selection else msg
     if torch.is_grad_enabled() and qkv.requires_grad:
         want_sel = topk > 0 or return_selection       # a dynamic layer always keeps its selection words
         out = _AttentionF64.apply(qkv, N, M, bool(cross), topk, want_sel)
