@@ -147,6 +147,19 @@ int mdgat_load_weights_f64(mdgat_handle* h, const double* blob, size_t n_doubles
 /* Device pointer to the handle's fp64 blob (NULL before mdgat_load_weights_f64; for an RCCL broadcast). */
 double* mdgat_weights_f64_device_ptr(mdgat_handle* h);
 
+/* descriptor = 'FPFH_gloabal' (mdgat.py:156-174, 342-347): the second MLP of the pooled descriptor encoder, which the blob has no room
+ * for.  `w` holds mdgat_pooled_encoder_doubles() fp64 values as pack.py's pack_pooled_encoder lays them out: encoder2.0 folded with its
+ * BatchNorm and split into W1e [256][128] (the columns that read the keypoint's own encoder output e) and W1g [256][128] (those that read
+ * the frame maximum of e), its bias [256], then [encoder2.3 | kenc.9] [128][384] over [hidden ; the keypoint encoder's last hidden layer]
+ * and the sum of the two biases [128].  The blob of such a checkpoint carries [denc.6 | 0] and denc.6's bias as its encl.  MDGAT_ARITH_FP64
+ * handles only (MDGAT_ERR_BAD_ARG otherwise); call it after mdgat_load_weights_f64.  From then on every forward of the handle runs
+ * desc = encoder2([e ; max over the frame's own keypoints of e]) + kenc(...) in fp64, one product per launch (csrc/api.hip:
+ * pooled_encoder64, csrc/pool_f64.hip) - with f64_layers = MDGAT_F64_ENCODERS_ONLY and f64_sinkhorn = MDGAT_F64_SINKHORN_OFF the
+ * encoders alone, everything behind them on the fp32-class path.  In a ragged batch the maximum runs over a pair's counts.  A handle
+ * this entry was never called on behaves exactly as before. */
+int mdgat_load_pooled_encoder_f64(mdgat_handle* h, const double* w, size_t n_doubles, int on_device);
+size_t mdgat_pooled_encoder_doubles(void);
+
 /* Device pointer to the handle's packed weights (for an RCCL broadcast from rank 0). */
 float* mdgat_weights_device_ptr(mdgat_handle* h);
 
@@ -506,6 +519,12 @@ int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0, const doub
                            const double* dout, const mdgat_mlp_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
 /* part 0: the forward's `saved`; part 1: the backward's workspace.  0 for a descriptor the calls refuse (and for R == 0) */
 size_t mdgat_mlp_workspace_bytes(const mdgat_mlp_desc* d, int part);
+
+/* The frame maximum of the pooled descriptor encoder as a call of its own (the training path: ops.frame_max_f64).  e [B][n][128] fp64 ->
+ * g [B][128] = max over the n rows, idx [B][128] (optional) the FIRST row that holds it.  The backward writes dg [B][128] to row idx of
+ * de [B][n][128] and zero elsewhere: the indices are the forward's, never decided again; one writer per element, no atomics. */
+int mdgat_frame_max_f64(int B, int n, const double* e, double* g, int64_t* idx, void* stream);
+int mdgat_frame_max_backward_f64(int B, int n, const double* dg, const int64_t* idx, double* de, void* stream);
 
 /* match extraction (mdgat.py:441-483) from Z [B][N+1][M+1]. */
 int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold,

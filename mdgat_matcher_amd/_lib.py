@@ -97,6 +97,10 @@ SIGNATURES = {
     'mdgat_load_weights': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     'mdgat_load_weights_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     'mdgat_weights_f64_device_ptr': (C.c_void_p, [C.c_void_p]),
+    'mdgat_load_pooled_encoder_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    'mdgat_pooled_encoder_doubles': (C.c_size_t, []),
+    'mdgat_frame_max_f64': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'mdgat_frame_max_backward_f64': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mdgat_blob_floats': (C.c_size_t, [C.c_int]),
     'mdgat_weights_device_ptr': (C.c_void_p, [C.c_void_p]),
     'mdgat_destroy': (None, [C.c_void_p]),

@@ -12,6 +12,7 @@
 #include "coop_chain.hpp"
 #include "loss.hpp"
 #include "weights.hpp"
+#include "pool_f64.hpp"
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -64,6 +65,7 @@ struct mdgat_handle {
     int device = 0;
     DeviceWeights w;     // the device copies of the checkpoint and their layout (weights.hpp)
     bool loaded = false, loaded64 = false;
+    double* pool64 = nullptr;       // mdgat_load_pooled_encoder_f64: encoder2 of the pooled descriptor encoder (PoolLayout), else nullptr
     unsigned* host_error = nullptr; // MDGAT_STATUS_WORDS host-mapped words the kernels set (common.hpp): Sinkhorn fallback taken, f16 range guard,
                                     // token of the last forward that matched a frame-0 keypoint
     unsigned match_token = 0;       // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
@@ -219,9 +221,35 @@ extern "C" int mdgat_load_weights_f64(mdgat_handle* h, const double* blob, size_
     return MDGAT_OK;
 }
 
+// ---- descriptor = 'FPFH_gloabal' (mdgat.py:156-174): encoder2 of the pooled descriptor encoder, beside the blob (pack.py: pack_pooled_encoder) ----
+namespace PoolLayout {
+constexpr size_t W1E = 0;                      // encoder2.0 (BN folded), the columns that read the keypoint's own e   [256][128]
+constexpr size_t W1G = W1E + 256 * 128;        // ... the columns that read the frame maximum g                         [256][128]
+constexpr size_t B1 = W1G + 256 * 128;         // its bias                                                              [256]
+constexpr size_t W2K = B1 + 256;               // [encoder2.3 | kenc.9] over [hidden (256) ; hk3 (128)]                 [128][384]
+constexpr size_t B2 = W2K + 128 * 384;         // encoder2.3.bias + kenc.9.bias                                         [128]
+constexpr size_t TOTAL = B2 + 128;
+}
+
+extern "C" size_t mdgat_pooled_encoder_doubles(void) { return PoolLayout::TOTAL; }
+
+extern "C" int mdgat_load_pooled_encoder_f64(mdgat_handle* h, const double* w, size_t n_doubles, int on_device) {
+    const char* who = "mdgat_load_pooled_encoder_f64";
+    if (!h || !w) { mdgat_set_error("%s: null argument", who); return MDGAT_ERR_BAD_ARG; }
+    if (h->cfg.arithmetic != MDGAT_ARITH_FP64) { mdgat_set_error("%s: the handle was not created with MDGAT_ARITH_FP64 (the pooled encoder runs on the fp64 products)", who); return MDGAT_ERR_BAD_ARG; }
+    if (n_doubles != PoolLayout::TOTAL) { mdgat_set_error("%s: %zu doubles, expected %zu", who, n_doubles, PoolLayout::TOTAL); return MDGAT_ERR_BAD_ARG; }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    int rc = mdgat_check_hip(hipSetDevice(h->device), "hipSetDevice");
+    if (!rc && !h->pool64) rc = mdgat_check_hip(hipMalloc(&h->pool64, PoolLayout::TOTAL * sizeof(double)), "hipMalloc(pooled encoder)");
+    if (!rc) rc = mdgat_check_hip(hipMemcpy(h->pool64, w, n_doubles * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice), "hipMemcpy(pooled encoder)");
+    (void)hipSetDevice(prev);
+    return rc;
+}
+
 extern "C" void mdgat_destroy(mdgat_handle* h) {
     if (!h) return;
-    for (void* p : {(void*)h->w.blob, (void*)h->w.split, (void*)h->w.blob64, (void*)h->w.frag64})
+    for (void* p : {(void*)h->w.blob, (void*)h->w.split, (void*)h->w.blob64, (void*)h->w.frag64, (void*)h->pool64})
         if (p) (void)hipFree(p);
     if (h->host_error) (void)hipHostFree(h->host_error);
     if (h->lane_stream) { (void)hipStreamSynchronize(h->lane_stream); (void)hipStreamDestroy(h->lane_stream); }
@@ -553,6 +581,11 @@ struct Fwd {
         const GemmF64Args g{A0, K0, K0, A1, lda1, w64 + m.w, m.K, w64 + m.b, Rs, m.rows, C, m.rows, R, m.rows, m.K, relu, guard()};
         return launch_gemm_f64(g, s);
     }
+    // the same with a matrix outside the blob: W [n][K] (row pitch ldw), the K input columns from A0 (K0) and A1, over `rows` rows
+    int gemm64(const double* W, int ldw, const double* bias, int n, int K, const double* A0, int K0, const double* A1, int lda1, int relu, double* C, int rows) const {
+        const GemmF64Args g{A0, K0, K0, A1, lda1, W, ldw, bias, nullptr, n, C, n, rows, n, K, relu, guard()};
+        return launch_gemm_f64(g, s);
+    }
 };
 
 // ---- encoders (mdgat.py:392-393), one fused launch ----
@@ -562,6 +595,38 @@ static int encoders32(Fwd& f, const FwdIn& in) {
     if (int rc = launch_encoder(e, f.s)) return rc;
     f.mark(MDGAT_PROF_ENCODER);
     return f.tap(f.taps.x_enc, f.ws.x, (size_t)f.R * 128, "tap x_enc");
+}
+
+// ---- descriptor = 'FPFH_gloabal' (mdgat_load_pooled_encoder_f64): desc = encoder2([e ; max over the frame of e]) + kenc, e = denc.encoder ----
+// One product per launch.  The frame maximum g is taken over a pair's OWN keypoints (the counts of a ragged batch), its half of encoder2.0
+// is formed once per (pair, frame) - 2B rows, not R - and joins the keypoint half in an epilogue of its own; encoder2.3 and kenc.9 are one
+// product over [hidden ; hk3], as the blob's encl is for 'FPFH'.  Then layer 0's q | k | v by the plain product when the layer tails are fused
+// (the fused encoder launch, which would have written it, does not run).
+// The q | k | v + hidden area (640 doubles per point) in units of R doubles: hk3 0..128 | hk1 128..160, hk2 ..224, hd1 ..288, hd2 ..416, later
+// hidden 128..384 | c (2B x 256 <= 256 R) from 384 | the assembled inputs in the last 37.  e lives in the message area, g (2B x 128) in x's.
+static int pooled_encoder64(Fwd& f, const double* in4, const double* in33) {
+    const Workspace& ws = f.ws;
+    const DeviceWeights& w = f.h->w;
+    const double* pw = f.h->pool64;
+    const size_t Rz = (size_t)f.R;
+    double *hk3 = ws.qkv64, *hk1 = hk3 + Rz * 128, *hk2 = hk1 + Rz * 32, *hd1 = hk2 + Rz * 64, *hd2 = hd1 + Rz * 64;
+    double *hidden = ws.qkv64 + Rz * 128, *c = ws.qkv64 + Rz * 384, *e = ws.msg64, *g = ws.x64;
+    if (int rc = f.gemm64(w.im.enc(ENC_K0), in4, 4, nullptr, 0, 1, nullptr, hk1)) return rc;
+    if (int rc = f.gemm64(w.im.enc(ENC_K1), hk1, 32, nullptr, 0, 1, nullptr, hk2)) return rc;
+    if (int rc = f.gemm64(w.im.enc(ENC_K2), hk2, 64, nullptr, 0, 1, nullptr, hk3)) return rc;
+    if (int rc = f.gemm64(w.im.enc(ENC_D0), in33, 33, nullptr, 0, 1, nullptr, hd1)) return rc;
+    if (int rc = f.gemm64(w.im.enc(ENC_D1), hd1, 64, nullptr, 0, 1, nullptr, hd2)) return rc;
+    // e = denc.encoder.6 alone: the first 128 columns of the blob's encl ([denc.6 | 0] for this descriptor, its bias denc.6's)
+    const WeightMat& l = w.im.enc(ENC_L);
+    if (int rc = f.gemm64(w.blob64 + l.w, l.K, w.blob64 + l.b, 128, 128, hd2, 128, nullptr, 0, 0, e, f.R)) return rc;
+    if (int rc = launch_frame_max_f64(FrameMaxArgs{e, f.B, f.N, f.M, f.cnt0, f.cnt1, g, nullptr}, f.s)) return rc;
+    if (int rc = f.gemm64(pw + PoolLayout::W1G, 128, pw + PoolLayout::B1, 256, 128, g, 128, nullptr, 0, 0, c, 2 * f.B)) return rc;
+    if (int rc = f.gemm64(pw + PoolLayout::W1E, 128, nullptr, 256, 128, e, 128, nullptr, 0, 0, hidden, f.R)) return rc;
+    if (int rc = launch_add_rows_relu_f64(hidden, c, 256, f.B, f.N, f.M, f.guard(), f.s)) return rc;
+    if (int rc = f.gemm64(pw + PoolLayout::W2K, 384, pw + PoolLayout::B2, 128, 384, hidden, 256, hk3, 128, 0, ws.x64, f.R)) return rc;
+    if (f.p.fused64 && f.p.first > 0)
+        if (int rc = f.gemm64(w.im.proj(0), ws.x64, 128, nullptr, 0, 0, nullptr, ws.qkv64)) return rc;
+    return MDGAT_OK;
 }
 
 // ---- MDGAT_ARITH_FP64 (f64.hip): the inputs, the encoders and the layers before p.first in the reference's arithmetic ----
@@ -579,7 +644,9 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
                          : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_F64_OTHER);
     // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
-    if (f.p.fused64) {
+    if (f.h->pool64) {
+        if (int rc = pooled_encoder64(f, in4, in33)) return rc;
+    } else if (f.p.fused64) {
         const Mat64 k0 = w.mat64(&w.im.enc(ENC_K0)), d0 = w.mat64(&w.im.enc(ENC_D0)), k1 = w.mat64(&w.im.enc(ENC_K1)), k2 = w.mat64(&w.im.enc(ENC_K2)),
                     d1 = w.mat64(&w.im.enc(ENC_D1)), l = w.mat64(&w.im.enc(ENC_L)), q = w.mat64(first > 0 ? &w.im.proj(0) : nullptr);
         const EncoderF64Args e{in4, in33, k0.wf, k0.b, d0.wf, d0.b, k1.wf, k1.b, k2.wf, k2.b, d1.wf, d1.b, l.wf, l.b, q.wf, q.b,
@@ -647,7 +714,7 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
 
 // ---- the hand-over to the fp32-class kernels (nothing behind p.first is discontinuous); the fused fp64 launches write it on the side ----
 static int hand_over(Fwd& f) {
-    if (f.p.fused64) return MDGAT_OK;
+    if (f.p.fused64 && !(f.h->pool64 && f.p.first == 0)) return MDGAT_OK;      // (the pooled encoder is never a fused launch)
     const int rc = launch_f64_to_f32(f.ws.x64, f.ws.x, (size_t)f.R * 128, f.guard(), f.s);
     if (!rc) f.mark(MDGAT_PROF_F64_OTHER);
     return rc;
@@ -1202,4 +1269,21 @@ extern "C" int mdgat_attention_backward_f64(int B, int N, int M, int cross, int 
     if (topk > 0 && !sel) { mdgat_set_error("%s: topk=%d needs the forward's selection words (sel)", who, topk); return MDGAT_ERR_BAD_ARG; }
     if (int rc = grad_buffer(who, "workspace", workspace, workspace_bytes, attention_backward_f64_workspace_bytes(B, N, M))) return rc;
     return launch_attention_backward_f64(B, N, M, cross, topk, qkv, sel, dmsg, dqkv, workspace, static_cast<hipStream_t>(stream));
+}
+
+// ---- the frame maximum of the pooled descriptor encoder as a call of its own, and its backward: csrc/pool_f64.hip ----
+extern "C" int mdgat_frame_max_f64(int B, int n, const double* e, double* g, int64_t* idx, void* stream) {
+    const char* who = "mdgat_frame_max_f64";
+    if (B < 0 || n < 1 || (long long)B * n > (1LL << 24)) { mdgat_set_error("%s: bad shape B=%d n=%d (n >= 1, at most 2^24 rows)", who, B, n); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (!e || !g) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    return launch_frame_max_f64(FrameMaxArgs{e, B, n, 0, nullptr, nullptr, g, idx}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_frame_max_backward_f64(int B, int n, const double* dg, const int64_t* idx, double* de, void* stream) {
+    const char* who = "mdgat_frame_max_backward_f64";
+    if (B < 0 || n < 1 || (long long)B * n > (1LL << 24)) { mdgat_set_error("%s: bad shape B=%d n=%d (n >= 1, at most 2^24 rows)", who, B, n); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (!dg || !idx || !de) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    return launch_frame_max_backward_f64(B, n, dg, idx, de, static_cast<hipStream_t>(stream));
 }

@@ -1,7 +1,8 @@
 """Drop-in ``MDGAT`` module and ``match()`` API over the gfx950 HIP library.
 
-Host-side mirror of ``/root/reference/models/mdgat.py:315-603`` (class ``MDGAT``) for the
-``descriptor == 'FPFH'`` inference path:
+Host-side mirror of ``/root/reference/models/mdgat.py:315-603`` (class ``MDGAT``) for the FPFH descriptors - ``'FPFH'``,
+``'FPFH_gloabal'`` (the descriptor encoder pooled over the frame, mdgat.py:156-174: its encoders run on the fp64 products on every path)
+and ``'FPFH_only'`` (no keypoint encoder: keypoints give the shapes only, the saliency is not read) - on the inference path:
 
 * same constructor config dict (``test.py:137-151``), same parameter and buffer names and shapes, so
   ``load_state_dict(checkpoint['net'])`` works (also through ``torch.nn.DataParallel``, whose keys carry a
@@ -38,6 +39,7 @@ from torch import nn
 from . import _lib, pack
 
 _D = 128
+DESCRIPTORS = ('FPFH', 'FPFH_gloabal', 'FPFH_only')
 
 
 def _mlp_modules(channels):
@@ -57,6 +59,17 @@ class _Encoder(nn.Module):
         super().__init__()
         self.encoder = _mlp_modules([cin, *hidden, cout])
         nn.init.constant_(self.encoder[-1].bias, 0.0)
+
+
+class _GlobalEncoder(nn.Module):
+    """DescriptorGloabalEncoder (mdgat.py:156-174): the FPFH MLP, then a second MLP over [per-keypoint | frame maximum]."""
+
+    def __init__(self, cin, hidden, cout):
+        super().__init__()
+        self.encoder = _mlp_modules([cin, *hidden, cout])
+        nn.init.constant_(self.encoder[-1].bias, 0.0)
+        self.encoder2 = _mlp_modules([2 * cout, 2 * cout, cout])
+        nn.init.constant_(self.encoder2[-1].bias, 0.0)
 
 
 class _Attn(nn.Module):
@@ -90,6 +103,7 @@ class _DeviceState:
         self.handle = handle
         self.device = device
         self.f64 = f64                  # the handle computes in MDGAT_ARITH_FP64 (fixed at mdgat_create)
+        self.exact = f64                # ... and runs the exact mode (False with f64: the fp64 encoders of 'FPFH_gloabal' in front of the fp32-class path)
         self.workspaces = {}            # stream handle -> uint8 tensor, in order of last use
         self.lock = threading.Lock()
 
@@ -193,17 +207,21 @@ class MDGAT(nn.Module):
             raise ValueError(f"sinkhorn_arithmetic={self.sinkhorn_arithmetic!r}: expected 'auto', 'fp32' or 'fp64'")
         if self.arithmetic == 'fp64' and self.attention_dtype != 'fp32':
             raise ValueError("arithmetic='fp64' and attention_dtype='f16' exclude each other")
-        if self.descriptor != 'FPFH':
+        if self.descriptor == 'FPFH_gloabal' and self.attention_dtype != 'fp32':
+            raise ValueError("descriptor='FPFH_gloabal' (its encoders run in fp64 on every path) and attention_dtype='f16' exclude each other")
+        if self.descriptor not in DESCRIPTORS:
             raise NotImplementedError(
-                f"descriptor={self.descriptor!r}: only the 'FPFH' hot path is implemented on MI355X "
-                "(pointnet / FPFH_gloabal / FPFH_only variants are out of scope, see DESIGN.md)")
+                f"descriptor={self.descriptor!r}: the FPFH encoders {DESCRIPTORS} are implemented on MI355X "
+                "(the pointnet variants are out of scope, see DESIGN.md)")
         d = self.config['descriptor_dim']
         if d != _D or list(self.config['keypoint_encoder']) != [32, 64, 128] or \
                 list(self.config['descritor_encoder']) != [64, 128]:
             raise NotImplementedError('the HIP kernels implement the default widths: descriptor_dim=128, '
                                       'keypoint_encoder=[32,64,128], descritor_encoder=[64,128]')
-        self.kenc = _Encoder(4, self.config['keypoint_encoder'], d)
-        self.denc = _Encoder(33, self.config['descritor_encoder'], d)
+        # mdgat.py:336-350: 'FPFH_only' has no keypoint encoder, 'FPFH_gloabal' pools the descriptor encoder over the frame
+        if self.descriptor != 'FPFH_only':
+            self.kenc = _Encoder(4, self.config['keypoint_encoder'], d)
+        self.denc = (_GlobalEncoder if self.descriptor == 'FPFH_gloabal' else _Encoder)(33, self.config['descritor_encoder'], d)
         self.gnn = _GNN(d, 2 * L)
         self.final_proj = nn.Conv1d(d, d, kernel_size=1, bias=True)
         self.register_parameter('bin_score', nn.Parameter(torch.tensor(1.)))
@@ -218,12 +236,13 @@ class MDGAT(nn.Module):
         #     module's own parameters: casts / moves of the module must not throw it away.
         self._blob_holder = [None, False]
         self._blob64_holder = [None]        # exact mode: the same blob before its rounding to fp32 (shared like [0] above)
+        self._pooled_holder = [None]        # 'FPFH_gloabal': encoder2 as mdgat_load_pooled_encoder_f64 takes it (pack.pack_pooled_encoder)
         self._sig_holder = [self._signature()]
         # replicas never run __init__, so only the original module owns (and finally frees) the handles
         weakref.finalize(self, _close_states, self._states)
 
     # ------------------------------------------------------------------ copy / pickle
-    _RUNTIME_ATTRS = ('_states', '_states_lock', '_blob_holder', '_blob64_holder', '_sig_holder')
+    _RUNTIME_ATTRS = ('_states', '_states_lock', '_blob_holder', '_blob64_holder', '_pooled_holder', '_sig_holder')
 
     def __getstate__(self):
         """copy.deepcopy(net) / torch.save(net) (the reference's nn.Module supports both): library handles, locks and packed
@@ -239,6 +258,7 @@ class MDGAT(nn.Module):
         self._states_lock = threading.RLock()
         self._blob_holder = [None, False]
         self._blob64_holder = [None]
+        self._pooled_holder = [None]
         self._sig_holder = [self._signature()]
         weakref.finalize(self, _close_states, self._states)
 
@@ -251,6 +271,12 @@ class MDGAT(nn.Module):
             self._blob_holder[0] = None
             self._blob_holder[1] = False
             self._blob64_holder[0] = None
+            self._pooled_holder[0] = None
+
+    def _handle_f64(self) -> bool:
+        """Is this module's library handle an MDGAT_ARITH_FP64 one?  The exact mode, and every 'FPFH_gloabal' module: its encoders run
+        on the fp64 products whatever follows (a float32 module hands over to the fp32-class layers right behind them)."""
+        return self.exact() or getattr(self, 'descriptor', 'FPFH') == 'FPFH_gloabal'
 
     def exact(self) -> bool:
         """Does a forward of this module, as it stands, run the reference-exact (fp64) mode?  'auto' follows the module's
@@ -323,16 +349,18 @@ class MDGAT(nn.Module):
                     raise RuntimeError('this MDGAT is a DataParallel replica without packed weights: the owner module '
                                        'packs them in _replicate_for_data_parallel() - was replicate() bypassed?')
                 self._blob_holder[0] = self.packed_weights()
-            if self._blob64_holder[0] is None and self.exact() and 'bin_score' in self._parameters and not self._blob_holder[1]:
+            if self._blob64_holder[0] is None and self._handle_f64() and 'bin_score' in self._parameters and not self._blob_holder[1]:
                 import numpy as np
                 self._blob64_holder[0] = self.packed_weights(np.float64)
+                if self.descriptor == 'FPFH_gloabal':
+                    self._pooled_holder[0] = pack.pack_pooled_encoder(self.state_dict())
             return self._blob_holder[0]
 
     def _state_for(self, device: torch.device, blob_device_tensor: Optional[torch.Tensor] = None) -> _DeviceState:
         idx = device.index if device.index is not None else torch.cuda.current_device()
         with self._states_lock:
             st = self._states.get(idx)
-            if st is not None and (st.f64 == self.exact() or blob_device_tensor is not None):
+            if st is not None and ((st.f64 == self._handle_f64() and st.exact == self.exact()) or blob_device_tensor is not None):
                 return st
             if st is not None:
                 # the module's dtype changed under a blob installed by load_packed() (casts keep such a blob): the handle's
@@ -349,14 +377,18 @@ class MDGAT(nn.Module):
             cfg.extract_mode = self._extract_mode()
             cfg.match_threshold = float(self.config['match_threshold'])
             cfg.attention_mode = 0 if self.attention_dtype == 'fp32' else 1
-            f64 = self.exact()
+            f64, exact = self._handle_f64(), self.exact()
             cfg.arithmetic = _lib.ARITH_FP64 if f64 else _lib.ARITH_FP32
             fl = getattr(self, 'f64_layers', None)
             cfg.f64_layers = 0 if fl is None else (_lib.F64_ENCODERS_ONLY if fl == 0 else int(fl))     # (C ABI: 0 = automatic)
             cfg.f64_sinkhorn = {'auto': 0, 'fp64': 1, 'fp32': -1}[getattr(self, 'sinkhorn_arithmetic', 'auto')]
+            if f64 and not exact:
+                # 'FPFH_gloabal' on the fp32-class path: the encoders alone in fp64, the hand-over right behind them
+                cfg.f64_layers, cfg.f64_sinkhorn = _lib.F64_ENCODERS_ONLY, -1
             handle = C.c_void_p()
             _lib.check(lib.mdgat_create(C.byref(cfg), idx, C.byref(handle)), 'mdgat_create')
             st = _DeviceState(handle, idx, f64)
+            st.exact = exact
             try:
                 if self.lanes:
                     _lib.check(lib.mdgat_set_lanes(handle, self.lanes), 'mdgat_set_lanes')
@@ -376,6 +408,14 @@ class MDGAT(nn.Module):
                                            'load_packed(blob, blob64) on ranks that received their weights by broadcast')
                     _lib.check(lib.mdgat_load_weights_f64(handle, blob64.ctypes.data_as(C.c_void_p), blob64.size, 0),
                                'mdgat_load_weights_f64')
+                    if self.descriptor == 'FPFH_gloabal':
+                        pooled = self._pooled_holder[0]
+                        if pooled is None:
+                            raise RuntimeError("descriptor='FPFH_gloabal' needs the pooled encoder's weights: load_packed(blob, blob64, pooled) "
+                                               'on ranks that received their weights by broadcast')
+                        assert pooled.size == lib.mdgat_pooled_encoder_doubles(), pooled.size
+                        _lib.check(lib.mdgat_load_pooled_encoder_f64(handle, pooled.ctypes.data_as(C.c_void_p), pooled.size, 0),
+                                   'mdgat_load_pooled_encoder_f64')
             except Exception:
                 st.close()
                 raise
@@ -393,15 +433,18 @@ class MDGAT(nn.Module):
                 with st.lock:
                     _lib.check(_lib.load().mdgat_set_lanes(st.handle, lanes), 'mdgat_set_lanes')
 
-    def load_packed(self, blob: torch.Tensor, blob64: Optional[torch.Tensor] = None):
+    def load_packed(self, blob: torch.Tensor, blob64: Optional[torch.Tensor] = None, pooled: Optional[torch.Tensor] = None):
         """Install an already packed fp32 blob that lives on a GPU (e.g. received by an RCCL broadcast,
         see shard.broadcast_weights) instead of packing this module's own parameters.  arithmetic='fp64' needs
-        ``blob64`` as well: the same blob in float64 (``packed_weights(numpy.float64)``)."""
+        ``blob64`` as well: the same blob in float64 (``packed_weights(numpy.float64)``); descriptor='FPFH_gloabal' needs ``blob64``
+        and ``pooled``, the float64 tensor of ``pack.pack_pooled_encoder``."""
         assert blob.is_cuda and blob.dtype == torch.float32 and blob.is_contiguous()
-        if self.exact():
+        if self._handle_f64():
             if blob64 is None or blob64.dtype != torch.float64 or blob64.numel() != blob.numel():
-                raise ValueError("the exact mode (a float64 module, or arithmetic='fp64'): load_packed needs blob64, the float64 "
-                                 'blob of the same layout')
+                raise ValueError("the exact mode (a float64 module, or arithmetic='fp64') and descriptor='FPFH_gloabal': load_packed needs "
+                                 'blob64, the float64 blob of the same layout')
+        if self.descriptor == 'FPFH_gloabal' and (pooled is None or pooled.dtype != torch.float64 or pooled.numel() != pack.POOLED_ENCODER_DOUBLES):
+            raise ValueError("descriptor='FPFH_gloabal': load_packed needs pooled, the float64 tensor of pack.pack_pooled_encoder")
         idx = blob.device.index
         with self._states_lock:
             old = self._states.pop(idx, None)
@@ -411,6 +454,7 @@ class MDGAT(nn.Module):
             # weights from it - never this module's own parameters, which are random init on a rank that received a blob
             self._blob_holder[0] = blob.detach().cpu().numpy().copy()
             self._blob64_holder[0] = blob64.detach().cpu().numpy().copy() if blob64 is not None else None
+            self._pooled_holder[0] = pooled.detach().cpu().numpy().copy() if pooled is not None else None
             self._blob_holder[1] = True     # stands until load_state_dict() / repack(): see _invalidate_if_changed
             self._sig_holder[0] = self._signature()
             for other in [i for i in self._states if i != idx]:
@@ -437,8 +481,9 @@ class MDGAT(nn.Module):
                                       'losses of mdgat.py:486-594 and backward are out of scope)')
         loss_req = self._loss_request(data, kpts0, kpts1) if getattr(self, 'eval_loss', False) else None
         token = [0]
-        res = self._run(kpts0, data['scores0'], data['descriptors0'], kpts1, data['scores1'], data['descriptors1'], token_out=token,
-                        loss=loss_req)
+        # ('FPFH_only', mdgat.py:421-426, never reads the saliency)
+        sig0, sig1 = (None, None) if self.descriptor == 'FPFH_only' else (data['scores0'], data['scores1'])
+        res = self._run(kpts0, sig0, data['descriptors0'], kpts1, sig1, data['descriptors1'], token_out=token, loss=loss_req)
         m0, m1, s0, s1 = res[:4]
         s0, s1 = s0.to(out_dtype), s1.to(out_dtype)
         if self.loss_method != 'superglue':
@@ -524,6 +569,9 @@ class MDGAT(nn.Module):
         st = self._state_for(dev)
         ins = [packed[k].to(device=dev, dtype=torch.float64).contiguous()
                for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
+        if self.descriptor == 'FPFH_only':          # keypoints and saliency give the shapes only (as in _run)
+            for i in (0, 1, 3, 4):
+                ins[i] = torch.zeros_like(ins[i])
         d0, d1, h0, h1 = ops._ragged_counts(packed, B, dev)
         lib = _lib.load()
         with torch.cuda.device(dev), st.lock:
@@ -613,7 +661,7 @@ class MDGAT(nn.Module):
         return {'pairs': self._ragged_dicts(padded, False), 'metrics': metrics, 'T': T}
 
     def training_forward(self, data):
-        """The reference's forward (mdgat.py:369-603, descriptor='FPFH') in fp64 with BatchNorm as ``self.training`` says, composed from the
+        """The reference's forward (mdgat.py:369-603, any of the three FPFH descriptors) in fp64 with BatchNorm as ``self.training`` says, composed from the
         differentiable device primitives (``mdgat_matcher_amd/train.py``): the reference's dict, whose ``loss`` (0-d for superglue /
         triplet, [B] for gap) carries a grad_fn whenever grad is enabled and a parameter requires grad, so ``loss.mean().backward()``
         fills the ``.grad`` of this module's own parameters.  In train() mode the BatchNorm buffers move as the reference's do (every
@@ -741,11 +789,20 @@ class MDGAT(nn.Module):
             if frames[0].shape[-1] != 37 or frames[1].shape[-1] != 37 or frames[0].dim() != 3:
                 raise ValueError('expected frame records [B, N, 37] = xyz | saliency | 33-D FPFH (load_data.py:152-165)')
             ins = [self._f32(frames[0], dev), self._f32(frames[1], dev)]
+            if self.descriptor == 'FPFH_only':
+                ins = [t.clone() for t in ins]
+                for t in ins:
+                    t[..., :4] = 0          # keypoints and saliency are not read (below)
             B, N, M = ins[0].shape[0], ins[0].shape[1], ins[1].shape[1]
         else:
             if fpfh0.shape[-1] != 33 or fpfh1.shape[-1] != 33 or kpts0.shape[-1] != 3 or kpts1.shape[-1] != 3:
                 raise ValueError('expected keypoints [B, N, 3] and 33-D FPFH descriptors [B, N, 33]')
             in_dtype = torch.float64 if f64 else torch.float32
+            if self.descriptor == 'FPFH_only':
+                # mdgat.py:421-426 reads the keypoints for their shapes only and the saliency not at all: the library, whose packed
+                # keypoint encoder is all zeros, is handed zeros (0 x a huge or non-finite coordinate would not be an exact zero)
+                kpts0, kpts1 = (torch.zeros(k.shape, dtype=in_dtype, device=dev) for k in (kpts0, kpts1))
+                sigma0, sigma1 = (torch.zeros(k.shape[:-1], dtype=in_dtype, device=dev) for k in (kpts0, kpts1))
             ins = [t.to(device=dev, dtype=in_dtype).contiguous() for t in (kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1)]
             B, N, M = kpts0.shape[0], kpts0.shape[1], kpts1.shape[1]
         lib = _lib.load()
@@ -817,12 +874,13 @@ class MDGAT(nn.Module):
         scores = per-keypoint saliency, which the keypoint encoder consumes (mdgat.py:184-188) and is
         therefore required.  Returns ``(matches0, matches1, mscores0, mscores1[, Z])``; ``Z`` is the
         (N+1) x (M+1) log assignment matrix of log_optimal_transport."""
-        if scores0 is None or scores1 is None:
+        only = self.descriptor == 'FPFH_only'           # (no KeypointEncoder: the saliency is not read)
+        if (scores0 is None or scores1 is None) and not only:
             raise ValueError('match() needs the keypoint saliency scores0/scores1 (KeypointEncoder input)')
         single = kpts0.dim() == 2
         if single:
             kpts0, desc0, kpts1, desc1 = kpts0[None], desc0[None], kpts1[None], desc1[None]
-            scores0, scores1 = scores0[None], scores1[None]
+            scores0, scores1 = (None, None) if only else (scores0[None], scores1[None])
         m0, m1, s0, s1, Z = self._run(kpts0, scores0, desc0, kpts1, scores1, desc1, want_Z=return_scores)
         outs = [m0, m1, s0, s1] + ([Z] if return_scores else [])
         if single:

@@ -1237,3 +1237,61 @@ def mlp_f64_tensors(x: torch.Tensor, weights, biases, bns=(), training: bool = T
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         return _MlpTensorsF64.apply((len(ws), len(gammas), bufs, eps, momentum, training), x, x1, residual, *params)
     return _mlp_forward(x, x1, ws, bs, gammas, betas, bufs, eps, momentum, training, residual)[0]
+
+
+# ---- the frame maximum of the pooled descriptor encoder ('FPFH_gloabal', mdgat.py:168: torch.max(desc, dim=2); csrc/pool_f64.hip) ----
+def _frame_max_values(e):
+    if not isinstance(e, torch.Tensor) or e.dtype != torch.float64 or e.dim() != 3 or e.shape[2] != 128:
+        raise ValueError('frame_max_f64 takes a float64 tensor [B, n, 128] (channel-last)')
+    _need_cuda(e)
+    B, n = e.shape[0], e.shape[1]
+    if n < 1:
+        raise ValueError('frame_max_f64: a frame without keypoints has no maximum')
+    x = e.detach().contiguous()
+    g = torch.empty((B, 128), dtype=torch.float64, device=e.device)
+    idx = torch.empty((B, 128), dtype=torch.int64, device=e.device)
+    with torch.cuda.device(e.device):
+        _lib.check(_lib.load().mdgat_frame_max_f64(B, n, x.data_ptr(), g.data_ptr(), idx.data_ptr(), _stream(x)), 'mdgat_frame_max_f64')
+    return g, idx
+
+
+def frame_max_backward(dg: torch.Tensor, idx: torch.Tensor, n: int) -> torch.Tensor:
+    """Gradient of ``frame_max_f64``: dg [B, 128] float64 and the forward's ``idx`` [B, 128] int64 -> de [B, n, 128], dg at row idx and
+    zero elsewhere.  The indices are the forward's, never decided again; one writer per element, no atomics."""
+    if dg.dtype != torch.float64 or idx.dtype != torch.int64 or dg.dim() != 2 or dg.shape[1] != 128 or tuple(idx.shape) != tuple(dg.shape) or \
+            idx.device != dg.device or n < 1:
+        raise ValueError('frame_max_backward: dg float64 [B, 128], idx int64 [B, 128] on one device, n >= 1')
+    _need_cuda(dg)
+    B = dg.shape[0]
+    dg, idx = dg.detach().contiguous(), idx.contiguous()
+    de = torch.empty((B, n, 128), dtype=torch.float64, device=dg.device)
+    with torch.cuda.device(dg.device):
+        _lib.check(_lib.load().mdgat_frame_max_backward_f64(B, n, dg.data_ptr(), idx.data_ptr(), de.data_ptr(), _stream(dg)),
+                   'mdgat_frame_max_backward_f64')
+    return de
+
+
+class _FrameMaxF64(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e):
+        g, idx = _frame_max_values(e)
+        ctx.n = e.shape[1]
+        ctx.save_for_backward(idx)
+        ctx.mark_non_differentiable(idx)
+        return g, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dg, _):
+        (idx,) = ctx.saved_tensors
+        return frame_max_backward(dg, idx, ctx.n)
+
+
+def frame_max_f64(e: torch.Tensor):
+    """``torch.max(e, dim=1)`` for e [B, n, 128] float64 on the device, channel-last: (g [B, 128], idx [B, 128] int64), g the maximum of
+    every channel over the frame's n keypoints and idx the FIRST row that holds it - the pooling of the reference's
+    ``DescriptorGloabalEncoder`` (mdgat.py:168).  Differentiable (not twice) when e requires grad: the backward sends dg to row idx and
+    zero to every other row, with the indices the forward saved."""
+    if torch.is_grad_enabled() and isinstance(e, torch.Tensor) and e.requires_grad:
+        return _FrameMaxF64.apply(e)
+    return _frame_max_values(e)

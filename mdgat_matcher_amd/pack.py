@@ -21,6 +21,15 @@ All folding is done in fp64 and rounded to fp32 once:
   (``tools/fuzz_checkpoint.py``: rescalings by 10^-3 ... 10^3 leave the results unchanged);
 * the last layers of the two encoders are summed (``mdgat.py:392-393``) by concatenating them along K:
   ``[denc.6 | kenc.9] [hd ; hk]``.
+
+The reference's other two FPFH encoders (``mdgat.py:342-350``) are told by the state dict's own names (``descriptor_of``):
+
+* ``'FPFH_only'`` has no ``kenc``: the same blob with every kenc matrix and bias zero, ``encl = [denc.6 | 0]`` and denc.6's bias - the
+  kernels then add exact zeros where ``'FPFH'`` adds the keypoint encoder;
+* ``'FPFH_gloabal'`` (``mdgat.py:156-174``): the blob carries kenc.0 .. kenc.6, denc.0, denc.3 and ``encl = [denc.6 | 0]`` (the product
+  that gives e alone); ``pack_pooled_encoder`` lays out what the blob has no room for - ``encoder2.0`` folded with its BatchNorm, its
+  hidden gauge fixed, split into the columns that read e and those that read the frame maximum, and ``[encoder2.3 | kenc.9]`` over
+  ``[hidden ; hk]`` - for ``mdgat_load_pooled_encoder_f64``.
 """
 from __future__ import annotations
 
@@ -122,20 +131,67 @@ def _fix_hidden(w, b, w_next, cols=None):
     return w * s[:, None], b * s, w_next
 
 
+def descriptor_of(sd) -> str:
+    """Which of the reference's FPFH encoders a state dict holds (mdgat.py:336-350), by its names."""
+    sd = strip_module_prefix(sd)
+    if 'denc.encoder2.0.weight' in sd:
+        return 'FPFH_gloabal'
+    return 'FPFH' if any(k.startswith('kenc.') for k in sd) else 'FPFH_only'
+
+
+_KENC_SHAPES = {'kenc.encoder.0.weight': (32, 4, 1), 'kenc.encoder.3.weight': (64, 32, 1),
+                'kenc.encoder.6.weight': (128, 64, 1), 'kenc.encoder.9.weight': (128, 128, 1)}
+_ENC2_SHAPES = {'denc.encoder2.0.weight': (256, 256, 1), 'denc.encoder2.3.weight': (128, 256, 1)}
+
+
 def check_supported(sd, L):
+    descriptor = descriptor_of(sd)
     shapes = {
-        'kenc.encoder.0.weight': (32, 4, 1), 'kenc.encoder.3.weight': (64, 32, 1),
-        'kenc.encoder.6.weight': (128, 64, 1), 'kenc.encoder.9.weight': (128, 128, 1),
+        **({} if descriptor == 'FPFH_only' else _KENC_SHAPES), **(_ENC2_SHAPES if descriptor == 'FPFH_gloabal' else {}),
         'denc.encoder.0.weight': (64, 33, 1), 'denc.encoder.3.weight': (128, 64, 1),
         'denc.encoder.6.weight': (128, 128, 1), 'final_proj.weight': (128, 128, 1),
     }
     for k, shp in shapes.items():
         if k not in sd:
-            raise KeyError(f'state dict lacks {k} (only descriptor="FPFH" checkpoints are supported)')
+            raise KeyError(f'state dict lacks {k} (a descriptor={descriptor!r} checkpoint holds it)')
         if tuple(sd[k].shape) != shp:
             raise ValueError(f'{k} has shape {tuple(sd[k].shape)}; the HIP path implements the default widths {shp}')
     if f'gnn.layers.{2 * L - 1}.mlp.3.weight' not in sd or f'gnn.layers.{2 * L}.mlp.3.weight' in sd:
         raise ValueError(f'state dict does not hold exactly 2L={2 * L} GNN layers')
+
+
+def _kenc(sd):
+    """The keypoint encoder's four (W, b), BN folded and the hidden gauges fixed; exact zeros for a state dict without one ('FPFH_only')."""
+    if not any(k.startswith('kenc.') for k in sd):
+        return [(np.zeros((o, i)), np.zeros(o)) for o, i in ((32, 4), (64, 32), (128, 64), (128, 128))]
+    wk0, bk0 = _fold_bn(sd, 'kenc.encoder.0', 'kenc.encoder.1')
+    wk1, bk1 = _fold_bn(sd, 'kenc.encoder.3', 'kenc.encoder.4')
+    wk2, bk2 = _fold_bn(sd, 'kenc.encoder.6', 'kenc.encoder.7')
+    wk3, bk3 = _plain(sd, 'kenc.encoder.9')
+    wk0, bk0, wk1 = _fix_hidden(wk0, bk0, wk1)
+    wk1, bk1, wk2 = _fix_hidden(wk1, bk1, wk2)
+    wk2, bk2, wk3 = _fix_hidden(wk2, bk2, wk3)
+    return [(wk0, bk0), (wk1, bk1), (wk2, bk2), (wk3, bk3)]
+
+
+POOLED_ENCODER_DOUBLES = 2 * 256 * 128 + 256 + 128 * 384 + 128
+
+
+def pack_pooled_encoder(sd) -> np.ndarray:
+    """``encoder2`` of a 'FPFH_gloabal' state dict (mdgat.py:160-161) as ``mdgat_load_pooled_encoder_f64`` takes it, float64:
+    W1e [256, 128] | W1g [256, 128] | b1 [256] | [encoder2.3 | kenc.9] [128, 384] | encoder2.3.bias + kenc.9.bias [128] - encoder2.0
+    folded with its BatchNorm, its hidden gauge fixed like every other MLP's, split into the columns that read the keypoint's own
+    encoder output (0..127) and those that read the frame maximum (128..255)."""
+    sd = strip_module_prefix(sd)
+    if descriptor_of(sd) != 'FPFH_gloabal':
+        raise KeyError('state dict lacks denc.encoder2.0.weight (only a descriptor="FPFH_gloabal" checkpoint has a pooled encoder)')
+    w1, b1 = _fold_bn(sd, 'denc.encoder2.0', 'denc.encoder2.1')
+    w2, b2 = _plain(sd, 'denc.encoder2.3')
+    w1, b1, w2 = _fix_hidden(w1, b1, w2)
+    wk3, bk3 = _kenc(sd)[3]
+    out = np.concatenate([w1[:, :D].ravel(), w1[:, D:].ravel(), b1, np.concatenate([w2, wk3], axis=1).ravel(), b2 + bk3]).astype(np.float64)
+    assert out.size == POOLED_ENCODER_DOUBLES
+    return out
 
 
 def pack_state_dict(sd, L: int, dtype=np.float32) -> np.ndarray:
@@ -151,18 +207,16 @@ def pack_state_dict(sd, L: int, dtype=np.float32) -> np.ndarray:
         blob[off:off + a.size] = a
 
     # encoders: BN folded, then the gauge of every hidden layer fixed (module docstring)
-    wk0, bk0 = _fold_bn(sd, 'kenc.encoder.0', 'kenc.encoder.1')
-    wk1, bk1 = _fold_bn(sd, 'kenc.encoder.3', 'kenc.encoder.4')
-    wk2, bk2 = _fold_bn(sd, 'kenc.encoder.6', 'kenc.encoder.7')
-    wk3, bk3 = _plain(sd, 'kenc.encoder.9')
+    descriptor = descriptor_of(sd)
+    (wk0, bk0), (wk1, bk1), (wk2, bk2), (wk3, bk3) = _kenc(sd)
     wd0, bd0 = _fold_bn(sd, 'denc.encoder.0', 'denc.encoder.1')
     wd1, bd1 = _fold_bn(sd, 'denc.encoder.3', 'denc.encoder.4')
     wd2, bd2 = _plain(sd, 'denc.encoder.6')
-    wk0, bk0, wk1 = _fix_hidden(wk0, bk0, wk1)
-    wk1, bk1, wk2 = _fix_hidden(wk1, bk1, wk2)
-    wk2, bk2, wk3 = _fix_hidden(wk2, bk2, wk3)
     wd0, bd0, wd1 = _fix_hidden(wd0, bd0, wd1)
     wd1, bd1, wd2 = _fix_hidden(wd1, bd1, wd2)
+    if descriptor == 'FPFH_gloabal':
+        # encl gives e = denc.6(hd) alone; kenc.9 joins encoder2.3 (pack_pooled_encoder)
+        wk3, bk3 = np.zeros_like(wk3), np.zeros_like(bk3)
     put(lay['kenc0_w'], wk0); put(lay['kenc0_b'], bk0)
     put(lay['denc0_w'], wd0); put(lay['denc0_b'], bd0)
     put(lay['kenc1_w'], wk1); put(lay['kenc1_b'], bk1)

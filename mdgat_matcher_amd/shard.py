@@ -105,7 +105,8 @@ def broadcast_weights(net, device, rank: int, world: int, out64=None):
         blob = torch.empty(n, dtype=torch.float32, device=device)
     broadcast_blob(blob, 0)
     blob64 = None
-    if net.exact() or getattr(net, 'arithmetic', 'auto') == 'auto':
+    pooled_encoder = getattr(net, 'descriptor', 'FPFH') == 'FPFH_gloabal'      # its encoders run in fp64 on every path
+    if net.exact() or getattr(net, 'arithmetic', 'auto') == 'auto' or pooled_encoder:
         # the reference-exact mode loads the folded weights before their rounding to fp32 as well (29 MB at L = 9)
         import numpy as np
         if rank == 0:
@@ -115,8 +116,16 @@ def broadcast_weights(net, device, rank: int, world: int, out64=None):
         broadcast_blob(blob64, 0)
         if out64 is not None:
             out64.append(blob64)
+    pooled = None
+    if pooled_encoder:
+        # encoder2 of the pooled descriptor encoder, which the blob has no room for (pack.pack_pooled_encoder): a third broadcast
+        if rank == 0:
+            pooled = torch.from_numpy(pack.pack_pooled_encoder(net.state_dict())).to(device)
+        else:
+            pooled = torch.empty(pack.POOLED_ENCODER_DOUBLES, dtype=torch.float64, device=device)
+        broadcast_blob(pooled, 0)
     if blob.is_cuda:
-        net.load_packed(blob, blob64)
+        net.load_packed(blob, blob64, pooled)
     return blob
 
 

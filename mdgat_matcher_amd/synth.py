@@ -89,8 +89,12 @@ def _mlp(rs, sd, prefix, channels):
 
 def make_state_dict(L=9, seed=0, bin_score=1.0, dtype=torch.float64, feature_dim=128,
                     keypoint_encoder=(32, 64, 128), descriptor_encoder=(64, 128),
-                    logit_std=4.0, score_std=1.0):
+                    logit_std=4.0, score_std=1.0, descriptor='FPFH'):
     """Reference-named state dict (348 entries at L=9) from a seed.
+
+    ``descriptor``: 'FPFH' (default), 'FPFH_only' - the same weights without the ``kenc.*`` entries (mdgat.py:348-350) - or
+    'FPFH_gloabal' - the same weights plus ``denc.encoder2.*`` (mdgat.py:160-161) drawn from a stream of their own, so the entries the
+    three share are equal and the default's are what they always were.
 
     The scales are chosen so that a random-weight network behaves like a trained one
     numerically: keypoint coordinates (tens of metres) are brought to O(1) by the first
@@ -125,6 +129,16 @@ def make_state_dict(L=9, seed=0, bin_score=1.0, dtype=torch.float64, feature_dim
     sd['final_proj.weight'] = w
     sd['final_proj.bias'] = b
     sd['bin_score'] = np.asarray(bin_score, dtype=np.float64)
+    if descriptor == 'FPFH_only':
+        sd = {k: v for k, v in sd.items() if not k.startswith('kenc.')}
+    elif descriptor == 'FPFH_gloabal':
+        enc2 = {}
+        _mlp(np.random.RandomState(seed + 104729), enc2, 'denc.encoder2', [2 * D, 2 * D, D])
+        # (state-dict order of the reference: encoder2 behind denc.encoder)
+        head = [k for k in sd if k.startswith(('kenc.', 'denc.'))]
+        sd = {**{k: sd[k] for k in head}, **enc2, **{k: v for k, v in sd.items() if k not in head}}
+    elif descriptor != 'FPFH':
+        raise ValueError(f"descriptor={descriptor!r}: expected 'FPFH', 'FPFH_gloabal' or 'FPFH_only'")
     out = {}
     for k, v in sd.items():
         t = torch.from_numpy(np.ascontiguousarray(v)).reshape(np.shape(v))

@@ -1,4 +1,4 @@
-"""The training-mode forward of the whole MDGAT (models/mdgat.py:369-603, descriptor='FPFH') in fp64, composed in Python from the
+"""The training-mode forward of the whole MDGAT (models/mdgat.py:369-603, descriptor='FPFH', 'FPFH_gloabal' or 'FPFH_only') in fp64, composed in Python from the
 differentiable device primitives of ``ops``: ``mlp_f64_tensors`` (the encoders, q | k | v, merge, the layer MLP), ``attention_f64``,
 ``match_head``, ``log_optimal_transport``, ``extract`` and ``matching_loss``.  ``MDGAT.training_forward`` is the public entry.
 
@@ -55,11 +55,23 @@ def _layer(layer, d0, d1, cross, k, training, perm):
 def descriptors(net, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1):
     """The encoders and the GNN: (desc0 [B, N, 128], desc1 [B, M, 128]) as ``final_proj`` receives them, point-major."""
     training = bool(net.training)
-    kw, kb, kbn = _enc_parts(net.kenc.encoder)
+    descriptor = net.descriptor
     dw, db, dbn = _enc_parts(net.denc.encoder)
+    if descriptor != 'FPFH_only':
+        kw, kb, kbn = _enc_parts(net.kenc.encoder)
+    if descriptor == 'FPFH_gloabal':
+        gw, gb, gbn = _enc_parts(net.denc.encoder2)
     out = []
     for kpts, sigma, fpfh in ((kpts0, sigma0, fpfh0), (kpts1, sigma1, fpfh1)):        # mdgat.py:392-393: denc, then kenc, per frame
         enc = ops.mlp_f64_tensors(fpfh, dw, db, dbn, training)
+        if descriptor == 'FPFH_gloabal':
+            # DescriptorGloabalEncoder (mdgat.py:163-174): encoder2 over [e | the frame's maximum of e, repeated]; its BatchNorm sees this
+            # frame's B * n rows
+            g, _ = ops.frame_max_f64(enc)
+            enc = ops.mlp_f64_tensors(enc, gw, gb, gbn, training, x1=g.unsqueeze(1).expand(-1, enc.shape[1], -1))
+        if descriptor == 'FPFH_only':       # mdgat.py:421-426: denc alone
+            out.append(enc)
+            continue
         out.append(ops.mlp_f64_tensors(torch.cat([kpts, sigma.unsqueeze(-1)], dim=-1), kw, kb, kbn, training, residual=enc))
     d0, d1 = out
     perm = torch.tensor(_PERM, dtype=torch.int64, device=d0.device)
@@ -92,7 +104,9 @@ def training_forward(net, data):
     method = _lib.LOSS_METHODS.get(net.loss_method)
     if method is None:
         raise ValueError(f"loss_method={net.loss_method!r}: the loss is defined for 'superglue', 'triplet_loss' and 'gap_loss'")
-    ins = [data[k].to(device=dev, dtype=torch.float64) for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
+    keys = ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')
+    # ('FPFH_only' never reads the saliency, mdgat.py:421-426)
+    ins = [None if net.descriptor == 'FPFH_only' and k.startswith('scores') else data[k].to(device=dev, dtype=torch.float64) for k in keys]
     if ins[2].shape[-1] != 33 or ins[5].shape[-1] != 33 or kpts0.shape[-1] != 3 or kpts1.shape[-1] != 3:
         raise ValueError('expected keypoints [B, N, 3] and 33-D FPFH descriptors [B, N, 33]')
     gt0, gt1 = data['gt_matches0'], data['gt_matches1']            # KeyError when absent, as in the reference (mdgat.py:438-439)
