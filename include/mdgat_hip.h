@@ -211,7 +211,7 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  * MDGAT_ERR_BAD_ARG naming the first offending pair.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
  * f64_sinkhorn not MDGAT_F64_SINKHORN_OFF, f64_layers automatic, mdgat_set_f64_sinkhorn_form not 1 (else MDGAT_ERR_UNSUPPORTED); an fp32
  * handle is MDGAT_ERR_BAD_ARG.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
- * There is no ragged mdgat_forward_frames and no ragged loss. */
+ * The ragged mdgat_forward_frames is mdgat_forward_frames_ragged below; there is no ragged loss. */
 int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                              const int32_t* counts1_host, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
                              const double* sigma1, const double* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
@@ -229,6 +229,34 @@ int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* fram
                          int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                          float* Z, const mdgat_taps* taps,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* mdgat_forward_f64_ragged fed from a BANK of raw records: the records of a whole sequence lie on the device once (rec0 [rows0][37], rec1
+ * [rows1][37] fp32, the layout of mdgat_forward_frames; both may be the same buffer) and a chunk of pairs is two vectors of start rows.
+ * Frame 0 of pair b is the counts0[b] records from row starts0[b] of rec0, frame 1 the counts1[b] records from row starts1[b] of rec1;
+ * the assemble kernel decodes, normalises (normalize_fpfh, the loader's float32 arithmetic bit for bit as in mdgat_forward_frames), widens
+ * and pads them into the forward's slots of Np / Mp rows, zeros beyond the counts.  Everything behind it, every result and every limit
+ * are mdgat_forward_f64_ragged's; so are its checks, made on the host copies before anything is enqueued, plus 0 <= starts[b] and
+ * starts[b] + counts[b] <= rows (else MDGAT_ERR_BAD_ARG naming the first offending pair).  starts0 / starts1: DEVICE int64 [B];
+ * starts0_host / starts1_host: the same in HOST memory.
+ *   - Only a pair's own records are read: what any other record of the bank holds - NaN included - reaches no result and no guard.
+ *   - A non-finite word or (normalize_fpfh) an all-zero FPFH row among a pair's own records raises the handle's range-violation word
+ *     (mdgat_async_status), as in mdgat_forward_frames.
+ *   - kpts0_out [B][Np][3] / kpts1_out [B][Mp][3] fp32 (optional, each on its own): the keypoints as they lie in the
+ *     records, zeros beyond the counts - what mdgat_gt_matches_ragged and mdgat_eval_metrics_ragged take.
+ * Exact mode only (an fp32 handle is MDGAT_ERR_BAD_ARG), Np, Mp <= 575, no taps.  workspace: mdgat_workspace_bytes(h, B, Np, Mp). */
+int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
+                                const int32_t* counts0_host, const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
+                                const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0, const float* rec1,
+                                int64_t rows1, int normalize_fpfh, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                float* Z, float* kpts0_out, float* kpts1_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Its assemble launch alone, into caller-owned in4 [B][Np+Mp][4] and in33 [B][Np+Mp][33] fp64 (rows of a pair: frame 0's Np, then frame
+ * 1's Mp): x y z saliency and the FPFH row as the encoders read them.  guard (device memory, optional; the caller clears it) is set to 1
+ * where the forward would raise its range-violation word.  No handle: the same checks of counts and starts. */
+int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                     const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1, const int64_t* starts0_host,
+                                     const int64_t* starts1_host, const float* rec0, int64_t rows0, const float* rec1, int64_t rows1,
+                                     int normalize_fpfh, double* in4, double* in33, float* kpts0_out, float* kpts1_out, unsigned* guard,
+                                     void* stream);
 
 /* ---- evaluation loss (mdgat.py:486-594) and its gradient with respect to Z (mdgat_loss_backward below) ------------------------- */
 
@@ -639,6 +667,14 @@ int mdgat_pose(int B, int N, int M, const float* kpts0, const float* kpts1, cons
  * keypoints with a frame-1 keypoint within the threshold (load_data.py:264). */
 int mdgat_gt_matches(int B, int N, int M, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
                      double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream);
+
+/* The same on a RAGGED batch: pair b has counts0[b] x counts1[b] keypoints in slots padded to Np x Mp (kpts0 [B][Np][3], kpts1 [B][Mp][3],
+ * gt0 [B][Np], gt1 [B][Mp]); its matches and rep[b] are those of mdgat_gt_matches on the pair alone, gt0 / gt1 beyond its counts are -1,
+ * the keypoints there are not read.  counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same in HOST memory, checked
+ * before the launch (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp).  The LDS follows Np + Mp (MDGAT_ERR_UNSUPPORTED beyond 160 KB). */
+int mdgat_gt_matches_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                            const int32_t* counts1_host, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
+                            double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream);
 
 /* ---- the evaluation scripts' per-pair record ------------------------------------------------------------------------------
  * What test.py:212-296 and test_registration_metric.py:213-264 derive for one pair from the matcher's output, the ground-truth

@@ -316,6 +316,12 @@ struct FwdIn {
     // a ragged batch (mdgat_forward_f64_ragged): the pairs' own keypoint counts in slots of N / M - device int32 [B] for the kernels, the
     // same values on the host for plan_forward's checks
     const int *cnt0 = nullptr, *cnt1 = nullptr, *cnt0_host = nullptr, *cnt1_host = nullptr;
+    // a ragged chunk out of a bank of records (mdgat_forward_frames_ragged): rec0 / rec1 are [rows0 | rows1][37] and frame f of pair b is the
+    // cnt[b] records from row start[b] - device int64 [B] for the kernel, host copies for the checks; kp0_out / kp1_out (optional):
+    // the padded float32 keypoints [B][N][3] / [B][M][3] the assemble kernel writes for the steps behind the matcher
+    const long long *start0 = nullptr, *start1 = nullptr, *start0_host = nullptr, *start1_host = nullptr;
+    long long rows0 = 0, rows1 = 0;
+    float *kp0_out = nullptr, *kp1_out = nullptr;
     static FwdIn arrays(const float* k0, const float* s0, const float* f0, const float* k1, const float* s1, const float* f1) {
         FwdIn in; in.kpts0 = k0; in.sigma0 = s0; in.fpfh0 = f0; in.kpts1 = k1; in.sigma1 = s1; in.fpfh1 = f1; return in;
     }
@@ -326,9 +332,10 @@ struct FwdIn {
     FwdIn from(size_t c, int N, int M) const {
         auto o = [](auto* q, size_t n) { return q ? q + n : q; };
         return FwdIn{o(kpts0, c * N * 3), o(sigma0, c * N), o(fpfh0, c * N * 33), o(kpts1, c * M * 3), o(sigma1, c * M), o(fpfh1, c * M * 33),
-                     o(rec0, c * N * 37), o(rec1, c * M * 37), normalize_fpfh,
+                     o(rec0, start0 ? 0 : c * N * 37), o(rec1, start0 ? 0 : c * M * 37), normalize_fpfh,      // (a bank is indexed by the starts)
                      o(dk0, c * N * 3), o(ds0, c * N), o(df0, c * N * 33), o(dk1, c * M * 3), o(ds1, c * M), o(df1, c * M * 33),
-                     o(cnt0, c), o(cnt1, c), o(cnt0_host, c), o(cnt1_host, c)};
+                     o(cnt0, c), o(cnt1, c), o(cnt0_host, c), o(cnt1_host, c),
+                     o(start0, c), o(start1, c), o(start0_host, c), o(start1_host, c), rows0, rows1, o(kp0_out, c * N * 3), o(kp1_out, c * M * 3)};
     }
 };
 
@@ -504,8 +511,9 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     if (in.cnt0) {
         // The ragged plan: the kernels that take per-pair counts are the exact mode's with its fp64 tail on the register-resident Sinkhorn;
         // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); every count is checked on its host copy, naming the first offending pair.
-        const char* who = "mdgat_forward_f64_ragged";
+        const char* who = in.start0 ? "mdgat_forward_frames_ragged" : "mdgat_forward_f64_ragged";
         if (!in.cnt1 || !in.cnt0_host || !in.cnt1_host) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
+        if (in.start0 && (!in.start1 || !in.start0_host || !in.start1_host)) { mdgat_set_error("%s: null starts pointer", who); return MDGAT_ERR_BAD_ARG; }
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
         if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || !sinkhorn_f64_ragged_supported(N, M)) {
             mdgat_set_error("%s: ragged batches need the fp64 tail on the register-resident Sinkhorn: f64_sinkhorn not off, f64_layers automatic, "
@@ -526,6 +534,15 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
                 }
             cmin = n < cmin ? n : cmin;
             cmin = m < cmin ? m : cmin;
+            if (in.start0) {
+                // (the pair's records lie inside the bank: the kernel reads rows start .. start + count - 1 and no others)
+                const long long s0 = in.start0_host[b], s1 = in.start1_host[b];
+                if (s0 < 0 || s0 + n > in.rows0 || s1 < 0 || s1 + m > in.rows1) {
+                    mdgat_set_error("%s: pair %d reads records %lld .. %lld of %lld and %lld .. %lld of %lld: outside the bank", who, b, s0, s0 + n,
+                                    in.rows0, s1, s1 + m, in.rows1);
+                    return MDGAT_ERR_BAD_ARG;
+                }
+            }
         }
         p.cnt_min = cmin;
     }
@@ -640,7 +657,9 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     // 32 + 64 + 128 + 64 + 128 = 416 of the 603 doubles per point there
     double* in4 = ws.hid64 + Rz * (256 - 37);
     double* in33 = in4 + Rz * 4;
-    if (int rc = in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
+    if (int rc = in.start0 ? launch_assemble_frames_ragged_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.start0, in.start1, f.cnt0, f.cnt1, in.normalize_fpfh, in4,
+                                                               in33, in.kp0_out, in.kp1_out, f.guard(), f.s)
+               : in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
                          : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_F64_OTHER);
     // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
@@ -899,6 +918,59 @@ extern "C" int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, 
     return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
 }
 
+// The same fed from a bank of raw records: the ragged assemble kernel in front, everything behind it as above.
+extern "C" int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
+                                           const int32_t* counts0_host, const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
+                                           const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0,
+                                           const float* rec1, int64_t rows1, int normalize_fpfh, int64_t* matches0, int64_t* matches1,
+                                           float* mscores0, float* mscores1, float* Z, float* kpts0_out, float* kpts1_out, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_forward_frames_ragged";
+    if (!rec0 || !rec1 || !counts0 || !counts1 || !counts0_host || !counts1_host || !starts0 || !starts1 || !starts0_host || !starts1_host) {
+        mdgat_set_error("%s: null input pointer", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    if (rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: negative record count", who); return MDGAT_ERR_BAD_ARG; }
+    if (h && h->cfg.arithmetic != MDGAT_ARITH_FP64) { mdgat_set_error("%s: the handle needs MDGAT_ARITH_FP64 (ragged batches run in the exact mode only)", who); return MDGAT_ERR_BAD_ARG; }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the starts are passed on as long long");
+    FwdIn in;
+    in.rec0 = rec0; in.rec1 = rec1; in.normalize_fpfh = normalize_fpfh;
+    in.cnt0 = counts0; in.cnt1 = counts1; in.cnt0_host = counts0_host; in.cnt1_host = counts1_host;
+    in.start0 = reinterpret_cast<const long long*>(starts0); in.start1 = reinterpret_cast<const long long*>(starts1);
+    in.start0_host = reinterpret_cast<const long long*>(starts0_host); in.start1_host = reinterpret_cast<const long long*>(starts1_host);
+    in.rows0 = rows0; in.rows1 = rows1; in.kp0_out = kpts0_out; in.kp1_out = kpts1_out;
+    return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The assemble launch alone, into caller-owned buffers: every check of the counts and the starts on their host copies, as the forward makes them.
+extern "C" int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                                const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
+                                                const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0,
+                                                const float* rec1, int64_t rows1, int normalize_fpfh, double* in4, double* in33, float* kpts0_out,
+                                                float* kpts1_out, unsigned* guard, void* stream) {
+    const char* who = "mdgat_assemble_frames_f64_ragged";
+    if (!rec0 || !rec1 || !counts0 || !counts1 || !counts0_host || !counts1_host || !starts0 || !starts1 || !starts0_host || !starts1_host || !in4 || !in33) {
+        mdgat_set_error("%s: null pointer", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    if (B < 0 || Np <= 0 || Mp <= 0 || rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d", who, B, Np, Mp); return MDGAT_ERR_BAD_ARG; }
+    for (int b = 0; b < B; ++b) {
+        const int n = counts0_host[b], m = counts1_host[b];
+        if (n < 1 || n > Np || m < 1 || m > Mp) {
+            mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, n, m, Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        const long long s0 = starts0_host[b], s1 = starts1_host[b];
+        if (s0 < 0 || s0 + n > rows0 || s1 < 0 || s1 + m > rows1) {
+            mdgat_set_error("%s: pair %d reads records %lld .. %lld of %lld and %lld .. %lld of %lld: outside the bank", who, b, s0, s0 + n,
+                            (long long)rows0, s1, s1 + m, (long long)rows1);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    }
+    return launch_assemble_frames_ragged_f64(B, Np, Mp, rec0, rec1, reinterpret_cast<const long long*>(starts0), reinterpret_cast<const long long*>(starts1),
+                                             counts0, counts1, normalize_fpfh, in4, in33, kpts0_out, kpts1_out, guard, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
                                   const float* fpfh0, const float* kpts1, const float* sigma1, const float* fpfh1,
                                   int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z,
@@ -1069,6 +1141,23 @@ extern "C" int mdgat_gt_matches(int B, int N, int M, const float* kpts0, const f
     if (!kpts0 || !kpts1 || !gt0 || !gt1 || !rep) { mdgat_set_error("mdgat_gt_matches: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (N <= 0 || M <= 0) { mdgat_set_error("mdgat_gt_matches: empty frame"); return MDGAT_ERR_BAD_ARG; }
     return launch_gt_match(B, N, M, kpts0, kpts1, T0, T1, threshold, mutual, gt0, gt1, rep, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_gt_matches_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                       const int32_t* counts1_host, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
+                                       double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream) {
+    if (B < 0) { mdgat_set_error("mdgat_gt_matches_ragged: negative batch"); return MDGAT_ERR_BAD_ARG; }
+    if (Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_gt_matches_ragged: empty frame"); return MDGAT_ERR_BAD_ARG; }
+    if (!kpts0 || !kpts1 || !gt0 || !gt1 || !rep || !counts0 || !counts1 || !counts0_host || !counts1_host) {
+        mdgat_set_error("mdgat_gt_matches_ragged: null pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    for (int b = 0; b < B; ++b)
+        if (counts0_host[b] < 1 || counts0_host[b] > Np || counts1_host[b] < 1 || counts1_host[b] > Mp) {
+            mdgat_set_error("mdgat_gt_matches_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, counts0_host[b], counts1_host[b], Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+    return launch_gt_match(B, Np, Mp, kpts0, kpts1, T0, T1, threshold, mutual, gt0, gt1, rep, static_cast<hipStream_t>(stream), counts0, counts1);
 }
 
 extern "C" int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,

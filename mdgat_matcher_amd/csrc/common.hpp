@@ -224,7 +224,8 @@ int launch_extract_from_bests(int B, int N, int M, const SkExtract* ex, const in
 int launch_pose(int B, int N, int M, const float* kpts0, const float* kpts1, const int64_t* matches0, const double* T_gt,
                 double inlier_dist, double* T, double* stats, hipStream_t s);
 int launch_gt_match(int B, int N, int M, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
-                    double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, hipStream_t s);
+                    double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, hipStream_t s, const int* cnt0 = nullptr,
+                    const int* cnt1 = nullptr);      // cnt: a ragged batch in slots of N / M - gt -1 beyond a pair's counts
 // the evaluation scripts' per-pair record (eval_metrics.hip)
 int launch_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0, const int64_t* gt1,
                         const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist, double* metrics, double* T,

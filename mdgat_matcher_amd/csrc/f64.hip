@@ -698,46 +698,81 @@ __global__ __launch_bounds__(256) void assemble_f64_kernel(const double* kpts0, 
 // pairwise reduction for 8 <= n <= 128 (eight strided partial sums, combined as a tree, the tail added last), correctly rounded
 // square root, reciprocal and products, nothing contracted into an FMA.  tests/test_oracle_golden.py pins this order against the
 // reference loader's own outputs; tests/test_gpu_f64.py asks for a bit-identical Z.
-__global__ __launch_bounds__(256) void assemble_frames_f64_kernel(const float* rec0, const float* rec1, int normalize, double* in4, double* in33,
-                                                                   int B, int N, int M, unsigned* guard) {
+// One record -> its rows of in4 / in33 (and, with kp, its float32 keypoint); true when the record holds a non-finite word or - under
+// `normalize` - an all-zero FPFH row.  The one body of the uniform and the ragged kernel below: the two cannot drift.
+__device__ __forceinline__ bool assemble_record_f64(const float* rec, int normalize, double* in4, double* in33, float* kp) {
     // (every operation rounded by itself: no product contracted into the sum behind it.  Plain operators - HIP's __fmul_rn /
     // __fadd_rn ARE plain operators in this toolchain and __fsqrt_rn is the native approximation; `/` and __builtin_sqrtf are
     // correctly rounded under hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt)
 #pragma clang fp contract(off)
+    float v[37];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 37; ++c) {
+        const unsigned b = reinterpret_cast<const unsigned*>(rec)[c];
+        bad |= f32_bits_nonfinite(b);
+        v[c] = __builtin_bit_cast(float, b);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) in4[c] = (double)v[c];
+    if (kp) { kp[0] = v[0]; kp[1] = v[1]; kp[2] = v[2]; }
+    float inv = 1.f;
+    if (normalize) {
+        float r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = v[4 + j] * v[4 + j];
+#pragma unroll
+        for (int i = 8; i < 32; i += 8)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { const float q = v[4 + i + j] * v[4 + i + j]; r[j] = r[j] + q; }
+        float sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        const float q = v[36] * v[36];
+        sum = sum + q;
+        inv = 1.f / __builtin_sqrtf(sum);
+    }
+    bad |= !(inv < 3.0e38f);                 // (a row of zeros: 1 / 0 - NaN descriptors in the reference)
+#pragma unroll
+    for (int c = 0; c < 33; ++c) in33[c] = (double)(normalize ? v[4 + c] * inv : v[4 + c]);
+    return bad;
+}
+
+__global__ __launch_bounds__(256) void assemble_frames_f64_kernel(const float* rec0, const float* rec1, int normalize, double* in4, double* in33,
+                                                                   int B, int N, int M, unsigned* guard) {
     const int P = N + M;
     const size_t rows = (size_t)B * P;
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < rows; row += (size_t)gridDim.x * 256) {
         const int b = (int)(row / P), p = (int)(row - (size_t)b * P);
         const bool f1 = p >= N;
         const float* rec = (f1 ? rec1 + ((size_t)b * M + (p - N)) * 37 : rec0 + ((size_t)b * N + p) * 37);
-        float v[37];
-        bool bad = false;
+        if (assemble_record_f64(rec, normalize, in4 + row * 4, in33 + row * 33, nullptr)) f64_raise(guard);
+    }
+}
+
+// A ragged chunk out of a bank of records (mdgat_forward_frames_ragged): frame f of pair b is the cnt[b] records from row start[b] of
+// rec0 / rec1 [rows][37] (which may be one buffer), written into the forward's padded slots of N + M rows per pair.  Rows beyond a pair's
+// counts are written as ZEROS and no record is read for them, as assemble_f64_kernel does with counts; records no pair points at are
+// never read at all.  kp0 [B][N][3] / kp1 [B][M][3] (optional): the float32 keypoints as they lie in the records, zeros beyond the counts.
+__global__ __launch_bounds__(256) void assemble_frames_ragged_f64_kernel(const float* rec0, const float* rec1, const long long* start0,
+                                                                          const long long* start1, const int* cnt0, const int* cnt1, int normalize,
+                                                                          double* in4, double* in33, float* kp0, float* kp1, int B, int N, int M,
+                                                                          unsigned* guard) {
+    const int P = N + M;
+    const size_t rows = (size_t)B * P;
+    for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < rows; row += (size_t)gridDim.x * 256) {
+        const int b = (int)(row / P), p = (int)(row - (size_t)b * P);
+        const bool f1 = p >= N;
+        const int n = f1 ? p - N : p;
+        float* kp = f1 ? (kp1 ? kp1 + ((size_t)b * M + n) * 3 : nullptr) : (kp0 ? kp0 + ((size_t)b * N + n) * 3 : nullptr);
+        if (n >= (f1 ? cnt1[b] : cnt0[b])) {
 #pragma unroll
-        for (int c = 0; c < 37; ++c) {
-            const unsigned b = reinterpret_cast<const unsigned*>(rec)[c];
-            bad |= f32_bits_nonfinite(b);
-            v[c] = __builtin_bit_cast(float, b);
+            for (int c = 0; c < 4; ++c) in4[row * 4 + c] = 0.0;
+#pragma unroll
+            for (int c = 0; c < 33; ++c) in33[row * 33 + c] = 0.0;
+            if (kp) { kp[0] = 0.f; kp[1] = 0.f; kp[2] = 0.f; }
+            continue;
         }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) in4[row * 4 + c] = (double)v[c];
-        float inv = 1.f;
-        if (normalize) {
-            float r[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = v[4 + j] * v[4 + j];
-#pragma unroll
-            for (int i = 8; i < 32; i += 8)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float q = v[4 + i + j] * v[4 + i + j]; r[j] = r[j] + q; }
-            float sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-            const float q = v[36] * v[36];
-            sum = sum + q;
-            inv = 1.f / __builtin_sqrtf(sum);
-        }
-        bad |= !(inv < 3.0e38f);                 // (a row of zeros: 1 / 0 - NaN descriptors in the reference)
-#pragma unroll
-        for (int c = 0; c < 33; ++c) in33[row * 33 + c] = (double)(normalize ? v[4 + c] * inv : v[4 + c]);
-        if (bad) f64_raise(guard);
+        const float* rec = (f1 ? rec1 + ((size_t)start1[b] + n) * 37 : rec0 + ((size_t)start0[b] + n) * 37);
+        if (assemble_record_f64(rec, normalize, in4 + row * 4, in33 + row * 33, kp)) f64_raise(guard);
     }
 }
 
@@ -944,6 +979,17 @@ int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const flo
     const int blocks = (int)((rows + 255) / 256 < 8192 ? (rows + 255) / 256 : 8192);
     hipLaunchKernelGGL(assemble_frames_f64_kernel, dim3(blocks), dim3(256), 0, s, rec0, rec1, normalize, in4, in33, B, N, M, guard);
     return mdgat_check_hip(hipGetLastError(), "assemble_frames_f64 launch");
+}
+
+int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
+                                      const int* cnt0, const int* cnt1, int normalize, double* in4, double* in33, float* kp0, float* kp1,
+                                      unsigned* guard, hipStream_t s) {
+    const size_t rows = (size_t)B * (N + M);
+    if (!rows) return MDGAT_OK;
+    const int blocks = (int)((rows + 255) / 256 < 8192 ? (rows + 255) / 256 : 8192);
+    hipLaunchKernelGGL(assemble_frames_ragged_f64_kernel, dim3(blocks), dim3(256), 0, s, rec0, rec1, start0, start1, cnt0, cnt1, normalize, in4, in33,
+                       kp0, kp1, B, N, M, guard);
+    return mdgat_check_hip(hipGetLastError(), "assemble_frames_ragged_f64 launch");
 }
 
 int launch_f64_to_f32(const double* in, float* out, size_t n, unsigned* guard, hipStream_t s) {

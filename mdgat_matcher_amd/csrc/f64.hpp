@@ -58,7 +58,12 @@ int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* 
 // the same from raw float32 records [B][N][37] (load_data.py:146-165; FPFH normalised as numpy does it in float32, 290-292)
 int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const float* rec1, int normalize, double* in4, double* in33, unsigned* guard,
                                hipStream_t s);
-// guard (all three): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
+// a ragged chunk out of a bank of records: frame f of pair b = the cnt[b] records from row start[b] of rec0 / rec1 [rows][37], in slots of
+// N + M rows per pair; rows beyond the counts are zeros, their records unread; kp0 [B][N][3] / kp1 [B][M][3] float32 keypoints (optional)
+int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
+                                      const int* cnt0, const int* cnt1, int normalize, double* in4, double* in33, float* kp0, float* kp1,
+                                      unsigned* guard, hipStream_t s);
+// guard (all four): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
 int launch_f64_to_f32(const double* in, float* out, size_t n, unsigned* guard, hipStream_t s);
 
 // ---- layer_f64.hip: the tail of a propagation layer (mlp.0 + ReLU, mlp.3 + residual, the next layer's q | k | v) as ONE launch ----

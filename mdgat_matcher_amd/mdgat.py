@@ -540,8 +540,13 @@ class MDGAT(nn.Module):
                 if tuple(packed[key + f].shape) != (B, P) + tail:
                     raise ValueError(f'ragged batch: {key}{f} has shape {tuple(packed[key + f].shape)}: expected {(B, P) + tail} '
                                      f'({B} pairs by the count vectors)')
+        self._ragged_counts_checked(h0, h1, Np, Mp)
+        return B, Np, Mp
+
+    def _ragged_counts_checked(self, h0, h1, Np, Mp):
+        """the kernels' limits on the counts of a ragged batch in slots of Np x Mp"""
         kmax = max([int(k) for k in self._topk_schedule()] + [0])
-        for b in range(B):
+        for b in range(int(h0.numel())):
             n, m = int(h0[b]), int(h1[b])
             if n > self.RAGGED_MAX_KEYPOINTS or m > self.RAGGED_MAX_KEYPOINTS:
                 raise ValueError(f'pair {b} has {n} x {m} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
@@ -551,7 +556,6 @@ class MDGAT(nn.Module):
                 raise ValueError(f'pair {b} has {n} x {m} keypoints in slots of {Np} x {Mp}')
         if Np > self.RAGGED_MAX_KEYPOINTS or Mp > self.RAGGED_MAX_KEYPOINTS:
             raise ValueError(f'slots of {Np} x {Mp} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
-        return B, Np, Mp
 
     def _run_ragged(self, packed, return_Z):
         """One ragged forward through the library: the PADDED device outputs (matches -1 and scores 0 beyond a pair's counts), the host
@@ -591,6 +595,101 @@ class MDGAT(nn.Module):
         matched = (m0 >= 0).any(dim=1).cpu() if dustbin else None
         self.check(dev, synchronize=not dustbin)
         return m0, m1, s0, s1, Z, h0, h1, matched
+
+    def _run_frames_ragged(self, bank, counts, starts, normalize, return_Z, want_kpts=False):
+        """``_run_ragged`` fed from a bank of records (``ops.pack_frames``): the chunk's host counts and starts (``ops.frames_chunk``, no
+        empty frame among them) -> ``_run_ragged``'s tuple and, with ``want_kpts``, the padded float32 keypoints the assemble kernel wrote."""
+        from . import ops
+        if not self.exact() or self.bin_score.dtype != torch.float64:
+            raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'")
+        if self.training or getattr(self, 'eval_loss', False):
+            raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)')
+        h0, h1 = counts
+        B, Np, Mp = int(h0.numel()), int(h0.max()), int(h1.max())
+        self._ragged_counts_checked(h0, h1, Np, Mp)
+        rec = bank['records']
+        if not rec.is_cuda:
+            raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: the bank must be on a CUDA/HIP device; there is no CPU fallback')
+        dev = rec.device
+        st = self._state_for(dev)
+        if self.descriptor == 'FPFH_only':          # keypoints and saliency are not read (as in _run): a copy of the bank without them
+            rec = rec.clone()
+            rec[:, :4] = 0
+        args, dc, ds = ops._frames_args(bank, counts, starts, records=rec)
+        lib = _lib.load()
+        with torch.cuda.device(dev), st.lock:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, B, Np, Mp), dev)
+            m0 = torch.empty((B, Np), dtype=torch.int64, device=dev)
+            m1 = torch.empty((B, Mp), dtype=torch.int64, device=dev)
+            s0 = torch.empty((B, Np), dtype=torch.float32, device=dev)
+            s1 = torch.empty((B, Mp), dtype=torch.float32, device=dev)
+            Z = torch.empty((B, Np + 1, Mp + 1), dtype=torch.float32, device=dev) if return_Z else None
+            kp0 = torch.empty((B, Np, 3), dtype=torch.float32, device=dev) if want_kpts else None
+            kp1 = torch.empty((B, Mp, 3), dtype=torch.float32, device=dev) if want_kpts else None
+            _lib.check(lib.mdgat_forward_frames_ragged(st.handle, B, Np, Mp, *args, int(bool(normalize)), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
+                                                       s1.data_ptr(), Z.data_ptr() if Z is not None else None,
+                                                       kp0.data_ptr() if want_kpts else None, kp1.data_ptr() if want_kpts else None,
+                                                       ws.data_ptr(), ws.numel(), stream), 'mdgat_forward_frames_ragged')
+        dustbin = self.loss_method != 'superglue'
+        # the one synchronisation: which pairs matched nothing comes to the host with it
+        matched = (m0 >= 0).any(dim=1).cpu() if dustbin else None
+        self.check(dev, synchronize=not dustbin)
+        return (m0, m1, s0, s1, Z, h0, h1, matched), kp0, kp1, dc
+
+    @torch.no_grad()
+    def match_frames_ragged(self, bank, idx0, idx1, normalize=True, return_Z=False):
+        """``forward_ragged`` straight from raw frame records: ``bank`` is what ``ops.pack_frames`` made of a sequence's keypoint files
+        (uploaded once), the chunk of pairs two index vectors into it - pair b matches frame ``idx0[b]`` against frame ``idx1[b]``; a
+        frame may serve any number of pairs.  Decoding, the loader's float32 FPFH normalisation (``normalize``; load_data.py:290-292,
+        bit for bit), widening, padding and the forward run in one call of the library with one synchronisation; nothing is packed on
+        the host.  Returns the list of per-pair dicts ``forward_ragged`` returns (same keys, dtypes, leading axis of 1, the integer-zero
+        scores of a pair that matched nothing, ``'Z'`` with ``return_Z``), each bit for bit ``match_frames`` on that pair alone under
+        ``mdgat_set_f64_attention_form(0)``.  A pair with an empty frame gets the early-out dict of mdgat.py:374-382 and is left out of
+        the launch.  Records no pair of the chunk points at are never read.
+
+        ``ValueError`` for index vectors of different length, ``IndexError`` for an index outside the bank (both before anything touches
+        a device); then ``forward_ragged``'s refusals: the exact mode only, at most 575 keypoints per frame, no fewer than a dynamic
+        layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``."""
+        from . import ops
+        (h0, h1), (a0, a1) = ops.frames_chunk(bank, idx0, idx1)
+        rec = bank['records']
+        empty = ((h0 == 0) | (h1 == 0)).tolist()
+        zeros = lambda n: rec.new_zeros((1, int(n), 3), dtype=torch.float64)      # noqa: E731
+        results = [self._ragged_early_out({'keypoints0': zeros(h0[b]), 'keypoints1': zeros(h1[b])}) if e else None for b, e in enumerate(empty)]
+        order = [b for b, e in enumerate(empty) if not e]
+        if order:
+            padded = self._run_frames_ragged(bank, (h0[order].contiguous(), h1[order].contiguous()), (a0[order].contiguous(), a1[order].contiguous()),
+                                             normalize, return_Z)[0]
+            for b, d in zip(order, self._ragged_dicts(padded, return_Z)):
+                results[b] = d
+        return results
+
+    @torch.no_grad()
+    def evaluate_frames_ragged(self, bank, idx0, idx1, T0, T1, T_gt=None, gt_threshold=0.5, gt_mutual=False, normalize=True):
+        """``match_frames_ragged`` and then everything the loader and the evaluation scripts derive for the chunk, on the device: the
+        ground-truth matches of load_data.py:238-285 (``ops.gt_matches`` with the pairs' counts, on the float32 keypoints the assemble
+        kernel wrote; ``gt_threshold``, ``gt_mutual``) and the scripts' per-pair record against them (``ops.evaluate_matches``).  ``T0`` /
+        ``T1`` [B, 4, 4] float64: sensor -> world of frame ``idx0[b]`` / ``idx1[b]`` (``pose @ T_cam0_velo``; None = identity), ``T_gt``
+        [B, 4, 4] (optional) the relative pose - 4x4 products the caller makes on the host from the pose files.  Returns ``{'pairs':
+        match_frames_ragged's list, 'metrics': [B, len(ops.EvalColumns)] float64, 'T': [B, 4, 4], 'gt_matches0': [B, Np], 'gt_matches1':
+        [B, Mp] (int64, -1 beyond a pair's counts), 'rep': [B]}``, which ``ops.EvalMeter.update`` takes.  The forward's one
+        synchronisation, and ``evaluate_matches``' read of its bad-index word, as in ``evaluate_ragged``.  A pair with an empty frame
+        has nothing to evaluate: ``ValueError``."""
+        from . import ops
+        counts, starts = ops.frames_chunk(bank, idx0, idx1)
+        h0, h1 = counts
+        if int(h0.numel()) == 0 or int(h0.min()) < 1 or int(h1.min()) < 1:
+            raise ValueError('evaluate_frames_ragged: an empty chunk or a pair with an empty frame has nothing to evaluate (mdgat.py:374-382): leave it out')
+        only = self.descriptor == 'FPFH_only'
+        padded, kp0, kp1, dc = self._run_frames_ragged(bank, counts, starts, normalize, False, want_kpts=not only)
+        cnt = {'counts0': dc[0], 'counts1': dc[1], 'counts0_host': h0, 'counts1_host': h1}
+        if only:        # (the forward ran on a copy of the bank without keypoints: the true ones from the assemble kernel alone)
+            a = ops.assemble_frames_ragged(bank, idx0, idx1, normalize=False)
+            kp0, kp1 = a['keypoints0_f32'], a['keypoints1_f32']
+        g0, g1, rep = ops.gt_matches(kp0, kp1, T0, T1, threshold=gt_threshold, mutual=gt_mutual, counts=cnt)
+        metrics, T, _ = ops.evaluate_matches(padded[0], padded[1], g0, g1, kp0, kp1, T_gt=T_gt, counts=cnt)
+        return {'pairs': self._ragged_dicts(padded, False), 'metrics': metrics, 'T': T, 'gt_matches0': g0, 'gt_matches1': g1, 'rep': rep}
 
     def _ragged_dicts(self, padded, return_Z):
         """the per-pair dicts of ``forward`` from the padded outputs of ``_run_ragged`` (views, no copies)"""

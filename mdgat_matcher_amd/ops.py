@@ -137,6 +137,90 @@ def _ragged_counts(counts, B, device):
     return d0, d1, h0, h1
 
 
+def pack_frames(frames, device) -> dict:
+    """A bank of frames from their raw keypoint records: a list of [n_i, 37] float32 arrays (numpy or torch), as
+    ``np.fromfile(path, dtype=np.float32).reshape(-1, 37)`` gives the KITTI keypoint files (load_data.py:146-165) - a whole sequence, or
+    whatever a test list walks.  Returns ``{'records': [R, 37] float32 on ``device`` (one concatenation, one upload), 'starts': int64
+    [F], 'counts': int32 [F]}`` (host tensors): frame i is rows ``starts[i] .. starts[i] + counts[i]`` of ``records``.  A frame may be
+    empty; another width than 37 raises ``ValueError`` naming the frame; other dtypes are narrowed to float32.  Pure torch up to the
+    upload.  A chunk of pairs is then two index vectors into the bank (``assemble_frames_ragged``, ``MDGAT.match_frames_ragged``)."""
+    rows = []
+    for i, f in enumerate(frames):
+        t = torch.as_tensor(f)
+        if t.dim() != 2 or t.shape[1] != 37:
+            raise ValueError(f'pack_frames: frame {i} has shape {tuple(t.shape)}: expected [n, 37] records = xyz | saliency | 33-D FPFH')
+        rows.append(t.detach().to(device='cpu', dtype=torch.float32))
+    if not rows:
+        raise ValueError('pack_frames: no frames')
+    counts = torch.tensor([int(t.shape[0]) for t in rows], dtype=torch.int32)
+    starts = torch.zeros(len(rows), dtype=torch.int64)
+    starts[1:] = torch.cumsum(counts[:-1].to(torch.int64), 0)
+    return {'records': torch.cat(rows).contiguous().to(device), 'starts': starts, 'counts': counts}
+
+
+def frames_chunk(bank, idx0, idx1):
+    """The chunk of pairs (idx0[b], idx1[b]) of a ``pack_frames`` bank, checked on the host: (counts0, counts1) int32 [B] and
+    (starts0, starts1) int64 [B], CPU tensors.  ``ValueError`` for index vectors of different length, ``IndexError`` for an index
+    outside the bank.  Needs no device."""
+    i0, i1 = (torch.as_tensor(i, dtype=torch.int64).detach().to('cpu').reshape(-1) for i in (idx0, idx1))
+    if i0.numel() != i1.numel():
+        raise ValueError(f'idx0 holds {i0.numel()} frames, idx1 {i1.numel()}: a chunk is one frame of each per pair')
+    F = int(bank['counts'].numel())
+    for name, i in (('idx0', i0), ('idx1', i1)):
+        out = ((i < 0) | (i >= F)).nonzero()
+        if out.numel():
+            b = int(out[0])
+            raise IndexError(f'{name}[{b}] = {int(i[b])}: the bank holds frames 0 .. {F - 1}')
+    counts, starts = bank['counts'].to(torch.int32), bank['starts'].to(torch.int64)
+    return (counts[i0].contiguous(), counts[i1].contiguous()), (starts[i0].contiguous(), starts[i1].contiguous())
+
+
+def _frames_args(bank, counts, starts, records=None):
+    """the device copies of a chunk's counts and starts (one upload each) and the argument list the library's two record entries share"""
+    rec = bank['records'] if records is None else records
+    _need_cuda(rec)
+    if rec.dtype != torch.float32 or rec.dim() != 2 or rec.shape[1] != 37 or not rec.is_contiguous():
+        raise ValueError(f"bank['records'] {tuple(rec.shape)} {rec.dtype}: expected contiguous float32 [R, 37] (ops.pack_frames)")
+    dev = rec.device
+    dc = torch.stack(list(counts)).to(dev)
+    ds = torch.stack(list(starts)).to(dev)
+    h0, h1 = counts
+    s0, s1 = starts
+    args = (dc[0].data_ptr(), dc[1].data_ptr(), h0.data_ptr(), h1.data_ptr(), ds[0].data_ptr(), ds[1].data_ptr(), s0.data_ptr(), s1.data_ptr(),
+            rec.data_ptr(), int(rec.shape[0]), rec.data_ptr(), int(rec.shape[0]))
+    return args, dc, ds
+
+
+def assemble_frames_ragged(bank, idx0, idx1, normalize: bool = True) -> dict:
+    """What the loader makes of the records of a chunk of pairs, on the device (csrc/f64.hip, the ragged assemble kernel alone): frames
+    ``idx0[b]`` / ``idx1[b]`` of a ``pack_frames`` bank, decoded, the FPFH rows L2-normalised in float32 exactly as numpy does it
+    (load_data.py:290-292; ``normalize``), widened to float64 and padded with zeros to the largest count.  Returns a ``pack_ragged``-shaped
+    dict ``forward_ragged`` accepts - ``keypoints0/1`` [B, Np | Mp, 3], ``scores0/1``, ``descriptors0/1`` [.., 33] (views of the
+    kernel's two outputs), ``counts0/1`` and their ``_host`` copies - plus ``keypoints0_f32`` / ``keypoints1_f32`` (the float32 keypoints
+    ``gt_matches`` and ``evaluate_matches`` take) and ``range_violation`` (int32 [1] on the device: 1 when a record of a pair held a
+    non-finite word or an all-zero FPFH row; reading it synchronises).  Records no pair points at are never read."""
+    counts, starts = frames_chunk(bank, idx0, idx1)
+    h0, h1 = counts
+    B = int(h0.numel())
+    if B == 0 or int(h0.min()) < 1 or int(h1.min()) < 1:
+        raise ValueError('assemble_frames_ragged: an empty chunk or a pair with an empty frame has nothing to assemble')
+    Np, Mp = int(h0.max()), int(h1.max())
+    args, dc, ds = _frames_args(bank, counts, starts)
+    dev = bank['records'].device
+    in4 = torch.empty((B, Np + Mp, 4), dtype=torch.float64, device=dev)
+    in33 = torch.empty((B, Np + Mp, 33), dtype=torch.float64, device=dev)
+    kp0 = torch.empty((B, Np, 3), dtype=torch.float32, device=dev)
+    kp1 = torch.empty((B, Mp, 3), dtype=torch.float32, device=dev)
+    guard = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mdgat_assemble_frames_f64_ragged(B, Np, Mp, *args, int(bool(normalize)), in4.data_ptr(), in33.data_ptr(), kp0.data_ptr(),
+                                                                kp1.data_ptr(), guard.data_ptr(), _stream(in4)), 'mdgat_assemble_frames_f64_ragged')
+    return {'keypoints0': in4[:, :Np, :3], 'scores0': in4[:, :Np, 3], 'descriptors0': in33[:, :Np],
+            'keypoints1': in4[:, Np:, :3], 'scores1': in4[:, Np:, 3], 'descriptors1': in33[:, Np:],
+            'counts0': dc[0], 'counts1': dc[1], 'counts0_host': h0, 'counts1_host': h1,
+            'keypoints0_f32': kp0, 'keypoints1_f32': kp1, 'range_violation': guard}
+
+
 def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64.
 
@@ -430,10 +514,13 @@ def pose_from_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, matches0: torch.
     return T, stats
 
 
-def gt_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, T0=None, T1=None, threshold: float = 0.5, mutual: bool = False):
+def gt_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, T0=None, T1=None, threshold: float = 0.5, mutual: bool = False, counts=None):
     """Ground-truth matches of the loader (load_data.py:238-285): kpts [B, N, 3] / [B, M, 3] in the sensor frame,
     T0 / T1 [B, 4, 4] float64 sensor -> world (None = identity).  Returns (gt_matches0 [B, N], gt_matches1 [B, M],
-    rep [B]) as int64, -1 = no match."""
+    rep [B]) as int64, -1 = no match.
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch in padded slots - pair b's matches and rep are those of
+    the pair alone, -1 beyond its counts; the keypoints there are not read."""
     _need_cuda(kpts0, kpts1)
     k0 = kpts0.to(torch.float32).contiguous()
     k1 = kpts1.to(torch.float32).contiguous()
@@ -443,11 +530,18 @@ def gt_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, T0=None, T1=None, thres
     rep = torch.empty((B,), dtype=torch.int64, device=k0.device)
     t0 = T0.to(device=k0.device, dtype=torch.float64).contiguous() if T0 is not None else None
     t1 = T1.to(device=k0.device, dtype=torch.float64).contiguous() if T1 is not None else None
+    for name, t in (('T0', t0), ('T1', t1)):
+        if counts is not None and t is not None and tuple(t.shape) != (B, 4, 4):
+            raise ValueError(f'{name} {tuple(t.shape)}: expected [{B}, 4, 4]')
+    tail = (t0.data_ptr() if t0 is not None else None, t1.data_ptr() if t1 is not None else None, float(threshold), int(bool(mutual)),
+            g0.data_ptr(), g1.data_ptr(), rep.data_ptr(), _stream(k0))
     with torch.cuda.device(k0.device):
-        _lib.check(_lib.load().mdgat_gt_matches(B, N, M, k0.data_ptr(), k1.data_ptr(),
-                                                t0.data_ptr() if t0 is not None else None,
-                                                t1.data_ptr() if t1 is not None else None, float(threshold), int(bool(mutual)),
-                                                g0.data_ptr(), g1.data_ptr(), rep.data_ptr(), _stream(k0)), 'mdgat_gt_matches')
+        if counts is not None:
+            d0, d1, h0, h1 = _ragged_counts(counts, B, k0.device)
+            _lib.check(_lib.load().mdgat_gt_matches_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), k0.data_ptr(),
+                                                           k1.data_ptr(), *tail), 'mdgat_gt_matches_ragged')
+        else:
+            _lib.check(_lib.load().mdgat_gt_matches(B, N, M, k0.data_ptr(), k1.data_ptr(), *tail), 'mdgat_gt_matches')
     return g0, g1, rep
 
 

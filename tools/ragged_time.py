@@ -6,7 +6,12 @@ In one process, alternating, after warming all:
   (a) 64 single-pair ``forward`` calls (what test.py's batch_size=1 loop does),
   (b) one ``forward_ragged`` of the 64, packed once outside the clock (``ops.pack_ragged``),
   (b') the same on the LIST of per-pair dicts, as INTEGRATION.md's loop calls it: packing inside the clock,
-  (c) for scale, ``forward`` on 64 uniform pairs of the largest count.
+  (c) for scale, ``forward`` on 64 uniform pairs of the largest count,
+  (d) one ``match_frames_ragged`` of the 64 out of a bank of their 128 frames' raw float32 records, uploaded once outside the clock
+      (``ops.pack_frames``): decode, normalisation and padding on the device,
+  (d') the same with ``ops.pack_frames`` - the concatenation of the host records and the upload - inside the clock.
+(The records are the pairs' own arrays narrowed to float32, so (d) re-normalises FPFH rows that are already normalised: the same work as
+on loader records, results equal to (b)'s to float32 rounding of the inputs.)
 Device-synchronised host clock; the median of --windows windows and their spread (min .. max)."""
 import argparse
 import json
@@ -42,6 +47,10 @@ def main():
     packed = ops.pack_ragged(pairs)
     Np, Mp = max(n for n, _ in counts), max(m for _, m in counts)
     uniform = synth.make_batch(a.pairs, Np, Mp, device=dev)
+    # the frames as np.fromfile(...).reshape(-1, 37) would give them: host float32 records, frame 0 and frame 1 of every pair
+    frames = [torch.cat([p['keypoints' + f][0], p['scores' + f][0][:, None], p['descriptors' + f][0]], -1).float().cpu().numpy() for p in pairs for f in '01']
+    idx0, idx1 = list(range(0, 2 * a.pairs, 2)), list(range(1, 2 * a.pairs, 2))
+    bank = ops.pack_frames(frames, dev)
 
     def run_a():
         for p in pairs:
@@ -56,7 +65,14 @@ def main():
     def run_c():
         net(uniform)
 
-    legs = {'a_single_pair_calls': run_a, 'b_forward_ragged': run_b, 'b_list_with_packing': run_b_list, 'c_uniform_largest': run_c}
+    def run_d():
+        net.match_frames_ragged(bank, idx0, idx1)
+
+    def run_d_pack():
+        net.match_frames_ragged(ops.pack_frames(frames, dev), idx0, idx1)
+
+    legs = {'a_single_pair_calls': run_a, 'b_forward_ragged': run_b, 'b_list_with_packing': run_b_list, 'c_uniform_largest': run_c,
+            'd_match_frames_ragged': run_d, 'd_with_pack_frames': run_d_pack}
     times = {k: [] for k in legs}
     with torch.no_grad():
         for fn in legs.values():
@@ -69,12 +85,15 @@ def main():
                 fn()
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) * 1e3)
-        prof = None
+        prof = prof_d = None
         if a.profile:
             net.profile(dev, True)
             run_b()
             torch.cuda.synchronize()
-            prof = {k: v for k, v in net.profile(dev, False).items() if v[1]}
+            prof = {k: v for k, v in net.profile(dev, True).items() if v[1]}
+            run_d()
+            torch.cuda.synchronize()
+            prof_d = {k: v for k, v in net.profile(dev, False).items() if v[1]}
     med = {k: float(np.median(v)) for k, v in times.items()}
     # the work of the ragged batch relative to the uniform one: attention and Sinkhorn scale with N_b M_b (and N_b^2 + M_b^2), the
     # row-wise launches with N_b + M_b; both ratios are given
@@ -86,9 +105,12 @@ def main():
            'ratio_a_over_b': med['a_single_pair_calls'] / med['b_forward_ragged'],
            'ratio_a_over_b_list': med['a_single_pair_calls'] / med['b_list_with_packing'],
            'work_ragged_over_uniform': {'quadratic': quad, 'linear': lin},
-           'b_over_c': med['b_forward_ragged'] / med['c_uniform_largest']}
+           'b_over_c': med['b_forward_ragged'] / med['c_uniform_largest'],
+           'd_over_b': med['d_match_frames_ragged'] / med['b_forward_ragged'],
+           'd_pack_over_b_list': med['d_with_pack_frames'] / med['b_list_with_packing']}
     if prof:
         res['profile_ms_launches'] = prof
+        res['profile_ms_launches_d'] = prof_d
     print(json.dumps(res))
 
 
