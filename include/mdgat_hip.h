@@ -193,6 +193,13 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
                       float* Z, const mdgat_taps* taps,
                       void* workspace, size_t workspace_bytes, void* stream);
 #define MDGAT_RAGGED_MAX_KEYPOINTS 575   /* keypoints per frame (and per padded slot) of a ragged batch: what the register-resident fp64 Sinkhorn holds */
+/* THE COUNTS OF A RAGGED BATCH.  Every ..._ragged entry takes pairs of different sizes in slots padded to Np x Mp and, behind B, Np, Mp, their
+ * keypoint counts twice: counts0 / counts1, DEVICE int32 [B], read by the kernels; counts0_host / counts1_host, the same values in HOST
+ * memory, on which every check is made before anything is enqueued - one function for all entries (csrc/ragged.hpp), pair by pair:
+ * 1 <= counts0[b] <= Np and 1 <= counts1[b] <= Mp; where the entry runs dynamic attention, no k exceeds min(counts0[b], counts1[b])
+ * (torch.topk raises in the reference); where it reads a bank of records (starts0 / starts1, DEVICE int64 [B], and starts0_host /
+ * starts1_host), 0 <= starts[b] and starts[b] + counts[b] <= rows.  Else MDGAT_ERR_BAD_ARG naming the first offending pair; so for a
+ * null count or start vector. */
 /* mdgat_forward_f64 on a RAGGED batch: B pairs of different sizes in one call (the evaluation scripts run one pair per call because no two
  * frames hold the same number of keypoints - test.py:132; padding is no way out: padded keypoints change every softmax, every top-k and
  * the optimal transport).  Pair b has counts0[b] x counts1[b] keypoints and is stored in a slot padded to Np x Mp: kpts0 [B][Np][3], sigma0
@@ -206,9 +213,7 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  *   - Beyond a pair's counts: matches -1, scores 0, the rest of its Z slot 0.
  *   - What the inputs hold beyond a pair's counts is never read: NaN there reaches no result and no guard.
  *   - Uniform counts (all Np / Mp) give the bits of mdgat_forward_f64 (with the same exception: Np == Mp == a dynamic layer's k).
- * counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same values in HOST memory - every check is made on them before
- * anything is enqueued: 1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp, and every dynamic layer's k <= both (torch.topk raises), else
- * MDGAT_ERR_BAD_ARG naming the first offending pair.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
+ * The counts are checked as described at THE COUNTS OF A RAGGED BATCH above, against every dynamic layer's k.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
  * f64_sinkhorn not MDGAT_F64_SINKHORN_OFF, f64_layers automatic, mdgat_set_f64_sinkhorn_form not 1 (else MDGAT_ERR_UNSUPPORTED); an fp32
  * handle is MDGAT_ERR_BAD_ARG.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
  * The ragged mdgat_forward_frames is mdgat_forward_frames_ragged below; there is no ragged loss. */
@@ -235,9 +240,7 @@ int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* fram
  * Frame 0 of pair b is the counts0[b] records from row starts0[b] of rec0, frame 1 the counts1[b] records from row starts1[b] of rec1;
  * the assemble kernel decodes, normalises (normalize_fpfh, the loader's float32 arithmetic bit for bit as in mdgat_forward_frames), widens
  * and pads them into the forward's slots of Np / Mp rows, zeros beyond the counts.  Everything behind it, every result and every limit
- * are mdgat_forward_f64_ragged's; so are its checks, made on the host copies before anything is enqueued, plus 0 <= starts[b] and
- * starts[b] + counts[b] <= rows (else MDGAT_ERR_BAD_ARG naming the first offending pair).  starts0 / starts1: DEVICE int64 [B];
- * starts0_host / starts1_host: the same in HOST memory.
+ * are mdgat_forward_f64_ragged's; counts and starts are checked as described at THE COUNTS OF A RAGGED BATCH.
  *   - Only a pair's own records are read: what any other record of the bank holds - NaN included - reaches no result and no guard.
  *   - A non-finite word or (normalize_fpfh) an all-zero FPFH row among a pair's own records raises the handle's range-violation word
  *     (mdgat_async_status), as in mdgat_forward_frames.
@@ -251,7 +254,8 @@ int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int Mp, const in
                                 float* Z, float* kpts0_out, float* kpts1_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Its assemble launch alone, into caller-owned in4 [B][Np+Mp][4] and in33 [B][Np+Mp][33] fp64 (rows of a pair: frame 0's Np, then frame
  * 1's Mp): x y z saliency and the FPFH row as the encoders read them.  guard (device memory, optional; the caller clears it) is set to 1
- * where the forward would raise its range-violation word.  No handle: the same checks of counts and starts. */
+ * where the forward would raise its range-violation word.  No handle; counts and starts are checked as described at THE COUNTS OF A
+ * RAGGED BATCH. */
 int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                      const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1, const int64_t* starts0_host,
                                      const int64_t* starts1_host, const float* rec0, int64_t rows0, const float* rec1, int64_t rows1,
@@ -441,9 +445,8 @@ int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double
  * Z[b][0 .. counts0[b]][0 .. counts1[b]] with the dustbin row at row counts0[b] and the dustbin column at column counts1[b], its matches
  * (dustbin = no match), its scores, and the rule of mdgat.py:465-467 (no frame-0 keypoint matched: all scores zero) applied to the pair
  * alone.  Beyond a pair's counts the outputs are fixed: the rest of its Z slot 0, matches -1, scores 0.
- * counts0 / counts1: DEVICE int32 [B], read by the kernels; counts0_host / counts1_host: the same values in HOST memory, checked before
- * anything is launched (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp, else MDGAT_ERR_BAD_ARG naming the first offending pair).  Np, Mp <=
- * 575 (the register-resident form; else MDGAT_ERR_UNSUPPORTED, as under mdgat_set_f64_sinkhorn_form(1)).  workspace:
+ * Np, Mp <= 575 (the register-resident form; else MDGAT_ERR_UNSUPPORTED, as under mdgat_set_f64_sinkhorn_form(1)); then the counts are
+ * checked as described at THE COUNTS OF A RAGGED BATCH.  workspace:
  * mdgat_sinkhorn_f64_ragged_workspace_bytes, 256-byte aligned.  Unlike their uniform siblings these two entries hand the kernel an error
  * word and read it back: they SYNCHRONISE `stream` before they return, and return MDGAT_ERR_HIP instead of numbers when a workgroup gave
  * up waiting for its partners. */
@@ -613,9 +616,7 @@ int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* 
  * and are never read; their message rows and selection words are zero.  A pair's rows are those of mdgat_attention_f64 on the pair alone -
  * bit for bit where both launches run the same kernel form (mdgat_set_f64_attention_form(0), and the larger frame of both launches on the
  * same side of 512 keys for a dynamic layer), to rounding otherwise; the kept keys are the same always.  topk > 0 runs the dynamic kernel
- * also where k equals a pair's key count.  counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same values in HOST
- * memory, checked before the launch: 1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp and topk <= both (torch.topk raises), else
- * MDGAT_ERR_BAD_ARG naming the first offending pair. */
+ * also where k equals a pair's key count.  The counts are checked as described at THE COUNTS OF A RAGGED BATCH, against topk. */
 int mdgat_attention_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                const int32_t* counts1_host, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream);
 
@@ -670,8 +671,7 @@ int mdgat_gt_matches(int B, int N, int M, const float* kpts0, const float* kpts1
 
 /* The same on a RAGGED batch: pair b has counts0[b] x counts1[b] keypoints in slots padded to Np x Mp (kpts0 [B][Np][3], kpts1 [B][Mp][3],
  * gt0 [B][Np], gt1 [B][Mp]); its matches and rep[b] are those of mdgat_gt_matches on the pair alone, gt0 / gt1 beyond its counts are -1,
- * the keypoints there are not read.  counts0 / counts1: DEVICE int32 [B]; counts0_host / counts1_host: the same in HOST memory, checked
- * before the launch (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp).  The LDS follows Np + Mp (MDGAT_ERR_UNSUPPORTED beyond 160 KB). */
+ * the keypoints there are not read.  The counts are checked as described at THE COUNTS OF A RAGGED BATCH.  The LDS follows Np + Mp (MDGAT_ERR_UNSUPPORTED beyond 160 KB). */
 int mdgat_gt_matches_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                             const int32_t* counts1_host, const float* kpts0, const float* kpts1, const double* T0, const double* T1,
                             double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream);
@@ -734,8 +734,8 @@ int mdgat_eval_metrics(int B, int N, int M, const int64_t* matches0, const int64
                        unsigned* bad_index, void* stream);
 /* The same on a RAGGED batch (mdgat_forward_f64_ragged's outputs): pair b has counts0[b] x counts1[b] keypoints in slots padded to Np x Mp
  * (matches0 / gt0 [B][Np], matches1 / gt1 [B][Mp], kpts0 [B][Np][3], kpts1 [B][Mp][3]); what lies beyond a pair's counts is not read, and
- * its row and T are those of mdgat_eval_metrics on the pair alone, bit for bit.  counts0 / counts1: DEVICE int32 [B]; counts0_host /
- * counts1_host: the same in HOST memory, checked before the launch (1 <= counts0[b] <= Np, 1 <= counts1[b] <= Mp). */
+ * its row and T are those of mdgat_eval_metrics on the pair alone, bit for bit.  The counts are checked as described at THE COUNTS OF A
+ * RAGGED BATCH. */
 int mdgat_eval_metrics_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                               const int32_t* counts1_host, const int64_t* matches0, const int64_t* matches1, const int64_t* gt0,
                               const int64_t* gt1, const float* kpts0, const float* kpts1, const double* T_gt, double inlier_dist,

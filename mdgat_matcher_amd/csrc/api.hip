@@ -13,6 +13,7 @@
 #include "loss.hpp"
 #include "weights.hpp"
 #include "pool_f64.hpp"
+#include "ragged.hpp"
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local char g_err[512] = "";
@@ -306,6 +307,39 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss) {
 }  // namespace
 
 
+// ---------------------------------------------------------------------------------- ragged batches
+// every per-pair check of a ragged batch (ragged.hpp), for every entry that takes one
+int mdgat_check_ragged(const char* who, int B, int Np, int Mp, const RaggedCounts& c, const RaggedStarts* bank, const int* topk, int ntopk, int* cnt_min) {
+    if (!c.cnt0 || !c.cnt1 || !c.host0 || !c.host1) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (bank && (!bank->start0 || !bank->start1 || !bank->host0 || !bank->host1)) { mdgat_set_error("%s: null starts pointer", who); return MDGAT_ERR_BAD_ARG; }
+    int cmin = Np < Mp ? Np : Mp;
+    for (int b = 0; b < B; ++b) {
+        const int n = c.host0[b], m = c.host1[b], keys = n < m ? n : m;
+        if (n < 1 || n > Np || m < 1 || m > Mp) {
+            mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, n, m, Np, Mp);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        for (int i = 0; i < ntopk; ++i)
+            if (topk[i] > keys) {      // torch.topk raises (mdgat.py:202)
+                if (ntopk > 1) mdgat_set_error("%s: pair %d: k=%d exceeds the number of keys (%d), layer %d", who, b, topk[i], keys, i);
+                else mdgat_set_error("%s: pair %d: k=%d exceeds the number of keys (%d)", who, b, topk[i], keys);
+                return MDGAT_ERR_BAD_ARG;
+            }
+        if (bank) {
+            // (the pair's records lie inside the bank: the kernel reads rows start .. start + count - 1 and no others)
+            const long long s0 = bank->host0[b], s1 = bank->host1[b];
+            if (s0 < 0 || s0 + n > bank->rows0 || s1 < 0 || s1 + m > bank->rows1) {
+                mdgat_set_error("%s: pair %d reads records %lld .. %lld of %lld and %lld .. %lld of %lld: outside the bank", who, b, s0, s0 + n,
+                                bank->rows0, s1, s1 + m, bank->rows1);
+                return MDGAT_ERR_BAD_ARG;
+            }
+        }
+        cmin = keys < cmin ? keys : cmin;
+    }
+    if (cnt_min) *cnt_min = cmin;
+    return MDGAT_OK;
+}
+
 // ---------------------------------------------------------------------------------- forward
 // inputs of a forward: six fp32 arrays, or raw 37-float frame records, or (MDGAT_ARITH_FP64) six fp64 arrays
 struct FwdIn {
@@ -313,14 +347,11 @@ struct FwdIn {
     const float *rec0 = nullptr, *rec1 = nullptr;
     int normalize_fpfh = 0;
     const double *dk0 = nullptr, *ds0 = nullptr, *df0 = nullptr, *dk1 = nullptr, *ds1 = nullptr, *df1 = nullptr;
-    // a ragged batch (mdgat_forward_f64_ragged): the pairs' own keypoint counts in slots of N / M - device int32 [B] for the kernels, the
-    // same values on the host for plan_forward's checks
-    const int *cnt0 = nullptr, *cnt1 = nullptr, *cnt0_host = nullptr, *cnt1_host = nullptr;
-    // a ragged chunk out of a bank of records (mdgat_forward_frames_ragged): rec0 / rec1 are [rows0 | rows1][37] and frame f of pair b is the
-    // cnt[b] records from row start[b] - device int64 [B] for the kernel, host copies for the checks; kp0_out / kp1_out (optional):
-    // the padded float32 keypoints [B][N][3] / [B][M][3] the assemble kernel writes for the steps behind the matcher
-    const long long *start0 = nullptr, *start1 = nullptr, *start0_host = nullptr, *start1_host = nullptr;
-    long long rows0 = 0, rows1 = 0;
+    // a ragged batch (mdgat_forward_f64_ragged): the pairs' own keypoint counts in slots of N / M; out of a bank of records
+    // (mdgat_forward_frames_ragged): rec0 / rec1 are the bank's, indexed by the starts (ragged.hpp); kp0_out / kp1_out (optional): the
+    // padded float32 keypoints [B][N][3] / [B][M][3] the assemble kernel writes for the steps behind the matcher
+    RaggedCounts counts;
+    RaggedStarts bank;
     float *kp0_out = nullptr, *kp1_out = nullptr;
     static FwdIn arrays(const float* k0, const float* s0, const float* f0, const float* k1, const float* s1, const float* f1) {
         FwdIn in; in.kpts0 = k0; in.sigma0 = s0; in.fpfh0 = f0; in.kpts1 = k1; in.sigma1 = s1; in.fpfh1 = f1; return in;
@@ -332,10 +363,9 @@ struct FwdIn {
     FwdIn from(size_t c, int N, int M) const {
         auto o = [](auto* q, size_t n) { return q ? q + n : q; };
         return FwdIn{o(kpts0, c * N * 3), o(sigma0, c * N), o(fpfh0, c * N * 33), o(kpts1, c * M * 3), o(sigma1, c * M), o(fpfh1, c * M * 33),
-                     o(rec0, start0 ? 0 : c * N * 37), o(rec1, start0 ? 0 : c * M * 37), normalize_fpfh,      // (a bank is indexed by the starts)
+                     o(rec0, bank ? 0 : c * N * 37), o(rec1, bank ? 0 : c * M * 37), normalize_fpfh,      // (a bank is indexed by the starts)
                      o(dk0, c * N * 3), o(ds0, c * N), o(df0, c * N * 33), o(dk1, c * M * 3), o(ds1, c * M), o(df1, c * M * 33),
-                     o(cnt0, c), o(cnt1, c), o(cnt0_host, c), o(cnt1_host, c),
-                     o(start0, c), o(start1, c), o(start0_host, c), o(start1_host, c), rows0, rows1, o(kp0_out, c * N * 3), o(kp1_out, c * M * 3)};
+                     counts.from(c), bank.from(c), o(kp0_out, c * N * 3), o(kp1_out, c * M * 3)};
     }
 };
 
@@ -434,7 +464,7 @@ struct Path {
     bool tail64;      // MDGAT_ARITH_FP64: final_proj, scores, Sinkhorn and the extraction's arg-maxes in fp64 too
     bool fused64;     // the fp64 encoders and layer tails as fused launches, the last one writing the hand-over to fp32
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
-    int cnt_min;      // a ragged batch (FwdIn::cnt0): the smallest keypoint count of any frame; 0 otherwise
+    int cnt_min;      // a ragged batch (FwdIn::counts): the smallest keypoint count of any frame; 0 otherwise
     LanePlan lanes;
 };
 
@@ -478,7 +508,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         mdgat_set_error("mdgat_forward: null pointer argument");
         return MDGAT_ERR_BAD_ARG;
     }
-    p.lanes = (taps || in.cnt0) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
+    p.lanes = (taps || in.counts) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
     const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
@@ -508,43 +538,18 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
     p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
     p.cnt_min = 0;
-    if (in.cnt0) {
+    if (in.counts) {
         // The ragged plan: the kernels that take per-pair counts are the exact mode's with its fp64 tail on the register-resident Sinkhorn;
-        // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); every count is checked on its host copy, naming the first offending pair.
-        const char* who = in.start0 ? "mdgat_forward_frames_ragged" : "mdgat_forward_f64_ragged";
-        if (!in.cnt1 || !in.cnt0_host || !in.cnt1_host) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
-        if (in.start0 && (!in.start1 || !in.start0_host || !in.start1_host)) { mdgat_set_error("%s: null starts pointer", who); return MDGAT_ERR_BAD_ARG; }
+        // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); the counts (and the starts into a bank)
+        // are checked on their host copies, against the whole k schedule (mdgat_check_ragged).
+        const char* who = in.bank ? "mdgat_forward_frames_ragged" : "mdgat_forward_f64_ragged";
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
         if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || !sinkhorn_f64_ragged_supported(N, M)) {
             mdgat_set_error("%s: ragged batches need the fp64 tail on the register-resident Sinkhorn: f64_sinkhorn not off, f64_layers automatic, "
                             "mdgat_set_f64_sinkhorn_form not 1, and at most %d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_MAX_KEYPOINTS, N, M);
             return MDGAT_ERR_UNSUPPORTED;
         }
-        int cmin = N < M ? N : M;
-        for (int b = 0; b < B; ++b) {
-            const int n = in.cnt0_host[b], m = in.cnt1_host[b];
-            if (n < 1 || n > N || m < 1 || m > M) {
-                mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, n, m, N, M);
-                return MDGAT_ERR_BAD_ARG;
-            }
-            for (int i = 0; i < L2; ++i)
-                if (h->cfg.topk[i] > (n < m ? n : m)) {      // torch.topk raises (mdgat.py:202)
-                    mdgat_set_error("%s: pair %d (%d x %d keypoints): layer %d: dynamic attention k=%d exceeds the number of keys", who, b, n, m, i, h->cfg.topk[i]);
-                    return MDGAT_ERR_BAD_ARG;
-                }
-            cmin = n < cmin ? n : cmin;
-            cmin = m < cmin ? m : cmin;
-            if (in.start0) {
-                // (the pair's records lie inside the bank: the kernel reads rows start .. start + count - 1 and no others)
-                const long long s0 = in.start0_host[b], s1 = in.start1_host[b];
-                if (s0 < 0 || s0 + n > in.rows0 || s1 < 0 || s1 + m > in.rows1) {
-                    mdgat_set_error("%s: pair %d reads records %lld .. %lld of %lld and %lld .. %lld of %lld: outside the bank", who, b, s0, s0 + n,
-                                    in.rows0, s1, s1 + m, in.rows1);
-                    return MDGAT_ERR_BAD_ARG;
-                }
-            }
-        }
-        p.cnt_min = cmin;
+        if (int rc = mdgat_check_ragged(who, B, N, M, in.counts, in.bank ? &in.bank : nullptr, h->cfg.topk, L2, &p.cnt_min)) return rc;
     }
     return MDGAT_OK;
 }
@@ -561,8 +566,8 @@ struct Fwd {
     mdgat_taps taps;         // all null when the call has none
     mdgat_handle::ProfLane& pl;
     int defer_alldust;       // a slice: the batch-wide rule is applied after the last one
-    const int *cnt0, *cnt1;  // a ragged batch (FwdIn): null otherwise
-    int cnt_min;
+    const int *cnt0, *cnt1;  // a ragged batch (FwdIn::counts): null otherwise
+    int cnt_min;             // Path::cnt_min
     unsigned* guard() const { return status + MDGAT_STATUS_RANGE; }
     // profiling (off by default): an event after every launch on this lane's stream; the intervals are attributed to the
     // kernel classes after the whole batch has been enqueued (prof_collect), which then ends with a synchronisation
@@ -657,8 +662,8 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     // 32 + 64 + 128 + 64 + 128 = 416 of the 603 doubles per point there
     double* in4 = ws.hid64 + Rz * (256 - 37);
     double* in33 = in4 + Rz * 4;
-    if (int rc = in.start0 ? launch_assemble_frames_ragged_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.start0, in.start1, f.cnt0, f.cnt1, in.normalize_fpfh, in4,
-                                                               in33, in.kp0_out, in.kp1_out, f.guard(), f.s)
+    if (int rc = in.bank ? launch_assemble_frames_ragged_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.bank.start0, in.bank.start1, f.cnt0, f.cnt1, in.normalize_fpfh, in4,
+                                                             in33, in.kp0_out, in.kp1_out, f.guard(), f.s)
                : in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
                          : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_F64_OTHER);
@@ -792,8 +797,8 @@ static int tail32(Fwd& f, const FwdOut& o) {
 static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
     const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss);
-    Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust};
-    f.cnt0 = in.cnt0; f.cnt1 = in.cnt1; f.cnt_min = p.cnt_min;
+    Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust,
+          in.counts.cnt0, in.counts.cnt1, p.cnt_min};
     f.mark(-1);
     int rc;
     if ((N & 31) || (M & 31))   // the attention kernel reads V^T in whole 32-key blocks: pad columns must be zero
@@ -914,8 +919,15 @@ extern "C" int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, 
         return MDGAT_ERR_BAD_ARG;
     }
     FwdIn in = FwdIn::arrays(kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1);
-    in.cnt0 = counts0; in.cnt1 = counts1; in.cnt0_host = counts0_host; in.cnt1_host = counts1_host;
+    in.counts = RaggedCounts{counts0, counts1, counts0_host, counts1_host};
     return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+}
+
+// the ABI's int64 starts as the launchers take them
+static RaggedStarts ragged_starts(const int64_t* s0, const int64_t* s1, const int64_t* h0, const int64_t* h1, int64_t rows0, int64_t rows1) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the starts are passed on as long long");
+    auto ll = [](const int64_t* q) { return reinterpret_cast<const long long*>(q); };
+    return RaggedStarts{ll(s0), ll(s1), ll(h0), ll(h1), rows0, rows1};
 }
 
 // The same fed from a bank of raw records: the ragged assemble kernel in front, everything behind it as above.
@@ -932,13 +944,11 @@ extern "C" int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int M
     }
     if (rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: negative record count", who); return MDGAT_ERR_BAD_ARG; }
     if (h && h->cfg.arithmetic != MDGAT_ARITH_FP64) { mdgat_set_error("%s: the handle needs MDGAT_ARITH_FP64 (ragged batches run in the exact mode only)", who); return MDGAT_ERR_BAD_ARG; }
-    static_assert(sizeof(long long) == sizeof(int64_t), "the starts are passed on as long long");
     FwdIn in;
     in.rec0 = rec0; in.rec1 = rec1; in.normalize_fpfh = normalize_fpfh;
-    in.cnt0 = counts0; in.cnt1 = counts1; in.cnt0_host = counts0_host; in.cnt1_host = counts1_host;
-    in.start0 = reinterpret_cast<const long long*>(starts0); in.start1 = reinterpret_cast<const long long*>(starts1);
-    in.start0_host = reinterpret_cast<const long long*>(starts0_host); in.start1_host = reinterpret_cast<const long long*>(starts1_host);
-    in.rows0 = rows0; in.rows1 = rows1; in.kp0_out = kpts0_out; in.kp1_out = kpts1_out;
+    in.counts = RaggedCounts{counts0, counts1, counts0_host, counts1_host};
+    in.bank = ragged_starts(starts0, starts1, starts0_host, starts1_host, rows0, rows1);
+    in.kp0_out = kpts0_out; in.kp1_out = kpts1_out;
     return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, nullptr, workspace, workspace_bytes, stream);
 }
 
@@ -949,26 +959,12 @@ extern "C" int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int
                                                 const float* rec1, int64_t rows1, int normalize_fpfh, double* in4, double* in33, float* kpts0_out,
                                                 float* kpts1_out, unsigned* guard, void* stream) {
     const char* who = "mdgat_assemble_frames_f64_ragged";
-    if (!rec0 || !rec1 || !counts0 || !counts1 || !counts0_host || !counts1_host || !starts0 || !starts1 || !starts0_host || !starts1_host || !in4 || !in33) {
-        mdgat_set_error("%s: null pointer", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
+    if (!rec0 || !rec1 || !in4 || !in33) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
     if (B < 0 || Np <= 0 || Mp <= 0 || rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d", who, B, Np, Mp); return MDGAT_ERR_BAD_ARG; }
-    for (int b = 0; b < B; ++b) {
-        const int n = counts0_host[b], m = counts1_host[b];
-        if (n < 1 || n > Np || m < 1 || m > Mp) {
-            mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, n, m, Np, Mp);
-            return MDGAT_ERR_BAD_ARG;
-        }
-        const long long s0 = starts0_host[b], s1 = starts1_host[b];
-        if (s0 < 0 || s0 + n > rows0 || s1 < 0 || s1 + m > rows1) {
-            mdgat_set_error("%s: pair %d reads records %lld .. %lld of %lld and %lld .. %lld of %lld: outside the bank", who, b, s0, s0 + n,
-                            (long long)rows0, s1, s1 + m, (long long)rows1);
-            return MDGAT_ERR_BAD_ARG;
-        }
-    }
-    return launch_assemble_frames_ragged_f64(B, Np, Mp, rec0, rec1, reinterpret_cast<const long long*>(starts0), reinterpret_cast<const long long*>(starts1),
-                                             counts0, counts1, normalize_fpfh, in4, in33, kpts0_out, kpts1_out, guard, static_cast<hipStream_t>(stream));
+    const RaggedStarts bank = ragged_starts(starts0, starts1, starts0_host, starts1_host, rows0, rows1);
+    if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, &bank, nullptr, 0, nullptr)) return rc;
+    return launch_assemble_frames_ragged_f64(B, Np, Mp, rec0, rec1, bank.start0, bank.start1, counts0, counts1, normalize_fpfh, in4, in33, kpts0_out, kpts1_out,
+                                             guard, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,
@@ -1148,15 +1144,8 @@ extern "C" int mdgat_gt_matches_ragged(int B, int Np, int Mp, const int32_t* cou
                                        double threshold, int mutual, int64_t* gt0, int64_t* gt1, int64_t* rep, void* stream) {
     if (B < 0) { mdgat_set_error("mdgat_gt_matches_ragged: negative batch"); return MDGAT_ERR_BAD_ARG; }
     if (Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_gt_matches_ragged: empty frame"); return MDGAT_ERR_BAD_ARG; }
-    if (!kpts0 || !kpts1 || !gt0 || !gt1 || !rep || !counts0 || !counts1 || !counts0_host || !counts1_host) {
-        mdgat_set_error("mdgat_gt_matches_ragged: null pointer");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    for (int b = 0; b < B; ++b)
-        if (counts0_host[b] < 1 || counts0_host[b] > Np || counts1_host[b] < 1 || counts1_host[b] > Mp) {
-            mdgat_set_error("mdgat_gt_matches_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, counts0_host[b], counts1_host[b], Np, Mp);
-            return MDGAT_ERR_BAD_ARG;
-        }
+    if (!kpts0 || !kpts1 || !gt0 || !gt1 || !rep) { mdgat_set_error("mdgat_gt_matches_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = mdgat_check_ragged("mdgat_gt_matches_ragged", B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, nullptr, 0, nullptr)) return rc;
     return launch_gt_match(B, Np, Mp, kpts0, kpts1, T0, T1, threshold, mutual, gt0, gt1, rep, static_cast<hipStream_t>(stream), counts0, counts1);
 }
 
@@ -1179,15 +1168,10 @@ extern "C" int mdgat_eval_metrics_ragged(int B, int Np, int Mp, const int32_t* c
                                          double* metrics, double* T, unsigned* bad_index, void* stream) {
     if (B < 0) { mdgat_set_error("mdgat_eval_metrics_ragged: negative batch"); return MDGAT_ERR_BAD_ARG; }
     if (Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_eval_metrics_ragged: empty frame"); return MDGAT_ERR_BAD_ARG; }
-    if (B > 0 && (!matches0 || !matches1 || !gt0 || !gt1 || !kpts0 || !kpts1 || !metrics || !T || !counts0 || !counts1 || !counts0_host || !counts1_host)) {
-        mdgat_set_error("mdgat_eval_metrics_ragged: null pointer");
-        return MDGAT_ERR_BAD_ARG;
+    if (B > 0) {      // (an empty batch may come without pointers)
+        if (!matches0 || !matches1 || !gt0 || !gt1 || !kpts0 || !kpts1 || !metrics || !T) { mdgat_set_error("mdgat_eval_metrics_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
+        if (int rc = mdgat_check_ragged("mdgat_eval_metrics_ragged", B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, nullptr, 0, nullptr)) return rc;
     }
-    for (int b = 0; b < B; ++b)
-        if (counts0_host[b] < 1 || counts0_host[b] > Np || counts1_host[b] < 1 || counts1_host[b] > Mp) {
-            mdgat_set_error("mdgat_eval_metrics_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, counts0_host[b], counts1_host[b], Np, Mp);
-            return MDGAT_ERR_BAD_ARG;
-        }
     return launch_eval_metrics(B, Np, Mp, matches0, matches1, gt0, gt1, kpts0, kpts1, T_gt, inlier_dist, metrics, T, bad_index,
                                static_cast<hipStream_t>(stream), counts0, counts1);
 }
@@ -1320,22 +1304,10 @@ extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, con
 // a ragged batch: the counts on the device for the kernel, on the host for the checks made before the launch
 extern "C" int mdgat_attention_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                           const int32_t* counts1_host, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
-    if (!qkv || !msg || !counts0 || !counts1 || !counts0_host || !counts1_host) { mdgat_set_error("mdgat_attention_f64_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_attention_f64_ragged: bad shape B=%d Np=%d Mp=%d topk=%d", B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
-    int cmin = Np < Mp ? Np : Mp;
-    for (int b = 0; b < B; ++b) {
-        const int n = counts0_host[b], m = counts1_host[b];
-        if (n < 1 || n > Np || m < 1 || m > Mp) {
-            mdgat_set_error("mdgat_attention_f64_ragged: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", b, n, m, Np, Mp);
-            return MDGAT_ERR_BAD_ARG;
-        }
-        if (topk > (n < m ? n : m)) {      // torch.topk raises (mdgat.py:202)
-            mdgat_set_error("mdgat_attention_f64_ragged: pair %d: k=%d exceeds the number of keys (%d)", b, topk, n < m ? n : m);
-            return MDGAT_ERR_BAD_ARG;
-        }
-        cmin = n < cmin ? n : cmin;
-        cmin = m < cmin ? m : cmin;
-    }
+    int cmin = 0;
+    if (int rc = mdgat_check_ragged("mdgat_attention_f64_ragged", B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, &cmin)) return rc;
     return launch_attention_f64(B, Np, Mp, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream), nullptr, counts0, counts1, cmin);
 }
 

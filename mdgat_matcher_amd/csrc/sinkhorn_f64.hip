@@ -26,6 +26,7 @@
 #include "f64.hpp"
 #include "sinkhorn_f64.hpp"
 #include "coop_chain.hpp"
+#include "ragged.hpp"
 
 namespace {
 
@@ -839,19 +840,14 @@ extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* sco
 }
 
 // ---- ragged batches (include/mdgat_hip.h): pairs of different sizes in slots padded to Np x Mp ----
-// The counts come twice: on the device for the kernels, and on the host for the checks made before anything is launched.
+// The counts come twice: on the device for the kernels, and on the host for the checks made before anything is launched: these entries'
+// own limit on the slots, then the per-pair checks every ragged entry makes (ragged.hpp).
 static int s64_check_counts(const char* who, int B, int Np, int Mp, const int32_t* c0, const int32_t* c1, const int32_t* h0, const int32_t* h1) {
-    if (!c0 || !c1 || !h0 || !h1) { mdgat_set_error("%s: null counts pointer", who); return MDGAT_ERR_BAD_ARG; }
     if (!s64_resident_supported(Np, Mp) || Np > MDGAT_RAGGED_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_MAX_KEYPOINTS) {
         mdgat_set_error("%s: padded sizes %d x %d: ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_MAX_KEYPOINTS);
         return MDGAT_ERR_UNSUPPORTED;
     }
-    for (int b = 0; b < B; ++b)
-        if (h0[b] < 1 || h0[b] > Np || h1[b] < 1 || h1[b] > Mp) {
-            mdgat_set_error("%s: pair %d has %d x %d keypoints, outside 1 .. %d x 1 .. %d", who, b, h0[b], h1[b], Np, Mp);
-            return MDGAT_ERR_BAD_ARG;
-        }
-    return MDGAT_OK;
+    return mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{c0, c1, h0, h1}, nullptr, nullptr, 0, nullptr);
 }
 // The error word sits behind the uniform entries' workspace.  Reading it back is the one synchronisation of these entries: a launch
 // whose workgroups gave up waiting for each other returns an error, not numbers.

@@ -31,12 +31,13 @@ import ctypes as C
 import os
 import threading
 import weakref
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
 from torch import nn
 
-from . import _lib, pack
+from . import _lib, ops, pack
 
 _D = 128
 DESCRIPTORS = ('FPFH', 'FPFH_gloabal', 'FPFH_only')
@@ -139,6 +140,12 @@ def _close_states(states):
     for st in list(states.values()):
         st.close()
     states.clear()
+
+
+# What a ragged runner prepares for MDGAT._ragged_forward: the device, (B, Np, Mp), the host counts (h0, h1), the library's entry, its
+# arguments between the shape and the outputs (lead) and between Z and the workspace (behind_Z), and what the runner wants back - the
+# tensors those arguments point into among it.
+_RaggedCall = namedtuple('_RaggedCall', 'dev shape counts entry lead behind_Z kept')
 
 
 class MDGAT(nn.Module):
@@ -465,15 +472,8 @@ class MDGAT(nn.Module):
     def forward(self, data):
         kpts0, kpts1 = data['keypoints0'], data['keypoints1']
         out_dtype = self.bin_score.dtype
-        if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:      # mdgat.py:374-382
-            shape0, shape1 = kpts0.shape[:-1], kpts1.shape[:-1]
-            return {
-                'matches0': kpts0.new_full(shape0, -1, dtype=torch.int)[0],
-                'matches1': kpts1.new_full(shape1, -1, dtype=torch.int)[0],
-                'matching_scores0': kpts0.new_zeros(shape0, dtype=torch.float64)[0],
-                'matching_scores1': kpts1.new_zeros(shape1, dtype=torch.float64)[0],
-                'skip_train': True,
-            }
+        if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:
+            return self._early_out(kpts0, kpts1)
         if self.training and getattr(self, 'train_forward', False):
             return self.training_forward(data)
         if self.training:
@@ -510,9 +510,10 @@ class MDGAT(nn.Module):
 
     RAGGED_MAX_KEYPOINTS = 575      # what the register-resident fp64 Sinkhorn holds (csrc/sinkhorn_f64.hip)
 
-    def _ragged_early_out(self, pair):
-        """the dict of mdgat.py:374-382 for a pair with an empty frame, as ``forward`` returns it"""
-        k0, k1 = (pair[k] if pair[k].dim() == 3 else pair[k][None] for k in ('keypoints0', 'keypoints1'))
+    @staticmethod
+    def _early_out(kpts0, kpts1):
+        """the dict of mdgat.py:374-382 for a batch (or, without the batch axis, a pair) with an empty frame"""
+        k0, k1 = (k if k.dim() == 3 else k[None] for k in (kpts0, kpts1))
         shape0, shape1 = k0.shape[:-1], k1.shape[:-1]
         return {
             'matches0': k0.new_full(shape0, -1, dtype=torch.int)[0],
@@ -557,85 +558,80 @@ class MDGAT(nn.Module):
         if Np > self.RAGGED_MAX_KEYPOINTS or Mp > self.RAGGED_MAX_KEYPOINTS:
             raise ValueError(f'slots of {Np} x {Mp} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
 
-    def _run_ragged(self, packed, return_Z):
+    def _ragged_forward(self, inputs, return_Z):
         """One ragged forward through the library: the PADDED device outputs (matches -1 and scores 0 beyond a pair's counts), the host
-        counts and - in the dustbin modes, with the call's one synchronisation - which pairs matched anything (mdgat.py:465, per pair)."""
-        from . import ops
+        counts and - in the dustbin modes, with the call's one synchronisation - which pairs matched anything (mdgat.py:465, per pair).
+        ``inputs()`` is the runner's own preparation, made behind the mode refusals: a ``_RaggedCall``.  Returns (the outputs' tuple, the
+        call's ``kept``)."""
         if not self.exact() or self.bin_score.dtype != torch.float64:
             raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'")
         if self.training or getattr(self, 'eval_loss', False):
             raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)')
-        B, Np, Mp = self._ragged_checked(packed)
-        probe = packed['keypoints0']
-        if not probe.is_cuda:
-            raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP device; there is no CPU fallback')
-        dev = probe.device
+        call = inputs()
+        dev, shape = call.dev, call.shape
         st = self._state_for(dev)
-        ins = [packed[k].to(device=dev, dtype=torch.float64).contiguous()
-               for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
-        if self.descriptor == 'FPFH_only':          # keypoints and saliency give the shapes only (as in _run)
-            for i in (0, 1, 3, 4):
-                ins[i] = torch.zeros_like(ins[i])
-        d0, d1, h0, h1 = ops._ragged_counts(packed, B, dev)
         lib = _lib.load()
         with torch.cuda.device(dev), st.lock:
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, B, Np, Mp), dev)
-            m0 = torch.empty((B, Np), dtype=torch.int64, device=dev)
-            m1 = torch.empty((B, Mp), dtype=torch.int64, device=dev)
-            s0 = torch.empty((B, Np), dtype=torch.float32, device=dev)
-            s1 = torch.empty((B, Mp), dtype=torch.float32, device=dev)
-            Z = torch.empty((B, Np + 1, Mp + 1), dtype=torch.float32, device=dev) if return_Z else None
-            _lib.check(lib.mdgat_forward_f64_ragged(st.handle, B, Np, Mp, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(),
-                                                    *[t.data_ptr() for t in ins], m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(),
-                                                    Z.data_ptr() if Z is not None else None, None, ws.data_ptr(), ws.numel(), stream),
-                       'mdgat_forward_f64_ragged')
+            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, *shape), dev)
+            m0, m1, s0, s1, Z = ops._match_outputs(*shape, dev, return_Z)
+            _lib.check(getattr(lib, call.entry)(st.handle, *shape, *call.lead, m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(),
+                                                Z.data_ptr() if Z is not None else None, *call.behind_Z, ws.data_ptr(), ws.numel(), stream),
+                       call.entry)
         dustbin = self.loss_method != 'superglue'
         # the one synchronisation: which pairs matched nothing comes to the host with it
         matched = (m0 >= 0).any(dim=1).cpu() if dustbin else None
         self.check(dev, synchronize=not dustbin)
-        return m0, m1, s0, s1, Z, h0, h1, matched
+        return (m0, m1, s0, s1, Z, *call.counts, matched), call.kept
+
+    def _run_ragged(self, packed, return_Z):
+        """``_ragged_forward`` on a packed batch (``ops.pack_ragged``): its outputs' tuple."""
+        def inputs():
+            B, Np, Mp = self._ragged_checked(packed)
+            probe = packed['keypoints0']
+            if not probe.is_cuda:
+                raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP device; there is no CPU fallback')
+            dev = probe.device
+            ins = [packed[k].to(device=dev, dtype=torch.float64).contiguous()
+                   for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
+            if self.descriptor == 'FPFH_only':          # keypoints and saliency give the shapes only (as in _run)
+                for i in (0, 1, 3, 4):
+                    ins[i] = torch.zeros_like(ins[i])
+            cnt = ops._ragged_counts(packed, B, dev)
+            return _RaggedCall(dev, (B, Np, Mp), (cnt.h0, cnt.h1), 'mdgat_forward_f64_ragged', (*cnt.ptrs(), *[t.data_ptr() for t in ins]),
+                               behind_Z=(None,), kept=(cnt, ins))        # (behind Z: no taps)
+        return self._ragged_forward(inputs, return_Z)[0]
 
     def _run_frames_ragged(self, bank, counts, starts, normalize, return_Z, want_kpts=False):
-        """``_run_ragged`` fed from a bank of records (``ops.pack_frames``): the chunk's host counts and starts (``ops.frames_chunk``, no
-        empty frame among them) -> ``_run_ragged``'s tuple and, with ``want_kpts``, the padded float32 keypoints the assemble kernel wrote."""
-        from . import ops
-        if not self.exact() or self.bin_score.dtype != torch.float64:
-            raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'")
-        if self.training or getattr(self, 'eval_loss', False):
-            raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)')
-        h0, h1 = counts
-        B, Np, Mp = int(h0.numel()), int(h0.max()), int(h1.max())
-        self._ragged_counts_checked(h0, h1, Np, Mp)
-        rec = bank['records']
-        if not rec.is_cuda:
-            raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: the bank must be on a CUDA/HIP device; there is no CPU fallback')
-        dev = rec.device
-        st = self._state_for(dev)
-        if self.descriptor == 'FPFH_only':          # keypoints and saliency are not read (as in _run): a copy of the bank without them
-            rec = rec.clone()
-            rec[:, :4] = 0
-        args, dc, ds = ops._frames_args(bank, counts, starts, records=rec)
-        lib = _lib.load()
-        with torch.cuda.device(dev), st.lock:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = st.workspace_for(stream, lib.mdgat_workspace_bytes(st.handle, B, Np, Mp), dev)
-            m0 = torch.empty((B, Np), dtype=torch.int64, device=dev)
-            m1 = torch.empty((B, Mp), dtype=torch.int64, device=dev)
-            s0 = torch.empty((B, Np), dtype=torch.float32, device=dev)
-            s1 = torch.empty((B, Mp), dtype=torch.float32, device=dev)
-            Z = torch.empty((B, Np + 1, Mp + 1), dtype=torch.float32, device=dev) if return_Z else None
-            kp0 = torch.empty((B, Np, 3), dtype=torch.float32, device=dev) if want_kpts else None
-            kp1 = torch.empty((B, Mp, 3), dtype=torch.float32, device=dev) if want_kpts else None
-            _lib.check(lib.mdgat_forward_frames_ragged(st.handle, B, Np, Mp, *args, int(bool(normalize)), m0.data_ptr(), m1.data_ptr(), s0.data_ptr(),
-                                                       s1.data_ptr(), Z.data_ptr() if Z is not None else None,
-                                                       kp0.data_ptr() if want_kpts else None, kp1.data_ptr() if want_kpts else None,
-                                                       ws.data_ptr(), ws.numel(), stream), 'mdgat_forward_frames_ragged')
-        dustbin = self.loss_method != 'superglue'
-        # the one synchronisation: which pairs matched nothing comes to the host with it
-        matched = (m0 >= 0).any(dim=1).cpu() if dustbin else None
-        self.check(dev, synchronize=not dustbin)
-        return (m0, m1, s0, s1, Z, h0, h1, matched), kp0, kp1, dc
+        """``_ragged_forward`` fed from a bank of records (``ops.pack_frames``): the chunk's host counts and starts (``ops.frames_chunk``, no
+        empty frame among them) -> its outputs' tuple and, with ``want_kpts``, the padded float32 keypoints the assemble kernel wrote."""
+        def inputs():
+            h0, h1 = counts
+            B, Np, Mp = int(h0.numel()), int(h0.max()), int(h1.max())
+            self._ragged_counts_checked(h0, h1, Np, Mp)
+            rec = bank['records']
+            if not rec.is_cuda:
+                raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: the bank must be on a CUDA/HIP device; there is no CPU fallback')
+            dev = rec.device
+            if self.descriptor == 'FPFH_only':          # keypoints and saliency are not read (as in _run): a copy of the bank without them
+                rec = rec.clone()
+                rec[:, :4] = 0
+            args, dc, ds = ops._frames_args(bank, counts, starts, records=rec)
+            kp0, kp1 = (torch.empty((B, P, 3), dtype=torch.float32, device=dev) if want_kpts else None for P in (Np, Mp))
+            return _RaggedCall(dev, (B, Np, Mp), counts, 'mdgat_forward_frames_ragged', (*args, int(bool(normalize))),
+                               behind_Z=(kp0.data_ptr() if want_kpts else None, kp1.data_ptr() if want_kpts else None), kept=(kp0, kp1, dc, ds, rec))
+        padded, (kp0, kp1, dc, _, _) = self._ragged_forward(inputs, return_Z)
+        return padded, kp0, kp1, dc
+
+    def _ragged_scatter(self, empty, early_out, run, return_Z):
+        """The per-pair dicts of a chunk some of whose pairs have an empty frame (``empty[b]``): those get ``early_out(b)`` and are set aside,
+        the others run in their order as one batch (``run(order)`` -> ``_ragged_forward``'s outputs) and every dict lands at its pair's place."""
+        results = [early_out(b) if e else None for b, e in enumerate(empty)]
+        order = [b for b, e in enumerate(empty) if not e]
+        if order:
+            for b, d in zip(order, self._ragged_dicts(run(order), return_Z)):
+                results[b] = d
+        return results
 
     @torch.no_grad()
     def match_frames_ragged(self, bank, idx0, idx1, normalize=True, return_Z=False):
@@ -651,19 +647,14 @@ class MDGAT(nn.Module):
         ``ValueError`` for index vectors of different length, ``IndexError`` for an index outside the bank (both before anything touches
         a device); then ``forward_ragged``'s refusals: the exact mode only, at most 575 keypoints per frame, no fewer than a dynamic
         layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``."""
-        from . import ops
         (h0, h1), (a0, a1) = ops.frames_chunk(bank, idx0, idx1)
         rec = bank['records']
         empty = ((h0 == 0) | (h1 == 0)).tolist()
         zeros = lambda n: rec.new_zeros((1, int(n), 3), dtype=torch.float64)      # noqa: E731
-        results = [self._ragged_early_out({'keypoints0': zeros(h0[b]), 'keypoints1': zeros(h1[b])}) if e else None for b, e in enumerate(empty)]
-        order = [b for b, e in enumerate(empty) if not e]
-        if order:
-            padded = self._run_frames_ragged(bank, (h0[order].contiguous(), h1[order].contiguous()), (a0[order].contiguous(), a1[order].contiguous()),
-                                             normalize, return_Z)[0]
-            for b, d in zip(order, self._ragged_dicts(padded, return_Z)):
-                results[b] = d
-        return results
+        take = lambda t, order: t[order].contiguous()     # noqa: E731
+        return self._ragged_scatter(empty, lambda b: self._early_out(zeros(h0[b]), zeros(h1[b])),
+                                    lambda order: self._run_frames_ragged(bank, (take(h0, order), take(h1, order)), (take(a0, order), take(a1, order)),
+                                                                          normalize, return_Z)[0], return_Z)
 
     @torch.no_grad()
     def evaluate_frames_ragged(self, bank, idx0, idx1, T0, T1, T_gt=None, gt_threshold=0.5, gt_mutual=False, normalize=True):
@@ -676,7 +667,6 @@ class MDGAT(nn.Module):
         [B, Mp] (int64, -1 beyond a pair's counts), 'rep': [B]}``, which ``ops.EvalMeter.update`` takes.  The forward's one
         synchronisation, and ``evaluate_matches``' read of its bad-index word, as in ``evaluate_ragged``.  A pair with an empty frame
         has nothing to evaluate: ``ValueError``."""
-        from . import ops
         counts, starts = ops.frames_chunk(bank, idx0, idx1)
         h0, h1 = counts
         if int(h0.numel()) == 0 or int(h0.min()) < 1 or int(h1.min()) < 1:
@@ -722,18 +712,13 @@ class MDGAT(nn.Module):
         The exact mode only (a float64 module in eval() mode, no ``eval_loss``): ``NotImplementedError`` otherwise.  ``ValueError`` for a
         frame of more than 575 keypoints or of fewer than a dynamic layer's k, and for tensors that are not [B, N, 3] / [B, N] /
         [B, N, 33] with one B and count vectors of B entries."""
-        from . import ops
         if isinstance(pairs_or_packed, dict):
             return self._ragged_dicts(self._run_ragged(pairs_or_packed, return_Z), return_Z)
         pairs = list(pairs_or_packed)
         empty = [p['keypoints0'].shape[-2] == 0 or p['keypoints1'].shape[-2] == 0 for p in pairs]
-        results = [self._ragged_early_out(p) if e else None for p, e in zip(pairs, empty)]
-        order = [i for i, e in enumerate(empty) if not e]
-        if order:
-            packed = ops.pack_ragged([pairs[i] for i in order], device=self.bin_score.device)
-            for i, d in zip(order, self._ragged_dicts(self._run_ragged(packed, return_Z), return_Z)):
-                results[i] = d
-        return results
+        return self._ragged_scatter(empty, lambda b: self._early_out(pairs[b]['keypoints0'], pairs[b]['keypoints1']),
+                                    lambda order: self._run_ragged(ops.pack_ragged([pairs[i] for i in order], device=self.bin_score.device), return_Z),
+                                    return_Z)
 
     @torch.no_grad()
     def evaluate_ragged(self, pairs_or_packed):
@@ -743,7 +728,6 @@ class MDGAT(nn.Module):
         ``evaluate``'s on each pair alone - so the scripts' loop over a chunk of pairs becomes
         ``meter.update(net.evaluate_ragged(chunk))``.  Pairs with an empty frame have nothing to evaluate (``evaluate`` returns None for
         them): ``ValueError``."""
-        from . import ops
         packed = pairs_or_packed if isinstance(pairs_or_packed, dict) else None
         if packed is None:
             pairs = list(pairs_or_packed)
@@ -784,7 +768,6 @@ class MDGAT(nn.Module):
         the forward's own device outputs against ``data['gt_matches0/1']`` and ``data['T_gt']`` (optional): the forward's dict plus
         ``'metrics'`` [B, len(ops.EvalColumns)] float64 and ``'T'`` [B, 4, 4], the pose from the matches.  The scripts' loop body
         becomes ``meter.update(net.evaluate(pred))`` with an ``ops.EvalMeter``.  ``forward`` itself is unchanged."""
-        from . import ops
         out = self.forward(data)
         if out.get('skip_train'):                 # an empty frame: nothing to evaluate (mdgat.py:374-382)
             return {**out, 'metrics': None, 'T': None}
@@ -909,11 +892,7 @@ class MDGAT(nn.Module):
             stream = torch.cuda.current_stream(dev).cuda_stream
             need = lib.mdgat_forward_loss_workspace_bytes(st.handle, B, N, M) if loss is not None else lib.mdgat_workspace_bytes(st.handle, B, N, M)
             ws = st.workspace_for(stream, need, dev)
-            m0 = torch.empty((B, N), dtype=torch.int64, device=dev)
-            m1 = torch.empty((B, M), dtype=torch.int64, device=dev)
-            s0 = torch.empty((B, N), dtype=torch.float32, device=dev)
-            s1 = torch.empty((B, M), dtype=torch.float32, device=dev)
-            Z = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=dev) if want_Z else None
+            m0, m1, s0, s1, Z = ops._match_outputs(B, N, M, dev, want_Z)
             tap_struct = None
             if taps is not None:
                 tap_struct = _lib.MdgatTaps()

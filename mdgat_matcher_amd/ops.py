@@ -5,6 +5,7 @@ callers that want a single stage (e.g. Sinkhorn on their own score matrix)."""
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -19,6 +20,19 @@ def _need_cuda(*ts):
     for t in ts:
         if not t.is_cuda:
             raise RuntimeError('mdgat_matcher_amd ops run on MI355X only (no CPU fallback)')
+
+
+def _workspace(need, device):
+    """Scratch memory for one call of the library: (the buffer that owns it, its first 256-byte aligned address, ``need``)."""
+    buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return buf, buf.data_ptr() + (-buf.data_ptr()) % 256, need
+
+
+def _match_outputs(B, N, M, device, want_Z=False):
+    """What a matching call fills: (matches0 [B, N], matches1 [B, M] int64, mscores0, mscores1 float32, Z [B, N+1, M+1] float32 or None)."""
+    return (torch.empty((B, N), dtype=torch.int64, device=device), torch.empty((B, M), dtype=torch.int64, device=device),
+            torch.empty((B, N), dtype=torch.float32, device=device), torch.empty((B, M), dtype=torch.float32, device=device),
+            torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=device) if want_Z else None)
 
 
 def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool = False) -> torch.Tensor:
@@ -47,11 +61,7 @@ def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: i
     _need_cuda(scores)
     s = scores.to(torch.float32).contiguous()
     B, N, M = s.shape
-    m0 = torch.empty((B, N), dtype=torch.int64, device=s.device)
-    m1 = torch.empty((B, M), dtype=torch.int64, device=s.device)
-    s0 = torch.empty((B, N), dtype=torch.float32, device=s.device)
-    s1 = torch.empty((B, M), dtype=torch.float32, device=s.device)
-    Zbuf = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=s.device)     # Z, or the buffer lent for redone pairs
+    m0, m1, s0, s1, Zbuf = _match_outputs(B, N, M, s.device, want_Z=True)     # (Z, or the buffer lent for redone pairs)
     lib = _lib.load()
     with torch.cuda.device(s.device):
         need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
@@ -121,7 +131,16 @@ def pack_ragged(pairs, device=None) -> dict:
     return out
 
 
-def _ragged_counts(counts, B, device):
+class _Counts(namedtuple('_Counts', 'd0 d1 h0 h1')):
+    """The counts of a ragged batch as the library takes them: int32 [B] on the device (d0, d1) and the same values on the host (h0, h1)."""
+    __slots__ = ()
+
+    def ptrs(self):
+        """the four leading pointers of every ``*_ragged`` entry, in the ABI's order"""
+        return self.d0.data_ptr(), self.d1.data_ptr(), self.h0.data_ptr(), self.h1.data_ptr()
+
+
+def _ragged_counts(counts, B, device) -> _Counts:
     """counts: a pack_ragged dict, or (counts0, counts1) as tensors or sequences -> device and host int32 copies of both."""
     if isinstance(counts, dict):
         h0, h1 = counts['counts0_host'], counts['counts1_host']
@@ -134,7 +153,16 @@ def _ragged_counts(counts, B, device):
         d0, d1 = counts['counts0'].contiguous(), counts['counts1'].contiguous()
     else:
         d0, d1 = h0.to(device), h1.to(device)
-    return d0, d1, h0, h1
+    return _Counts(d0, d1, h0, h1)
+
+
+def _entry(name, counts, B, device):
+    """The entry that runs a batch: ``name`` for a uniform one (``counts`` None), ``name_ragged`` fed the count vectors for a ragged one.
+    Returns (the entry's name, its leading arguments behind B, N, M, the tensors those point into - to be kept until the call is made)."""
+    if counts is None:
+        return name, (), None
+    cnt = _ragged_counts(counts, B, device)
+    return name + '_ragged', cnt.ptrs(), cnt
 
 
 def pack_frames(frames, device) -> dict:
@@ -184,9 +212,8 @@ def _frames_args(bank, counts, starts, records=None):
     dev = rec.device
     dc = torch.stack(list(counts)).to(dev)
     ds = torch.stack(list(starts)).to(dev)
-    h0, h1 = counts
     s0, s1 = starts
-    args = (dc[0].data_ptr(), dc[1].data_ptr(), h0.data_ptr(), h1.data_ptr(), ds[0].data_ptr(), ds[1].data_ptr(), s0.data_ptr(), s1.data_ptr(),
+    args = (*_Counts(dc[0], dc[1], *counts).ptrs(), ds[0].data_ptr(), ds[1].data_ptr(), s0.data_ptr(), s1.data_ptr(),
             rec.data_ptr(), int(rec.shape[0]), rec.data_ptr(), int(rec.shape[0]))
     return args, dc, ds
 
@@ -235,19 +262,10 @@ def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None
     Z = torch.empty((B, N + 1, M + 1), dtype=torch.float64, device=s.device)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        if counts is not None:
-            d0, d1, h0, h1 = _ragged_counts(counts, B, s.device)
-            need = lib.mdgat_sinkhorn_f64_ragged_workspace_bytes(B, N, M)
-            ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
-            off = (-ws.data_ptr()) % 256
-            _lib.check(lib.mdgat_sinkhorn_f64_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), s.data_ptr(), float(bin_score),
-                                                     int(iters), Z.data_ptr(), ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_f64_ragged')
-            return Z
-        need = lib.mdgat_sinkhorn_f64_workspace_bytes(B, N, M)
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
-        off = (-ws.data_ptr()) % 256
-        _lib.check(lib.mdgat_sinkhorn_f64(B, N, M, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), ws.data_ptr() + off, need, _stream(s)),
-                   'mdgat_sinkhorn_f64')
+        name, lead, _keep = _entry('mdgat_sinkhorn_f64', counts, B, s.device)
+        size = lib.mdgat_sinkhorn_f64_workspace_bytes if counts is None else lib.mdgat_sinkhorn_f64_ragged_workspace_bytes
+        ws, base, need = _workspace(size(B, N, M), s.device)
+        _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), base, need, _stream(s)), name)
     return Z
 
 
@@ -262,29 +280,14 @@ def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mod
         raise RuntimeError('sinkhorn_f64_extract(counts=): ragged batches run the forward only (no gradient)')
     s = scores.to(torch.float64).contiguous()
     B, N, M = s.shape
-    m0 = torch.empty((B, N), dtype=torch.int64, device=s.device)
-    m1 = torch.empty((B, M), dtype=torch.int64, device=s.device)
-    s0 = torch.empty((B, N), dtype=torch.float32, device=s.device)
-    s1 = torch.empty((B, M), dtype=torch.float32, device=s.device)
-    Z = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=s.device) if want_Z else None
+    m0, m1, s0, s1, Z = _match_outputs(B, N, M, s.device, want_Z)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        if counts is not None:
-            d0, d1, h0, h1 = _ragged_counts(counts, B, s.device)
-            need = lib.mdgat_sinkhorn_f64_ragged_workspace_bytes(B, N, M)
-            ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
-            off = (-ws.data_ptr()) % 256
-            _lib.check(lib.mdgat_sinkhorn_f64_extract_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), s.data_ptr(),
-                                                             float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
-                                                             m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None,
-                                                             ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_f64_extract_ragged')
-            return (m0, m1, s0, s1, Z) if want_Z else (m0, m1, s0, s1)
-        need = lib.mdgat_sinkhorn_f64_workspace_bytes(B, N, M)
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
-        off = (-ws.data_ptr()) % 256
-        _lib.check(lib.mdgat_sinkhorn_f64_extract(B, N, M, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
-                                                  m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None,
-                                                  ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_f64_extract')
+        name, lead, _keep = _entry('mdgat_sinkhorn_f64_extract', counts, B, s.device)
+        size = lib.mdgat_sinkhorn_f64_workspace_bytes if counts is None else lib.mdgat_sinkhorn_f64_ragged_workspace_bytes
+        ws, base, need = _workspace(size(B, N, M), s.device)
+        _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
+                                      m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None, base, need, _stream(s)), name)
     return (m0, m1, s0, s1, Z) if want_Z else (m0, m1, s0, s1)
 
 
@@ -306,11 +309,9 @@ def sinkhorn_backward(scores: torch.Tensor, bin_score, iters: int, dZ: torch.Ten
     dbin = torch.empty((B,), dtype=torch.float64, device=s.device)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        need = lib.mdgat_sinkhorn_backward_workspace_bytes(B, N, M, int(iters))
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=s.device)
-        off = (-ws.data_ptr()) % 256
+        ws, base, need = _workspace(lib.mdgat_sinkhorn_backward_workspace_bytes(B, N, M, int(iters)), s.device)
         _lib.check(lib.mdgat_sinkhorn_backward(B, N, M, s.data_ptr(), float(bin_score), int(iters), g.data_ptr(), dscores.data_ptr(),
-                                               dbin.data_ptr(), ws.data_ptr() + off, need, _stream(s)), 'mdgat_sinkhorn_backward')
+                                               dbin.data_ptr(), base, need, _stream(s)), 'mdgat_sinkhorn_backward')
     return dscores.to(scores.dtype), dbin
 
 
@@ -536,12 +537,8 @@ def gt_matches(kpts0: torch.Tensor, kpts1: torch.Tensor, T0=None, T1=None, thres
     tail = (t0.data_ptr() if t0 is not None else None, t1.data_ptr() if t1 is not None else None, float(threshold), int(bool(mutual)),
             g0.data_ptr(), g1.data_ptr(), rep.data_ptr(), _stream(k0))
     with torch.cuda.device(k0.device):
-        if counts is not None:
-            d0, d1, h0, h1 = _ragged_counts(counts, B, k0.device)
-            _lib.check(_lib.load().mdgat_gt_matches_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), k0.data_ptr(),
-                                                           k1.data_ptr(), *tail), 'mdgat_gt_matches_ragged')
-        else:
-            _lib.check(_lib.load().mdgat_gt_matches(B, N, M, k0.data_ptr(), k1.data_ptr(), *tail), 'mdgat_gt_matches')
+        name, lead, _keep = _entry('mdgat_gt_matches', counts, B, k0.device)
+        _lib.check(getattr(_lib.load(), name)(B, N, M, *lead, k0.data_ptr(), k1.data_ptr(), *tail), name)
     return g0, g1, rep
 
 
@@ -593,16 +590,10 @@ def evaluate_matches(matches0: torch.Tensor, matches1: torch.Tensor, gt0: torch.
     T = torch.empty((B, 4, 4), dtype=torch.float64, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        if counts is not None:
-            d0, d1, h0, h1 = _ragged_counts(counts, B, dev)
-            _lib.check(_lib.load().mdgat_eval_metrics_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), m0.data_ptr(),
-                                                             m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(), k1.data_ptr(),
-                                                             g.data_ptr() if g is not None else None, float(inlier_dist), metrics.data_ptr(),
-                                                             T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics_ragged')
-        else:
-            _lib.check(_lib.load().mdgat_eval_metrics(B, N, M, m0.data_ptr(), m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(),
-                                                      k1.data_ptr(), g.data_ptr() if g is not None else None, float(inlier_dist),
-                                                      metrics.data_ptr(), T.data_ptr(), bad.data_ptr(), _stream(k0)), 'mdgat_eval_metrics')
+        name, lead, _keep = _entry('mdgat_eval_metrics', counts, B, dev)
+        _lib.check(getattr(_lib.load(), name)(B, N, M, *lead, m0.data_ptr(), m1.data_ptr(), g0.data_ptr(), g1.data_ptr(), k0.data_ptr(), k1.data_ptr(),
+                                              g.data_ptr() if g is not None else None, float(inlier_dist), metrics.data_ptr(), T.data_ptr(),
+                                              bad.data_ptr(), _stream(k0)), name)
     if int(bad.item()):
         raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1), or the matches one outside '
                          f'[-1, {M}) / [-1, {N})')
@@ -740,14 +731,9 @@ def _attention_f64_values(qkv, N, M, cross, topk, want_sel, counts=None):
     msg = torch.empty((B, P, 128), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
         sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if want_sel else None
-        if counts is not None:
-            d0, d1, h0, h1 = _ragged_counts(counts, B, x.device)
-            _lib.check(_lib.load().mdgat_attention_f64_ragged(B, N, M, d0.data_ptr(), d1.data_ptr(), h0.data_ptr(), h1.data_ptr(), int(bool(cross)),
-                                                              int(topk), x.data_ptr(), msg.data_ptr(), sel.data_ptr() if sel is not None else None,
-                                                              _stream(x)), 'mdgat_attention_f64_ragged')
-            return msg, sel
-        _lib.check(_lib.load().mdgat_attention_f64(B, N, M, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
-                                                   sel.data_ptr() if sel is not None else None, _stream(x)), 'mdgat_attention_f64')
+        name, lead, _keep = _entry('mdgat_attention_f64', counts, B, x.device)
+        _lib.check(getattr(_lib.load(), name)(B, N, M, *lead, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
+                                              sel.data_ptr() if sel is not None else None, _stream(x)), name)
     return msg, sel
 
 
@@ -779,11 +765,9 @@ def attention_f64_backward(qkv: torch.Tensor, N: int, M: int, cross: bool, dmsg:
     dqkv = torch.empty_like(x)
     lib = _lib.load()
     with torch.cuda.device(x.device):
-        need = lib.mdgat_attention_backward_workspace_bytes(B, N, M)
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=x.device)
-        off = (-ws.data_ptr()) % 256
+        ws, base, need = _workspace(lib.mdgat_attention_backward_workspace_bytes(B, N, M), x.device)
         _lib.check(lib.mdgat_attention_backward_f64(B, N, M, int(bool(cross)), topk, x.data_ptr(), sel.data_ptr() if sel is not None else None,
-                                                    g.data_ptr(), dqkv.data_ptr(), ws.data_ptr() + off, need, _stream(x)),
+                                                    g.data_ptr(), dqkv.data_ptr(), base, need, _stream(x)),
                    'mdgat_attention_backward_f64')
     return dqkv
 
@@ -872,12 +856,10 @@ def _matching_loss_values(Z, gt0, gt1, method, gamma):
     bad = torch.zeros(1, dtype=torch.int32, device=z.device)
     lib = _lib.load()
     with torch.cuda.device(z.device):
-        need = lib.mdgat_loss_workspace_bytes(B, N, M)
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=z.device)
-        off = (-ws.data_ptr()) % 256
+        ws, base, need = _workspace(lib.mdgat_loss_workspace_bytes(B, N, M), z.device)
         fn = lib.mdgat_loss_f64 if f64 else lib.mdgat_loss
         _lib.check(fn(B, N, M, z.data_ptr(), g0.data_ptr(), g1.data_ptr(), m, float(gamma), loss.data_ptr(), bad.data_ptr(),
-                      ws.data_ptr() + off, need, _stream(z)), 'mdgat_loss_f64' if f64 else 'mdgat_loss')
+                      base, need, _stream(z)), 'mdgat_loss_f64' if f64 else 'mdgat_loss')
     if int(bad.item()):
         raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1)')
     return loss
@@ -901,12 +883,10 @@ def matching_loss_backward(Z: torch.Tensor, gt0: torch.Tensor, gt1: torch.Tensor
     bad = torch.zeros(1, dtype=torch.int32, device=z.device)
     lib = _lib.load()
     with torch.cuda.device(z.device):
-        need = lib.mdgat_loss_backward_workspace_bytes(B, N, M)
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=z.device)
-        off = (-ws.data_ptr()) % 256
+        ws, base, need = _workspace(lib.mdgat_loss_backward_workspace_bytes(B, N, M), z.device)
         fn = lib.mdgat_loss_backward_f64 if f64 else lib.mdgat_loss_backward
         _lib.check(fn(B, N, M, z.data_ptr(), g0.data_ptr(), g1.data_ptr(), m, float(gamma), g.data_ptr(), dZ.data_ptr(), bad.data_ptr(),
-                      ws.data_ptr() + off, need, _stream(z)), 'mdgat_loss_backward_f64' if f64 else 'mdgat_loss_backward')
+                      base, need, _stream(z)), 'mdgat_loss_backward_f64' if f64 else 'mdgat_loss_backward')
     if int(bad.item()):
         raise IndexError(f'gt_matches hold an index outside [-1, {M}] (gt0) or [-1, {N}] (gt1)')
     return dZ.to(Z.dtype)
@@ -962,9 +942,7 @@ def _head_args(desc0, desc1, weight, bias):
 
 
 def _head_workspace(lib, B, N, M, device):
-    need = lib.mdgat_match_head_workspace_bytes(B, N, M)
-    ws = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, need
+    return _workspace(lib.mdgat_match_head_workspace_bytes(B, N, M), device)
 
 
 def _match_head_values(desc0, desc1, weight, bias):
@@ -1127,9 +1105,7 @@ def _mlp_desc(rows, k0, k1, training, ws, bs, gammas, betas, bufs, eps, momentum
 
 
 def _mlp_buffer(lib, desc, part, device):
-    need = lib.mdgat_mlp_workspace_bytes(C.byref(desc), part)
-    buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    return buf, buf.data_ptr() + (-buf.data_ptr()) % 256, need
+    return _workspace(lib.mdgat_mlp_workspace_bytes(C.byref(desc), part), device)
 
 
 def _mlp_split(seq):
