@@ -262,6 +262,31 @@ int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int32_t* count
                                      int normalize_fpfh, double* in4, double* in33, float* kpts0_out, float* kpts1_out, unsigned* guard,
                                      void* stream);
 
+/* The loader's TRAIN-mode assembly of a chunk out of the same bank (SparseDataset.__getitem__ with ensure_kpts_num, train.py's default for
+ * the training and the validation set; load_data.py:180-211), one launch, no handle.  Frame f of pair b is the counts[b] records from
+ * row starts[b], as above, of any size >= 1.  Per frame:
+ *   - the records with saliency > min_saliency (a float32 compare; 10 in the reference: a saliency of exactly min_saliency and a NaN
+ *     saliency are dropped) are kept in their order, v of them;
+ *   - v >= T: the first T kept records; else the loader's loop `a = vstack((a[:T - len(a)], a))` until T rows stand, so with v = 3 and
+ *     T = 8 the slots hold kept rows 0 1 0 1 2 0 1 2;
+ *   - every slot is decoded like a record of mdgat_assemble_frames_f64_ragged (normalize_fpfh: the loader's float32 arithmetic bit for
+ *     bit) into in4 [B][T+T][4] and in33 [B][T+T][33] fp64 (rows of a pair: frame 0's T, then frame 1's T) and kpts0_out / kpts1_out
+ *     [B][T][3] fp32 (what mdgat_gt_matches takes); source0 / source1 [B][T]: the record's row within its frame behind each slot;
+ *     salient0 / salient1 [B]: v.
+ *   - v == 0: the reference's loop never ends.  status [B][2] (pair, frame) is written for every frame: 1 there, else 0; of such a
+ *     frame's outputs only salient (0) is written.
+ * Only kept records are decoded: a non-finite word or (normalize_fpfh) an all-zero FPFH row among them sets guard (device memory,
+ * optional; the caller clears it) to 1; what a dropped record holds beside its saliency, and what any record outside the chunk holds,
+ * is never read.  The outputs are a pure function of the inputs (no atomics on values).  T outside 1 .. 2048 (the attention's limit)
+ * and a NaN min_saliency are MDGAT_ERR_BAD_ARG; counts (>= 1, no upper limit) and starts are checked as described at THE COUNTS OF A
+ * RAGGED BATCH. */
+int mdgat_assemble_frames_train_f64(int B, int T, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                    const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1, const int64_t* starts0_host,
+                                    const int64_t* starts1_host, const float* rec0, int64_t rows0, const float* rec1, int64_t rows1,
+                                    float min_saliency, int normalize_fpfh, double* in4, double* in33, float* kpts0_out, float* kpts1_out,
+                                    int32_t* source0, int32_t* source1, int32_t* salient0, int32_t* salient1, unsigned* status, unsigned* guard,
+                                    void* stream);
+
 /* ---- evaluation loss (mdgat.py:486-594) and its gradient with respect to Z (mdgat_loss_backward below) ------------------------- */
 
 /* config['loss_method'] of the loss: superglue (487-511), triplet_loss (512-546), gap_loss (547-594) */

@@ -116,6 +116,8 @@ SIGNATURES = {
                                               C.c_int] + [C.c_void_p] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_assemble_frames_f64_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                    C.c_int] + [C.c_void_p] * 6),
+    'mdgat_assemble_frames_train_f64': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float,
+                                                  C.c_int] + [C.c_void_p] * 11),
     'mdgat_forward_frames': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 +
                              [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_forward_loss': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p] * 4 +

@@ -1,5 +1,6 @@
 // C ABI of libmdgat_hip.so (see include/mdgat_hip.h) and the launch sequence of one forward.
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -965,6 +966,28 @@ extern "C" int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int
     if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, &bank, nullptr, 0, nullptr)) return rc;
     return launch_assemble_frames_ragged_f64(B, Np, Mp, rec0, rec1, bank.start0, bank.start1, counts0, counts1, normalize_fpfh, in4, in33, kpts0_out, kpts1_out,
                                              guard, static_cast<hipStream_t>(stream));
+}
+
+// The loader's train-mode assembly of a chunk (ensure_kpts_num): the saliency filter and the pad / truncate to T in front of the same decode.
+// A frame may hold any number of records (>= 1), so the counts are checked against no slot size.
+extern "C" int mdgat_assemble_frames_train_f64(int B, int T, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                               const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
+                                               const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0,
+                                               const float* rec1, int64_t rows1, float min_saliency, int normalize_fpfh, double* in4, double* in33,
+                                               float* kpts0_out, float* kpts1_out, int32_t* source0, int32_t* source1, int32_t* salient0,
+                                               int32_t* salient1, unsigned* status, unsigned* guard, void* stream) {
+    const char* who = "mdgat_assemble_frames_train_f64";
+    if (!rec0 || !rec1 || !in4 || !in33 || !kpts0_out || !kpts1_out || !source0 || !source1 || !salient0 || !salient1 || !status) {
+        mdgat_set_error("%s: null pointer", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    if (B < 0 || T <= 0 || rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: bad shape B=%d T=%d", who, B, T); return MDGAT_ERR_BAD_ARG; }
+    if (T > 2048) { mdgat_set_error("%s: max_keypoints=%d: at most 2048 keypoints per frame (the attention's limit)", who, T); return MDGAT_ERR_BAD_ARG; }
+    if (min_saliency != min_saliency) { mdgat_set_error("%s: min_saliency is NaN", who); return MDGAT_ERR_BAD_ARG; }
+    const RaggedStarts bank = ragged_starts(starts0, starts1, starts0_host, starts1_host, rows0, rows1);
+    if (int rc = mdgat_check_ragged(who, B, INT32_MAX, INT32_MAX, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, &bank, nullptr, 0, nullptr)) return rc;
+    return launch_assemble_frames_train_f64(B, T, rec0, rec1, bank.start0, bank.start1, counts0, counts1, min_saliency, normalize_fpfh, in4, in33, kpts0_out,
+                                            kpts1_out, source0, source1, salient0, salient1, status, guard, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mdgat_forward_loss(mdgat_handle* h, int B, int N, int M, const float* kpts0, const float* sigma0,

@@ -776,6 +776,89 @@ __global__ __launch_bounds__(256) void assemble_frames_ragged_f64_kernel(const f
     }
 }
 
+// The loader's TRAIN-mode assembly (SparseDataset.__getitem__ with ensure_kpts_num, load_data.py:180-211) out of the same bank: one
+// workgroup per (pair, frame).  Of the frame's n records those with saliency > min_saliency are kept in their order (v of them); the
+// first T are taken when v >= T, else the loader's loop `a = vstack((a[:T - len(a)], a))` runs until T rows stand: step k puts the first
+// c_k = min(T - L_k, L_k) rows of the L_k there are in front of them.  Slot j's kept row comes from walking the steps backwards (j -= c_k
+// whenever j >= c_k: it lay behind what step k put in front); v = 3, T = 8 gives 0 1 0 1 2 0 1 2.  At most 11 steps for T <= 2048.
+// Every slot then goes through assemble_record_f64 like a record of the kernels above, so only KEPT records are decoded and guarded.
+// in4 / in33: pairs of T + T rows (frame 0's, then frame 1's); kp [B][T][3] float32; source [B][T]: the record row within its frame
+// behind each slot; salient [B]: v; status [B][2]: 1 where v == 0 - the loader's loop never ends there - and nothing but status and
+// salient is written for that frame.  A pure function of its inputs: plain stores, every output word written by one thread.
+#define TRAIN_MAX_KEYPOINTS 2048
+// float32 order as an unsigned order, by the bits (this file is compiled with -fno-honor-nans: see f64_bits_nonfinite); -0 == +0
+__device__ __forceinline__ unsigned f32_order_key(unsigned b) {
+    if ((b & 0x7fffffffu) == 0u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ bool f32_bits_nan(unsigned b) { return (b & 0x7fffffffu) > 0x7f800000u; }
+
+__global__ __launch_bounds__(256) void assemble_frames_train_f64_kernel(const float* rec0, const float* rec1, const long long* start0,
+                                                                         const long long* start1, const int* cnt0, const int* cnt1,
+                                                                         unsigned min_saliency_bits, int normalize, double* in4, double* in33,
+                                                                         float* kp0, float* kp1, int* source0, int* source1, int* salient0,
+                                                                         int* salient1, unsigned* status, int T, unsigned* guard) {
+    __shared__ int kept[TRAIN_MAX_KEYPOINTS];      // the record rows of the first min(v, T) kept records
+    __shared__ int wave_total[4];
+    __shared__ int c[12], steps;                   // the pad steps' row counts (11 at most: v = 1, T = 2048)
+    const int b = blockIdx.x >> 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool f1 = blockIdx.x & 1;
+    const int n = f1 ? cnt1[b] : cnt0[b];
+    const float* rec = f1 ? rec1 + (size_t)start1[b] * 37 : rec0 + (size_t)start0[b] * 37;
+    const unsigned thr = f32_order_key(min_saliency_bits);
+    int v = 0;                                     // kept so far (uniform)
+    for (int r0 = 0; r0 < n; r0 += 256) {
+        const int r = r0 + tid;
+        bool keep = false;
+        if (r < n) {
+            const unsigned s = reinterpret_cast<const unsigned*>(rec)[(size_t)r * 37 + 3];
+            keep = !f32_bits_nan(s) && f32_order_key(s) > thr;
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_total[wave] = __popcll(m);
+        __syncthreads();
+        int pos = v + __popcll(m & ((1ull << lane) - 1ull));
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int t = wave_total[w];
+            if (w < wave) pos += t;
+            total += t;
+        }
+        if (keep && pos < T) kept[pos] = r;
+        v += total;
+        __syncthreads();
+    }
+    int* salient = f1 ? salient1 : salient0;
+    if (tid == 0) {
+        salient[b] = v;
+        status[blockIdx.x] = v == 0 ? 1u : 0u;
+    }
+    if (v == 0) return;
+    if (tid == 0) {
+        int k = 0;
+        for (int L = v; L < T; ++k) {
+            c[k] = T - L < L ? T - L : L;
+            L += c[k];
+        }
+        steps = k;
+    }
+    __syncthreads();
+    int* source = (f1 ? source1 : source0) + (size_t)b * T;
+    float* kp = (f1 ? kp1 : kp0) + (size_t)b * T * 3;
+    const size_t row0 = (size_t)b * 2 * T + (f1 ? T : 0);
+    bool bad = false;
+    for (int j = tid; j < T; j += 256) {
+        int i = j;
+        for (int k = steps - 1; k >= 0; --k)
+            if (i >= c[k]) i -= c[k];
+        const int r = kept[i];
+        source[j] = r;
+        bad |= assemble_record_f64(rec + (size_t)r * 37, normalize, in4 + (row0 + j) * 4, in33 + (row0 + j) * 33, kp + (size_t)j * 3);
+    }
+    if (bad) f64_raise(guard);
+}
+
 __global__ __launch_bounds__(256) void f64_to_f32_kernel(const double* in, float* out, size_t n, unsigned* guard) {
     bool bad = false;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -990,6 +1073,18 @@ int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, co
     hipLaunchKernelGGL(assemble_frames_ragged_f64_kernel, dim3(blocks), dim3(256), 0, s, rec0, rec1, start0, start1, cnt0, cnt1, normalize, in4, in33,
                        kp0, kp1, B, N, M, guard);
     return mdgat_check_hip(hipGetLastError(), "assemble_frames_ragged_f64 launch");
+}
+
+int launch_assemble_frames_train_f64(int B, int T, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
+                                     const int* cnt0, const int* cnt1, float min_saliency, int normalize, double* in4, double* in33, float* kp0,
+                                     float* kp1, int* source0, int* source1, int* salient0, int* salient1, unsigned* status, unsigned* guard,
+                                     hipStream_t s) {
+    if (T < 1 || T > TRAIN_MAX_KEYPOINTS) return MDGAT_ERR_BAD_ARG;      // (the kernel's LDS list; the entry refuses with a text)
+    if (!B) return MDGAT_OK;
+    hipLaunchKernelGGL(assemble_frames_train_f64_kernel, dim3(2 * B), dim3(256), 0, s, rec0, rec1, start0, start1, cnt0, cnt1,
+                       __builtin_bit_cast(unsigned, min_saliency), normalize, in4, in33, kp0, kp1, source0, source1, salient0, salient1, status, T,
+                       guard);
+    return mdgat_check_hip(hipGetLastError(), "assemble_frames_train_f64 launch");
 }
 
 int launch_f64_to_f32(const double* in, float* out, size_t n, unsigned* guard, hipStream_t s) {

@@ -63,7 +63,15 @@ int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const flo
 int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
                                       const int* cnt0, const int* cnt1, int normalize, double* in4, double* in33, float* kp0, float* kp1,
                                       unsigned* guard, hipStream_t s);
-// guard (all four): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
+// the loader's train-mode assembly (ensure_kpts_num, load_data.py:180-211) of the same chunk: the records with saliency > min_saliency, the
+// first T of them or padded to T by the loader's prepend loop; in4 / in33 in slots of T + T rows per pair, kp0 / kp1 [B][T][3], source0 / 1
+// [B][T] (the record row within its frame behind each slot), salient0 / 1 [B] (records kept), status [B][2] (1: a frame kept none and was
+// left unwritten).  1 <= T <= 2048
+int launch_assemble_frames_train_f64(int B, int T, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
+                                     const int* cnt0, const int* cnt1, float min_saliency, int normalize, double* in4, double* in33, float* kp0,
+                                     float* kp1, int* source0, int* source1, int* salient0, int* salient1, unsigned* status, unsigned* guard,
+                                     hipStream_t s);
+// guard (all five): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
 int launch_f64_to_f32(const double* in, float* out, size_t n, unsigned* guard, hipStream_t s);
 
 // ---- layer_f64.hip: the tail of a propagation layer (mlp.0 + ReLU, mlp.3 + residual, the next layer's q | k | v) as ONE launch ----

@@ -763,6 +763,36 @@ class MDGAT(nn.Module):
                 self._invalidate_if_changed()   # in-place optimizer updates since the last call: the packed weights are stale
         return train.training_forward(self, data)
 
+    def training_batch_frames(self, bank, idx0, idx1, T0, T1, T_gt=None, max_keypoints=512, gt_threshold=0.5, gt_mutual=None, min_saliency=10.0,
+                              normalize=True):
+        """The reference loader's TRAINING batch (``SparseDataset.__getitem__`` with ``ensure_kpts_num``, train.py's default for the training
+        and the validation set) for the chunk of pairs ``idx0[b]`` / ``idx1[b]`` of an ``ops.pack_frames`` bank, as device tensors: the
+        saliency filter, the truncation or padding to ``max_keypoints``, the float32 FPFH normalisation (``ops.assemble_frames_train``)
+        and the ground-truth matches of load_data.py:238-285 (``ops.gt_matches`` on the float32 keypoints) - two launches, one
+        synchronisation.  ``T0`` / ``T1`` [B, 4, 4] float64: sensor -> world of the frames (``pose @ T_cam0_velo``; None = identity), as
+        in ``evaluate_frames_ragged``; ``gt_mutual`` None = ``self.mutual_check`` (the reference hands one option to loader and model).
+        Returns what ``training_forward`` takes - ``keypoints0/1`` [B, T, 3], ``scores0/1``, ``descriptors0/1`` (float64), ``gt_matches0/1``
+        (int64 [B, T]) - plus ``rep`` [B], ``T_gt`` when given, and the assemble's ``keypoints0_f32/1_f32``, ``source0/1``, ``salient0/1``.
+        ``ValueError`` naming the pair and the frame for a frame without a salient keypoint (the reference's loader does not terminate
+        on it); ``RuntimeError`` for a kept record with a non-finite word or an all-zero FPFH row; ``ops.assemble_frames_train``'s
+        refusals otherwise."""
+        from . import train
+        return train.training_batch_frames(self, bank, idx0, idx1, T0, T1, T_gt=T_gt, max_keypoints=max_keypoints, gt_threshold=gt_threshold,
+                                           gt_mutual=gt_mutual, min_saliency=min_saliency, normalize=normalize)
+
+    def training_forward_frames(self, bank, idx0, idx1, T0, T1, **batch_options):
+        """``training_forward(training_batch_frames(bank, idx0, idx1, T0, T1, **batch_options))``: a training step (train() mode) or a
+        validation step (eval() mode: train.py's validation loader runs with ``ensure_kpts_num`` too) straight from a resident bank of
+        raw records.  ``training_forward``'s requirements: a float64 module on the bank's device, ``NotImplementedError`` otherwise
+        (before anything is launched)."""
+        if 'bin_score' not in self._parameters:
+            raise NotImplementedError('training_forward on a DataParallel replica: multi-GPU training is out of scope (one device only)')
+        dev = bank['records'].device
+        if self.bin_score.dtype != torch.float64 or self.bin_score.device != dev:
+            raise NotImplementedError(f'training_forward_frames needs a float64 module on the bank\'s device ({dev}): call net.double().to(device) '
+                                      f'(the module is {self.bin_score.dtype} on {self.bin_score.device}); the fp32-class path has no backward')
+        return self.training_forward(self.training_batch_frames(bank, idx0, idx1, T0, T1, **batch_options))
+
     def evaluate(self, data):
         """``forward(data)`` and then the evaluation scripts' per-pair record (test.py:212-296, test_registration_metric.py:213-264) of
         the forward's own device outputs against ``data['gt_matches0/1']`` and ``data['T_gt']`` (optional): the forward's dict plus

@@ -248,6 +248,52 @@ def assemble_frames_ragged(bank, idx0, idx1, normalize: bool = True) -> dict:
             'keypoints0_f32': kp0, 'keypoints1_f32': kp1, 'range_violation': guard}
 
 
+TRAIN_MAX_KEYPOINTS = 2048      # max_keypoints of assemble_frames_train: the attention's limit
+
+
+def assemble_frames_train(bank, idx0, idx1, max_keypoints: int, min_saliency: float = 10.0, normalize: bool = True) -> dict:
+    """What the loader makes of a chunk of pairs in TRAIN mode (``ensure_kpts_num``, train.py's default for the training and the
+    validation set; load_data.py:180-211), on the device in one launch: of frames ``idx0[b]`` / ``idx1[b]`` of a ``pack_frames`` bank the
+    records with saliency > ``min_saliency`` (float32; exactly ``min_saliency`` and NaN are dropped) in their order, the first
+    ``T = max_keypoints`` of them or - when there are fewer - padded to T by the loader's loop ``vstack((a[:T - len(a)], a))``; then
+    decoded, the FPFH rows L2-normalised in float32 exactly as numpy does it (``normalize``), widened to float64.  Returns uniform
+    ``keypoints0/1`` [B, T, 3], ``scores0/1`` [B, T], ``descriptors0/1`` [B, T, 33] (float64 views of the kernel's two outputs),
+    ``keypoints0_f32/1_f32`` (what ``gt_matches`` takes), ``source0/1`` (int32 [B, T]: the record's row within its frame behind each
+    slot), ``salient0/1`` (int32 [B]: records kept) and two device words, which to read synchronises: ``status`` (int32 [B, 2]: 1 where
+    frame 0 / 1 of a pair kept NO record - the reference's loop never ends there; that frame's rows are unwritten) and
+    ``range_violation`` (int32 [1]: a kept record held a non-finite word or an all-zero FPFH row).  Dropped records are never decoded,
+    records no pair points at never read.  ``ValueError`` for an empty chunk, ``max_keypoints`` outside 1 .. 2048 and a frame without
+    records."""
+    counts, starts = frames_chunk(bank, idx0, idx1)
+    h0, h1 = counts
+    B, T = int(h0.numel()), int(max_keypoints)
+    if B == 0:
+        raise ValueError('assemble_frames_train: an empty chunk has nothing to assemble')
+    if not 1 <= T <= TRAIN_MAX_KEYPOINTS:
+        raise ValueError(f'assemble_frames_train: max_keypoints={max_keypoints}: expected 1 .. {TRAIN_MAX_KEYPOINTS} (the attention\'s limit)')
+    for f, h in enumerate(counts):
+        if int(h.min()) < 1:
+            raise ValueError(f'assemble_frames_train: pair {int(h.argmin())}: frame {f} holds no record')
+    args, dc, ds = _frames_args(bank, counts, starts)
+    dev = bank['records'].device
+    in4 = torch.empty((B, 2 * T, 4), dtype=torch.float64, device=dev)
+    in33 = torch.empty((B, 2 * T, 33), dtype=torch.float64, device=dev)
+    kp0, kp1 = (torch.empty((B, T, 3), dtype=torch.float32, device=dev) for _ in '01')
+    src0, src1 = (torch.empty((B, T), dtype=torch.int32, device=dev) for _ in '01')
+    sal0, sal1 = (torch.empty((B,), dtype=torch.int32, device=dev) for _ in '01')
+    status = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    guard = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mdgat_assemble_frames_train_f64(B, T, *args, float(min_saliency), int(bool(normalize)), in4.data_ptr(), in33.data_ptr(),
+                                                               kp0.data_ptr(), kp1.data_ptr(), src0.data_ptr(), src1.data_ptr(), sal0.data_ptr(),
+                                                               sal1.data_ptr(), status.data_ptr(), guard.data_ptr(), _stream(in4)),
+                   'mdgat_assemble_frames_train_f64')
+    return {'keypoints0': in4[:, :T, :3], 'scores0': in4[:, :T, 3], 'descriptors0': in33[:, :T],
+            'keypoints1': in4[:, T:, :3], 'scores1': in4[:, T:, 3], 'descriptors1': in33[:, T:],
+            'keypoints0_f32': kp0, 'keypoints1_f32': kp1, 'source0': src0, 'source1': src1, 'salient0': sal0, 'salient1': sal1,
+            'range_violation': guard, 'status': status}
+
+
 def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64.
 

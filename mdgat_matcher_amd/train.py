@@ -135,3 +135,27 @@ def training_forward(net, data):
                 s0, s1 = torch.zeros_like(m0), torch.zeros_like(m1)
         loss = per_pair if method == _lib.LOSS_GAP else per_pair.mean()
     return {'matches0': m0, 'matches1': m1, 'matching_scores0': s0, 'matching_scores1': s1, 'loss': loss}
+
+
+def training_batch_frames(net, bank, idx0, idx1, T0, T1, T_gt=None, max_keypoints=512, gt_threshold=0.5, gt_mutual=None, min_saliency=10.0,
+                          normalize=True):
+    """See ``MDGAT.training_batch_frames``."""
+    a = ops.assemble_frames_train(bank, idx0, idx1, max_keypoints, min_saliency=min_saliency, normalize=normalize)
+    # the one read of the two device words: which frames kept no record, and whether a kept record was unusable
+    words = torch.cat([a['status'].reshape(-1), a['range_violation']]).cpu()
+    none = words[:-1].nonzero()
+    if none.numel():
+        w = int(none[0])
+        b, f = w // 2, w % 2
+        frame = int(torch.as_tensor((idx0, idx1)[f]).reshape(-1)[b])
+        raise ValueError(f'pair {b}: frame {f} (frame {frame} of the bank) has no keypoint with saliency > {float(min_saliency):g}: the '
+                         f"reference's loader does not terminate on it (load_data.py:198, `while kp1_num > len(kp1)` on an empty array)")
+    if int(words[-1]):
+        raise RuntimeError('training_batch_frames: a kept record of the chunk holds a non-finite word or an all-zero FPFH row (NaN '
+                           'descriptors in the reference): the batch is invalid')
+    mutual = net.mutual_check if gt_mutual is None else gt_mutual
+    g0, g1, rep = ops.gt_matches(a['keypoints0_f32'], a['keypoints1_f32'], T0, T1, threshold=gt_threshold, mutual=bool(mutual))
+    batch = {**a, 'gt_matches0': g0, 'gt_matches1': g1, 'rep': rep}
+    if T_gt is not None:
+        batch['T_gt'] = torch.as_tensor(T_gt).to(device=g0.device, dtype=torch.float64)
+    return batch
