@@ -636,6 +636,21 @@ int mdgat_mfma_f64_probe(int reps, void* workspace, size_t workspace_bytes, floa
 int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda, const double* W, int ldw, const double* bias,
                         int relu, const double* R, int ldr, double* C, int ldc, void* stream);
 int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream);
+/* Which kernel a product of the fp64 path runs (csrc/f64.hip: gemm_f64_kernel carries every Conv1d(k=1) of the exact mode and every
+ * product of the training path, mdgat_pointwise_f64 included).  It exists in ten instantiations, numbered 5 * bnt + form:
+ *   form 0: 64 x 64 tiles, guarded 8-byte copies, chunks of 32 (any shape, stride and 8-byte alignment)
+ *   form 1: 64 x 64 tiles, whole-tile 16-byte copies, chunks of 32      form 2: the same with chunks of 64
+ *   form 3: 64 x 128 tiles, guarded copies                              form 4: 64 x 128 tiles, whole-tile copies
+ *   bnt: the A operand is max(a (y - mean) + beta, 0) of what is loaded (the training-mode MLP's products behind a BatchNorm).
+ * mdgat_gemm_f64_plan: the index the launcher chooses for C [M][N] = A [M][K] W [N][K]^T whose first K0 columns come from the first
+ * source (K0 >= K: one source), `batch` independent products, on a device of `cus` compute units.  aligned != 0: every condition the
+ * whole-tile copies put on the operands holds - A, W (and the second source) 16-byte aligned, their leading dimensions (and batch
+ * strides) even.  A pure function of its arguments: no device is needed or touched.  -1: no launch (an empty product, or bnt with
+ * two sources, which the launcher refuses).
+ * mdgat_gemm_f64_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
+ * counters, never reset: read them before and after a call and subtract). */
+int mdgat_gemm_f64_plan(int M, int N, int K, int K0, int batch, int aligned, int bnt, int cus);
+void mdgat_gemm_f64_launches(uint64_t counts[10]);
 /* The same on a RAGGED batch: pair b has counts0[b] / counts1[b] keypoints in slots padded to Np / Mp (qkv [B][Np+Mp][384], frame 1 from row
  * Np on; msg and sel likewise, sel with the words of mdgat_topk_sel_words(B, Np, Mp)).  Queries and keys beyond a pair's counts take no part
  * and are never read; their message rows and selection words are zero.  A pair's rows are those of mdgat_attention_f64 on the pair alone -

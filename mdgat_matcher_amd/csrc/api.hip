@@ -1206,6 +1206,14 @@ extern "C" int mdgat_pointwise_f64(int M, int N, int K, const double* A, int lda
     return launch_gemm_f64(g, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int mdgat_gemm_f64_plan(int M, int N, int K, int K0, int batch, int aligned, int bnt, int cus) {
+    return gemm_f64_plan_index(M, N, K, K0, batch, aligned, bnt, cus);
+}
+
+extern "C" void mdgat_gemm_f64_launches(uint64_t counts[10]) {
+    if (counts) gemm_f64_launch_counts(counts);
+}
+
 // ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----
 // the shape and buffer checks of the gradient entries (this section and the two below)
 // nmax: keypoints per frame; rows: the rows the largest array of a pair holds

@@ -906,47 +906,76 @@ __global__ void mfma64_probe_fill(double* p, int n) {
 }  // namespace
 
 // ================================================================================================ launchers
+// The instantiation a launch runs, as the index 5 BNT + form that mdgat_gemm_f64_plan returns and mdgat_gemm_f64_launches counts by
+// (include/mdgat_hip.h): form 0 <2, slow>, 1 <2, fast, 32>, 2 <2, fast, 64>, 3 <4, slow>, 4 <4, fast>
+struct GemmF64Plan {
+    int wn; bool fast, deep;
+    int form() const { return wn == 4 ? (fast ? 4 : 3) : deep ? 2 : fast ? 1 : 0; }
+};
+static std::atomic<unsigned long long> gemm_f64_launch_count[10];
+
 template <bool BNT>
-static int gemm_f64_go(const GemmF64Args& a, int wn, bool fast, bool deep, hipStream_t s) {
+static int gemm_f64_go(const GemmF64Args& a, const GemmF64Plan& p, hipStream_t s) {
     static std::atomic<unsigned long long> done2{0}, done4{0}, done2f{0}, done4f{0}, done2d{0};
-    const int bn = 32 * wn;
-    const size_t lds = (size_t)(G_BM + bn) * ((deep ? 64 : G_KC) + 2) * sizeof(double);
+    const int bn = 32 * p.wn;
+    const size_t lds = (size_t)(G_BM + bn) * ((p.deep ? 64 : G_KC) + 2) * sizeof(double);
     const dim3 grid((a.M + G_BM - 1) / G_BM, (a.N + bn - 1) / bn, a.batch > 1 ? a.batch : 1);
     auto go = [&](auto kern, std::atomic<unsigned long long>& done) -> int {
         if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "gemm_f64 LDS")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+        gemm_f64_launch_count[5 * BNT + p.form()].fetch_add(1, std::memory_order_relaxed);
         return MDGAT_OK;
     };
-    if (wn == 4) return fast ? go(gemm_f64_kernel<4, true, G_KC, BNT>, done4f) : go(gemm_f64_kernel<4, false, G_KC, BNT>, done4);
-    if (deep) return go(gemm_f64_kernel<2, true, 64, BNT>, done2d);
-    return fast ? go(gemm_f64_kernel<2, true, G_KC, BNT>, done2f) : go(gemm_f64_kernel<2, false, G_KC, BNT>, done2);
+    if (p.wn == 4) return p.fast ? go(gemm_f64_kernel<4, true, G_KC, BNT>, done4f) : go(gemm_f64_kernel<4, false, G_KC, BNT>, done4);
+    if (p.deep) return go(gemm_f64_kernel<2, true, 64, BNT>, done2d);
+    return p.fast ? go(gemm_f64_kernel<2, true, G_KC, BNT>, done2f) : go(gemm_f64_kernel<2, false, G_KC, BNT>, done2);
 }
 
-int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
-    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return MDGAT_OK;
-    if (a.bn_mean && a.K0 < a.K) { mdgat_set_error("gemm_f64: the BatchNorm operand transform takes a single source"); return MDGAT_ERR_BAD_ARG; }
+// The choice, from the shape, the batch count, the device's CU count and `aligned`: every stride and alignment condition of the
+// whole-tile copies holds (gemm_f64_plan below).  Pure: no HIP call.
+static GemmF64Plan gemm_f64_plan_shape(int M, int N, int K, int K0, int batch, bool aligned, int cus) {
+    const long nb = batch > 1 ? batch : 1;
     // Tile width.  64 x 128 tiles do a third more arithmetic per byte staged through LDS; 64 x 64 tiles are twice as many workgroups
     // (four resident per CU instead of three).  Up to a few rounds of workgroups the launch is bound by how evenly it fills the
     // CUs, not by its inner loop: one pair of 512 keypoints is 16 row tiles - 48 wide workgroups on 256 CUs for the q|k|v product,
     // 96 narrow ones, 20 -> 17 us; 8192 rows x 128 outputs 31 -> 21 us (profiles/NOTES_r5.md section 9).  The narrow tile is taken
     // when its rounds of resident workgroups, priced at 0.55 of a wide round, come out below the wide tile's.
     int wn = 2;
-    if (a.N > 64) {
-        const int cus = mdgat_cu_count();
-        const long tiles_m64 = (long)((a.M + G_BM - 1) / G_BM) * (a.batch > 1 ? a.batch : 1);
-        const long tw = tiles_m64 * ((a.N + 127) / 128), tn = tiles_m64 * ((a.N + 63) / 64);
+    if (N > 64) {
+        const long tiles_m64 = (long)((M + G_BM - 1) / G_BM) * nb;
+        const long tw = tiles_m64 * ((N + 127) / 128), tn = tiles_m64 * ((N + 63) / 64);
         const long rw = (tw + 3 * cus - 1) / (3 * cus), rn = (tn + 4 * cus - 1) / (4 * cus);
         wn = (tw <= 6L * cus && rn * 55 < rw * 100) ? 2 : 4;
     }
     const int bn = 32 * wn;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool fast = a.M % G_BM == 0 && a.N % bn == 0 && a.K % G_KC == 0 && a.K0 % G_KC == 0 && a.lda0 % 2 == 0 && a.ldw % 2 == 0 && al16(a.A0) && al16(a.W) &&
-                      (a.K0 >= a.K || (a.lda1 % 2 == 0 && al16(a.A1))) && (a.batch <= 1 || (a.sA % 2 == 0 && a.sW % 2 == 0));
+    const bool fast = M % G_BM == 0 && N % bn == 0 && K % G_KC == 0 && K0 % G_KC == 0 && aligned;
     // (chunks of 64 for whole-tile launches of at most one 64 x 64 tile per CU: one or two pairs of 512 keypoints - 19.0 -> 17.8 us
     // at K = 256, the one-pair forward 1.54 -> 1.48 ms; from eight pairs on the shallower chunks' third resident workgroup wins)
-    const bool deep = fast && wn == 2 && a.K % 64 == 0 && (a.K0 >= a.K || a.K0 % 64 == 0) &&
-                      (long)((a.M + G_BM - 1) / G_BM) * ((a.N + 63) / 64) * (a.batch > 1 ? a.batch : 1) <= (long)mdgat_cu_count();
-    const int rc = a.bn_mean ? gemm_f64_go<true>(a, wn, fast, deep, s) : gemm_f64_go<false>(a, wn, fast, deep, s);
+    const bool deep = fast && wn == 2 && K % 64 == 0 && (K0 >= K || K0 % 64 == 0) && (long)((M + G_BM - 1) / G_BM) * ((N + 63) / 64) * nb <= (long)cus;
+    return GemmF64Plan{wn, fast, deep};
+}
+
+static GemmF64Plan gemm_f64_plan(const GemmF64Args& a, int cus) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool aligned = a.lda0 % 2 == 0 && a.ldw % 2 == 0 && al16(a.A0) && al16(a.W) && (a.K0 >= a.K || (a.lda1 % 2 == 0 && al16(a.A1))) &&
+                         (a.batch <= 1 || (a.sA % 2 == 0 && a.sW % 2 == 0));
+    return gemm_f64_plan_shape(a.M, a.N, a.K, a.K0, a.batch, aligned, cus);
+}
+
+int gemm_f64_plan_index(int M, int N, int K, int K0, int batch, int aligned, int bnt, int cus) {
+    if (M <= 0 || N <= 0 || K <= 0 || K0 < 0 || cus <= 0 || (bnt && K0 < K)) return -1;
+    return (bnt ? 5 : 0) + gemm_f64_plan_shape(M, N, K, K0, batch, aligned != 0, cus).form();
+}
+
+void gemm_f64_launch_counts(uint64_t counts[10]) {
+    for (int i = 0; i < 10; ++i) counts[i] = gemm_f64_launch_count[i].load(std::memory_order_relaxed);
+}
+
+int launch_gemm_f64(const GemmF64Args& a, hipStream_t s) {
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return MDGAT_OK;
+    if (a.bn_mean && a.K0 < a.K) { mdgat_set_error("gemm_f64: the BatchNorm operand transform takes a single source"); return MDGAT_ERR_BAD_ARG; }
+    const GemmF64Plan p = gemm_f64_plan(a, mdgat_cu_count());
+    const int rc = a.bn_mean ? gemm_f64_go<true>(a, p, s) : gemm_f64_go<false>(a, p, s);
     if (rc) return rc;
     return mdgat_check_hip(hipGetLastError(), "gemm_f64 launch");
 }

@@ -28,6 +28,10 @@ struct GemmF64Args {
                                        // formed as the operand is loaded
 };
 int launch_gemm_f64(const GemmF64Args& a, hipStream_t s);
+// Which of gemm_f64_kernel's ten instantiations launch_gemm_f64 runs (mdgat_gemm_f64_plan, include/mdgat_hip.h), and how often each
+// has been launched by this process (mdgat_gemm_f64_launches).  Host code only; the first touches no HIP call.
+int gemm_f64_plan_index(int M, int N, int K, int K0, int batch, int aligned, int bnt, int cus);
+void gemm_f64_launch_counts(uint64_t counts[10]);
 
 struct AttnF64Args {
     const double* qkv;     // [B][P][384]: q | k | v, each [4 heads][32 dims] (the rows of pack.py's qkv_w)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_f64_forms as F
 import head_grad_ref as R
 from sinkhorn_grad_ref import max_rel
 from test_head_grad_ref import CASE_METHODS, GRADS, random_inputs, torch_head
@@ -93,12 +94,26 @@ def test_kernel_against_the_restatement_float32(B, N, M):
 
 
 # ------------------------------------------------------------------------------------------------ 3: the forward
-@pytest.mark.parametrize('B,N,M', [(2, 17, 33), (3, 64, 64), (2, 257, 255)])
+# (gemm_f64_forms.BATCHED: batched, scaled score products of more than a round of workgroups, each written for one instantiation of
+# gemm_f64_kernel - B is the first candidate for which the launcher's plan names that instantiation on this device)
+@pytest.mark.parametrize('B,N,M', [(2, 17, 33), (3, 64, 64), (2, 257, 255)] + sorted(F.BATCHED))
 def test_forward_against_torch_and_grad_fn(B, N, M):
     ops = _ops()
+    want = None
+    if (B, N, M) in F.BATCHED:
+        form, cands = F.BATCHED[(B, N, M)]
+        cus, want = F.cu_count(), F.index(form)
+        B = F.pick(cands, want, cus, lambda b: dict(M=N, N=M, K=128, batch=b))
     a = random_inputs(B, N, M, 4000 + 7 * N + M)
     t = [_dev(x) for x in a[:4]]
-    plain = ops.match_head(*t)
+    with F.watch() as launches:
+        plain = ops.match_head(*t)
+    if want is not None:        # final_proj of either frame, then the scores: by the counters, the instantiation this case was written for
+        planned = np.zeros(10, dtype=np.int64)
+        for idx in (F.plan(B * N, 128, 128, cus=cus), F.plan(B * M, 128, 128, cus=cus), F.plan(N, M, 128, batch=B, cus=cus)):
+            planned[idx] += 1
+        assert np.array_equal(launches.delta, planned) and launches.delta[want] >= 1, \
+            f'{B}x{N}x{M}: wanted {F.NAMES[want]} for the scores, launched {launches.launched()} on a device of {cus} CUs'
     assert plain.grad_fn is None and not plain.requires_grad
     ref = torch_head(*t)
     _assert_within(plain.cpu().numpy(), ref.cpu().numpy(), R.tolerances(*a[:4])['scores'], f'{B}x{N}x{M} scores vs torch fp64')

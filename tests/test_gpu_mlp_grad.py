@@ -6,11 +6,13 @@ and to torch autograd by tests/test_mlp_grad_ref.py).
 Tolerance (mlp_grad_ref.tolerances), derived there: K u sum|a_k b_k| per product, carried through the layers on absolute values, with
 the terms BN brings (the relative error of invstd grows with 1 + |mean| / std and multiplies yhat, dgamma and dY), times 4.  Every
 input here has its ReLU decided by a factor 1e3 (tests/test_mlp_grad_ref.py asserts it on the CPU).  Every comparison prints the worst
-|difference| / tolerance it met."""
+|difference| / tolerance it met.  The two-source and behind-a-BatchNorm cases assert by the launch counters (tests/gemm_f64_forms.py)
+which instantiation of gemm_f64_kernel each of their products ran."""
 import numpy as np
 import pytest
 import torch
 
+import gemm_f64_forms as F
 import mlp_grad_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -48,14 +50,20 @@ def _grads(seq, xs):
     return g
 
 
-def _run(seq, x, dout, split=0, x_grad=True):
-    """ops.mlp_f64 and .backward() on rows x (split > 0: the two sources x[:, :split] | x[:, split:]): (out, grads, seq)."""
+def _run(seq, x, dout, split=0, x_grad=True, launches=None):
+    """ops.mlp_f64 and .backward() on rows x (split > 0: the two sources x[:, :split] | x[:, split:]): (out, grads, seq).
+    launches (a dict): filled with the fp64 GEMM launches by instantiation of the 'forward' and of the 'backward' (gemm_f64_forms)."""
     ops = _ops()
     xs = [_dev(x)] if split == 0 else [_dev(x[:, :split]), _dev(x[:, split:])]
     for t in xs:
         t.requires_grad_(x_grad)
-    out = ops.mlp_f64(seq, *xs)
-    out.backward(_dev(dout))
+    g = _dev(dout)
+    with F.watch() as fwd:
+        out = ops.mlp_f64(seq, *xs)
+    with F.watch() as bwd:
+        out.backward(g)
+    if launches is not None:
+        launches.update(forward=fwd.delta, backward=bwd.delta)
     torch.cuda.synchronize()
     return out.detach().cpu().numpy(), _grads(seq, xs), seq
 
@@ -95,7 +103,7 @@ def test_kernel_reproduces_fixture(golden_dir, name):
     assert worst <= 1.0
 
 
-def _against_restatement(stack, rows, training=True, case=None):
+def _against_restatement(stack, rows, training=True, case=None, split=None, launches=None):
     x, p, dout = case if case is not None else R.gpu_case(stack, rows)
     bare = len(p['W']) == 1
     out, cache, (rm, rv) = R.forward(x, p, training)
@@ -103,7 +111,7 @@ def _against_restatement(stack, rows, training=True, case=None):
     t = R.tolerances(x, p, dout, training)
     seq = _seq(p, training, bare)
     before = _buffers(seq) if not bare else None
-    got_out, got, _ = _run(seq, x, dout, split=128 if stack == 'layer' else 0)
+    got_out, got, _ = _run(seq, x, dout, split=(128 if stack == 'layer' else 0) if split is None else split, launches=launches)
     worst = max(R.worst_fraction(got_out, out, t['out']), R.compare_grads(got, want, t))
     assert set(got) == set(want) and all(v is not None for k in ('dW', 'db', 'dgamma', 'dbeta') for v in got[k])
     if not bare:
@@ -124,6 +132,58 @@ def test_kernel_agrees_with_restatement(stack):
         worst, _, _ = _against_restatement(stack, rows)
         print(f'{stack} R={rows}: worst fraction of the bound {worst:.3f}')
         assert worst <= 1.0
+
+
+# ---- the instantiations of gemm_f64_kernel (csrc/f64.hip) that only these products reach: two sources, and the operand behind a BN ----
+def _gemm_case(channels, rows, seed):
+    """(x, params, dout) of a stack ``channels`` at ``rows`` rows, its ReLU condition asserted on the CPU."""
+    rs = np.random.RandomState(seed)
+    x, p, dout = rs.standard_normal((rows, channels[0])), R.random_params(channels, seed + 1), rs.standard_normal((rows, channels[-1]))
+    margin = R.relu_margin(x, p)
+    assert margin >= 1e3, f'a BN output lies within {margin:.3g} bounds of zero: pick another seed'
+    return x, p, dout
+
+
+def _planned(cus, *products):
+    """Launches by instantiation of the products (M, N, K, K0, bnt) as the plan names them on this device (operands out of torch's
+    allocator and the library's workspace carve: 16-byte aligned, natural leading dimensions)."""
+    want = np.zeros(10, dtype=np.int64)
+    for M, N, K, K0, bnt in products:
+        want[F.plan(M, N, K, K0, bnt=bnt, cus=cus)] += 1
+    return want
+
+
+@pytest.mark.parametrize('K0,K1,rows', sorted(F.TWO_SOURCE))
+def test_two_source_convolution_reaches_its_form(K0, K1, rows):
+    """A bare 64-output convolution of the sources K0 | K1: whole chunks of one source each (32 | 32), chunks of 64 (64 | 64), and the
+    general form with a chunk that straddles K0 (40 | 24: the second chunk; 8 | 56: the first), on whole and ragged row tiles.  The same
+    run checks dx0 and dx1, the two products on the halves of the transposed weight with ldc = K0 and ldc = K1."""
+    cus, form = F.cu_count(), F.TWO_SOURCE[(K0, K1, rows)]
+    launches = {}
+    worst, _, _ = _against_restatement('two_source', rows, case=_gemm_case((K0 + K1, 64), rows, 7900 + 64 * K0 + rows), split=K0, launches=launches)
+    print(f'{K0} | {K1} R={rows}: worst fraction of the bound {worst:.3f}, forward {F.NAMES[int(launches["forward"].argmax())]} on {cus} CUs')
+    want = np.zeros(10, dtype=np.int64)
+    want[F.index(form)] = 1
+    assert np.array_equal(launches['forward'], want), f'wanted {form}, launched {dict(zip(F.NAMES, launches["forward"]))} on a device of {cus} CUs'
+    assert np.array_equal(launches['backward'], _planned(cus, (rows, K0, 64, 64, False), (rows, K1, 64, 64, False))), (launches['backward'], cus)
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize('name', sorted(F.BNT))
+def test_product_behind_a_batchnorm_reaches_its_form(name):
+    """The second convolution of a two-convolution stack reads max(BN(Y), 0) formed as the operand is loaded: the five BNT
+    instantiations, the two wide ones at the row counts at which the launcher takes 64 x 128 tiles on this device."""
+    ch, cands, form = F.BNT[name]
+    cus, want = F.cu_count(), F.index(form, True)
+    rows = F.pick(cands, want, cus, lambda r: dict(M=r, N=ch[2], K=ch[1], bnt=True))
+    launches = {}
+    worst, _, _ = _against_restatement(name, rows, case=_gemm_case(ch, rows, 8100 + rows), launches=launches)
+    print(f'{ch} R={rows}: worst fraction of the bound {worst:.3f}, forward {dict((F.NAMES[i], int(n)) for i, n in enumerate(launches["forward"]) if n)} on {cus} CUs')
+    assert np.array_equal(launches['forward'], _planned(cus, (rows, ch[1], ch[0], ch[0], False), (rows, ch[2], ch[1], ch[1], True))), \
+        f'wanted {F.NAMES[want]}, launched {dict(zip(F.NAMES, launches["forward"]))} on a device of {cus} CUs'
+    assert launches['forward'][want] == 1 and launches['forward'][5:].sum() == 1
+    assert np.array_equal(launches['backward'], _planned(cus, (rows, ch[1], ch[2], ch[2], False), (rows, ch[0], ch[1], ch[1], False))), (launches['backward'], cus)
+    assert worst <= 1.0
 
 
 @pytest.mark.parametrize('stack', ['kenc', 'denc', 'layer', 'ragged'])
