@@ -600,6 +600,34 @@ size_t mdgat_attention_workspace_bytes(int B, int N, int M);
 int mdgat_attention_sel(int B, int N, int M, int cross, int topk, const float* qkv, float* msg, uint32_t* sel,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which kernel an attention launch of the fp32 class runs (csrc/attention.hip: launch_attention, which mdgat_attention, mdgat_attention_sel
+ * and every layer of the fp32-class forward go through), and with what launch geometry.  The instantiations it can reach:
+ *    0 stream              full attention, both frames multiples of 64 keys (attention_stream_kernel<false>)
+ *    1 full<4>             attention_kernel<false, 4, false>: full, <= 128 keys                     (tiles of 256 queries)
+ *    2 full<8>             attention_kernel<false, 8, false>: full, <= 512 keys                     (256)
+ *    3 full<8,windowed>    attention_kernel<false, 8, true>:  full, > 512 keys, a 512-key window    (256)
+ *    4 dyn<4>              attention_kernel<true, 4, false>:  top-k, <= 128 keys                    (256)
+ *    5 dyn<8>              attention_kernel<true, 8, false>:  top-k, <= 256 keys                    (256)
+ *    6 dyn<16>             attention_kernel<true, 16, false>: top-k, <= 512 keys                    (128)
+ *    7 topk16<256>         attention_topk16_kernel<false, false, 256>: top-k, 256 x 256             (16)
+ *    8 topk16<512>         attention_topk16_kernel<false, false, 512>: top-k, 512 x 512             (16)
+ *    9 wide<4>             attention_topk_wide_kernel<4>: top-k, <= 1024 keys                       (64 per pass)
+ *   10 wide<8>             attention_topk_wide_kernel<8>: top-k, <= 2048 keys                       (32 per pass)
+ *   11 .. 17               the TAP twins of 4 .. 10 (a selection buffer is passed: index + 7)
+ *   18 stream,FAST         19 topk16<256>,FAST      20 topk16<512>,FAST      21, 22 the TAP twins of 19, 20
+ *                          (mode MDGAT_ATTENTION_F16; the other kernels have no FAST form: mode 1 launches the index mode 0 does)
+ * mdgat_attention_plan: the index for B pairs of N x M keypoints, `topk` (0: full), tap != 0: a selection buffer is passed, mode: an
+ * mdgat_attention_mode.  -1: nothing is launched (an empty batch) or the launcher refuses (topk < 0, topk > min(N, M), top-k over more
+ * than 2048 keys).  *split (optional): the workgroups that share the query tiles of one (pair, frame, head) - gridDim.x of
+ * attention_kernel, the grid_split of the 16-query and wide kernels, the tile count of the streamed one.  *tiles (optional): the most
+ * query tiles (wide kernels: passes) one workgroup walks, ceil(tiles of the larger frame / split).  Both 0 with -1.  A pure function of
+ * its arguments: no device is needed or touched; launch_attention takes its branch and its split from the same code.
+ * mdgat_attention_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
+ * counters, never reset: read them before and after a call and subtract). */
+#define MDGAT_ATTENTION_FORMS 23
+int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles);
+void mdgat_attention_launches(uint64_t counts[MDGAT_ATTENTION_FORMS]);
+
 /* Measurement only (bench.py, roofline_qk): the Q K^T contraction of the streamed full-attention kernel in isolation -
  * the same chunk ring, LDS reads and split-f16 MFMA sequence as mdgat_attention, without V^T traffic, softmax and P.V.
  * msg [B][P][128]: element [p][head * 32] receives the row maximum of the base-2 logits, the rest is left alone.

@@ -1104,6 +1104,17 @@ extern "C" int mdgat_attention_sel(int B, int N, int M, int cross, int topk, con
     return launch_attention(B, N, M, cross, topk, q16, msg, s, 0, sel);
 }
 
+extern "C" int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles) {
+    const AttnPlan p = topk < 0 ? AttnPlan{-1, 0, 0, MDGAT_ERR_BAD_ARG} : attention_plan(B, N, M, topk, tap != 0, mode);   // (topk < 0: mdgat_attention refuses)
+    if (split) *split = p.split;
+    if (tiles) *tiles = p.tiles;
+    return p.form;
+}
+
+extern "C" void mdgat_attention_launches(uint64_t counts[MDGAT_ATTENTION_FORMS]) {
+    if (counts) attention_launch_counts(counts);
+}
+
 extern "C" int mdgat_attention_qk_probe(int B, int N, int M, int cross, const float* qkv, float* msg, void* workspace,
                                         size_t workspace_bytes, void* stream) {
     if (!qkv || !msg || !workspace) { mdgat_set_error("mdgat_attention_qk_probe: null pointer"); return MDGAT_ERR_BAD_ARG; }

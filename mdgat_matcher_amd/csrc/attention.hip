@@ -1262,27 +1262,19 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
     }
 }
 
-static int launch_attention_topk_wide(const AttnArgs& a, int B, int nk_max, hipStream_t s) {
-    const int nblk = (nk_max + 31) / 32;
-    if (nblk > 64) {
-        mdgat_set_error("dynamic attention: %d keys per frame > 2048 supported", nk_max);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
+static int launch_attention_topk_wide(const AttnArgs& a, int B, const AttnPlan& p, hipStream_t s) {
     const size_t lds = (size_t)(1040 + 8 * 18 * 64 + 4 * 8 * 64) * sizeof(float);
     AttnArgs w = a;
     w.grid_units = B * 2 * MDGAT_HEADS;
-    const int ugroups = (w.grid_units + 7) / 8;
-    if (nblk <= 32) {
-        w.grid_split = (nk_max + 63) / 64;
-        const dim3 grid(8 * w.grid_split * ugroups);
-        if (a.sel) hipLaunchKernelGGL((attention_topk_wide_kernel<4, true>), grid, dim3(512), lds, s, w);
-        else hipLaunchKernelGGL(attention_topk_wide_kernel<4>, grid, dim3(512), lds, s, w);
-    } else {
-        w.grid_split = (nk_max + 31) / 32;
-        const dim3 grid(8 * w.grid_split * ugroups);
-        if (a.sel) hipLaunchKernelGGL((attention_topk_wide_kernel<8, true>), grid, dim3(512), lds, s, w);
-        else hipLaunchKernelGGL(attention_topk_wide_kernel<8>, grid, dim3(512), lds, s, w);
+    w.grid_split = p.split;
+    const dim3 grid(8 * w.grid_split * ((w.grid_units + 7) / 8));
+    switch (p.form) {
+    case ATTN_WIDE4: hipLaunchKernelGGL(attention_topk_wide_kernel<4>, grid, dim3(512), lds, s, w); break;
+    case ATTN_WIDE4 + ATTN_TAP: hipLaunchKernelGGL((attention_topk_wide_kernel<4, true>), grid, dim3(512), lds, s, w); break;
+    case ATTN_WIDE8: hipLaunchKernelGGL(attention_topk_wide_kernel<8>, grid, dim3(512), lds, s, w); break;
+    default: hipLaunchKernelGGL((attention_topk_wide_kernel<8, true>), grid, dim3(512), lds, s, w); break;
     }
+    attention_count_launch(p.form);
     return mdgat_check_hip(hipGetLastError(), "wide dynamic attention launch");
 }
 
@@ -1364,80 +1356,125 @@ extern "C" size_t mdgat_topk_sel_words(int B, int N, int M) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     return (size_t)B * 4 * (N + M) * (((N > M ? N : M) + 31) / 32); }
 
+// ---- the launcher's choice as a pure function (mdgat_attention_plan; no HIP call), and the launches counted by it ----
+static std::atomic<unsigned long long> attention_launch_count[ATTN_FORMS];
+void attention_count_launch(int form) { attention_launch_count[form].fetch_add(1, std::memory_order_relaxed); }
+void attention_launch_counts(uint64_t counts[MDGAT_ATTENTION_FORMS]) {
+    for (int i = 0; i < ATTN_FORMS; ++i) counts[i] = attention_launch_count[i].load(std::memory_order_relaxed);
+}
+
+AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
+    if (B <= 0 || N <= 0 || M <= 0) return AttnPlan{-1, 0, 0, MDGAT_OK};
+    const int nk_max = N > M ? N : M, nk_min = N < M ? N : M;
+    // torch.topk raises when k exceeds the number of keys of either direction (mdgat.py:202)
+    if (topk > nk_min) return AttnPlan{-1, 0, 0, MDGAT_ERR_BAD_ARG};
+    // k == number of keys on both sides keeps every key: identical to full attention
+    const bool dyn = topk > 0 && !(topk == N && topk == M);
+    const bool fast = mode == 1;
+    const int nblk = (nk_max + 31) / 32;
+    const int units = B * 2 * MDGAT_HEADS;
+    if (!dyn && attention_stream_supported(N, M)) return AttnPlan{fast ? ATTN_STREAM_FAST : ATTN_STREAM, attention_stream_qtiles(N, M), 1, MDGAT_OK};
+    // attention_kernel: one workgroup per (pair, frame, head) loops over its query tiles (32 queries per wave); split the tiles over
+    // more workgroups only when there are too few (pair, frame, head) units to fill the chip twice
+    auto go = [&](int form, int threads) {
+        const int qt = (threads / 64) * 32;
+        const int qtiles = (nk_max + qt - 1) / qt;
+        int qsplit = (512 + units - 1) / units;
+        if (qsplit > qtiles) qsplit = qtiles;
+        if (qsplit < 1) qsplit = 1;
+        if (nk_max > 512) qsplit = qtiles;     // windowed kernel: every pass re-stages its keys anyway
+        return AttnPlan{form, qsplit, (qtiles + qsplit - 1) / qsplit, MDGAT_OK};
+    };
+    // exactly 512 (or 256) keys in both frames: one wave = 16 queries, the row in four lanes
+    auto go16 = [&](int form, int nkey) {
+        // a workgroup is 8 waves = 8 query tiles per pass: nkey / 128 workgroups per (pair, frame, head) keep every wave busy;
+        // more (every workgroup stages all keys: up to 4, half the waves idle at 256 keys) only while the launch is smaller than the part
+        int qsplit = (512 + units - 1) / units;
+        const int qmax = units * (nkey / 128) >= 256 ? nkey / 128 : 4;
+        if (qsplit > qmax) qsplit = qmax;
+        if (fast) form += ATTN_TOPK16_256_FAST - ATTN_TOPK16_256 + (tap ? ATTN_FAST_TAP : 0);
+        else if (tap) form += ATTN_TAP;
+        return AttnPlan{form, qsplit, (nkey / 16 + qsplit - 1) / qsplit, MDGAT_OK};
+    };
+    if (!dyn) {
+        // chunks of 8 blocks (256 keys), two waves per SIMD
+        if (nblk <= 4) return go(ATTN_FULL4, 512);
+        if (nblk > 16) return go(ATTN_FULL8_WINDOWED, 512);
+        return go(ATTN_FULL8, 512);
+    }
+    // the whole row in one chunk
+    if (N == 256 && M == 256) return go16(ATTN_TOPK16_256, 256);
+    if (tap && !(N == 512 && M == 512) && nblk <= 16)
+        return nblk <= 4 ? go(ATTN_DYN4 + ATTN_TAP, 512) : nblk <= 8 ? go(ATTN_DYN8 + ATTN_TAP, 512) : go(ATTN_DYN16 + ATTN_TAP, 256);
+    if (nblk <= 4) return go(ATTN_DYN4, 512);
+    if (nblk <= 8) return go(ATTN_DYN8, 512);
+    if (N == 512 && M == 512) return go16(ATTN_TOPK16_512, 512);
+    if (nblk <= 16) return go(ATTN_DYN16, 256);
+    if (nblk > 64) return AttnPlan{-1, 0, 0, MDGAT_ERR_UNSUPPORTED};
+    // wide kernels: a workgroup pass is 64 (four waves per tile) or 32 (eight) queries, one workgroup per pass of the larger frame
+    const int per_pass = nblk <= 32 ? 64 : 32;
+    const int npass = (nk_max + per_pass - 1) / per_pass;
+    return AttnPlan{(nblk <= 32 ? ATTN_WIDE4 : ATTN_WIDE8) + (tap ? ATTN_TAP : 0), npass, 1, MDGAT_OK};
+}
+
 int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode, uint32_t* sel) {
     if (B <= 0 || N <= 0 || M <= 0) return MDGAT_OK;
     const int nk_max = N > M ? N : M;
-    if (topk > 0) {
-        // torch.topk raises when k exceeds the number of keys of either direction (mdgat.py:202)
-        const int nk_min = N < M ? N : M;
-        if (topk > nk_min) {
-            mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", topk, nk_min);
-            return MDGAT_ERR_BAD_ARG;
-        }
+    const bool dyn = topk > 0 && !(topk == N && topk == M);
+    const AttnPlan p = attention_plan(B, N, M, topk, sel && dyn, mode);
+    if (p.rc == MDGAT_ERR_BAD_ARG) {
+        mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", topk, N < M ? N : M);
+        return p.rc;
     }
     AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, (nk_max + 31) / 32};
     if (topk > 0) a.zq = normal_quantile_upper(((double)topk - 0.5) / (double)nk_max);
     const int nkp = ((nk_max + 31) / 32) * 32;
     const int wkeys = nkp > 512 ? 512 : nkp;      // keys the LDS window holds
     const size_t lds = ((size_t)wkeys * KROWH + (size_t)64 * (wkeys + 8)) * sizeof(_Float16);
-    // k == number of keys on both sides keeps every key: identical to full attention
-    const bool dyn = topk > 0 && !(topk == N && topk == M);
-    const int nblk = nkp / 32;
     if (sel && topk > 0) {
         // parity tap: the kept keys of every (pair, head, query) as a bit mask; k == number of keys keeps them all
         if (int rc = mdgat_check_hip(hipMemsetAsync(sel, dyn ? 0 : 0xff, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
         if (dyn) a.sel = sel;
     }
-    if (!dyn && attention_stream_supported(N, M)) return launch_attention_stream(B, N, M, cross, qkv, msg, s, mode);
-    // one workgroup per (pair, frame, head) loops over its query tiles; split the tiles over more
-    // workgroups only when there are too few (pair, frame, head) units to fill the chip twice
+    if (p.rc == MDGAT_ERR_UNSUPPORTED) {
+        mdgat_set_error("dynamic attention: %d keys per frame > 2048 supported", nk_max);
+        return p.rc;
+    }
+    if (p.form == ATTN_STREAM || p.form == ATTN_STREAM_FAST) return launch_attention_stream(B, N, M, cross, qkv, msg, s, mode);
     auto go = [&](auto kern, int threads) {
-        const int qt = (threads / 64) * 32;
-        const int qtiles = (nk_max + qt - 1) / qt;
-        int qsplit = (512 + B * 2 * MDGAT_HEADS - 1) / (B * 2 * MDGAT_HEADS);
-        if (qsplit > qtiles) qsplit = qtiles;
-        if (qsplit < 1) qsplit = 1;
-        if (nk_max > 512) qsplit = qtiles;     // windowed kernel: every pass re-stages its keys anyway
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(qsplit, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
+        hipLaunchKernelGGL(kern, dim3(p.split, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
     };
-    // exactly 512 (or 256) keys in both frames: one wave = 16 queries, the row in four lanes
     auto launch16 = [&](auto nkc) {
         constexpr int NKEY = decltype(nkc)::value;
-        // a workgroup is 8 waves = 8 query tiles per pass: NKEY / 128 workgroups per (pair, frame, head) keep every wave busy;
-        // more (every workgroup stages all keys: up to 4, half the waves idle at 256 keys) only while the launch is smaller than the part
-        int qsplit = (512 + B * 2 * MDGAT_HEADS - 1) / (B * 2 * MDGAT_HEADS);
-        const int qmax = B * 2 * MDGAT_HEADS * (NKEY / 128) >= 256 ? NKEY / 128 : 4;
-        if (qsplit > qmax) qsplit = qmax;
         const size_t lds3 = ((size_t)2 * 4 * NKEY * 8 + (size_t)64 * (NKEY + 8)) * sizeof(_Float16) + 16;    // + the tile counter
         AttnArgs w = a;
-        w.grid_split = qsplit;
+        w.grid_split = p.split;
         w.grid_units = B * 2 * MDGAT_HEADS;
         auto run = [&](auto kern) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL(kern, dim3(8 * qsplit * ((w.grid_units + 7) / 8)), dim3(512), lds3, s, w);
+            hipLaunchKernelGGL(kern, dim3(8 * p.split * ((w.grid_units + 7) / 8)), dim3(512), lds3, s, w);
         };
         if (a.sel) { if (mode == 1) run(attention_topk16_kernel<true, true, NKEY>); else run(attention_topk16_kernel<false, true, NKEY>); }
         else if (mode == 1) run(attention_topk16_kernel<true, false, NKEY>);
         else run(attention_topk16_kernel<false, false, NKEY>);
     };
-    if (dyn) {
-        // the whole row in one chunk
-        if (N == 256 && M == 256) launch16(std::integral_constant<int, 256>{});
-        else if (a.sel && !(N == 512 && M == 512) && nblk <= 16) {
-            if (nblk <= 4) go(attention_kernel<true, 4, false, true>, 512);
-            else if (nblk <= 8) go(attention_kernel<true, 8, false, true>, 512);
-            else go(attention_kernel<true, 16, false, true>, 256);
-        } else if (nblk <= 4) go(attention_kernel<true, 4, false>, 512);
-        else if (nblk <= 8) go(attention_kernel<true, 8, false>, 512);
-        else if (N == 512 && M == 512) launch16(std::integral_constant<int, 512>{});
-        else if (nblk <= 16) go(attention_kernel<true, 16, false>, 256);
-        else return launch_attention_topk_wide(a, B, nk_max, s);
-    } else {
-        // chunks of 8 blocks (256 keys), two waves per SIMD
-        if (nblk <= 4) go(attention_kernel<false, 4, false>, 512);
-        else if (nblk > 16) go(attention_kernel<false, 8, true>, 512);
-        else go(attention_kernel<false, 8, false>, 512);
+    switch (p.form) {
+    case ATTN_FULL4: go(attention_kernel<false, 4, false>, 512); break;
+    case ATTN_FULL8: go(attention_kernel<false, 8, false>, 512); break;
+    case ATTN_FULL8_WINDOWED: go(attention_kernel<false, 8, true>, 512); break;
+    case ATTN_DYN4: go(attention_kernel<true, 4, false>, 512); break;
+    case ATTN_DYN8: go(attention_kernel<true, 8, false>, 512); break;
+    case ATTN_DYN16: go(attention_kernel<true, 16, false>, 256); break;
+    case ATTN_DYN4 + ATTN_TAP: go(attention_kernel<true, 4, false, true>, 512); break;
+    case ATTN_DYN8 + ATTN_TAP: go(attention_kernel<true, 8, false, true>, 512); break;
+    case ATTN_DYN16 + ATTN_TAP: go(attention_kernel<true, 16, false, true>, 256); break;
+    case ATTN_TOPK16_256: case ATTN_TOPK16_256 + ATTN_TAP: case ATTN_TOPK16_256_FAST: case ATTN_TOPK16_256_FAST + ATTN_FAST_TAP:
+        launch16(std::integral_constant<int, 256>{}); break;
+    case ATTN_TOPK16_512: case ATTN_TOPK16_512 + ATTN_TAP: case ATTN_TOPK16_512_FAST: case ATTN_TOPK16_512_FAST + ATTN_FAST_TAP:
+        launch16(std::integral_constant<int, 512>{}); break;
+    default: return launch_attention_topk_wide(a, B, p, s);
     }
+    attention_count_launch(p.form);
     return mdgat_check_hip(hipGetLastError(), "attention launch");
 }

@@ -453,14 +453,14 @@ __global__ __launch_bounds__(256, 2) void qk_phase_probe_kernel(StreamArgs a) {
 bool attention_stream_supported(int N, int M) { return N % 64 == 0 && M % 64 == 0; }
 
 int launch_attention_stream(int B, int N, int M, int cross, const Qkv16& qkv, float* msg, hipStream_t s, int mode) {
-    const int nq_max = N > M ? N : M;
-    StreamArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, (nq_max + 127) / 128};
+    StreamArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, attention_stream_qtiles(N, M)};
     const size_t lds = (size_t)NSLOT * CHUNK_BYTES;
     static std::atomic<unsigned long long> optin[2];
     const void* kern = mode == 1 ? reinterpret_cast<const void*>(attention_stream_kernel<true>) : reinterpret_cast<const void*>(attention_stream_kernel<false>);
     if (int rc = mdgat_lds_optin(kern, lds, optin[mode == 1], "attention LDS attribute")) return rc;
     if (mode == 1) hipLaunchKernelGGL(attention_stream_kernel<true>, dim3(B * 8 * a.QT), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(attention_stream_kernel<false>, dim3(B * 8 * a.QT), dim3(256), lds, s, a);
+    attention_count_launch(mode == 1 ? ATTN_STREAM_FAST : ATTN_STREAM);
     return mdgat_check_hip(hipGetLastError(), "attention launch");
 }
 

@@ -158,8 +158,24 @@ int launch_qkv_split(int B, int N, int M, const float* qkv, const Qkv16& out, hi
 // mode: mdgat_attention_mode (1 = single-f16 products where implemented)
 // sel (parity tap, may be NULL): the kept keys of a dynamic layer as bit masks [B][4][P][W], W = ceil(max(N, M) / 32)
 int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode = 0, uint32_t* sel = nullptr);
+// Which instantiation launch_attention runs and its launch geometry (mdgat_attention_plan, include/mdgat_hip.h: the table of indices), and
+// how often each has been launched by this process (mdgat_attention_launches).  Host code only; the plan touches no HIP call.
+enum AttnForm {
+    ATTN_STREAM = 0, ATTN_FULL4, ATTN_FULL8, ATTN_FULL8_WINDOWED, ATTN_DYN4, ATTN_DYN8, ATTN_DYN16, ATTN_TOPK16_256, ATTN_TOPK16_512, ATTN_WIDE4,
+    ATTN_WIDE8, ATTN_TAP = 7 /* + ATTN_DYN4 .. ATTN_WIDE8 */, ATTN_STREAM_FAST = 18, ATTN_TOPK16_256_FAST, ATTN_TOPK16_512_FAST,
+    ATTN_FAST_TAP = 2 /* + the two above */, ATTN_FORMS = MDGAT_ATTENTION_FORMS
+};
+struct AttnPlan {
+    int form;           // AttnForm, or -1: no launch
+    int split, tiles;   // workgroups per (pair, frame, head); the most query tiles one of them walks
+    int rc;             // why not, where the launcher refuses (MDGAT_OK otherwise; the message is the launcher's)
+};
+AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode);
+void attention_count_launch(int form);
+void attention_launch_counts(uint64_t counts[MDGAT_ATTENTION_FORMS]);
 // full attention as a stream of 64-key chunks (attention_stream.hip); frames with key counts that are multiples of 64
 bool attention_stream_supported(int N, int M);
+inline int attention_stream_qtiles(int N, int M) { return ((N > M ? N : M) + 127) / 128; }   // workgroups (128 queries each) per (pair, frame, head)
 int launch_attention_stream(int B, int N, int M, int cross, const Qkv16& qkv, float* msg, hipStream_t s, int mode = 0);
 // measurement only: the Q K^T phase of the streamed kernel in isolation (msg[row][head * 32] receives the row maximum)
 int launch_attention_qk_probe(int B, int N, int M, int cross, const Qkv16& qkv, float* msg, hipStream_t s);

@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import attention_forms as AF  # noqa: E402
 from mdgat_matcher_amd import MDGAT, synth  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -340,12 +341,21 @@ def test_f16_attention_mode_configs2():
     ref = O.mdgat_forward(sd, cfg, data, cap)
     d = {k: v.to(DEV) for k, v in data.items()}
     out = {}
+    fast = [i for i, nm in enumerate(AF.NAMES) if nm.endswith(',FAST')]
     for dt in ('fp32', 'f16'):
         net = MDGAT(dict(cfg, attention_dtype=dt)).double()
         net.load_state_dict(sd)
         net = net.double().eval().to(DEV)
-        out[dt] = net.match(d['keypoints0'], d['descriptors0'], d['keypoints1'], d['descriptors1'],
-                            d['scores0'], d['scores1'], return_scores=True)
+        with AF.watch() as w:
+            out[dt] = net.match(d['keypoints0'], d['descriptors0'], d['keypoints1'], d['descriptors1'],
+                                d['scores0'], d['scores1'], return_scores=True)
+        # by the launch counters: the f16 mode runs the FAST instantiations of the streamed and the 512-key kernels, one per layer, and
+        # no split-f16 instantiation of a kernel that has a FAST one; the fp32 mode the other way round
+        dyn = sum(kk > 0 for kk in net._topk_schedule())
+        assert 0 < dyn < 2 * L
+        tw = {'stream': 2 * L - dyn, 'topk16<512>': dyn}
+        assert w.launched() == ({nm + ',FAST': c for nm, c in tw.items()} if dt == 'f16' else tw), (dt, w.launched())
+        assert all(w.delta[AF.SPLIT_TWIN[i] if dt == 'f16' else i] == 0 for i in fast), (dt, w.launched())
     e32 = (out['fp32'][4].cpu().double() - cap['Z']).abs().max().item()
     e16 = (out['f16'][4].cpu().double() - cap['Z']).abs().amax(dim=(1, 2))
     same0 = (out['f16'][0].cpu() == ref['matches0']).double().mean(dim=1)
@@ -364,7 +374,9 @@ def test_f16_attention_mode_configs2():
     # a configs[2]-sized batch (512 pairs, sliced) in f16 mode: deterministic, batch-independent across a slice boundary
     big = synth.make_batch(512, n, n, device=DEV, dtype=torch.float32)
     bargs = (big['keypoints0'], big['descriptors0'], big['keypoints1'], big['descriptors1'], big['scores0'], big['scores1'])
-    r1 = net.match(*bargs)
+    with AF.watch() as w:
+        r1 = net.match(*bargs)
+    assert set(w.launched()) == {'stream,FAST', 'topk16<512>,FAST'}, w.launched()       # (every slice of it)
     r2 = net.match(*bargs)
     assert all(torch.equal(a, b) for a, b in zip(r1, r2))
     for p in (63, 64, 511):
@@ -378,8 +390,10 @@ def test_f16_attention_mode_configs2():
         net = MDGAT(dict(synth.default_config(L=2, k=[16, None], sinkhorn_iterations=10), attention_dtype=dt))
         net.load_state_dict(synth.make_state_dict(L=2, seed=3))
         net = net.double().eval().to(DEV)
-        zs.append(net.match(ds['keypoints0'], ds['descriptors0'], ds['keypoints1'], ds['descriptors1'],
-                            ds['scores0'], ds['scores1'], return_scores=True)[4])
+        with AF.watch() as w:
+            zs.append(net.match(ds['keypoints0'], ds['descriptors0'], ds['keypoints1'], ds['descriptors1'],
+                                ds['scores0'], ds['scores1'], return_scores=True)[4])
+        assert w.launched() and all(AF.NAMES.index(nm) in AF.MODE0 for nm in w.launched()), (dt, w.launched())
     assert torch.equal(zs[0], zs[1])
 
 
@@ -415,6 +429,10 @@ CROSS_DYNAMIC = [(2, 512, 512, 2, [None, 128, 64, 64]), (2, 256, 256, 2, [None, 
                  (1, 1500, 520, 2, [64, 64, None, 128])]
 
 
+# the dynamic kernel (tests/attention_forms.py) a CROSS layer of each schedule is there for
+CROSS_DYNAMIC_KERNELS = {(512, 512): 'topk16<512>', (256, 256): 'topk16<256>', (100, 77): 'dyn<4>', (1500, 520): 'wide<8>'}
+
+
 @pytest.mark.parametrize('B,n,m,L,k', CROSS_DYNAMIC)
 def test_cross_dynamic_schedules_vs_oracle(B, n, m, L, k):
     """Top-k schedules with dynamic CROSS layers (odd layer indices; the reference's default schedule and the goldens make only
@@ -429,7 +447,20 @@ def test_cross_dynamic_schedules_vs_oracle(B, n, m, L, k):
     net = net.double().eval().to(DEV)
     assert not net.exact()
     data = synth.make_batch(B, n, m, first_pair=3)
-    res = attributed_parity(net, cfg, sd, data, DEV)
+    # the kernels named above, by the plan: the instantiation of every layer, with the tap (the attributed forward) and without ...
+    sched = net._topk_schedule()
+    want = {}
+    for kk in sched:
+        for tap in (True, False):
+            nm = AF.name(AF.plan(B, n, m, kk, tap)[0])
+            want[nm] = want.get(nm, 0) + 1
+    named = CROSS_DYNAMIC_KERNELS[n, m]
+    assert any(kk > 0 and AF.name(AF.plan(B, n, m, kk)[0]) == named for kk in sched[1::2]), (named, sched)
+    assert named in want and named + ',TAP' in want
+    # ... and by the launch counters those are the ones the two forwards ran
+    with AF.watch() as w:
+        res = attributed_parity(net, cfg, sd, data, DEV)
+    assert w.launched() == want, (w.launched(), want)
     assert_attributed(res, f'cross-dynamic {B}x{n}x{m} k={k}')
     assert_plain_vs_oracle(res, cfg, sd, data, f'cross-dynamic {B}x{n}x{m} k={k}')
 

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import attention_forms as AF  # noqa: E402
 from mdgat_matcher_amd import _lib, ops  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -59,14 +60,24 @@ def _ref_msg_to_lib(msg):
     return msg.permute(0, 3, 2, 1).reshape(b, n, h * dh)
 
 
-@pytest.mark.parametrize('N,M', [(64, 64), (40, 56), (128, 96), (512, 512), (257, 130), (33, 31), (600, 700), (1024, 1024),
-                                 (2048, 1300), (128, 320), (192, 64), (2048, 1344)])   # multiples of 64: the streamed kernel
+# the instantiation each shape of test_attention_full reaches (tests/attention_forms.py); multiples of 64: the streamed kernel
+FULL_FORMS = {(64, 64): 'stream', (40, 56): 'full<4>', (128, 96): 'full<4>', (512, 512): 'stream', (257, 130): 'full<8>', (33, 31): 'full<4>',
+              (600, 700): 'full<8,windowed>', (1024, 1024): 'stream', (2048, 1300): 'full<8,windowed>', (128, 320): 'stream',
+              (192, 64): 'stream', (2048, 1344): 'stream'}
+
+
+@pytest.mark.parametrize('N,M', list(FULL_FORMS))
 @pytest.mark.parametrize('cross', [False, True])
 def test_attention_full(N, M, cross):
     rs = np.random.RandomState(N * 7 + M)
     B = 2 if N <= 1024 else 1
     qkv = torch.from_numpy(rs.standard_normal((B, N + M, 3, 4, 32)) * 1.3)
-    out = ops.attention(qkv.to(DEV), N, M, cross).cpu().double()
+    # the kernel this shape is here for: by the plan, and by the launch counters the one that ran
+    want = FULL_FORMS[N, M]
+    assert AF.name(AF.plan(B, N, M)[0]) == want
+    with AF.watch() as w:
+        out = ops.attention(qkv.to(DEV), N, M, cross).cpu().double()
+    AF.assert_launched(w, want, f'full {N}x{M}')
     # oracle per frame
     for side, (lo, hi) in enumerate(((0, N), (N, N + M))):
         slo, shi = ((N, N + M) if side == 0 else (0, N)) if cross else (lo, hi)
@@ -137,14 +148,23 @@ def test_attention_mismatched_magnitudes(N, topk, case):
         assert err[ok].max() < tol, (case, float(err[ok].max()), tol)
 
 
-@pytest.mark.parametrize('N,M,k', [(64, 64, 16), (64, 64, 1), (64, 64, 63), (40, 56, 8), (512, 512, 128), (512, 512, 64),
-                                   (256, 256, 128), (100, 70, 70), (48, 64, 16), (300, 500, 64), (1024, 1024, 128),
-                                   (2048, 2048, 64), (700, 600, 100), (1500, 520, 64), (513, 513, 512)])
+# the (untapped) instantiation each case of test_attention_topk reaches
+TOPK_FORMS = {(64, 64, 16): 'dyn<4>', (64, 64, 1): 'dyn<4>', (64, 64, 63): 'dyn<4>', (40, 56, 8): 'dyn<4>', (512, 512, 128): 'topk16<512>',
+              (512, 512, 64): 'topk16<512>', (256, 256, 128): 'topk16<256>', (100, 70, 70): 'dyn<4>', (48, 64, 16): 'dyn<4>',
+              (300, 500, 64): 'dyn<16>', (1024, 1024, 128): 'wide<4>', (2048, 2048, 64): 'wide<8>', (700, 600, 100): 'wide<4>',
+              (1500, 520, 64): 'wide<8>', (513, 513, 512): 'wide<4>'}
+
+
+@pytest.mark.parametrize('N,M,k', list(TOPK_FORMS))
 def test_attention_topk(N, M, k):
     rs = np.random.RandomState(N + 13 * M + k)
     B = 2 if N <= 1024 else 1
     qkv = torch.from_numpy(rs.standard_normal((B, N + M, 3, 4, 32)) * 1.3)
-    out = ops.attention(qkv.to(DEV), N, M, False, topk=k).cpu().double()
+    want = TOPK_FORMS[N, M, k]
+    assert AF.name(AF.plan(B, N, M, k)[0]) == want
+    with AF.watch() as w:
+        out = ops.attention(qkv.to(DEV), N, M, False, topk=k).cpu().double()
+    AF.assert_launched(w, want, f'top-k {N}x{M} k={k}')
     for lo, hi in ((0, N), (N, N + M)):
         q = qkv[:, lo:hi, 0].permute(0, 3, 2, 1)
         kk = qkv[:, lo:hi, 1].permute(0, 3, 2, 1)
@@ -360,14 +380,21 @@ def _frames(qkv, N, M, cross):
     return out
 
 
-def _check_topk_cross(qkv, N, M, k, tag):
+def _check_topk_cross(qkv, N, M, k, tag, want):
     """Both kernel instantiations (with and without the selection tap) of one dynamic cross layer against the fp64 oracle:
     exactly k keys per row on both sides, the selection of torch.topk on the fp64 logits outside near-ties (< 2e-3 of the rows),
     the message within 1e-5 of the oracle with the kernel's selection forced on every row and with the oracle's own selection on
-    the other rows, and the two instantiations within 1e-6 of each other."""
+    the other rows, and the two instantiations within 1e-6 of each other.  ``want``: the kernel (tests/attention_forms.py) - by the plan,
+    and by the launch counters its TAP twin and itself are the two that run."""
     x = qkv.to(DEV)
-    out, sels = ops.attention(x, N, M, True, topk=k, return_selection=True)
-    shipped = ops.attention(x, N, M, True, topk=k)
+    for tap in (True, False):
+        assert AF.plan(qkv.shape[0], N, M, k, tap)[0] == AF.index(want, tap), (tag, tap)
+    with AF.watch() as w:
+        out, sels = ops.attention(x, N, M, True, topk=k, return_selection=True)
+    AF.assert_launched(w, AF.index(want, True), tag)
+    with AF.watch() as w:
+        shipped = ops.attention(x, N, M, True, topk=k)
+    AF.assert_launched(w, AF.index(want), tag)
     d_tap = float((out - shipped).abs().max())
     assert d_tap < 1e-6, (tag, d_tap)
     out = out.cpu().double()
@@ -404,14 +431,18 @@ def _check_topk_cross(qkv, N, M, k, tag):
     print(f'[topk-cross] {tag}: near-tie rows {ties} of {rows}, worst message error {worst:.2e}, tap vs shipped {d_tap:.1e}')
 
 
-@pytest.mark.parametrize('N,M,k', [
-    (40, 100, 8), (100, 40, 40),                    # attention_kernel<true, 4>: max(N, M) <= 128
-    (200, 130, 64), (130, 256, 130),                # attention_kernel<true, 8>: <= 256 keys, not 256 x 256
-    (256, 256, 128), (256, 256, 1),                 # attention_topk16_kernel<256>: N = M = 256
-    (300, 500, 64), (500, 300, 300),                # attention_kernel<true, 16>: <= 512 keys, not 512 x 512
-    (512, 512, 128), (512, 512, 64),                # attention_topk16_kernel<512>: N = M = 512
-    (700, 600, 100), (1000, 513, 64),               # attention_topk_wide_kernel<4>: 513 ... 1024 keys
-    (1500, 520, 64), (2048, 700, 128), (130, 2048, 130)])   # attention_topk_wide_kernel<8>: 1025 ... 2048 keys
+# the kernel each case of test_attention_topk_cross is here for (tests/attention_forms.py)
+CROSS_FORMS = {
+    (40, 100, 8): 'dyn<4>', (100, 40, 40): 'dyn<4>',                    # attention_kernel<true, 4>: max(N, M) <= 128
+    (200, 130, 64): 'dyn<8>', (130, 256, 130): 'dyn<8>',                # attention_kernel<true, 8>: <= 256 keys, not 256 x 256
+    (256, 256, 128): 'topk16<256>', (256, 256, 1): 'topk16<256>',       # attention_topk16_kernel<256>: N = M = 256
+    (300, 500, 64): 'dyn<16>', (500, 300, 300): 'dyn<16>',              # attention_kernel<true, 16>: <= 512 keys, not 512 x 512
+    (512, 512, 128): 'topk16<512>', (512, 512, 64): 'topk16<512>',      # attention_topk16_kernel<512>: N = M = 512
+    (700, 600, 100): 'wide<4>', (1000, 513, 64): 'wide<4>',             # attention_topk_wide_kernel<4>: 513 ... 1024 keys
+    (1500, 520, 64): 'wide<8>', (2048, 700, 128): 'wide<8>', (130, 2048, 130): 'wide<8>'}   # attention_topk_wide_kernel<8>: 1025 ... 2048 keys
+
+
+@pytest.mark.parametrize('N,M,k', list(CROSS_FORMS))
 def test_attention_topk_cross(N, M, k):
     """Dynamic CROSS layers at every fp32-class top-k kernel form the dispatcher picks (launch_attention, from max(N, M) and the
     tap).  With N != M a workgroup's query count (its side) differs from its key count (the other frame): a kernel that takes one
@@ -422,7 +453,7 @@ def test_attention_topk_cross(N, M, k):
     rs = np.random.RandomState(N + 13 * M + k + 1)
     B = 2 if max(N, M) <= 1024 else 1
     qkv = torch.from_numpy(rs.standard_normal((B, N + M, 3, 4, 32)) * 1.3)
-    _check_topk_cross(qkv, N, M, k, f'{N}x{M} k={k}')
+    _check_topk_cross(qkv, N, M, k, f'{N}x{M} k={k}', CROSS_FORMS[N, M, k])
 
 
 def test_attention_topk_cross_k_equals_both_frames():
