@@ -412,6 +412,27 @@ int mdgat_set_lanes(mdgat_handle* h, int lanes);
  * results are bit-identical either way.  tiles = 0: never; tiles < 0: back to the default.  Returns the previous value. */
 int mdgat_set_layer_split_tiles(int tiles);
 
+/* Which kernel a layer-tail launch of the fp32 class runs (csrc/layer.hip: launch_layer, which every layer of the fp32-class forward goes
+ * through), and with what launch geometry.  The 14 instantiations it can reach, <DO_MLP, MODE3> (DO_MLP 0: projection only, the launch
+ * in front of the first fp32-class layer; MODE3 1: the next layer's q | k | v, 2: final_proj) and, for layer_kernel, <.., VW, NW>:
+ *    0 split<0,1>      1 split<0,2>      2 split<1,1>      3 split<1,2>       layer_split_kernel: 32 keypoints per workgroup; launches of
+ *                                                                             at most mdgat_set_layer_split_tiles tiles of 128 keypoints
+ *    4 layer<0,1,0,4>  5 layer<0,2,0,4>  6 layer<1,1,0,4>  7 layer<1,2,0,4>   layer_kernel, 64 keypoints per workgroup: at most 128 tiles
+ *    8 layer<0,1,0,8>  9 layer<0,1,1,8> 10 layer<0,2,0,8>                     layer_kernel, 128 keypoints per workgroup: larger launches;
+ *   11 layer<1,1,0,8> 12 layer<1,1,1,8> 13 layer<1,2,0,8>                     VW = 1: q | k | v with N and M multiples of 128
+ * mdgat_layer_plan: the index for a launch of R = B (N + M) keypoint rows, do_mlp != 0: with the MLP and residual, mode3: 1 = q | k | v,
+ * anything else = final_proj.  -1: nothing is launched (R <= 0).  *workgroups (optional): the grid, ceil(R / *keypoints_per_workgroup);
+ * *keypoints_per_workgroup (optional): 32, 64 or 128; *v_store (optional): the V^T store path, as the keypoints that go out in one
+ * piece - 0: none (final_proj), 1: single halves, 4: 8-byte stores ((N | M) % 4 == 0), 16: whole 32-byte row pieces of a wave
+ * ((N | M) % 16 == 0; layer_kernel only: the split kernel stores such frames in runs of 4), 128: 256-byte pieces through the gather
+ * buffers (VW).  All 0 with -1.  It reads the current mdgat_set_layer_split_tiles value and nothing else but its arguments: no device
+ * is needed or touched; launch_layer takes its branch and its grid from the same code.
+ * mdgat_layer_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
+ * counters, incremented after a launch that succeeded, never reset: read them before and after a call and subtract). */
+#define MDGAT_LAYER_FORMS 14
+int mdgat_layer_plan(int R, int N, int M, int do_mlp, int mode3, int* workgroups, int* keypoints_per_workgroup, int* v_store);
+void mdgat_layer_launches(uint64_t counts[MDGAT_LAYER_FORMS]);
+
 /* MDGAT_ARITH_FP64: how the tail of an fp64 layer (mlp.0 + ReLU, mlp.3 + residual; models/mdgat.py:246-248, 274) and the next
  * layer's q | k | v projection (227-232) are launched.  1 (default; MDGAT_F64_LAYER_FUSION=0 in the environment selects 0): one
  * launch per layer with the hidden activation kept on chip (csrc/layer_f64.hip) - launches of at most a quarter of the compute

@@ -141,6 +141,8 @@ SIGNATURES = {
     'mdgat_profile': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     'mdgat_set_lanes': (C.c_int, [C.c_void_p, C.c_int]),
     'mdgat_set_layer_split_tiles': (C.c_int, [C.c_int]),
+    'mdgat_layer_plan': (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 3),
+    'mdgat_layer_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_set_f64_layer_fusion': (C.c_int, [C.c_int]),
     'mdgat_set_f64_attention_form': (C.c_int, [C.c_int]),
     'mdgat_set_f64_sinkhorn_form': (C.c_int, [C.c_int]),

@@ -1115,6 +1115,18 @@ extern "C" void mdgat_attention_launches(uint64_t counts[MDGAT_ATTENTION_FORMS])
     if (counts) attention_launch_counts(counts);
 }
 
+extern "C" int mdgat_layer_plan(int R, int N, int M, int do_mlp, int mode3, int* workgroups, int* keypoints_per_workgroup, int* v_store) {
+    const LayerPlan p = layer_plan(R, N, M, do_mlp, mode3);
+    if (workgroups) *workgroups = p.workgroups;
+    if (keypoints_per_workgroup) *keypoints_per_workgroup = p.keypoints;
+    if (v_store) *v_store = p.v_store;
+    return p.form;
+}
+
+extern "C" void mdgat_layer_launches(uint64_t counts[MDGAT_LAYER_FORMS]) {
+    if (counts) layer_launch_counts(counts);
+}
+
 extern "C" int mdgat_attention_qk_probe(int B, int N, int M, int cross, const float* qkv, float* msg, void* workspace,
                                         size_t workspace_bytes, void* stream) {
     if (!qkv || !msg || !workspace) { mdgat_set_error("mdgat_attention_qk_probe: null pointer"); return MDGAT_ERR_BAD_ARG; }

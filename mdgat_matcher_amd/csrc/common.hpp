@@ -197,6 +197,20 @@ struct LayerLaunch {
                                        // operand range (|v| >= MDGAT_F16_GUARD) or a non-finite one
 };
 int launch_layer(const LayerLaunch& p, hipStream_t s);
+// Which of the 14 instantiations launch_layer runs and its launch geometry (mdgat_layer_plan, include/mdgat_hip.h: the table of
+// indices), and how often each has been launched by this process (mdgat_layer_launches).  Host code only; the plan touches no HIP call.
+enum LayerForm {
+    LAYER_SPLIT = 0 /* + 2 do_mlp + (mode3 != 1) */, LAYER_NW4 = 4 /* + the same */,
+    LAYER_NW8 = 8 /* + 3 do_mlp + {0: q|k|v, 1: q|k|v with the V^T gather (VW), 2: final_proj} */, LAYER_FORMS = MDGAT_LAYER_FORMS
+};
+struct LayerPlan {
+    int form;           // LayerForm index, or -1: no launch
+    int workgroups;     // grid size: ceil(R / keypoints)
+    int keypoints;      // per workgroup: 32 (split), 64 (NW = 4), 128 (NW = 8)
+    int v_store;        // keypoints per V^T store run: 0 (final_proj: no V), 1, 4, 16, 128 (VW: 256-byte pieces through the gather buffers)
+};
+LayerPlan layer_plan(int R, int N, int M, int do_mlp, int mode3);
+void layer_launch_counts(uint64_t counts[MDGAT_LAYER_FORMS]);
 // rowh >= 2 K: row pitch (halves); the first nperm rows are written in the P/Q row order of layer.hip
 int launch_split_rows(const float* w, _Float16* out, int rows, int K, int rowh, int nperm, hipStream_t s);
 // row image [rows][rowh] (launch_split_rows) -> fragment order [rows / 16][K / 32][plane][lane = row l15 + 16 g][8 halves] (layer_split.hip)

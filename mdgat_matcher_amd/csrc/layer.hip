@@ -390,7 +390,7 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
                     *reinterpret_cast<f16x4_a*>(c0 + 4 * 2 * TILE_FLOATS) = f16x4{stl[0], stl[1], stl[2], stl[3]};
                     *reinterpret_cast<f16x4_a*>(c0 + 6 * 2 * TILE_FLOATS) = f16x4{stl[4], stl[5], stl[6], stl[7]};
                 }
-            } else if (((a.N | a.M) & 15) == 0) {
+            } else if (layer_vt_runs_of(16, a.N, a.M)) {
                 // the 16 keypoints of the wave share frame and pair: 32 contiguous bytes per (plane, dim) row,
                 // gathered through the tile so that a lane writes one whole row
                 if (wave_pt0 < a.R) {
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(64 * NW) void layer_kernel(LayerArgs a) {
                 }
             } else if (u == 11) {
                 // ragged frames: 4 consecutive keypoints per lane (8-byte stores) or single halves
-                const bool fast = ((a.N | a.M) & 3) == 0;      // 4 consecutive keypoints share frame and pair, 8-byte aligned
+                const bool fast = layer_vt_runs_of(4, a.N, a.M);      // 4 consecutive keypoints share frame and pair, 8-byte aligned
                 const int p0 = wave_pt0 + 4 * g;
 #pragma unroll
                 for (int blk = 0; blk < 2; ++blk) {
@@ -593,13 +593,13 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* w, _Float1
 }
 
 template <int DO_MLP, int MODE3, int VW, int NW>
-int launch_layer_t(const LayerArgs& a, hipStream_t s) {
+int launch_layer_t(const LayerArgs& a, const LayerPlan& p, hipStream_t s) {
     constexpr int NWAVE = NW;
+    static_assert(WPTS * NW == (NW == 4 ? 64 : 128), "layer_plan states the keypoints per workgroup as 64 (NW = 4) and 128 (NW = 8)");
     const size_t lds = (size_t)NSLOT * SLOT_BYTES + (768 + NWAVE * TILE_FLOATS) * sizeof(float);
     static std::atomic<unsigned long long> optin;        // (one per template instance)
     if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(layer_kernel<DO_MLP, MODE3, VW, NW>), lds, optin, "layer LDS attribute")) return rc;
-    constexpr int TILE_PTS = WPTS * NWAVE;
-    hipLaunchKernelGGL((layer_kernel<DO_MLP, MODE3, VW, NW>), dim3((a.R + TILE_PTS - 1) / TILE_PTS), dim3(64 * NWAVE), lds, s, a);
+    hipLaunchKernelGGL((layer_kernel<DO_MLP, MODE3, VW, NW>), dim3(p.workgroups), dim3(64 * NWAVE), lds, s, a);
     return mdgat_check_hip(hipGetLastError(), "layer launch");
 }
 
@@ -616,23 +616,53 @@ int launch_split_rows(const float* w, _Float16* out, int rows, int K, int rowh, 
 static std::atomic<int> g_split_tiles{[] { const char* e = getenv("MDGAT_LAYER_SPLIT_TILES"); return e ? atoi(e) : MDGAT_LAYER_SPLIT_TILES_DEFAULT; }()};
 extern "C" int mdgat_set_layer_split_tiles(int tiles) { return g_split_tiles.exchange(tiles < 0 ? MDGAT_LAYER_SPLIT_TILES_DEFAULT : tiles); }
 
+// ---- the launcher's choice as a pure function (mdgat_layer_plan; no HIP call), and the launches counted by it ----
+static std::atomic<unsigned long long> layer_launch_count[LAYER_FORMS];
+void layer_launch_counts(uint64_t counts[MDGAT_LAYER_FORMS]) {
+    for (int i = 0; i < LAYER_FORMS; ++i) counts[i] = layer_launch_count[i].load(std::memory_order_relaxed);
+}
+
+LayerPlan layer_plan(int R, int N, int M, int do_mlp, int mode3) {
+    if (R <= 0) return LayerPlan{-1, 0, 0, 0};
+    const int tiles = (R + 127) / 128;
+    const int mlp = do_mlp ? 1 : 0;
+    const bool qkv = mode3 == 1;                 // (every other mode3 is final_proj, as the launchers always read it)
+    const int run = !qkv ? 0 : layer_vt_runs_of(16, N, M) ? 16 : layer_vt_runs_of(4, N, M) ? 4 : 1;
+    auto go = [&](int form, int keypoints, int v_store) { return LayerPlan{form, (R + keypoints - 1) / keypoints, keypoints, v_store}; };
+    // launches of a few tiles (one pair, small batches): the channel-split kernel of layer_split.hip - 32-keypoint workgroups
+    // whose eight waves share the output channels; bit-identical results (mdgat_set_layer_split_tiles: tuning / A-B hook).
+    // It has no whole-row V^T path: runs of 16 go out as four runs of 4
+    if (tiles <= g_split_tiles.load(std::memory_order_relaxed)) return go(LAYER_SPLIT + 2 * mlp + !qkv, MDGAT_LAYER_SPLIT_PTS, run > 4 ? 4 : run);
+    // small launches (fewer 128-keypoint tiles than half the CUs of the part): 64-keypoint workgroups, one wave per SIMD
+    if (tiles <= MDGAT_LAYER_TILE64_TILES) return go(LAYER_NW4 + 2 * mlp + !qkv, 64, run);
+    // frames that are multiples of 128 keypoints: the V^T rows of the whole workgroup through the gather buffers (VW)
+    const bool vw = qkv && layer_vt_runs_of(128, N, M);
+    return go(LAYER_NW8 + 3 * mlp + (!qkv ? 2 : vw ? 1 : 0), 128, vw ? 128 : run);
+}
+
 int launch_layer(const LayerLaunch& p, hipStream_t s) {
-    if (p.R <= 0) return MDGAT_OK;
+    const LayerPlan pl = layer_plan(p.R, p.N, p.M, p.do_mlp, p.proj.mode3);
+    if (pl.form < 0) return MDGAT_OK;
     LayerArgs a{};
     a.x = p.x; a.msg = p.msg;
     a.w1s = p.mlp.w1s; a.b1 = p.mlp.b1; a.w2s = p.mlp.w2s; a.b2 = p.mlp.b2; a.w3s = p.proj.w3s; a.b3 = p.proj.b3;
     a.w1f = p.mlp.w1f; a.w2f = p.mlp.w2f; a.w3f = p.proj.w3f;
     a.q16 = p.out.q16; a.k16 = p.out.k16; a.vt16 = p.out.vt16; a.mdesc = p.mdesc;
     a.R = p.R; a.N = p.N; a.M = p.M; a.Npad = p.out.Npad; a.PP = p.out.PP; a.guard = p.guard;
-    // launches of a few tiles (one pair, small batches): the channel-split kernel of layer_split.hip - 32-keypoint workgroups
-    // whose eight waves share the output channels; bit-identical results (mdgat_set_layer_split_tiles: tuning / A-B hook)
-    if ((p.R + 127) / 128 <= g_split_tiles.load(std::memory_order_relaxed)) return launch_layer_split(a, p.do_mlp, p.proj.mode3, s);
-    // small launches (fewer 128-keypoint tiles than half the CUs of the part): 64-keypoint workgroups, one wave per SIMD
-    if ((p.R + 127) / 128 <= MDGAT_LAYER_TILE64_TILES) {
-        if (p.do_mlp) return p.proj.mode3 != 1 ? launch_layer_t<1, 2, 0, 4>(a, s) : launch_layer_t<1, 1, 0, 4>(a, s);
-        return p.proj.mode3 != 1 ? launch_layer_t<0, 2, 0, 4>(a, s) : launch_layer_t<0, 1, 0, 4>(a, s);
+    int rc;
+    switch (pl.form) {
+    case LAYER_NW4 + 0: rc = launch_layer_t<0, 1, 0, 4>(a, pl, s); break;
+    case LAYER_NW4 + 1: rc = launch_layer_t<0, 2, 0, 4>(a, pl, s); break;
+    case LAYER_NW4 + 2: rc = launch_layer_t<1, 1, 0, 4>(a, pl, s); break;
+    case LAYER_NW4 + 3: rc = launch_layer_t<1, 2, 0, 4>(a, pl, s); break;
+    case LAYER_NW8 + 0: rc = launch_layer_t<0, 1, 0, 8>(a, pl, s); break;
+    case LAYER_NW8 + 1: rc = launch_layer_t<0, 1, 1, 8>(a, pl, s); break;
+    case LAYER_NW8 + 2: rc = launch_layer_t<0, 2, 0, 8>(a, pl, s); break;
+    case LAYER_NW8 + 3: rc = launch_layer_t<1, 1, 0, 8>(a, pl, s); break;
+    case LAYER_NW8 + 4: rc = launch_layer_t<1, 1, 1, 8>(a, pl, s); break;
+    case LAYER_NW8 + 5: rc = launch_layer_t<1, 2, 0, 8>(a, pl, s); break;
+    default: rc = launch_layer_split(a, pl.form, pl.workgroups, s); break;
     }
-    const bool vw = p.proj.mode3 == 1 && ((p.N | p.M) & 127) == 0;
-    if (p.do_mlp) return p.proj.mode3 != 1 ? launch_layer_t<1, 2, 0, 8>(a, s) : vw ? launch_layer_t<1, 1, 1, 8>(a, s) : launch_layer_t<1, 1, 0, 8>(a, s);
-    return p.proj.mode3 != 1 ? launch_layer_t<0, 2, 0, 8>(a, s) : vw ? launch_layer_t<0, 1, 1, 8>(a, s) : launch_layer_t<0, 1, 0, 8>(a, s);
+    if (rc == MDGAT_OK) layer_launch_count[pl.form].fetch_add(1, std::memory_order_relaxed);
+    return rc;
 }

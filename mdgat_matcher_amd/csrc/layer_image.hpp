@@ -27,8 +27,17 @@ struct LayerArgs {
     unsigned* guard;        // optional, host-mapped: set when an input value is outside the f16 operand range or not finite
 };
 
+// Do `run` (a power of two) consecutive keypoints of the [pair][N + M] row order, starting at a multiple of `run`, always share pair
+// and frame and land on V^T columns aligned to as many halves (frame 1 starts at column Npad, a multiple of 32)?  The one place the
+// V^T store path of a q|k|v launch is decided - both kernels and layer_plan (layer.hip) ask here: 128 (the launcher's VW: a workgroup's
+// 128 keypoints go out as 256-byte row pieces through the gather buffers), 16 (a wave's 16 keypoints as whole 32-byte row pieces;
+// layer.hip only), 4 (a lane's 4 keypoints as one 8-byte store); otherwise single halves.
+__host__ __device__ inline bool layer_vt_runs_of(int run, int N, int M) { return ((N | M) & (run - 1)) == 0; }
+
 // layer_split.hip: the same layer for launches of a few tiles (one pair, small batches)
 constexpr int MDGAT_LAYER_SPLIT_TILES_DEFAULT = 64;   // measured (tools/split_threshold.sh, N = M = 512): wins up to 64 tiles (B = 8), ties at 96-128, loses beyond
+constexpr int MDGAT_LAYER_SPLIT_PTS = 32;             // keypoints per workgroup of layer_split_kernel
 // layer.hip: launches of at most this many 128-keypoint tiles (fewer than half the CUs of the part) use 64-keypoint workgroups
 constexpr int MDGAT_LAYER_TILE64_TILES = 128;
-int launch_layer_split(const LayerArgs& a, int do_mlp, int mode3, hipStream_t s);
+// form: a LAYER_SPLIT index of layer_plan (common.hpp), workgroups: the plan's
+int launch_layer_split(const LayerArgs& a, int form, int workgroups, hipStream_t s);

@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64 * SP_NW) void layer_split_kernel(LayerArgs a) {
             const int head = wave >> 1, dim = 16 * (wave & 1) + l15;
             const float bias = bias3[(8 + head) * 32 + dim];
             const int P = a.N + a.M;
-            const bool fast = ((a.N | a.M) & 3) == 0;      // 4 consecutive keypoints share frame and pair, 8-byte aligned
+            const bool fast = layer_vt_runs_of(4, a.N, a.M);      // 4 consecutive keypoints share frame and pair, 8-byte aligned
 #pragma unroll
             for (int kpb = 0; kpb < SP_KPB; ++kpb) {
                 const int p0 = pt0 + kpb * 16 + 4 * g;
@@ -410,10 +410,11 @@ __global__ __launch_bounds__(256) void frag_image_kernel(const _Float16* img, _F
 }
 
 template <int DO_MLP, int MODE3>
-int launch_split_t(const LayerArgs& a, hipStream_t s) {
+int launch_split_t(const LayerArgs& a, int workgroups, hipStream_t s) {
+    static_assert(SP_PTS == MDGAT_LAYER_SPLIT_PTS, "layer_plan states the keypoints per workgroup");
     static std::atomic<unsigned long long> optin;        // (one per template instance)
     if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(layer_split_kernel<DO_MLP, MODE3>), sizeof(SpLds), optin, "layer (split) LDS attribute")) return rc;
-    hipLaunchKernelGGL((layer_split_kernel<DO_MLP, MODE3>), dim3((a.R + SP_PTS - 1) / SP_PTS), dim3(64 * SP_NW), sizeof(SpLds), s, a);
+    hipLaunchKernelGGL((layer_split_kernel<DO_MLP, MODE3>), dim3(workgroups), dim3(64 * SP_NW), sizeof(SpLds), s, a);
     return mdgat_check_hip(hipGetLastError(), "layer (split) launch");
 }
 
@@ -425,7 +426,13 @@ int launch_frag_image(const _Float16* img, _Float16* out, int rows, int K, int r
     return mdgat_check_hip(hipGetLastError(), "frag_image launch");
 }
 
-int launch_layer_split(const LayerArgs& a, int do_mlp, int mode3, hipStream_t s) {
-    if (do_mlp) return mode3 != 1 ? launch_split_t<1, 2>(a, s) : launch_split_t<1, 1>(a, s);
-    return mode3 != 1 ? launch_split_t<0, 2>(a, s) : launch_split_t<0, 1>(a, s);
+int launch_layer_split(const LayerArgs& a, int form, int workgroups, hipStream_t s) {
+    switch (form) {
+    case LAYER_SPLIT + 0: return launch_split_t<0, 1>(a, workgroups, s);
+    case LAYER_SPLIT + 1: return launch_split_t<0, 2>(a, workgroups, s);
+    case LAYER_SPLIT + 2: return launch_split_t<1, 1>(a, workgroups, s);
+    case LAYER_SPLIT + 3: return launch_split_t<1, 2>(a, workgroups, s);
+    }
+    mdgat_set_error("layer (split): form %d is not one of its four", form);
+    return MDGAT_ERR_BAD_ARG;
 }

@@ -320,6 +320,11 @@ def test_f64_stages_vs_reference(golden_dir, name):
     for i in range(2 * L):
         e = max(np.abs(xl[i][:, :n] - t(g[f'layer{i}_desc0'])).max(), np.abs(xl[i][:, n:] - t(g[f'layer{i}_desc1'])).max())
         assert e < 5e-6, (i, e)
+    # final_proj and the score matrix: the fp32-class tail behind the fp64 layers (the projection-only final_proj launch of
+    # csrc/layer.hip), at the bars of tests/test_gpu_forward.py::test_forward_stages_golden
+    md = taps['mdesc'].cpu().double().numpy()
+    assert max(np.abs(md[:, :n] - t(g['mdesc0'])).max(), np.abs(md[:, n:] - t(g['mdesc1'])).max()) < 5e-5
+    assert np.abs(taps['scores'].cpu().double().numpy() - g['scores']).max() < Z_TOL
     assert np.abs(Z.cpu().double().numpy() - g['Z']).max() < 2e-5
     np.testing.assert_array_equal(m0.cpu().numpy(), g['default_matches0'])
     np.testing.assert_array_equal(m1.cpu().numpy(), g['default_matches1'])

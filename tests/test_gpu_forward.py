@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attention_forms as AF  # noqa: E402
+import layer_forms as LF  # noqa: E402
 from mdgat_matcher_amd import MDGAT, synth  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -967,11 +968,14 @@ def test_weights_beyond_the_f16_range_are_refused():
 
 
 @pytest.mark.parametrize('B,n,m,L,k', [(1, 256, 256, 4, None), (1, 512, 512, 2, [128, None, 64, None]), (3, 100, 77, 2, [16, None, 8, None]),
-                                       (2, 37, 53, 1, []), (1, 1, 9, 1, []), (5, 130, 75, 2, []), (16, 512, 512, 1, [])])
+                                       (2, 37, 53, 1, []), (1, 1, 9, 1, []), (5, 130, 75, 2, []), (16, 512, 512, 1, []),
+                                       (131, 61, 66, 1, [])])
 def test_layer_split_equals_layer_kernel(B, n, m, L, k):
     """csrc/layer_split.hip (32-keypoint workgroups, output channels split over the waves: launches of a few tiles) against
     csrc/layer.hip (a wave owns 16 keypoints): every stage tensor and every output of the forward bit for bit - the two kernels
-    run the same split-f16 products in the same order (mdgat.py:227-232, 246-248, 274, 397)."""
+    run the same split-f16 products in the same order (mdgat.py:227-232, 246-248, 274, 397).  By the launch counters the one side ran
+    split<...> forms only and the other layer<...> forms only: 64-keypoint workgroups (NW = 4) up to 128 tiles of 128 keypoints, and
+    128-keypoint workgroups (NW = 8) at 131 x 61 x 66 (130 tiles; every form: tests/test_gpu_layer_forms.py)."""
     from mdgat_matcher_amd import _lib
     lib = _lib.load()
     cfg = synth.default_config(L=L, sinkhorn_iterations=10) if k is None else synth.default_config(L=L, k=k, sinkhorn_iterations=10)
@@ -991,11 +995,17 @@ def test_layer_split_equals_layer_kernel(B, n, m, L, k):
 
     prev = lib.mdgat_set_layer_split_tiles(1 << 20)      # every launch on the channel-split kernel
     try:
-        split = run()
+        with LF.watch() as ws:
+            split = run()
         lib.mdgat_set_layer_split_tiles(0)               # never
-        whole = run()
+        with LF.watch() as ww:
+            whole = run()
     finally:
         lib.mdgat_set_layer_split_tiles(prev)
+    # 2 L + 1 launches a side (the forward is tapped: one launch of all rows), of the family asked for
+    width = LF.NW4 if B * (n + m) <= 128 * LF.TILE64_TILES else LF.NW8
+    assert sum(ws.launched().values()) == 2 * L + 1 and set(ws.launched()) <= set(LF.SPLIT), ws.launched()
+    assert sum(ww.launched().values()) == 2 * L + 1 and set(ww.launched()) <= set(width), ww.launched()
     net.check()                                         # raises on a range violation
     for a, b in zip(split, whole):
         assert torch.equal(a, b)
