@@ -193,6 +193,7 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
                       float* Z, const mdgat_taps* taps,
                       void* workspace, size_t workspace_bytes, void* stream);
 #define MDGAT_RAGGED_MAX_KEYPOINTS 575   /* keypoints per frame (and per padded slot) of a ragged batch: what the register-resident fp64 Sinkhorn holds */
+#define MDGAT_RAGGED_FP32_MAX_KEYPOINTS 512   /* the same for the fp32-class entries that take counts (mdgat_forward_ragged and its per-op siblings) */
 /* THE COUNTS OF A RAGGED BATCH.  Every ..._ragged entry takes pairs of different sizes in slots padded to Np x Mp and, behind B, Np, Mp, their
  * keypoint counts twice: counts0 / counts1, DEVICE int32 [B], read by the kernels; counts0_host / counts1_host, the same values in HOST
  * memory, on which every check is made before anything is enqueued - one function for all entries (csrc/ragged.hpp), pair by pair:
@@ -221,6 +222,21 @@ int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32
                              const int32_t* counts1_host, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
                              const double* sigma1, const double* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                              float* Z, const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
+/* mdgat_forward on a RAGGED batch: the fp32-class path (an MDGAT_ARITH_FP32 handle, else MDGAT_ERR_BAD_ARG), laid out as above with float
+ * inputs.  The kernels that must know a pair's own size take the counts - the encoder (a keypoint beyond its frame's count reads none of its
+ * inputs and is encoded from zeros), the general attention kernel (mdgat_attention_ragged) and the one-workgroup-per-pair streaming Sinkhorn
+ * with the extraction (mdgat_sinkhorn_extract_ragged); the row-wise launches in between run over the padded rows.  The stream and topk16
+ * attention kernels and the cluster Sinkhorn take no counts, so this is not the uniform forward's kernel selection.
+ *   - Pair b's results depend on the pair alone: bit-identical whatever its position and companions, as long as the slots are equal, and to
+ *     fp32-class rounding those of mdgat_forward on the pair alone; the rule of mdgat.py:465-467 is applied per pair.
+ *   - Beyond a pair's counts: matches -1, scores 0, the rest of its Z slot 0; what the inputs hold there reaches no result and no guard.
+ * Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS, attention_mode not 1 (single-f16 products), taps NULL (else MDGAT_ERR_UNSUPPORTED); the counts
+ * are checked as described at THE COUNTS OF A RAGGED BATCH, against every dynamic layer's k.  workspace: mdgat_workspace_bytes(h, B, Np, Mp);
+ * Z is produced there when the caller wants none.  One unsliced lane on `stream`; no loss. */
+int mdgat_forward_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                         const int32_t* counts1_host, const float* kpts0, const float* sigma0, const float* fpfh0, const float* kpts1,
+                         const float* sigma1, const float* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                         float* Z, const mdgat_taps* taps, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The same forward fed with the loader's raw frame records instead of separate arrays: frames [B][N][37] fp32,
  * one record per keypoint = xyz(3) | saliency(1) | FPFH(33), the layout of the KITTI keypoint files that
@@ -505,6 +521,22 @@ int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const int32_t* coun
                                       float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                       float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* RAGGED batches in fp32: mdgat_sinkhorn / mdgat_sinkhorn_extract on pairs of different sizes, laid out as above with fp32 scores and Z.
+ * They run the one-workgroup-per-pair streaming kernel (the cluster kernel takes no counts), whose ragged instantiation is picked from the
+ * padded sizes alone: pair b's block of Z, its matches and its scores are those of the pair run alone through the uniform entry WITHOUT a
+ * workspace (the streaming kernel), bit for bit, whatever its position and companions; the rule of mdgat.py:465-467 is applied to the pair
+ * alone; beyond its counts the rest of its Z slot is 0, matches -1, scores 0, and what scores holds there is never read.
+ * Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS (else MDGAT_ERR_UNSUPPORTED); then the counts are checked as described at THE COUNTS OF A RAGGED
+ * BATCH.  No synchronisation.  The extraction scans Z: Z_or_null, or - when the caller wants none - a Z produced into `workspace`
+ * (mdgat_sinkhorn_ragged_workspace_bytes, 256-byte aligned; not needed with Z). */
+size_t mdgat_sinkhorn_ragged_workspace_bytes(int B, int Np, int Mp);
+int mdgat_sinkhorn_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                          const int32_t* counts1_host, const float* scores, float bin_score, int iters, float* Z, void* stream);
+int mdgat_sinkhorn_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                  const int32_t* counts1_host, const float* scores, float bin_score, int iters, int mode,
+                                  float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                  float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of log_optimal_transport (mdgat.py:279-308) in fp64: given scores [B][N][M] fp64, the bin score and dZ = dL/dZ
  * [B][N+1][M+1] fp64 (contiguous), writes dscores [B][N][M] and dbin [B] (the bin score's gradient PER PAIR: the sum of dL/dC over
  * the pair's dustbin row and column; a caller with one shared bin score sums them).  N, M <= 2175 (else MDGAT_ERR_UNSUPPORTED),
@@ -620,6 +652,18 @@ size_t mdgat_attention_workspace_bytes(int B, int N, int M);
  * (layout as mdgat_taps.topk_sel). */
 int mdgat_attention_sel(int B, int N, int M, int cross, int topk, const float* qkv, float* msg, uint32_t* sel,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* mdgat_attention_sel on a RAGGED batch: pair b has counts0[b] / counts1[b] keypoints in slots padded to Np / Mp (qkv [B][Np+Mp][384], frame 1
+ * from row Np of a pair; msg and sel laid out for Np, Mp; sel may be NULL).  Pair b's rows depend on its own q/k/v rows alone - not on its
+ * position, its companions or what the slots hold beyond its counts, which no result sees - and are bit-identical in every batch with the
+ * same slots; message rows and masks beyond its counts are zero.  A dynamic layer keeps exactly topk keys per row, all inside the pair's counts
+ * (every key where the source frame has just topk of them).  The instantiation follows the slots alone (never a count): indices 1, 2 for full
+ * attention (<= 128 / <= 512 keys per slot), 4, 5, 6 (11, 12, 13 with sel) for a dynamic layer, which mdgat_attention_launches counts as for a
+ * uniform launch; the stream, topk16, windowed and wide kernels take no counts.  Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS (else
+ * MDGAT_ERR_UNSUPPORTED); then the counts are checked as described at THE COUNTS OF A RAGGED BATCH, against topk.  workspace:
+ * mdgat_attention_workspace_bytes(B, Np, Mp). */
+int mdgat_attention_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                           const int32_t* counts1_host, int cross, int topk, const float* qkv, float* msg, uint32_t* sel,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* Which kernel an attention launch of the fp32 class runs (csrc/attention.hip: launch_attention, which mdgat_attention, mdgat_attention_sel
  * and every layer of the fp32-class forward go through), and with what launch geometry.  The instantiations it can reach:

@@ -112,6 +112,8 @@ SIGNATURES = {
                           [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_forward_f64_ragged': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p] * 6 + [C.c_void_p] * 4 +
                                  [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_forward_ragged': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p] * 6 + [C.c_void_p] * 4 +
+                             [C.c_void_p, C.POINTER(MdgatTaps), C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_forward_frames_ragged': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                               C.c_int] + [C.c_void_p] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_assemble_frames_f64_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -155,6 +157,10 @@ SIGNATURES = {
                                             C.c_void_p]),
     'mdgat_sinkhorn_f64_extract_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_int, C.c_float] +
                                           [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    'mdgat_sinkhorn_ragged_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'mdgat_sinkhorn_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    'mdgat_sinkhorn_extract_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_float] +
+                                      [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     'mdgat_sinkhorn_backward': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_sinkhorn_backward_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -192,6 +198,8 @@ SIGNATURES = {
     'mdgat_attention_qk_probe_sets': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'mdgat_attention_sel': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    'mdgat_attention_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                               [C.c_size_t, C.c_void_p]),
     'mdgat_topk_sel_words': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_pointwise': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

@@ -539,7 +539,21 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
     p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
     p.cnt_min = 0;
-    if (in.counts) {
+    if (in.counts && !f64) {
+        // The ragged plan's fp32-class branch (mdgat_forward_ragged): the encoder, the general attention kernel and the streaming Sinkhorn
+        // take the counts (their RAGGED instantiations) in slots of at most MDGAT_RAGGED_FP32_MAX_KEYPOINTS, the row-wise launches in between run
+        // over the padded rows, which the encoder makes from zeros.  One unsliced lane, no taps, no loss; the single-f16 attention mode has
+        // no kernel that takes counts.
+        const char* who = "mdgat_forward_ragged";
+        if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (in.rec0 || in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (h->cfg.attention_mode == 1) { mdgat_set_error("%s: attention_mode = 1 (single-f16 products) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+            mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+            return MDGAT_ERR_UNSUPPORTED;
+        }
+        if (int rc = mdgat_check_ragged(who, B, N, M, in.counts, nullptr, h->cfg.topk, L2, &p.cnt_min)) return rc;
+    } else if (in.counts) {
         // The ragged plan: the kernels that take per-pair counts are the exact mode's with its fp64 tail on the register-resident Sinkhorn;
         // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); the counts (and the starts into a bank)
         // are checked on their host copies, against the whole k schedule (mdgat_check_ragged).
@@ -614,7 +628,7 @@ struct Fwd {
 // ---- encoders (mdgat.py:392-393), one fused launch ----
 static int encoders32(Fwd& f, const FwdIn& in) {
     const EncoderLaunch e{in.kpts0, in.sigma0, in.fpfh0, in.kpts1, in.sigma1, in.fpfh1, in.rec0, in.rec1, in.normalize_fpfh,
-                          f.h->w.encoder32(), f.ws.x, f.B, f.N, f.M};
+                          f.h->w.encoder32(), f.ws.x, f.B, f.N, f.M, f.cnt0, f.cnt1};
     if (int rc = launch_encoder(e, f.s)) return rc;
     f.mark(MDGAT_PROF_ENCODER);
     return f.tap(f.taps.x_enc, f.ws.x, (size_t)f.R * 128, "tap x_enc");
@@ -762,7 +776,8 @@ static int layers32(Fwd& f) {
     for (int i = f.p.first; i < L2; ++i) {
         const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
         const int kk = h->cfg.topk[i];
-        if (int rc = launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
+        if (int rc = f.cnt0 ? launch_attention_ragged(f.B, f.N, f.M, f.cnt0, f.cnt1, cross, kk, f.q16, f.ws.msg, f.s)
+                            : launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
         LayerLaunch p{};
         p.msg = f.ws.msg; p.do_mlp = 1; p.mlp = h->w.layer32(i);
@@ -788,8 +803,11 @@ static int tail32(Fwd& f, const FwdOut& o) {
     // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
     float* Zout = o.Z ? o.Z : (f.p.cluster32 && !o.loss ? nullptr : ws.Z);
     const SkExtract ex = f.extract(o);
-    if (int rc = launch_sinkhorn(B, N, M, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
-                              f.status, o.Z ? o.Z : ws.Z, sk_clear != 0)) return rc;
+    // (a ragged batch: the streaming kernel with the counts - the cluster kernel takes none - into the caller's Z or the workspace's)
+    if (int rc = f.cnt0 ? launch_sinkhorn_ragged(B, N, M, f.cnt0, f.cnt1, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters,
+                                                 o.Z ? o.Z : ws.Z, &ex, f.s)
+                        : launch_sinkhorn(B, N, M, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
+                                          f.status, o.Z ? o.Z : ws.Z, sk_clear != 0)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const float*>(Zout));
 }
@@ -917,6 +935,26 @@ extern "C" int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, 
                                         size_t workspace_bytes, void* stream) {
     if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1 || !counts0 || !counts1 || !counts0_host || !counts1_host) {
         mdgat_set_error("mdgat_forward_f64_ragged: null input pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    FwdIn in = FwdIn::arrays(kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1);
+    in.counts = RaggedCounts{counts0, counts1, counts0_host, counts1_host};
+    return forward_batched(h, B, Np, Mp, in, matches0, matches1, mscores0, mscores1, Z, taps, workspace, workspace_bytes, stream);
+}
+
+// The same on the fp32-class path (an MDGAT_ARITH_FP32 handle, float inputs): the ragged plan's second branch in plan_forward.  The encoder,
+// the attention kernel and the streaming Sinkhorn take the counts; what the inputs hold beyond them is never read.
+extern "C" int mdgat_forward_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
+                                    const int32_t* counts0_host, const int32_t* counts1_host, const float* kpts0, const float* sigma0,
+                                    const float* fpfh0, const float* kpts1, const float* sigma1, const float* fpfh1, int64_t* matches0,
+                                    int64_t* matches1, float* mscores0, float* mscores1, float* Z, const mdgat_taps* taps, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (!kpts0 || !sigma0 || !fpfh0 || !kpts1 || !sigma1 || !fpfh1 || !counts0 || !counts1 || !counts0_host || !counts1_host) {
+        mdgat_set_error("mdgat_forward_ragged: null input pointer");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    if (h && h->cfg.arithmetic != MDGAT_ARITH_FP32) {
+        mdgat_set_error("mdgat_forward_ragged: the handle needs MDGAT_ARITH_FP32 (an exact-mode handle runs mdgat_forward_f64_ragged)");
         return MDGAT_ERR_BAD_ARG;
     }
     FwdIn in = FwdIn::arrays(kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1);
@@ -1074,6 +1112,53 @@ extern "C" int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, 
                            Z_or_null ? Z_or_null : Z_fallback_or_null);
 }
 
+// ---- the two above on a ragged batch: the streaming kernel's ragged instantiations (sinkhorn.hip) ----
+// the slot limit of the fp32 ragged entries, then the per-pair checks every ragged entry makes (ragged.hpp)
+static int sk_ragged_check(const char* who, int B, int Np, int Mp, int iters, const RaggedCounts& c) {
+    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    return mdgat_check_ragged(who, B, Np, Mp, c, nullptr, nullptr, 0, nullptr);
+}
+
+extern "C" size_t mdgat_sinkhorn_ragged_workspace_bytes(int B, int Np, int Mp) {
+    if (B <= 0 || Np <= 0 || Mp <= 0 || Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return 0;
+    return ((size_t)B * (Np + 1) * (Mp + 1) * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" int mdgat_sinkhorn_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                     const int32_t* counts1_host, const float* scores, float bin_score, int iters, float* Z, void* stream) {
+    const char* who = "mdgat_sinkhorn_ragged";
+    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = sk_ragged_check(who, B, Np, Mp, iters, RaggedCounts{counts0, counts1, counts0_host, counts1_host})) return rc;
+    return launch_sinkhorn_ragged(B, Np, Mp, counts0, counts1, scores, nullptr, bin_score, iters, Z, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_sinkhorn_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                             const int32_t* counts1_host, const float* scores, float bin_score, int iters, int mode,
+                                             float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                             float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_sinkhorn_extract_ragged";
+    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
+    if (int rc = sk_ragged_check(who, B, Np, Mp, iters, RaggedCounts{counts0, counts1, counts0_host, counts1_host})) return rc;
+    if (B == 0) return MDGAT_OK;
+    // the extraction scans Z: the caller's, or one produced into the workspace
+    float* Z = Z_or_null;
+    if (!Z) {
+        if (!workspace || workspace_bytes < mdgat_sinkhorn_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+            mdgat_set_error("%s: without Z the workspace holds it: too small or not 256-byte aligned", who);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        Z = static_cast<float*>(workspace);
+    }
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
+    return launch_sinkhorn_ragged(B, Np, Mp, counts0, counts1, scores, nullptr, bin_score, iters, Z, &ex, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold, int64_t* matches0,
                              int64_t* matches1, float* mscores0, float* mscores1, void* stream) {
     if (!Z || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
@@ -1102,6 +1187,29 @@ extern "C" int mdgat_attention_sel(int B, int N, int M, int cross, int topk, con
     const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, N, M);
     if (int rc = launch_qkv_split(B, N, M, qkv, q16, s)) return rc;
     return launch_attention(B, N, M, cross, topk, q16, msg, s, 0, sel);
+}
+
+// a ragged batch: the counts on the device for the kernel, on the host for the checks made before the launch
+extern "C" int mdgat_attention_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                      const int32_t* counts1_host, int cross, int topk, const float* qkv, float* msg, uint32_t* sel, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_attention_ragged";
+    if (!qkv || !msg || !workspace) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, nullptr)) return rc;
+    if (workspace_bytes < mdgat_attention_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+        mdgat_set_error("%s: workspace too small or not 16-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, Np, Mp);
+    if (int rc = launch_qkv_split(B, Np, Mp, qkv, q16, s)) return rc;      // (over the padded rows: the kernel reads none beyond a pair's counts)
+    return launch_attention_ragged(B, Np, Mp, counts0, counts1, cross, topk, q16, msg, s, sel);
 }
 
 extern "C" int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles) {

@@ -44,7 +44,20 @@ struct AttnArgs {
     // works on part `part` of the query tiles of unit ugroup * 8 + xcd, unit = (pair * 2 + frame) * 4 + head: the parts of a unit share
     // an XCD (round-robin dispatch), so its K and V^T are fetched into one L2 only.  The grid is padded to 8 units.
     int grid_split, grid_units;
+    // RAGGED instantiations of attention_kernel only (device int32 [B]): pair b has cnt0[b] / cnt1[b] keypoints; N, M above are then the padded
+    // sizes, and with them P, the frame offsets, Npad, PP and selW stay those of the slots
+    const int* cnt0;
+    const int* cnt1;
 };
+
+// Upper-tail standard normal quantile on the device, for the RAGGED instantiations: a ragged pair's first probe of the threshold search follows
+// its own k / keys.  Only a search start: the central branch of the launcher's rational approximation, the argument clamped to its range.
+__device__ __forceinline__ float normal_quantile_upper_dev(float p) {
+    const float q = 0.5f - fminf(fmaxf(p, 0.02425f), 0.97575f), r = q * q;
+    const float num = (((((-3.969683028665376e+01f * r + 2.209460984245205e+02f) * r - 2.759285104469687e+02f) * r + 1.383577518672690e+02f) * r - 3.066479806614716e+01f) * r + 2.506628277459239e+00f) * q;
+    const float den = ((((-5.447609879822406e+01f * r + 1.615858368580409e+02f) * r - 1.556989798598866e+02f) * r + 6.680131188771972e+01f) * r - 1.328068155288572e+01f) * r + 1.0f;
+    return num / den;
+}
 
 // parity tap (mdgat_taps.topk_sel): OR `bits` (NB consecutive keys starting at key0, NB | 32) into the row's mask
 __device__ __forceinline__ void tap_keys(uint32_t* row, int key0, unsigned bits) {
@@ -446,10 +459,14 @@ __device__ __forceinline__ void topk_break_ties(f32x16 (&S)[NBLK], float thr, in
 // LARGE = more than 512 keys (full attention only): LDS holds a window of 512 keys that is re-staged for
 //         every query pass; the online softmax carries across windows.
 // Threads: 512 (two waves per SIMD, <= 256 registers) for NBLK <= 8, else 256 (one wave per SIMD).
-template <bool TOPK, int NBLK, bool LARGE, bool TAP = false>
+// RAGGED = per-pair keypoint counts in padded slots (AttnArgs::cnt0 / cnt1): the queries and keys of workgroup (b, side) are the pair's own,
+//         every offset and stride is the slots'; the V^T columns beyond the pair's keys are staged as zeros whatever the slot holds there, and
+//         the message rows beyond its queries are written 0.  What a row gets depends on its pair alone.
+template <bool TOPK, int NBLK, bool LARGE, bool TAP = false, bool RAGGED = false>
 __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void attention_kernel(AttnArgs a) {
     static_assert(TOPK || !TAP, "the selection tap belongs to the dynamic layers");
     static_assert(!(TOPK && LARGE), "dynamic attention needs the whole row in one chunk");
+    static_assert(!(RAGGED && LARGE), "ragged batches: slots of at most 512 keys");
     constexpr int NT = NBLK <= 8 ? 512 : 256;
     extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
     const int tid = threadIdx.x;
@@ -459,11 +476,17 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
     const int head = blockIdx.y;
     const int b = blockIdx.z >> 1, side = blockIdx.z & 1;
     const int P = a.N + a.M;
-    const int nq = side ? a.M : a.N;
     const int q_off = side ? a.N : 0;
     const int src = a.cross ? (1 - side) : side;
-    const int nk = src ? a.M : a.N;
     const int k_off = src ? a.N : 0;
+    int nq = side ? a.M : a.N, nk = src ? a.M : a.N;
+    float zq = a.zq;
+    if constexpr (RAGGED) {
+        const int n0 = __builtin_amdgcn_readfirstlane(a.cnt0[b]), n1 = __builtin_amdgcn_readfirstlane(a.cnt1[b]);
+        nq = side ? n1 : n0;
+        nk = src ? n1 : n0;
+        if (TOPK) zq = normal_quantile_upper_dev(((float)a.topk - 0.5f) / (float)max(n0, n1));      // (as the launcher's, of the pair's own sizes)
+    }
     const int nblk = (nk + 31) >> 5;                    // all blocks of the row
     const int wcap = LARGE ? 16 : nblk;                 // blocks the LDS window holds
     const int VSTR = wcap * 32 + 8;         // V^T row stride in halves: (32 wcap + 8) / 8 is odd -> conflict free
@@ -501,7 +524,20 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
             for (int u = 0; u < 4; ++u) {
                 const int idx = base + u * NT;
                 const int row = idx / cpr, c = idx - row * cpr;
-                if (idx < nv) x[u] = *reinterpret_cast<const f32x4*>(vg + (size_t)row * a.PP + c * 8);
+                if (!RAGGED) {
+                    if (idx < nv) x[u] = *reinterpret_cast<const f32x4*>(vg + (size_t)row * a.PP + c * 8);
+                } else if (idx < nv) {
+                    // the slot's columns beyond the pair's keys are another matter than the zero pads of a uniform batch: not read, zeros
+                    const int left = krem - c * 8;      // keys of this pair in the 8 columns
+                    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (left > 0) x[u] = *reinterpret_cast<const f32x4*>(vg + (size_t)row * a.PP + c * 8);
+                    if (left < 8) {
+                        f16x8 h = __builtin_bit_cast(f16x8, x[u]);
+#pragma unroll
+                        for (int j = 1; j < 8; ++j) h[j] = j < left ? h[j] : (_Float16)0.f;
+                        x[u] = __builtin_bit_cast(f32x4, h);
+                    }
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -602,7 +638,7 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
                 float thr = NEG_INF;
                 if (TOPK) {
                     WaveComm comm;
-                    thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, a.zq, comm);
+                    thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, zq, comm);
                     if (TAP) {      // the TAP build counts first, so that the selection it records is final
                         int c = 0;
 #pragma unroll
@@ -700,6 +736,12 @@ __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void atte
             const int q = qw + row;
             if (q < nq) out[(size_t)q * 128] = (Om[r] + Ox[r]) * inv;
         }
+    }
+    if constexpr (RAGGED) {
+        // this head's 32 columns of the slot's rows beyond the pair's queries, shared among the workgroups of the (pair, frame, head)
+        const int nqs = side ? a.M : a.N;
+        float* out = a.msg + ((size_t)b * P + q_off + nq) * 128 + head * 32;
+        for (int idx = blockIdx.x * NT + tid; idx < (nqs - nq) * 32; idx += gridDim.x * NT) out[(size_t)(idx >> 5) * 128 + (idx & 31)] = 0.f;
     }
 }
 
@@ -1415,6 +1457,50 @@ AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
     const int per_pass = nblk <= 32 ? 64 : 32;
     const int npass = (nk_max + per_pass - 1) / per_pass;
     return AttnPlan{(nblk <= 32 ? ATTN_WIDE4 : ATTN_WIDE8) + (tap ? ATTN_TAP : 0), npass, 1, MDGAT_OK};
+}
+
+// A ragged batch: pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M <= 512 (counts checked by the caller against topk).  The form
+// follows the slots alone - never a count, so a pair's launch geometry does not depend on its companions' sizes: attention_kernel's RAGGED
+// instantiation for the slots' 32-key blocks, a dynamic layer always a dynamic one (a pair whose frame has just k keys keeps them all inside
+// the kernel).  The stream, topk16, windowed and wide kernels take no counts.  Counted under the uniform sibling's form.
+int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
+                            uint32_t* sel) {
+    if (B <= 0) return MDGAT_OK;
+    const int nk_max = N > M ? N : M;
+    if (!cnt0 || !cnt1 || N <= 0 || M <= 0 || topk < 0 || nk_max > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+        mdgat_set_error("attention (ragged): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", N, M, topk, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    const bool dyn = topk > 0, tap = dyn && sel;
+    const int nblk = (nk_max + 31) / 32;
+    const int form = !dyn ? (nblk <= 4 ? ATTN_FULL4 : ATTN_FULL8) : (nblk <= 4 ? ATTN_DYN4 : nblk <= 8 ? ATTN_DYN8 : ATTN_DYN16) + (tap ? ATTN_TAP : 0);
+    const int threads = dyn && nblk > 8 ? 256 : 512;
+    // the query tiles of a (pair, frame, head) over more workgroups only when there are too few units to fill the chip twice (attention_plan)
+    const int qt = (threads / 64) * 32, qtiles = (nk_max + qt - 1) / qt, units = B * 2 * MDGAT_HEADS;
+    int split = (512 + units - 1) / units;
+    split = split > qtiles ? qtiles : split;
+    AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, nblk, 0, 0, cnt0, cnt1};
+    if (sel && dyn) {
+        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, 0, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
+        a.sel = sel;
+    }
+    const size_t lds = ((size_t)nblk * 32 * KROWH + (size_t)64 * (nblk * 32 + 8)) * sizeof(_Float16);
+    auto go = [&](auto kern) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(split, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
+    };
+    switch (form) {
+    case ATTN_FULL4: go(attention_kernel<false, 4, false, false, true>); break;
+    case ATTN_FULL8: go(attention_kernel<false, 8, false, false, true>); break;
+    case ATTN_DYN4: go(attention_kernel<true, 4, false, false, true>); break;
+    case ATTN_DYN8: go(attention_kernel<true, 8, false, false, true>); break;
+    case ATTN_DYN16: go(attention_kernel<true, 16, false, false, true>); break;
+    case ATTN_DYN4 + ATTN_TAP: go(attention_kernel<true, 4, false, true, true>); break;
+    case ATTN_DYN8 + ATTN_TAP: go(attention_kernel<true, 8, false, true, true>); break;
+    default: go(attention_kernel<true, 16, false, true, true>); break;
+    }
+    attention_count_launch(form);
+    return mdgat_check_hip(hipGetLastError(), "attention launch (ragged)");
 }
 
 int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode, uint32_t* sel) {

@@ -141,6 +141,9 @@ struct EncoderLaunch {
     Encoder32 enc;
     float* x;
     int B, N, M;
+    // a ragged batch (device int32 [B], both or neither; arrays, or records that are not normalised): pair b has cnt0[b] / cnt1[b] keypoints in
+    // slots of N / M; a keypoint beyond its frame's count reads none of its inputs and is encoded from zeros
+    const int *cnt0 = nullptr, *cnt1 = nullptr;
 };
 int launch_encoder(const EncoderLaunch& p, hipStream_t s);
 int launch_split_rows_pad(const float* w, _Float16* out, int rows, int Kin, int Kpad, hipStream_t s);
@@ -158,6 +161,11 @@ int launch_qkv_split(int B, int N, int M, const float* qkv, const Qkv16& out, hi
 // mode: mdgat_attention_mode (1 = single-f16 products where implemented)
 // sel (parity tap, may be NULL): the kept keys of a dynamic layer as bit masks [B][4][P][W], W = ceil(max(N, M) / 32)
 int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode = 0, uint32_t* sel = nullptr);
+// The same on a ragged batch: pair b has cnt0[b] / cnt1[b] keypoints (device int32 [B], checked by the caller against topk) in slots of
+// N / M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS.  The general kernel's ragged instantiations, chosen from the slots alone and counted under their
+// uniform siblings' forms; message rows (and tap masks) beyond a pair's counts are zero.
+int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
+                            uint32_t* sel = nullptr);
 // Which instantiation launch_attention runs and its launch geometry (mdgat_attention_plan, include/mdgat_hip.h: the table of indices), and
 // how often each has been launched by this process (mdgat_attention_launches).  Host code only; the plan touches no HIP call.
 enum AttnForm {
@@ -241,6 +249,11 @@ constexpr float MDGAT_F16_GUARD = 6.0e4f;     // f16 max is 65504; the split's h
 int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_score_dev, float bin_score_host,
                     int iters, float* Z, void* ws, size_t ws_bytes, const SkExtract* ex, hipStream_t s, unsigned* status = nullptr,
                     float* Zfb = nullptr, bool slots_cleared = false);
+// A ragged batch on the streaming kernel: pair b has cnt0[b] x cnt1[b] keypoints (device int32 [B], checked by the caller) in slots of
+// N x M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS; its block of Z has the bits of the pair run alone through the streaming kernel, the rest of its
+// slot is 0.  Z is required; ex: the extraction with the same counts (extract_kernel scans Z).
+int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const float* scores, const float* bin_score_dev,
+                           float bin_score_host, int iters, float* Z, const SkExtract* ex, hipStream_t s);
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M);   // 0: the shape does not use the cluster kernel
 size_t mdgat_sinkhorn_ws_bytes_impl(int B, int N, int M);
 

@@ -27,6 +27,9 @@ struct EncArgs {
     const _Float16 *k1s, *k2s, *d0s, *d1s, *els;   // split weights [rows][2][K]: 64x32, 128x64, 64x48, 128x64, 128x256
     float* x;                     // [R][128]
     int B, N, M, R;
+    // the RAGGED instantiation only (device int32 [B]): pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M
+    const int* cnt0;
+    const int* cnt1;
 };
 
 // LDS map (halves)
@@ -64,6 +67,10 @@ template <int K, int ROWS> struct CopyRows {
     }
 };
 
+// RAGGED: per-pair keypoint counts in padded slots (EncArgs::cnt0 / cnt1).  A keypoint beyond its frame's count reads none of its inputs
+// and is encoded from zeros: whatever the caller's tensors hold there, the padded rows of x are finite, and so is everything the row-wise
+// kernels behind make of them.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(ENC_THREADS, 2) void encoder_kernel(EncArgs a) {
     extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
     const int tid = threadIdx.x;
@@ -102,7 +109,13 @@ __global__ __launch_bounds__(ENC_THREADS, 2) void encoder_kernel(EncArgs a) {
     const size_t pi = (size_t)b * nside + n;
     float xyzs[4];
     float f[24];                 // FPFH entries 16 ks + 8 hi + j of this lane, ks = 0..2 (zero beyond 33)
-    {
+    bool padded = false;
+    if constexpr (RAGGED) padded = n >= (f1 ? a.cnt1 : a.cnt0)[b];
+    if (RAGGED && padded) {
+        xyzs[0] = xyzs[1] = xyzs[2] = xyzs[3] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 24; ++i) f[i] = 0.f;
+    } else {
         const float* rec = f1 ? a.rec1 : a.rec0;
         const float* fp;
         if (rec) {
@@ -260,8 +273,17 @@ int launch_encoder(const EncoderLaunch& p, hipStream_t s) {
     a.k1s = e.k1s; a.k2s = e.k2s; a.d0s = e.d0s; a.d1s = e.d1s; a.els = e.els;
     a.x = p.x; a.B = p.B; a.N = p.N; a.M = p.M; a.R = p.B * (p.N + p.M);
     const size_t lds = (size_t)OFF_END * sizeof(_Float16) + 672 * sizeof(float);
+    const dim3 grid((a.R + ENC_THREADS / 2 - 1) / (ENC_THREADS / 2));
+    if (p.cnt0) {
+        if (!p.cnt1 || (p.rec0 && p.normalize)) { mdgat_set_error("encoder (ragged): counts for one frame only, or records to normalise"); return MDGAT_ERR_BAD_ARG; }
+        a.cnt0 = p.cnt0; a.cnt1 = p.cnt1;
+        static std::atomic<unsigned long long> optin_ragged;
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<true>), lds, optin_ragged, "encoder LDS attribute")) return rc;
+        hipLaunchKernelGGL(encoder_kernel<true>, grid, dim3(ENC_THREADS), lds, s, a);
+        return mdgat_check_hip(hipGetLastError(), "encoder launch (ragged)");
+    }
     static std::atomic<unsigned long long> optin;
-    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel), lds, optin, "encoder LDS attribute")) return rc;
-    hipLaunchKernelGGL(encoder_kernel, dim3((a.R + ENC_THREADS / 2 - 1) / (ENC_THREADS / 2)), dim3(ENC_THREADS), lds, s, a);
+    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<false>), lds, optin, "encoder LDS attribute")) return rc;
+    hipLaunchKernelGGL(encoder_kernel<false>, grid, dim3(ENC_THREADS), lds, s, a);
     return mdgat_check_hip(hipGetLastError(), "encoder launch");
 }

@@ -35,6 +35,10 @@ struct SkArgs {
     const unsigned* only_if;
     unsigned* status_fallback;
     const unsigned* pair_flags;
+    // RAGGED instantiations only (device int32 [B]): pair b has cnt0[b] x cnt1[b] keypoints; N, M above are then the padded sizes - the strides of
+    // scores and Z and what the LDS is sized for
+    const int* cnt0;
+    const int* cnt1;
 };
 
 __device__ __forceinline__ float wave_max(float v) {
@@ -61,10 +65,16 @@ __device__ __forceinline__ float wave_lse2(const float* x, int n, float extra, i
     return m + lg2(s);
 }
 
-template <int NC, int NW>
+// RAGGED: per-pair keypoint counts in padded slots (SkArgs::cnt0 / cnt1).  A pair then computes exactly what it computes alone through the
+// instantiation its own M selects: rows, columns, norm, mu, nu and the dustbins are its own, only the strides are the slots'; a lane's column
+// registers beyond the pair's M hold NEG_BIG as they do beyond M in a uniform launch - exp2 gives an exact 0, added last - so a wider NC
+// changes no bit.  The rest of the pair's Z slot is written 0.
+template <int NC, int NW, bool RAGGED = false>
 __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int N = a.N, M = a.M;
+    const int Ns = a.N, Ms = a.M;                // the strides (RAGGED: the padded sizes)
+    int N = Ns, M = Ms;
+    if constexpr (RAGGED) { N = __builtin_amdgcn_readfirstlane(a.cnt0[blockIdx.x]); M = __builtin_amdgcn_readfirstlane(a.cnt1[blockIdx.x]); }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (a.only_if) {
@@ -73,8 +83,8 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
         if (!mine) return;
         if (tid == 0 && a.status_fallback) __hip_atomic_store(a.status_fallback, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    const float* S = a.scores + (size_t)blockIdx.x * N * M;
-    float* Z = a.Z + (size_t)blockIdx.x * (N + 1) * (M + 1);
+    const float* S = a.scores + (size_t)blockIdx.x * Ns * Ms;
+    float* Z = a.Z + (size_t)blockIdx.x * (Ns + 1) * (Ms + 1);
 
     float* u = smem;                 // [N+1]
     float* v = u + (N + 1);          // [M+1]
@@ -111,7 +121,7 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
         for (int c = 0; c < NC; ++c) { cm[c] = NEG_BIG; cs[c] = 0.f; }
 
         for (int i = wave; i < N; i += NW) {
-            const float* row = S + (size_t)i * M;
+            const float* row = S + (size_t)i * Ms;
             float s[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -164,13 +174,21 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
     const float uN = u[N], vM = v[M];
     for (int i = wave; i < N; i += NW) {
         const float ui = u[i];
-        const float* row = S + (size_t)i * M;
-        float* zr = Z + (size_t)i * (M + 1);
+        const float* row = S + (size_t)i * Ms;
+        float* zr = Z + (size_t)i * (Ms + 1);
         for (int j = lane; j < M; j += 64) zr[j] = (row[j] * MDGAT_LOG2E + ui + v[j]) * MDGAT_LN2 - norm;
         if (lane == 0) zr[M] = (alpha + ui + vM) * MDGAT_LN2 - norm;
+        if constexpr (RAGGED)
+            for (int j = M + 1 + lane; j <= Ms; j += 64) zr[j] = 0.f;
     }
-    float* zl = Z + (size_t)N * (M + 1);
+    float* zl = Z + (size_t)N * (Ms + 1);
     for (int j = tid; j <= M; j += NW * 64) zl[j] = (alpha + uN + v[j]) * MDGAT_LN2 - norm;
+    if constexpr (RAGGED) {
+        // the rest of the slot: the dustbin row's tail and the rows below it, which are contiguous
+        float* rest = zl + M + 1;
+        const int nrest = (Ms - M) + (Ns - N) * (Ms + 1);
+        for (int j = tid; j < nrest; j += NW * 64) rest[j] = 0.f;
+    }
 }
 
 
@@ -1080,13 +1098,13 @@ __global__ __launch_bounds__(256) void extract_alldust_fixup(const int64_t* m0, 
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n1; i += (size_t)gridDim.x * 256) s1[i] = 0.f;
 }
 
-template <int NC, int NW>
+template <int NC, int NW, bool RAGGED = false>
 int launch_sk(const SkArgs& a, int B, hipStream_t s) {
     const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)NW * a.M) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_kernel<NC, NW>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_kernel<NC, NW, RAGGED>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return mdgat_check_hip(e, "sinkhorn LDS attribute");
-    hipLaunchKernelGGL((sinkhorn_kernel<NC, NW>), dim3(B), dim3(NW * 64), lds, s, a);
+    hipLaunchKernelGGL((sinkhorn_kernel<NC, NW, RAGGED>), dim3(B), dim3(NW * 64), lds, s, a);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn launch");
 }
 
@@ -1129,6 +1147,27 @@ static int launch_streaming(const SkArgs& a, int B, hipStream_t s) {
     if (M <= 2048 && N <= 4096) return launch_sk<32, 8>(a, B, s);
     mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", M);
     return MDGAT_ERR_UNSUPPORTED;
+}
+
+// A ragged batch (pairs of cnt0[b] x cnt1[b] keypoints in slots of N x M): the streaming kernel's RAGGED instantiation for the slot, picked
+// from the padded sizes alone - a wider NC than a pair's own M would select gives the pair the same bits - then, with `ex`, extract_kernel
+// with the same counts.  Z is required: the extraction scans it.  The counts have been checked by the caller (mdgat_check_ragged).
+int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const float* scores, const float* bin_score_dev, float bin_score_host,
+                           int iters, float* Z, const SkExtract* ex, hipStream_t s) {
+    if (B <= 0) return MDGAT_OK;
+    if (!cnt0 || !cnt1 || !scores || !Z) { mdgat_set_error("sinkhorn (ragged): null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn (ragged): bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
+    if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+        mdgat_set_error("sinkhorn (ragged): padded sizes %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    const SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr, cnt0, cnt1};
+    const int rc = M <= 64 ? launch_sk<1, 16, true>(a, B, s) : M <= 128 ? launch_sk<2, 16, true>(a, B, s)
+                 : M <= 256 ? launch_sk<4, 16, true>(a, B, s) : launch_sk<8, 16, true>(a, B, s);
+    if (rc || !ex) return rc;
+    ExArgs xa{Z, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1,
+              ex->matched, ex->matched_token, cnt0, cnt1};
+    return launch_extract_impl(B, N, M, xa, s, ex->defer_alldust != 0);
 }
 
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return (N > 2048 || M > 2048) ? 0 : slots_bytes(N, M) + flags_bytes(B); }

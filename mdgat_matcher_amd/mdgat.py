@@ -201,6 +201,13 @@ class MDGAT(nn.Module):
         # raising.  MDGAT_TRAIN_FORWARD=1 in the environment replaces the default (off) for modules whose config does not carry the key.
         tf = self.config.get('train_forward')
         self.train_forward = bool(tf) if tf is not None else os.environ.get('MDGAT_TRAIN_FORWARD') == '1'
+        # not a reference key: which modules forward_ragged / evaluate_ragged take.  'exact' (default): the exact mode only;
+        #   'auto': a module whose forward is fp32-class (not exact()) runs the library's fp32-class ragged forward (mdgat_forward_ragged:
+        #   slots of at most 512 keypoints), an exact one its own as before.
+        # MDGAT_RAGGED_ARITHMETIC in the environment replaces the default for modules whose config does not carry the key.
+        self.ragged_arithmetic = str(self.config.get('ragged_arithmetic') or os.environ.get('MDGAT_RAGGED_ARITHMETIC') or 'exact')
+        if self.ragged_arithmetic not in ('exact', 'auto'):
+            raise ValueError(f"ragged_arithmetic={self.ragged_arithmetic!r}: expected 'exact' or 'auto'")
         f64_layers = self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -509,6 +516,12 @@ class MDGAT(nn.Module):
         }
 
     RAGGED_MAX_KEYPOINTS = 575      # what the register-resident fp64 Sinkhorn holds (csrc/sinkhorn_f64.hip)
+    RAGGED_FP32_MAX_KEYPOINTS = 512     # the slots of the fp32-class ragged forward (include/mdgat_hip.h: MDGAT_RAGGED_FP32_MAX_KEYPOINTS)
+
+    def _ragged_fp32(self) -> bool:
+        """Does a ragged batch of this module, as it stands, run the fp32-class ragged forward?  Opt-in (config['ragged_arithmetic'] =
+        'auto'), and then what ``forward`` runs decides: a module that is not ``exact()``."""
+        return getattr(self, 'ragged_arithmetic', 'exact') == 'auto' and not self.exact()
 
     @staticmethod
     def _early_out(kpts0, kpts1):
@@ -547,26 +560,33 @@ class MDGAT(nn.Module):
     def _ragged_counts_checked(self, h0, h1, Np, Mp):
         """the kernels' limits on the counts of a ragged batch in slots of Np x Mp"""
         kmax = max([int(k) for k in self._topk_schedule()] + [0])
+        limit = self.RAGGED_FP32_MAX_KEYPOINTS if self._ragged_fp32() else self.RAGGED_MAX_KEYPOINTS
         for b in range(int(h0.numel())):
             n, m = int(h0[b]), int(h1[b])
-            if n > self.RAGGED_MAX_KEYPOINTS or m > self.RAGGED_MAX_KEYPOINTS:
-                raise ValueError(f'pair {b} has {n} x {m} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
+            if n > limit or m > limit:
+                raise ValueError(f'pair {b} has {n} x {m} keypoints: ragged batches hold at most {limit} per frame')
             if min(n, m) < max(kmax, 1):
                 raise ValueError(f'pair {b} has {n} x {m} keypoints: fewer than a dynamic layer keeps (k={kmax}; torch.topk raises in the reference)')
             if n > Np or m > Mp:
                 raise ValueError(f'pair {b} has {n} x {m} keypoints in slots of {Np} x {Mp}')
-        if Np > self.RAGGED_MAX_KEYPOINTS or Mp > self.RAGGED_MAX_KEYPOINTS:
-            raise ValueError(f'slots of {Np} x {Mp} keypoints: ragged batches hold at most {self.RAGGED_MAX_KEYPOINTS} per frame')
+        if Np > limit or Mp > limit:
+            raise ValueError(f'slots of {Np} x {Mp} keypoints: ragged batches hold at most {limit} per frame')
 
-    def _ragged_forward(self, inputs, return_Z):
+    def _ragged_forward(self, inputs, return_Z, fp32_entry=False):
         """One ragged forward through the library: the PADDED device outputs (matches -1 and scores 0 beyond a pair's counts), the host
         counts and - in the dustbin modes, with the call's one synchronisation - which pairs matched anything (mdgat.py:465, per pair).
         ``inputs()`` is the runner's own preparation, made behind the mode refusals: a ``_RaggedCall``.  Returns (the outputs' tuple, the
-        call's ``kept``)."""
-        if not self.exact() or self.bin_score.dtype != torch.float64:
-            raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'")
+        call's ``kept``).  ``fp32_entry``: the runner has an fp32-class entry for a module that opted in (``_ragged_fp32``)."""
+        fp32 = fp32_entry and self._ragged_fp32()
+        if not fp32 and (not self.exact() or self.bin_score.dtype != torch.float64):
+            raise NotImplementedError("ragged batches run in the exact mode only: a float64 module (net.double()) without config['arithmetic']='fp32'"
+                                      " (forward_ragged and evaluate_ragged take an fp32-class module with config['ragged_arithmetic']='auto')")
         if self.training or getattr(self, 'eval_loss', False):
-            raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)')
+            raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)' if not fp32 else
+                                      'ragged batches run in eval() mode, without the evaluation loss (eval_loss)')
+        if fp32 and (self.descriptor == 'FPFH_gloabal' or self.attention_dtype != 'fp32'):
+            raise NotImplementedError("the fp32-class ragged forward takes descriptor 'FPFH' or 'FPFH_only' and attention_dtype='fp32': the pooled "
+                                      "encoder of 'FPFH_gloabal' and the single-f16 attention kernels take no per-pair counts")
         call = inputs()
         dev, shape = call.dev, call.shape
         st = self._state_for(dev)
@@ -592,15 +612,16 @@ class MDGAT(nn.Module):
             if not probe.is_cuda:
                 raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP device; there is no CPU fallback')
             dev = probe.device
-            ins = [packed[k].to(device=dev, dtype=torch.float64).contiguous()
+            fp32 = self._ragged_fp32()
+            ins = [packed[k].to(device=dev, dtype=torch.float32 if fp32 else torch.float64).contiguous()
                    for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
             if self.descriptor == 'FPFH_only':          # keypoints and saliency give the shapes only (as in _run)
                 for i in (0, 1, 3, 4):
                     ins[i] = torch.zeros_like(ins[i])
             cnt = ops._ragged_counts(packed, B, dev)
-            return _RaggedCall(dev, (B, Np, Mp), (cnt.h0, cnt.h1), 'mdgat_forward_f64_ragged', (*cnt.ptrs(), *[t.data_ptr() for t in ins]),
-                               behind_Z=(None,), kept=(cnt, ins))        # (behind Z: no taps)
-        return self._ragged_forward(inputs, return_Z)[0]
+            return _RaggedCall(dev, (B, Np, Mp), (cnt.h0, cnt.h1), 'mdgat_forward_ragged' if fp32 else 'mdgat_forward_f64_ragged',
+                               (*cnt.ptrs(), *[t.data_ptr() for t in ins]), behind_Z=(None,), kept=(cnt, ins))        # (behind Z: no taps)
+        return self._ragged_forward(inputs, return_Z, fp32_entry=True)[0]
 
     def _run_frames_ragged(self, bank, counts, starts, normalize, return_Z, want_kpts=False):
         """``_ragged_forward`` fed from a bank of records (``ops.pack_frames``): the chunk's host counts and starts (``ops.frames_chunk``, no
@@ -711,7 +732,14 @@ class MDGAT(nn.Module):
 
         The exact mode only (a float64 module in eval() mode, no ``eval_loss``): ``NotImplementedError`` otherwise.  ``ValueError`` for a
         frame of more than 575 keypoints or of fewer than a dynamic layer's k, and for tensors that are not [B, N, 3] / [B, N] /
-        [B, N, 33] with one B and count vectors of B entries."""
+        [B, N, 33] with one B and count vectors of B entries.
+
+        With ``config['ragged_arithmetic'] = 'auto'`` (or ``MDGAT_RAGGED_ARITHMETIC=auto``) a module whose forward is fp32-class (not
+        ``exact()``) runs the library's fp32-class ragged forward instead (``mdgat_forward_ragged``): frames of at most 512 keypoints,
+        descriptors 'FPFH' and 'FPFH_only', ``attention_dtype='fp32'``, eval() mode without ``eval_loss`` (``NotImplementedError`` /
+        ``ValueError`` before anything touches a device).  Per pair the same keys, dtypes and shapes as ``forward`` on the pair alone,
+        computed by the kernels that take per-pair counts: to fp32-class rounding of ``forward``, and bit-identical whatever the pair's
+        position and companions as long as the slots are equal."""
         if isinstance(pairs_or_packed, dict):
             return self._ragged_dicts(self._run_ragged(pairs_or_packed, return_Z), return_Z)
         pairs = list(pairs_or_packed)

@@ -35,42 +35,59 @@ def _match_outputs(B, N, M, device, want_Z=False):
             torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=device) if want_Z else None)
 
 
-def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool = False) -> torch.Tensor:
+def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool = False, counts=None) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308): scores [B, N, M] -> Z [B, N+1, M+1] (fp32).
 
     N, M <= 2048 run on the register-resident cluster kernel (128 x 512 tiles per workgroup; needs a small workspace,
-    allocated here); ``streaming=True`` selects the one-workgroup-per-pair streaming kernel."""
+    allocated here); ``streaming=True`` selects the one-workgroup-per-pair streaming kernel.
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch in slots of N x M <= 512 - pair b is
+    ``scores[b, :counts0[b], :counts1[b]]``, the rest of its slot is never read.  It runs on the streaming kernel:
+    ``Z[b, :counts0[b]+1, :counts1[b]+1]`` has the bits of the pair run alone with ``streaming=True`` (its dustbins at row
+    ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0."""
     _need_cuda(scores)
     s = scores.to(torch.float32).contiguous()
     B, N, M = s.shape
     Z = torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=s.device)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
+        name, lead, _keep = _entry('mdgat_sinkhorn', counts, B, s.device)
+        need = 0 if streaming or counts is not None else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
         ws = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
-        _lib.check(lib.mdgat_sinkhorn(B, N, M, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(),
-                                      ws.data_ptr() if ws is not None else None, need, _stream(s)), 'mdgat_sinkhorn')
+        tail = () if counts is not None else (ws.data_ptr() if ws is not None else None, need)
+        _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), *tail, _stream(s)), name)
     return Z
 
 
 def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2,
-                     want_Z: bool = False, streaming: bool = False):
+                     want_Z: bool = False, streaming: bool = False, counts=None):
     """fp32 Sinkhorn + match extraction as the forward runs them (launch_sinkhorn with an extraction request): (matches0, matches1,
     mscores0, mscores1[, Z]).  On the cluster kernel (N, M <= 2048) the arg-maxes are decided in its epilogue and Z is written only
-    if wanted; ``streaming=True`` passes no workspace: the one-workgroup-per-pair kernel writes Z and the extraction kernel scans it."""
+    if wanted; ``streaming=True`` passes no workspace: the one-workgroup-per-pair kernel writes Z and the extraction kernel scans it.
+
+    ``counts`` as in ``sinkhorn``: pair b's matches and scores are those of the pair run alone with ``streaming=True`` (no match: -1; the
+    rule of mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0."""
     _need_cuda(scores)
     s = scores.to(torch.float32).contiguous()
     B, N, M = s.shape
     m0, m1, s0, s1, Zbuf = _match_outputs(B, N, M, s.device, want_Z=True)     # (Z, or the buffer lent for redone pairs)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
-        ws = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
-        z_out = want_Z or not need
-        _lib.check(lib.mdgat_sinkhorn_extract(B, N, M, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
-                                              m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Zbuf.data_ptr() if z_out else None,
-                                              None if z_out else Zbuf.data_ptr(), ws.data_ptr() if ws is not None else None, need, _stream(s)),
-                   'mdgat_sinkhorn_extract')
+        name, lead, _keep = _entry('mdgat_sinkhorn_extract', counts, B, s.device)
+        if counts is not None:
+            # the ragged entry scans the Z it is given, or - when none is wanted - one it produces into a workspace
+            need = 0 if want_Z else lib.mdgat_sinkhorn_ragged_workspace_bytes(B, N, M)
+            _buf, ws_ptr, _ = _workspace(need, s.device) if need else (None, None, 0)
+            z_out, lent = want_Z, ()
+        else:
+            need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
+            _buf = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
+            ws_ptr = _buf.data_ptr() if need else None
+            z_out = want_Z or not need
+            lent = (None if z_out else Zbuf.data_ptr(),)
+        _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
+                                      m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Zbuf.data_ptr() if z_out else None, *lent,
+                                      ws_ptr, need, _stream(s)), name)
     return (m0, m1, s0, s1, Zbuf) if want_Z else (m0, m1, s0, s1)
 
 
@@ -433,10 +450,14 @@ def topk_sel_to_masks(sel: torch.Tensor, B: int, N: int, M: int, cross: bool):
     return bits[:, :, :N, :nk0], bits[:, :, N:, :nk1]
 
 
-def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False):
+def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None):
     """attention / dynamic_attention (mdgat.py:190-210).  qkv [B, N+M, 3, 4, 32] -> message [B, N+M, 128]
     (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks).
-    The fp32-class kernels have no backward: the result never carries a grad_fn (``attention_f64`` is the differentiable one)."""
+    The fp32-class kernels have no backward: the result never carries a grad_fn (``attention_f64`` is the differentiable one).
+
+    ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b has ``counts0[b]`` / ``counts1[b]`` keypoints in
+    slots of N / M <= 512 rows; its rows are those of its own q/k/v rows alone, bit-identical wherever it stands in a batch of the same slots;
+    message rows and masks beyond its counts are zero / False, and what ``qkv`` holds there reaches no result."""
     _need_cuda(qkv)
     x = qkv.to(torch.float32).contiguous()
     B, P = x.shape[0], x.shape[1]
@@ -447,9 +468,10 @@ def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, ret
         need = lib.mdgat_attention_workspace_bytes(B, N, M)
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if return_selection else None
-        _lib.check(lib.mdgat_attention_sel(B, N, M, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
-                                           sel.data_ptr() if sel is not None else None,
-                                           ws.data_ptr(), need, _stream(x)), 'mdgat_attention')
+        name, lead, _keep = _entry('mdgat_attention', counts, B, x.device)
+        _lib.check(getattr(lib, name if counts is not None else 'mdgat_attention_sel')(
+            B, N, M, *lead, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(), sel.data_ptr() if sel is not None else None,
+            ws.data_ptr(), need, _stream(x)), name)
     if return_selection:
         return msg, topk_sel_to_masks(sel, B, N, M, cross)
     return msg
