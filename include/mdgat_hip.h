@@ -489,6 +489,37 @@ int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_s
                            int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
                            float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which kernels an fp32 Sinkhorn launch runs (csrc/sinkhorn.hip: launch_sinkhorn, which mdgat_sinkhorn, mdgat_sinkhorn_extract and the
+ * fp32-class forward go through, and launch_sinkhorn_ragged behind their ragged entry points), and with what launch parameters.  The
+ * instantiations, as mdgat_sinkhorn_launches counts them:
+ *    0 scaling<false,4>    sinkhorn_scaling_kernel<false, 4>:  one column slab, <= 4 row slabs (N <= 512, M <= 512)
+ *    1 scaling<false,16>   sinkhorn_scaling_kernel<false, 16>: one column slab, 5 .. 16 row slabs (N <= 2048, M <= 512)
+ *    2 scaling<true,16>    sinkhorn_scaling_kernel<true, 16>:  2 .. 4 column slabs (M <= 2048, N <= 2048)
+ *    3 .. 8   stream<1,16> stream<2,16> stream<4,16> stream<8,16> stream<16,8> stream<32,8>: sinkhorn_kernel<NC, NW> launched on its own,
+ *             M <= 64 | 128 | 256 | 512 | 1024 | 2048 (the last two: N <= 4096)
+ *    9 .. 12  their RAGGED twins <1,16> .. <8,16> (the ragged entry points; from the padded M alone)
+ *   13 gated  a streaming kernel launched behind a cluster launch, gated on its error word and per-pair range flags (which one: the
+ *             plan's streaming index)
+ *   14 extract  extract_kernel (every caller: the fp32 and fp64 Sinkhorn paths and mdgat_extract)
+ * mdgat_sinkhorn_plan: the path - 0 the cluster kernel, 1 the streaming kernel alone, -1 nothing is launched (an empty batch) or the
+ * launcher refuses (M > 2048, or N > 4096 with M > 512; more workgroups per pair than `cus`; a ragged slot over
+ * MDGAT_RAGGED_FP32_MAX_KEYPOINTS) - for B pairs of N x M on a device of `cus` compute units.  workspace / workspace_bytes: what the call
+ * would pass (the address is compared and never dereferenced: NULL, too few bytes for mdgat_sinkhorn_workspace_bytes or an address that
+ * is not 256-byte aligned select the streaming kernel); fallback_buffer != 0: a Z is asked for or a buffer is lent (else the cluster launch
+ * is cooperative and nothing is launched behind it); ragged != 0: the ragged entry points (no workspace is used).  out (optional):
+ * [0] the scaling index (0 .. 2, -1: none), [1] the streaming index (3 .. 12: launched alone on path 1 - counted under it - or gated behind
+ * the cluster launch on path 0 - counted under 13; -1: none), [2] GR and [3] GC (row slabs of 128 rows, column slabs of 512 columns: GR * GC
+ * workgroups per pair), [4] ngroups (pairs in flight), [5] xcd_map (the partners of a pair placed on one XCD, the grid padded to a multiple
+ * of 8 groups), [6] the grid of the first launch, [7] cooperative != 0.  A pure function of its arguments: no device is needed or touched;
+ * the launchers take every one of these values from the same code.
+ * mdgat_sinkhorn_launches: counts[i] = launches of index i by this process so far, on any device and stream (relaxed atomic counters,
+ * never reset: read them before and after a call and subtract). */
+#define MDGAT_SINKHORN_COUNTERS 15
+#define MDGAT_SINKHORN_PLAN_WORDS 8
+int mdgat_sinkhorn_plan(int B, int N, int M, int cus, const void* workspace, size_t workspace_bytes, int fallback_buffer, int ragged,
+                        int32_t out[MDGAT_SINKHORN_PLAN_WORDS]);
+void mdgat_sinkhorn_launches(uint64_t counts[MDGAT_SINKHORN_COUNTERS]);
+
 /* The same in fp64 - the reference's own arithmetic (mdgat.py:279-308 run in float64, test.py:193) - on fp64 scores: Z [B][N+1][M+1]
  * fp64; N, M <= 2175.  Frames of at most 575 keypoints run in one launch with the couplings held in registers; larger ones stream them
  * from memory, one launch per iteration (csrc/sinkhorn_f64.hip).  workspace: mdgat_sinkhorn_f64_workspace_bytes, 256-byte aligned. */

@@ -178,6 +178,8 @@ SIGNATURES = {
     'mdgat_sinkhorn_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_sinkhorn_extract': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_sinkhorn_plan': (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    'mdgat_sinkhorn_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_extract': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 4 + [C.c_void_p]),
     'mdgat_attention': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

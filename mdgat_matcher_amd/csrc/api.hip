@@ -1223,6 +1223,21 @@ extern "C" void mdgat_attention_launches(uint64_t counts[MDGAT_ATTENTION_FORMS])
     if (counts) attention_launch_counts(counts);
 }
 
+extern "C" int mdgat_sinkhorn_plan(int B, int N, int M, int cus, const void* workspace, size_t workspace_bytes, int fallback_buffer, int ragged,
+                                   int32_t out[MDGAT_SINKHORN_PLAN_WORDS]) {
+    const bool usable = !ragged && B > 0 && N > 0 && M > 0 && sinkhorn_workspace_usable(B, N, M, workspace, workspace_bytes);
+    const SkPlan p = sinkhorn_plan(B, N, M, cus, usable, fallback_buffer != 0, ragged != 0);
+    if (out) {
+        const int32_t w[MDGAT_SINKHORN_PLAN_WORDS] = {p.scaling, p.stream, p.GR, p.GC, p.ngroups, p.xcd_map, p.grid, p.cooperative};
+        for (int i = 0; i < MDGAT_SINKHORN_PLAN_WORDS; ++i) out[i] = w[i];
+    }
+    return p.path;
+}
+
+extern "C" void mdgat_sinkhorn_launches(uint64_t counts[MDGAT_SINKHORN_COUNTERS]) {
+    if (counts) sinkhorn_launch_counts(counts);
+}
+
 extern "C" int mdgat_layer_plan(int R, int N, int M, int do_mlp, int mode3, int* workgroups, int* keypoints_per_workgroup, int* v_store) {
     const LayerPlan p = layer_plan(R, N, M, do_mlp, mode3);
     if (workgroups) *workgroups = p.workgroups;

@@ -254,6 +254,32 @@ int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_s
 // slot is 0.  Z is required; ex: the extraction with the same counts (extract_kernel scans Z).
 int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const float* scores, const float* bin_score_dev,
                            float bin_score_host, int iters, float* Z, const SkExtract* ex, hipStream_t s);
+// What launch_sinkhorn and launch_sinkhorn_ragged choose (mdgat_sinkhorn_plan, include/mdgat_hip.h: the table of indices), and how often each
+// instantiation has been launched by this process (mdgat_sinkhorn_launches).  Host code only; the plan touches no HIP call.
+enum SkForm {
+    SK_SCALING_4 = 0, SK_SCALING_16, SK_SCALING_2D,                                               // sinkhorn_scaling_kernel<false, 4>, <false, 16>, <true, 16>
+    SK_STREAM_1, SK_STREAM_2, SK_STREAM_4, SK_STREAM_8, SK_STREAM_16, SK_STREAM_32,               // sinkhorn_kernel<NC, NW>, launched on its own
+    SK_RAGGED_1, SK_RAGGED_2, SK_RAGGED_4, SK_RAGGED_8,                                           // ... its RAGGED twins
+    SK_GATED,                                                                                     // a streaming kernel gated behind a cluster launch
+    SK_EXTRACT,                                                                                   // extract_kernel
+    SK_COUNTERS = MDGAT_SINKHORN_COUNTERS
+};
+enum SkPath { SK_PATH_NONE = -1, SK_PATH_CLUSTER = 0, SK_PATH_STREAMING = 1 };
+struct SkPlan {
+    int path;           // SkPath; SK_PATH_NONE: nothing is launched (an empty batch), or rc says why not
+    int scaling;        // SK_SCALING_* of a cluster launch, else -1
+    int stream;         // SK_STREAM_* / SK_RAGGED_*: launched on its own (streaming path) or gated behind the cluster launch; -1: none
+    int GR, GC;         // cluster: row slabs of 128 rows x column slabs of 512 columns, one workgroup each
+    int ngroups;        // cluster: pairs in flight
+    int xcd_map;        // cluster: the partners of a pair share blockIdx % 8, the grid padded to 8 groups per slot
+    int grid;           // workgroups of the (first) launch
+    int cooperative;    // cluster: hipLaunchCooperativeKernel
+    int rc;             // MDGAT_ERR_UNSUPPORTED where the launcher refuses (the message is the launcher's)
+};
+// workspace: sinkhorn_workspace_usable; fallback_buffer: a Z, or one lent for redone pairs; ragged: launch_sinkhorn_ragged
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged);
+bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes);   // large enough for the cluster kernel and 256-byte aligned
+void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]);
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M);   // 0: the shape does not use the cluster kernel
 size_t mdgat_sinkhorn_ws_bytes_impl(int B, int N, int M);
 

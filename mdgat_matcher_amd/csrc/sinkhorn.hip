@@ -16,6 +16,7 @@
 // per-wave column partials are merged through LDS -> v_j.  Everything is kept in the base-2 log domain
 // (potentials carry a factor log2(e)) so each element costs v_exp_f32 without a pre-multiply.
 #include "common.hpp"
+#include <atomic>
 #include <cstdlib>
 
 namespace {
@@ -1135,18 +1136,91 @@ size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M) {
 
 static int launch_extract_impl(int B, int N, int M, ExArgs a, hipStream_t s, bool defer_alldust = false);
 
-// the one-workgroup-per-pair streaming kernel: any shape up to M = 2048, no workspace
-static bool streaming_supported(int N, int M) { return M <= 512 || (M <= 2048 && N <= 4096); }
-static int launch_streaming(const SkArgs& a, int B, hipStream_t s) {
-    const int N = a.N, M = a.M;
-    if (M <= 64) return launch_sk<1, 16>(a, B, s);
-    if (M <= 128) return launch_sk<2, 16>(a, B, s);
-    if (M <= 256) return launch_sk<4, 16>(a, B, s);
-    if (M <= 512) return launch_sk<8, 16>(a, B, s);
-    if (M <= 1024 && N <= 4096) return launch_sk<16, 8>(a, B, s);
-    if (M <= 2048 && N <= 4096) return launch_sk<32, 8>(a, B, s);
-    mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", M);
-    return MDGAT_ERR_UNSUPPORTED;
+// ---- the launchers' choices as a pure function (mdgat_sinkhorn_plan; no HIP call), and the launches counted by it ----
+static std::atomic<unsigned long long> sinkhorn_launch_count[SK_COUNTERS];
+static void sinkhorn_count_launch(int index) { sinkhorn_launch_count[index].fetch_add(1, std::memory_order_relaxed); }
+void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]) {
+    for (int i = 0; i < SK_COUNTERS; ++i) counts[i] = sinkhorn_launch_count[i].load(std::memory_order_relaxed);
+}
+
+bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes) {
+    const size_t need = sinkhorn_cluster_workspace_bytes(B, N, M);
+    return need && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0;
+}
+
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged) {
+    SkPlan p{SK_PATH_NONE, -1, -1, 0, 0, 0, 0, 0, 0, MDGAT_OK};
+    if (B <= 0 || N <= 0 || M <= 0) return p;
+    // the one-workgroup-per-pair streaming kernel: any shape up to M = 2048, no workspace
+    const int nc = M <= 64 ? 0 : M <= 128 ? 1 : M <= 256 ? 2 : M <= 512 ? 3 : (M <= 1024 && N <= 4096) ? 4 : (M <= 2048 && N <= 4096) ? 5 : -1;
+    if (ragged) {
+        // the RAGGED instantiation for the slot, picked from the padded sizes alone (launch_sinkhorn_ragged)
+        if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
+        p.path = SK_PATH_STREAMING;
+        p.stream = SK_RAGGED_1 + nc;
+        p.grid = B;
+        return p;
+    }
+    if (!workspace || N > 2048 || M > 2048) {
+        if (nc < 0) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
+        p.path = SK_PATH_STREAMING;
+        p.stream = SK_STREAM_1 + nc;
+        p.grid = B;
+        return p;
+    }
+    sk_tiling(N, M, p.GR, p.GC);
+    const int P = p.GR * p.GC;                     // workgroups per pair, one per CU
+    int ngroups = num_cu / P;
+    if (ngroups > sk_max_groups(N, M)) ngroups = sk_max_groups(N, M);
+    if (ngroups > B) ngroups = B;
+    p.ngroups = ngroups;
+    if (ngroups < 1) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
+    // Placement: the workgroups of a pair exchange through L2 every iteration, which is fast and steady only inside one XCD
+    // (workgroup i runs on XCD i % 8): group g takes the workgroups with blockIdx % 8 == g % 8, and the grid is padded to a
+    // multiple of 8 groups - the surplus workgroups leave at once.  (Before: only batches that are multiples of 8 were placed,
+    // others ran their partners on four different XCDs - 1.0 ms against an erratic 1.0 ... 3.5 ms per forward at B = 2 ... 4 -
+    // and a batch of 12 ran as 8 + 4.)  A pair's workgroups must fit the 32 CUs of an XCD next to the other groups placed there.
+    const int ng8 = (ngroups + 7) & ~7;
+    p.xcd_map = P * (ng8 / 8) <= num_cu / 8;
+    p.grid = p.xcd_map ? ng8 * P : ngroups * P;
+    p.path = SK_PATH_CLUSTER;
+    p.scaling = p.GC > 1 ? SK_SCALING_2D : p.GR > 4 ? SK_SCALING_16 : SK_SCALING_4;
+    // The workgroups of a pair wait for each other, so all of them must become resident.  A workgroup takes a whole CU
+    // (512 threads x 256 registers), and ngroups * P <= num_cu by construction: every workgroup gets a CU as soon as the
+    // stragglers of earlier launches leave.  A plain launch therefore suffices when this launch has the device to itself, and
+    // it starts 20-30 us sooner than hipLaunchCooperativeKernel (measured at B = 64: 430 -> 397 us for launch + 100
+    // iterations).  It is NOT assumed: workgroups are dispatched in order (per XCD), so of every concurrent cluster launch at
+    // most one pair per XCD is incomplete and the complete ones finish and make room - but enough concurrent launches (other
+    // streams, other processes) could leave every CU with a workgroup whose partners cannot be dispatched.  The spins are
+    // therefore bounded, a workgroup that gives up raises the launch's error word, and the streaming kernel launched right
+    // behind (gated on that word: it leaves at once otherwise, ~3 us) redoes the launch one workgroup per pair - slow, never
+    // wrong.  Without a fallback buffer (no Z and none lent) the launch is cooperative: the runtime then checks co-residency.
+    const bool can_fall_back = fallback_buffer && nc >= 0;
+    p.cooperative = !can_fall_back || ngroups * P > num_cu;
+    if (can_fall_back) p.stream = SK_STREAM_1 + nc;
+    return p;
+}
+
+// the streaming kernel in the plan's instantiation; gated: behind a cluster launch (a.only_if), counted apart
+static int launch_streaming(const SkArgs& a, int B, int form, bool gated, hipStream_t s) {
+    int rc;
+    switch (form) {
+    case SK_STREAM_1: rc = launch_sk<1, 16>(a, B, s); break;
+    case SK_STREAM_2: rc = launch_sk<2, 16>(a, B, s); break;
+    case SK_STREAM_4: rc = launch_sk<4, 16>(a, B, s); break;
+    case SK_STREAM_8: rc = launch_sk<8, 16>(a, B, s); break;
+    case SK_STREAM_16: rc = launch_sk<16, 8>(a, B, s); break;
+    case SK_STREAM_32: rc = launch_sk<32, 8>(a, B, s); break;
+    case SK_RAGGED_1: rc = launch_sk<1, 16, true>(a, B, s); break;
+    case SK_RAGGED_2: rc = launch_sk<2, 16, true>(a, B, s); break;
+    case SK_RAGGED_4: rc = launch_sk<4, 16, true>(a, B, s); break;
+    case SK_RAGGED_8: rc = launch_sk<8, 16, true>(a, B, s); break;
+    default:
+        mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", a.M);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (!rc) sinkhorn_count_launch(gated ? SK_GATED : form);
+    return rc;
 }
 
 // A ragged batch (pairs of cnt0[b] x cnt1[b] keypoints in slots of N x M): the streaming kernel's RAGGED instantiation for the slot, picked
@@ -1157,13 +1231,13 @@ int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1
     if (B <= 0) return MDGAT_OK;
     if (!cnt0 || !cnt1 || !scores || !Z) { mdgat_set_error("sinkhorn (ragged): null pointer"); return MDGAT_ERR_BAD_ARG; }
     if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn (ragged): bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
+    const SkPlan p = sinkhorn_plan(B, N, M, 0, false, true, true);
+    if (p.rc) {
         mdgat_set_error("sinkhorn (ragged): padded sizes %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
-        return MDGAT_ERR_UNSUPPORTED;
+        return p.rc;
     }
     const SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr, cnt0, cnt1};
-    const int rc = M <= 64 ? launch_sk<1, 16, true>(a, B, s) : M <= 128 ? launch_sk<2, 16, true>(a, B, s)
-                 : M <= 256 ? launch_sk<4, 16, true>(a, B, s) : launch_sk<8, 16, true>(a, B, s);
+    const int rc = launch_streaming(a, B, p.stream, false, s);
     if (rc || !ex) return rc;
     ExArgs xa{Z, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1,
               ex->matched, ex->matched_token, cnt0, cnt1};
@@ -1172,23 +1246,10 @@ int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1
 
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return (N > 2048 || M > 2048) ? 0 : slots_bytes(N, M) + flags_bytes(B); }
 
-static int launch_scaling(int B, int N, int M, const float* scores, const float* alpha_dev, float alpha_host, int iters,
-                          float* Z, void* ws, int num_cu, const SkExtract* ex, unsigned* status, float* Zfb, bool slots_cleared, hipStream_t s) {
-    int GR, GC;
-    sk_tiling(N, M, GR, GC);
-    const int P = GR * GC;                         // workgroups per pair, one per CU
-    int ngroups = num_cu / P;
-    if (ngroups > sk_max_groups(N, M)) ngroups = sk_max_groups(N, M);
-    if (ngroups > B) ngroups = B;
-    // Placement: the workgroups of a pair exchange through L2 every iteration, which is fast and steady only inside one XCD
-    // (workgroup i runs on XCD i % 8): group g takes the workgroups with blockIdx % 8 == g % 8, and the grid is padded to a
-    // multiple of 8 groups - the surplus workgroups leave at once.  (Before: only batches that are multiples of 8 were placed,
-    // others ran their partners on four different XCDs - 1.0 ms against an erratic 1.0 ... 3.5 ms per forward at B = 2 ... 4 -
-    // and a batch of 12 ran as 8 + 4.)  A pair's workgroups must fit the 32 CUs of an XCD next to the other groups placed there.
-    const int ng8 = (ngroups + 7) & ~7;
-    const bool xcd_map = P * (ng8 / 8) <= num_cu / 8;
-    const int grid = xcd_map ? ng8 * P : ngroups * P;
-    if (ngroups < 1) { mdgat_set_error("sinkhorn: %d workgroups per pair do not fit the device", P); return MDGAT_ERR_UNSUPPORTED; }
+static int launch_scaling(const SkPlan& pl, int B, int N, int M, const float* scores, const float* alpha_dev, float alpha_host, int iters,
+                          float* Z, void* ws, const SkExtract* ex, unsigned* status, float* Zfb, bool slots_cleared, hipStream_t s) {
+    const int GR = pl.GR, GC = pl.GC, ngroups = pl.ngroups;
+    if (pl.rc) { mdgat_set_error("sinkhorn: %d workgroups per pair do not fit the device", GR * GC); return pl.rc; }
     const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
     if (!slots_cleared) {    // (the forward has the score kernel clear them)
         if (int rc = mdgat_check_hip(hipMemsetAsync(ws, 0, 256 + per_group * ngroups, s), "memset(sinkhorn slots)")) return rc;
@@ -1200,7 +1261,7 @@ static int launch_scaling(int B, int N, int M, const float* scores, const float*
         if (int rc = mdgat_check_hip(hipMemsetAsync(ws, 1, sizeof(unsigned), s), "memset(sinkhorn error word)")) return rc;
     SksArgs a{scores, alpha_dev, alpha_host, Z, reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + 256),
               static_cast<unsigned*>(ws), reinterpret_cast<unsigned*>(static_cast<char*>(ws) + slots_bytes(N, M)),
-              status ? status + MDGAT_STATUS_RANGE : nullptr, B, N, M, iters, ngroups, GR, GC, xcd_map ? 1 : 0, -1, nullptr, nullptr, nullptr, nullptr};
+              status ? status + MDGAT_STATUS_RANGE : nullptr, B, N, M, iters, ngroups, GR, GC, pl.xcd_map, -1, nullptr, nullptr, nullptr, nullptr};
     if (ex) {
         char* p = static_cast<char*>(ws) + slots_bytes(N, M) + flags_bytes(B);
         a.ext_mode = ex->mode;
@@ -1210,28 +1271,20 @@ static int launch_scaling(int B, int N, int M, const float* scores, const float*
         a.cbest_val = reinterpret_cast<float*>(p);
     }
     void* args[] = {&a};
-    const void* kern = GC > 1 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<true, 16>)
-                     : GR > 4 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 16>)
-                              : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 4>);
-    // The workgroups of a pair wait for each other, so all of them must become resident.  A workgroup takes a whole CU
-    // (512 threads x 256 registers), and ngroups * P <= num_cu by construction: every workgroup gets a CU as soon as the
-    // stragglers of earlier launches leave.  A plain launch therefore suffices when this launch has the device to itself, and
-    // it starts 20-30 us sooner than hipLaunchCooperativeKernel (measured at B = 64: 430 -> 397 us for launch + 100
-    // iterations).  It is NOT assumed: workgroups are dispatched in order (per XCD), so of every concurrent cluster launch at
-    // most one pair per XCD is incomplete and the complete ones finish and make room - but enough concurrent launches (other
-    // streams, other processes) could leave every CU with a workgroup whose partners cannot be dispatched.  The spins are
-    // therefore bounded, a workgroup that gives up raises the launch's error word, and the streaming kernel launched right
-    // behind (gated on that word: it leaves at once otherwise, ~3 us) redoes the launch one workgroup per pair - slow, never
-    // wrong.  Without a fallback buffer (no Z and none lent) the launch is cooperative: the runtime then checks co-residency.
+    const void* kern = pl.scaling == SK_SCALING_2D ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<true, 16>)
+                     : pl.scaling == SK_SCALING_16 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 16>)
+                                                  : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 4>);
+    // plain or cooperative, and whether the gated streaming kernel follows: sinkhorn_plan
     float* zfb = Z ? Z : Zfb;
-    const bool can_fall_back = zfb != nullptr && streaming_supported(N, M);
+    const bool can_fall_back = pl.stream >= 0;
     hipError_t e;
-    if (!can_fall_back || ngroups * P > num_cu) e = hipLaunchCooperativeKernel(kern, dim3(grid), dim3(SKS_THREADS), args, 0, s);
-    else e = hipLaunchKernel(kern, dim3(grid), dim3(SKS_THREADS), args, 0, s);
+    if (pl.cooperative) e = hipLaunchCooperativeKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s);
+    else e = hipLaunchKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s);
     if (int rc = mdgat_check_hip(e, "sinkhorn scaling launch")) return rc;
+    sinkhorn_count_launch(pl.scaling);
     if (can_fall_back) {
         SkArgs f{scores, alpha_dev, alpha_host, zfb, N, M, iters, a.error_word, status ? status + MDGAT_STATUS_SK_FALLBACK : nullptr, a.pair_flags};
-        if (int rc = launch_streaming(f, B, s)) return rc;
+        if (int rc = launch_streaming(f, B, pl.stream, true, s)) return rc;
     }
     if (ex) {
         // (header words 2, 3 of the workspace: the all-dustbin counters of the extraction, cleared with the slots)
@@ -1253,14 +1306,12 @@ int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_s
     if (B <= 0) return MDGAT_OK;
     if (!Z && !ex) { mdgat_set_error("sinkhorn: nothing to compute (no Z, no extraction)"); return MDGAT_ERR_BAD_ARG; }
     if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    const size_t need = sinkhorn_cluster_workspace_bytes(B, N, M);
-    if (need && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0) {
-        const int num_cu = mdgat_cu_count();
-        return launch_scaling(B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, num_cu, ex, status, Zfb, slots_cleared, s);
-    }
+    const bool usable = sinkhorn_workspace_usable(B, N, M, ws, ws_bytes);
+    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, Z || Zfb, false);
+    if (usable) return launch_scaling(p, B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, ex, status, Zfb, slots_cleared, s);
     if (!Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
     SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr};
-    const int rc = launch_streaming(a, B, s);
+    const int rc = launch_streaming(a, B, p.stream, false, s);
     if (rc || !ex) return rc;
     ExArgs xa{Z, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1,
               ex->matched, ex->matched_token};
@@ -1280,6 +1331,7 @@ static int launch_extract_impl(int B, int N, int M, ExArgs a, hipStream_t s, boo
     const size_t lds = (size_t)(2 * (N + M) + 4) * sizeof(float);
     hipLaunchKernelGGL(extract_kernel, dim3(B), dim3(1024), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "extract launch")) return rc;
+    sinkhorn_count_launch(SK_EXTRACT);
     if (defer_alldust || a.alldust_counters || a.cnt0) return MDGAT_OK;      // (counters, or a ragged batch: the kernel applied the rule itself)
     return launch_alldust_fixup(B, N, M, a.mode, a.m0, a.s1, s);
 }

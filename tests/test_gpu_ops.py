@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attention_forms as AF  # noqa: E402
+import sinkhorn_forms as SF  # noqa: E402
 from mdgat_matcher_amd import _lib, ops  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -562,14 +563,23 @@ def test_sinkhorn_512_golden(golden_dir):
     assert np.abs(Z[:, :, -1] - g['sk_512x512_Z_lastcol']).max() < 1e-4
 
 
+def _sk_plan(B, N, M, streaming=False):
+    """What the launchers choose for an ops.sinkhorn call on this device (sinkhorn_forms.assert_launched compares the counters with it)."""
+    return SF.plan(B, N, M, cus=torch.cuda.get_device_properties(0).multi_processor_count, workspace=not streaming)
+
+
 @pytest.mark.parametrize('N,M,iters', [(1, 1, 3), (3, 200, 10), (130, 65, 25), (256, 256, 20), (300, 513, 30), (700, 900, 10),
                                        (64, 64, 0)])
 def test_sinkhorn_vs_oracle(N, M, iters):
     rs = np.random.RandomState(N * 3 + M)
     s = torch.from_numpy(rs.standard_normal((3, N, M)) * 4.0)
     ref = O.log_optimal_transport(s, 0.7, iters)
-    for streaming in (False, True):     # cluster kernel (N, M <= 512) and streaming kernel
-        Z = ops.sinkhorn(s.to(DEV), 0.7, iters, streaming=streaming).cpu().double()
+    for streaming in (False, True):     # cluster kernel (with the gated streaming kernel behind it) and streaming kernel
+        p = _sk_plan(3, N, M, streaming)
+        assert p.path == (SF.STREAMING if streaming else SF.CLUSTER)
+        with SF.watch() as w:
+            Z = ops.sinkhorn(s.to(DEV), 0.7, iters, streaming=streaming).cpu().double()
+        SF.assert_launched(w, p, (N, M, streaming))
         assert (Z - ref).abs().max() < 1e-4, streaming
 
 
@@ -582,10 +592,21 @@ def test_sinkhorn_wide_dynamic_range(N, M, iters, scale):
     rs = np.random.RandomState(N + M + iters)
     s = torch.from_numpy(rs.standard_normal((2, N, M)) * scale + 50.0)
     ref = O.log_optimal_transport(s, 0.37, iters)
+    # EVERY pair of all four cases (512 x 128, 512 x 512, 300 x 200, 1024 x 512) has entries below 2^-100 of their row maximum: the
+    # range test flags it, and what the cluster call returns is the gated streaming kernel's result, bit for bit - the scaling form's
+    # own result is never compared here, and no fold fires (tests/test_sinkhorn_scaling_ref.py runs the restatement on these inputs).
+    # The scaling form's folds and its denormal re-read are tested in tests/test_gpu_sinkhorn_forms.py.
+    got = {}
     for streaming in (False, True):
-        Z = ops.sinkhorn(s.to(DEV), 0.37, iters, streaming=streaming).cpu().double()
+        p = _sk_plan(2, N, M, streaming)
+        with SF.watch() as w:
+            Z = ops.sinkhorn(s.to(DEV), 0.37, iters, streaming=streaming)
+        SF.assert_launched(w, p, (N, M, streaming))
+        got[streaming] = Z
+        Z = Z.cpu().double()
         assert torch.isfinite(Z).all(), streaming
         assert (Z - ref).abs().max() < 1e-4 * max(1.0, float(ref.abs().max()) / 100), (streaming, float((Z - ref).abs().max()))
+    assert torch.equal(got[False], got[True])
 
 
 @pytest.mark.parametrize('B,N,M,wide', [(5, 512, 512, (1,)), (9, 300, 400, (0, 7)), (3, 1024, 700, (2,)), (66, 512, 512, (13, 40))])
@@ -598,12 +619,20 @@ def test_sinkhorn_range_fallback_is_per_pair(B, N, M, wide):
     s = torch.randn(B, N, M, device=DEV, generator=g) * 3
     for w in wide:
         s[w] = s[w] * 14 + 50.0                    # spread over ~250 units: far beyond 100 octaves below the row maximum
-    Z = ops.sinkhorn(s, 0.8, 20)
-    Zs = ops.sinkhorn(s, 0.8, 20, streaming=True)
+    p = _sk_plan(B, N, M)
+    assert p.path == SF.CLUSTER and p.scaling == ('scaling<true,16>' if M > 512 else 'scaling<false,4>')
+    with SF.watch() as w:
+        Z = ops.sinkhorn(s, 0.8, 20)
+    SF.assert_launched(w, p, 'the cluster kernel and the gated streaming kernel behind it')
+    with SF.watch() as w:
+        Zs = ops.sinkhorn(s, 0.8, 20, streaming=True)
+    SF.assert_launched(w, p.stream, 'the streaming kernel on its own')
     torch.cuda.synchronize()
     assert torch.isfinite(Z).all()
     for b in sorted(set(wide) | {0, B - 1, B // 2}):
-        alone = ops.sinkhorn(s[b:b + 1].contiguous(), 0.8, 20)
+        with SF.watch() as w:
+            alone = ops.sinkhorn(s[b:b + 1].contiguous(), 0.8, 20)
+        SF.assert_launched(w, _sk_plan(1, N, M), b)
         assert torch.equal(alone[0], Z[b]), b
         if b in wide:
             assert torch.equal(Z[b], Zs[b]), b      # redone by the streaming kernel
@@ -623,10 +652,18 @@ def test_sinkhorn_fallback_after_a_lost_partner(B, N, M, monkeypatch):
     from its Z run for real: same Z as the streaming kernel on its own (bit for bit: it IS that kernel), 1e-4 from the
     oracle, and the cluster path again once the hook is off."""
     s = torch.randn(B, N, M, device=DEV, generator=torch.Generator(DEV).manual_seed(N + M)) * 3
-    Zs = ops.sinkhorn(s, 0.8, 25, streaming=True)
-    Zc = ops.sinkhorn(s, 0.8, 25)
+    p = _sk_plan(B, N, M)
+    assert p.path == SF.CLUSTER and p.scaling == ('scaling<true,16>' if M > 512 else 'scaling<false,4>') and not p.cooperative
+    with SF.watch() as w:
+        Zs = ops.sinkhorn(s, 0.8, 25, streaming=True)
+    SF.assert_launched(w, p.stream, 'the streaming kernel on its own')
+    with SF.watch() as w:
+        Zc = ops.sinkhorn(s, 0.8, 25)
+    SF.assert_launched(w, p, 'the cluster kernel')
     monkeypatch.setenv('MDGAT_SK_FORCE_FALLBACK', '1')
-    Zf = ops.sinkhorn(s, 0.8, 25)
+    with SF.watch() as w:
+        Zf = ops.sinkhorn(s, 0.8, 25)
+    SF.assert_launched(w, p, 'the same two launches with the error word set: the gated kernel runs for real')
     torch.cuda.synchronize()
     monkeypatch.delenv('MDGAT_SK_FORCE_FALLBACK')
     assert torch.equal(Zf, Zs)
@@ -645,8 +682,18 @@ def test_sinkhorn_cluster_matches_streaming(B, N, M):
     (more pairs than resident groups: the persistent loop; ragged shapes: the masks; batches that are not multiples of 8:
     the grid padded to 8 groups for the XCD placement, surplus workgroups leaving at once; 2048 x 2048: no placement)."""
     s = torch.randn(B, N, M, device=DEV, generator=torch.Generator(DEV).manual_seed(B + N)) * 3
-    Zc = ops.sinkhorn(s, 1.0, 30)
-    Zs = ops.sinkhorn(s, 1.0, 30, streaming=True)
+    p = _sk_plan(B, N, M)
+    GR, GC = -(-N // 128), -(-M // 512)
+    assert (p.path, p.GR, p.GC) == (SF.CLUSTER, GR, GC)
+    assert p.scaling == ('scaling<true,16>' if GC > 1 else 'scaling<false,16>' if GR > 4 else 'scaling<false,4>')
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert p.xcd_map == ((N, M) != (2048, 2048)) and p.ngroups == min(B, 64, 256 // (GR * GC))
+    with SF.watch() as w:
+        Zc = ops.sinkhorn(s, 1.0, 30)
+    SF.assert_launched(w, p, 'the cluster kernel')
+    with SF.watch() as w:
+        Zs = ops.sinkhorn(s, 1.0, 30, streaming=True)
+    SF.assert_launched(w, p.stream, 'the streaming kernel on its own')
     assert torch.isfinite(Zc).all()
     assert (Zc - Zs).abs().max() < 2e-5
 

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import sinkhorn_forms as SF  # noqa: E402
 from mdgat_matcher_amd import _lib, ops  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -26,6 +27,8 @@ SETS = {
     'A32': (((40, 33), (17, 64), (64, 17), (65, 48), (8, 8), (31, 32), (33, 97)), 20, 32.0, 3.0, 27.0),
 }
 UNMATCHED = {'A32': 4}
+# the RAGGED instantiation each set's slots select (from the padded M alone): one of the four per set
+RAGGED_FORM = {'s64': 'stream<1,16>,RAGGED', 'A32': 'stream<2,16>,RAGGED', 's256': 'stream<4,16>,RAGGED', 's512': 'stream<8,16>,RAGGED'}
 
 
 def _cnt(counts):
@@ -65,7 +68,11 @@ def test_ragged_sinkhorn_equals_every_pair_alone_and_the_oracle(name):
     log_optimal_transport within 1e-4."""
     counts, iters, alpha, _, _ = SETS[name]
     s, alone = _alone(name)
-    Z = ops.sinkhorn(s.to(DEV), alpha, iters, counts=_cnt(counts))
+    p = SF.plan(len(counts), s.shape[1], s.shape[2], ragged=True)
+    assert p.path == SF.STREAMING and p.stream == RAGGED_FORM[name] and sorted(RAGGED_FORM.values()) == sorted(SF.RAGGED)
+    with SF.watch() as w:
+        Z = ops.sinkhorn(s.to(DEV), alpha, iters, counts=_cnt(counts))
+    SF.assert_launched(w, p, name)
     for b, (n, m) in enumerate(counts):
         assert torch.equal(Z[b, :n + 1, :m + 1], alone[b][0][0]), (name, b)
         rest = Z[b].clone()
@@ -85,7 +92,9 @@ def test_ragged_extraction_equals_every_pair_alone(name):
     s, alone = _alone(name)
     for mode in range(4):
         for want_Z in (True, False):
-            got = ops.sinkhorn_extract(s.to(DEV), alpha, iters, mode=mode, match_threshold=THR, want_Z=want_Z, counts=_cnt(counts))
+            with SF.watch() as w:
+                got = ops.sinkhorn_extract(s.to(DEV), alpha, iters, mode=mode, match_threshold=THR, want_Z=want_Z, counts=_cnt(counts))
+            SF.assert_launched(w, {RAGGED_FORM[name]: 1, SF.EXTRACT: 1}, (name, mode, want_Z))
             m0, m1, s0, s1 = got[:4]
             for b, (n, m) in enumerate(counts):
                 a0, a1, as0, as1, aZ = alone[b][1][mode]
