@@ -199,8 +199,9 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  * memory, on which every check is made before anything is enqueued - one function for all entries (csrc/ragged.hpp), pair by pair:
  * 1 <= counts0[b] <= Np and 1 <= counts1[b] <= Mp; where the entry runs dynamic attention, no k exceeds min(counts0[b], counts1[b])
  * (torch.topk raises in the reference); where it reads a bank of records (starts0 / starts1, DEVICE int64 [B], and starts0_host /
- * starts1_host), 0 <= starts[b] and starts[b] + counts[b] <= rows.  Else MDGAT_ERR_BAD_ARG naming the first offending pair; so for a
- * null count or start vector. */
+ * starts1_host: mdgat_forward_frames_ragged on a handle of either arithmetic, mdgat_assemble_frames_f64_ragged,
+ * mdgat_assemble_frames_train_f64), 0 <= starts[b] and starts[b] + counts[b] <= rows.  Else MDGAT_ERR_BAD_ARG naming the first offending
+ * pair; so for a null count or start vector. */
 /* mdgat_forward_f64 on a RAGGED batch: B pairs of different sizes in one call (the evaluation scripts run one pair per call because no two
  * frames hold the same number of keypoints - test.py:132; padding is no way out: padded keypoints change every softmax, every top-k and
  * the optimal transport).  Pair b has counts0[b] x counts1[b] keypoints and is stored in a slot padded to Np x Mp: kpts0 [B][Np][3], sigma0
@@ -217,7 +218,12 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  * The counts are checked as described at THE COUNTS OF A RAGGED BATCH above, against every dynamic layer's k.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
  * f64_sinkhorn not MDGAT_F64_SINKHORN_OFF, f64_layers automatic, mdgat_set_f64_sinkhorn_form not 1 (else MDGAT_ERR_UNSUPPORTED); an fp32
  * handle is MDGAT_ERR_BAD_ARG.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
- * The ragged mdgat_forward_frames is mdgat_forward_frames_ragged below; there is no ragged loss. */
+ * The ragged mdgat_forward_frames is mdgat_forward_frames_ragged below; there is no ragged loss.
+ * One more handle is taken: the one that runs the ENCODERS ALONE in fp64 - f64_layers = MDGAT_F64_ENCODERS_ONLY, f64_sinkhorn =
+ * MDGAT_F64_SINKHORN_OFF, the pooled encoder loaded (mdgat_load_pooled_encoder_f64; what a float32 'FPFH_gloabal' module creates).  Its
+ * batch runs the fp64 assemble kernel and the pooled encoder with the counts (the frame maximum over a pair's own keypoints), the hand-over,
+ * and behind it mdgat_forward_ragged's kernels: that entry's results (to fp32-class rounding of the pair alone, bit-identical whatever the
+ * pair's position and companions in equal slots) and that entry's limits - Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS, attention_mode not 1. */
 int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                              const int32_t* counts1_host, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
                              const double* sigma1, const double* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
@@ -232,7 +238,8 @@ int mdgat_forward_f64_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32
  *   - Beyond a pair's counts: matches -1, scores 0, the rest of its Z slot 0; what the inputs hold there reaches no result and no guard.
  * Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS, attention_mode not 1 (single-f16 products), taps NULL (else MDGAT_ERR_UNSUPPORTED); the counts
  * are checked as described at THE COUNTS OF A RAGGED BATCH, against every dynamic layer's k.  workspace: mdgat_workspace_bytes(h, B, Np, Mp);
- * Z is produced there when the caller wants none.  One unsliced lane on `stream`; no loss. */
+ * Z is produced there when the caller wants none.  One unsliced lane on `stream`; no loss.  The same plan fed from a bank of raw records:
+ * mdgat_forward_frames_ragged on an MDGAT_ARITH_FP32 handle, below. */
 int mdgat_forward_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                          const int32_t* counts1_host, const float* kpts0, const float* sigma0, const float* fpfh0, const float* kpts1,
                          const float* sigma1, const float* fpfh1, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
@@ -262,7 +269,12 @@ int mdgat_forward_frames(mdgat_handle* h, int B, int N, int M, const float* fram
  *     (mdgat_async_status), as in mdgat_forward_frames.
  *   - kpts0_out [B][Np][3] / kpts1_out [B][Mp][3] fp32 (optional, each on its own): the keypoints as they lie in the
  *     records, zeros beyond the counts - what mdgat_gt_matches_ragged and mdgat_eval_metrics_ragged take.
- * Exact mode only (an fp32 handle is MDGAT_ERR_BAD_ARG), Np, Mp <= 575, no taps.  workspace: mdgat_workspace_bytes(h, B, Np, Mp). */
+ * Np, Mp <= 575, no taps.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).
+ * The entry follows the handle, as mdgat_forward_frames does.  On an MDGAT_ARITH_FP32 handle it runs mdgat_forward_ragged's plan with that
+ * entry's results and limits (Np, Mp <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS, attention_mode not 1): the encoder kernel's bank form reads the
+ * records itself - no assemble pass, no staging copy - with the same normalisation, the same guard and the same kpts0_out / kpts1_out, and
+ * hands the layers bit for bit what mdgat_forward_ragged gets from the float32 values of mdgat_assemble_frames_f64_ragged.  On the fp64
+ * handle that runs the encoders alone (mdgat_forward_f64_ragged, its last paragraph) the assemble kernel runs in front of that plan. */
 int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
                                 const int32_t* counts0_host, const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
                                 const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0, const float* rec1,

@@ -539,20 +539,26 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
     p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
     p.cnt_min = 0;
-    if (in.counts && !f64) {
-        // The ragged plan's fp32-class branch (mdgat_forward_ragged): the encoder, the general attention kernel and the streaming Sinkhorn
-        // take the counts (their RAGGED instantiations) in slots of at most MDGAT_RAGGED_FP32_MAX_KEYPOINTS, the row-wise launches in between run
+    // An fp64 handle that runs the encoders ALONE in fp64 - f64_layers = MDGAT_F64_ENCODERS_ONLY, f64_sinkhorn off, the pooled encoder
+    // loaded: what a float32 'FPFH_gloabal' module creates - hands over to the fp32-class kernels right behind them (p.first == 0): its
+    // ragged batches run the fp32-class branch below behind head64's ragged assemble kernels and the pooled encoder, whose frame maximum
+    // is taken over a pair's own counts.  (An exact handle with an fp32-class tail keeps the refusal of the branch behind.)
+    const bool enc_only64 = f64 && !p.tail64 && p.first == 0 && h->pool64 && h->cfg.f64_layers < 0 && h->cfg.f64_sinkhorn < 0;
+    if (in.counts && (!f64 || enc_only64)) {
+        // The ragged plan's fp32-class branch (mdgat_forward_ragged; mdgat_forward_frames_ragged on an MDGAT_ARITH_FP32 handle): the encoder,
+        // the general attention kernel and the streaming Sinkhorn take the counts (their RAGGED instantiations; out of a bank the encoder's
+        // BANK one, which reads the records itself) in slots of at most MDGAT_RAGGED_FP32_MAX_KEYPOINTS, the row-wise launches in between run
         // over the padded rows, which the encoder makes from zeros.  One unsliced lane, no taps, no loss; the single-f16 attention mode has
-        // no kernel that takes counts.
-        const char* who = "mdgat_forward_ragged";
+        // no kernel that takes counts.  The counts - and the starts into a bank - are checked on their host copies before anything is enqueued.
+        const char* who = in.bank ? "mdgat_forward_frames_ragged" : f64 ? "mdgat_forward_f64_ragged" : "mdgat_forward_ragged";
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
-        if (in.rec0 || in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (in.rec0 && !in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
         if (h->cfg.attention_mode == 1) { mdgat_set_error("%s: attention_mode = 1 (single-f16 products) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
         if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
             mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
             return MDGAT_ERR_UNSUPPORTED;
         }
-        if (int rc = mdgat_check_ragged(who, B, N, M, in.counts, nullptr, h->cfg.topk, L2, &p.cnt_min)) return rc;
+        if (int rc = mdgat_check_ragged(who, B, N, M, in.counts, in.bank ? &in.bank : nullptr, h->cfg.topk, L2, &p.cnt_min)) return rc;
     } else if (in.counts) {
         // The ragged plan: the kernels that take per-pair counts are the exact mode's with its fp64 tail on the register-resident Sinkhorn;
         // the batch runs unsliced on the caller's stream (p.lanes above, like a call with taps); the counts (and the starts into a bank)
@@ -627,8 +633,13 @@ struct Fwd {
 
 // ---- encoders (mdgat.py:392-393), one fused launch ----
 static int encoders32(Fwd& f, const FwdIn& in) {
-    const EncoderLaunch e{in.kpts0, in.sigma0, in.fpfh0, in.kpts1, in.sigma1, in.fpfh1, in.rec0, in.rec1, in.normalize_fpfh,
-                          f.h->w.encoder32(), f.ws.x, f.B, f.N, f.M, f.cnt0, f.cnt1};
+    EncoderLaunch e{in.kpts0, in.sigma0, in.fpfh0, in.kpts1, in.sigma1, in.fpfh1, in.rec0, in.rec1, in.normalize_fpfh,
+                    f.h->w.encoder32(), f.ws.x, f.B, f.N, f.M, f.cnt0, f.cnt1};
+    if (in.bank) {      // a ragged chunk out of a bank (mdgat_forward_frames_ragged): the encoder's bank form reads the records itself
+        e.start0 = in.bank.start0; e.start1 = in.bank.start1;
+        e.kp0_out = in.kp0_out; e.kp1_out = in.kp1_out;
+        e.guard = f.guard();
+    }
     if (int rc = launch_encoder(e, f.s)) return rc;
     f.mark(MDGAT_PROF_ENCODER);
     return f.tap(f.taps.x_enc, f.ws.x, (size_t)f.R * 128, "tap x_enc");
@@ -969,7 +980,9 @@ static RaggedStarts ragged_starts(const int64_t* s0, const int64_t* s1, const in
     return RaggedStarts{ll(s0), ll(s1), ll(h0), ll(h1), rows0, rows1};
 }
 
-// The same fed from a bank of raw records: the ragged assemble kernel in front, everything behind it as above.
+// The same fed from a bank of raw records; the entry follows the handle, as mdgat_forward_frames does.  An exact-mode handle (and the fp64
+// handle that runs the encoders alone): the ragged assemble kernel in front, everything behind it as above.  An MDGAT_ARITH_FP32 handle:
+// mdgat_forward_ragged's plan, the encoder's bank form reading the records itself.
 extern "C" int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1,
                                            const int32_t* counts0_host, const int32_t* counts1_host, const int64_t* starts0, const int64_t* starts1,
                                            const int64_t* starts0_host, const int64_t* starts1_host, const float* rec0, int64_t rows0,
@@ -982,7 +995,6 @@ extern "C" int mdgat_forward_frames_ragged(mdgat_handle* h, int B, int Np, int M
         return MDGAT_ERR_BAD_ARG;
     }
     if (rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: negative record count", who); return MDGAT_ERR_BAD_ARG; }
-    if (h && h->cfg.arithmetic != MDGAT_ARITH_FP64) { mdgat_set_error("%s: the handle needs MDGAT_ARITH_FP64 (ragged batches run in the exact mode only)", who); return MDGAT_ERR_BAD_ARG; }
     FwdIn in;
     in.rec0 = rec0; in.rec1 = rec1; in.normalize_fpfh = normalize_fpfh;
     in.counts = RaggedCounts{counts0, counts1, counts0_host, counts1_host};

@@ -144,6 +144,14 @@ struct EncoderLaunch {
     // a ragged batch (device int32 [B], both or neither; arrays, or records that are not normalised): pair b has cnt0[b] / cnt1[b] keypoints in
     // slots of N / M; a keypoint beyond its frame's count reads none of its inputs and is encoded from zeros
     const int *cnt0 = nullptr, *cnt1 = nullptr;
+    // a ragged chunk out of a bank of records (device int64 [B], both or neither, with the counts): rec0 / rec1 are the bank's [rows][37],
+    // keypoint n of frame f of pair b is record start_f[b] + n - checked by the caller (mdgat_check_ragged); `normalize` is the loader's
+    // float32 arithmetic to the bit (fpfh_norm.hpp).  kp0_out [B][N][3] / kp1_out [B][M][3] (optional): the keypoints as they lie in the
+    // records, zeros beyond the counts.  guard (optional, host-mapped): raised for a non-finite word or, under normalize, an all-zero FPFH
+    // row among a pair's own records.  Records no pair points at are never read.
+    const long long *start0 = nullptr, *start1 = nullptr;
+    float *kp0_out = nullptr, *kp1_out = nullptr;
+    unsigned* guard = nullptr;
 };
 int launch_encoder(const EncoderLaunch& p, hipStream_t s);
 int launch_split_rows_pad(const float* w, _Float16* out, int rows, int Kin, int Kpad, hipStream_t s);

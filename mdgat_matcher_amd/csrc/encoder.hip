@@ -13,6 +13,7 @@
 // All weights but the last product's sit in LDS at once (92 KB); the 256 -> 128 product streams its four
 // 32-row blocks through two 33 KB buffers.
 #include "common.hpp"
+#include "fpfh_norm.hpp"
 #include "mma_chain.hpp"
 
 namespace {
@@ -27,9 +28,17 @@ struct EncArgs {
     const _Float16 *k1s, *k2s, *d0s, *d1s, *els;   // split weights [rows][2][K]: 64x32, 128x64, 64x48, 128x64, 128x256
     float* x;                     // [R][128]
     int B, N, M, R;
-    // the RAGGED instantiation only (device int32 [B]): pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M
+    // the RAGGED and BANK instantiations only (device int32 [B]): pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M
     const int* cnt0;
     const int* cnt1;
+    // the BANK instantiation only: rec0 / rec1 are a bank's [rows][37] records, keypoint n of frame f of pair b is record start_f[b] + n
+    // (device int64 [B]); kp0_out [B][N][3] / kp1_out [B][M][3] (optional): the keypoints as they lie in the records, zeros beyond the
+    // counts; guard (optional, host-mapped): set when a pair's own record holds a non-finite word or - under normalize - an all-zero FPFH row
+    const long long* start0;
+    const long long* start1;
+    float* kp0_out;
+    float* kp1_out;
+    unsigned* guard;
 };
 
 // LDS map (halves)
@@ -70,7 +79,14 @@ template <int K, int ROWS> struct CopyRows {
 // RAGGED: per-pair keypoint counts in padded slots (EncArgs::cnt0 / cnt1).  A keypoint beyond its frame's count reads none of its inputs
 // and is encoded from zeros: whatever the caller's tensors hold there, the padded rows of x are finite, and so is everything the row-wise
 // kernels behind make of them.
-template <bool RAGGED = false>
+// BANK: the same slots filled straight from a bank of raw records (EncArgs::start0 / start1) - what ops.pack_ragged and the exact mode's
+// assemble kernel make of a chunk, without the pass: a lane reads its keypoint's record by dwords (the stride of 148 bytes aligns to no
+// more), tests every word's bits and, under `normalize`, scales the FPFH row by the loader's float32 inverse norm (fpfh_norm.hpp; the sum
+// runs over the whole row in numpy's order, so both lanes of a keypoint read all of it - the second read hits the cache).  The values that
+// reach the layers are bit for bit the float32 ones of assemble_record_f64 (f64.hip), so everything behind is the RAGGED form's.  Records
+// no pair points at are never read.
+enum class EncForm { UNIFORM, RAGGED, BANK };
+template <EncForm FORM = EncForm::UNIFORM>
 __global__ __launch_bounds__(ENC_THREADS, 2) void encoder_kernel(EncArgs a) {
     extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
     const int tid = threadIdx.x;
@@ -110,11 +126,38 @@ __global__ __launch_bounds__(ENC_THREADS, 2) void encoder_kernel(EncArgs a) {
     float xyzs[4];
     float f[24];                 // FPFH entries 16 ks + 8 hi + j of this lane, ks = 0..2 (zero beyond 33)
     bool padded = false;
-    if constexpr (RAGGED) padded = n >= (f1 ? a.cnt1 : a.cnt0)[b];
-    if (RAGGED && padded) {
+    if constexpr (FORM != EncForm::UNIFORM) padded = n >= (f1 ? a.cnt1 : a.cnt0)[b];
+    if (FORM != EncForm::UNIFORM && padded) {
         xyzs[0] = xyzs[1] = xyzs[2] = xyzs[3] = 0.f;
 #pragma unroll
         for (int i = 0; i < 24; ++i) f[i] = 0.f;
+    } else if constexpr (FORM == EncForm::BANK) {
+        const unsigned* r = reinterpret_cast<const unsigned*>(f1 ? a.rec1 : a.rec0) + ((size_t)(f1 ? a.start1 : a.start0)[b] + n) * 37;
+        float v[37];
+        bool bad = false;
+#pragma unroll
+        for (int c = 0; c < 37; ++c) {
+            const unsigned w = r[c];
+            bad |= (w & 0x7f800000u) == 0x7f800000u;      // NaN / inf, by the bits (as assemble_record_f64)
+            v[c] = __builtin_bit_cast(float, w);
+        }
+        xyzs[0] = v[0]; xyzs[1] = v[1]; xyzs[2] = v[2]; xyzs[3] = v[3];
+        const float inv = a.normalize ? fpfh_inv_norm(v + 4) : 1.f;
+        bad |= !(inv < 3.0e38f);                          // (a row of zeros: 1 / 0 - NaN descriptors in the reference)
+        {
+#pragma clang fp contract(off)      // load_data.py:292: np.multiply(descs, 1 / norm), a product rounded by itself
+#pragma unroll
+            for (int ks = 0; ks < 3; ++ks)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int c0 = 16 * ks + j, c1 = c0 + 8;       // this entry's FPFH column on the hi = 0 / 1 lane (static indices)
+                    const float v0 = c0 < MDGAT_FPFH ? v[4 + (c0 < MDGAT_FPFH ? c0 : 0)] : 0.f;
+                    const float v1 = c1 < MDGAT_FPFH ? v[4 + (c1 < MDGAT_FPFH ? c1 : 0)] : 0.f;
+                    const float e = hi ? v1 : v0;
+                    f[8 * ks + j] = a.normalize ? e * inv : e;
+                }
+        }
+        if (bad && a.guard) __hip_atomic_store(a.guard, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     } else {
         const float* rec = f1 ? a.rec1 : a.rec0;
         const float* fp;
@@ -144,6 +187,12 @@ __global__ __launch_bounds__(ENC_THREADS, 2) void encoder_kernel(EncArgs a) {
 #pragma unroll
             for (int i = 0; i < 24; ++i) f[i] *= inv;
         }
+    }
+    if constexpr (FORM == EncForm::BANK) {
+        // the keypoints for the steps behind the matcher (mdgat_gt_matches_ragged, mdgat_eval_metrics_ragged), one lane per keypoint
+        // (lanes past the end rewrite the last keypoint's values)
+        float* kp = f1 ? a.kp1_out : a.kp0_out;
+        if (kp && hi == 0) { kp[pi * 3] = xyzs[0]; kp[pi * 3 + 1] = xyzs[1]; kp[pi * 3 + 2] = xyzs[2]; }
     }
     __syncthreads();
 
@@ -274,16 +323,29 @@ int launch_encoder(const EncoderLaunch& p, hipStream_t s) {
     a.x = p.x; a.B = p.B; a.N = p.N; a.M = p.M; a.R = p.B * (p.N + p.M);
     const size_t lds = (size_t)OFF_END * sizeof(_Float16) + 672 * sizeof(float);
     const dim3 grid((a.R + ENC_THREADS / 2 - 1) / (ENC_THREADS / 2));
+    if (p.start0 || p.start1) {
+        // a ragged chunk out of a bank: the starts and counts of both frames, the records themselves
+        if (!p.start0 || !p.start1 || !p.cnt0 || !p.cnt1 || !p.rec0 || !p.rec1) {
+            mdgat_set_error("encoder (bank): needs the records, the starts and the counts of both frames");
+            return MDGAT_ERR_BAD_ARG;
+        }
+        a.cnt0 = p.cnt0; a.cnt1 = p.cnt1; a.start0 = p.start0; a.start1 = p.start1;
+        a.kp0_out = p.kp0_out; a.kp1_out = p.kp1_out; a.guard = p.guard;
+        static std::atomic<unsigned long long> optin_bank;
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<EncForm::BANK>), lds, optin_bank, "encoder LDS attribute")) return rc;
+        hipLaunchKernelGGL(encoder_kernel<EncForm::BANK>, grid, dim3(ENC_THREADS), lds, s, a);
+        return mdgat_check_hip(hipGetLastError(), "encoder launch (bank)");
+    }
     if (p.cnt0) {
         if (!p.cnt1 || (p.rec0 && p.normalize)) { mdgat_set_error("encoder (ragged): counts for one frame only, or records to normalise"); return MDGAT_ERR_BAD_ARG; }
         a.cnt0 = p.cnt0; a.cnt1 = p.cnt1;
         static std::atomic<unsigned long long> optin_ragged;
-        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<true>), lds, optin_ragged, "encoder LDS attribute")) return rc;
-        hipLaunchKernelGGL(encoder_kernel<true>, grid, dim3(ENC_THREADS), lds, s, a);
+        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<EncForm::RAGGED>), lds, optin_ragged, "encoder LDS attribute")) return rc;
+        hipLaunchKernelGGL(encoder_kernel<EncForm::RAGGED>, grid, dim3(ENC_THREADS), lds, s, a);
         return mdgat_check_hip(hipGetLastError(), "encoder launch (ragged)");
     }
     static std::atomic<unsigned long long> optin;
-    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<false>), lds, optin, "encoder LDS attribute")) return rc;
-    hipLaunchKernelGGL(encoder_kernel<false>, grid, dim3(ENC_THREADS), lds, s, a);
+    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(encoder_kernel<EncForm::UNIFORM>), lds, optin, "encoder LDS attribute")) return rc;
+    hipLaunchKernelGGL(encoder_kernel<EncForm::UNIFORM>, grid, dim3(ENC_THREADS), lds, s, a);
     return mdgat_check_hip(hipGetLastError(), "encoder launch");
 }

@@ -35,6 +35,7 @@
 #include "common.hpp"
 #include "f64.hpp"
 #include "f64_dev.hpp"
+#include "fpfh_norm.hpp"
 
 #include "row_search.hpp"
 #include "exp2_tab256.hpp"
@@ -716,20 +717,7 @@ __device__ __forceinline__ bool assemble_record_f64(const float* rec, int normal
 #pragma unroll
     for (int c = 0; c < 4; ++c) in4[c] = (double)v[c];
     if (kp) { kp[0] = v[0]; kp[1] = v[1]; kp[2] = v[2]; }
-    float inv = 1.f;
-    if (normalize) {
-        float r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = v[4 + j] * v[4 + j];
-#pragma unroll
-        for (int i = 8; i < 32; i += 8)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float q = v[4 + i + j] * v[4 + i + j]; r[j] = r[j] + q; }
-        float sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        const float q = v[36] * v[36];
-        sum = sum + q;
-        inv = 1.f / __builtin_sqrtf(sum);
-    }
+    const float inv = normalize ? fpfh_inv_norm(v + 4) : 1.f;      // (fpfh_norm.hpp: shared with the encoder's bank form)
     bad |= !(inv < 3.0e38f);                 // (a row of zeros: 1 / 0 - NaN descriptors in the reference)
 #pragma unroll
     for (int c = 0; c < 33; ++c) in33[c] = (double)(normalize ? v[4 + c] * inv : v[4 + c]);

@@ -15,7 +15,8 @@ struct RaggedCounts {
 };
 
 // A ragged chunk out of a bank of records [rows0 | rows1][37]: frame f of pair b is the counts[b] records from row start[b] - device
-// int64 [B] for the assemble kernel, host copies for the check.
+// int64 [B] for the kernel that reads the records (the exact mode's assemble kernel, the fp32-class encoder's bank form), host copies for
+// the check.
 struct RaggedStarts {
     const long long *start0 = nullptr, *start1 = nullptr, *host0 = nullptr, *host1 = nullptr;
     long long rows0 = 0, rows1 = 0;

@@ -203,11 +203,15 @@ class MDGAT(nn.Module):
         self.train_forward = bool(tf) if tf is not None else os.environ.get('MDGAT_TRAIN_FORWARD') == '1'
         # not a reference key: which modules forward_ragged / evaluate_ragged take.  'exact' (default): the exact mode only;
         #   'auto': a module whose forward is fp32-class (not exact()) runs the library's fp32-class ragged forward (mdgat_forward_ragged:
-        #   slots of at most 512 keypoints), an exact one its own as before.
+        #   slots of at most 512 keypoints), an exact one its own as before;
+        #   'module': EVERY ragged entry - forward_ragged / evaluate_ragged and the bank's match_frames_ragged / evaluate_frames_ragged -
+        #   runs the arithmetic the module's forward runs, for all three FPFH descriptors: 'auto', plus the bank entries on an fp32-class
+        #   module (mdgat_forward_frames_ragged on its handle) and the pooled descriptor ('FPFH_gloabal': its encoders in fp64, the
+        #   fp32-class kernels behind them).
         # MDGAT_RAGGED_ARITHMETIC in the environment replaces the default for modules whose config does not carry the key.
         self.ragged_arithmetic = str(self.config.get('ragged_arithmetic') or os.environ.get('MDGAT_RAGGED_ARITHMETIC') or 'exact')
-        if self.ragged_arithmetic not in ('exact', 'auto'):
-            raise ValueError(f"ragged_arithmetic={self.ragged_arithmetic!r}: expected 'exact' or 'auto'")
+        if self.ragged_arithmetic not in ('exact', 'auto', 'module'):
+            raise ValueError(f"ragged_arithmetic={self.ragged_arithmetic!r}: expected 'exact', 'auto' or 'module'")
         f64_layers = self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -520,8 +524,12 @@ class MDGAT(nn.Module):
 
     def _ragged_fp32(self) -> bool:
         """Does a ragged batch of this module, as it stands, run the fp32-class ragged forward?  Opt-in (config['ragged_arithmetic'] =
-        'auto'), and then what ``forward`` runs decides: a module that is not ``exact()``."""
-        return getattr(self, 'ragged_arithmetic', 'exact') == 'auto' and not self.exact()
+        'auto' or 'module'), and then what ``forward`` runs decides: a module that is not ``exact()``."""
+        return getattr(self, 'ragged_arithmetic', 'exact') in ('auto', 'module') and not self.exact()
+
+    def _ragged_module(self) -> bool:
+        """... and with config['ragged_arithmetic'] = 'module': the bank entries and the pooled descriptor run that arithmetic too."""
+        return getattr(self, 'ragged_arithmetic', 'exact') == 'module' and not self.exact()
 
     @staticmethod
     def _early_out(kpts0, kpts1):
@@ -584,9 +592,12 @@ class MDGAT(nn.Module):
         if self.training or getattr(self, 'eval_loss', False):
             raise NotImplementedError('ragged batches run in the exact mode only: eval() mode, without the evaluation loss (eval_loss)' if not fp32 else
                                       'ragged batches run in eval() mode, without the evaluation loss (eval_loss)')
-        if fp32 and (self.descriptor == 'FPFH_gloabal' or self.attention_dtype != 'fp32'):
+        if fp32 and self._ragged_module() and self.attention_dtype != 'fp32':
+            raise NotImplementedError("the fp32-class ragged forward takes attention_dtype='fp32': the single-f16 attention kernels take no per-pair counts")
+        if fp32 and not self._ragged_module() and (self.descriptor == 'FPFH_gloabal' or self.attention_dtype != 'fp32'):
             raise NotImplementedError("the fp32-class ragged forward takes descriptor 'FPFH' or 'FPFH_only' and attention_dtype='fp32': the pooled "
-                                      "encoder of 'FPFH_gloabal' and the single-f16 attention kernels take no per-pair counts")
+                                      "encoder of 'FPFH_gloabal' and the single-f16 attention kernels take no per-pair counts "
+                                      "(config['ragged_arithmetic']='module' takes the pooled descriptor)")
         call = inputs()
         dev, shape = call.dev, call.shape
         st = self._state_for(dev)
@@ -612,7 +623,8 @@ class MDGAT(nn.Module):
             if not probe.is_cuda:
                 raise RuntimeError('mdgat_matcher_amd runs on MI355X (gfx950) only: inputs must be on a CUDA/HIP device; there is no CPU fallback')
             dev = probe.device
-            fp32 = self._ragged_fp32()
+            # (the pooled descriptor's handle computes its encoders in fp64 on every path: float64 inputs into mdgat_forward_f64_ragged)
+            fp32 = self._ragged_fp32() and self.descriptor != 'FPFH_gloabal'
             ins = [packed[k].to(device=dev, dtype=torch.float32 if fp32 else torch.float64).contiguous()
                    for k in ('keypoints0', 'scores0', 'descriptors0', 'keypoints1', 'scores1', 'descriptors1')]
             if self.descriptor == 'FPFH_only':          # keypoints and saliency give the shapes only (as in _run)
@@ -641,7 +653,7 @@ class MDGAT(nn.Module):
             kp0, kp1 = (torch.empty((B, P, 3), dtype=torch.float32, device=dev) if want_kpts else None for P in (Np, Mp))
             return _RaggedCall(dev, (B, Np, Mp), counts, 'mdgat_forward_frames_ragged', (*args, int(bool(normalize))),
                                behind_Z=(kp0.data_ptr() if want_kpts else None, kp1.data_ptr() if want_kpts else None), kept=(kp0, kp1, dc, ds, rec))
-        padded, (kp0, kp1, dc, _, _) = self._ragged_forward(inputs, return_Z)
+        padded, (kp0, kp1, dc, _, _) = self._ragged_forward(inputs, return_Z, fp32_entry=self._ragged_module())
         return padded, kp0, kp1, dc
 
     def _ragged_scatter(self, empty, early_out, run, return_Z):
@@ -667,7 +679,13 @@ class MDGAT(nn.Module):
 
         ``ValueError`` for index vectors of different length, ``IndexError`` for an index outside the bank (both before anything touches
         a device); then ``forward_ragged``'s refusals: the exact mode only, at most 575 keypoints per frame, no fewer than a dynamic
-        layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``."""
+        layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``.
+
+        With ``config['ragged_arithmetic'] = 'module'`` a module whose forward is fp32-class runs the chunk on ITS arithmetic
+        (``mdgat_forward_frames_ragged`` on its handle): 'FPFH' and 'FPFH_only' through the encoder kernel's bank form, which reads the
+        records itself, 'FPFH_gloabal' through the fp64 assemble kernel and pooled encoder - each bit for bit ``forward_ragged`` of
+        ``ops.assemble_frames_ragged(bank, idx0, idx1, normalize)`` on the same module, with that call's limits (512 keypoints per frame,
+        ``attention_dtype='fp32'``, eval() mode without ``eval_loss``)."""
         (h0, h1), (a0, a1) = ops.frames_chunk(bank, idx0, idx1)
         rec = bank['records']
         empty = ((h0 == 0) | (h1 == 0)).tolist()
@@ -739,7 +757,9 @@ class MDGAT(nn.Module):
         descriptors 'FPFH' and 'FPFH_only', ``attention_dtype='fp32'``, eval() mode without ``eval_loss`` (``NotImplementedError`` /
         ``ValueError`` before anything touches a device).  Per pair the same keys, dtypes and shapes as ``forward`` on the pair alone,
         computed by the kernels that take per-pair counts: to fp32-class rounding of ``forward``, and bit-identical whatever the pair's
-        position and companions as long as the slots are equal."""
+        position and companions as long as the slots are equal.  ``'module'`` instead of ``'auto'`` takes 'FPFH_gloabal' as well (inputs
+        widened to float64 into ``mdgat_forward_f64_ragged`` on the module's handle: the encoders in fp64 with the frame maximum over a
+        pair's own keypoints, the same fp32-class kernels behind them) and opens the bank entries (``match_frames_ragged``)."""
         if isinstance(pairs_or_packed, dict):
             return self._ragged_dicts(self._run_ragged(pairs_or_packed, return_Z), return_Z)
         pairs = list(pairs_or_packed)

@@ -13,9 +13,12 @@ In one process, alternating, after warming all:
   (d') the same with ``ops.pack_frames`` - the concatenation of the host records and the upload - inside the clock.
 (The records are the pairs' own arrays narrowed to float32, so (d) re-normalises FPFH rows that are already normalised: the same work as
 on loader records, results equal to (b)'s to float32 rounding of the inputs.)
-The fp32-class legs, in the same run (a float32 module with config['ragged_arithmetic'] = 'auto'):
+The fp32-class legs, in the same run (a float32 module with config['ragged_arithmetic'] = 'module'):
   (f32 b) one ``forward_ragged`` of the 64, packed beforehand; (f32 b') the same with ``ops.pack_ragged`` inside the clock;
-  (f32 a) 64 single-pair fp32-class ``forward`` calls; (f32 c) the uniform fp32-class batch of the slot size.
+  (f32 a) 64 single-pair fp32-class ``forward`` calls; (f32 c) the uniform fp32-class batch of the slot size;
+  (f32 d) one ``match_frames_ragged`` of the 64 out of the bank uploaded beforehand (the encoder kernel reads the records itself);
+  (f32 d') the same with ``ops.pack_frames`` and the upload inside the clock;
+  (f32 gloabal) for the record, ``forward_ragged`` of the packed 64 on a float32 'FPFH_gloabal' module (its encoders in fp64).
 Device-synchronised host clock; the median of --windows windows and their spread (min .. max)."""
 import argparse
 import json
@@ -45,9 +48,12 @@ def main():
     net = MDGAT(cfg).double()
     net.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net = net.eval().to(dev)
-    net32 = MDGAT({**cfg, 'ragged_arithmetic': 'auto'})
+    net32 = MDGAT({**cfg, 'ragged_arithmetic': 'module'})
     net32.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net32 = net32.float().eval().to(dev)
+    net32g = MDGAT({**cfg, 'ragged_arithmetic': 'module', 'descriptor': 'FPFH_gloabal'})
+    net32g.load_state_dict(synth.make_state_dict(L=L, seed=1, descriptor='FPFH_gloabal'))
+    net32g = net32g.float().eval().to(dev)
     rs = np.random.RandomState(a.seed)
     counts = [(int(rs.randint(a.lo, a.hi + 1)), int(rs.randint(a.lo, a.hi + 1))) for _ in range(a.pairs)]
     pairs = [{k: v.to(dev) for k, v in synth.make_batch(1, n, m, first_pair=b).items()} for b, (n, m) in enumerate(counts)]
@@ -85,7 +91,10 @@ def main():
     legs = {'a_single_pair_calls': run_a, 'b_forward_ragged': run_b, 'b_list_with_packing': run_b_list, 'c_uniform_largest': run_c,
             'd_match_frames_ragged': run_d, 'd_with_pack_frames': run_d_pack,
             'f32_a_single_pair_calls': run_a32, 'f32_b_forward_ragged': lambda: net32.forward_ragged(packed),
-            'f32_b_list_with_packing': lambda: net32.forward_ragged(pairs), 'f32_c_uniform_largest': lambda: net32(uniform)}
+            'f32_b_list_with_packing': lambda: net32.forward_ragged(pairs), 'f32_c_uniform_largest': lambda: net32(uniform),
+            'f32_d_match_frames_ragged': lambda: net32.match_frames_ragged(bank, idx0, idx1),
+            'f32_d_with_pack_frames': lambda: net32.match_frames_ragged(ops.pack_frames(frames, dev), idx0, idx1),
+            'f32_gloabal_forward_ragged': lambda: net32g.forward_ragged(packed)}
     times = {k: [] for k in legs}
     with torch.no_grad():
         for fn in legs.values():
@@ -98,12 +107,15 @@ def main():
                 fn()
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) * 1e3)
-        prof = prof_d = prof32 = None
+        prof = prof_d = prof32 = prof32_d = None
         if a.profile:
             net32.profile(dev, True)
             net32.forward_ragged(packed)
             torch.cuda.synchronize()
-            prof32 = {k: v for k, v in net32.profile(dev, False).items() if v[1]}
+            prof32 = {k: v for k, v in net32.profile(dev, True).items() if v[1]}
+            net32.match_frames_ragged(bank, idx0, idx1)
+            torch.cuda.synchronize()
+            prof32_d = {k: v for k, v in net32.profile(dev, False).items() if v[1]}
             net.profile(dev, True)
             run_b()
             torch.cuda.synchronize()
@@ -128,11 +140,14 @@ def main():
            'f32_ratio_a_over_b': med['f32_a_single_pair_calls'] / med['f32_b_forward_ragged'],
            'f32_b_over_c': med['f32_b_forward_ragged'] / med['f32_c_uniform_largest'],
            'f32_b_over_exact_b': med['f32_b_forward_ragged'] / med['b_forward_ragged'],
+           'f32_d_over_b': med['f32_d_match_frames_ragged'] / med['f32_b_forward_ragged'],
+           'f32_d_pack_over_b_list': med['f32_d_with_pack_frames'] / med['f32_b_list_with_packing'],
            'pairs_per_s': {k: 1e3 * a.pairs / v for k, v in med.items()}}
     if prof:
         res['profile_ms_launches'] = prof
         res['profile_ms_launches_d'] = prof_d
         res['profile_ms_launches_f32_b'] = prof32
+        res['profile_ms_launches_f32_d'] = prof32_d
     print(json.dumps(res))
 
 
