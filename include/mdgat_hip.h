@@ -202,6 +202,23 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  * starts1_host: mdgat_forward_frames_ragged on a handle of either arithmetic, mdgat_assemble_frames_f64_ragged,
  * mdgat_assemble_frames_train_f64), 0 <= starts[b] and starts[b] + counts[b] <= rows.  Else MDGAT_ERR_BAD_ARG naming the first offending
  * pair; so for a null count or start vector. */
+#define MDGAT_RAGGED_WIDE_MAX_KEYPOINTS 2048   /* the same on a handle that opted into the streaming fp64 Sinkhorn (mdgat_set_ragged_sinkhorn): the dynamic fp64 attention's limit */
+/* WHICH fp64 SINKHORN A RAGGED BATCH RUNS, per handle (the exact mode's entries mdgat_forward_f64_ragged and mdgat_forward_frames_ragged;
+ * the enc-only and fp32-class ragged branches never look at it).  Returns the previous mode, -1 for a null handle or a bad mode.
+ *   0  default: the register-resident form only - slots of at most MDGAT_RAGGED_MAX_KEYPOINTS, refused under
+ *      mdgat_set_f64_sinkhorn_form(1);
+ *   1  automatic: slots within 575 keypoints, the form not forced to 1, run as under mode 0, the same bits; every other slot runs the
+ *      STREAMING form with the counts (mdgat_sinkhorn_f64_extract_stream_ragged's kernels), up to MDGAT_RAGGED_WIDE_MAX_KEYPOINTS = 2048
+ *      per frame;
+ *   2  always the streaming form, up to the same 2048.
+ * Where the streaming form runs, pair b's results are those of mdgat_forward_f64 on the pair alone under mdgat_set_f64_attention_form(0)
+ * and mdgat_set_f64_sinkhorn_form(1), bit for bit (with the exception stated below: counts0[b] == counts1[b] == a dynamic layer's k).
+ * Against the pair alone in the DEFAULT forms they agree to fp64 rounding: a small pair alone runs the register-resident Sinkhorn, which
+ * sums in another order.  Beyond 2048 the entries refuse with MDGAT_ERR_UNSUPPORTED, naming 2048.  mdgat_workspace_bytes(h, ...) follows
+ * the mode by the predicate the forward itself uses: wherever a ragged batch in slots of Np x Mp would run the streaming form - mode 2 at
+ * every size, mode 1 from a slot of 576 rows or columns on and under mdgat_set_f64_sinkhorn_form(1) - it reserves that form's K,
+ * [B][Np][Mp rounded up to 128] doubles, carved by the slot (35.6 MB per pair at 2048): size the workspace after changing either. */
+int mdgat_set_ragged_sinkhorn(mdgat_handle* h, int mode);
 /* mdgat_forward_f64 on a RAGGED batch: B pairs of different sizes in one call (the evaluation scripts run one pair per call because no two
  * frames hold the same number of keypoints - test.py:132; padding is no way out: padded keypoints change every softmax, every top-k and
  * the optimal transport).  Pair b has counts0[b] x counts1[b] keypoints and is stored in a slot padded to Np x Mp: kpts0 [B][Np][3], sigma0
@@ -217,7 +234,7 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  *   - Uniform counts (all Np / Mp) give the bits of mdgat_forward_f64 (with the same exception: Np == Mp == a dynamic layer's k).
  * The counts are checked as described at THE COUNTS OF A RAGGED BATCH above, against every dynamic layer's k.  The handle must run the fp64 tail on the register-resident Sinkhorn: Np, Mp <= 575,
  * f64_sinkhorn not MDGAT_F64_SINKHORN_OFF, f64_layers automatic, mdgat_set_f64_sinkhorn_form not 1 (else MDGAT_ERR_UNSUPPORTED); an fp32
- * handle is MDGAT_ERR_BAD_ARG.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
+ * handle is MDGAT_ERR_BAD_ARG.  A handle in mode 1 or 2 of mdgat_set_ragged_sinkhorn (above) takes Np, Mp <= 2048 under either form.  taps must be NULL.  workspace: mdgat_workspace_bytes(h, B, Np, Mp).  The batch runs unsliced on `stream`.
  * The ragged mdgat_forward_frames is mdgat_forward_frames_ragged below; there is no ragged loss.
  * One more handle is taken: the one that runs the ENCODERS ALONE in fp64 - f64_layers = MDGAT_F64_ENCODERS_ONLY, f64_sinkhorn =
  * MDGAT_F64_SINKHORN_OFF, the pooled encoder loaded (mdgat_load_pooled_encoder_f64; what a float32 'FPFH_gloabal' module creates).  Its
@@ -563,6 +580,26 @@ int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const int32_t* coun
                                       const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
                                       float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                       float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The two entries above on the STREAMING form of the fp64 Sinkhorn (K in memory, one launch per iteration), whose kernels take the counts
+ * as well: the same arguments, layout and fixed outputs beyond the counts, in slots of up to 2175 keypoints - Np, Mp <= 2175, else
+ * MDGAT_ERR_UNSUPPORTED with "<entry>: padded sizes Np x Mp: the streaming form holds at most 2175 keypoints per frame".  They ALWAYS run
+ * the streaming form, small slots included, whatever mdgat_set_f64_sinkhorn_form says.  Pair b's results are those of the pair run alone
+ * through the uniform entry under mdgat_set_f64_sinkhorn_form(1), bit for bit; against the pair alone on the register-resident form they
+ * agree to fp64 rounding (the two forms sum in different orders).  A pair works on its own extent only - row slabs 0 .. ceil(n / 32) - 1,
+ * column chunks 0 .. ceil((m + 1) / 128) - 1 - so small pairs in large slots cost what they cost alone, not what the slot costs.
+ * No workgroup of this form waits for another: there is no error word, and the entries are ASYNCHRONOUS like their uniform siblings.  The
+ * counts are checked as described at THE COUNTS OF A RAGGED BATCH before anything is enqueued.  workspace:
+ * mdgat_sinkhorn_f64_stream_ragged_workspace_bytes (0 for an unsupported slot), 256-byte aligned.  It is carved by the SLOT: K is
+ * [B][Np][Mp rounded up to 128] doubles whatever the pairs' own sizes - 35.6 MB per pair in slots of 2048, 570 MB for 16 pairs. */
+size_t mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(int B, int Np, int Mp);
+int mdgat_sinkhorn_f64_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                     const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int mdgat_sinkhorn_f64_extract_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                             const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
+                                             float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                             float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
 /* RAGGED batches in fp32: mdgat_sinkhorn / mdgat_sinkhorn_extract on pairs of different sizes, laid out as above with fp32 scores and Z.
  * They run the one-workgroup-per-pair streaming kernel (the cluster kernel takes no counts), whose ragged instantiation is picked from the

@@ -157,6 +157,12 @@ SIGNATURES = {
                                             C.c_void_p]),
     'mdgat_sinkhorn_f64_extract_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_int, C.c_float] +
                                           [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    'mdgat_sinkhorn_f64_stream_ragged_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'mdgat_sinkhorn_f64_stream_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p]),
+    'mdgat_sinkhorn_f64_extract_stream_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double, C.c_int, C.c_int, C.c_float] +
+                                                 [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
+    'mdgat_set_ragged_sinkhorn': (C.c_int, [C.c_void_p, C.c_int]),
     'mdgat_sinkhorn_ragged_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_sinkhorn_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     'mdgat_sinkhorn_extract_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_float] +

@@ -73,6 +73,7 @@ struct mdgat_handle {
     unsigned match_token = 0;       // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
     // Two lanes (forward_batched): the second lane's stream and the events that fork it off the caller's stream and join it again
     int lanes = 2;                  // 1 or 2 (mdgat_set_lanes; default 2, MDGAT_FORWARD_LANES)
+    int ragged_sinkhorn = 0;        // which fp64 Sinkhorn an exact ragged batch runs (mdgat_set_ragged_sinkhorn): 0 resident only, 1 automatic, 2 streaming
     hipStream_t lane_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // optional per-kernel-class timing of mdgat_forward (mdgat_profile): HIP events on the launch stream of each lane
@@ -274,7 +275,9 @@ struct Workspace {
     double* Z64;                           // ... and on an exact-mode handle, whose fp64 tail hands the loss the fp64 Z, room for that Z
     size_t total;   // bytes
 };
-Workspace carve(void* base, int B, int N, int M, bool f64, bool loss) {
+// stream64: room for the streaming fp64 Sinkhorn on a ragged batch as well (a handle in mode 2 of mdgat_set_ragged_sinkhorn: that form at sizes
+// where the uniform forward runs the resident one)
+Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, bool stream64 = false) {
     const size_t R = (size_t)B * (N + M);
     Workspace w{};
     WsCarver c{static_cast<char*>(base)};
@@ -293,6 +296,7 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss) {
         c.take(w.hid64, R * 256);
         c.take(w.msg64, R * 128);
         w.sk64_bytes = sinkhorn_f64_supported(N, M) ? sinkhorn_f64_workspace_bytes(B, N, M) : 0;
+        if (stream64 && w.sk64_bytes && sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M) > w.sk64_bytes) w.sk64_bytes = sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M);
         c.take(w.sk64, w.sk64_bytes ? w.sk64_bytes + sinkhorn_f64_bests(nullptr, B, N, M).bytes : 0);
         if ((size_t)N * M <= (size_t)384 * (N + M) || !w.sk64_bytes) w.scores64 = w.qkv64;
         else c.take(w.scores64, (size_t)B * N * M);
@@ -439,11 +443,19 @@ static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss) {
     return p;
 }
 
+// Would an exact ragged batch in slots of N x M run the streaming fp64 Sinkhorn on this handle (mdgat_set_ragged_sinkhorn)?  Mode 2, or mode 1
+// where the register-resident form takes no counts (a slot beyond 575, 576 rows included, or the form forced to 1).  ONE predicate for
+// plan_forward and for mdgat_workspace_bytes, which knows nothing of the call to come and so reserves the form's K whenever a ragged call
+// could need it.
+static bool ragged_sinkhorn_streams(const mdgat_handle* h, int N, int M) {
+    return h && (h->ragged_sinkhorn == 2 || (h->ragged_sinkhorn == 1 && !sinkhorn_f64_ragged_supported(N, M)));
+}
+
 static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool loss) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     // (taps run unsliced: the whole batch's workspace is the lower bound in every case)
     const bool f64 = h && h->cfg.arithmetic == MDGAT_ARITH_FP64;
-    const size_t whole = carve(nullptr, B, N, M, f64, loss).total;
+    const size_t whole = carve(nullptr, B, N, M, f64, loss, ragged_sinkhorn_streams(h, N, M)).total;
     const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
@@ -451,6 +463,13 @@ static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool l
 
 extern "C" size_t mdgat_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, false); }
 extern "C" size_t mdgat_forward_loss_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, true); }
+
+extern "C" int mdgat_set_ragged_sinkhorn(mdgat_handle* h, int mode) {
+    if (!h || mode < 0 || mode > 2) { mdgat_set_error("mdgat_set_ragged_sinkhorn: mode must be 0 (resident), 1 (automatic) or 2 (streaming)"); return -1; }
+    const int prev = h->ragged_sinkhorn;
+    h->ragged_sinkhorn = mode;
+    return prev;
+}
 
 extern "C" int mdgat_set_lanes(mdgat_handle* h, int lanes) {
     if (!h || lanes < 1 || lanes > 2) { mdgat_set_error("mdgat_set_lanes: lanes must be 1 or 2"); return MDGAT_ERR_BAD_ARG; }
@@ -466,6 +485,7 @@ struct Path {
     bool fused64;     // the fp64 encoders and layer tails as fused launches, the last one writing the hand-over to fp32
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
     int cnt_min;      // a ragged batch (FwdIn::counts): the smallest keypoint count of any frame; 0 otherwise
+    bool stream_ragged;   // an exact ragged batch on the streaming fp64 Sinkhorn (mdgat_set_ragged_sinkhorn: mode 2, or mode 1 where the resident form takes no counts)
     LanePlan lanes;
 };
 
@@ -510,7 +530,8 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         return MDGAT_ERR_BAD_ARG;
     }
     p.lanes = (taps || in.counts) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
-    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss).total;
+    p.stream_ragged = in.counts && f64 && ragged_sinkhorn_streams(h, N, M);
+    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.stream_ragged).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
     const int L2 = 2 * h->cfg.L;
@@ -551,6 +572,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         // over the padded rows, which the encoder makes from zeros.  One unsliced lane, no taps, no loss; the single-f16 attention mode has
         // no kernel that takes counts.  The counts - and the starts into a bank - are checked on their host copies before anything is enqueued.
         const char* who = in.bank ? "mdgat_forward_frames_ragged" : f64 ? "mdgat_forward_f64_ragged" : "mdgat_forward_ragged";
+        p.stream_ragged = false;      // (mdgat_set_ragged_sinkhorn is the exact tail's: this branch has no fp64 Sinkhorn)
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
         if (in.rec0 && !in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
         if (h->cfg.attention_mode == 1) { mdgat_set_error("%s: attention_mode = 1 (single-f16 products) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
@@ -565,6 +587,15 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         // are checked on their host copies, against the whole k schedule (mdgat_check_ragged).
         const char* who = in.bank ? "mdgat_forward_frames_ragged" : "mdgat_forward_f64_ragged";
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
+        if (p.stream_ragged) {
+            // the handle opted in (mdgat_set_ragged_sinkhorn): the streaming Sinkhorn's RAGGED instantiations behind the same kernels, in
+            // slots up to the dynamic fp64 attention's limit
+            if (!p.tail64 || N > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || M > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || !sinkhorn_f64_stream_ragged_supported(N, M)) {
+                mdgat_set_error("%s: ragged batches on the streaming Sinkhorn need the fp64 tail: f64_sinkhorn not off, f64_layers automatic, and at most "
+                                "%d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_WIDE_MAX_KEYPOINTS, N, M);
+                return MDGAT_ERR_UNSUPPORTED;
+            }
+        } else
         if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || !sinkhorn_f64_ragged_supported(N, M)) {
             mdgat_set_error("%s: ragged batches need the fp64 tail on the register-resident Sinkhorn: f64_sinkhorn not off, f64_layers automatic, "
                             "mdgat_set_f64_sinkhorn_form not 1, and at most %d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_MAX_KEYPOINTS, N, M);
@@ -755,8 +786,12 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
     if (int rc = f.tap(f.taps.scores, scores64, (size_t)B * N * M)) return rc;
     const Sk64Bests b = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
     const SkExtract ex = f.extract(o);
-    if (int rc = launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
-                                  b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score, f.cnt0, f.cnt1)) return rc;
+    if (int rc = f.p.stream_ragged
+                     ? launch_sinkhorn_f64_stream_ragged(B, N, M, f.cnt0, f.cnt1, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z,
+                                                         f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.s,
+                                                         f.h->w.blob64 + f.h->w.bl.bin_score)
+                     : launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
+                                           b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score, f.cnt0, f.cnt1)) return rc;
     if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const double*>(ws.Z64));
@@ -826,7 +861,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
 // one slice of a call (checked by plan_forward) on one lane
 static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
-    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss);
+    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.stream_ragged);
     Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust,
           in.counts.cnt0, in.counts.cnt1, p.cnt_min};
     f.mark(-1);

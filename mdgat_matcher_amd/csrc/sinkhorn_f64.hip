@@ -22,6 +22,7 @@
 // The partners of a pair sit on one XCD under round-robin dispatch (blockIdx % 8), which only matters for speed.
 //
 // Frames beyond 575 keypoints (to 2175) run the STREAMING form further down: K written to memory once, one launch per iteration.
+// Both forms have RAGGED instantiations (per-pair counts in padded slots); the streaming one's take slots of any size the form holds.
 #include "common.hpp"
 #include "f64.hpp"
 #include "sinkhorn_f64.hpp"
@@ -409,46 +410,66 @@ struct Wk64Args {
     // optional potential history for the backward (sinkhorn_grad.hip; null for the forward): a_{it+1} (a_N last) into row 2 it + 1 of
     // hist_a [B][2 iters][hist_lda], b_it into row 2 it of hist_b [B][2 iters][Mp] (it < iters)
     double* hist_a; double* hist_b; int hist_lda;
+    // RAGGED instantiations only: pair b has cnt0[b] x cnt1[b] keypoints; N, M, Mp, G above are then the SLOT's - the strides of every array
+    // and what the grids are sized for - and everything the transport itself depends on comes from the pair's own counts
+    const int* cnt0; const int* cnt1;
 };
 
 typedef double w64x2 __attribute__((ext_vector_type(2)));
 
 // one wave per row: the row maximum (over the scores and the bin score of the dustbin column), K = exp(Z0 - it), zero in the padding
+// RAGGED (all five kernels of this form): per-pair keypoint counts in padded slots (Wk64Args::cnt0 / cnt1).  A pair computes exactly what it
+// computes alone through the uniform launch of its own size: its marginals, norm, dustbin column (at column m of its K rows) and dustbin
+// row (row n of Z, its share of the column sums added by the pair's OWN last slab) come from its counts; it works on row slabs
+// 0 .. ceil(n / 32) - 1 and on the 128-column chunks 0 .. ceil((m + 1) / 128) - 1 and touches nothing else of its slot.  Workgroups of
+// slabs, rows or chunks beyond a pair's own leave at once - no workgroup of this form waits for another - and what they would have
+// written (K, the partials, b beyond the pair's chunks) is never read: every sum runs over the pair's own slabs and chunks in the order
+// of the uniform launch, so the bits are those of the pair alone.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void sinkhorn_f64_wide_init_kernel(Wk64Args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int blocks = (a.N + 7) / 8;
+    const int Ns = a.N, Ms = a.M, Mps = a.Mp;            // the strides (RAGGED: the slot's)
+    const int blocks = (Ns + 7) / 8;
     const int pair = blockIdx.x / blocks, row = (blockIdx.x % blocks) * 8 + wave;
-    if (row >= a.N) return;
+    int N = Ns, M = Ms, Mp = Mps;
+    if constexpr (RAGGED) { N = a.cnt0[pair]; M = a.cnt1[pair]; Mp = (M + 1 + 127) & ~127; }
+    if (row >= N) return;
     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
-    const double* sc = a.scores + ((size_t)pair * a.N + row) * a.M;
+    const double* sc = a.scores + ((size_t)pair * Ns + row) * Ms;
     double m = alpha;
-    for (int j = lane; j < a.M; j += 64) m = fmax(m, sc[j]);
+    for (int j = lane; j < M; j += 64) m = fmax(m, sc[j]);
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) m = fmax(m, shfl_xor_d(m, s));
-    double* k = a.K + ((size_t)pair * a.N + row) * a.Mp;
-    for (int j = lane; j < a.Mp; j += 64) k[j] = j < a.M ? exp(sc[j] - m) : j == a.M ? exp(alpha - m) : 0.0;
-    if (lane == 0) a.rmax[(size_t)pair * a.N + row] = m;
+    double* k = a.K + ((size_t)pair * Ns + row) * Mps;
+    for (int j = lane; j < Mp; j += 64) k[j] = j < M ? exp(sc[j] - m) : j == M ? exp(alpha - m) : 0.0;
+    if (lane == 0) a.rmax[(size_t)pair * Ns + row] = m;
 }
 
 // b_j = nu_j / (sum over the slabs, in slab order, of the column partials launch `it` - 1 left) for launch `it` (it = iters: for the last
 // launch); b = 1 before the first iteration, 0 in the padding.  One thread per column, the G partials in flight at once.
+template <bool RAGGED>
 __global__ __launch_bounds__(128) void sinkhorn_f64_wide_b_kernel(Wk64Args a) {
-    const int M = a.M, Mp = a.Mp, G = a.G;
+    const int Mp = a.Mp, Gs = a.G;                       // the strides (RAGGED: the slot's)
     const int per = Mp >> 7;
     const int pair = blockIdx.x / per, j = (blockIdx.x % per) * 128 + threadIdx.x;
-    const double nm = (double)(a.N + M);
-    const double mu = 1.0 / nm, nuM = (double)a.N / nm;
+    int N = a.N, M = a.M, G = Gs;
+    if constexpr (RAGGED) {
+        N = a.cnt0[pair]; M = a.cnt1[pair]; G = (N + W64_ROWS - 1) / W64_ROWS;
+        if ((int)(blockIdx.x % per) * 128 > M) return;   // a chunk beyond the pair's own: nothing reads its b
+    }
+    const double nm = (double)(N + M);
+    const double mu = 1.0 / nm, nuM = (double)N / nm;
     double bv = 0.0;
     if (j <= M) {
         if (a.it == 0) bv = 1.0;
         else {
-            const double* Pp = a.P + (((size_t)pair * 2 + ((a.it + 1) & 1)) * G) * Mp + j;      // what launch it - 1 wrote
+            const double* Pp = a.P + (((size_t)pair * 2 + ((a.it + 1) & 1)) * Gs) * Mp + j;     // what launch it - 1 wrote
             double v[W64_GMAX];
 #pragma unroll
             for (int q = 0; q < W64_GMAX; ++q) v[q] = q < G ? Pp[(size_t)q * Mp] : 0.0;
             double tot = v[0];
 #pragma unroll
-            for (int q = 1; q < W64_GMAX; ++q) tot += v[q];                                       // (+ 0.0 beyond G)
+            for (int q = 1; q < W64_GMAX; ++q) tot += v[q];                                       // (+ 0.0 beyond G; RAGGED: beyond the pair's own slabs)
             bv = (j < M ? mu : nuM) * recip_f64(tot);
         }
     }
@@ -456,24 +477,29 @@ __global__ __launch_bounds__(128) void sinkhorn_f64_wide_b_kernel(Wk64Args a) {
     if (a.hist_b && a.it < a.iters) a.hist_b[((size_t)pair * 2 * a.iters + 2 * a.it) * Mp + j] = bv;
 }
 
-template <int NC2>
+template <int NC2, bool RAGGED>
 __global__ __launch_bounds__(512) void sinkhorn_f64_wide_iter_kernel(Wk64Args a) {
     extern __shared__ __attribute__((aligned(16))) double w64_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, M = a.M, Mp = a.Mp, G = a.G;
-    const int nc2 = Mp >> 7;
+    const int Ns = a.N, Mp = a.Mp, Gs = a.G;       // the strides (RAGGED: the slot's; NC2 is chosen from the slot)
+    const int pair = blockIdx.x / Gs, g = blockIdx.x % Gs;
+    int N = Ns, M = a.M, G = Gs, nc2 = Mp >> 7;
+    if constexpr (RAGGED) {
+        N = __builtin_amdgcn_readfirstlane(a.cnt0[pair]); M = __builtin_amdgcn_readfirstlane(a.cnt1[pair]);
+        G = (N + W64_ROWS - 1) / W64_ROWS; nc2 = (M + 1 + 127) >> 7;
+        if (g >= G) return;                        // a slab beyond the pair's own (the whole workgroup)
+    }
     double* bl = w64_lds;                          // [Mp]
     double* colbuf = w64_lds + Mp;                 // [8][Mp]
-    const int pair = blockIdx.x / G, g = blockIdx.x % G;
     const double nm = (double)(N + M);
     const double mu = 1.0 / nm, muN = (double)M / nm;
-    for (int j = 2 * tid; j < Mp; j += 1024) *reinterpret_cast<w64x2*>(bl + j) = *reinterpret_cast<const w64x2*>(a.bvec + (size_t)pair * Mp + j);
+    for (int j = 2 * tid; j < 128 * nc2; j += 1024) *reinterpret_cast<w64x2*>(bl + j) = *reinterpret_cast<const w64x2*>(a.bvec + (size_t)pair * Mp + j);
     double acc[2 * NC2];
 #pragma unroll
     for (int c = 0; c < 2 * NC2; ++c) acc[c] = 0.0;
     const int rbeg = g * W64_ROWS, rend = rbeg + W64_ROWS < N ? rbeg + W64_ROWS : N;
-    const double* kbase = a.K + (size_t)pair * N * Mp + 2 * lane;
+    const double* kbase = a.K + (size_t)pair * Ns * Mp + 2 * lane;
     auto fetch = [&](w64x2 (&kv)[NC2], int row) {
         const double* k = kbase + (size_t)row * Mp;
 #pragma unroll
@@ -489,7 +515,7 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_iter_kernel(Wk64Args a)
                 p = __builtin_fma(kv[c].y, bb.y, p);
             }
         const double ai = mu * recip_f64(wave_sum_f64(p));
-        if (lane == 0) a.av[(size_t)pair * (N + 1) + row] = ai;
+        if (lane == 0) a.av[(size_t)pair * (Ns + 1) + row] = ai;
         if (a.hist_a && lane == 0) a.hist_a[((size_t)pair * 2 * a.iters + 2 * a.it + 1) * a.hist_lda + row] = ai;
 #pragma unroll
         for (int c = 0; c < NC2; ++c) {
@@ -516,35 +542,40 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_iter_kernel(Wk64Args a)
     for (int c = 0; c < NC2; ++c)
         if (c < nc2) *reinterpret_cast<w64x2*>(colbuf + (size_t)wave * Mp + 128 * c + 2 * lane) = w64x2{acc[2 * c], acc[2 * c + 1]};
     __syncthreads();
-    const bool last = g == G - 1;
-    double* mine = a.P + (((size_t)pair * 2 + (a.it & 1)) * G + g) * Mp;
-    for (int j = tid; j < Mp; j += 512) {
+    const bool last = g == G - 1;                               // (RAGGED: the pair's own last slab)
+    double* mine = a.P + (((size_t)pair * 2 + (a.it & 1)) * Gs + g) * Mp;
+    for (int j = tid; j < 128 * nc2; j += 512) {
         double p = colbuf[j];
 #pragma unroll
         for (int w = 1; w < 8; ++w) p += colbuf[(size_t)w * Mp + j];
         if (last) p += aN;                                      // the dustbin row's share (K = 1)
         mine[j] = p;
     }
-    if (last && tid == 0) a.av[(size_t)pair * (N + 1) + N] = aN;
+    if (last && tid == 0) a.av[(size_t)pair * (Ns + 1) + N] = aN;
     if (last && tid == 0 && a.hist_a) a.hist_a[((size_t)pair * 2 * a.iters + 2 * a.it + 1) * a.hist_lda + N] = aN;
 }
 
 // Z = Z0 - r + log a + log b - norm and the arg-maxes, decided on the fp64 values (as the register-resident kernel's epilogue)
-template <int NC2>
+template <int NC2, bool RAGGED>
 __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a) {
     extern __shared__ __attribute__((aligned(16))) double w64_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, M = a.M, Mp = a.Mp, G = a.G;
-    const int nc2 = Mp >> 7;
+    const int Ns = a.N, Ms = a.M, Mp = a.Mp, Gs = a.G;           // the strides (RAGGED: the slot's)
+    const int pair = blockIdx.x / Gs, g = blockIdx.x % Gs;
+    int N = Ns, M = Ms, G = Gs, nc2 = Mp >> 7;
+    if constexpr (RAGGED) {
+        N = __builtin_amdgcn_readfirstlane(a.cnt0[pair]); M = __builtin_amdgcn_readfirstlane(a.cnt1[pair]);
+        G = (N + W64_ROWS - 1) / W64_ROWS; nc2 = (M + 1 + 127) >> 7;
+        if (g >= G) return;                                      // a slab beyond the pair's own: the merge does not read it
+    }
     double* bl = w64_lds;                                        // [Mp]: log b - norm
     double* cbv = w64_lds + Mp;                                  // [Mp]: column arg-max over the slab, value ...
     int* cbi = reinterpret_cast<int*>(cbv + Mp);                 // ... and row
     double* zN = reinterpret_cast<double*>(cbi + Mp);            // [Mp]: the dustbin row of Z (last slab)
-    const int pair = blockIdx.x / G, g = blockIdx.x % G;
     const double norm = -log((double)(N + M));
     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
-    const double* sc = a.scores + (size_t)pair * N * M;
+    const double* sc = a.scores + (size_t)pair * Ns * Ms;
     for (int j = tid; j < Mp; j += 512) {
         bl[j] = j <= M ? log(a.bvec[(size_t)pair * Mp + j]) - norm : 0.0;
         cbv[j] = -__builtin_inf();
@@ -558,16 +589,16 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a
     for (int c = 0; c < 2 * NC2; ++c) { cb[c] = -__builtin_inf(); ci[c] = 0x7fffffff; }
     const int rbeg = g * W64_ROWS, rend = rbeg + W64_ROWS < N ? rbeg + W64_ROWS : N;
     for (int row = rbeg + wave; row < rend; row += 8) {
-        const double la = a.iters ? log(a.av[(size_t)pair * (N + 1) + row]) - a.rmax[(size_t)pair * N + row] : 0.0;      // (no iteration: u = 0)
+        const double la = a.iters ? log(a.av[(size_t)pair * (Ns + 1) + row]) - a.rmax[(size_t)pair * Ns + row] : 0.0;      // (no iteration: u = 0)
         double best = -__builtin_inf();
         int bj = 0x7fffffff;
 #pragma unroll
         for (int c = 0; c < 2 * NC2; ++c) {
             const int j = 128 * (c >> 1) + 2 * lane + (c & 1);
             if ((c >> 1) >= nc2 || j > M) continue;
-            const double z = (j < M ? sc[(size_t)row * M + j] : alpha) + la + bl[j];
-            if (a.Z64) a.Z64[((size_t)pair * (N + 1) + row) * (M + 1) + j] = z;
-            if (a.Z32) a.Z32[((size_t)pair * (N + 1) + row) * (M + 1) + j] = (float)z;
+            const double z = (j < M ? sc[(size_t)row * Ms + j] : alpha) + la + bl[j];
+            if (a.Z64) a.Z64[((size_t)pair * (Ns + 1) + row) * (Ms + 1) + j] = z;
+            if (a.Z32) a.Z32[((size_t)pair * (Ns + 1) + row) * (Ms + 1) + j] = (float)z;
             if (j < jlim && z > best) { best = z; bj = j; }            // ascending j within the lane
             if (z > cb[c]) { cb[c] = z; ci[c] = row; }                 // ascending rows within the wave
         }
@@ -578,17 +609,17 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a
                 const int oj = __shfl_xor(bj, s, 64);
                 if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
             }
-            if (lane == 0) { a.rbest_idx[(size_t)pair * N + row] = bj; a.rbest_val[(size_t)pair * N + row] = (float)best; }
+            if (lane == 0) { a.rbest_idx[(size_t)pair * Ns + row] = bj; a.rbest_val[(size_t)pair * Ns + row] = (float)best; }
         }
     }
-    const bool last = g == G - 1;
+    const bool last = g == G - 1;                                // (RAGGED: the pair's own last slab)
     if (last && wave == 0) {
-        const double laN = a.iters ? log(a.av[(size_t)pair * (N + 1) + N]) : alpha;      // (no iteration: the dustbin row is the bin score)
+        const double laN = a.iters ? log(a.av[(size_t)pair * (Ns + 1) + N]) : alpha;     // (no iteration: the dustbin row is the bin score)
         for (int j = lane; j <= M; j += 64) {
             const double z = laN + bl[j];
             zN[j] = z;
-            if (a.Z64) a.Z64[((size_t)pair * (N + 1) + N) * (M + 1) + j] = z;
-            if (a.Z32) a.Z32[((size_t)pair * (N + 1) + N) * (M + 1) + j] = (float)z;
+            if (a.Z64) a.Z64[((size_t)pair * (Ns + 1) + N) * (Ms + 1) + j] = z;
+            if (a.Z32) a.Z32[((size_t)pair * (Ns + 1) + N) * (Ms + 1) + j] = (float)z;
         }
     }
     if (a.cslab_idx) {
@@ -608,9 +639,28 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a
             double bv = cbv[j];
             int bi = cbi[j];
             if (last && !a.inner && zN[j] > bv) { bv = zN[j]; bi = N; }
-            a.cslab_val[((size_t)pair * G + g) * M + j] = bv;
-            a.cslab_idx[((size_t)pair * G + g) * M + j] = bi == 0x7fffffff ? 0 : bi;
+            a.cslab_val[((size_t)pair * Gs + g) * Ms + j] = bv;
+            a.cslab_idx[((size_t)pair * Gs + g) * Ms + j] = bi == 0x7fffffff ? 0 : bi;
         }
+    }
+}
+
+// the slab merge of a RAGGED streaming launch: sinkhorn_f64_merge_kernel over the pair's OWN slabs and columns (the slabs behind them
+// were written by nobody), cbest beyond the pair's columns left alone
+__global__ __launch_bounds__(256) void sinkhorn_f64_merge_ragged_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val,
+                                                                        const int* cnt0, const int* cnt1) {
+    const size_t total = (size_t)B * M;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t pair = e / M, j = e % M;
+        if (j >= (size_t)cnt1[pair]) continue;
+        const int own = (cnt0[pair] + W64_ROWS - 1) / W64_ROWS;
+        const size_t base = pair * G * M + j;
+        double bv = sval[base];
+        int bi = sidx[base];
+        for (int g = 1; g < own; ++g)
+            if (sval[base + (size_t)g * M] > bv) { bv = sval[base + (size_t)g * M]; bi = sidx[base + (size_t)g * M]; }
+        cbest_idx[e] = bi;
+        cbest_val[e] = (float)bv;
     }
 }
 
@@ -693,20 +743,20 @@ static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, 
 }
 
 // final: the last launch (Z, the arg-maxes); without it (the backward's history run) the launches stop at b_iters
-template <int NC2>
+template <int NC2, bool RAGGED = false>
 static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final = true) {
     Wk64Args a = a0;
     const size_t lds_it = (size_t)9 * a.Mp * sizeof(double), lds_fin = (size_t)a.Mp * (3 * sizeof(double) + sizeof(int));
     static std::atomic<unsigned long long> optin_it{0}, optin_fin{0};
-    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_wide_iter_kernel<NC2>), lds_it, optin_it, "sinkhorn_f64 (streaming) LDS")) return rc;
-    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_wide_final_kernel<NC2>), lds_fin, optin_fin, "sinkhorn_f64 (streaming, last) LDS")) return rc;
-    hipLaunchKernelGGL(sinkhorn_f64_wide_init_kernel, dim3((unsigned)(a.B * ((a.N + 7) / 8))), dim3(512), 0, s, a);
+    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_wide_iter_kernel<NC2, RAGGED>), lds_it, optin_it, "sinkhorn_f64 (streaming) LDS")) return rc;
+    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_wide_final_kernel<NC2, RAGGED>), lds_fin, optin_fin, "sinkhorn_f64 (streaming, last) LDS")) return rc;
+    hipLaunchKernelGGL(sinkhorn_f64_wide_init_kernel<RAGGED>, dim3((unsigned)(a.B * ((a.N + 7) / 8))), dim3(512), 0, s, a);
     for (int it = 0; it <= a.iters; ++it) {
         a.it = it;
-        hipLaunchKernelGGL(sinkhorn_f64_wide_b_kernel, dim3((unsigned)(a.B * (a.Mp >> 7))), dim3(128), 0, s, a);
-        if (it < a.iters) hipLaunchKernelGGL(sinkhorn_f64_wide_iter_kernel<NC2>, dim3((unsigned)(a.B * a.G)), dim3(512), lds_it, s, a);
+        hipLaunchKernelGGL(sinkhorn_f64_wide_b_kernel<RAGGED>, dim3((unsigned)(a.B * (a.Mp >> 7))), dim3(128), 0, s, a);
+        if (it < a.iters) hipLaunchKernelGGL((sinkhorn_f64_wide_iter_kernel<NC2, RAGGED>), dim3((unsigned)(a.B * a.G)), dim3(512), lds_it, s, a);
     }
-    if (final) hipLaunchKernelGGL(sinkhorn_f64_wide_final_kernel<NC2>, dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
+    if (final) hipLaunchKernelGGL((sinkhorn_f64_wide_final_kernel<NC2, RAGGED>), dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming) launch");
 }
 
@@ -723,6 +773,46 @@ static int launch_sinkhorn_f64_wide(int B, int N, int M, const double* scores, d
     int rc = nc2 <= 5 ? s64_wide_launches<5>(a, s) : nc2 <= 9 ? s64_wide_launches<9>(a, s) : s64_wide_launches<W64_NC2MAX>(a, s);
     if (rc) return rc;
     return s64_merge_columns(w.sidx, w.sval, B, a.G, M, cbest_idx, cbest_val, s);
+}
+
+// ---- the streaming form on a RAGGED batch: the kernels' RAGGED instantiations over slots of N x M (sinkhorn_f64.hpp) ----
+// The workspace is the uniform launch's of the SLOT size - K is [B][N][Mp], 35.6 MB per pair at 2048, whatever the pairs' own sizes: a
+// pair's rows sit at the slot's strides (K is not compacted) and only its own extent is written and read.
+bool sinkhorn_f64_stream_ragged_supported(int N, int M) { return s64_wide_supported(N, M); }
+size_t sinkhorn_f64_stream_ragged_workspace_bytes(int B, int N, int M) {
+    return B <= 0 || !s64_wide_supported(N, M) ? 0 : s64_wide_carve(nullptr, B, N, M).bytes;
+}
+int launch_sinkhorn_f64_stream_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const double* scores, double alpha, int iters, double* Z64,
+                                      float* Z32, int inner, int* rbest_idx, float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace,
+                                      size_t workspace_bytes, hipStream_t s, const double* alpha_dev) {
+    if (B <= 0) return MDGAT_OK;
+    if (!cnt0 || !cnt1) { mdgat_set_error("fp64 Sinkhorn (streaming, ragged): null counts pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (!s64_wide_supported(N, M)) {
+        mdgat_set_error("fp64 Sinkhorn (streaming, ragged): padded sizes %d x %d > %d supported", N, M, 128 * W64_NC2MAX - 1);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (!workspace || workspace_bytes < sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("fp64 Sinkhorn (streaming, ragged): workspace too small or not 256-byte aligned");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    Wk64Args a{};
+    a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.inner = inner;
+    a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
+    a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val; a.cnt0 = cnt0; a.cnt1 = cnt1;
+    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
+    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
+    a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
+    // (the kernels write a pair's own block of Z only: the rest of every padded slot is zero)
+    if (Z64) if (int rc = mdgat_check_hip(hipMemsetAsync(Z64, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(double), s), "memset(fp64 Sinkhorn Z)")) return rc;
+    if (Z32) if (int rc = mdgat_check_hip(hipMemsetAsync(Z32, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(float), s), "memset(fp64 Sinkhorn Z32)")) return rc;
+    // (the register budget follows the SLOT: a pair's own chunk count only bounds what its lanes load)
+    const int nc2 = a.Mp >> 7;
+    int rc = nc2 <= 5 ? s64_wide_launches<5, true>(a, s) : nc2 <= 9 ? s64_wide_launches<9, true>(a, s) : s64_wide_launches<W64_NC2MAX, true>(a, s);
+    if (rc || !cbest_idx) return rc;
+    const size_t total = (size_t)B * M;
+    hipLaunchKernelGGL(sinkhorn_f64_merge_ragged_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, w.sidx, w.sval,
+                       B, a.G, M, cbest_idx, cbest_val, cnt0, cnt1);
+    return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming, ragged) merge launch");
 }
 
 int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
@@ -919,4 +1009,57 @@ extern "C" int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const in
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
     if (int rc = launch_extract_from_bests(B, Np, Mp, &ex, b.ri, b.rv, b.ci, b.cv, s, counts0, counts1)) return rc;
     return s64_ragged_finish(who, word, s);
+}
+
+// ---- the same two on the streaming form (include/mdgat_hip.h): slots of up to 2175 keypoints, asynchronous - no error word ----
+static int s64_stream_check_counts(const char* who, int B, int Np, int Mp, const int32_t* c0, const int32_t* c1, const int32_t* h0, const int32_t* h1) {
+    if (!s64_wide_supported(Np, Mp)) {
+        mdgat_set_error("%s: padded sizes %d x %d: the streaming form holds at most %d keypoints per frame", who, Np, Mp, 128 * W64_NC2MAX - 1);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    return mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{c0, c1, h0, h1}, nullptr, nullptr, 0, nullptr);
+}
+extern "C" size_t mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(int B, int Np, int Mp) {
+    if (B <= 0 || Np <= 0 || Mp <= 0 || !s64_wide_supported(Np, Mp)) return 0;
+    return sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) + sinkhorn_f64_bests(nullptr, B, Np, Mp).bytes;
+}
+
+extern "C" int mdgat_sinkhorn_f64_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                                const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_sinkhorn_f64_stream_ragged";
+    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (int rc = s64_stream_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
+    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return launch_sinkhorn_f64_stream_ragged(B, Np, Mp, counts0, counts1, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace,
+                                             sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_sinkhorn_f64_extract_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                                        const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
+                                                        float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                                        float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_sinkhorn_f64_extract_stream_ragged";
+    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
+    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (int rc = s64_stream_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
+    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t kb = sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp);
+    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, Np, Mp);
+    const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
+    if (int rc = launch_sinkhorn_f64_stream_ragged(B, Np, Mp, counts0, counts1, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv,
+                                                   workspace, kb, s)) return rc;
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
+    return launch_extract_from_bests(B, Np, Mp, &ex, b.ri, b.rv, b.ci, b.cv, s, counts0, counts1);
 }

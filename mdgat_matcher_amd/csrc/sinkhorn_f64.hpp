@@ -20,6 +20,15 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
                         float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
                         CoopGroup& group, const double* alpha_dev = nullptr,       // on the group's stream; alpha_dev: the bin score on the device (replaces alpha)
                         const int* cnt0 = nullptr, const int* cnt1 = nullptr);
+// A RAGGED batch on the STREAMING form (its kernels' RAGGED instantiations): the same arguments and outputs as launch_sinkhorn_f64 with
+// counts, in slots of N, M <= 2175, whatever mdgat_set_f64_sinkhorn_form says.  Pair b's bits are those of the pair run alone through
+// the uniform streaming form.  No workgroup waits for another: no error word, no CoopGroup.  The workspace is carved by the slot (K is
+// [B][N][Mp]: 35.6 MB per pair at 2048), 256-byte aligned.
+bool sinkhorn_f64_stream_ragged_supported(int N, int M);
+size_t sinkhorn_f64_stream_ragged_workspace_bytes(int B, int N, int M);
+int launch_sinkhorn_f64_stream_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const double* scores, double alpha, int iters, double* Z64,
+                                      float* Z32, int inner, int* rbest_idx, float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace,
+                                      size_t workspace_bytes, hipStream_t s, const double* alpha_dev = nullptr);
 // rbest / cbest (idx + val each) for the extraction, carved behind the kernel's own workspace (a null base: their size only)
 struct Sk64Bests { int* ri; float* rv; int* ci; float* cv; size_t bytes; };
 Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M);

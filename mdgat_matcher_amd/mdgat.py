@@ -212,6 +212,16 @@ class MDGAT(nn.Module):
         self.ragged_arithmetic = str(self.config.get('ragged_arithmetic') or os.environ.get('MDGAT_RAGGED_ARITHMETIC') or 'exact')
         if self.ragged_arithmetic not in ('exact', 'auto', 'module'):
             raise ValueError(f"ragged_arithmetic={self.ragged_arithmetic!r}: expected 'exact', 'auto' or 'module'")
+        # not a reference key: which fp64 Sinkhorn an EXACT module's ragged batches run (include/mdgat_hip.h: mdgat_set_ragged_sinkhorn).
+        #   'resident' (default): the register-resident form only - at most 575 keypoints per frame;
+        #   'auto': that form, the same bits, in slots within 575; the streaming form with per-pair counts beyond, up to 2048 per frame;
+        #   'streaming': always the streaming form, up to 2048.
+        # Where the streaming form runs, a pair has the bits of the pair alone under set_f64_sinkhorn_form(1).  A module whose ragged calls
+        # run the fp32-class branch (ragged_arithmetic) ignores the key and keeps its limit of 512.
+        # MDGAT_RAGGED_SINKHORN in the environment replaces the default for modules whose config does not carry the key.
+        self.ragged_sinkhorn = str(self.config.get('ragged_sinkhorn') or os.environ.get('MDGAT_RAGGED_SINKHORN') or 'resident')
+        if self.ragged_sinkhorn not in ('resident', 'auto', 'streaming'):
+            raise ValueError(f"ragged_sinkhorn={self.ragged_sinkhorn!r}: expected 'resident', 'auto' or 'streaming'")
         f64_layers = self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -410,6 +420,9 @@ class MDGAT(nn.Module):
             try:
                 if self.lanes:
                     _lib.check(lib.mdgat_set_lanes(handle, self.lanes), 'mdgat_set_lanes')
+                if exact and self._ragged_wide():
+                    if lib.mdgat_set_ragged_sinkhorn(handle, {'auto': 1, 'streaming': 2}[self.ragged_sinkhorn]) < 0:
+                        raise RuntimeError('mdgat_set_ragged_sinkhorn: ' + _lib.last_error())
                 if blob_device_tensor is not None:
                     n = blob_device_tensor.numel()
                     _lib.check(lib.mdgat_load_weights(handle, C.c_void_p(blob_device_tensor.data_ptr()), n, 1),
@@ -521,6 +534,12 @@ class MDGAT(nn.Module):
 
     RAGGED_MAX_KEYPOINTS = 575      # what the register-resident fp64 Sinkhorn holds (csrc/sinkhorn_f64.hip)
     RAGGED_FP32_MAX_KEYPOINTS = 512     # the slots of the fp32-class ragged forward (include/mdgat_hip.h: MDGAT_RAGGED_FP32_MAX_KEYPOINTS)
+    RAGGED_WIDE_MAX_KEYPOINTS = 2048    # an exact module with config['ragged_sinkhorn'] = 'auto' or 'streaming' (MDGAT_RAGGED_WIDE_MAX_KEYPOINTS)
+
+    def _ragged_wide(self) -> bool:
+        """Do this module's ragged batches, as it stands, reach the streaming fp64 Sinkhorn?  Opt-in (config['ragged_sinkhorn'] = 'auto' or
+        'streaming'), and an exact module only: the fp32-class ragged branch has no fp64 Sinkhorn."""
+        return getattr(self, 'ragged_sinkhorn', 'resident') in ('auto', 'streaming') and self.exact() and not self._ragged_fp32()
 
     def _ragged_fp32(self) -> bool:
         """Does a ragged batch of this module, as it stands, run the fp32-class ragged forward?  Opt-in (config['ragged_arithmetic'] =
@@ -568,7 +587,7 @@ class MDGAT(nn.Module):
     def _ragged_counts_checked(self, h0, h1, Np, Mp):
         """the kernels' limits on the counts of a ragged batch in slots of Np x Mp"""
         kmax = max([int(k) for k in self._topk_schedule()] + [0])
-        limit = self.RAGGED_FP32_MAX_KEYPOINTS if self._ragged_fp32() else self.RAGGED_MAX_KEYPOINTS
+        limit = self.RAGGED_FP32_MAX_KEYPOINTS if self._ragged_fp32() else self.RAGGED_WIDE_MAX_KEYPOINTS if self._ragged_wide() else self.RAGGED_MAX_KEYPOINTS
         for b in range(int(h0.numel())):
             n, m = int(h0[b]), int(h1[b])
             if n > limit or m > limit:
@@ -678,8 +697,8 @@ class MDGAT(nn.Module):
         the launch.  Records no pair of the chunk points at are never read.
 
         ``ValueError`` for index vectors of different length, ``IndexError`` for an index outside the bank (both before anything touches
-        a device); then ``forward_ragged``'s refusals: the exact mode only, at most 575 keypoints per frame, no fewer than a dynamic
-        layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``.
+        a device); then ``forward_ragged``'s refusals: the exact mode only, at most 575 keypoints per frame (2048 with
+        ``config['ragged_sinkhorn']`` = 'auto' or 'streaming', as there), no fewer than a dynamic layer's k.  A non-finite record word or an all-zero FPFH row among a pair's own records: ``RuntimeError`` from ``check``.
 
         With ``config['ragged_arithmetic'] = 'module'`` a module whose forward is fp32-class runs the chunk on ITS arithmetic
         (``mdgat_forward_frames_ragged`` on its handle): 'FPFH' and 'FPFH_only' through the encoder kernel's bank form, which reads the
@@ -751,6 +770,13 @@ class MDGAT(nn.Module):
         The exact mode only (a float64 module in eval() mode, no ``eval_loss``): ``NotImplementedError`` otherwise.  ``ValueError`` for a
         frame of more than 575 keypoints or of fewer than a dynamic layer's k, and for tensors that are not [B, N, 3] / [B, N] /
         [B, N, 33] with one B and count vectors of B entries.
+
+        With ``config['ragged_sinkhorn'] = 'auto'`` (or ``MDGAT_RAGGED_SINKHORN=auto``) an exact module takes frames of up to 2048
+        keypoints: slots within 575 run as before, the same bits; beyond, the streaming fp64 Sinkhorn runs with the pairs' counts, and
+        every pair is bit for bit ``forward`` on that pair alone under ``mdgat_set_f64_attention_form(0)`` and
+        ``mdgat_set_f64_sinkhorn_form(1)`` - to fp64 rounding of the pair alone in the default forms, where a small pair runs the
+        register-resident Sinkhorn.  ``'streaming'`` runs the streaming form at every size.  Its workspace follows the SLOT: 35.6 MB per
+        pair at 2048 keypoints.
 
         With ``config['ragged_arithmetic'] = 'auto'`` (or ``MDGAT_RAGGED_ARITHMETIC=auto``) a module whose forward is fp32-class (not
         ``exact()``) runs the library's fp32-class ragged forward instead (``mdgat_forward_ragged``): frames of at most 512 keypoints,

@@ -182,6 +182,22 @@ def _entry(name, counts, B, device):
     return name + '_ragged', cnt.ptrs(), cnt
 
 
+def _sinkhorn_f64_entry(name, counts, form, B, device):
+    """``_entry`` for the two fp64 Sinkhorn ops, whose ragged batches have a second entry: ``form='streaming'`` runs the streaming form's
+    (``name_stream_ragged``).  Returns ``_entry``'s triple and the function that sizes the entry's workspace."""
+    lib = _lib.load()
+    if form not in (None, 'streaming'):
+        raise ValueError(f"form={form!r}: expected None or 'streaming'")
+    if form is not None and counts is None:
+        raise ValueError("form='streaming' selects the ragged entry of the streaming form: it needs counts (a uniform batch follows set_f64_sinkhorn_form)")
+    entry, lead, keep = _entry(name, counts, B, device)
+    if counts is None:
+        return entry, lead, keep, lib.mdgat_sinkhorn_f64_workspace_bytes
+    if form == 'streaming':
+        return name + '_stream_ragged', lead, keep, lib.mdgat_sinkhorn_f64_stream_ragged_workspace_bytes
+    return entry, lead, keep, lib.mdgat_sinkhorn_f64_ragged_workspace_bytes
+
+
 def pack_frames(frames, device) -> dict:
     """A bank of frames from their raw keypoint records: a list of [n_i, 37] float32 arrays (numpy or torch), as
     ``np.fromfile(path, dtype=np.float32).reshape(-1, 37)`` gives the KITTI keypoint files (load_data.py:146-165) - a whole sequence, or
@@ -311,12 +327,17 @@ def assemble_frames_train(bank, idx0, idx1, max_keypoints: int, min_saliency: fl
             'range_violation': guard, 'status': status}
 
 
-def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None) -> torch.Tensor:
+def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None, form=None) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308) in fp64 (csrc/sinkhorn_f64.hip): scores [B, N, M] float64 -> Z [B, N+1, M+1] float64.
 
     ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b is ``scores[b, :counts0[b], :counts1[b]]``,
     the rest of its slot is never read.  ``Z[b, :counts0[b]+1, :counts1[b]+1]`` then has the bits of the pair run alone (its dustbins at
-    row ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0.  N, M <= 575; the forward only."""
+    row ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0.  N, M <= 575; the forward only.
+
+    ``form='streaming'`` (with counts): the ragged entry of the streaming form (K in memory, one launch per iteration), in slots of
+    N, M <= 2175 - small ones included.  Pair b then has the bits of the pair run alone under ``set_f64_sinkhorn_form(1)``; against the
+    pair alone on the register-resident form it agrees to fp64 rounding.  The call is asynchronous.  The workspace holds K for the whole
+    slot, ``B * N * roundup(M + 1, 128)`` doubles: 35.6 MB per pair at 2048."""
     _need_cuda(scores)
     if counts is not None and scores.requires_grad:
         raise RuntimeError('sinkhorn_f64(counts=): ragged batches run the forward only (no gradient)')
@@ -325,19 +346,18 @@ def sinkhorn_f64(scores: torch.Tensor, bin_score: float, iters: int, counts=None
     Z = torch.empty((B, N + 1, M + 1), dtype=torch.float64, device=s.device)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        name, lead, _keep = _entry('mdgat_sinkhorn_f64', counts, B, s.device)
-        size = lib.mdgat_sinkhorn_f64_workspace_bytes if counts is None else lib.mdgat_sinkhorn_f64_ragged_workspace_bytes
+        name, lead, _keep, size = _sinkhorn_f64_entry('mdgat_sinkhorn_f64', counts, form, B, s.device)
         ws, base, need = _workspace(size(B, N, M), s.device)
         _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), base, need, _stream(s)), name)
     return Z
 
 
 def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2,
-                         want_Z: bool = False, counts=None):
+                         want_Z: bool = False, counts=None, form=None):
     """fp64 Sinkhorn + match extraction with every arg-max decided on the fp64 Z: (matches0, matches1, mscores0, mscores1[, Z fp32]).
 
     ``counts`` as in ``sinkhorn_f64``: pair b's matches and scores are those of the pair run alone (no match: -1; the rule of
-    mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0."""
+    mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0.  ``form='streaming'`` as in ``sinkhorn_f64``."""
     _need_cuda(scores)
     if counts is not None and scores.requires_grad:
         raise RuntimeError('sinkhorn_f64_extract(counts=): ragged batches run the forward only (no gradient)')
@@ -346,8 +366,7 @@ def sinkhorn_f64_extract(scores: torch.Tensor, bin_score: float, iters: int, mod
     m0, m1, s0, s1, Z = _match_outputs(B, N, M, s.device, want_Z)
     lib = _lib.load()
     with torch.cuda.device(s.device):
-        name, lead, _keep = _entry('mdgat_sinkhorn_f64_extract', counts, B, s.device)
-        size = lib.mdgat_sinkhorn_f64_workspace_bytes if counts is None else lib.mdgat_sinkhorn_f64_ragged_workspace_bytes
+        name, lead, _keep, size = _sinkhorn_f64_entry('mdgat_sinkhorn_f64_extract', counts, form, B, s.device)
         ws, base, need = _workspace(size(B, N, M), s.device)
         _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
                                       m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Z.data_ptr() if Z is not None else None, base, need, _stream(s)), name)

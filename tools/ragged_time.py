@@ -19,7 +19,17 @@ The fp32-class legs, in the same run (a float32 module with config['ragged_arith
   (f32 d) one ``match_frames_ragged`` of the 64 out of the bank uploaded beforehand (the encoder kernel reads the records itself);
   (f32 d') the same with ``ops.pack_frames`` and the upload inside the clock;
   (f32 gloabal) for the record, ``forward_ragged`` of the packed 64 on a float32 'FPFH_gloabal' module (its encoders in fp64).
-Device-synchronised host clock; the median of --windows windows and their spread (min .. max)."""
+Device-synchronised host clock; the median of --windows windows and their spread (min .. max).
+
+Ranges beyond the register-resident fp64 Sinkhorn (575 keypoints): ``--ragged_sinkhorn auto`` (or ``streaming``) builds the exact module
+with that config key, and the ranges ``--lo 512 --hi 1024`` and ``--lo 1024 --hi 2048`` then run the exact legs on the streaming fp64
+Sinkhorn with per-pair counts.  Its K workspace follows the SLOT (35.6 MB per pair at 2048; 16 pairs: 570 MB), so --pairs defaults to 16
+and 8 there, 64 below.  The fp32-class ragged forward holds 512 keypoints per frame: its legs are left out of larger ranges.
+
+``--per_op``: instead of all the above, the streaming ragged per-op launch (``ops.sinkhorn_f64(..., counts=, form='streaming')``, 100
+iterations) on the counts (40, 1200), (1100, 40), (40, 33), (64, 64) in their slots of 1100 x 1200, against the uniform streaming launch
+of four pairs of the slot size, and the same with the four repeated eight times (32 pairs: beyond the launch-latency floor of the 201
+launches): small pairs in large slots must cost less than the slot."""
 import argparse
 import json
 import os
@@ -35,7 +45,10 @@ from mdgat_matcher_amd import MDGAT, ops, synth  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--pairs', type=int, default=64)
+    ap.add_argument('--pairs', type=int, default=None, help='default: 64 up to 575 keypoints, 16 up to 1024, 8 beyond')
+    ap.add_argument('--ragged_sinkhorn', choices=['resident', 'auto', 'streaming'], default='resident',
+                    help="config['ragged_sinkhorn'] of the exact module; counts beyond 575 need 'auto' or 'streaming'")
+    ap.add_argument('--per_op', action='store_true', help='the streaming ragged Sinkhorn launch against the uniform one of the slot size')
     ap.add_argument('--lo', type=int, default=128)
     ap.add_argument('--hi', type=int, default=256)
     ap.add_argument('--windows', type=int, default=7)
@@ -43,9 +56,16 @@ def main():
     ap.add_argument('--profile', action='store_true', help='per-stage times of one ragged call (mdgat_profile)')
     a = ap.parse_args()
     dev = 'cuda:0'
+    if a.per_op:
+        return per_op(dev, a.windows)
+    if a.pairs is None:
+        a.pairs = 64 if a.hi <= MDGAT.RAGGED_MAX_KEYPOINTS else 16 if a.hi <= 1024 else 8
+    if a.hi > MDGAT.RAGGED_MAX_KEYPOINTS and a.ragged_sinkhorn == 'resident':
+        ap.error(f'counts up to {a.hi} are beyond the register-resident fp64 Sinkhorn ({MDGAT.RAGGED_MAX_KEYPOINTS}): --ragged_sinkhorn auto')
+    with_f32 = a.hi <= MDGAT.RAGGED_FP32_MAX_KEYPOINTS
     L = 9
     cfg = synth.default_config(L=L, sinkhorn_iterations=100)
-    net = MDGAT(cfg).double()
+    net = MDGAT({**cfg, 'ragged_sinkhorn': a.ragged_sinkhorn}).double()
     net.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net = net.eval().to(dev)
     net32 = MDGAT({**cfg, 'ragged_arithmetic': 'module'})
@@ -95,6 +115,8 @@ def main():
             'f32_d_match_frames_ragged': lambda: net32.match_frames_ragged(bank, idx0, idx1),
             'f32_d_with_pack_frames': lambda: net32.match_frames_ragged(ops.pack_frames(frames, dev), idx0, idx1),
             'f32_gloabal_forward_ragged': lambda: net32g.forward_ragged(packed)}
+    if not with_f32:
+        legs = {k: v for k, v in legs.items() if not k.startswith('f32_')}
     times = {k: [] for k in legs}
     with torch.no_grad():
         for fn in legs.values():
@@ -109,13 +131,14 @@ def main():
                 times[name].append((time.perf_counter() - t0) * 1e3)
         prof = prof_d = prof32 = prof32_d = None
         if a.profile:
-            net32.profile(dev, True)
-            net32.forward_ragged(packed)
-            torch.cuda.synchronize()
-            prof32 = {k: v for k, v in net32.profile(dev, True).items() if v[1]}
-            net32.match_frames_ragged(bank, idx0, idx1)
-            torch.cuda.synchronize()
-            prof32_d = {k: v for k, v in net32.profile(dev, False).items() if v[1]}
+            if with_f32:
+                net32.profile(dev, True)
+                net32.forward_ragged(packed)
+                torch.cuda.synchronize()
+                prof32 = {k: v for k, v in net32.profile(dev, True).items() if v[1]}
+                net32.match_frames_ragged(bank, idx0, idx1)
+                torch.cuda.synchronize()
+                prof32_d = {k: v for k, v in net32.profile(dev, False).items() if v[1]}
             net.profile(dev, True)
             run_b()
             torch.cuda.synchronize()
@@ -128,7 +151,7 @@ def main():
     # row-wise launches with N_b + M_b; both ratios are given
     quad = sum(n * n + m * m + 2 * n * m for n, m in counts) / (a.pairs * (Np + Mp) ** 2)
     lin = sum(n + m for n, m in counts) / (a.pairs * (Np + Mp))
-    res = {'pairs': a.pairs, 'counts': [a.lo, a.hi], 'Np': Np, 'Mp': Mp, 'windows': a.windows,
+    res = {'pairs': a.pairs, 'counts': [a.lo, a.hi], 'Np': Np, 'Mp': Mp, 'windows': a.windows, 'ragged_sinkhorn': a.ragged_sinkhorn,
            'ms_median': med, 'ms_min_max': {k: [float(min(v)), float(max(v))] for k, v in times.items()},
            'ms_per_pair': {k: v / a.pairs for k, v in med.items()},
            'ratio_a_over_b': med['a_single_pair_calls'] / med['b_forward_ragged'],
@@ -137,18 +160,59 @@ def main():
            'b_over_c': med['b_forward_ragged'] / med['c_uniform_largest'],
            'd_over_b': med['d_match_frames_ragged'] / med['b_forward_ragged'],
            'd_pack_over_b_list': med['d_with_pack_frames'] / med['b_list_with_packing'],
-           'f32_ratio_a_over_b': med['f32_a_single_pair_calls'] / med['f32_b_forward_ragged'],
-           'f32_b_over_c': med['f32_b_forward_ragged'] / med['f32_c_uniform_largest'],
-           'f32_b_over_exact_b': med['f32_b_forward_ragged'] / med['b_forward_ragged'],
-           'f32_d_over_b': med['f32_d_match_frames_ragged'] / med['f32_b_forward_ragged'],
-           'f32_d_pack_over_b_list': med['f32_d_with_pack_frames'] / med['f32_b_list_with_packing'],
            'pairs_per_s': {k: 1e3 * a.pairs / v for k, v in med.items()}}
+    if with_f32:
+        res.update({'f32_ratio_a_over_b': med['f32_a_single_pair_calls'] / med['f32_b_forward_ragged'],
+                    'f32_b_over_c': med['f32_b_forward_ragged'] / med['f32_c_uniform_largest'],
+                    'f32_b_over_exact_b': med['f32_b_forward_ragged'] / med['b_forward_ragged'],
+                    'f32_d_over_b': med['f32_d_match_frames_ragged'] / med['f32_b_forward_ragged'],
+                    'f32_d_pack_over_b_list': med['f32_d_with_pack_frames'] / med['f32_b_list_with_packing']})
     if prof:
         res['profile_ms_launches'] = prof
         res['profile_ms_launches_d'] = prof_d
+    if prof32:
         res['profile_ms_launches_f32_b'] = prof32
         res['profile_ms_launches_f32_d'] = prof32_d
     print(json.dumps(res))
+
+
+def per_op(dev, windows):
+    for reps in (1, 8):
+        per_op_case(dev, windows, reps)
+
+
+def per_op_case(dev, windows, reps):
+    from mdgat_matcher_amd import _lib
+    counts = ((40, 1200), (1100, 40), (40, 33), (64, 64)) * reps
+    Np, Mp, iters = max(n for n, _ in counts), max(m for _, m in counts), 100
+    rs = np.random.RandomState(0)
+    s = torch.from_numpy(rs.standard_normal((len(counts), Np, Mp)) * 3.0).to(dev)
+    cnt = ([n for n, _ in counts], [m for _, m in counts])
+    cnt = {'counts0_host': torch.tensor(cnt[0], dtype=torch.int32), 'counts1_host': torch.tensor(cnt[1], dtype=torch.int32)}
+    cnt.update(counts0=cnt['counts0_host'].to(dev), counts1=cnt['counts1_host'].to(dev))
+    alone = [s[b:b + 1, :n, :m].contiguous() for b, (n, m) in enumerate(counts)]
+    lib = _lib.load()
+    legs = {'stream_ragged': lambda: ops.sinkhorn_f64(s, 1.0, iters, counts=cnt, form='streaming'),
+            'uniform_streaming_slot_size': lambda: ops.sinkhorn_f64(s, 1.0, iters),
+            'pairs_alone_streaming': lambda: [ops.sinkhorn_f64(x, 1.0, iters) for x in alone]}
+    times = {k: [] for k in legs}
+    prev = lib.mdgat_set_f64_sinkhorn_form(1)
+    try:
+        for fn in legs.values():
+            fn(); fn()
+        for _ in range(windows):
+            for name, fn in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    finally:
+        lib.mdgat_set_f64_sinkhorn_form(prev)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print(json.dumps({'per_op': 'sinkhorn_f64', 'counts': counts, 'Np': Np, 'Mp': Mp, 'iters': iters, 'windows': windows, 'ms_median': med,
+                      'ms_min_max': {k: [float(min(v)), float(max(v))] for k, v in times.items()},
+                      'ragged_over_uniform': med['stream_ragged'] / med['uniform_streaming_slot_size']}))
 
 
 if __name__ == '__main__':
