@@ -12,6 +12,9 @@
  * Conventions
  *   - plain pointers and sizes only; every data pointer is DEVICE memory unless stated otherwise;
  *   - all tensors are owned by the caller (PyTorch); the library keeps only its packed weights;
+ *   - a workspace and every output buffer may hold anything on entry: no result depends on what they held before the call (a
+ *     workspace may be re-used for another shape or another entry; the library clears, inside the call, whatever a kernel needs
+ *     cleared).  An optional output that an entry documents as "left untouched" is exactly that;
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream);
  *   - return 0 on success, a negative mdgat_status otherwise; mdgat_last_error() gives the text;
  *   - a handle is bound to one device: the forward entry points make it current for the length of the call and restore the

@@ -158,7 +158,10 @@ class _Counts(namedtuple('_Counts', 'd0 d1 h0 h1')):
 
 
 def _ragged_counts(counts, B, device) -> _Counts:
-    """counts: a pack_ragged dict, or (counts0, counts1) as tensors or sequences -> device and host int32 copies of both."""
+    """counts: a pack_ragged dict, or (counts0, counts1) as tensors or sequences -> device and host int32 copies of both
+    (a ``_Counts`` is handed back as it is)."""
+    if isinstance(counts, _Counts):
+        return counts
     if isinstance(counts, dict):
         h0, h1 = counts['counts0_host'], counts['counts1_host']
     else:
@@ -469,9 +472,29 @@ def topk_sel_to_masks(sel: torch.Tensor, B: int, N: int, M: int, cross: bool):
     return bits[:, :, :N, :nk0], bits[:, :, N:, :nk1]
 
 
+def _selection_masks(sel, B, N, M, cross, topk, cnt, device):
+    """The masks ``return_selection`` hands out: (mask0 [B, 4, N, keys of frame 0's source], mask1 [B, 4, M, keys of frame 1's source]).
+    A dynamic layer (``topk`` > 0): the library's selection words, decoded.  Full attention writes no words (include/mdgat_hip.h: "slices
+    of full-attention layers are left untouched") and is asked for none: every key of the query's source frame is kept - of a ragged
+    batch (``cnt``: its ``_Counts``), every key within the pair's counts for every query within them."""
+    if topk > 0:
+        return topk_sel_to_masks(sel, B, N, M, cross)
+    keys0, keys1 = (M, N) if cross else (N, M)
+    mask0 = torch.ones((B, 4, N, keys0), dtype=torch.bool, device=device)
+    mask1 = torch.ones((B, 4, M, keys1), dtype=torch.bool, device=device)
+    if cnt is not None:
+        n0, n1 = cnt.d0.to(torch.int64)[:, None, None, None], cnt.d1.to(torch.int64)[:, None, None, None]
+        k0, k1 = (n1, n0) if cross else (n0, n1)
+        rows, cols = (lambda n: torch.arange(n, device=device)[None, None, :, None]), (lambda n: torch.arange(n, device=device)[None, None, None, :])
+        mask0 &= (rows(N) < n0) & (cols(keys0) < k0)
+        mask1 &= (rows(M) < n1) & (cols(keys1) < k1)
+    return mask0, mask1
+
+
 def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None):
     """attention / dynamic_attention (mdgat.py:190-210).  qkv [B, N+M, 3, 4, 32] -> message [B, N+M, 128]
-    (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks).
+    (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks; full attention keeps
+    every key of a pair: all True within its counts).
     The fp32-class kernels have no backward: the result never carries a grad_fn (``attention_f64`` is the differentiable one).
 
     ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b has ``counts0[b]`` / ``counts1[b]`` keypoints in
@@ -486,13 +509,13 @@ def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, ret
     with torch.cuda.device(x.device):
         need = lib.mdgat_attention_workspace_bytes(B, N, M)
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if return_selection else None
-        name, lead, _keep = _entry('mdgat_attention', counts, B, x.device)
+        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if return_selection and topk > 0 else None
+        name, lead, cnt = _entry('mdgat_attention', counts, B, x.device)
         _lib.check(getattr(lib, name if counts is not None else 'mdgat_attention_sel')(
             B, N, M, *lead, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(), sel.data_ptr() if sel is not None else None,
             ws.data_ptr(), need, _stream(x)), name)
     if return_selection:
-        return msg, topk_sel_to_masks(sel, B, N, M, cross)
+        return msg, _selection_masks(sel, B, N, M, cross, int(topk), cnt, x.device)
     return msg
 
 
@@ -817,7 +840,7 @@ def _attention_f64_values(qkv, N, M, cross, topk, want_sel, counts=None):
     assert P == N + M and tuple(x.shape[2:]) == (3, 4, 32)
     msg = torch.empty((B, P, 128), dtype=torch.float64, device=x.device)
     with torch.cuda.device(x.device):
-        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if want_sel else None
+        sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if want_sel and int(topk) > 0 else None
         name, lead, _keep = _entry('mdgat_attention_f64', counts, B, x.device)
         _lib.check(getattr(_lib.load(), name)(B, N, M, *lead, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(),
                                               sel.data_ptr() if sel is not None else None, _stream(x)), name)
@@ -881,7 +904,8 @@ class _AttentionF64(torch.autograd.Function):
 
 def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None):
     """attention / dynamic_attention (mdgat.py:190-210) in fp64.  qkv [B, N+M, 3, 4, 32] float64 -> message [B, N+M, 128] float64
-    (with ``return_selection``: also the masks of the keys a dynamic layer kept, see topk_sel_to_masks).
+    (with ``return_selection``: also the masks of the keys a dynamic layer kept, see topk_sel_to_masks; full attention keeps every key of
+    a pair: all True within its counts).
 
     Differentiable with respect to qkv (``attention_f64_backward``; not twice): when qkv requires grad and grad is enabled the message
     carries a grad_fn.  The launch and the values are the same either way; a dynamic layer then always asks for the selection words
@@ -896,16 +920,17 @@ def attention_f64(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0,
     if counts is not None:
         if qkv.requires_grad and torch.is_grad_enabled():
             raise RuntimeError('attention_f64(counts=): ragged batches run the forward only (no gradient)')
-        msg, sel = _attention_f64_values(qkv, N, M, cross, topk, return_selection, counts)
-        return (msg, topk_sel_to_masks(sel, B, N, M, cross)) if return_selection else msg
+        cnt = _ragged_counts(counts, B, qkv.device)
+        msg, sel = _attention_f64_values(qkv, N, M, cross, topk, return_selection, cnt)
+        return (msg, _selection_masks(sel, B, N, M, cross, topk, cnt, msg.device)) if return_selection else msg
     if torch.is_grad_enabled() and qkv.requires_grad:
-        want_sel = topk > 0 or return_selection       # a dynamic layer always keeps its selection words
+        want_sel = topk > 0                           # a dynamic layer always keeps its selection words; full attention writes none
         out = _AttentionF64.apply(qkv, N, M, bool(cross), topk, want_sel)
         msg, sel = out if want_sel else (out, None)
     else:
         msg, sel = _attention_f64_values(qkv, N, M, cross, topk, return_selection)
     if return_selection:
-        return msg, topk_sel_to_masks(sel, B, N, M, cross)
+        return msg, _selection_masks(sel, B, N, M, cross, topk, None, msg.device)
     return msg
 
 
