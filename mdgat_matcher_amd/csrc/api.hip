@@ -275,9 +275,9 @@ struct Workspace {
     double* Z64;                           // ... and on an exact-mode handle, whose fp64 tail hands the loss the fp64 Z, room for that Z
     size_t total;   // bytes
 };
-// stream64: room for the streaming fp64 Sinkhorn on a ragged batch as well (a handle in mode 2 of mdgat_set_ragged_sinkhorn: that form at sizes
-// where the uniform forward runs the resident one)
-Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, bool stream64 = false) {
+// sk64: a form of the fp64 Sinkhorn to hold beside the one a uniform call runs at this shape (sinkhorn_f64_form) - a ragged call's, which
+// mdgat_set_ragged_sinkhorn can put on the streaming form at sizes where the uniform forward runs the resident one
+Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form sk64 = Sk64Form::unsupported) {
     const size_t R = (size_t)B * (N + M);
     Workspace w{};
     WsCarver c{static_cast<char*>(base)};
@@ -295,8 +295,8 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, bool strea
         c.take(w.qkv64, R * 384);     // qkv64 and hid64 are contiguous: the encoder stages live there
         c.take(w.hid64, R * 256);
         c.take(w.msg64, R * 128);
-        w.sk64_bytes = sinkhorn_f64_supported(N, M) ? sinkhorn_f64_workspace_bytes(B, N, M) : 0;
-        if (stream64 && w.sk64_bytes && sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M) > w.sk64_bytes) w.sk64_bytes = sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M);
+        const size_t uniform = sinkhorn_f64_workspace_bytes(B, N, M, sinkhorn_f64_form(N, M, false, 0)), beside = sinkhorn_f64_workspace_bytes(B, N, M, sk64);
+        w.sk64_bytes = beside > uniform ? beside : uniform;      // (0: the shape is beyond both forms)
         c.take(w.sk64, w.sk64_bytes ? w.sk64_bytes + sinkhorn_f64_bests(nullptr, B, N, M).bytes : 0);
         if ((size_t)N * M <= (size_t)384 * (N + M) || !w.sk64_bytes) w.scores64 = w.qkv64;
         else c.take(w.scores64, (size_t)B * N * M);
@@ -443,19 +443,13 @@ static LanePlan lane_plan(int lanes, int B, int N, int M, bool f64, bool loss) {
     return p;
 }
 
-// Would an exact ragged batch in slots of N x M run the streaming fp64 Sinkhorn on this handle (mdgat_set_ragged_sinkhorn)?  Mode 2, or mode 1
-// where the register-resident form takes no counts (a slot beyond 575, 576 rows included, or the form forced to 1).  ONE predicate for
-// plan_forward and for mdgat_workspace_bytes, which knows nothing of the call to come and so reserves the form's K whenever a ragged call
-// could need it.
-static bool ragged_sinkhorn_streams(const mdgat_handle* h, int N, int M) {
-    return h && (h->ragged_sinkhorn == 2 || (h->ragged_sinkhorn == 1 && !sinkhorn_f64_ragged_supported(N, M)));
-}
-
 static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool loss) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     // (taps run unsliced: the whole batch's workspace is the lower bound in every case)
     const bool f64 = h && h->cfg.arithmetic == MDGAT_ARITH_FP64;
-    const size_t whole = carve(nullptr, B, N, M, f64, loss, ragged_sinkhorn_streams(h, N, M)).total;
+    // (this knows nothing of the call to come: it holds the form an exact ragged batch in slots of N x M would run on this handle -
+    // mdgat_set_ragged_sinkhorn - beside the uniform call's, so the streaming form's K is there whenever a ragged call could need it)
+    const size_t whole = carve(nullptr, B, N, M, f64, loss, sinkhorn_f64_form(N, M, true, h ? h->ragged_sinkhorn : 0)).total;
     const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
@@ -485,7 +479,7 @@ struct Path {
     bool fused64;     // the fp64 encoders and layer tails as fused launches, the last one writing the hand-over to fp32
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
     int cnt_min;      // a ragged batch (FwdIn::counts): the smallest keypoint count of any frame; 0 otherwise
-    bool stream_ragged;   // an exact ragged batch on the streaming fp64 Sinkhorn (mdgat_set_ragged_sinkhorn: mode 2, or mode 1 where the resident form takes no counts)
+    Sk64Form sk64;    // the form of the fp64 Sinkhorn this call runs if it has the fp64 tail (sinkhorn_f64_form; a ragged batch: by mdgat_set_ragged_sinkhorn)
     LanePlan lanes;
 };
 
@@ -530,8 +524,8 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         return MDGAT_ERR_BAD_ARG;
     }
     p.lanes = (taps || in.counts) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
-    p.stream_ragged = in.counts && f64 && ragged_sinkhorn_streams(h, N, M);
-    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.stream_ragged).total;
+    p.sk64 = f64 ? sinkhorn_f64_form(N, M, (bool)in.counts, h->ragged_sinkhorn) : Sk64Form::unsupported;
+    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.sk64).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
     const int L2 = 2 * h->cfg.L;
@@ -572,7 +566,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         // over the padded rows, which the encoder makes from zeros.  One unsliced lane, no taps, no loss; the single-f16 attention mode has
         // no kernel that takes counts.  The counts - and the starts into a bank - are checked on their host copies before anything is enqueued.
         const char* who = in.bank ? "mdgat_forward_frames_ragged" : f64 ? "mdgat_forward_f64_ragged" : "mdgat_forward_ragged";
-        p.stream_ragged = false;      // (mdgat_set_ragged_sinkhorn is the exact tail's: this branch has no fp64 Sinkhorn)
+        p.sk64 = Sk64Form::unsupported;      // (mdgat_set_ragged_sinkhorn is the exact tail's: this branch has no fp64 Sinkhorn)
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
         if (in.rec0 && !in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
         if (h->cfg.attention_mode == 1) { mdgat_set_error("%s: attention_mode = 1 (single-f16 products) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
@@ -587,16 +581,16 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         // are checked on their host copies, against the whole k schedule (mdgat_check_ragged).
         const char* who = in.bank ? "mdgat_forward_frames_ragged" : "mdgat_forward_f64_ragged";
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
-        if (p.stream_ragged) {
-            // the handle opted in (mdgat_set_ragged_sinkhorn): the streaming Sinkhorn's RAGGED instantiations behind the same kernels, in
-            // slots up to the dynamic fp64 attention's limit
-            if (!p.tail64 || N > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || M > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || !sinkhorn_f64_stream_ragged_supported(N, M)) {
+        if (h->ragged_sinkhorn != 0 && p.sk64 != Sk64Form::resident) {
+            // the handle opted in (mdgat_set_ragged_sinkhorn: mode 2, or mode 1 where the resident form takes no counts): the streaming
+            // Sinkhorn's RAGGED instantiations behind the same kernels, in slots up to the dynamic fp64 attention's limit
+            if (!p.tail64 || N > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || M > MDGAT_RAGGED_WIDE_MAX_KEYPOINTS || p.sk64 != Sk64Form::streaming) {
                 mdgat_set_error("%s: ragged batches on the streaming Sinkhorn need the fp64 tail: f64_sinkhorn not off, f64_layers automatic, and at most "
                                 "%d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_WIDE_MAX_KEYPOINTS, N, M);
                 return MDGAT_ERR_UNSUPPORTED;
             }
         } else
-        if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || !sinkhorn_f64_ragged_supported(N, M)) {
+        if (!p.tail64 || N > MDGAT_RAGGED_MAX_KEYPOINTS || M > MDGAT_RAGGED_MAX_KEYPOINTS || p.sk64 != Sk64Form::resident) {
             mdgat_set_error("%s: ragged batches need the fp64 tail on the register-resident Sinkhorn: f64_sinkhorn not off, f64_layers automatic, "
                             "mdgat_set_f64_sinkhorn_form not 1, and at most %d keypoints per frame (Np=%d, Mp=%d)", who, MDGAT_RAGGED_MAX_KEYPOINTS, N, M);
             return MDGAT_ERR_UNSUPPORTED;
@@ -784,15 +778,14 @@ static int tail64(Fwd& f, const FwdOut& o, CoopGroup& coop) {
     if (int rc = launch_gemm_f64(sg, f.s)) return rc;
     f.mark(MDGAT_PROF_F64_GEMM);
     if (int rc = f.tap(f.taps.scores, scores64, (size_t)B * N * M)) return rc;
-    const Sk64Bests b = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
+    Sk64Call c{};
+    c.B = B; c.N = N; c.M = M; c.scores = scores64; c.alpha_dev = f.h->w.blob64 + f.h->w.bl.bin_score; c.iters = f.h->cfg.sinkhorn_iters;
+    c.Z64 = ws.Z64; c.Z32 = o.Z; c.inner = f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD;
+    c.bests = sinkhorn_f64_bests(ws.sk64 + ws.sk64_bytes, B, N, M);
+    c.cnt0 = f.cnt0; c.cnt1 = f.cnt1;
     const SkExtract ex = f.extract(o);
-    if (int rc = f.p.stream_ragged
-                     ? launch_sinkhorn_f64_stream_ragged(B, N, M, f.cnt0, f.cnt1, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z,
-                                                         f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD, b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.s,
-                                                         f.h->w.blob64 + f.h->w.bl.bin_score)
-                     : launch_sinkhorn_f64(B, N, M, scores64, 0.0, f.h->cfg.sinkhorn_iters, ws.Z64, o.Z, f.h->cfg.extract_mode >= MDGAT_EXTRACT_THRESHOLD,
-                                           b.ri, b.rv, b.ci, b.cv, ws.sk64, ws.sk64_bytes, f.guard(), coop, f.h->w.blob64 + f.h->w.bl.bin_score, f.cnt0, f.cnt1)) return rc;
-    if (int rc = launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, f.s, f.cnt0, f.cnt1)) return rc;
+    if (int rc = launch_sinkhorn_f64(c, f.p.sk64, ws.sk64, ws.sk64_bytes, f.s, &coop, f.guard())) return rc;
+    if (int rc = launch_extract_from_bests(B, N, M, &ex, c.bests.ri, c.bests.rv, c.bests.ci, c.bests.cv, f.s, f.cnt0, f.cnt1)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const double*>(ws.Z64));
 }
@@ -861,7 +854,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
 // one slice of a call (checked by plan_forward) on one lane
 static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
-    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.stream_ragged);
+    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.sk64);
     Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust,
           in.counts.cnt0, in.counts.cnt1, p.cnt_min};
     f.mark(-1);

@@ -360,25 +360,6 @@ __global__ __launch_bounds__(64 * S64_WAVES, S64_WAVES / 4) void sinkhorn_f64_ke
     }
 }
 
-// column arg-max over the G row slabs of a pair, in fp64: ascending slabs, strict compare (the first of equal maxima).  cnt1 (optional):
-// the pairs' own column counts in slots of M - columns beyond a pair's count are left alone
-__global__ __launch_bounds__(256) void sinkhorn_f64_merge_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val,
-                                                                 const int* cnt1) {
-    const size_t total = (size_t)B * M;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const size_t pair = e / M, j = e % M;
-        if (cnt1 && j >= (size_t)cnt1[pair]) continue;
-        const size_t base = pair * G * M + j;
-        double bv = sval[base];
-        int bi = sidx[base];
-        for (int g = 1; g < G; ++g)
-            if (sval[base + (size_t)g * M] > bv) { bv = sval[base + (size_t)g * M]; bi = sidx[base + (size_t)g * M]; }
-        cbest_idx[e] = bi;
-        cbest_val[e] = (float)bv;
-    }
-}
-
-
 // ---- the STREAMING form: frames beyond what the register-resident kernel holds (M + 1 > 576 or N > 576), up to 2175 keypoints ----
 // The same iteration, K = exp(Z0 - row maximum) written to memory ONCE (fp64, rows padded to 128 columns: 35.6 MB for a pair of 2048
 // keypoints) and streamed once per iteration - one launch per iteration, no workgroup waits for another inside a launch:
@@ -645,15 +626,17 @@ __global__ __launch_bounds__(512) void sinkhorn_f64_wide_final_kernel(Wk64Args a
     }
 }
 
-// the slab merge of a RAGGED streaming launch: sinkhorn_f64_merge_kernel over the pair's OWN slabs and columns (the slabs behind them
-// were written by nobody), cbest beyond the pair's columns left alone
-__global__ __launch_bounds__(256) void sinkhorn_f64_merge_ragged_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val,
-                                                                        const int* cnt0, const int* cnt1) {
+// Both forms: the column arg-max over the row slabs of a pair (W64_ROWS rows each, [B][G][M]), in fp64: ascending slabs, strict compare
+// (the first of equal maxima).  cnt0 / cnt1 (both or neither): a ragged batch in slots of G slabs by M columns - the merge runs over the
+// pair's OWN slabs (the streaming form leaves the slabs behind them unwritten; the resident form writes -inf there, which a strict
+// compare never takes) and columns, cbest beyond the pair's columns left alone
+__global__ __launch_bounds__(256) void sinkhorn_f64_merge_kernel(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val,
+                                                                 const int* cnt0, const int* cnt1) {
     const size_t total = (size_t)B * M;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const size_t pair = e / M, j = e % M;
-        if (j >= (size_t)cnt1[pair]) continue;
-        const int own = (cnt0[pair] + W64_ROWS - 1) / W64_ROWS;
+        if (cnt1 && j >= (size_t)cnt1[pair]) continue;
+        const int own = cnt0 ? (cnt0[pair] + W64_ROWS - 1) / W64_ROWS : G;
         const size_t base = pair * G * M + j;
         double bv = sval[base];
         int bi = sidx[base];
@@ -668,6 +651,7 @@ __global__ __launch_bounds__(256) void sinkhorn_f64_merge_ragged_kernel(const in
 
 static size_t s64_lds_bytes(int waves) { return ((size_t)waves * S64_SLOT + S64_SLOT) * sizeof(double) + (size_t)waves * S64_SLOT * sizeof(int); }
 
+// ---- which form runs a call, and its workspace (sinkhorn_f64.hpp) ----
 static bool s64_resident_supported(int N, int M) { return N >= 1 && M >= 1 && M + 1 <= 64 * S64_NC && N <= 32 * S64_GMAX; }
 static bool s64_wide_supported(int N, int M) { return N >= 1 && M >= 1 && M + 1 <= 128 * W64_NC2MAX && N + 1 <= 128 * W64_NC2MAX; }
 
@@ -685,35 +669,48 @@ extern "C" int mdgat_set_f64_sinkhorn_form(int mode) {
     g_s64_form.store(mode == 1 ? 1 : mode == -1 ? -1 : -2, std::memory_order_relaxed);
     return prev;
 }
-static bool s64_use_wide(int N, int M) { return !s64_resident_supported(N, M) || (s64_form() == 1 && s64_wide_supported(N, M)); }
+
+// (the resident kernel holds 576 rows and 575 columns; the ragged entries document and take one limit for both frames)
+static_assert(MDGAT_RAGGED_MAX_KEYPOINTS == 64 * S64_NC - 1 && MDGAT_RAGGED_MAX_KEYPOINTS <= 32 * S64_GMAX, "the ragged limit is the resident kernel's");
+Sk64Form sinkhorn_f64_form(int N, int M, bool ragged, int ragged_mode) {
+    const bool resident = s64_resident_supported(N, M) && (!ragged || N <= MDGAT_RAGGED_MAX_KEYPOINTS) && s64_form() != 1;
+    if (resident && !(ragged && ragged_mode == 2)) return Sk64Form::resident;
+    if (s64_wide_supported(N, M) && !(ragged && ragged_mode == 0)) return Sk64Form::streaming;
+    return Sk64Form::unsupported;
+}
+
+// both forms' row slabs, and the streaming form's row length: whole 128-column chunks that hold the dustbin column
+static size_t s64_slabs(size_t N) { return (N + W64_ROWS - 1) / W64_ROWS; }
+static size_t s64_padded_columns(size_t M) { return (M + 1 + 127) & ~127; }
 
 // the streaming form's workspace (a null base: its size only); sval / sidx: the column slabs of the extraction's arg-maxes
-struct Wk64Ws { double *K, *rmax, *av, *P, *bvec, *sval; int* sidx; size_t bytes; };
+struct Wk64Ws { double *K, *rmax, *av, *P, *bvec, *sval; int* sidx; int Mp, G; size_t bytes; };
 static Wk64Ws s64_wide_carve(void* base, int B, int N, int M) {
-    const size_t Mp = ((size_t)M + 1 + 127) & ~(size_t)127, G = ((size_t)N + W64_ROWS - 1) / W64_ROWS;
+    const size_t Mp = s64_padded_columns(M), G = s64_slabs(N);
     Wk64Ws w{};
     WsCarver c{static_cast<char*>(base)};
     c.take(w.K, (size_t)B * N * Mp); c.take(w.rmax, (size_t)B * N); c.take(w.av, (size_t)B * (N + 1));
     c.take(w.P, (size_t)B * 2 * G * Mp); c.take(w.bvec, (size_t)B * Mp);
     c.take(w.sval, (size_t)B * G * M); c.take(w.sidx, (size_t)B * G * M);
-    w.bytes = c.bytes;
+    w.Mp = (int)Mp; w.G = (int)G; w.bytes = c.bytes;
     return w;
 }
 
 // the register-resident form's workspace, sized for the eight-wave workgroups (the larger slab count)
-struct Sk64Ws { double* slots; unsigned* flags; double* sval; int* sidx; size_t bytes; };
+struct Sk64Ws { double* slots; unsigned* flags; double* sval; int* sidx; int G; size_t bytes; };
 static Sk64Ws s64_resident_carve(void* base, int B, int N, int M) {
-    const size_t G = (N + 31) / 32;
+    const size_t G = s64_slabs(N);
     Sk64Ws w{};
     WsCarver c{static_cast<char*>(base)};
     c.take(w.slots, (size_t)B * 2 * G * S64_SLOT); c.take(w.flags, (size_t)B * 3 * G);
     c.take(w.sval, (size_t)B * G * M); c.take(w.sidx, (size_t)B * G * M);
-    w.bytes = c.bytes;
+    w.G = (int)G; w.bytes = c.bytes;
     return w;
 }
 
-size_t sinkhorn_f64_workspace_bytes(int B, int N, int M) {
-    return B <= 0 ? 0 : s64_use_wide(N, M) ? s64_wide_carve(nullptr, B, N, M).bytes : s64_resident_carve(nullptr, B, N, M).bytes;
+size_t sinkhorn_f64_workspace_bytes(int B, int N, int M, Sk64Form form) {
+    if (B <= 0 || form == Sk64Form::unsupported) return 0;
+    return form == Sk64Form::streaming ? s64_wide_carve(nullptr, B, N, M).bytes : s64_resident_carve(nullptr, B, N, M).bytes;
 }
 
 Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M) {
@@ -725,26 +722,41 @@ Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M) {
     return b;
 }
 
-bool sinkhorn_f64_supported(int N, int M) { return s64_resident_supported(N, M) || s64_wide_supported(N, M); }
-// (the resident kernel holds 576 rows and 575 columns; the ragged entries document and take one limit for both frames)
-static_assert(MDGAT_RAGGED_MAX_KEYPOINTS == 64 * S64_NC - 1 && MDGAT_RAGGED_MAX_KEYPOINTS <= 32 * S64_GMAX, "the ragged limit is the resident kernel's");
-bool sinkhorn_f64_ragged_supported(int N, int M) {
-    return s64_resident_supported(N, M) && N <= MDGAT_RAGGED_MAX_KEYPOINTS && M <= MDGAT_RAGGED_MAX_KEYPOINTS && s64_form() != 1;
+// ---- what the two forms' launches share ----
+// a ragged batch: the kernels write a pair's own block of Z only - the rest of every padded slot is zero
+static int s64_zero_Z(const Sk64Call& c, hipStream_t s) {
+    const size_t n = (size_t)c.B * (c.N + 1) * (c.M + 1);
+    if (c.Z64) if (int rc = mdgat_check_hip(hipMemsetAsync(c.Z64, 0, n * sizeof(double), s), "memset(fp64 Sinkhorn Z)")) return rc;
+    if (c.Z32) if (int rc = mdgat_check_hip(hipMemsetAsync(c.Z32, 0, n * sizeof(float), s), "memset(fp64 Sinkhorn Z32)")) return rc;
+    return MDGAT_OK;
 }
 
-// both forms: the column arg-maxes of the G row slabs merged in fp64, if the caller asked for them
-static int s64_merge_columns(const int* sidx, const double* sval, int B, int G, int M, int* cbest_idx, float* cbest_val, hipStream_t s,
-                             const int* cnt1 = nullptr) {
-    if (!cbest_idx) return MDGAT_OK;
-    const size_t total = (size_t)B * M;
-    hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, sidx, sval, B, G, M,
-                       cbest_idx, cbest_val, cnt1);
+// the column arg-maxes of the G row slabs merged in fp64, if the caller asked for them
+static int s64_merge_columns(const Sk64Call& c, const int* sidx, const double* sval, int G, hipStream_t s) {
+    if (!c.bests.ci) return MDGAT_OK;
+    const size_t blocks = ((size_t)c.B * c.M + 255) / 256;
+    hipLaunchKernelGGL(sinkhorn_f64_merge_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, sidx, sval, c.B, G, c.M, c.bests.ci, c.bests.cv,
+                       c.cnt0, c.cnt1);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 merge launch");
 }
 
+// ---- the streaming form's launches: a uniform or a ragged call (the kernels' RAGGED instantiations over slots of N x M), and the
+// backward's history run ----
+// The workspace of a ragged call is the uniform launch's of the SLOT size - K is [B][N][Mp], 35.6 MB per pair at 2048, whatever the
+// pairs' own sizes: a pair's rows sit at the slot's strides (K is not compacted) and only its own extent is written and read.
+static Wk64Args s64_wide_args(const Sk64Call& c, const Wk64Ws& w) {
+    Wk64Args a{};
+    a.scores = c.scores; a.alpha = c.alpha; a.alpha_dev = c.alpha_dev; a.B = c.B; a.N = c.N; a.M = c.M; a.iters = c.iters; a.inner = c.inner;
+    a.Mp = w.Mp; a.G = w.G;
+    a.Z64 = c.Z64; a.Z32 = c.Z32; a.rbest_idx = c.bests.ri; a.rbest_val = c.bests.rv; a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;
+    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
+    a.cslab_idx = c.bests.ci ? w.sidx : nullptr; a.cslab_val = c.bests.ci ? w.sval : nullptr;
+    return a;
+}
+
 // final: the last launch (Z, the arg-maxes); without it (the backward's history run) the launches stop at b_iters
-template <int NC2, bool RAGGED = false>
-static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final = true) {
+template <int NC2, bool RAGGED>
+static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final) {
     Wk64Args a = a0;
     const size_t lds_it = (size_t)9 * a.Mp * sizeof(double), lds_fin = (size_t)a.Mp * (3 * sizeof(double) + sizeof(int));
     static std::atomic<unsigned long long> optin_it{0}, optin_fin{0};
@@ -759,92 +771,52 @@ static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final = tru
     if (final) hipLaunchKernelGGL((sinkhorn_f64_wide_final_kernel<NC2, RAGGED>), dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming) launch");
 }
-
-static int launch_sinkhorn_f64_wide(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
-                                    float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, hipStream_t s, const double* alpha_dev) {
-    Wk64Args a{};
-    a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.inner = inner;
-    a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
-    a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val;
-    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
-    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
-    a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
+// (the register budget NC2 follows the SLOT: a pair's own chunk count only bounds what its lanes load)
+template <bool RAGGED>
+static int s64_wide_dispatch(const Wk64Args& a, hipStream_t s, bool final) {
     const int nc2 = a.Mp >> 7;
-    int rc = nc2 <= 5 ? s64_wide_launches<5>(a, s) : nc2 <= 9 ? s64_wide_launches<9>(a, s) : s64_wide_launches<W64_NC2MAX>(a, s);
-    if (rc) return rc;
-    return s64_merge_columns(w.sidx, w.sval, B, a.G, M, cbest_idx, cbest_val, s);
+    return nc2 <= 5 ? s64_wide_launches<5, RAGGED>(a, s, final) : nc2 <= 9 ? s64_wide_launches<9, RAGGED>(a, s, final) : s64_wide_launches<W64_NC2MAX, RAGGED>(a, s, final);
 }
 
-// ---- the streaming form on a RAGGED batch: the kernels' RAGGED instantiations over slots of N x M (sinkhorn_f64.hpp) ----
-// The workspace is the uniform launch's of the SLOT size - K is [B][N][Mp], 35.6 MB per pair at 2048, whatever the pairs' own sizes: a
-// pair's rows sit at the slot's strides (K is not compacted) and only its own extent is written and read.
-bool sinkhorn_f64_stream_ragged_supported(int N, int M) { return s64_wide_supported(N, M); }
-size_t sinkhorn_f64_stream_ragged_workspace_bytes(int B, int N, int M) {
-    return B <= 0 || !s64_wide_supported(N, M) ? 0 : s64_wide_carve(nullptr, B, N, M).bytes;
+static int s64_launch_streaming(const Sk64Call& c, void* workspace, hipStream_t s) {
+    const Wk64Ws w = s64_wide_carve(workspace, c.B, c.N, c.M);
+    const Wk64Args a = s64_wide_args(c, w);
+    if (c.cnt0) if (int rc = s64_zero_Z(c, s)) return rc;
+    if (int rc = c.cnt0 ? s64_wide_dispatch<true>(a, s, true) : s64_wide_dispatch<false>(a, s, true)) return rc;
+    return s64_merge_columns(c, w.sidx, w.sval, w.G, s);
 }
-int launch_sinkhorn_f64_stream_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const double* scores, double alpha, int iters, double* Z64,
-                                      float* Z32, int inner, int* rbest_idx, float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace,
-                                      size_t workspace_bytes, hipStream_t s, const double* alpha_dev) {
-    if (B <= 0) return MDGAT_OK;
-    if (!cnt0 || !cnt1) { mdgat_set_error("fp64 Sinkhorn (streaming, ragged): null counts pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (!s64_wide_supported(N, M)) {
-        mdgat_set_error("fp64 Sinkhorn (streaming, ragged): padded sizes %d x %d > %d supported", N, M, 128 * W64_NC2MAX - 1);
+
+Sk64Stream sinkhorn_f64_stream_carve(void* base, int B, int N, int M) {
+    const Wk64Ws w = s64_wide_carve(base, B, N, M);
+    return Sk64Stream{w.K, w.P, w.bvec, w.Mp, w.G, w.bytes};
+}
+
+int sinkhorn_f64_stream_history(const Sk64Call& c, double* hist_a, int hist_lda, double* hist_b, void* workspace, hipStream_t s) {
+    if (c.B <= 0) return MDGAT_OK;
+    if (!s64_wide_supported(c.N, c.M)) {
+        mdgat_set_error("fp64 Sinkhorn (streaming): %d x %d keypoints > %d supported", c.N, c.M, 128 * W64_NC2MAX - 1);
         return MDGAT_ERR_UNSUPPORTED;
     }
-    if (!workspace || workspace_bytes < sinkhorn_f64_stream_ragged_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("fp64 Sinkhorn (streaming, ragged): workspace too small or not 256-byte aligned");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    Wk64Args a{};
-    a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.inner = inner;
-    a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
-    a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val; a.cnt0 = cnt0; a.cnt1 = cnt1;
-    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
-    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
-    a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
-    // (the kernels write a pair's own block of Z only: the rest of every padded slot is zero)
-    if (Z64) if (int rc = mdgat_check_hip(hipMemsetAsync(Z64, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(double), s), "memset(fp64 Sinkhorn Z)")) return rc;
-    if (Z32) if (int rc = mdgat_check_hip(hipMemsetAsync(Z32, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(float), s), "memset(fp64 Sinkhorn Z32)")) return rc;
-    // (the register budget follows the SLOT: a pair's own chunk count only bounds what its lanes load)
-    const int nc2 = a.Mp >> 7;
-    int rc = nc2 <= 5 ? s64_wide_launches<5, true>(a, s) : nc2 <= 9 ? s64_wide_launches<9, true>(a, s) : s64_wide_launches<W64_NC2MAX, true>(a, s);
-    if (rc || !cbest_idx) return rc;
-    const size_t total = (size_t)B * M;
-    hipLaunchKernelGGL(sinkhorn_f64_merge_ragged_kernel, dim3((unsigned)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024)), dim3(256), 0, s, w.sidx, w.sval,
-                       B, a.G, M, cbest_idx, cbest_val, cnt0, cnt1);
-    return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming, ragged) merge launch");
+    Wk64Args a = s64_wide_args(c, s64_wide_carve(workspace, c.B, c.N, c.M));
+    a.hist_a = hist_a; a.hist_b = hist_b; a.hist_lda = hist_lda;
+    return s64_wide_dispatch<false>(a, s, false);
 }
 
-int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha, int iters, double* Z64, float* Z32, int inner, int* rbest_idx,
-                        float* rbest_val, int* cbest_idx, float* cbest_val, void* workspace, size_t workspace_bytes, unsigned* error_word,
-                        CoopGroup& group, const double* alpha_dev, const int* cnt0, const int* cnt1) {
-    if (B <= 0) return MDGAT_OK;
-    const hipStream_t s = group.stream();
-    const bool ragged = cnt0 != nullptr;
-    if (ragged && (!cnt1 || !s64_resident_supported(N, M) || s64_form() == 1)) {
-        mdgat_set_error("fp64 Sinkhorn: per-pair counts run on the register-resident form only (padded sizes %d x %d, at most %d; form %d)", N, M,
-                        64 * S64_NC - 1, s64_form());
-        return cnt1 ? MDGAT_ERR_UNSUPPORTED : MDGAT_ERR_BAD_ARG;
-    }
-    if (!sinkhorn_f64_supported(N, M)) { mdgat_set_error("fp64 Sinkhorn: %d x %d keypoints > %d supported", N, M, 128 * W64_NC2MAX - 1); return MDGAT_ERR_UNSUPPORTED; }
-    if (!workspace || workspace_bytes < sinkhorn_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("fp64 Sinkhorn: workspace too small or not 256-byte aligned");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    if (s64_use_wide(N, M))
-        return launch_sinkhorn_f64_wide(B, N, M, scores, alpha, iters, Z64, Z32, inner, rbest_idx, rbest_val, cbest_idx, cbest_val, workspace, s, alpha_dev);
+// ---- the register-resident form's launch ----
+static int s64_launch_resident(const Sk64Call& c, void* workspace, hipStream_t s, CoopGroup& group, unsigned* error_word) {
     // Eight-wave workgroups at every launch size.  Sixteen-wave ones (64 rows, half the partners, one per CU) were 7 % faster once the
     // launch no longer gives every workgroup a CU (32 pairs of 512: 818 against 878 us per 100 iterations; one pair 602 against 432) -
     // at 128 registers with spills, a second grouping of the column sums (so results that depend on the batch a pair travels in), and a
     // code generation that turned to garbage under a harmless edit (profiles/NOTES_r6.md section 12): not kept.
     constexpr int waves = 8;
-    const int G = (N + 4 * waves - 1) / (4 * waves);
-    const Sk64Ws w = s64_resident_carve(workspace, B, N, M);
+    static_assert(4 * waves == W64_ROWS, "both forms' slabs have the rows s64_slabs and the merge kernel count with");
+    const Sk64Ws w = s64_resident_carve(workspace, c.B, c.N, c.M);
+    const int B = c.B, G = w.G;
     Sk64Args a{};
-    a.scores = scores; a.alpha = alpha; a.alpha_dev = alpha_dev; a.B = B; a.N = N; a.M = M; a.iters = iters; a.G = G; a.inner = inner;
-    a.Z64 = Z64; a.Z32 = Z32; a.rbest_idx = rbest_idx; a.rbest_val = rbest_val;
-    a.slots = w.slots; a.flags = w.flags; a.cslab_idx = cbest_idx ? w.sidx : nullptr; a.cslab_val = cbest_idx ? w.sval : nullptr;
-    a.error_word = error_word; a.cnt0 = cnt0; a.cnt1 = cnt1;
+    a.scores = c.scores; a.alpha = c.alpha; a.alpha_dev = c.alpha_dev; a.B = B; a.N = c.N; a.M = c.M; a.iters = c.iters; a.G = G; a.inner = c.inner;
+    a.Z64 = c.Z64; a.Z32 = c.Z32; a.rbest_idx = c.bests.ri; a.rbest_val = c.bests.rv;
+    a.slots = w.slots; a.flags = w.flags; a.cslab_idx = c.bests.ci ? w.sidx : nullptr; a.cslab_val = c.bests.ci ? w.sval : nullptr;
+    a.error_word = error_word; a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;
     // ONE launch of this kernel at a time per device: the caller's CoopGroup admits it after the previous waiting launch, whatever stream
     // that was on (coop_chain.hpp; shared with the clustered fp64 layer tail).  The workgroups of a pair wait for each other, and a
     // workgroup that waits holds its CU.  Within one launch that is safe - an XCD gets its pairs in order, each as a contiguous run of
@@ -857,10 +829,8 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
     const int groups = (B + 7) / 8;
     const size_t lds = s64_lds_bytes(waves);
     static std::atomic<unsigned long long> optin8{0}, optin8r{0};
-    if (ragged) {
-        // (the kernel writes a pair's own block of Z only: the rest of every padded slot is zero)
-        if (Z64) if (int rc = mdgat_check_hip(hipMemsetAsync(Z64, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(double), s), "memset(fp64 Sinkhorn Z)")) return rc;
-        if (Z32) if (int rc = mdgat_check_hip(hipMemsetAsync(Z32, 0, (size_t)B * (N + 1) * (M + 1) * sizeof(float), s), "memset(fp64 Sinkhorn Z32)")) return rc;
+    if (c.cnt0) {
+        if (int rc = s64_zero_Z(c, s)) return rc;
         if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(sinkhorn_f64_kernel<8, true>), lds, optin8r, "sinkhorn_f64 (ragged) LDS")) return rc;
         hipLaunchKernelGGL((sinkhorn_f64_kernel<8, true>), dim3(groups * 8 * G), dim3(512), lds, s, a);
     } else {
@@ -868,83 +838,67 @@ int launch_sinkhorn_f64(int B, int N, int M, const double* scores, double alpha,
         hipLaunchKernelGGL((sinkhorn_f64_kernel<8, false>), dim3(groups * 8 * G), dim3(512), lds, s, a);
     }
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
-    return s64_merge_columns(w.sidx, w.sval, B, G, M, cbest_idx, cbest_val, s, cnt1);
+    return s64_merge_columns(c, w.sidx, w.sval, G, s);
 }
 
-// ---- the streaming form's iterations with their potential history, for the backward (sinkhorn_grad.hip) ----
-Sk64Stream sinkhorn_f64_stream_carve(void* base, int B, int N, int M) {
-    const Wk64Ws w = s64_wide_carve(base, B, N, M);
-    return Sk64Stream{w.K, w.P, w.bvec, (M + 1 + 127) & ~127, (N + W64_ROWS - 1) / W64_ROWS, w.bytes};
-}
-
-int sinkhorn_f64_stream_history(int B, int N, int M, const double* scores, double alpha, int iters, double* hist_a, int hist_lda, double* hist_b,
-                                void* workspace, hipStream_t s) {
-    if (B <= 0) return MDGAT_OK;
-    if (!s64_wide_supported(N, M)) { mdgat_set_error("fp64 Sinkhorn (streaming): %d x %d keypoints > %d supported", N, M, 128 * W64_NC2MAX - 1); return MDGAT_ERR_UNSUPPORTED; }
-    Wk64Args a{};
-    a.scores = scores; a.alpha = alpha; a.B = B; a.N = N; a.M = M; a.iters = iters;
-    a.Mp = (M + 1 + 127) & ~127; a.G = (N + W64_ROWS - 1) / W64_ROWS;
-    const Wk64Ws w = s64_wide_carve(workspace, B, N, M);
-    a.K = w.K; a.rmax = w.rmax; a.av = w.av; a.P = w.P; a.bvec = w.bvec;
-    a.hist_a = hist_a; a.hist_b = hist_b; a.hist_lda = hist_lda;
-    const int nc2 = a.Mp >> 7;
-    return nc2 <= 5 ? s64_wide_launches<5>(a, s, false) : nc2 <= 9 ? s64_wide_launches<9>(a, s, false) : s64_wide_launches<W64_NC2MAX>(a, s, false);
-}
-
-// ---- per-op entry points (include/mdgat_hip.h) ----
-extern "C" size_t mdgat_sinkhorn_f64_workspace_bytes(int B, int N, int M) {
-    if (B <= 0 || N <= 0 || M <= 0) return 0;
-    return sinkhorn_f64_workspace_bytes(B, N, M) + sinkhorn_f64_bests(nullptr, B, N, M).bytes;
-}
-
-extern "C" int mdgat_sinkhorn_f64(int B, int N, int M, const double* scores, double bin_score, int iters, double* Z, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
-    if (!scores || !Z) { mdgat_set_error("mdgat_sinkhorn_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("mdgat_sinkhorn_f64: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    CoopGroup group;
-    if (int rc = group.open(mdgat_current_device(), static_cast<hipStream_t>(stream))) return rc;
-    return launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, nullptr, group);
-}
-
-extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double bin_score, int iters, int mode, float match_threshold,
-                                          int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
-    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_sinkhorn_f64_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("mdgat_sinkhorn_f64_extract: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("mdgat_sinkhorn_f64_extract: workspace too small or not 256-byte aligned");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t kb = sinkhorn_f64_workspace_bytes(B, N, M);
-    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, N, M);
-    const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
-    {
-        CoopGroup group;
-        if (int rc = group.open(mdgat_current_device(), s)) return rc;
-        if (int rc = launch_sinkhorn_f64(B, N, M, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv, workspace, kb, nullptr, group))
-            return rc;
-    }
-    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    return launch_extract_from_bests(B, N, M, &ex, b.ri, b.rv, b.ci, b.cv, s);
-}
-
-// ---- ragged batches (include/mdgat_hip.h): pairs of different sizes in slots padded to Np x Mp ----
-// The counts come twice: on the device for the kernels, and on the host for the checks made before anything is launched: these entries'
-// own limit on the slots, then the per-pair checks every ragged entry makes (ragged.hpp).
-static int s64_check_counts(const char* who, int B, int Np, int Mp, const int32_t* c0, const int32_t* c1, const int32_t* h0, const int32_t* h1) {
-    if (!s64_resident_supported(Np, Mp) || Np > MDGAT_RAGGED_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_MAX_KEYPOINTS) {
-        mdgat_set_error("%s: padded sizes %d x %d: ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_MAX_KEYPOINTS);
+// The form is the caller's decision; what is checked here is that sinkhorn_f64_form gives it to a call like this one under some ragged
+// mode (0 the resident form, 2 the streaming one), that the resident form has its group, and the workspace.
+int launch_sinkhorn_f64(const Sk64Call& c, Sk64Form form, void* workspace, size_t workspace_bytes, hipStream_t s, CoopGroup* group, unsigned* error_word) {
+    if (c.B <= 0) return MDGAT_OK;
+    const bool ragged = c.cnt0 || c.cnt1;
+    if (ragged && (!c.cnt0 || !c.cnt1)) { mdgat_set_error("fp64 Sinkhorn: null counts pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (!sinkhorn_f64_supported(c.N, c.M)) {
+        mdgat_set_error("fp64 Sinkhorn: %d x %d keypoints > %d supported", c.N, c.M, 128 * W64_NC2MAX - 1);
         return MDGAT_ERR_UNSUPPORTED;
     }
-    return mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{c0, c1, h0, h1}, nullptr, nullptr, 0, nullptr);
+    const bool streaming = form == Sk64Form::streaming;
+    if (form == Sk64Form::unsupported || sinkhorn_f64_form(c.N, c.M, ragged, streaming ? 2 : 0) != form || (!streaming && !group)) {
+        mdgat_set_error("fp64 Sinkhorn: the %s form does not hold this call (%d x %d keypoints%s, form %d)", streaming ? "streaming" : "register-resident", c.N, c.M,
+                        ragged ? ", per-pair counts" : "", s64_form());
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (!workspace || workspace_bytes < sinkhorn_f64_workspace_bytes(c.B, c.N, c.M, form) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        mdgat_set_error("fp64 Sinkhorn: workspace too small or not 256-byte aligned");
+        return MDGAT_ERR_BAD_ARG;
+    }
+    return streaming ? s64_launch_streaming(c, workspace, s) : s64_launch_resident(c, workspace, s, *group, error_word);
 }
-// The error word sits behind the uniform entries' workspace.  Reading it back is the one synchronisation of these entries: a launch
-// whose workgroups gave up waiting for each other returns an error, not numbers.
-static size_t s64_ragged_word_offset(int B, int Np, int Mp) { return (mdgat_sinkhorn_f64_workspace_bytes(B, Np, Mp) + 255) & ~(size_t)255; }
+
+// ---- per-op entry points (include/mdgat_hip.h): the uniform pair, and for ragged batches - pairs of different sizes in slots padded to
+// Np x Mp - the pair on the resident form (slots within 575; synchronous: the error word is read back) and the pair on the streaming
+// form (slots within 2175, asynchronous) ----
+// An entry's workspace: the form's own (a shape beyond both forms is sized as the streaming one, as ever: the call refuses it), the
+// arg-maxes behind it and, for a ragged batch on the resident form, the error word behind those.  Reading that word back is the one
+// synchronisation of these entries: a launch whose workgroups gave up waiting for each other returns an error, not numbers.
+static size_t s64_op_kernel_bytes(int B, int N, int M, Sk64Form form) {
+    return sinkhorn_f64_workspace_bytes(B, N, M, form == Sk64Form::unsupported ? Sk64Form::streaming : form);
+}
+static size_t s64_op_word_offset(int B, int N, int M, Sk64Form form) {
+    return (s64_op_kernel_bytes(B, N, M, form) + sinkhorn_f64_bests(nullptr, B, N, M).bytes + 255) & ~(size_t)255;
+}
+static size_t s64_op_bytes(int B, int N, int M, Sk64Form form, bool ragged) {
+    if (B <= 0 || N <= 0 || M <= 0) return 0;
+    if (ragged && form == Sk64Form::resident) return s64_op_word_offset(B, N, M, form) + 256;
+    return s64_op_kernel_bytes(B, N, M, form) + sinkhorn_f64_bests(nullptr, B, N, M).bytes;
+}
+extern "C" size_t mdgat_sinkhorn_f64_workspace_bytes(int B, int N, int M) { return s64_op_bytes(B, N, M, sinkhorn_f64_form(N, M, false, 0), false); }
 extern "C" size_t mdgat_sinkhorn_f64_ragged_workspace_bytes(int B, int Np, int Mp) {
-    if (B <= 0 || Np <= 0 || Mp <= 0 || !s64_resident_supported(Np, Mp) || Np > MDGAT_RAGGED_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_MAX_KEYPOINTS || s64_form() == 1) return 0;
-    return s64_ragged_word_offset(B, Np, Mp) + 256;
+    return sinkhorn_f64_form(Np, Mp, true, 0) == Sk64Form::resident ? s64_op_bytes(B, Np, Mp, Sk64Form::resident, true) : 0;
+}
+extern "C" size_t mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(int B, int Np, int Mp) {
+    return sinkhorn_f64_form(Np, Mp, true, 2) == Sk64Form::streaming ? s64_op_bytes(B, Np, Mp, Sk64Form::streaming, true) : 0;
+}
+
+// The counts come twice: on the device for the kernels, and on the host for the checks made before anything is launched: the form's
+// own limit on the slots, then the per-pair checks every ragged entry makes (ragged.hpp).
+static int s64_check_counts(const char* who, int B, int Np, int Mp, const RaggedCounts& counts, Sk64Form form) {
+    const int limit = form == Sk64Form::resident ? MDGAT_RAGGED_MAX_KEYPOINTS : 128 * W64_NC2MAX - 1;
+    if (Np > limit || Mp > limit) {
+        mdgat_set_error(form == Sk64Form::resident ? "%s: padded sizes %d x %d: ragged batches hold at most %d keypoints per frame"
+                                                   : "%s: padded sizes %d x %d: the streaming form holds at most %d keypoints per frame", who, Np, Mp, limit);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    return mdgat_check_ragged(who, B, Np, Mp, counts, nullptr, nullptr, 0, nullptr);
 }
 static int s64_ragged_finish(const char* who, unsigned* word, hipStream_t s) {
     unsigned host = 0;
@@ -954,112 +908,97 @@ static int s64_ragged_finish(const char* who, unsigned* word, hipStream_t s) {
     return MDGAT_OK;
 }
 
-extern "C" int mdgat_sinkhorn_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
-                                         const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_sinkhorn_f64_ragged";
-    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (int rc = s64_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
-    if (s64_form() == 1) { mdgat_set_error("%s: the streaming form (mdgat_set_f64_sinkhorn_form(1)) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
-    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+// ONE body for the six entries.  c: the call without its counts, Z64 set by the entries that return Z; counts: null for the uniform
+// entries, else with ragged_mode the form the entry runs (0: resident, 2: streaming); ex: the extraction request of the entries that
+// return matches (they hand c.Z32 out, optionally).
+static int s64_op(const char* who, Sk64Call c, const RaggedCounts* counts, int ragged_mode, const SkExtract* ex, void* workspace, size_t workspace_bytes,
+                  hipStream_t s) {
+    const int B = c.B, N = c.N, M = c.M;
+    if (!c.scores || (ex ? !ex->m0 || !ex->m1 || !ex->s0 || !ex->s1 : !c.Z64)) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (counts) {
+        if (B < 0 || N <= 0 || M <= 0 || c.iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, N, M, c.iters); return MDGAT_ERR_BAD_ARG; }
+        if (ex && (ex->mode < 0 || ex->mode > 3)) { mdgat_set_error("%s: bad mode %d", who, ex->mode); return MDGAT_ERR_BAD_ARG; }
+        if (B == 0) return MDGAT_OK;
+        if (int rc = s64_check_counts(who, B, N, M, *counts, ragged_mode == 2 ? Sk64Form::streaming : Sk64Form::resident)) return rc;
+        c.cnt0 = counts->cnt0; c.cnt1 = counts->cnt1;
+    } else if (N <= 0 || M <= 0 || c.iters < 0) { mdgat_set_error("%s: bad shape N=%d M=%d iters=%d", who, N, M, c.iters); return MDGAT_ERR_BAD_ARG; }
+    const Sk64Form form = sinkhorn_f64_form(N, M, counts != nullptr, ragged_mode);
+    // (slots within the entry's limit: only the forced form leaves a ragged batch without one)
+    if (counts && form == Sk64Form::unsupported) { mdgat_set_error("%s: the streaming form (mdgat_set_f64_sinkhorn_form(1)) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
+    // (the uniform entry that returns Z has no arg-maxes behind its workspace: the launcher's own check is all it needs)
+    if ((counts || ex) && (!workspace || workspace_bytes < s64_op_bytes(B, N, M, form, counts != nullptr) || (reinterpret_cast<uintptr_t>(workspace) & 255))) {
         mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
         return MDGAT_ERR_BAD_ARG;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned* word = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + s64_ragged_word_offset(B, Np, Mp));
-    if (int rc = mdgat_check_hip(hipMemsetAsync(word, 0, 256, s), "memset(fp64 Sinkhorn error word)")) return rc;
-    {
-        CoopGroup group;
-        if (int rc = group.open(mdgat_current_device(), s)) return rc;
-        if (int rc = launch_sinkhorn_f64(B, Np, Mp, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace,
-                                         sinkhorn_f64_workspace_bytes(B, Np, Mp), word, group, nullptr, counts0, counts1)) return rc;
+    unsigned* word = nullptr;
+    if (counts && form == Sk64Form::resident) {
+        word = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + s64_op_word_offset(B, N, M, form));
+        if (int rc = mdgat_check_hip(hipMemsetAsync(word, 0, 256, s), "memset(fp64 Sinkhorn error word)")) return rc;
     }
-    return s64_ragged_finish(who, word, s);
+    if (ex) {
+        c.bests = sinkhorn_f64_bests(static_cast<char*>(workspace) + s64_op_kernel_bytes(B, N, M, form), B, N, M);
+        c.inner = ex->mode >= MDGAT_EXTRACT_THRESHOLD;
+    }
+    {
+        CoopGroup group;      // (held while the resident form's launch is enqueued: coop_chain.hpp)
+        if (form == Sk64Form::resident) if (int rc = group.open(mdgat_current_device(), s)) return rc;
+        if (int rc = launch_sinkhorn_f64(c, form, workspace, workspace_bytes, s, &group, word)) return rc;
+    }
+    if (ex) if (int rc = launch_extract_from_bests(B, N, M, ex, c.bests.ri, c.bests.rv, c.bests.ci, c.bests.cv, s, c.cnt0, c.cnt1)) return rc;
+    return word ? s64_ragged_finish(who, word, s) : MDGAT_OK;
+}
+static Sk64Call s64_op_call(int B, int N, int M, const double* scores, double bin_score, int iters, double* Z64, float* Z32) {
+    Sk64Call c{};
+    c.B = B; c.N = N; c.M = M; c.scores = scores; c.alpha = bin_score; c.iters = iters; c.Z64 = Z64; c.Z32 = Z32;
+    return c;
+}
+
+extern "C" int mdgat_sinkhorn_f64(int B, int N, int M, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return s64_op("mdgat_sinkhorn_f64", s64_op_call(B, N, M, scores, bin_score, iters, Z, nullptr), nullptr, 0, nullptr, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_sinkhorn_f64_extract(int B, int N, int M, const double* scores, double bin_score, int iters, int mode, float match_threshold,
+                                          int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
+    return s64_op("mdgat_sinkhorn_f64_extract", s64_op_call(B, N, M, scores, bin_score, iters, nullptr, Z_or_null), nullptr, 0, &ex, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mdgat_sinkhorn_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                         const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    return s64_op("mdgat_sinkhorn_f64_ragged", s64_op_call(B, Np, Mp, scores, bin_score, iters, Z, nullptr), &counts, 0, nullptr, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mdgat_sinkhorn_f64_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                                  const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
                                                  float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                                  float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_sinkhorn_f64_extract_ragged";
-    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
-    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (int rc = s64_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
-    if (s64_form() == 1) { mdgat_set_error("%s: the streaming form (mdgat_set_f64_sinkhorn_form(1)) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
-    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned* word = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + s64_ragged_word_offset(B, Np, Mp));
-    if (int rc = mdgat_check_hip(hipMemsetAsync(word, 0, 256, s), "memset(fp64 Sinkhorn error word)")) return rc;
-    const size_t kb = sinkhorn_f64_workspace_bytes(B, Np, Mp);
-    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, Np, Mp);
-    const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
-    {
-        CoopGroup group;
-        if (int rc = group.open(mdgat_current_device(), s)) return rc;
-        if (int rc = launch_sinkhorn_f64(B, Np, Mp, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv, workspace, kb, word, group,
-                                         nullptr, counts0, counts1)) return rc;
-    }
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    if (int rc = launch_extract_from_bests(B, Np, Mp, &ex, b.ri, b.rv, b.ci, b.cv, s, counts0, counts1)) return rc;
-    return s64_ragged_finish(who, word, s);
-}
-
-// ---- the same two on the streaming form (include/mdgat_hip.h): slots of up to 2175 keypoints, asynchronous - no error word ----
-static int s64_stream_check_counts(const char* who, int B, int Np, int Mp, const int32_t* c0, const int32_t* c1, const int32_t* h0, const int32_t* h1) {
-    if (!s64_wide_supported(Np, Mp)) {
-        mdgat_set_error("%s: padded sizes %d x %d: the streaming form holds at most %d keypoints per frame", who, Np, Mp, 128 * W64_NC2MAX - 1);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    return mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{c0, c1, h0, h1}, nullptr, nullptr, 0, nullptr);
-}
-extern "C" size_t mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(int B, int Np, int Mp) {
-    if (B <= 0 || Np <= 0 || Mp <= 0 || !s64_wide_supported(Np, Mp)) return 0;
-    return sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) + sinkhorn_f64_bests(nullptr, B, Np, Mp).bytes;
+    return s64_op("mdgat_sinkhorn_f64_extract_ragged", s64_op_call(B, Np, Mp, scores, bin_score, iters, nullptr, Z_or_null), &counts, 0, &ex, workspace,
+                  workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mdgat_sinkhorn_f64_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                                 const int32_t* counts1_host, const double* scores, double bin_score, int iters, double* Z, void* workspace,
                                                 size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_sinkhorn_f64_stream_ragged";
-    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (int rc = s64_stream_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
-    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    return launch_sinkhorn_f64_stream_ragged(B, Np, Mp, counts0, counts1, scores, bin_score, iters, Z, nullptr, 0, nullptr, nullptr, nullptr, nullptr, workspace,
-                                             sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp), static_cast<hipStream_t>(stream));
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    return s64_op("mdgat_sinkhorn_f64_stream_ragged", s64_op_call(B, Np, Mp, scores, bin_score, iters, Z, nullptr), &counts, 2, nullptr, workspace,
+                  workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mdgat_sinkhorn_f64_extract_stream_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                                         const int32_t* counts1_host, const double* scores, double bin_score, int iters, int mode,
                                                         float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                                         float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_sinkhorn_f64_extract_stream_ragged";
-    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
-    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (int rc = s64_stream_check_counts(who, B, Np, Mp, counts0, counts1, counts0_host, counts1_host)) return rc;
-    if (!workspace || workspace_bytes < mdgat_sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-        mdgat_set_error("%s: workspace too small or not 256-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t kb = sinkhorn_f64_stream_ragged_workspace_bytes(B, Np, Mp);
-    const Sk64Bests b = sinkhorn_f64_bests(static_cast<char*>(workspace) + kb, B, Np, Mp);
-    const int inner = mode >= MDGAT_EXTRACT_THRESHOLD;
-    if (int rc = launch_sinkhorn_f64_stream_ragged(B, Np, Mp, counts0, counts1, scores, bin_score, iters, nullptr, Z_or_null, inner, b.ri, b.rv, b.ci, b.cv,
-                                                   workspace, kb, s)) return rc;
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    return launch_extract_from_bests(B, Np, Mp, &ex, b.ri, b.rv, b.ci, b.cv, s, counts0, counts1);
+    return s64_op("mdgat_sinkhorn_f64_extract_stream_ragged", s64_op_call(B, Np, Mp, scores, bin_score, iters, nullptr, Z_or_null), &counts, 2, &ex, workspace,
+                  workspace_bytes, static_cast<hipStream_t>(stream));
 }

@@ -275,7 +275,9 @@ extern "C" int mdgat_sinkhorn_backward(int B, int N, int M, const double* scores
         return MDGAT_ERR_BAD_ARG;
     }
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = sinkhorn_f64_stream_history(B, N, M, scores, bin_score, iters, w.X, w.Np, w.Y, workspace, s)) return rc;
+    Sk64Call fw{};
+    fw.B = B; fw.N = N; fw.M = M; fw.scores = scores; fw.alpha = bin_score; fw.iters = iters;
+    if (int rc = sinkhorn_f64_stream_history(fw, w.X, w.Np, w.Y, workspace, s)) return rc;
     SkgArgs a{};
     a.B = B; a.N = N; a.M = M; a.Mp = w.fw.Mp; a.Np = w.Np; a.G = w.fw.G; a.T = iters;
     a.K = w.fw.K; a.bT = w.fw.bvec; a.dZ = dZ; a.X = w.X; a.Y = w.Y; a.P = w.fw.P; a.d = w.d; a.drow = w.drow; a.dcol = w.dcol;

@@ -166,7 +166,7 @@ def streaming_kernel(N, M):
 
 
 def f64_kernel(N, M, form: int = -1):
-    """csrc/sinkhorn_f64.hip s64_use_wide and the streaming form's NC2: ('resident', row slabs of 32) or ('streaming', NC2, slabs)."""
+    """csrc/sinkhorn_f64.hip sinkhorn_f64_form (a uniform call) and the streaming form's NC2: ('resident', row slabs of 32) or ('streaming', NC2, slabs)."""
     resident = N >= 1 and M >= 1 and M + 1 <= 576 and N <= 576
     wide_ok = N >= 1 and M >= 1 and M + 1 <= 2176 and N + 1 <= 2176
     if not resident and not wide_ok:
