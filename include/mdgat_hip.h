@@ -827,6 +827,21 @@ int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* 
  * counters, never reset: read them before and after a call and subtract). */
 int mdgat_gemm_f64_plan(int M, int N, int K, int K0, int batch, int aligned, int bnt, int cus);
 void mdgat_gemm_f64_launches(uint64_t counts[10]);
+/* Which kernel mdgat_attention_f64 / mdgat_attention_f64_ragged (and every attention of the exact mode) runs.  attention_f64_kernel exists
+ * in seven instantiations:
+ *   0: full attention, 16 queries per workgroup      1: full attention, 32 queries per workgroup
+ *   2: dynamic attention, at most 512 keys (the fp64 logits stay in registers), writing the selection words      3: the same without them
+ *   4: dynamic attention beyond 512 keys (the logits are recomputed), writing the selection words               5: the same without them
+ *   6: full attention, one wave per 32 queries
+ * mdgat_attention_f64_plan: the index the launcher chooses for B pairs in slots of N x M keypoints, top-k `topk` (0: full attention),
+ * tap != 0: selection words are asked for, ragged != 0: per-pair counts are given, the smallest of them `cnt_min` (ignored otherwise),
+ * `form` as mdgat_set_f64_attention_form takes it (-1 by launch size, 0, 1), on a device of `cus` compute units.  topk == N == M is full
+ * attention unless ragged.  A pure function of its arguments: no device is needed or touched.  Negative: no launch - -1 an empty one,
+ * -2 / -3 what the launcher refuses (k above the smallest key count or bad counts / more than 2048 keys in a dynamic layer).
+ * mdgat_attention_f64_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
+ * counters, never reset: read them before and after a call and subtract). */
+int mdgat_attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus);
+void mdgat_attention_f64_launches(uint64_t counts[7]);
 /* The same on a RAGGED batch: pair b has counts0[b] / counts1[b] keypoints in slots padded to Np / Mp (qkv [B][Np+Mp][384], frame 1 from row
  * Np on; msg and sel likewise, sel with the words of mdgat_topk_sel_words(B, Np, Mp)).  Queries and keys beyond a pair's counts take no part
  * and are never read; their message rows and selection words are zero.  A pair's rows are those of mdgat_attention_f64 on the pair alone -

@@ -1400,6 +1400,14 @@ extern "C" void mdgat_gemm_f64_launches(uint64_t counts[10]) {
     if (counts) gemm_f64_launch_counts(counts);
 }
 
+extern "C" int mdgat_attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus) {
+    return attention_f64_plan_index(B, N, M, topk, tap, ragged, cnt_min, form, cus);
+}
+
+extern "C" void mdgat_attention_f64_launches(uint64_t counts[7]) {
+    if (counts) attention_f64_launch_counts(counts);
+}
+
 // ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----
 // the shape and buffer checks of the gradient entries (this section and the two below)
 // nmax: keypoints per frame; rows: the rows the largest array of a pair holds

@@ -209,7 +209,7 @@ struct AttnLds {
     double* mw;          // [4][QT] row maxima per wave
     double* lw;          // [4][QT] row sums per wave
     double* lS;          // [QT][A_LIST]   fp64 logits of the tied candidates
-    int* lkey;           // [QT][A_LIST]   their keys (bit 31: kept, set by the resolution)
+    int* lkey;           // [QT][A_LIST]   their keys (bit 31: kept, set by the resolution, which also sorts the list by rank)
     int* lcount;         // [QT]
     RowSel* sel;         // [QT]
     int* hist;           // [4 waves][RS_HIST_INTS] radix-select histograms (row_search.hpp)
@@ -613,8 +613,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                     const int kj = sm.lkey[q * A_LIST + j];
                     rank += (sj > si) || (sj == si && kj < ki);
                 }
+                // (back into the list IN RANK ORDER - every lane has read the whole list by now, and the ranks are a permutation: the
+                // order in which the waves happened to list the candidates varies from launch to launch, and the combine below adds the
+                // kept ones in list order - a row that keeps several of them must not round differently from one launch to the next)
+                sm.lS[q * A_LIST + rank] = si;
+                sm.lkey[q * A_LIST + rank] = rank < r.aux ? ki | (int)0x80000000 : ki;
                 if (rank < r.aux) {
-                    sm.lkey[q * A_LIST + lane] = ki | (int)0x80000000;
                     if (TAP && q0 + q < nq) atomicOr(a.sel + (((size_t)b * 4 + head) * P + q_off + q0 + q) * a.selW + (ki >> 5), 1u << (ki & 31));
                 }
             }
@@ -997,6 +1001,38 @@ extern "C" int mdgat_set_f64_attention_form(int mode) {
     return prev;
 }
 
+// Which of attention_f64_kernel's seven instantiations a launch runs, as the index mdgat_attention_f64_plan returns and
+// mdgat_attention_f64_launches counts by (include/mdgat_hip.h): 0 full attention, 16 queries per workgroup; 1 full, 32 queries;
+// 2 dynamic, at most 512 keys (KEEP), with the selection tap; 3 the same without; 4 dynamic beyond 512 keys (recomputing) with the
+// tap; 5 without; 6 full, one wave per 32 queries.  Pure: no HIP call.  Negative: no launch - -1 nothing to do, -2 / -3 what the
+// launcher refuses as MDGAT_ERR_BAD_ARG / MDGAT_ERR_UNSUPPORTED.
+static std::atomic<unsigned long long> attention_f64_launch_count[7];
+int attention_f64_plan_index(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus) {
+    if (B <= 0 || N <= 0 || M <= 0 || cus <= 0) return -1;
+    if (ragged && (cnt_min < 1 || cnt_min > (N < M ? N : M))) return -2;
+    // (a ragged batch: the grid, the LDS and the choice of the kernel follow the padded sizes)
+    const int nk_max = N > M ? N : M, nk_min = ragged ? cnt_min : N < M ? N : M;
+    if (topk > nk_min) return -2;      // torch.topk raises (mdgat.py:202)
+    if (nk_max > 2048 && topk > 0) return -3;
+    const bool dyn = topk > 0 && (ragged || !(topk == N && topk == M));
+    // full attention: 32 queries per workgroup (half the key traffic per query).  Dynamic attention: 16 - at most 512 keys the
+    // fp64 logits stay in registers between the passes (KEEP), beyond that the rounding images of 32 rows would not fit the LDS
+    if (!dyn) {
+        // (fewer than two workgroups per CU with 32 queries each - a pair or two of 512 keypoints: 16 queries per workgroup, the
+        // same arithmetic per row.  64 queries per workgroup - 234 registers, two waves per SIMD - lose: 236 -> 289 us at batch 32)
+        // one wave per 32 queries (SOLO) from F64_SOLO_MIN_WG_PER_CU workgroups of four such waves per CU on; mdgat_set_f64_attention_form(1)
+        // forces it at every size (tests: ragged frames, one pair), (0) never
+        const long ugroups = ((long)B * 2 * MDGAT_HEADS + 7) / 8;
+        const long solo_wgs = 8L * ((nk_max + 127) / 128) * ugroups;
+        if (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)cus)) return 6;
+        return 8L * ((nk_max + 31) / 32) * ugroups < 2L * cus ? 0 : 1;
+    }
+    return (nk_max <= 512 ? 2 : 4) + (tap ? 0 : 1);
+}
+void attention_f64_launch_counts(uint64_t counts[7]) {
+    for (int i = 0; i < 7; ++i) counts[i] = attention_f64_launch_count[i].load(std::memory_order_relaxed);
+}
+
 int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard,
                          const int* cnt0, const int* cnt1, int cnt_min) {
     if (B <= 0 || N <= 0 || M <= 0) return MDGAT_OK;
@@ -1012,7 +1048,9 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
         mdgat_set_error("dynamic attention (fp64): %d keys per frame > 2048 supported", nk_max);
         return MDGAT_ERR_UNSUPPORTED;
     }
-    const bool dyn = topk > 0 && (ragged || !(topk == N && topk == M));
+    const int plan = attention_f64_plan_index(B, N, M, topk, sel != nullptr, ragged, cnt_min, f64_attention_form(), mdgat_cu_count());
+    if (plan < 0 || plan > 6) { mdgat_set_error("attention (fp64): no kernel for this launch (plan %d)", plan); return MDGAT_ERR_BAD_ARG; }
+    const bool dyn = plan >= 2 && plan <= 5;
     AttnF64Args a{};
     a.cnt0 = cnt0; a.cnt1 = cnt1;
     // (the kernel writes the rows of a pair's own queries only)
@@ -1040,27 +1078,19 @@ int launch_attention_f64(int B, int N, int M, int cross, int topk, const double*
         if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), solo ? lds : attn_lds_bytes(QT, cap, tk, tk ? (cap > 512 ? 4 * RS_HIST_INTS : 16 * RQ_HIST_INTS) : 0), done, "attention_f64 LDS")) return rc;
         a.tiles = (nk_max + QT - 1) / QT;
         hipLaunchKernelGGL(kern, dim3(8 * a.tiles * ugroups), dim3(256), lds, s, a);
+        attention_f64_launch_count[decltype(tag)::value].fetch_add(1, std::memory_order_relaxed);
         return mdgat_check_hip(hipGetLastError(), "attention_f64 launch");
     };
-    // full attention: 32 queries per workgroup (half the key traffic per query).  Dynamic attention: 16 - at most 512 keys the
-    // fp64 logits stay in registers between the passes (KEEP), beyond that the rounding images of 32 rows would not fit the LDS
-    if (!dyn) {
-        // (fewer than two workgroups per CU with 32 queries each - a pair or two of 512 keypoints: 16 queries per workgroup, the
-        // same arithmetic per row.  64 queries per workgroup - 234 registers, two waves per SIMD - lose: 236 -> 289 us at batch 32)
-        // one wave per 32 queries (SOLO) from F64_SOLO_MIN_WG_PER_CU workgroups of four such waves per CU on; mdgat_set_f64_attention_form(1)
-        // forces it at every size (tests: ragged frames, one pair), (0) never
-        const int form = f64_attention_form();
-        const long solo_wgs = 8L * ((nk_max + 127) / 128) * ugroups;
-        const bool solo = form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)mdgat_cu_count());
-        if (solo) return go(attention_f64_kernel<false, 2, false, false, true>, 128, false, 0, std::integral_constant<int, 6>());
-        const bool small = 8L * ((nk_max + 31) / 32) * ugroups < 2L * mdgat_cu_count();
-        if (small) return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
-        return go(attention_f64_kernel<false, 2, false>, 32, false, 0, std::integral_constant<int, 1>());
+    // (the choice: attention_f64_plan_index above)
+    switch (plan) {
+    case 6: return go(attention_f64_kernel<false, 2, false, false, true>, 128, false, 0, std::integral_constant<int, 6>());
+    case 0: return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
+    case 1: return go(attention_f64_kernel<false, 2, false>, 32, false, 0, std::integral_constant<int, 1>());
+    case 2: return go(attention_f64_kernel<true, 1, true, true>, 16, true, 512, std::integral_constant<int, 2>());
+    case 3: return go(attention_f64_kernel<true, 1, false, true>, 16, true, 512, std::integral_constant<int, 3>());
+    case 4: return go(attention_f64_kernel<true, 1, true>, 16, true, 2048, std::integral_constant<int, 4>());
+    default: return go(attention_f64_kernel<true, 1, false>, 16, true, 2048, std::integral_constant<int, 5>());
     }
-    if (nk_max <= 512) return a.sel ? go(attention_f64_kernel<true, 1, true, true>, 16, true, 512, std::integral_constant<int, 2>())
-                                    : go(attention_f64_kernel<true, 1, false, true>, 16, true, 512, std::integral_constant<int, 3>());
-    return a.sel ? go(attention_f64_kernel<true, 1, true>, 16, true, 2048, std::integral_constant<int, 4>())
-                 : go(attention_f64_kernel<true, 1, false>, 16, true, 2048, std::integral_constant<int, 5>());
 }
 
 int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,

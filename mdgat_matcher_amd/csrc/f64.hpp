@@ -50,6 +50,10 @@ struct AttnF64Args {
 // mdgat_set_f64_attention_form / MDGAT_F64_ATTENTION_FORM: -1 full attention by launch size; 0 always the split-key form (results do not
 // depend on the batch a pair travels in); 1 the big-launch form at every size
 int f64_attention_form();
+// Which of attention_f64_kernel's seven instantiations launch_attention_f64 runs (mdgat_attention_f64_plan, include/mdgat_hip.h), and how
+// often each has been launched by this process (mdgat_attention_f64_launches).  Host code only; the first touches no HIP call.
+int attention_f64_plan_index(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus);
+void attention_f64_launch_counts(uint64_t counts[7]);
 // cnt0 / cnt1: a ragged batch in slots padded to N / M (cnt_min: the smallest count of either frame, known to the caller on the host, who
 // has checked 1 <= cnt0[b] <= N, 1 <= cnt1[b] <= M).  A pair's message rows and selection words are those of the pair run alone wherever
 // the same instantiation runs it; message rows and selection words beyond its counts are zero.
