@@ -521,8 +521,8 @@ int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_s
                            int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
                            float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Which kernels an fp32 Sinkhorn launch runs (csrc/sinkhorn.hip: launch_sinkhorn, which mdgat_sinkhorn, mdgat_sinkhorn_extract and the
- * fp32-class forward go through, and launch_sinkhorn_ragged behind their ragged entry points), and with what launch parameters.  The
+/* Which kernels an fp32 Sinkhorn launch runs (csrc/sinkhorn.hip: launch_sinkhorn, which mdgat_sinkhorn, mdgat_sinkhorn_extract, their
+ * ragged entry points - a call with counts - and the fp32-class forward go through), and with what launch parameters.  The
  * instantiations, as mdgat_sinkhorn_launches counts them:
  *    0 scaling<false,4>    sinkhorn_scaling_kernel<false, 4>:  one column slab, <= 4 row slabs (N <= 512, M <= 512)
  *    1 scaling<false,16>   sinkhorn_scaling_kernel<false, 16>: one column slab, 5 .. 16 row slabs (N <= 2048, M <= 512)

@@ -287,7 +287,7 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form s
     c.take(w.msg, R * 128);
     c.take(w.scores, (size_t)B * N * M);
     c.take(w.Z, (size_t)B * (N + 1) * (M + 1));
-    w.sk_bytes = mdgat_sinkhorn_ws_bytes_impl(B, N, M);
+    w.sk_bytes = sinkhorn_cluster_workspace_bytes(B, N, M);
     c.take(w.sk, w.sk_bytes);
     c.take(w.qkv16, mdgat_qkv16_halves(B, N, M));
     if (f64) {
@@ -552,7 +552,7 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     // layer 0's projection; the last fp64 launch also writes the fp32 rounding of x, the hand-over.  mdgat_set_f64_layer_fusion(0)
     // keeps the one-product-per-launch form (bit-identical).
     p.fused64 = f64 && layer_f64_fused() && h->w.frag64;
-    p.cluster32 = mdgat_sinkhorn_ws_bytes_impl(B, N, M) != 0;
+    p.cluster32 = sinkhorn_cluster_workspace_bytes(B, N, M) != 0;
     p.cnt_min = 0;
     // An fp64 handle that runs the encoders ALONE in fp64 - f64_layers = MDGAT_F64_ENCODERS_ONLY, f64_sinkhorn off, the pooled encoder
     // loaded: what a float32 'FPFH_gloabal' module creates - hands over to the fp32-class kernels right behind them (p.first == 0): its
@@ -840,13 +840,14 @@ static int tail32(Fwd& f, const FwdOut& o) {
     f.mark(MDGAT_PROF_SCORES);
     if (int rc = f.tap(f.taps.scores, ws.scores, (size_t)B * N * M, "tap scores")) return rc;
     // (Z is only materialised when the caller asks for it, the streaming Sinkhorn needs it for the extraction or the loss reads it)
-    float* Zout = o.Z ? o.Z : (f.p.cluster32 && !o.loss ? nullptr : ws.Z);
-    const SkExtract ex = f.extract(o);
     // (a ragged batch: the streaming kernel with the counts - the cluster kernel takes none - into the caller's Z or the workspace's)
-    if (int rc = f.cnt0 ? launch_sinkhorn_ragged(B, N, M, f.cnt0, f.cnt1, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters,
-                                                 o.Z ? o.Z : ws.Z, &ex, f.s)
-                        : launch_sinkhorn(B, N, M, ws.scores, f.h->w.blob + f.h->w.bl.bin_score, 0.f, f.h->cfg.sinkhorn_iters, Zout, ws.sk, ws.sk_bytes, &ex, f.s,
-                                          f.status, o.Z ? o.Z : ws.Z, sk_clear != 0)) return rc;
+    float* const Zroom = o.Z ? o.Z : ws.Z;
+    float* Zout = o.Z || f.cnt0 || !f.p.cluster32 || o.loss ? Zroom : nullptr;
+    const SkExtract ex = f.extract(o);
+    SkCall c{B, N, M, f.h->cfg.sinkhorn_iters, ws.scores, f.h->w.blob + f.h->w.bl.bin_score};
+    c.Z = Zout; c.Zfb = Zroom; c.cnt0 = f.cnt0; c.cnt1 = f.cnt1;      // (Zfb: where redone pairs go when the cluster kernel writes no Z)
+    c.ws = ws.sk; c.ws_bytes = ws.sk_bytes; c.slots_cleared = sk_clear != 0; c.status = f.status; c.ex = &ex; c.stream = f.s;
+    if (int rc = launch_sinkhorn(c)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const float*>(Zout));
 }
@@ -1132,27 +1133,13 @@ extern "C" int mdgat_profile(mdgat_handle* h, int enable, double* ms_out, long l
 }
 
 // ---------------------------------------------------------------------------------- per-op entry points
-extern "C" size_t mdgat_sinkhorn_workspace_bytes(int B, int N, int M) { return mdgat_sinkhorn_ws_bytes_impl(B, N, M); }
+extern "C" size_t mdgat_sinkhorn_workspace_bytes(int B, int N, int M) { return sinkhorn_cluster_workspace_bytes(B, N, M); }
 
-extern "C" int mdgat_sinkhorn(int B, int N, int M, const float* scores, float bin_score, int iters, float* Z, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    if (!scores || !Z) { mdgat_set_error("mdgat_sinkhorn: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    // without (enough, 256-byte aligned) workspace the streaming kernel is used instead of the cluster kernel
-    return launch_sinkhorn(B, N, M, scores, nullptr, bin_score, iters, Z, workspace, workspace_bytes, nullptr, static_cast<hipStream_t>(stream));
+extern "C" size_t mdgat_sinkhorn_ragged_workspace_bytes(int B, int Np, int Mp) {
+    if (B <= 0 || Np <= 0 || Mp <= 0 || Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return 0;
+    return ((size_t)B * (Np + 1) * (Mp + 1) * sizeof(float) + 255) & ~(size_t)255;
 }
 
-extern "C" int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_score, int iters, int mode, float match_threshold,
-                                      int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
-                                      float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_sinkhorn_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (mode < 0 || mode > 3) { mdgat_set_error("mdgat_sinkhorn_extract: bad mode %d", mode); return MDGAT_ERR_BAD_ARG; }
-    // the forward's call (tail32): the same launcher, the same SkExtract, the batch-wide rule applied inside the launch
-    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    return launch_sinkhorn(B, N, M, scores, nullptr, bin_score, iters, Z_or_null, workspace, workspace_bytes, &ex, static_cast<hipStream_t>(stream), nullptr,
-                           Z_or_null ? Z_or_null : Z_fallback_or_null);
-}
-
-// ---- the two above on a ragged batch: the streaming kernel's ragged instantiations (sinkhorn.hip) ----
 // the slot limit of the fp32 ragged entries, then the per-pair checks every ragged entry makes (ragged.hpp)
 static int sk_ragged_check(const char* who, int B, int Np, int Mp, int iters, const RaggedCounts& c) {
     if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
@@ -1163,46 +1150,67 @@ static int sk_ragged_check(const char* who, int B, int Np, int Mp, int iters, co
     }
     return mdgat_check_ragged(who, B, Np, Mp, c, nullptr, nullptr, 0, nullptr);
 }
-
-extern "C" size_t mdgat_sinkhorn_ragged_workspace_bytes(int B, int Np, int Mp) {
-    if (B <= 0 || Np <= 0 || Mp <= 0 || Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return 0;
-    return ((size_t)B * (Np + 1) * (Mp + 1) * sizeof(float) + 255) & ~(size_t)255;
+static bool sk_outputs_null(const SkExtract& ex) { return !ex.m0 || !ex.m1 || !ex.s0 || !ex.s1; }
+static SkCall sk_op_call(int B, int N, int M, const float* scores, float bin_score, int iters, float* Z, void* workspace, size_t workspace_bytes, void* stream,
+                         float* Z_lent = nullptr) {
+    SkCall c{B, N, M, iters, scores};
+    c.alpha_host = bin_score; c.Z = Z; c.Zfb = Z_lent; c.ws = workspace; c.ws_bytes = workspace_bytes; c.stream = static_cast<hipStream_t>(stream);
+    return c;
 }
 
+// ONE body for the four Sinkhorn entries.  counts: null for the uniform entries, which run the streaming kernel instead of the cluster kernel without (enough,
+// 256-byte aligned) workspace; a ragged batch always does, and its extraction scans Z: the caller's, or one produced into the workspace.  ex: as in the
+// forward's call (tail32) - the same launcher, the same SkExtract, the batch-wide rule applied inside the launch.
+static int sk_op(const char* who, SkCall c, const RaggedCounts* counts, const SkExtract* ex) {
+    if (!c.scores || (ex ? sk_outputs_null(*ex) : !c.Z)) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (ex) if (int rc = extract_check_mode(who, ex->mode)) return rc;
+    c.ex = ex;
+    if (counts) {
+        if (int rc = sk_ragged_check(who, c.B, c.N, c.M, c.iters, *counts)) return rc;
+        if (c.B == 0) return MDGAT_OK;
+        if (!c.Z && (!c.ws || c.ws_bytes < mdgat_sinkhorn_ragged_workspace_bytes(c.B, c.N, c.M) || (reinterpret_cast<uintptr_t>(c.ws) & 255))) {
+            mdgat_set_error("%s: without Z the workspace holds it: too small or not 256-byte aligned", who);
+            return MDGAT_ERR_BAD_ARG;
+        }
+        if (!c.Z) c.Z = static_cast<float*>(c.ws);
+        c.cnt0 = counts->cnt0; c.cnt1 = counts->cnt1;
+    }
+    return launch_sinkhorn(c);
+}
+
+extern "C" int mdgat_sinkhorn(int B, int N, int M, const float* scores, float bin_score, int iters, float* Z, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    return sk_op("mdgat_sinkhorn", sk_op_call(B, N, M, scores, bin_score, iters, Z, workspace, workspace_bytes, stream), nullptr, nullptr);
+}
+
+extern "C" int mdgat_sinkhorn_extract(int B, int N, int M, const float* scores, float bin_score, int iters, int mode, float match_threshold,
+                                      int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1, float* Z_or_null,
+                                      float* Z_fallback_or_null, void* workspace, size_t workspace_bytes, void* stream) {
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1};
+    return sk_op("mdgat_sinkhorn_extract", sk_op_call(B, N, M, scores, bin_score, iters, Z_or_null, workspace, workspace_bytes, stream, Z_fallback_or_null), nullptr, &ex);
+}
+
+// ---- the two above on a ragged batch: the streaming kernel's ragged instantiations (sinkhorn.hip) ----
 extern "C" int mdgat_sinkhorn_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                      const int32_t* counts1_host, const float* scores, float bin_score, int iters, float* Z, void* stream) {
-    const char* who = "mdgat_sinkhorn_ragged";
-    if (!scores || !Z) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = sk_ragged_check(who, B, Np, Mp, iters, RaggedCounts{counts0, counts1, counts0_host, counts1_host})) return rc;
-    return launch_sinkhorn_ragged(B, Np, Mp, counts0, counts1, scores, nullptr, bin_score, iters, Z, nullptr, static_cast<hipStream_t>(stream));
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    return sk_op("mdgat_sinkhorn_ragged", sk_op_call(B, Np, Mp, scores, bin_score, iters, Z, nullptr, 0, stream), &counts, nullptr);
 }
 
 extern "C" int mdgat_sinkhorn_extract_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                              const int32_t* counts1_host, const float* scores, float bin_score, int iters, int mode,
                                              float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                              float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_sinkhorn_extract_ragged";
-    if (!scores || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
-    if (int rc = sk_ragged_check(who, B, Np, Mp, iters, RaggedCounts{counts0, counts1, counts0_host, counts1_host})) return rc;
-    if (B == 0) return MDGAT_OK;
-    // the extraction scans Z: the caller's, or one produced into the workspace
-    float* Z = Z_or_null;
-    if (!Z) {
-        if (!workspace || workspace_bytes < mdgat_sinkhorn_ragged_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
-            mdgat_set_error("%s: without Z the workspace holds it: too small or not 256-byte aligned", who);
-            return MDGAT_ERR_BAD_ARG;
-        }
-        Z = static_cast<float*>(workspace);
-    }
-    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1, 0, nullptr, 0u};
-    return launch_sinkhorn_ragged(B, Np, Mp, counts0, counts1, scores, nullptr, bin_score, iters, Z, &ex, static_cast<hipStream_t>(stream));
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1};
+    return sk_op("mdgat_sinkhorn_extract_ragged", sk_op_call(B, Np, Mp, scores, bin_score, iters, Z_or_null, workspace, workspace_bytes, stream), &counts, &ex);
 }
 
 extern "C" int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold, int64_t* matches0,
                              int64_t* matches1, float* mscores0, float* mscores1, void* stream) {
-    if (!Z || !matches0 || !matches1 || !mscores0 || !mscores1) { mdgat_set_error("mdgat_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    return launch_extract(B, N, M, Z, mode, match_threshold, matches0, matches1, mscores0, mscores1, static_cast<hipStream_t>(stream));
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1};
+    if (!Z || sk_outputs_null(ex)) { mdgat_set_error("mdgat_extract: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    return launch_extract(B, N, M, Z, ex, static_cast<hipStream_t>(stream));      // (its mode check: extract_check_mode, behind the empty-batch return)
 }
 
 extern "C" size_t mdgat_attention_workspace_bytes(int B, int N, int M) {

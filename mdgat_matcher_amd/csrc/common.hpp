@@ -251,18 +251,20 @@ constexpr int MDGAT_STATUS_MATCHED = 4;       // first of MDGAT_MATCH_SLOTS word
 constexpr int MDGAT_MATCH_SLOTS = 256;
 constexpr int MDGAT_STATUS_WORDS = MDGAT_STATUS_MATCHED + MDGAT_MATCH_SLOTS;
 constexpr float MDGAT_F16_GUARD = 6.0e4f;     // f16 max is 65504; the split's hi plane must stay finite
-// status (optional, device pointer to MDGAT_STATUS_WORDS host-mapped words).  Zfb: where the streaming fallback puts Z when
-// the cluster kernel lost a partner and the caller wanted no Z (NULL: the cluster launch is cooperative instead).
-// slots_cleared: the first sinkhorn_slots_clear_bytes(N, M) bytes of ws are already zero on the stream (no memset launch).
-int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_score_dev, float bin_score_host,
-                    int iters, float* Z, void* ws, size_t ws_bytes, const SkExtract* ex, hipStream_t s, unsigned* status = nullptr,
-                    float* Zfb = nullptr, bool slots_cleared = false);
-// A ragged batch on the streaming kernel: pair b has cnt0[b] x cnt1[b] keypoints (device int32 [B], checked by the caller) in slots of
-// N x M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS; its block of Z has the bits of the pair run alone through the streaming kernel, the rest of its
-// slot is 0.  Z is required; ex: the extraction with the same counts (extract_kernel scans Z).
-int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const float* scores, const float* bin_score_dev,
-                           float bin_score_host, int iters, float* Z, const SkExtract* ex, hipStream_t s);
-// What launch_sinkhorn and launch_sinkhorn_ragged choose (mdgat_sinkhorn_plan, include/mdgat_hip.h: the table of indices), and how often each
+// One fp32 Sinkhorn call, with `ex` also its match extraction (sinkhorn.hip).  Zero-initialise it and set what applies.
+struct SkCall {
+    int B, N, M, iters;
+    const float *scores, *alpha_dev; float alpha_host;      // [B][N][M]; the bin score as a device scalar, or null: alpha_host
+    float *Z, *Zfb;                     // Z [B][N+1][M+1]: may be null with `ex` on the cluster kernel, which fuses the arg-maxes.  Zfb: lent for the pairs the
+                                        // streaming kernel redoes when no Z is wanted (neither: the cluster launch is cooperative instead)
+    const int *cnt0, *cnt1;             // both or neither (device int32 [B], checked by the caller): a ragged batch on the streaming kernel - pair b has cnt0[b] x
+                                        // cnt1[b] keypoints in slots of N x M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS.  Z is required: 0 outside a pair's own block
+    void* ws; size_t ws_bytes;          // the cluster kernel's workspace; missing, short or not 256-byte aligned: the streaming kernel
+    bool slots_cleared;                 // the first sinkhorn_slots_clear_bytes(B, N, M) bytes of ws are already zero on the stream (no memset launch)
+    unsigned* status; const SkExtract* ex; hipStream_t stream;      // status: optional, a device pointer to MDGAT_STATUS_WORDS host-mapped words
+};
+int launch_sinkhorn(const SkCall& c);
+// What launch_sinkhorn chooses (mdgat_sinkhorn_plan, include/mdgat_hip.h: the table of indices), and how often each
 // instantiation has been launched by this process (mdgat_sinkhorn_launches).  Host code only; the plan touches no HIP call.
 enum SkForm {
     SK_SCALING_4 = 0, SK_SCALING_16, SK_SCALING_2D,                                               // sinkhorn_scaling_kernel<false, 4>, <false, 16>, <true, 16>
@@ -284,17 +286,17 @@ struct SkPlan {
     int cooperative;    // cluster: hipLaunchCooperativeKernel
     int rc;             // MDGAT_ERR_UNSUPPORTED where the launcher refuses (the message is the launcher's)
 };
-// workspace: sinkhorn_workspace_usable; fallback_buffer: a Z, or one lent for redone pairs; ragged: launch_sinkhorn_ragged
+// workspace: sinkhorn_workspace_usable; fallback_buffer: a Z, or one lent for redone pairs; ragged: a call with counts
 SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged);
-bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes);   // large enough for the cluster kernel and 256-byte aligned
 void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]);
-size_t sinkhorn_slots_clear_bytes(int B, int N, int M);   // 0: the shape does not use the cluster kernel
-size_t mdgat_sinkhorn_ws_bytes_impl(int B, int N, int M);
+size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M);      // the cluster kernel's workspace (its one layout: sinkhorn.hip); 0: the shape is beyond that kernel
+size_t sinkhorn_slots_clear_bytes(int B, int N, int M);            // ... the prefix of it that is zero when a launch starts
+bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes);      // ... whether a buffer is large enough for it and 256-byte aligned
 
-int launch_extract(int B, int N, int M, const float* Z, int mode, float thr, int64_t* m0, int64_t* m1,
-                   float* s0, float* s1, hipStream_t s);
+int extract_check_mode(const char* who, int mode);      // the one mode check: "<who>: bad mode <mode>"
 // cnt0 / cnt1 (optional, device int32 [B]): a ragged batch in slots of N x M - dustbins at a pair's own counts, the all-dustbin rule per pair,
 // matches -1 and scores 0 beyond the counts
+int launch_extract(int B, int N, int M, const float* Z, const SkExtract& ex, hipStream_t s, const int* cnt0 = nullptr, const int* cnt1 = nullptr);
 int launch_extract_from_bests(int B, int N, int M, const SkExtract* ex, const int* rbest_idx, const float* rbest_val, const int* cbest_idx,
                               const float* cbest_val, hipStream_t s, const int* cnt0 = nullptr, const int* cnt1 = nullptr);
 

@@ -1113,28 +1113,41 @@ int launch_sk(const SkArgs& a, int B, hipStream_t s) {
 
 // tiling of a pair: GR row slabs of 128 rows (16 rows per wave) x GC column slabs of 512 columns, one workgroup each
 static void sk_tiling(int N, int M, int& GR, int& GC) { GR = (N + 127) / 128; GC = (M + 511) / 512; }
-static int sk_max_groups(int N, int M) {      // pairs in flight on a 256-CU part (upper bound used for sizing)
-    int GR, GC;
-    sk_tiling(N, M, GR, GC);
-    int g = 256 / (GR * GC);
-    return g > 64 ? 64 : (g < 1 ? 1 : g);
-}
-static size_t slots_bytes(int N, int M) {
-    int GR, GC;
-    sk_tiling(N, M, GR, GC);
-    const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
-    return (256 + per_group * sk_max_groups(N, M) + 255) & ~(size_t)255;
-}
-static size_t flags_bytes(int B) { return ((size_t)B * sizeof(unsigned) + 255) & ~(size_t)255; }
-size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M) {
-    if (N > 2048 || M > 2048) return 0;
-    int GR, GC;
-    sk_tiling(N, M, GR, GC);
-    // exchange slots + per-pair range flags + fused arg-max scratch: row bests [B][GC][N] (int + float), column bests [B][GR][M] (int + float)
-    return slots_bytes(N, M) + flags_bytes(B) + ((size_t)B * GC * N * 2 + (size_t)B * GR * M * 2) * sizeof(float);
-}
+static int sk_max_groups(int P) { return 256 / P > 64 ? 64 : (256 / P < 1 ? 1 : 256 / P); }      // pairs of P workgroups in flight on a 256-CU part (upper bound used for sizing)
 
-static int launch_extract_impl(int B, int N, int M, ExArgs a, hipStream_t s, bool defer_alldust = false);
+// ---- the cluster kernel's workspace, stated once: byte offsets from its 256-byte aligned base ----
+//   header  256 bytes: word 0 the launch's error word, words 2 and 3 the all-dustbin ticket of the extraction
+//   slots   the exchange slots of a pair in flight (SksArgs::slots), for sk_max_groups pairs; rounded up to 256 together with the header
+//   flags   the per-pair range flags: B words, rounded up to 256
+//   bests   the fused arg-maxes: row bests [B][GC][N] (int, then float), column bests [B][GR][M] (int, then float)
+// Header, slots and flags are zero when a launch starts: a partner that reads a stale slot or flag spins to its bound.
+constexpr int SK_CLUSTER_MAX = 2048, SK_WORD_ERROR = 0, SK_WORD_TICKET = 2;    // keypoints per frame the cluster kernel takes (its limit is stated here only); header words
+struct SkLayout {
+    int GR, GC;
+    size_t per_group, flags_bytes;                                             // bytes of one pair's slots, of the flags
+    size_t header, slots, flags, rbest_idx, rbest_val, cbest_idx, cbest_val;   // offsets
+    size_t clear_bytes, total;                                                 // header + slots + flags; all of it (0: the shape is beyond the cluster kernel)
+    template <typename T> T* at(void* ws, size_t offset) const { return reinterpret_cast<T*>(static_cast<char*>(ws) + offset); }
+    bool usable(const void* ws, size_t ws_bytes) const { return total && ws && ws_bytes >= total && (reinterpret_cast<uintptr_t>(ws) & 255) == 0; }
+};
+static SkLayout sk_layout(int B, int N, int M) {
+    SkLayout l{};
+    if (N <= 0 || M <= 0 || N > SK_CLUSTER_MAX || M > SK_CLUSTER_MAX) return l;
+    sk_tiling(N, M, l.GR, l.GC);
+    l.per_group = ((size_t)2 * l.GC * l.GR * SLOT_STRIDE + (size_t)2 * l.GR * l.GC * ROW_STRIDE) * sizeof(unsigned long long);
+    l.flags_bytes = ((size_t)B * sizeof(unsigned) + 255) & ~(size_t)255;
+    l.slots = l.header + 256;
+    l.flags = (l.slots + l.per_group * sk_max_groups(l.GR * l.GC) + 255) & ~(size_t)255;
+    l.rbest_idx = l.clear_bytes = l.flags + l.flags_bytes;
+    l.rbest_val = l.rbest_idx + (size_t)B * l.GC * N * sizeof(int);
+    l.cbest_idx = l.rbest_val + (size_t)B * l.GC * N * sizeof(float);
+    l.cbest_val = l.cbest_idx + (size_t)B * l.GR * M * sizeof(int);
+    l.total = l.cbest_val + (size_t)B * l.GR * M * sizeof(float);
+    return l;
+}
+size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M) { return sk_layout(B, N, M).total; }
+size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return sk_layout(B, N, M).clear_bytes; }
+bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes) { return sk_layout(B, N, M).usable(ws, ws_bytes); }
 
 // ---- the launchers' choices as a pure function (mdgat_sinkhorn_plan; no HIP call), and the launches counted by it ----
 static std::atomic<unsigned long long> sinkhorn_launch_count[SK_COUNTERS];
@@ -1143,25 +1156,20 @@ void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]) {
     for (int i = 0; i < SK_COUNTERS; ++i) counts[i] = sinkhorn_launch_count[i].load(std::memory_order_relaxed);
 }
 
-bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes) {
-    const size_t need = sinkhorn_cluster_workspace_bytes(B, N, M);
-    return need && ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0;
-}
-
 SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged) {
     SkPlan p{SK_PATH_NONE, -1, -1, 0, 0, 0, 0, 0, 0, MDGAT_OK};
     if (B <= 0 || N <= 0 || M <= 0) return p;
     // the one-workgroup-per-pair streaming kernel: any shape up to M = 2048, no workspace
     const int nc = M <= 64 ? 0 : M <= 128 ? 1 : M <= 256 ? 2 : M <= 512 ? 3 : (M <= 1024 && N <= 4096) ? 4 : (M <= 2048 && N <= 4096) ? 5 : -1;
     if (ragged) {
-        // the RAGGED instantiation for the slot, picked from the padded sizes alone (launch_sinkhorn_ragged)
+        // the RAGGED instantiation for the slot, picked from the padded sizes alone (launch_sinkhorn: a call with counts)
         if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
         p.path = SK_PATH_STREAMING;
         p.stream = SK_RAGGED_1 + nc;
         p.grid = B;
         return p;
     }
-    if (!workspace || N > 2048 || M > 2048) {
+    if (!workspace || N > SK_CLUSTER_MAX || M > SK_CLUSTER_MAX) {
         if (nc < 0) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
         p.path = SK_PATH_STREAMING;
         p.stream = SK_STREAM_1 + nc;
@@ -1171,7 +1179,7 @@ SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallb
     sk_tiling(N, M, p.GR, p.GC);
     const int P = p.GR * p.GC;                     // workgroups per pair, one per CU
     int ngroups = num_cu / P;
-    if (ngroups > sk_max_groups(N, M)) ngroups = sk_max_groups(N, M);
+    if (ngroups > sk_max_groups(P)) ngroups = sk_max_groups(P);
     if (ngroups > B) ngroups = B;
     p.ngroups = ngroups;
     if (ngroups < 1) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
@@ -1201,121 +1209,18 @@ SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallb
     return p;
 }
 
-// the streaming kernel in the plan's instantiation; gated: behind a cluster launch (a.only_if), counted apart
-static int launch_streaming(const SkArgs& a, int B, int form, bool gated, hipStream_t s) {
-    int rc;
-    switch (form) {
-    case SK_STREAM_1: rc = launch_sk<1, 16>(a, B, s); break;
-    case SK_STREAM_2: rc = launch_sk<2, 16>(a, B, s); break;
-    case SK_STREAM_4: rc = launch_sk<4, 16>(a, B, s); break;
-    case SK_STREAM_8: rc = launch_sk<8, 16>(a, B, s); break;
-    case SK_STREAM_16: rc = launch_sk<16, 8>(a, B, s); break;
-    case SK_STREAM_32: rc = launch_sk<32, 8>(a, B, s); break;
-    case SK_RAGGED_1: rc = launch_sk<1, 16, true>(a, B, s); break;
-    case SK_RAGGED_2: rc = launch_sk<2, 16, true>(a, B, s); break;
-    case SK_RAGGED_4: rc = launch_sk<4, 16, true>(a, B, s); break;
-    case SK_RAGGED_8: rc = launch_sk<8, 16, true>(a, B, s); break;
-    default:
-        mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", a.M);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    if (!rc) sinkhorn_count_launch(gated ? SK_GATED : form);
-    return rc;
+// (the kernels' argument structs are filled by name behind their leading fields, the call and its Z)  An extraction request for B pairs in slots of
+// N x M; its source - a Z to scan, or arg-maxes (GR = GC = 1 unless said otherwise) - is the caller's to add
+static ExArgs ex_args(const SkExtract& ex, int B, int N, int M) {
+    ExArgs a{};
+    a.N = N; a.M = M; a.B = B; a.mode = ex.mode; a.thr = ex.thr; a.m0 = ex.m0; a.m1 = ex.m1; a.s0 = ex.s0; a.s1 = ex.s1;
+    a.GR = a.GC = 1; a.matched = ex.matched; a.matched_token = ex.matched_token;
+    return a;
 }
 
-// A ragged batch (pairs of cnt0[b] x cnt1[b] keypoints in slots of N x M): the streaming kernel's RAGGED instantiation for the slot, picked
-// from the padded sizes alone - a wider NC than a pair's own M would select gives the pair the same bits - then, with `ex`, extract_kernel
-// with the same counts.  Z is required: the extraction scans it.  The counts have been checked by the caller (mdgat_check_ragged).
-int launch_sinkhorn_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, const float* scores, const float* bin_score_dev, float bin_score_host,
-                           int iters, float* Z, const SkExtract* ex, hipStream_t s) {
-    if (B <= 0) return MDGAT_OK;
-    if (!cnt0 || !cnt1 || !scores || !Z) { mdgat_set_error("sinkhorn (ragged): null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn (ragged): bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    const SkPlan p = sinkhorn_plan(B, N, M, 0, false, true, true);
-    if (p.rc) {
-        mdgat_set_error("sinkhorn (ragged): padded sizes %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
-        return p.rc;
-    }
-    const SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr, cnt0, cnt1};
-    const int rc = launch_streaming(a, B, p.stream, false, s);
-    if (rc || !ex) return rc;
-    ExArgs xa{Z, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1,
-              ex->matched, ex->matched_token, cnt0, cnt1};
-    return launch_extract_impl(B, N, M, xa, s, ex->defer_alldust != 0);
-}
-
-size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return (N > 2048 || M > 2048) ? 0 : slots_bytes(N, M) + flags_bytes(B); }
-
-static int launch_scaling(const SkPlan& pl, int B, int N, int M, const float* scores, const float* alpha_dev, float alpha_host, int iters,
-                          float* Z, void* ws, const SkExtract* ex, unsigned* status, float* Zfb, bool slots_cleared, hipStream_t s) {
-    const int GR = pl.GR, GC = pl.GC, ngroups = pl.ngroups;
-    if (pl.rc) { mdgat_set_error("sinkhorn: %d workgroups per pair do not fit the device", GR * GC); return pl.rc; }
-    const size_t per_group = ((size_t)2 * GC * GR * SLOT_STRIDE + (size_t)2 * GR * GC * ROW_STRIDE) * sizeof(unsigned long long);
-    if (!slots_cleared) {    // (the forward has the score kernel clear them)
-        if (int rc = mdgat_check_hip(hipMemsetAsync(ws, 0, 256 + per_group * ngroups, s), "memset(sinkhorn slots)")) return rc;
-        if (int rc = mdgat_check_hip(hipMemsetAsync(static_cast<char*>(ws) + slots_bytes(N, M), 0, flags_bytes(B), s), "memset(sinkhorn pair flags)")) return rc;
-    }
-    // test hook (tests/test_gpu_ops.py): pretend a partner was lost - the launch's error word starts out set, so the gated
-    // streaming kernel and the extraction from its Z run for real
-    if (const char* f = getenv("MDGAT_SK_FORCE_FALLBACK"); f && *f == '1')
-        if (int rc = mdgat_check_hip(hipMemsetAsync(ws, 1, sizeof(unsigned), s), "memset(sinkhorn error word)")) return rc;
-    SksArgs a{scores, alpha_dev, alpha_host, Z, reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + 256),
-              static_cast<unsigned*>(ws), reinterpret_cast<unsigned*>(static_cast<char*>(ws) + slots_bytes(N, M)),
-              status ? status + MDGAT_STATUS_RANGE : nullptr, B, N, M, iters, ngroups, GR, GC, pl.xcd_map, -1, nullptr, nullptr, nullptr, nullptr};
-    if (ex) {
-        char* p = static_cast<char*>(ws) + slots_bytes(N, M) + flags_bytes(B);
-        a.ext_mode = ex->mode;
-        a.rbest_idx = reinterpret_cast<int*>(p);                      p += (size_t)B * GC * N * sizeof(int);
-        a.rbest_val = reinterpret_cast<float*>(p);                    p += (size_t)B * GC * N * sizeof(float);
-        a.cbest_idx = reinterpret_cast<int*>(p);                      p += (size_t)B * GR * M * sizeof(int);
-        a.cbest_val = reinterpret_cast<float*>(p);
-    }
-    void* args[] = {&a};
-    const void* kern = pl.scaling == SK_SCALING_2D ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<true, 16>)
-                     : pl.scaling == SK_SCALING_16 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 16>)
-                                                  : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 4>);
-    // plain or cooperative, and whether the gated streaming kernel follows: sinkhorn_plan
-    float* zfb = Z ? Z : Zfb;
-    const bool can_fall_back = pl.stream >= 0;
-    hipError_t e;
-    if (pl.cooperative) e = hipLaunchCooperativeKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s);
-    else e = hipLaunchKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s);
-    if (int rc = mdgat_check_hip(e, "sinkhorn scaling launch")) return rc;
-    sinkhorn_count_launch(pl.scaling);
-    if (can_fall_back) {
-        SkArgs f{scores, alpha_dev, alpha_host, zfb, N, M, iters, a.error_word, status ? status + MDGAT_STATUS_SK_FALLBACK : nullptr, a.pair_flags};
-        if (int rc = launch_streaming(f, B, pl.stream, true, s)) return rc;
-    }
-    if (ex) {
-        // (header words 2, 3 of the workspace: the all-dustbin counters of the extraction, cleared with the slots)
-        ExArgs x{nullptr, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, can_fall_back ? a.error_word : nullptr, zfb, a.pair_flags,
-                 (ex->defer_alldust || B >= 65536) ? nullptr : a.error_word + 2, B,
-                 a.rbest_idx, a.rbest_val, a.cbest_idx, a.cbest_val, GR, GC, ex->matched, ex->matched_token};
-        return launch_extract_impl(B, N, M, x, s, ex->defer_alldust != 0);
-    }
+int extract_check_mode(const char* who, int mode) {
+    if (mode < 0 || mode > 3) { mdgat_set_error("%s: bad mode %d", who, mode); return MDGAT_ERR_BAD_ARG; }
     return MDGAT_OK;
-}
-
-size_t mdgat_sinkhorn_ws_bytes_impl(int B, int N, int M) { return sinkhorn_cluster_workspace_bytes(B, N, M); }
-
-// ex != NULL: also extract the matches.  With the cluster kernel the arg-maxes are fused into its epilogue and Z may
-// be NULL; otherwise Z must be given and is scanned by the extraction kernel.
-int launch_sinkhorn(int B, int N, int M, const float* scores, const float* bin_score_dev, float bin_score_host,
-                    int iters, float* Z, void* ws, size_t ws_bytes, const SkExtract* ex, hipStream_t s, unsigned* status, float* Zfb,
-                    bool slots_cleared) {
-    if (B <= 0) return MDGAT_OK;
-    if (!Z && !ex) { mdgat_set_error("sinkhorn: nothing to compute (no Z, no extraction)"); return MDGAT_ERR_BAD_ARG; }
-    if (N <= 0 || M <= 0 || iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, iters); return MDGAT_ERR_BAD_ARG; }
-    const bool usable = sinkhorn_workspace_usable(B, N, M, ws, ws_bytes);
-    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, Z || Zfb, false);
-    if (usable) return launch_scaling(p, B, N, M, scores, bin_score_dev, bin_score_host, iters, Z, ws, ex, status, Zfb, slots_cleared, s);
-    if (!Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
-    SkArgs a{scores, bin_score_dev, bin_score_host, Z, N, M, iters, nullptr, nullptr, nullptr};
-    const int rc = launch_streaming(a, B, p.stream, false, s);
-    if (rc || !ex) return rc;
-    ExArgs xa{Z, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1,
-              ex->matched, ex->matched_token};
-    return launch_extract_impl(B, N, M, xa, s, ex->defer_alldust != 0);
 }
 
 int launch_alldust_fixup(int B, int N, int M, int mode, const int64_t* m0, float* s1, hipStream_t s) {
@@ -1326,14 +1231,21 @@ int launch_alldust_fixup(int B, int N, int M, int mode, const int64_t* m0, float
     return mdgat_check_hip(hipGetLastError(), "extract fixup launch");
 }
 
-static int launch_extract_impl(int B, int N, int M, ExArgs a, hipStream_t s, bool defer_alldust) {
-    if (a.mode < 0 || a.mode > 3) { mdgat_set_error("extract: bad mode %d", a.mode); return MDGAT_ERR_BAD_ARG; }
-    const size_t lds = (size_t)(2 * (N + M) + 4) * sizeof(float);
-    hipLaunchKernelGGL(extract_kernel, dim3(B), dim3(1024), lds, s, a);
+static int launch_extract_impl(const ExArgs& a, const SkExtract& ex, hipStream_t s) {
+    if (int rc = extract_check_mode("extract", a.mode)) return rc;
+    const size_t lds = (size_t)(2 * (a.N + a.M) + 4) * sizeof(float);
+    hipLaunchKernelGGL(extract_kernel, dim3(a.B), dim3(1024), lds, s, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "extract launch")) return rc;
     sinkhorn_count_launch(SK_EXTRACT);
-    if (defer_alldust || a.alldust_counters || a.cnt0) return MDGAT_OK;      // (counters, or a ragged batch: the kernel applied the rule itself)
-    return launch_alldust_fixup(B, N, M, a.mode, a.m0, a.s1, s);
+    if (ex.defer_alldust || a.alldust_counters || a.cnt0) return MDGAT_OK;      // (counters, or a ragged batch: the kernel applied the rule itself)
+    return launch_alldust_fixup(a.B, a.N, a.M, a.mode, a.m0, a.s1, s);
+}
+
+int launch_extract(int B, int N, int M, const float* Z, const SkExtract& ex, hipStream_t s, const int* cnt0, const int* cnt1) {
+    if (B <= 0) return MDGAT_OK;
+    ExArgs a = ex_args(ex, B, N, M);
+    a.Z = Z; a.cnt0 = cnt0; a.cnt1 = cnt1;
+    return launch_extract_impl(a, ex, s);
 }
 
 // the extraction from arg-maxes another kernel has decided (sinkhorn_f64.hip: on the fp64 Z): rbest [B][N], cbest [B][M]
@@ -1341,14 +1253,85 @@ int launch_extract_from_bests(int B, int N, int M, const SkExtract* ex, const in
                               const float* cbest_val, hipStream_t s, const int* cnt0, const int* cnt1) {
     if (B <= 0) return MDGAT_OK;
     if ((cnt0 != nullptr) != (cnt1 != nullptr)) { mdgat_set_error("extract: per-pair counts for one frame only"); return MDGAT_ERR_BAD_ARG; }
-    ExArgs xa{nullptr, N, M, ex->mode, ex->thr, ex->m0, ex->m1, ex->s0, ex->s1, nullptr, nullptr, nullptr, nullptr, B, rbest_idx, rbest_val, cbest_idx, cbest_val,
-              1, 1, ex->matched, ex->matched_token, cnt0, cnt1};
-    return launch_extract_impl(B, N, M, xa, s, ex->defer_alldust != 0);
+    ExArgs a = ex_args(*ex, B, N, M);
+    a.rbest_idx = rbest_idx; a.rbest_val = rbest_val; a.cbest_idx = cbest_idx; a.cbest_val = cbest_val; a.cnt0 = cnt0; a.cnt1 = cnt1;
+    return launch_extract_impl(a, *ex, s);
 }
 
-int launch_extract(int B, int N, int M, const float* Z, int mode, float thr, int64_t* m0, int64_t* m1, float* s0,
-                   float* s1, hipStream_t s) {
+// the streaming kernel in the plan's instantiation; gated: behind a cluster launch (a.only_if), counted apart
+static int launch_streaming(const SkArgs& a, int B, int form, bool gated, hipStream_t s) {
+    static int (*const launch[])(const SkArgs&, int, hipStream_t) = {      // SK_STREAM_1 .. SK_STREAM_32, SK_RAGGED_1 .. SK_RAGGED_8
+        launch_sk<1, 16>, launch_sk<2, 16>, launch_sk<4, 16>, launch_sk<8, 16>, launch_sk<16, 8>, launch_sk<32, 8>,
+        launch_sk<1, 16, true>, launch_sk<2, 16, true>, launch_sk<4, 16, true>, launch_sk<8, 16, true>};
+    if (form < SK_STREAM_1 || form > SK_RAGGED_8) { mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", a.M); return MDGAT_ERR_UNSUPPORTED; }
+    const int rc = launch[form - SK_STREAM_1](a, B, s);
+    if (!rc) sinkhorn_count_launch(gated ? SK_GATED : form);
+    return rc;
+}
+
+// the cluster kernel, the gated streaming kernel behind it where the plan has one, then the extraction from the cluster kernel's arg-maxes
+static int launch_scaling(const SkCall& c, const SkPlan& pl, const SkLayout& l) {
+    hipStream_t s = c.stream;
+    if (pl.rc) { mdgat_set_error("sinkhorn: %d workgroups per pair do not fit the device", pl.GR * pl.GC); return pl.rc; }
+    if (!c.slots_cleared) {    // (the forward has the score kernel clear l.clear_bytes; here: the slots of the pairs in flight, and the flags)
+        if (int rc = mdgat_check_hip(hipMemsetAsync(c.ws, 0, l.slots + l.per_group * pl.ngroups, s), "memset(sinkhorn slots)")) return rc;
+        if (int rc = mdgat_check_hip(hipMemsetAsync(l.at<char>(c.ws, l.flags), 0, l.flags_bytes, s), "memset(sinkhorn pair flags)")) return rc;
+    }
+    unsigned* const header = l.at<unsigned>(c.ws, l.header);
+    // test hook (tests/test_gpu_ops.py): pretend a partner was lost - the launch's error word starts out set, so the gated
+    // streaming kernel and the extraction from its Z run for real
+    if (const char* f = getenv("MDGAT_SK_FORCE_FALLBACK"); f && *f == '1')
+        if (int rc = mdgat_check_hip(hipMemsetAsync(header + SK_WORD_ERROR, 1, sizeof(unsigned), s), "memset(sinkhorn error word)")) return rc;
+    SksArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z};
+    a.slots = l.at<unsigned long long>(c.ws, l.slots); a.error_word = header + SK_WORD_ERROR; a.pair_flags = l.at<unsigned>(c.ws, l.flags);
+    a.range_guard = c.status ? c.status + MDGAT_STATUS_RANGE : nullptr;
+    a.B = c.B; a.N = c.N; a.M = c.M; a.iters = c.iters; a.ngroups = pl.ngroups; a.GR = pl.GR; a.GC = pl.GC; a.xcd_map = pl.xcd_map;
+    a.ext_mode = c.ex ? c.ex->mode : -1;
+    if (c.ex) {
+        a.rbest_idx = l.at<int>(c.ws, l.rbest_idx); a.rbest_val = l.at<float>(c.ws, l.rbest_val);
+        a.cbest_idx = l.at<int>(c.ws, l.cbest_idx); a.cbest_val = l.at<float>(c.ws, l.cbest_val);
+    }
+    void* args[] = {&a};
+    const void* kern = pl.scaling == SK_SCALING_2D ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<true, 16>)
+                     : pl.scaling == SK_SCALING_16 ? reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 16>)
+                                                  : reinterpret_cast<const void*>(sinkhorn_scaling_kernel<false, 4>);
+    // plain or cooperative, and whether the gated streaming kernel follows: sinkhorn_plan
+    float* zfb = c.Z ? c.Z : c.Zfb;
+    const bool can_fall_back = pl.stream >= 0;
+    const hipError_t e = pl.cooperative ? hipLaunchCooperativeKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s)
+                                        : hipLaunchKernel(kern, dim3(pl.grid), dim3(SKS_THREADS), args, 0, s);
+    if (int rc = mdgat_check_hip(e, "sinkhorn scaling launch")) return rc;
+    sinkhorn_count_launch(pl.scaling);
+    if (can_fall_back) {
+        SkArgs f{c.scores, c.alpha_dev, c.alpha_host, zfb, c.N, c.M, c.iters};
+        f.only_if = a.error_word; f.status_fallback = c.status ? c.status + MDGAT_STATUS_SK_FALLBACK : nullptr; f.pair_flags = a.pair_flags;
+        if (int rc = launch_streaming(f, c.B, pl.stream, true, s)) return rc;
+    }
+    if (!c.ex) return MDGAT_OK;
+    ExArgs x = ex_args(*c.ex, c.B, c.N, c.M);
+    x.sk_error = can_fall_back ? a.error_word : nullptr; x.Zfb = zfb; x.pair_flags = a.pair_flags;
+    x.alldust_counters = (c.ex->defer_alldust || c.B >= 65536) ? nullptr : header + SK_WORD_TICKET;      // (cleared with the slots)
+    x.rbest_idx = a.rbest_idx; x.rbest_val = a.rbest_val; x.cbest_idx = a.cbest_idx; x.cbest_val = a.cbest_val; x.GR = pl.GR; x.GC = pl.GC;
+    return launch_extract_impl(x, *c.ex, s);
+}
+
+// On a usable workspace the cluster kernel; otherwise, and for every call with counts, the streaming kernel into Z - a ragged batch on the RAGGED instantiation
+// for its slot, picked from the padded sizes alone: a wider NC than a pair's own M would select gives the pair the same bits - then extract_kernel on that Z.
+int launch_sinkhorn(const SkCall& c) {
+    const int B = c.B, N = c.N, M = c.M;
     if (B <= 0) return MDGAT_OK;
-    ExArgs a{Z, N, M, mode, thr, m0, m1, s0, s1, nullptr, nullptr, nullptr, nullptr, B, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr, 0u};
-    return launch_extract_impl(B, N, M, a, s);
+    const bool ragged = c.cnt0 || c.cnt1;
+    if (!c.scores || (ragged && (!c.cnt0 || !c.cnt1))) { mdgat_set_error("sinkhorn: null pointer"); return MDGAT_ERR_BAD_ARG; }
+    if (!c.Z && !c.ex) { mdgat_set_error("sinkhorn: nothing to compute (no Z, no extraction)"); return MDGAT_ERR_BAD_ARG; }
+    if (N <= 0 || M <= 0 || c.iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, c.iters); return MDGAT_ERR_BAD_ARG; }
+    const SkLayout l = sk_layout(B, N, M);
+    const bool usable = !ragged && l.usable(c.ws, c.ws_bytes);      // (the cluster kernel takes no counts)
+    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, c.Z || c.Zfb, ragged);
+    if (usable) return launch_scaling(c, p, l);
+    if (!c.Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
+    if (ragged && p.rc) { mdgat_set_error("sinkhorn: ragged slots of %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS); return p.rc; }
+    SkArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z, N, M, c.iters};
+    a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;
+    if (int rc = launch_streaming(a, B, p.stream, false, c.stream)) return rc;
+    return c.ex ? launch_extract(B, N, M, c.Z, *c.ex, c.stream, c.cnt0, c.cnt1) : MDGAT_OK;
 }

@@ -53,8 +53,8 @@ def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool
     with torch.cuda.device(s.device):
         name, lead, _keep = _entry('mdgat_sinkhorn', counts, B, s.device)
         need = 0 if streaming or counts is not None else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
-        ws = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
-        tail = () if counts is not None else (ws.data_ptr() if ws is not None else None, need)
+        _buf, ws_ptr, _ = _workspace(need, s.device) if need else (None, None, 0)
+        tail = () if counts is not None else (ws_ptr, need)
         _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), *tail, _stream(s)), name)
     return Z
 
@@ -77,14 +77,12 @@ def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: i
         if counts is not None:
             # the ragged entry scans the Z it is given, or - when none is wanted - one it produces into a workspace
             need = 0 if want_Z else lib.mdgat_sinkhorn_ragged_workspace_bytes(B, N, M)
-            _buf, ws_ptr, _ = _workspace(need, s.device) if need else (None, None, 0)
             z_out, lent = want_Z, ()
         else:
             need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
-            _buf = torch.empty(need, dtype=torch.uint8, device=s.device) if need else None
-            ws_ptr = _buf.data_ptr() if need else None
             z_out = want_Z or not need
             lent = (None if z_out else Zbuf.data_ptr(),)
+        _buf, ws_ptr, _ = _workspace(need, s.device) if need else (None, None, 0)
         _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), int(mode), float(match_threshold), m0.data_ptr(),
                                       m1.data_ptr(), s0.data_ptr(), s1.data_ptr(), Zbuf.data_ptr() if z_out else None, *lent,
                                       ws_ptr, need, _stream(s)), name)

@@ -1,4 +1,4 @@
-"""The 13 instantiations the fp32 Sinkhorn launchers (csrc/sinkhorn.hip: launch_sinkhorn, launch_sinkhorn_ragged) can reach, as the tests
+"""The 13 instantiations the fp32 Sinkhorn launcher (csrc/sinkhorn.hip: launch_sinkhorn, with or without per-pair counts) can reach, as the tests
 name them, and the two symbols that make their choices observable: mdgat_sinkhorn_plan (the path, the instantiations and the launch
 parameters as a pure function; no device) and mdgat_sinkhorn_launches (launches so far by index).  The table of indices: include/mdgat_hip.h.
 

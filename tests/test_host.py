@@ -660,3 +660,76 @@ def test_module_dtype_is_the_arithmetic_request(monkeypatch):
             p.eval()(d)
             assert cfgs[-1] == (_lib.ARITH_FP64, want), (given, cfgs[-1])
             p._invalidate()
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the uniform fp32 Sinkhorn / extraction entries: what they refuse before they need a device (codes and texts as they have always been).
+# As in test_ragged_fp32_refusals.py the "device" pointers are the address of a host tensor that is never read, because the call is refused
+# (or, at an empty batch, returns) first; so that a regression can never become a launch on host pointers, machines with a device skip them.
+no_device = pytest.mark.skipif(torch.cuda.is_available(), reason='hands host addresses over as device pointers: machines without a device only')
+_KEEP = torch.zeros(64, dtype=torch.float64)
+P = _KEEP.data_ptr()
+ALIGNED = 1 << 30                # stands for a 256-byte aligned workspace; never dereferenced
+
+
+def _sinkhorn(B=3, N=20, M=30, scores=P, iters=10, Z=P, ws=None, ws_bytes=0):
+    return 'mdgat_sinkhorn', (B, N, M, scores, 1.0, iters, Z, ws, ws_bytes, None)
+
+
+def _sinkhorn_extract(B=3, N=20, M=30, scores=P, iters=10, mode=0, outs=(P, P, P, P), Z=P, lent=None, ws=None, ws_bytes=0):
+    return 'mdgat_sinkhorn_extract', (B, N, M, scores, 1.0, iters, mode, 0.2, *outs, Z, lent, ws, ws_bytes, None)
+
+
+def _extract(B=3, N=20, M=30, Z=P, mode=0, outs=(P, P, P, P)):
+    return 'mdgat_extract', (B, N, M, Z, mode, 0.2, *outs, None)
+
+
+def _one_null(i):
+    return tuple(None if j == i else P for j in range(4))
+
+
+BAD, UNSUPPORTED = _lib.ERR_BAD_ARG, _lib.ERR_UNSUPPORTED
+SHORT = {'ws': ALIGNED, 'ws_bytes': -1}      # (-1: one byte less than mdgat_sinkhorn_workspace_bytes asks for)
+UNIFORM_REFUSALS = [
+    (_sinkhorn(scores=None), BAD, 'mdgat_sinkhorn: null pointer'),
+    (_sinkhorn(Z=None), BAD, 'mdgat_sinkhorn: null pointer'),
+    (_sinkhorn(B=-1), _lib.OK, ''),
+    (_sinkhorn(B=0), _lib.OK, ''),
+    (_sinkhorn(N=0), BAD, 'sinkhorn: bad shape N=0 M=30 iters=10'),
+    (_sinkhorn(M=-3), BAD, 'sinkhorn: bad shape N=20 M=-3 iters=10'),
+    (_sinkhorn(iters=-1), BAD, 'sinkhorn: bad shape N=20 M=30 iters=-1'),
+    (_sinkhorn(N=64, M=4096), UNSUPPORTED, 'sinkhorn: M=4096 > 2048 unsupported'),
+    (_sinkhorn(N=4097, M=1024), UNSUPPORTED, 'sinkhorn: M=1024 > 2048 unsupported'),
+    (_sinkhorn_extract(scores=None), BAD, 'mdgat_sinkhorn_extract: null pointer'),
+    *[(_sinkhorn_extract(outs=_one_null(i)), BAD, 'mdgat_sinkhorn_extract: null pointer') for i in range(4)],
+    (_sinkhorn_extract(mode=-1), BAD, 'mdgat_sinkhorn_extract: bad mode -1'),
+    (_sinkhorn_extract(mode=4), BAD, 'mdgat_sinkhorn_extract: bad mode 4'),
+    (_sinkhorn_extract(mode=4, B=0), BAD, 'mdgat_sinkhorn_extract: bad mode 4'),         # (the mode is checked before the empty batch returns)
+    (_sinkhorn_extract(B=-1), _lib.OK, ''),
+    (_sinkhorn_extract(B=0), _lib.OK, ''),
+    (_sinkhorn_extract(M=0), BAD, 'sinkhorn: bad shape N=20 M=0 iters=10'),
+    (_sinkhorn_extract(iters=-1), BAD, 'sinkhorn: bad shape N=20 M=30 iters=-1'),
+    (_sinkhorn_extract(Z=None), BAD, 'sinkhorn: the streaming kernel needs a Z buffer'),
+    (_sinkhorn_extract(Z=None, lent=P), BAD, 'sinkhorn: the streaming kernel needs a Z buffer'),
+    (_sinkhorn_extract(Z=None, lent=P, **SHORT), BAD, 'sinkhorn: the streaming kernel needs a Z buffer'),
+    (_sinkhorn_extract(Z=None, lent=P, ws=ALIGNED + 4, ws_bytes=1 << 40), BAD, 'sinkhorn: the streaming kernel needs a Z buffer'),
+    (_extract(Z=None), BAD, 'mdgat_extract: null pointer'),
+    *[(_extract(outs=_one_null(i)), BAD, 'mdgat_extract: null pointer') for i in range(4)],
+    (_extract(mode=-1), BAD, 'extract: bad mode -1'),
+    (_extract(mode=4), BAD, 'extract: bad mode 4'),
+    (_extract(mode=4, B=0), _lib.OK, ''),                                                   # (here the empty batch returns first)
+    (_extract(B=-1), _lib.OK, ''),
+]
+
+
+@no_device
+@pytest.mark.parametrize('case', range(len(UNIFORM_REFUSALS)))
+def test_uniform_sinkhorn_entries_refuse_before_any_device_call(case):
+    (name, args), code, text = UNIFORM_REFUSALS[case]
+    lib = _lib.load()
+    if name == 'mdgat_sinkhorn_extract' and args[-2] == -1:
+        args = (*args[:-2], lib.mdgat_sinkhorn_workspace_bytes(*args[:3]) - 1, None)
+        assert args[-2] > 0
+    assert getattr(lib, name)(*args) == code, (name, args)
+    if code:
+        assert _lib.last_error() == text
