@@ -410,8 +410,9 @@ def _A():
     return A
 
 
-def _attention(qkv, N, M, cross, masks, dmsg=None):
-    """(message [B, N + M, 128], dqkv or None) by attention_grad_ref's formulas, in the module's current precision."""
+def _attention(qkv, N, M, cross, masks, dmsg=None, kv_queries=None):
+    """(message [B, N + M, 128], dqkv or None) by attention_grad_ref's formulas, in the module's current precision.  ``kv_queries``
+    plants a mistake (train_ref's 'tile_tail'): a function nq -> how many of a side's leading queries contribute to dk and dv."""
     A = _A()
     qkv = _f(qkv)
     B, s = qkv.shape[0], 1 / np.sqrt(_DT[0](32))
@@ -432,8 +433,9 @@ def _attention(qkv, N, M, cross, masks, dmsg=None):
             G = A._heads(_f(dmsg)[:, qs].reshape(B, -1, 4, 32))
             dS = P * (G @ T(V) - (G * O).sum(axis=-1, keepdims=True))
             dqkv[:, qs, 0] += un(s * (dS @ K))
-            dqkv[:, ks, 1] += un(s * (T(dS) @ Q))
-            dqkv[:, ks, 2] += un(T(P) @ G)
+            c = Q.shape[2] if kv_queries is None else kv_queries(Q.shape[2])
+            dqkv[:, ks, 1] += un(s * (T(dS[:, :, :c]) @ Q[:, :, :c]))
+            dqkv[:, ks, 2] += un(T(P[:, :, :c]) @ G[:, :, :c])
     return msg, dqkv
 
 

@@ -5,7 +5,12 @@ Tolerance: per quantity 32 x the reference's own measured error ``err`` stored i
 every recorded gradient, every BatchNorm buffer.  Matches are compared exactly (the generator refuses a case whose arg-max is decided by
 less than 1e-5).  The matching scores come from ``ops.extract``, which reads Z rounded to float32 and takes exp in float32: they are held
 to its own bound, extract_ref.SCORE_TOL = 1e-6 (values <= 1), not to an fp64 one.  Every comparison prints the worst fraction of the
-bound it met."""
+bound it met.
+
+The shape cases (train_ref.SHAPE_CASES) take the step past one tile of every kernel it composes, to B = 1, dynamic self and full cross
+layers and two pairs of layers, under the same rule.  Their fixtures hold the reference's value of everything but the layers'
+convolution weights; for those the expected value is the float64 restatement run here on the host, which the generator held to the
+reference.  A dynamic layer's selection is asserted equal to the restatement's before any gradient is compared."""
 import functools
 
 import numpy as np
@@ -144,6 +149,110 @@ def test_eval_mode_leaves_the_buffers_and_agrees_with_forward():
         assert torch.equal(out[f'matches{f}'], ref[f'matches{f}'])
         d = (out[f'matching_scores{f}'] - ref[f'matching_scores{f}']).abs().max().item()
         print(f'eval mode: matching_scores{f}: training_forward against forward: {d:.3e}')
+
+
+# ---- the shape cases (train_ref.SHAPE_CASES): the step past one tile of every kernel it composes ----
+def _shape_net(case, training=True):
+    from mdgat_matcher_amd import MDGAT
+    method, _, _, _, L, k, _ = T.case_spec(case)
+    net = MDGAT(T.config(method, L=L, k=k)).double()
+    net.load_state_dict(T.initial_state(L=L))
+    return net.to(DEV).train(training)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(case):
+    """The float64 restatement of the case's step on the host: the expected value of the layers' convolution weights, and the masks."""
+    method, _, _, _, L, k, _ = T.case_spec(case)
+    return T.step(T.numpy_state(T.initial_state(L=L)), _case(case)['data'], method, L=L, k_list=k)
+
+
+@pytest.mark.parametrize('case', sorted(T.SHAPE_CASES))
+def test_step_reproduces_shape_fixture(case, monkeypatch):
+    from mdgat_matcher_amd import ops
+    c, res = _case(case), _restated(case)
+    method, B, N, M, L, k_list, _ = T.case_spec(case)
+    net, data = _shape_net(case), _data(case)
+    calls, attention = [], ops.attention_f64
+
+    def recording(qkv, *a, **kw):           # what every layer handed its attention
+        calls.append((qkv.detach().clone(), a, kw))
+        return attention(qkv, *a, **kw)
+    monkeypatch.setattr(ops, 'attention_f64', recording)
+    out = _step(net, data)
+    monkeypatch.undo()
+    assert out['loss'].grad_fn is not None and tuple(out['loss'].shape) == ((B,) if method == 'gap_loss' else ())
+    assert set(out) == {'matches0', 'matches1', 'matching_scores0', 'matching_scores1', 'loss'}
+    # a dynamic layer kept the keys the restatement kept: a gradient outside the bound below is no selection difference in disguise
+    sched = T.topk_schedule(L, k_list)
+    assert len(calls) == 2 * L
+    for i, (qkv, a, kw) in enumerate(calls):
+        assert a == (N, M, bool(i % 2)) and kw == {'topk': sched[i]}
+        if sched[i] > 0:
+            _, masks = ops.attention_f64(qkv, N, M, bool(i % 2), topk=sched[i], return_selection=True)
+            for side, (got_m, want_m) in enumerate(zip(masks, res['masks'][i])):
+                differ = int((got_m.cpu().numpy() != want_m).any(-1).sum())
+                assert differ == 0, f'layer {i}, frame {side}: {differ} rows selected unlike the top-{sched[i]} of the fp64 logits (gap {res["topk_gap"]:.2e})'
+    got = _result(net, out)
+    assert all(('grad:' + k) in got for k, p in net.named_parameters()), 'a parameter was left without a gradient'
+    want = T.shape_want(c, res)
+    names = [k for k in want if k != 'Z']
+    assert len(names) == len(c['err']) - 1 and sum(not T.shape_stored(k) for k in names) == 12 * L
+    worst, where, fr = T.compare(got, want, c['err'], names=names)
+    _report(case, fr)
+    print(f'{case}: worst fraction of the bound {worst:.4f} at {where}')
+    assert worst <= 1.0
+    assert _nbt(net) == c['nbt']
+    for f in (0, 1):
+        assert out[f'matches{f}'].dtype == torch.int64 and np.array_equal(out[f'matches{f}'].cpu().numpy(), c[f'matches{f}'])
+        s = out[f'matching_scores{f}']
+        assert s.dtype == torch.float64
+        e = float(np.abs(s.cpu().numpy() - c[f'mscores{f}']).max())
+        print(f'{case}: matching_scores{f}: {e / E.SCORE_TOL:.4f} of extract\'s bound')
+        assert e <= E.SCORE_TOL
+    if method != 'superglue':           # the reference's in-place rewrite of the caller's gts
+        g0, g1 = c['data']['gt_matches0'], c['data']['gt_matches1']
+        assert np.array_equal(data['gt_matches0'].cpu().numpy(), np.where(g0 == -1, g1.shape[1], g0))
+        assert np.array_equal(data['gt_matches1'].cpu().numpy(), np.where(g1 == -1, g0.shape[1], g1))
+    else:
+        assert np.array_equal(data['gt_matches0'].cpu().numpy(), c['data']['gt_matches0'])
+
+
+@pytest.mark.parametrize('case', ['one_pair', 'tiles'])
+def test_two_identical_shape_steps_give_the_same_bits(case):
+    res = []
+    for _ in range(2):
+        net = _shape_net(case)
+        out = _step(net, _data(case))
+        res.append((_result(net, out), out))
+    a, b = res[0][0], res[1][0]
+    assert set(a) == set(b) == {k for k in _case(case)['err'] if k != 'Z'}
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    for k in ('matches0', 'matches1', 'matching_scores0', 'matching_scores1'):
+        assert torch.equal(res[0][1][k], res[1][1][k])
+
+
+@pytest.mark.parametrize('case', sorted(T.SHAPE_CASES))
+def test_eval_mode_agrees_with_forward_at_shape(case):
+    """``training_forward`` in eval mode against the exact-mode ``forward`` of the same module.  Each side's scores are ``ops.extract``'s,
+    within SCORE_TOL of exp of its Z: 2 x SCORE_TOL between them."""
+    net = _shape_net(case, training=False)
+    before = {k: b.clone() for k, b in net.named_buffers()}
+    out = net.training_forward(_data(case))
+    assert out['loss'].grad_fn is not None
+    out['loss'].mean().backward()
+    torch.cuda.synchronize()
+    assert all(torch.equal(b, before[k]) for k, b in net.named_buffers())
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
+    with torch.no_grad():
+        ref = net(_data(case))
+    assert all(torch.equal(b, before[k]) for k, b in net.named_buffers())
+    for f in (0, 1):
+        assert torch.equal(out[f'matches{f}'], ref[f'matches{f}'])
+        d = (out[f'matching_scores{f}'] - ref[f'matching_scores{f}']).abs().max().item()
+        print(f'{case}, eval mode: matching_scores{f}: training_forward against forward: {d / (2 * E.SCORE_TOL):.4f} of the bound')
+        assert d <= 2 * E.SCORE_TOL
 
 
 def _train_loop(net, batches, optimizer):

@@ -18,7 +18,9 @@ float64 - that|; a gradient that is zero in exact arithmetic (the biases in fron
 4 u max|dW of the same convolution|.  A third float64 evaluation is held to 32 err: 2 for the two implementations compared, 16 for the
 tail over summation orders.
 
-``step(..., plant=...)`` plants the mistakes the bound must catch (PLANTS)."""
+``step(..., plant=...)`` plants the mistakes the bound must catch (PLANTS).  Two of them (TAIL_PLANTS) begin beyond one tile of a
+kernel - the queries of a ragged last tile missing from dk and dv, the rows of a second slab missing from a dW - and change no bit of
+the three small fixtures; the shape cases (SHAPE_CASES) are the ones that see them."""
 import os
 
 import numpy as np
@@ -30,7 +32,10 @@ U = 2.0 ** -53
 FACTOR = 32.0
 PERM = A.PERM
 EPS, MOMENTUM = 1e-5, 0.1               # nn.BatchNorm1d's defaults, which the reference's MLP takes
-PLANTS = ('joint_bn', 'frame_order', 'no_residual', 'cross_kv_grad', 'no_perm_merge', 'final_proj_entry', 'no_bin_grad')
+# the plants whose damage begins beyond one tile of a kernel: no-ops, bit for bit, on the three small fixtures (SHAPE_CASES shows them)
+TAIL_PLANTS = ('tile_tail', 'second_slab')
+TILE_QUERIES, SLAB_ROWS = 64, 512       # queries per workgroup of the attention backward's dk / dv pass; rows per slab of the dW kernel
+PLANTS = ('joint_bn', 'frame_order', 'no_residual', 'cross_kv_grad', 'no_perm_merge', 'final_proj_entry', 'no_bin_grad') + TAIL_PLANTS
 METHODS = ('superglue', 'triplet_loss', 'gap_loss')
 
 # ---- the fixtures (tools/make_goldens_train.py) ----
@@ -44,12 +49,48 @@ ENC_PREFIXES = ('kenc.', 'denc.', 'final_proj.', 'bin_score')          # the gra
 GAP_FILES = ('train_gap_io', 'train_gap_grads_enc', 'train_gap_grads_l0_attn', 'train_gap_grads_l0_mlp', 'train_gap_grads_l1_attn',
              'train_gap_grads_l1_mlp', 'train_gap_step2')
 FILES = {'gap': GAP_FILES, 'superglue': ('train_superglue',), 'triplet': ('train_triplet',)}
+# ---- the shape cases: a whole step past one tile of every kernel it composes (same generator, same seed, same iterations) ----
+# Each carries its own network: L pairs of layers and the k list (None: full attention; topk_schedule gives the k of every layer).
+#   tiles            2 and 3 query tiles of the attention backward with ragged 16-blocks (70 = 64 + 6, 180 = 11 x 16 + 4); 540 rows in
+#                    frame 1 and 750 in q | k | v: a second, ragged slab of the dW kernel; layer 1 cross with k = 16, layer 2 self with
+#                    k = 8, layer 3 cross and full; the residual gradient summed over four propagations
+#   one_pair         B = 1: the merged message's frames are views at a storage offset, BatchNorm over one pair's rows; layer 0 self
+#                    with k = 8, layer 1 cross and full
+#   square_triplet, square_superglue    three 64-point tiles, the last with 2 points; the equal-size losses beyond one tile
+#   wide             M + 1 > 640: the nine-chunk Sinkhorn backward with its history and the streaming forward inside a step; 11 key
+#                    tiles against one query tile in the cross layer
+#               case,               loss_method,    B, N,   M,   L, k list,               first_pair
+SHAPE_CASES = {'tiles':            ('gap_loss',     3, 70,  180, 2, [None, 16, 8, None], 40),
+               'one_pair':         ('gap_loss',     1, 33,  95,  1, [8, None],           41),
+               'square_triplet':   ('triplet_loss', 2, 130, 130, 1, [None, 32],          44),
+               'square_superglue': ('superglue',    2, 130, 130, 1, [None, 32],          44),
+               'wide':             ('gap_loss',     1, 24,  650, 1, [8],                 46)}
+# what a shape case stores of the reference's results (``r:``): the loss, Z, every buffer and every gradient but the layers' four
+# convolution weights (0.5 + 0.8 MB per layer); those are held to this restatement in float64, which the generator holds to the
+# reference.  Every quantity has its measured error (``e:``).
+SHAPE_UNSTORED = ('attn.proj.0.weight', 'attn.proj.1.weight', 'attn.proj.2.weight', 'attn.merge.weight', 'mlp.0.weight', 'mlp.3.weight')
+SHAPE_PARTS = ('io', 'z', 'grads')
+FILES.update({case: tuple(f'train_shape_{case}_{part}' for part in SHAPE_PARTS) for case in SHAPE_CASES})
 ALL_FILES = tuple(f for fs in FILES.values() for f in fs)
 
 
-def config(method, **over):
+def shape_stored(quantity):
+    """Whether a shape case stores the reference's value of this quantity of ``flatten``."""
+    return not (quantity.startswith('grad:gnn.layers.') and quantity.endswith(SHAPE_UNSTORED))
+
+
+def case_spec(case):
+    """(loss_method, B, N, M, L, k list, first_pair) of a case of CASES or SHAPE_CASES."""
+    if case in CASES:
+        method, B, n, m, first = CASES[case]
+        return method, B, n, m, L, list(K_LIST), first
+    method, B, n, m, Lc, k, first = SHAPE_CASES[case]
+    return method, B, n, m, Lc, list(k), first
+
+
+def config(method, L=L, k=K_LIST, **over):
     from mdgat_matcher_amd import synth
-    return synth.default_config(L=L, k=list(K_LIST), sinkhorn_iterations=ITERS, loss_method=method, triplet_loss_gamma=GAMMA, **over)
+    return synth.default_config(L=L, k=list(k), sinkhorn_iterations=ITERS, loss_method=method, triplet_loss_gamma=GAMMA, **over)
 
 
 def _dt():
@@ -117,12 +158,15 @@ class _Stack:
             return [outs[0][:cut], outs[0][cut:]]
         return outs
 
-    def backward(self, douts, grads, joint=False):
-        """douts per frame -> dx per frame; the parameters' gradients are summed into ``grads``."""
+    def backward(self, douts, grads, joint=False, slab_rows=None):
+        """douts per frame -> dx per frame; the parameters' gradients are summed into ``grads``.  ``slab_rows`` (a planted mistake): a
+        call of more rows than that forms the dW of its last convolution from the first ``slab_rows`` rows alone."""
         groups = [np.concatenate(douts)] if joint else list(douts)
         dxs = []
         for cache, dout in zip(self.calls, groups):
             g = R.backward(cache, self.p, dout)
+            if slab_rows is not None and dout.shape[0] > slab_rows:
+                g['dW'][-1] = _f(dout)[:slab_rows].T @ cache[-1]['A'][:slab_rows]
             dxs.append(g['dx'])
             for l in range(self.n):
                 _add(grads, f'{self.prefix}.{3 * l}.weight', g['dW'][l][:, :, None])
@@ -290,6 +334,13 @@ def topk_schedule(L, k_list):
     return [0 if not (i > 2 * L - 1 - n) or k_list[i - 2 * L + n] is None else int(k_list[i - 2 * L + n]) for i in range(2 * L)]
 
 
+def _whole_tiles(nq):
+    """The planted 'tile_tail': of nq queries, how many still reach dk and dv - those of the whole tiles of TILE_QUERIES.  A frame of
+    less than one tile has no ragged tail BEHIND a whole tile: its only tile is the one every kernel runs, so it is left alone (which is
+    what makes the plant invisible to the small fixtures)."""
+    return nq if nq < TILE_QUERIES else TILE_QUERIES * (nq // TILE_QUERIES)
+
+
 def step(sd, data, method, gamma=GAMMA, L=L, k_list=K_LIST, iters=ITERS, masks=None, plant=None):
     """One forward and ``loss.mean().backward()`` in the current precision.
 
@@ -348,7 +399,8 @@ def step(sd, data, method, gamma=GAMMA, L=L, k_list=K_LIST, iters=ITERS, masks=N
     dd = [g0, g1]
     for ly in reversed(layers):
         pre, mlp = ly['pre'], ly['mlp']
-        dX = [v.reshape(B, -1, 256) for v in mlp.backward([g.reshape(-1, 128) for g in dd], grads, joint)]
+        dX = [v.reshape(B, -1, 256) for v in mlp.backward([g.reshape(-1, 128) for g in dd], grads, joint,
+                                                          slab_rows=SLAB_ROWS if plant == 'second_slab' else None)]
         dmerged = np.concatenate([dX[0][..., 128:], dX[1][..., 128:]], axis=1)
         dd = [dX[f][..., :128] + (0 if plant == 'no_residual' else dd[f]) for f in (0, 1)]
         dWm = np.zeros((128, 128), dtype=_dt())
@@ -358,7 +410,7 @@ def step(sd, data, method, gamma=GAMMA, L=L, k_list=K_LIST, iters=ITERS, masks=N
         else:
             dWm[:, PERM] = prod
         grads[f'{pre}.attn.merge.weight'], grads[f'{pre}.attn.merge.bias'] = dWm[:, :, None], dmerged.sum(axis=(0, 1))
-        _, dqkv = R._attention(ly['qkv'], N, M, ly['cross'], ly['mk'], dmerged @ ly['WmP'])
+        _, dqkv = R._attention(ly['qkv'], N, M, ly['cross'], ly['mk'], dmerged @ ly['WmP'], kv_queries=_whole_tiles if plant == 'tile_tail' else None)
         dqkv = dqkv.reshape(B, N + M, 3, 128)
         ddesc = np.zeros_like(ly['desc'])
         for j, c in enumerate('qkv'):
@@ -454,7 +506,15 @@ def load(golden_dir, case):
     return out
 
 
-def initial_state(seed=SEED):
+def shape_want(c, res):
+    """What a step of a shape case is held to: the reference's recorded value where the fixture ``c`` stores one, this restatement's
+    float64 result ``res`` (which the generator held to the reference) for the layers' convolution weights."""
+    mine = flatten(res)
+    assert set(mine) == set(c['err']) and set(c['want']) <= set(mine)
+    return {k: c['want'].get(k, v) for k, v in mine.items()}
+
+
+def initial_state(seed=SEED, L=L):
     from mdgat_matcher_amd import synth
     return synth.make_state_dict(L, seed)
 

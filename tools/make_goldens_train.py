@@ -18,6 +18,13 @@ num_batches_tracked afterwards; quantities are ``loss``, ``Z``, ``grad:<paramete
 * ``superglue``, ``triplet``   2 pairs of 24 x 24: the inputs, loss, matches, scores, buffers and the gradients of kenc, denc,
                  final_proj and bin_score, one file each.
 
+* the shape cases (train_ref.SHAPE_CASES: ``tiles``, ``one_pair``, ``square_triplet``, ``square_superglue``, ``wide``), each with its
+                 own L and k list, three files each: ``train_shape_<case>_io`` (the inputs, meta, ``k`` with None written as 0, matches
+                 and scores, ``nbt:``, the loss and every buffer, and ``e:`` of EVERY quantity), ``_z`` (Z) and ``_grads`` (every
+                 gradient but the layers' convolution weights - q, k, v, merge and the two of the MLP, 1.3 MB per layer).  Those are
+                 held by the tests to the float64 restatement, so the generator asserts that the restatement meets the reference
+                 within the bound on every quantity, stored or not, and that its num_batches_tracked are the reference's.
+
 The generator REFUSES a case in which a discrete decision is open: a dynamic layer's k-th and (k + 1)-th largest logits of a row
 closer than 1e-9; a BatchNorm output |z| below 1e3 x the recorded error of that pre-activation; a triplet hard negative decided by
 less than 1e-9 or a clamp argument within 1e-9 of zero; a match arg-max decided by less than 1e-5 (ops.extract reads Z rounded to
@@ -161,9 +168,48 @@ def gen_case(M, case):
     return files
 
 
+def gen_shape_case(M, case):
+    """One case of train_ref.SHAPE_CASES: the same recipe as ``gen_case`` with the case's own L and k list, every quantity measured
+    (``e:``), and the reference's value (``r:``) of all of them but the layers' convolution weights.  For those the tests' expected
+    value is the float64 restatement, so it is held here to the reference on EVERY quantity, stored or not."""
+    method, B, n, m, L, k_list, first = T.case_spec(case)
+    cfg = T.config(method, L=L, k=k_list)
+    sd = T.initial_state(L=L)
+    net = M.MDGAT(cfg).double().train()
+    net.load_state_dict(sd, strict=True)
+    data = synth.make_batch(B, n, m, first_pair=first)
+    data['gt_matches0'], data['gt_matches1'] = GL.ground_truth(data, first)
+    sd0 = T.numpy_state(net.state_dict())
+    npdata = {k: v.numpy().copy() for k, v in data.items()}
+    rec, nbt, extra = ref_step(M, net, data)
+    err, mine, truth, err_z = T.reference_error(sd0, npdata, method, rec, L=L, k_list=k_list, iters=T.ITERS)
+    assert set(err) == set(rec) == set(T.flatten(mine)), 'a quantity without a measured error'
+    margin = check_decided(case, method, mine, err_z, rec['Z'], npdata['gt_matches0'], npdata['gt_matches1'], cfg['mutual_check'])
+    assert {k: int(v) for k, v in mine['after'].items() if k.endswith('num_batches_tracked')} == nbt
+    worst, where, _ = T.compare(T.flatten(mine), rec, err)
+    assert worst <= 1.0, f'{case}: the restatement is {worst:.3g} x the bound from the reference at {where}'
+    clamp = LG.clamp_margin(rec['Z'], npdata['gt_matches0'], npdata['gt_matches1'], method, T.GAMMA)
+    rel = rel_sizes(err, rec)
+    at = max(rel, key=rel.get)
+    print(f'{case}: relu margin {margin:.2e}, top-k gap {mine["topk_gap"]:.2e}, clamp margin {clamp:.2e}'
+          + (f', hard-negative gap {LG.triplet_top_gap(rec["Z"], npdata["gt_matches0"], npdata["gt_matches1"]):.2e}' if method == 'triplet_loss' else '')
+          + f'; err / max|value|: median {np.median(list(rel.values())):.1e}, loss {rel["loss"]:.1e}, Z {rel["Z"]:.1e}, worst {rel[at]:.1e} at {at}; '
+          f'restatement against the reference: {worst:.3f} of the bound at {where}')
+    io = {'meta': np.array([B, n, m, L, T.ITERS, T.SEED, first], dtype=np.int64), 'k': np.array([0 if v is None else v for v in k_list], dtype=np.int64),
+          'gamma': np.float64(T.GAMMA)}
+    io.update({'in:' + k: v for k, v in npdata.items()}, **extra, **{'nbt:' + k: np.int64(v) for k, v in nbt.items()})
+    io.update({'e:' + k: np.float64(e) for k, e in err.items()})
+    io.update({'r:' + k: rec[k] for k in rec if k == 'loss' or k.startswith('buf:')})
+    grads = {'r:' + k: rec[k] for k in rec if k.startswith('grad:') and T.shape_stored(k)}
+    files = dict(zip(T.FILES[case], (io, {'r:Z': rec['Z']}, grads)))
+    stored = sum(k.startswith('r:') for part in files.values() for k in part)
+    assert len(rec) - stored == 2 * L * len(T.SHAPE_UNSTORED), (len(rec), stored)
+    return files
+
+
 def generate(M, out_dir):
-    for case in T.CASES:
-        for name, part in gen_case(M, case).items():
+    for case in list(T.CASES) + list(T.SHAPE_CASES):
+        for name, part in (gen_case if case in T.CASES else gen_shape_case)(M, case).items():
             path = os.path.join(out_dir, name + '.npz')
             np.savez_compressed(path, **part)
             print(f'wrote {path} ({os.path.getsize(path)} bytes)')
