@@ -206,8 +206,21 @@ int mdgat_forward_f64(mdgat_handle* h, int B, int N, int M,
  * mdgat_assemble_frames_train_f64), 0 <= starts[b] and starts[b] + counts[b] <= rows.  Else MDGAT_ERR_BAD_ARG naming the first offending
  * pair; so for a null count or start vector. */
 #define MDGAT_RAGGED_WIDE_MAX_KEYPOINTS 2048   /* the same on a handle that opted into the streaming fp64 Sinkhorn (mdgat_set_ragged_sinkhorn): the dynamic fp64 attention's limit */
-/* WHICH fp64 SINKHORN A RAGGED BATCH RUNS, per handle (the exact mode's entries mdgat_forward_f64_ragged and mdgat_forward_frames_ragged;
- * the enc-only and fp32-class ragged branches never look at it).  Returns the previous mode, -1 for a null handle or a bad mode.
+/* WHICH SINKHORN A RAGGED BATCH RUNS, per handle.  Returns the previous mode, -1 for a null handle or a bad mode.
+ * ON AN MDGAT_ARITH_FP32 HANDLE (mdgat_forward_ragged, mdgat_forward_frames_ragged): which form of the fp32 log-domain Sinkhorn.
+ *   0  default: one workgroup per pair streams the pair's scores once per iteration, all iterations in one launch;
+ *   1, 2  (alike) the SPLIT form wherever the slot has G = ceil(Np / 128) >= 2 slabs of rows: workgroup (b, g) owns rows [128 g, 128 g + 128)
+ *      of pair b below counts0[b], one launch of B * G workgroups per iteration and a finishing one that writes Z - the stream's launch
+ *      order is the only dependency, no workgroup waits for another, no atomics.  A pair's column partials (one (max, sum) per slab and
+ *      column) and its row potentials pass from launch to launch through scratch in the workspace, 2 * G * Mp * 2 + 2 * (Np + 1) floats
+ *      per pair, which mdgat_workspace_bytes(h, ...) includes from the moment the mode is set: size the workspace after changing it.
+ *      The arithmetic per element is the default form's; the column partials merge in another order, so Z agrees with it to fp32
+ *      rounding (both within 1e-4 of the fp64 reference), not bit for bit.  A pair's results depend on its own inputs and its slot alone.
+ *      A slot of one slab (Np <= 128) runs the default form, the same bits as under mode 0.  Limits and refusals do not move (512).
+ *      mdgat_profile shows every iteration as a launch of MDGAT_PROF_SINKHORN; mdgat_sinkhorn_plan and mdgat_sinkhorn_launches know
+ *      nothing of the form beyond its extraction.  The per-op entries (mdgat_sinkhorn_ragged ...) take no handle and never run it.
+ * ON AN MDGAT_ARITH_FP64 HANDLE: which fp64 Sinkhorn (the exact mode's entries mdgat_forward_f64_ragged and mdgat_forward_frames_ragged;
+ * the enc-only branch, which runs the fp32-class kernels behind fp64 encoders, never looks at it).
  *   0  default: the register-resident form only - slots of at most MDGAT_RAGGED_MAX_KEYPOINTS, refused under
  *      mdgat_set_f64_sinkhorn_form(1);
  *   1  automatic: slots within 575 keypoints, the form not forced to 1, run as under mode 0, the same bits; every other slot runs the

@@ -73,7 +73,8 @@ struct mdgat_handle {
     unsigned match_token = 0;       // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
     // Two lanes (forward_batched): the second lane's stream and the events that fork it off the caller's stream and join it again
     int lanes = 2;                  // 1 or 2 (mdgat_set_lanes; default 2, MDGAT_FORWARD_LANES)
-    int ragged_sinkhorn = 0;        // which fp64 Sinkhorn an exact ragged batch runs (mdgat_set_ragged_sinkhorn): 0 resident only, 1 automatic, 2 streaming
+    int ragged_sinkhorn = 0;        // mdgat_set_ragged_sinkhorn.  MDGAT_ARITH_FP64: which fp64 Sinkhorn an exact ragged batch runs: 0 resident only, 1 automatic,
+                                    // 2 streaming.  MDGAT_ARITH_FP32: non-zero: the ragged forwards run the split form of the fp32 Sinkhorn (split32)
     hipStream_t lane_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // optional per-kernel-class timing of mdgat_forward (mdgat_profile): HIP events on the launch stream of each lane
@@ -273,11 +274,13 @@ struct Workspace {
     char* sk64; size_t sk64_bytes;         // ... and the workspace of the fp64 Sinkhorn (0: the shape is beyond that kernel), its arg-max arrays behind it
     char* loss; size_t loss_bytes;         // a forward with a loss request (mdgat_forward_loss): the loss kernels' workspace ...
     double* Z64;                           // ... and on an exact-mode handle, whose fp64 tail hands the loss the fp64 Z, room for that Z
+    char* sksplit; size_t sksplit_bytes;   // the scratch of the fp32 Sinkhorn's split form (an MDGAT_ARITH_FP32 handle that opted in: split32; 0: the slot has one slab)
     size_t total;   // bytes
 };
 // sk64: a form of the fp64 Sinkhorn to hold beside the one a uniform call runs at this shape (sinkhorn_f64_form) - a ragged call's, which
 // mdgat_set_ragged_sinkhorn can put on the streaming form at sizes where the uniform forward runs the resident one
-Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form sk64 = Sk64Form::unsupported) {
+// split32: room for the split form of the fp32 Sinkhorn, behind everything else
+Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form sk64 = Sk64Form::unsupported, bool split32 = false) {
     const size_t R = (size_t)B * (N + M);
     Workspace w{};
     WsCarver c{static_cast<char*>(base)};
@@ -305,6 +308,10 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form s
         w.loss_bytes = loss_workspace_bytes(B, N, M);
         c.take(w.loss, w.loss_bytes);
         if (f64) c.take(w.Z64, (size_t)B * (N + 1) * (M + 1));
+    }
+    if (split32) {
+        w.sksplit_bytes = sinkhorn_split_workspace_bytes(B, N, M);
+        c.take(w.sksplit, w.sksplit_bytes);
     }
     w.total = c.bytes;
     return w;
@@ -449,7 +456,9 @@ static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool l
     const bool f64 = h && h->cfg.arithmetic == MDGAT_ARITH_FP64;
     // (this knows nothing of the call to come: it holds the form an exact ragged batch in slots of N x M would run on this handle -
     // mdgat_set_ragged_sinkhorn - beside the uniform call's, so the streaming form's K is there whenever a ragged call could need it)
-    const size_t whole = carve(nullptr, B, N, M, f64, loss, sinkhorn_f64_form(N, M, true, h ? h->ragged_sinkhorn : 0)).total;
+    // (on an MDGAT_ARITH_FP32 handle that opted in, likewise: the scratch of the split form a ragged batch in these slots would run)
+    const bool split32 = h && h->cfg.arithmetic == MDGAT_ARITH_FP32 && h->ragged_sinkhorn != 0;
+    const size_t whole = carve(nullptr, B, N, M, f64, loss, sinkhorn_f64_form(N, M, true, h ? h->ragged_sinkhorn : 0), split32).total;
     const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
@@ -458,6 +467,7 @@ static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool l
 extern "C" size_t mdgat_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, false); }
 extern "C" size_t mdgat_forward_loss_workspace_bytes(const mdgat_handle* h, int B, int N, int M) { return workspace_bytes(h, B, N, M, true); }
 
+// (an MDGAT_ARITH_FP32 handle: non-zero selects the split form of the fp32 Sinkhorn for its ragged forwards - Path::split32)
 extern "C" int mdgat_set_ragged_sinkhorn(mdgat_handle* h, int mode) {
     if (!h || mode < 0 || mode > 2) { mdgat_set_error("mdgat_set_ragged_sinkhorn: mode must be 0 (resident), 1 (automatic) or 2 (streaming)"); return -1; }
     const int prev = h->ragged_sinkhorn;
@@ -480,6 +490,8 @@ struct Path {
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
     int cnt_min;      // a ragged batch (FwdIn::counts): the smallest keypoint count of any frame; 0 otherwise
     Sk64Form sk64;    // the form of the fp64 Sinkhorn this call runs if it has the fp64 tail (sinkhorn_f64_form; a ragged batch: by mdgat_set_ragged_sinkhorn)
+    bool split32;     // a ragged batch on an MDGAT_ARITH_FP32 handle that opted in (mdgat_set_ragged_sinkhorn non-zero): the fp32 Sinkhorn's split form
+                      // wherever the slot has two slabs of rows or more (sinkhorn_plan decides), its scratch in the workspace
     LanePlan lanes;
 };
 
@@ -525,7 +537,8 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     }
     p.lanes = (taps || in.counts) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
     p.sk64 = f64 ? sinkhorn_f64_form(N, M, (bool)in.counts, h->ragged_sinkhorn) : Sk64Form::unsupported;
-    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.sk64).total;
+    p.split32 = in.counts && !f64 && h->cfg.arithmetic == MDGAT_ARITH_FP32 && h->ragged_sinkhorn != 0;
+    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.sk64, p.split32).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
     const int L2 = 2 * h->cfg.L;
@@ -847,6 +860,9 @@ static int tail32(Fwd& f, const FwdOut& o) {
     SkCall c{B, N, M, f.h->cfg.sinkhorn_iters, ws.scores, f.h->w.blob + f.h->w.bl.bin_score};
     c.Z = Zout; c.Zfb = Zroom; c.cnt0 = f.cnt0; c.cnt1 = f.cnt1;      // (Zfb: where redone pairs go when the cluster kernel writes no Z)
     c.ws = ws.sk; c.ws_bytes = ws.sk_bytes; c.slots_cleared = sk_clear != 0; c.status = f.status; c.ex = &ex; c.stream = f.s;
+    // (a ragged batch of a handle that opted in: the split form, each of its iterations a launch of the profile's Sinkhorn class)
+    c.split = f.p.split32; c.split_ws = ws.sksplit; c.split_ws_bytes = ws.sksplit_bytes;
+    c.launched = [](void* fwd) { static_cast<Fwd*>(fwd)->mark(MDGAT_PROF_SINKHORN); }; c.launched_ctx = &f;
     if (int rc = launch_sinkhorn(c)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
     return f.loss(o, static_cast<const float*>(Zout));
@@ -855,7 +871,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
 // one slice of a call (checked by plan_forward) on one lane
 static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
-    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.sk64);
+    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.sk64, p.split32);
     Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust,
           in.counts.cnt0, in.counts.cnt1, p.cnt_min};
     f.mark(-1);

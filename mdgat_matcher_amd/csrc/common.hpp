@@ -262,6 +262,9 @@ struct SkCall {
     void* ws; size_t ws_bytes;          // the cluster kernel's workspace; missing, short or not 256-byte aligned: the streaming kernel
     bool slots_cleared;                 // the first sinkhorn_slots_clear_bytes(B, N, M) bytes of ws are already zero on the stream (no memset launch)
     unsigned* status; const SkExtract* ex; hipStream_t stream;      // status: optional, a device pointer to MDGAT_STATUS_WORDS host-mapped words
+    bool split;                         // a ragged batch only: the split form (one launch per iteration, a pair's rows over several workgroups) where the slot has
+    void* split_ws; size_t split_ws_bytes;      // two slabs of 128 rows or more; then its scratch: 256-byte aligned, sinkhorn_split_workspace_bytes(B, N, M)
+    void (*launched)(void*); void* launched_ctx;      // optional: called behind every launch of the split form's iterations (the forward's profile marks)
 };
 int launch_sinkhorn(const SkCall& c);
 // What launch_sinkhorn chooses (mdgat_sinkhorn_plan, include/mdgat_hip.h: the table of indices), and how often each
@@ -285,11 +288,14 @@ struct SkPlan {
     int grid;           // workgroups of the (first) launch
     int cooperative;    // cluster: hipLaunchCooperativeKernel
     int rc;             // MDGAT_ERR_UNSUPPORTED where the launcher refuses (the message is the launcher's)
+    int split;          // a ragged batch on the split form: row slabs per pair (grid = B * split per launch, `stream` names the NC); 0: not that form
 };
 // workspace: sinkhorn_workspace_usable; fallback_buffer: a Z, or one lent for redone pairs; ragged: a call with counts
-SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged);
+// split: the caller opted in to the split form (a ragged batch only)
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split = false);
 void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]);
 size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M);      // the cluster kernel's workspace (its one layout: sinkhorn.hip); 0: the shape is beyond that kernel
+size_t sinkhorn_split_workspace_bytes(int B, int N, int M);        // the split form's scratch; 0: the slot has one slab of rows (or is beyond the ragged kernels)
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M);            // ... the prefix of it that is zero when a launch starts
 bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes);      // ... whether a buffer is large enough for it and 256-byte aligned
 

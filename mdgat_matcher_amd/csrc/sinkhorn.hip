@@ -1099,6 +1099,201 @@ __global__ __launch_bounds__(256) void extract_alldust_fixup(const int64_t* m0, 
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n1; i += (size_t)gridDim.x * 256) s1[i] = 0.f;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Split form of the log-domain kernel: a call with counts in slots of N x M <= 512 keypoints, a pair's rows cut into G = ceil(N / 128)
+// slabs (by the slot alone).  Workgroup (b, g) owns rows [128 g, 128 g + 128) of pair b below the pair's own count; iteration `it` is
+// ONE LAUNCH of B * G workgroups, so the stream's launch order is the only dependency between the workgroups of a pair: nobody waits,
+// polls or adds atomically.  The arithmetic per element is sinkhorn_kernel's.  Between launches a pair's state lives in scratch, indexed
+// by the parity of `it`: one (max, sum) column partial per slab, and the row potentials u with u_N behind the pair's last row.
+// A launch reads only what the launch before it wrote: v = 0 at it = 0 comes from no memory.
+constexpr int SK_SPLIT_ROWS = 128, SK_SPLIT_GMAX = 4, SK_SPLIT_NW = 16;
+struct SkSplitArgs {
+    const float* scores;      // [B][N][M]
+    const float* alpha_dev;
+    float alpha_host;
+    float* Z;                 // [B][N+1][M+1]
+    int N, M, iters;          // the slot (strides), the iterations of the call
+    const int* cnt0;
+    const int* cnt1;
+    float2* part;             // [B][2][G][M]: (max, sum) of a slab's column log-sum-exps, by parity of the iteration that wrote them
+    float* u;                 // [B][2][N+1]: the row potentials of an iteration, u_N at the pair's own count
+    int G, it;                // slabs per pair; the iteration this launch runs (the finishing launch: iters)
+};
+
+// The pair's potentials as iteration `it` starts, formed by a whole workgroup in LDS (every workgroup of a pair forms the same bits):
+// u[0 .. N] of iteration it - 1 from scratch, v[0 .. M - 1] as the merge, in ascending g, of the G column partials of iteration it - 1 with
+// the dustbin-row term - sinkhorn_kernel's merge of its per-wave partials; a slab without rows wrote (NEG_BIG, 0), which adds an exact 0
+// below the maximum - and v_M from that u.  it = 0: all zero.  Ends on a barrier.
+template <int NW>
+__device__ __forceinline__ void sk_split_potentials(const SkSplitArgs& a, int b, int it, int N, int M, float alpha, float lnu, float lnuM,
+                                                    float* u, float* v) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (it == 0) {
+        for (int i = tid; i <= N; i += NW * 64) u[i] = 0.f;
+        for (int j = tid; j <= M; j += NW * 64) v[j] = 0.f;
+        __syncthreads();
+        return;
+    }
+    const int prev = (it - 1) & 1;
+    const float* up = a.u + ((size_t)b * 2 + prev) * (a.N + 1);
+    const float2* pp = a.part + ((size_t)b * 2 + prev) * a.G * a.M;
+    for (int i = tid; i <= N; i += NW * 64) u[i] = up[i];
+    const float bN = alpha + up[N];      // dustbin-row term of every column
+    for (int j = tid; j < M; j += NW * 64) {
+        float2 p[SK_SPLIT_GMAX];
+#pragma unroll
+        for (int g = 0; g < SK_SPLIT_GMAX; ++g) p[g] = g < a.G ? pp[(size_t)g * a.M + j] : float2{NEG_BIG, 0.f};
+        float m = bN;
+#pragma unroll
+        for (int g = 0; g < SK_SPLIT_GMAX; ++g) m = fmaxf(m, p[g].x);
+        float e = ex2(bN - m);
+#pragma unroll
+        for (int g = 0; g < SK_SPLIT_GMAX; ++g) e += p[g].y * ex2(p[g].x - m);
+        v[j] = lnu - (m + lg2(e));
+    }
+    __syncthreads();
+    if (wave == 0) {
+        // dustbin column: v_M = log_nu_M - LSE_i(alpha + u_i), i = 0..N
+        const float lse = alpha + wave_lse2(u, N, u[N], lane);
+        if (lane == 0) v[M] = lnuM - lse;
+    }
+    __syncthreads();
+}
+
+template <int NC, int NW>
+__global__ __launch_bounds__(NW * 64) void sinkhorn_split_kernel(SkSplitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Ns = a.N, Ms = a.M;
+    const int b = blockIdx.x / a.G, g = blockIdx.x % a.G;
+    const int N = __builtin_amdgcn_readfirstlane(a.cnt0[b]), M = __builtin_amdgcn_readfirstlane(a.cnt1[b]);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int cur = a.it & 1;
+    float2* pout = a.part + (((size_t)b * 2 + cur) * a.G + g) * Ms;
+    const int r0 = g * SK_SPLIT_ROWS, r1 = min(r0 + SK_SPLIT_ROWS, N);
+    if (r0 >= N) {
+        // a slab beyond the pair's rows: the neutral partial.  The whole workgroup leaves here, in front of every barrier
+        for (int j = tid; j < M; j += NW * 64) pout[j] = float2{NEG_BIG, 0.f};
+        return;
+    }
+    const float* S = a.scores + (size_t)b * Ns * Ms;
+    float* ucur = a.u + ((size_t)b * 2 + cur) * (Ns + 1);
+
+    float* u = smem;                 // [N+1]: the previous iteration's
+    float* v = u + (N + 1);          // [M+1]
+    float* pm = v + (M + 1);         // [NW][M]
+    float* ps = pm + NW * M;         // [NW][M]
+
+    const float alpha = (a.alpha_dev ? *a.alpha_dev : a.alpha_host) * MDGAT_LOG2E;
+    const float norm = -logf((float)(N + M));                 // mdgat.py:301
+    const float lmu = norm * MDGAT_LOG2E;                     // rows 0..N-1 (302)
+    const float lmuN = (logf((float)M) + norm) * MDGAT_LOG2E; // dustbin row
+    const float lnu = lmu;                                    // cols 0..M-1 (303)
+    const float lnuM = (logf((float)N) + norm) * MDGAT_LOG2E; // dustbin column
+
+    sk_split_potentials<NW>(a, b, a.it, N, M, alpha, lnu, lnuM, u, v);
+
+    // column potentials of this lane's columns
+    float vr[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int j = c * 64 + lane;
+        vr[c] = j < M ? v[j] : 0.f;
+    }
+    const float bM = alpha + v[M];   // dustbin-column term of every row
+    if (g == 0 && wave == NW - 1) {
+        // dustbin row: u_N = log_mu_N - LSE_j(alpha + v_j), j = 0..M (every workgroup of the pair would form the same bits: slab 0 stores them)
+        const float lse = alpha + wave_lse2(v, M, v[M], lane);
+        if (lane == 0) ucur[N] = lmuN - lse;
+    }
+    float cm[NC], cs[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { cm[c] = NEG_BIG; cs[c] = 0.f; }
+
+    for (int i = r0 + wave; i < r1; i += NW) {
+        const float* row = S + (size_t)i * Ms;
+        float s[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int j = c * 64 + lane;
+            s[c] = j < M ? row[j] * MDGAT_LOG2E : NEG_BIG;
+        }
+        float m = bM;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) m = fmaxf(m, s[c] + vr[c]);
+        m = wave_max(m);
+        float e = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) e += ex2(s[c] + vr[c] - m);
+        e = wave_sum(e) + ex2(bM - m);
+        const float ui = lmu - (m + lg2(e));          // mdgat.py:283
+        if (lane == 0) ucur[i] = ui;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {                // fold into the column LSEs (mdgat.py:284)
+            const float w = s[c] + ui;
+            const float nm = fmaxf(cm[c], w);
+            cs[c] = cs[c] * ex2(cm[c] - nm) + ex2(w - nm);
+            cm[c] = nm;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int j = c * 64 + lane;
+        if (j < M) { pm[wave * M + j] = cm[c]; ps[wave * M + j] = cs[c]; }
+    }
+    __syncthreads();
+    // the slab's partial: the waves in ascending order (a wave without rows holds (NEG_BIG, 0); wave 0 always has a row)
+    for (int j = tid; j < M; j += NW * 64) {
+        float m = pm[j];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) m = fmaxf(m, pm[w * M + j]);
+        float e = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) e += ps[w * M + j] * ex2(pm[w * M + j] - m);
+        pout[j] = float2{m, e};
+    }
+}
+
+// The finishing launch: the last u (scratch) and v (formed as above), then Z = couplings + u + v - norm (mdgat.py:285, 307) in natural-log
+// units over the pair's own block, the dustbins at its own counts, 0 over the rest of the slot.  Workgroup (b, g) writes the rows
+// [128 g, 128 g + 128) of the slot's N + 1, the last one to the slot's end.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void sinkhorn_split_finish_kernel(SkSplitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int Ns = a.N, Ms = a.M;
+    const int b = blockIdx.x / a.G, g = blockIdx.x % a.G;
+    const int N = __builtin_amdgcn_readfirstlane(a.cnt0[b]), M = __builtin_amdgcn_readfirstlane(a.cnt1[b]);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float* S = a.scores + (size_t)b * Ns * Ms;
+    float* Z = a.Z + (size_t)b * (Ns + 1) * (Ms + 1);
+    float* u = smem;                 // [N+1]
+    float* v = u + (N + 1);          // [M+1]
+    const float alpha = (a.alpha_dev ? *a.alpha_dev : a.alpha_host) * MDGAT_LOG2E;
+    const float norm = -logf((float)(N + M));
+    const float lnu = norm * MDGAT_LOG2E;
+    const float lnuM = (logf((float)N) + norm) * MDGAT_LOG2E;
+    sk_split_potentials<NW>(a, b, a.iters, N, M, alpha, lnu, lnuM, u, v);
+    const float uN = u[N], vM = v[M];
+    const int r0 = g * SK_SPLIT_ROWS, r1 = g == a.G - 1 ? Ns + 1 : r0 + SK_SPLIT_ROWS;
+    for (int i = r0 + wave; i < r1; i += NW) {
+        float* zr = Z + (size_t)i * (Ms + 1);
+        if (i < N) {
+            const float ui = u[i];
+            const float* row = S + (size_t)i * Ms;
+            for (int j = lane; j < M; j += 64) zr[j] = (row[j] * MDGAT_LOG2E + ui + v[j]) * MDGAT_LN2 - norm;
+            if (lane == 0) zr[M] = (alpha + ui + vM) * MDGAT_LN2 - norm;
+            for (int j = M + 1 + lane; j <= Ms; j += 64) zr[j] = 0.f;
+        } else if (i == N) {
+            for (int j = lane; j <= M; j += 64) zr[j] = (alpha + uN + v[j]) * MDGAT_LN2 - norm;
+            for (int j = M + 1 + lane; j <= Ms; j += 64) zr[j] = 0.f;
+        } else {
+            for (int j = lane; j <= Ms; j += 64) zr[j] = 0.f;
+        }
+    }
+}
+
 template <int NC, int NW, bool RAGGED = false>
 int launch_sk(const SkArgs& a, int B, hipStream_t s) {
     const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)NW * a.M) * sizeof(float);
@@ -1146,6 +1341,25 @@ static SkLayout sk_layout(int B, int N, int M) {
     return l;
 }
 size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M) { return sk_layout(B, N, M).total; }
+
+// ---- the split form's scratch, stated once: byte offsets from its 256-byte aligned base; nothing in it is read before the call wrote it ----
+//   part    SkSplitArgs::part: per pair 2 * G * M (max, sum) granules
+//   u       SkSplitArgs::u: per pair 2 * (N + 1) floats
+struct SkSplitLayout {
+    int G;                       // slabs of 128 rows in a slot (0: the slot is beyond the ragged kernels)
+    size_t part, u, total;       // total 0: the split form does not apply (G < 2)
+    bool usable(const void* ws, size_t ws_bytes) const { return total && ws && ws_bytes >= total && (reinterpret_cast<uintptr_t>(ws) & 255) == 0; }
+};
+static SkSplitLayout sk_split_layout(int B, int N, int M) {
+    SkSplitLayout l{};
+    if (B <= 0 || N <= 0 || M <= 0 || N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return l;
+    l.G = (N + SK_SPLIT_ROWS - 1) / SK_SPLIT_ROWS;
+    if (l.G < 2) return l;
+    l.u = ((size_t)B * 2 * l.G * M * sizeof(float2) + 255) & ~(size_t)255;
+    l.total = l.u + (((size_t)B * 2 * (N + 1) * sizeof(float) + 255) & ~(size_t)255);
+    return l;
+}
+size_t sinkhorn_split_workspace_bytes(int B, int N, int M) { return sk_split_layout(B, N, M).total; }
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return sk_layout(B, N, M).clear_bytes; }
 bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes) { return sk_layout(B, N, M).usable(ws, ws_bytes); }
 
@@ -1156,8 +1370,8 @@ void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]) {
     for (int i = 0; i < SK_COUNTERS; ++i) counts[i] = sinkhorn_launch_count[i].load(std::memory_order_relaxed);
 }
 
-SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged) {
-    SkPlan p{SK_PATH_NONE, -1, -1, 0, 0, 0, 0, 0, 0, MDGAT_OK};
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split) {
+    SkPlan p{SK_PATH_NONE, -1, -1, 0, 0, 0, 0, 0, 0, MDGAT_OK, 0};
     if (B <= 0 || N <= 0 || M <= 0) return p;
     // the one-workgroup-per-pair streaming kernel: any shape up to M = 2048, no workspace
     const int nc = M <= 64 ? 0 : M <= 128 ? 1 : M <= 256 ? 2 : M <= 512 ? 3 : (M <= 1024 && N <= 4096) ? 4 : (M <= 2048 && N <= 4096) ? 5 : -1;
@@ -1167,6 +1381,9 @@ SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallb
         p.path = SK_PATH_STREAMING;
         p.stream = SK_RAGGED_1 + nc;
         p.grid = B;
+        // the split form where the caller opted in and the slot has more than one slab of rows: iters launches of B * G workgroups and a
+        // finishing one, in the slot's NC; a slot of one slab keeps the one-workgroup kernel
+        if (const int G = sk_split_layout(B, N, M).G; split && G >= 2) { p.split = G; p.grid = B * G; }
         return p;
     }
     if (!workspace || N > SK_CLUSTER_MAX || M > SK_CLUSTER_MAX) {
@@ -1315,8 +1532,36 @@ static int launch_scaling(const SkCall& c, const SkPlan& pl, const SkLayout& l) 
     return launch_extract_impl(x, *c.ex, s);
 }
 
+// the split form (SkPlan::split slabs per pair): one launch per iteration and the finishing one into Z, then extract_kernel on that Z
+template <int NC>
+static hipError_t launch_sk_split(const SkSplitArgs& a, int B, hipStream_t s, bool prepare) {
+    const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)SK_SPLIT_NW * a.M) * sizeof(float);
+    if (prepare) return hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_split_kernel<NC, SK_SPLIT_NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((sinkhorn_split_kernel<NC, SK_SPLIT_NW>), dim3(B * a.G), dim3(SK_SPLIT_NW * 64), lds, s, a);
+    return hipGetLastError();
+}
+static int launch_split(const SkCall& c, const SkPlan& pl) {
+    static hipError_t (*const launch[])(const SkSplitArgs&, int, hipStream_t, bool) = {launch_sk_split<1>, launch_sk_split<2>, launch_sk_split<4>, launch_sk_split<8>};
+    const SkSplitLayout l = sk_split_layout(c.B, c.N, c.M);
+    if (pl.stream < SK_RAGGED_1 || pl.stream > SK_RAGGED_8 || pl.split != l.G || pl.split > SK_SPLIT_GMAX) { mdgat_set_error("sinkhorn: no split form for slots of %d x %d", c.N, c.M); return MDGAT_ERR_UNSUPPORTED; }
+    if (!l.usable(c.split_ws, c.split_ws_bytes)) { mdgat_set_error("sinkhorn: the split form needs %zu bytes of 256-byte aligned scratch", l.total); return MDGAT_ERR_BAD_ARG; }
+    SkSplitArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z, c.N, c.M, c.iters, c.cnt0, c.cnt1};
+    a.part = reinterpret_cast<float2*>(static_cast<char*>(c.split_ws) + l.part); a.u = reinterpret_cast<float*>(static_cast<char*>(c.split_ws) + l.u); a.G = l.G;
+    const auto run = launch[pl.stream - SK_RAGGED_1];
+    if (int rc = mdgat_check_hip(run(a, c.B, c.stream, true), "sinkhorn LDS attribute")) return rc;
+    for (a.it = 0; a.it < c.iters; ++a.it) {
+        if (int rc = mdgat_check_hip(run(a, c.B, c.stream, false), "sinkhorn split launch")) return rc;
+        if (c.launched) c.launched(c.launched_ctx);
+    }
+    const size_t lds = ((size_t)(c.N + 1) + (c.M + 1)) * sizeof(float);
+    hipLaunchKernelGGL((sinkhorn_split_finish_kernel<SK_SPLIT_NW>), dim3(c.B * a.G), dim3(SK_SPLIT_NW * 64), lds, c.stream, a);
+    if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn split finishing launch")) return rc;
+    return c.ex ? launch_extract(c.B, c.N, c.M, c.Z, *c.ex, c.stream, c.cnt0, c.cnt1) : MDGAT_OK;
+}
+
 // On a usable workspace the cluster kernel; otherwise, and for every call with counts, the streaming kernel into Z - a ragged batch on the RAGGED instantiation
-// for its slot, picked from the padded sizes alone: a wider NC than a pair's own M would select gives the pair the same bits - then extract_kernel on that Z.
+// for its slot, picked from the padded sizes alone: a wider NC than a pair's own M would select gives the pair the same bits - or, where the caller opted in
+// (SkCall::split) and the slot has two slabs of rows or more, the split form - then extract_kernel on that Z.
 int launch_sinkhorn(const SkCall& c) {
     const int B = c.B, N = c.N, M = c.M;
     if (B <= 0) return MDGAT_OK;
@@ -1326,10 +1571,11 @@ int launch_sinkhorn(const SkCall& c) {
     if (N <= 0 || M <= 0 || c.iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, c.iters); return MDGAT_ERR_BAD_ARG; }
     const SkLayout l = sk_layout(B, N, M);
     const bool usable = !ragged && l.usable(c.ws, c.ws_bytes);      // (the cluster kernel takes no counts)
-    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, c.Z || c.Zfb, ragged);
+    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, c.Z || c.Zfb, ragged, ragged && c.split);
     if (usable) return launch_scaling(c, p, l);
     if (!c.Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
     if (ragged && p.rc) { mdgat_set_error("sinkhorn: ragged slots of %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS); return p.rc; }
+    if (p.split) return launch_split(c, p);
     SkArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z, N, M, c.iters};
     a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;
     if (int rc = launch_streaming(a, B, p.stream, false, c.stream)) return rc;

@@ -222,7 +222,17 @@ class MDGAT(nn.Module):
         self.ragged_sinkhorn = str(self.config.get('ragged_sinkhorn') or os.environ.get('MDGAT_RAGGED_SINKHORN') or 'resident')
         if self.ragged_sinkhorn not in ('resident', 'auto', 'streaming'):
             raise ValueError(f"ragged_sinkhorn={self.ragged_sinkhorn!r}: expected 'resident', 'auto' or 'streaming'")
-        f64_layers = self.config.get('f64_layers')
+        # not a reference key: which form of the fp32 Sinkhorn the fp32-class ragged forward runs (ragged_arithmetic 'auto' / 'module' on a
+        # module that is not exact(); include/mdgat_hip.h: mdgat_set_ragged_sinkhorn on an MDGAT_ARITH_FP32 handle).
+        #   'pair' (default): one workgroup per pair, all iterations in one launch;
+        #   'split': a pair's rows over ceil(Np / 128) workgroups, one launch per iteration, in slots of more than 128 rows (smaller slots run
+        #   'pair', the same bits).  Z agrees with 'pair' to fp32 rounding, not bit for bit; the limit of 512 and every refusal stay.
+        # An exact module ignores the key.  MDGAT_RAGGED_SINKHORN_FP32 in the environment replaces the default for modules whose config does
+        # not carry the key.
+        self.ragged_sinkhorn_fp32 = str(self.config.get('ragged_sinkhorn_fp32') or os.environ.get('MDGAT_RAGGED_SINKHORN_FP32') or 'pair')
+        if self.ragged_sinkhorn_fp32 not in ('pair', 'split'):
+            raise ValueError(f"ragged_sinkhorn_fp32={self.ragged_sinkhorn_fp32!r}: expected 'pair' or 'split'")
+        f64_layers =self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
         # the score matrix and the optimal transport in fp64, every arg-max of the extraction decided on the fp64 Z (csrc/sinkhorn_f64.hip).
@@ -237,6 +247,10 @@ class MDGAT(nn.Module):
             raise ValueError("arithmetic='fp64' and attention_dtype='f16' exclude each other")
         if self.descriptor == 'FPFH_gloabal' and self.attention_dtype != 'fp32':
             raise ValueError("descriptor='FPFH_gloabal' (its encoders run in fp64 on every path) and attention_dtype='f16' exclude each other")
+        if self.descriptor == 'FPFH_gloabal' and self.ragged_sinkhorn_fp32 == 'split' and self.arithmetic != 'fp64':
+            # (a module is float32 as it is made: only arithmetic='fp64' makes it exact here)
+            raise NotImplementedError("ragged_sinkhorn_fp32='split' and descriptor='FPFH_gloabal' exclude each other on an fp32-class module: its handle "
+                                      "computes the encoders in fp64 (MDGAT_ARITH_FP64), where mdgat_set_ragged_sinkhorn selects the fp64 Sinkhorn")
         if self.descriptor not in DESCRIPTORS:
             raise NotImplementedError(
                 f"descriptor={self.descriptor!r}: the FPFH encoders {DESCRIPTORS} are implemented on MI355X "
@@ -422,6 +436,10 @@ class MDGAT(nn.Module):
                     _lib.check(lib.mdgat_set_lanes(handle, self.lanes), 'mdgat_set_lanes')
                 if exact and self._ragged_wide():
                     if lib.mdgat_set_ragged_sinkhorn(handle, {'auto': 1, 'streaming': 2}[self.ragged_sinkhorn]) < 0:
+                        raise RuntimeError('mdgat_set_ragged_sinkhorn: ' + _lib.last_error())
+                if not f64 and getattr(self, 'ragged_sinkhorn_fp32', 'pair') == 'split':
+                    # an MDGAT_ARITH_FP32 handle: its ragged forwards run the split form of the fp32 Sinkhorn (no other call reads the mode)
+                    if lib.mdgat_set_ragged_sinkhorn(handle, 1) < 0:
                         raise RuntimeError('mdgat_set_ragged_sinkhorn: ' + _lib.last_error())
                 if blob_device_tensor is not None:
                     n = blob_device_tensor.numel()
@@ -785,7 +803,9 @@ class MDGAT(nn.Module):
         computed by the kernels that take per-pair counts: to fp32-class rounding of ``forward``, and bit-identical whatever the pair's
         position and companions as long as the slots are equal.  ``'module'`` instead of ``'auto'`` takes 'FPFH_gloabal' as well (inputs
         widened to float64 into ``mdgat_forward_f64_ragged`` on the module's handle: the encoders in fp64 with the frame maximum over a
-        pair's own keypoints, the same fp32-class kernels behind them) and opens the bank entries (``match_frames_ragged``)."""
+        pair's own keypoints, the same fp32-class kernels behind them) and opens the bank entries (``match_frames_ragged``).
+        ``config['ragged_sinkhorn_fp32'] = 'split'`` (or ``MDGAT_RAGGED_SINKHORN_FP32=split``) runs that forward's Sinkhorn with a pair's
+        rows over several workgroups, one launch per iteration, in slots of more than 128 rows: Z to fp32 rounding of the default form's."""
         if isinstance(pairs_or_packed, dict):
             return self._ragged_dicts(self._run_ragged(pairs_or_packed, return_Z), return_Z)
         pairs = list(pairs_or_packed)

@@ -18,6 +18,8 @@ The fp32-class legs, in the same run (a float32 module with config['ragged_arith
   (f32 a) 64 single-pair fp32-class ``forward`` calls; (f32 c) the uniform fp32-class batch of the slot size;
   (f32 d) one ``match_frames_ragged`` of the 64 out of the bank uploaded beforehand (the encoder kernel reads the records itself);
   (f32 d') the same with ``ops.pack_frames`` and the upload inside the clock;
+  (f32 b split) / (f32 d split) (f32 b) and (f32 d) on a module with config['ragged_sinkhorn_fp32'] = 'split': the split form of the fp32
+      Sinkhorn, one launch per iteration, a pair's rows over ceil(Np / 128) workgroups;
   (f32 gloabal) for the record, ``forward_ragged`` of the packed 64 on a float32 'FPFH_gloabal' module (its encoders in fp64).
 Device-synchronised host clock; the median of --windows windows and their spread (min .. max).
 
@@ -54,6 +56,7 @@ def main():
     ap.add_argument('--windows', type=int, default=7)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--profile', action='store_true', help='per-stage times of one ragged call (mdgat_profile)')
+    ap.add_argument('--split_only', action='store_true', help="only (f32 b), (f32 d) and their 'split' twins: the two forms of the fp32 Sinkhorn side by side")
     a = ap.parse_args()
     dev = 'cuda:0'
     if a.per_op:
@@ -71,6 +74,9 @@ def main():
     net32 = MDGAT({**cfg, 'ragged_arithmetic': 'module'})
     net32.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net32 = net32.float().eval().to(dev)
+    net32s = MDGAT({**cfg, 'ragged_arithmetic': 'module', 'ragged_sinkhorn_fp32': 'split'})
+    net32s.load_state_dict(synth.make_state_dict(L=L, seed=1))
+    net32s = net32s.float().eval().to(dev)
     net32g = MDGAT({**cfg, 'ragged_arithmetic': 'module', 'descriptor': 'FPFH_gloabal'})
     net32g.load_state_dict(synth.make_state_dict(L=L, seed=1, descriptor='FPFH_gloabal'))
     net32g = net32g.float().eval().to(dev)
@@ -114,9 +120,15 @@ def main():
             'f32_b_list_with_packing': lambda: net32.forward_ragged(pairs), 'f32_c_uniform_largest': lambda: net32(uniform),
             'f32_d_match_frames_ragged': lambda: net32.match_frames_ragged(bank, idx0, idx1),
             'f32_d_with_pack_frames': lambda: net32.match_frames_ragged(ops.pack_frames(frames, dev), idx0, idx1),
+            'f32_b_split_forward_ragged': lambda: net32s.forward_ragged(packed),
+            'f32_d_split_match_frames_ragged': lambda: net32s.match_frames_ragged(bank, idx0, idx1),
             'f32_gloabal_forward_ragged': lambda: net32g.forward_ragged(packed)}
     if not with_f32:
         legs = {k: v for k, v in legs.items() if not k.startswith('f32_')}
+    if a.split_only:
+        if not with_f32:
+            ap.error('--split_only: the fp32-class ragged forward holds 512 keypoints per frame')
+        legs = {k: legs[k] for k in ('f32_b_forward_ragged', 'f32_b_split_forward_ragged', 'f32_d_match_frames_ragged', 'f32_d_split_match_frames_ragged')}
     times = {k: [] for k in legs}
     with torch.no_grad():
         for fn in legs.values():
@@ -129,9 +141,13 @@ def main():
                 fn()
                 torch.cuda.synchronize()
                 times[name].append((time.perf_counter() - t0) * 1e3)
-        prof = prof_d = prof32 = prof32_d = None
+        prof = prof_d = prof32 = prof32_d = prof32s = None
         if a.profile:
             if with_f32:
+                net32s.profile(dev, True)
+                net32s.forward_ragged(packed)
+                torch.cuda.synchronize()
+                prof32s = {k: v for k, v in net32s.profile(dev, False).items() if v[1]}
                 net32.profile(dev, True)
                 net32.forward_ragged(packed)
                 torch.cuda.synchronize()
@@ -139,6 +155,7 @@ def main():
                 net32.match_frames_ragged(bank, idx0, idx1)
                 torch.cuda.synchronize()
                 prof32_d = {k: v for k, v in net32.profile(dev, False).items() if v[1]}
+        if a.profile and not a.split_only:
             net.profile(dev, True)
             run_b()
             torch.cuda.synchronize()
@@ -153,14 +170,25 @@ def main():
     lin = sum(n + m for n, m in counts) / (a.pairs * (Np + Mp))
     res = {'pairs': a.pairs, 'counts': [a.lo, a.hi], 'Np': Np, 'Mp': Mp, 'windows': a.windows, 'ragged_sinkhorn': a.ragged_sinkhorn,
            'ms_median': med, 'ms_min_max': {k: [float(min(v)), float(max(v))] for k, v in times.items()},
-           'ms_per_pair': {k: v / a.pairs for k, v in med.items()},
+           'ms_per_pair': {k: v / a.pairs for k, v in med.items()}}
+    if with_f32:
+        res['f32_split_over_pair'] = {'b': med['f32_b_split_forward_ragged'] / med['f32_b_forward_ragged'],
+                                      'd': med['f32_d_split_match_frames_ragged'] / med['f32_d_match_frames_ragged']}
+    if prof32s:
+        res['profile_ms_launches_f32_b_split'] = prof32s
+    if a.split_only:
+        if prof32:
+            res['profile_ms_launches_f32_b'] = prof32
+        print(json.dumps(res))
+        return
+    res.update({
            'ratio_a_over_b': med['a_single_pair_calls'] / med['b_forward_ragged'],
            'ratio_a_over_b_list': med['a_single_pair_calls'] / med['b_list_with_packing'],
            'work_ragged_over_uniform': {'quadratic': quad, 'linear': lin},
            'b_over_c': med['b_forward_ragged'] / med['c_uniform_largest'],
            'd_over_b': med['d_match_frames_ragged'] / med['b_forward_ragged'],
            'd_pack_over_b_list': med['d_with_pack_frames'] / med['b_list_with_packing'],
-           'pairs_per_s': {k: 1e3 * a.pairs / v for k, v in med.items()}}
+           'pairs_per_s': {k: 1e3 * a.pairs / v for k, v in med.items()}})
     if with_f32:
         res.update({'f32_ratio_a_over_b': med['f32_a_single_pair_calls'] / med['f32_b_forward_ragged'],
                     'f32_b_over_c': med['f32_b_forward_ragged'] / med['f32_c_uniform_largest'],
