@@ -503,6 +503,40 @@ void mdgat_layer_launches(uint64_t counts[MDGAT_LAYER_FORMS]);
  * mode > 0: 1; mode < 0: back to the default.  Process-wide; the results are bit-identical either way.  Returns the previous value. */
 int mdgat_set_f64_layer_fusion(int mode);
 
+/* Which kernel a layer tail or the encoder launch of the exact mode runs (csrc/layer_f64.hip: launch_layer_tail_f64, launch_encoder_f64),
+ * and with what grid.  The seven forms:
+ *    0 tail, three launches     gemm_f64_kernel three times: q | k | v, mlp.0, mlp.3 + residual (mode 0, or a handle without fragment images)
+ *    1 tail<1>                  layer_tail_f64_kernel<1>: one workgroup per 16 rows
+ *    2 tail<2>                  layer_tail_f64_kernel<2>: one workgroup per 32 rows
+ *    3 tail, clustered          layer_tail_f64_cluster_kernel: four workgroups per 16-row block, clusters in whole groups of eight
+ *    4 encoder<1>               encoder_f64_kernel<1>: 16 rows per workgroup
+ *    5 encoder<2>               encoder_f64_kernel<2>: 32 rows
+ *    6 encoder, seven launches  gemm_f64_kernel once per Conv1d of the two encoders (six, and layer 0's q | k | v)
+ * mdgat_layer_f64_plan: the form for a launch of R = B (N + M) keypoint rows; encoder != 0: the encoder launch, otherwise a layer tail;
+ * has_hid != 0: the tail has its [R][256] scratch (every tail of a forward has); chained != 0: the launch group is chained, which it is
+ * unless its stream is being captured into a graph; mode: as mdgat_set_f64_layer_fusion takes it, negative: the current setting; cus: the
+ * device's compute units, <= 0: those of the current device (the only argument that touches one).  32 rows per workgroup when
+ * ceil(R / 32) >= 2 cus or mode 32 forces them, 16 otherwise; a tail is clustered when mode is 1, has_hid, chained, and its nblk =
+ * ceil(R / 16) blocks satisfy 4 nblk <= cus and nblk <= 256.  *workgroups (optional): the grid - ceil(R / *rows_per_workgroup), or for the
+ * clustered form ceil(nblk / 8) * 32, of which 4 nblk find rows; *rows_per_workgroup (optional): 16 or 32.  Both 0 for forms 0 and 6
+ * (their grids are the product kernel's: mdgat_gemm_f64_plan) and with -1: nothing is launched (R <= 0).  The launchers take their
+ * branch and their grid from the same code.
+ * mdgat_layer_f64_launches: counts[i] = layer tails / encoders run in form i by this process so far, on any device and stream (relaxed
+ * atomic counters, incremented after a launch that succeeded - forms 0 and 6 once per tail / encoder, after the last of their products -
+ * never reset: read them before and after a call and subtract).  The pooled encoder (mdgat_load_pooled_encoder_f64) is none of them. */
+#define MDGAT_LAYER_F64_FORMS 7
+enum {
+    MDGAT_LAYER_F64_TAIL_GEMMS = 0,
+    MDGAT_LAYER_F64_TAIL_16 = 1,
+    MDGAT_LAYER_F64_TAIL_32 = 2,
+    MDGAT_LAYER_F64_TAIL_CLUSTER = 3,
+    MDGAT_LAYER_F64_ENCODER_16 = 4,
+    MDGAT_LAYER_F64_ENCODER_32 = 5,
+    MDGAT_LAYER_F64_ENCODER_GEMMS = 6
+};
+int mdgat_layer_f64_plan(int R, int encoder, int has_hid, int chained, int mode, int cus, int* workgroups, int* rows_per_workgroup);
+void mdgat_layer_f64_launches(uint64_t counts[MDGAT_LAYER_F64_FORMS]);
+
 /* MDGAT_ARITH_FP64: how full attention (models/mdgat.py:190-194) is launched.  -1 (default; MDGAT_F64_ATTENTION_FORM in the
  * environment selects another): by launch size - launches of at least four 128-query workgroups per compute unit (32 pairs of 512
  * keypoints) give every wave 32 queries and all the keys of the frame, smaller ones split the keys of a 16- / 32-query tile over

@@ -749,6 +749,7 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
         if (int rc = f.gemm64(w.im.enc(ENC_D0), in33, 33, nullptr, 0, 1, nullptr, hd1)) return rc;
         if (int rc = f.gemm64(w.im.enc(ENC_D1), hd1, 64, nullptr, 0, 1, nullptr, hd2)) return rc;
         if (int rc = f.gemm64(w.im.enc(ENC_L), hd2, 128, hk3, 128, 0, nullptr, ws.x64)) return rc;
+        layer_f64_count_unfused(1);
     }
     f.mark(MDGAT_PROF_F64_GEMM);
     if (int rc = f.tap(f.taps.x_enc, ws.x64, Rz * 128)) return rc;
@@ -770,6 +771,7 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
         } else {
             if (int rc = f.gemm64(w.im.layer(i, MAT_W1), ws.x64, 128, ws.msg64, 128, 1, nullptr, ws.hid64)) return rc;
             if (int rc = f.gemm64(w.im.layer(i, MAT_W2), ws.hid64, 256, nullptr, 0, 0, ws.x64, ws.x64)) return rc;
+            layer_f64_count_unfused(0);
         }
         f.mark(MDGAT_PROF_F64_GEMM);
         if (int rc = f.tap(f.x_tap(i), ws.x64, Rz * 128)) return rc;
@@ -1430,6 +1432,17 @@ extern "C" int mdgat_attention_f64_plan(int B, int N, int M, int topk, int tap, 
 
 extern "C" void mdgat_attention_f64_launches(uint64_t counts[7]) {
     if (counts) attention_f64_launch_counts(counts);
+}
+
+extern "C" int mdgat_layer_f64_plan(int R, int encoder, int has_hid, int chained, int mode, int cus, int* workgroups, int* rows_per_workgroup) {
+    const LayerF64Plan p = layer_f64_plan(R, encoder, has_hid, chained, mode, cus);
+    if (workgroups) *workgroups = p.workgroups;
+    if (rows_per_workgroup) *rows_per_workgroup = p.rows;
+    return p.form;
+}
+
+extern "C" void mdgat_layer_f64_launches(uint64_t counts[MDGAT_LAYER_F64_FORMS]) {
+    if (counts) layer_f64_launch_counts(counts);
 }
 
 // ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----

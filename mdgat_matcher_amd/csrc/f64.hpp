@@ -114,6 +114,17 @@ int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s);
 int launch_frag64(const double* W, double* out, int N, int K, hipStream_t s);
 inline size_t frag64_doubles(int N, int K) { return (size_t)N * ((K + 7) / 8) * 8; }      // ... and its size (where the images are: weights.hpp)
 bool layer_f64_fused();               // mdgat_set_f64_layer_fusion / MDGAT_F64_LAYER_FUSION
+// Which form a layer tail or the encoder launch takes and its grid (mdgat_layer_f64_plan, include/mdgat_hip.h: the table of forms and the
+// arguments), and how often each form has run in this process (mdgat_layer_f64_launches).  Host code only; the plan touches no HIP call
+// unless cus <= 0 asks for the current device's count.  The two launchers above decide by it.
+struct LayerF64Plan {
+    int form;           // MDGAT_LAYER_F64_*, or -1: no launch
+    int workgroups;     // the grid (0: the form is not a launch of layer_f64.hip)
+    int rows;           // per workgroup: 16 or 32 (0 likewise)
+};
+LayerF64Plan layer_f64_plan(int R, int encoder, int has_hid, int chained, int mode, int cus);
+void layer_f64_launch_counts(uint64_t counts[MDGAT_LAYER_F64_FORMS]);
+void layer_f64_count_unfused(int encoder);      // api.hip: a tail / the encoders done as one product per launch (forms 0 / 6)
 
 // ---- dw_f64.hip: dW = dY^T X [Cout][K0 + K1] and db = colsum(dY) [Cout] of a Conv1d(k=1) Y = X W^T + b, the rows cut into slabs ----
 struct DwF64Args {

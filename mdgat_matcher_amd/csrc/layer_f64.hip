@@ -562,59 +562,90 @@ extern "C" int mdgat_set_f64_layer_fusion(int mode) {
     return prev < 0 ? fusion_default() : prev;
 }
 
-int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group) {
-    if (a.R <= 0) return MDGAT_OK;
-    const hipStream_t s = group.stream();
+// ---- the launchers' choice as a pure function (mdgat_layer_f64_plan, include/mdgat_hip.h), and the launches counted by it ----
+static std::atomic<unsigned long long> layer_f64_launch_count[MDGAT_LAYER_F64_FORMS];
+constexpr int LC_MAX_CLUSTERS = 256;    // 16-row blocks the flag buffer holds
+
+void layer_f64_launch_counts(uint64_t counts[MDGAT_LAYER_F64_FORMS]) {
+    for (int i = 0; i < MDGAT_LAYER_F64_FORMS; ++i) counts[i] = layer_f64_launch_count[i].load(std::memory_order_relaxed);
+}
+void layer_f64_count_unfused(int encoder) {
+    layer_f64_launch_count[encoder ? MDGAT_LAYER_F64_ENCODER_GEMMS : MDGAT_LAYER_F64_TAIL_GEMMS].fetch_add(1, std::memory_order_relaxed);
+}
+
+LayerF64Plan layer_f64_plan(int R, int encoder, int has_hid, int chained, int mode, int cus) {
+    if (R <= 0) return LayerF64Plan{-1, 0, 0};
+    mode = mode < 0 ? fusion_mode() : (mode == 16 || mode == 32 || mode == 2) ? mode : (mode != 0);      // (as the setter reads it)
+    if (cus <= 0) cus = mdgat_cu_count();
+    if (mode == 0) return LayerF64Plan{encoder ? MDGAT_LAYER_F64_ENCODER_GEMMS : MDGAT_LAYER_F64_TAIL_GEMMS, 0, 0};
     // Rows per workgroup.  32 (two workgroups per CU, four waves per SIMD) from a round of the device on; 16 below - one pair of 512
     // keypoints is 64 workgroups instead of 32, and a workgroup's chain of products half as long (mdgat_set_f64_layer_fusion(16 | 32)
     // forces one).
-    int tm = (long)((a.R + 31) / 32) >= 2L * mdgat_cu_count() ? 32 : 16;
-    if (fusion_mode() >= 16) tm = fusion_mode();
+    int tm = (long)((R + 31) / 32) >= 2L * cus ? 32 : 16;
+    if (mode >= 16) tm = mode;
     // Launches of at most a quarter of the CUs in 16-row blocks (one pair of 512 keypoints: 64): four workgroups per block
     // (layer_tail_f64_cluster_kernel; bit-identical).  Not under graph capture (its flags count launches), not without the scratch,
     // not when a tile height is forced or mdgat_set_f64_layer_fusion(2) asks for the one-workgroup-per-block kernel.
-    const int nblk = (a.R + 15) / 16;
-    constexpr int max_clusters = 256;
-    if (fusion_mode() == 1 && a.hid && LC_RANKS * nblk <= mdgat_cu_count() && nblk <= max_clusters && group.chained()) {
+    const int nblk = (R + 15) / 16;
+    if (!encoder && mode == 1 && has_hid && (long)LC_RANKS * nblk <= cus && nblk <= LC_MAX_CLUSTERS && chained)
+        return LayerF64Plan{MDGAT_LAYER_F64_TAIL_CLUSTER, ((nblk + 7) / 8) * 32, 16};      // (clusters in whole groups of eight: the kernel's blockIdx map)
+    const int form = encoder ? (tm == 16 ? MDGAT_LAYER_F64_ENCODER_16 : MDGAT_LAYER_F64_ENCODER_32) : (tm == 16 ? MDGAT_LAYER_F64_TAIL_16 : MDGAT_LAYER_F64_TAIL_32);
+    return LayerF64Plan{form, (R + tm - 1) / tm, tm};
+}
+
+// (a caller that decided on the fused form gets it: a setter that raced to 0 since then concerns the next call)
+static int launcher_mode() { const int m = fusion_mode(); return m == 0 ? 2 : m; }
+
+int launch_layer_tail_f64(const LayerF64Args& a, CoopGroup& group) {
+    if (a.R <= 0) return MDGAT_OK;
+    const hipStream_t s = group.stream();
+    const LayerF64Plan p = layer_f64_plan(a.R, 0, a.hid != nullptr, group.chained(), launcher_mode(), mdgat_cu_count());
+    auto launched = [&](const char* what) -> int {
+        const int rc = mdgat_check_hip(hipGetLastError(), what);
+        if (!rc) layer_f64_launch_count[p.form].fetch_add(1, std::memory_order_relaxed);
+        return rc;
+    };
+    if (p.form == MDGAT_LAYER_F64_TAIL_CLUSTER) {
         CoopChain& ch = group.chain();
-        constexpr size_t flag_bytes = (size_t)max_clusters * LC_RANKS * LC_WORDS * sizeof(unsigned long long);
+        constexpr size_t flag_bytes = (size_t)LC_MAX_CLUSTERS * LC_RANKS * LC_WORDS * sizeof(unsigned long long);
         if (!ch.cluster_flags) {
-            void* p = nullptr;
-            if (int rc = mdgat_check_hip(hipMalloc(&p, flag_bytes), "layer_tail_f64 cluster flags")) return rc;
-            if (int rc = mdgat_check_hip(hipMemset(p, 0, flag_bytes), "layer_tail_f64 cluster flags (clear)")) { (void)hipFree(p); return rc; }
-            ch.cluster_flags = static_cast<unsigned long long*>(p);
+            void* fp = nullptr;
+            if (int rc = mdgat_check_hip(hipMalloc(&fp, flag_bytes), "layer_tail_f64 cluster flags")) return rc;
+            if (int rc = mdgat_check_hip(hipMemset(fp, 0, flag_bytes), "layer_tail_f64 cluster flags (clear)")) { (void)hipFree(fp); return rc; }
+            ch.cluster_flags = static_cast<unsigned long long*>(fp);
         }
         if (int rc = group.admit()) return rc;
         const size_t lds = (size_t)16 * LF_LD * sizeof(double);
-        hipLaunchKernelGGL(layer_tail_f64_cluster_kernel, dim3((unsigned)(((nblk + 7) / 8) * 32)), dim3(64 * LF_WAVES), lds, s, a, ch.cluster_flags, ++ch.epoch);
-        return mdgat_check_hip(hipGetLastError(), "layer_tail_f64 (clustered) launch");
+        hipLaunchKernelGGL(layer_tail_f64_cluster_kernel, dim3((unsigned)p.workgroups), dim3(64 * LF_WAVES), lds, s, a, ch.cluster_flags, ++ch.epoch);
+        return launched("layer_tail_f64 (clustered) launch");
     }
-    const size_t lds = (size_t)tm * LF_LD * sizeof(double);
-    const dim3 grid((a.R + tm - 1) / tm);
+    const size_t lds = (size_t)p.rows * LF_LD * sizeof(double);
+    const dim3 grid((unsigned)p.workgroups);
     auto go = [&](auto kern, auto tag) -> int {
         (void)tag;
         static std::atomic<unsigned long long> done{0};
         if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "layer_tail_f64 LDS")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(64 * LF_WAVES), lds, s, a);
-        return mdgat_check_hip(hipGetLastError(), "layer_tail_f64 launch");
+        return launched("layer_tail_f64 launch");
     };
-    if (tm == 16) return go(layer_tail_f64_kernel<1>, std::integral_constant<int, 1>());
+    if (p.form == MDGAT_LAYER_F64_TAIL_16) return go(layer_tail_f64_kernel<1>, std::integral_constant<int, 1>());
     return go(layer_tail_f64_kernel<2>, std::integral_constant<int, 2>());
 }
 
 int launch_encoder_f64(const EncoderF64Args& a, hipStream_t s) {
     if (a.R <= 0) return MDGAT_OK;
-    int tm = (long)((a.R + 31) / 32) >= 2L * mdgat_cu_count() ? 32 : 16;
-    if (fusion_mode() == 16 || fusion_mode() == 32) tm = fusion_mode();
-    const size_t lds = (size_t)tm * LF_LD * sizeof(double);
-    const dim3 grid((a.R + tm - 1) / tm);
+    const LayerF64Plan p = layer_f64_plan(a.R, 1, 0, 0, launcher_mode(), mdgat_cu_count());
+    const size_t lds = (size_t)p.rows * LF_LD * sizeof(double);
+    const dim3 grid((unsigned)p.workgroups);
     auto go = [&](auto kern, auto tag) -> int {
         (void)tag;
         static std::atomic<unsigned long long> done{0};
         if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), lds, done, "encoder_f64 LDS")) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(64 * LF_WAVES), lds, s, a);
-        return mdgat_check_hip(hipGetLastError(), "encoder_f64 launch");
+        const int rc = mdgat_check_hip(hipGetLastError(), "encoder_f64 launch");
+        if (!rc) layer_f64_launch_count[p.form].fetch_add(1, std::memory_order_relaxed);
+        return rc;
     };
-    if (tm == 16) return go(encoder_f64_kernel<1>, std::integral_constant<int, 1>());
+    if (p.form == MDGAT_LAYER_F64_ENCODER_16) return go(encoder_f64_kernel<1>, std::integral_constant<int, 1>());
     return go(encoder_f64_kernel<2>, std::integral_constant<int, 2>());
 }

@@ -20,6 +20,9 @@ from oracle import mdgat_oracle as O  # noqa: E402
 DEV = 'cuda:0'
 Z_TOL = 1e-4            # north star, literal
 F64_TOL = 1e-11         # the fp64 kernels against torch fp64 on the same operands (summation order only)
+# the stage bars of test_f64_stages_vs_reference (fp32 taps of fp64 values; Z behind the fp32-class tail); tests/test_gpu_layer_f64_forms.py
+# holds its cases to the same ones
+X_ENC_STAGE_TOL, X_LAYER_STAGE_TOL, Z_STAGE_TOL = 2e-6, 5e-6, 2e-5
 
 
 def _g(golden_dir, name):
@@ -315,17 +318,17 @@ def test_f64_stages_vs_reference(golden_dir, name):
     net.check(DEV)
     t = lambda x: np.transpose(x, (0, 2, 1))
     enc = taps['x_enc'].cpu().double().numpy()
-    assert max(np.abs(enc[:, :n] - t(g['enc0'])).max(), np.abs(enc[:, n:] - t(g['enc1'])).max()) < 2e-6
+    assert max(np.abs(enc[:, :n] - t(g['enc0'])).max(), np.abs(enc[:, n:] - t(g['enc1'])).max()) < X_ENC_STAGE_TOL
     xl = taps['x_layers'].cpu().double().numpy()
     for i in range(2 * L):
         e = max(np.abs(xl[i][:, :n] - t(g[f'layer{i}_desc0'])).max(), np.abs(xl[i][:, n:] - t(g[f'layer{i}_desc1'])).max())
-        assert e < 5e-6, (i, e)
+        assert e < X_LAYER_STAGE_TOL, (i, e)
     # final_proj and the score matrix: the fp32-class tail behind the fp64 layers (the projection-only final_proj launch of
     # csrc/layer.hip), at the bars of tests/test_gpu_forward.py::test_forward_stages_golden
     md = taps['mdesc'].cpu().double().numpy()
     assert max(np.abs(md[:, :n] - t(g['mdesc0'])).max(), np.abs(md[:, n:] - t(g['mdesc1'])).max()) < 5e-5
     assert np.abs(taps['scores'].cpu().double().numpy() - g['scores']).max() < Z_TOL
-    assert np.abs(Z.cpu().double().numpy() - g['Z']).max() < 2e-5
+    assert np.abs(Z.cpu().double().numpy() - g['Z']).max() < Z_STAGE_TOL
     np.testing.assert_array_equal(m0.cpu().numpy(), g['default_matches0'])
     np.testing.assert_array_equal(m1.cpu().numpy(), g['default_matches1'])
     assert np.abs(s0.cpu().double().numpy() - g['default_mscores0']).max() < 2e-5
@@ -492,12 +495,16 @@ def test_f64_tail_applies_the_batch_wide_dustbin_rule(B):
     assert out['matching_scores0'].dtype == torch.int64 and (out['matching_scores0'] == 0).all() and (out['matching_scores1'] == 0).all()
 
 
-@pytest.mark.parametrize('B,n', [(3, 300), (2, 600), (40, 512)])
+@pytest.mark.parametrize('B,n', [(3, 300), (2, 600), (40, 512), (1, 256)])
 def test_exact_mode_forward_is_capturable_as_a_hip_graph(B, n):
     """The exact mode under stream capture (torch.cuda.CUDAGraph = hipGraph): the register-resident fp64 Sinkhorn (300 keypoints; its
     launcher's one-launch-at-a-time chaining stands aside for a capturing stream) and the streaming form (600 keypoints: 2 S + 3
     launches, nothing waits inside a launch); 40 pairs of 512: two lanes, a resident Sinkhorn launch on each, side by side in the graph.
-    The replay gives the bits of the eager call, also after the inputs changed in place."""
+    The replay gives the bits of the eager call, also after the inputs changed in place.
+    One pair of 256 + 249 keypoints: 32 blocks of 16 rows, which the layer tails run CLUSTERED when called eagerly (csrc/layer_f64.hip: four
+    workgroups per block that wait for each other on flags carrying the launch's number) - a replay would meet those flags already set, so
+    under capture the launcher must fall back to one workgroup per block: the counters show it did, in every case."""
+    import layer_f64_forms as LF
     cfg = synth.default_config(L=2, k=[64, None, 32, None], sinkhorn_iterations=12)
     net = MDGAT(cfg).double()
     net.load_state_dict(synth.make_state_dict(L=2, seed=5))
@@ -507,8 +514,15 @@ def test_exact_mode_forward_is_capturable_as_a_hip_graph(B, n):
     d = synth.make_batch(B, n, n - 7, device=DEV, dtype=torch.float64)
     other = synth.make_batch(B, n, n - 7, first_pair=300, device=DEV, dtype=torch.float64)
     inputs = tuple(d[k] for k in keys)
+    R, cus, tails = B * (2 * n - 7), LF.cu_count(), 4          # (the fp64 tail: all 2 L layers in fp64)
+    small = B == 1                                              # (one unsliced launch of R rows per tail)
+    if small and LF.plan(R, cus=cus)[0] != LF.CLUSTER:
+        pytest.skip(f'{R} rows are not clustered on a device of {cus} compute units')
     with torch.no_grad():
-        eager = [t.clone() for t in net._run(*inputs, want_Z=True)]
+        with LF.watch() as w_eager:
+            eager = [t.clone() for t in net._run(*inputs, want_Z=True)]
+        if small:
+            assert w_eager.launched() == {LF.ENC16: 1, LF.CLUSTER: tails}, LF.named(w_eager.launched())
         eager_other = [t.clone() for t in net._run(*(other[k] for k in keys), want_Z=True)]
         side = torch.cuda.Stream(DEV)
         side.wait_stream(torch.cuda.current_stream(DEV))
@@ -517,8 +531,13 @@ def test_exact_mode_forward_is_capturable_as_a_hip_graph(B, n):
         torch.cuda.current_stream(DEV).wait_stream(side)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = net._run(*inputs, want_Z=True)
+        with LF.watch() as w_capture:
+            with torch.cuda.graph(graph):
+                out = net._run(*inputs, want_Z=True)
+        assert LF.CLUSTER not in w_capture.launched() and w_capture.delta.sum() > 0, LF.named(w_capture.launched())
+        if small:
+            assert LF.plan(R, chained=False, cus=cus)[0] == LF.TAIL16
+            assert w_capture.launched() == {LF.ENC16: 1, LF.TAIL16: tails}, LF.named(w_capture.launched())
         graph.replay()
         torch.cuda.synchronize()
         assert all(torch.equal(a, b) for a, b in zip(eager, out))
@@ -639,9 +658,15 @@ def test_f64_fused_layer_tail_equals_three_launches(B, n, m, L, k):
     encoders, their sum, layer 0's q | k | v) against the seven it replaces: every accumulator walks k in the same order, so EVERY
     output bit is the same - matches, scores, Z, and the fp32 taps of the encoder output and of every layer's descriptors - for each
     tile height (16 / 32 keypoints per workgroup), ragged keypoint counts, one pair, a batch large enough to run in slices, and
-    a network without a dynamic layer (encoders only in fp64: the encoder launch hands over)."""
+    a network without a dynamic layer.  The launch counters (mdgat_layer_f64_launches) say which form ran: every run only forms its mode
+    allows, the tapped (unsliced) runs exactly the planned ones - under mode 1 the clustered kernel at the four shapes of at most 64
+    blocks of 16 rows.  One case per form and edge of a form: tests/test_gpu_layer_f64_forms.py."""
+    import layer_f64_forms as LF
     from mdgat_matcher_amd import _lib
     lib = _lib.load()
+    cus, R = LF.cu_count(), B * (n + m)
+    allowed = {0: {LF.TAIL_GEMMS, LF.ENC_GEMMS}, 1: {LF.TAIL16, LF.TAIL32, LF.CLUSTER, LF.ENC16, LF.ENC32}, 2: {LF.TAIL16, LF.TAIL32, LF.ENC16, LF.ENC32},
+               16: {LF.TAIL16, LF.ENC16}, 32: {LF.TAIL32, LF.ENC32}}
     cfg = synth.default_config(L=L, k=k, sinkhorn_iterations=10)
     net = MDGAT(cfg).double()
     net.load_state_dict(synth.make_state_dict(L=L, seed=21))
@@ -654,9 +679,17 @@ def test_f64_fused_layer_tail_equals_three_launches(B, n, m, L, k):
         prev = lib.mdgat_set_f64_layer_fusion(mode)
         try:
             t = {'x_layers': torch.zeros(2 * L, B, P, 128, device=DEV), 'x_enc': torch.zeros(B, P, 128, device=DEV)} if taps else None
-            out = net._run(d['keypoints0'], d['scores0'], d['descriptors0'], d['keypoints1'], d['scores1'], d['descriptors1'], want_Z=True, taps=t)
-            torch.cuda.synchronize()
+            with LF.watch() as w:
+                out = net._run(d['keypoints0'], d['scores0'], d['descriptors0'], d['keypoints1'], d['scores1'], d['descriptors1'], want_Z=True, taps=t)
+                torch.cuda.synchronize()
             net.check(DEV)
+            ran = w.launched()
+            assert ran and set(ran) <= allowed[mode], (mode, taps, LF.named(ran))
+            if taps:        # one launch of all R rows per stage: the encoders, then 2 L tails (the fp64 tail: every layer in fp64)
+                want = {LF.plan(R, True, mode=mode, cus=cus)[0]: 1, LF.plan(R, mode=mode, cus=cus)[0]: 2 * L}
+                assert ran == want, (mode, LF.named(ran), LF.named(want))
+                if mode == 1 and R <= 1024 and cus >= 256:
+                    assert ran.get(LF.CLUSTER) == 2 * L, LF.named(ran)
             return out, t
         finally:
             lib.mdgat_set_f64_layer_fusion(-1)

@@ -35,9 +35,9 @@ REDONE = {'fp32': 0, 'fp32-wide': 1, 'exact': 0}           # what ``check`` repo
 
 # The exact module's shapes are here for a form of the fp64 kernels: (3, 61, 66) and (1, 512, 512) the clustered layer tail and the
 # register-resident Sinkhorn, (20, 128, 128) the tail with one workgroup per block, (1, 600, 577) the streaming Sinkhorn.  The Sinkhorn's
-# form is asserted (``_assert_sinkhorn_form``); the layer tail's has no plan helper and no launch counter in the ABI - its clustered form
-# is chosen from the launch size (at most a quarter of the compute units in 16-keypoint blocks: include/mdgat_hip.h,
-# mdgat_set_f64_layer_fusion) - and stays a statement of intent.
+# form is asserted (``_assert_sinkhorn_form``); the layer tail's - clustered for launches of at most a quarter of the compute units in
+# 16-keypoint blocks (include/mdgat_hip.h: mdgat_layer_f64_plan) - is asserted by its launch counters where it is the subject, in
+# tests/test_gpu_layer_f64_forms.py, and stays a statement of intent here.
 STREAMING_F64 = {(3, 61, 66): False, (1, 512, 512): False, (20, 128, 128): False, (1, 600, 577): True}
 FIRST = {'fp32': [(3, 61, 66), (9, 48, 64), (2, 128, 256), (1, 512, 512)], 'fp32-wide': [(3, 61, 66), (9, 48, 64), (2, 128, 256), (1, 512, 512)],
          'exact': [(3, 61, 66), (1, 512, 512), (20, 128, 128), (1, 600, 577)]}
