@@ -651,6 +651,43 @@ int mdgat_sinkhorn_f64_extract_stream_ragged(int B, int Np, int Mp, const int32_
                                              float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
                                              float* Z_or_null, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Which kernels a call of the fp64 Sinkhorn runs (csrc/sinkhorn_f64.hip: launch_sinkhorn_f64, which the six entries above and the
+ * exact mode's forward go through, and sinkhorn_f64_stream_history, the forward pass of mdgat_sinkhorn_backward).  The eleven forms:
+ *    0 resident                   sinkhorn_f64_kernel<8, false>: one launch, the couplings in registers (N <= 576, M <= 575)
+ *    1 resident, ragged           sinkhorn_f64_kernel<8, true>: the same with per-pair counts (slots <= 575 x 575)
+ *    2, 3, 4 streaming            sinkhorn_f64_wide_iter_kernel / _final_kernel<NC2, false>, NC2 = 5, 9, 17: one launch per iteration and
+ *                                 a last one; NC2 column pairs per lane hold ceil((M + 1) / 128) = 1 .. 5, 6 .. 9, 10 .. 17 chunks of 128
+ *                                 columns (M <= 639, 1151, 2175; N <= 2175)
+ *    5, 6, 7 streaming, ragged    the <NC2, true> instantiations, NC2 from the SLOT's chunk count whatever the pairs' own
+ *    8, 9, 10 history             the <NC2, false> iteration launches with the potential history written and no last launch (the backward)
+ * mdgat_sinkhorn_f64_plan: the form a call in slots of N x M keypoints runs.  ragged != 0: a call with counts, following ragged_mode as
+ * mdgat_set_ragged_sinkhorn takes it (the ragged entries above run mode 0, the stream_ragged ones mode 2); form: -1 or 1 as
+ * mdgat_set_f64_sinkhorn_form takes them, any other value: the current setting; history != 0: the backward's history run (a uniform
+ * call; it streams at every size, whatever `form`).  *slabs (optional): the row slabs of 32 rows, ceil(N / 32); *chunks (optional): the
+ * chunks of 128 columns that hold M + 1 columns, (M + 1 + 127) >> 7, for the streaming forms, 0 for the resident ones.  Negative, with
+ * both 0: no form holds the call (N or M beyond 2175 or below 1; a ragged call under mode 0 beyond 575 or under form 1), or history
+ * with ragged.  A pure function of its arguments and that setting: no device is needed or touched; the launchers take their branch from
+ * the same code.
+ * mdgat_sinkhorn_f64_launches: counts[i] = calls run in form i by this process so far, on any device and stream (relaxed atomic
+ * counters, incremented once per call after its last launch succeeded - the column merge where arg-maxes are asked for, not the match
+ * extraction behind it - never reset: read them before and after a call and subtract). */
+#define MDGAT_SINKHORN_F64_FORMS 11
+enum {
+    MDGAT_SINKHORN_F64_RESIDENT = 0,
+    MDGAT_SINKHORN_F64_RESIDENT_RAGGED = 1,
+    MDGAT_SINKHORN_F64_STREAM_5 = 2,
+    MDGAT_SINKHORN_F64_STREAM_9 = 3,
+    MDGAT_SINKHORN_F64_STREAM_17 = 4,
+    MDGAT_SINKHORN_F64_STREAM_RAGGED_5 = 5,
+    MDGAT_SINKHORN_F64_STREAM_RAGGED_9 = 6,
+    MDGAT_SINKHORN_F64_STREAM_RAGGED_17 = 7,
+    MDGAT_SINKHORN_F64_HISTORY_5 = 8,
+    MDGAT_SINKHORN_F64_HISTORY_9 = 9,
+    MDGAT_SINKHORN_F64_HISTORY_17 = 10
+};
+int mdgat_sinkhorn_f64_plan(int N, int M, int ragged, int ragged_mode, int form, int history, int* slabs, int* chunks);
+void mdgat_sinkhorn_f64_launches(uint64_t counts[MDGAT_SINKHORN_F64_FORMS]);
+
 /* RAGGED batches in fp32: mdgat_sinkhorn / mdgat_sinkhorn_extract on pairs of different sizes, laid out as above with fp32 scores and Z.
  * They run the one-workgroup-per-pair streaming kernel (the cluster kernel takes no counts), whose ragged instantiation is picked from the
  * padded sizes alone: pair b's block of Z, its matches and its scores are those of the pair run alone through the uniform entry WITHOUT a

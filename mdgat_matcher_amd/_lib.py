@@ -202,6 +202,8 @@ SIGNATURES = {
     'mdgat_attention_f64_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_layer_f64_plan': (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2),
     'mdgat_layer_f64_launches': (None, [C.POINTER(C.c_uint64)]),
+    'mdgat_sinkhorn_f64_plan': (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2),
+    'mdgat_sinkhorn_f64_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_attention_f64': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'mdgat_attention_f64_ragged': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
     'mdgat_attention_backward_f64': (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),

@@ -1445,6 +1445,14 @@ extern "C" void mdgat_layer_f64_launches(uint64_t counts[MDGAT_LAYER_F64_FORMS])
     if (counts) layer_f64_launch_counts(counts);
 }
 
+extern "C" int mdgat_sinkhorn_f64_plan(int N, int M, int ragged, int ragged_mode, int form, int history, int* slabs, int* chunks) {
+    return sinkhorn_f64_plan(N, M, ragged, ragged_mode, form, history, slabs, chunks);
+}
+
+extern "C" void mdgat_sinkhorn_f64_launches(uint64_t counts[MDGAT_SINKHORN_F64_FORMS]) {
+    if (counts) sinkhorn_f64_launches(counts);
+}
+
 // ---- the matching head (final_proj, the score matrix) and its backward: csrc/head_grad.hip ----
 // the shape and buffer checks of the gradient entries (this section and the two below)
 // nmax: keypoints per frame; rows: the rows the largest array of a pair holds

@@ -672,12 +672,14 @@ extern "C" int mdgat_set_f64_sinkhorn_form(int mode) {
 
 // (the resident kernel holds 576 rows and 575 columns; the ragged entries document and take one limit for both frames)
 static_assert(MDGAT_RAGGED_MAX_KEYPOINTS == 64 * S64_NC - 1 && MDGAT_RAGGED_MAX_KEYPOINTS <= 32 * S64_GMAX, "the ragged limit is the resident kernel's");
-Sk64Form sinkhorn_f64_form(int N, int M, bool ragged, int ragged_mode) {
-    const bool resident = s64_resident_supported(N, M) && (!ragged || N <= MDGAT_RAGGED_MAX_KEYPOINTS) && s64_form() != 1;
+// (forced: the mdgat_set_f64_sinkhorn_form value the decision is made under - the current one for every launch, any for the plan)
+static Sk64Form s64_form_under(int N, int M, bool ragged, int ragged_mode, int forced) {
+    const bool resident = s64_resident_supported(N, M) && (!ragged || N <= MDGAT_RAGGED_MAX_KEYPOINTS) && forced != 1;
     if (resident && !(ragged && ragged_mode == 2)) return Sk64Form::resident;
     if (s64_wide_supported(N, M) && !(ragged && ragged_mode == 0)) return Sk64Form::streaming;
     return Sk64Form::unsupported;
 }
+Sk64Form sinkhorn_f64_form(int N, int M, bool ragged, int ragged_mode) { return s64_form_under(N, M, ragged, ragged_mode, s64_form()); }
 
 // both forms' row slabs, and the streaming form's row length: whole 128-column chunks that hold the dustbin column
 static size_t s64_slabs(size_t N) { return (N + W64_ROWS - 1) / W64_ROWS; }
@@ -720,6 +722,35 @@ Sk64Bests sinkhorn_f64_bests(void* base, int B, int N, int M) {
     c.take(b.ci, (size_t)B * M); c.take(b.cv, (size_t)B * M);
     b.bytes = c.bytes;
     return b;
+}
+
+// ---- which of the eleven forms a call runs (mdgat_sinkhorn_f64_plan, include/mdgat_hip.h: the table), and the calls counted by it ----
+// The streaming form's register budget, NC2 column pairs per lane, as a bucket 0 / 1 / 2 for <5> / <9> / <17>: s64_wide_dispatch takes
+// its instantiation from it, the plan its index.  (The budget follows the SLOT: a pair's own chunk count only bounds what its lanes load.)
+static int s64_wide_bucket(int Mp) {
+    const int nc2 = Mp >> 7;
+    return nc2 <= 5 ? 0 : nc2 <= 9 ? 1 : 2;
+}
+static int s64_streaming_index(int Mp, bool ragged, bool history) {
+    return (history ? MDGAT_SINKHORN_F64_HISTORY_5 : ragged ? MDGAT_SINKHORN_F64_STREAM_RAGGED_5 : MDGAT_SINKHORN_F64_STREAM_5) + s64_wide_bucket(Mp);
+}
+static std::atomic<uint64_t> g_s64_calls[MDGAT_SINKHORN_F64_FORMS];
+static void s64_count(int index) { g_s64_calls[index].fetch_add(1, std::memory_order_relaxed); }
+
+int sinkhorn_f64_plan(int N, int M, int ragged, int ragged_mode, int form, int history, int* slabs, int* chunks) {
+    if (slabs) *slabs = 0;
+    if (chunks) *chunks = 0;
+    if (history && ragged) return -1;                // (sinkhorn_f64_stream_history takes a uniform call)
+    const Sk64Form f = s64_form_under(N, M, ragged != 0, ragged_mode, form == 1 || form == -1 ? form : s64_form());
+    if (f == Sk64Form::unsupported) return -1;
+    if (slabs) *slabs = (int)s64_slabs((size_t)N);
+    if (!history && f == Sk64Form::resident) return ragged ? MDGAT_SINKHORN_F64_RESIDENT_RAGGED : MDGAT_SINKHORN_F64_RESIDENT;
+    const int Mp = (int)s64_padded_columns((size_t)M);
+    if (chunks) *chunks = Mp >> 7;
+    return s64_streaming_index(Mp, ragged != 0, history != 0);
+}
+void sinkhorn_f64_launches(uint64_t counts[MDGAT_SINKHORN_F64_FORMS]) {
+    for (int i = 0; i < MDGAT_SINKHORN_F64_FORMS; ++i) counts[i] = g_s64_calls[i].load(std::memory_order_relaxed);
 }
 
 // ---- what the two forms' launches share ----
@@ -771,11 +802,11 @@ static int s64_wide_launches(const Wk64Args& a0, hipStream_t s, bool final) {
     if (final) hipLaunchKernelGGL((sinkhorn_f64_wide_final_kernel<NC2, RAGGED>), dim3((unsigned)(a.B * a.G)), dim3(512), lds_fin, s, a);
     return mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 (streaming) launch");
 }
-// (the register budget NC2 follows the SLOT: a pair's own chunk count only bounds what its lanes load)
+// (the instantiation: s64_wide_bucket of the slot)
 template <bool RAGGED>
 static int s64_wide_dispatch(const Wk64Args& a, hipStream_t s, bool final) {
-    const int nc2 = a.Mp >> 7;
-    return nc2 <= 5 ? s64_wide_launches<5, RAGGED>(a, s, final) : nc2 <= 9 ? s64_wide_launches<9, RAGGED>(a, s, final) : s64_wide_launches<W64_NC2MAX, RAGGED>(a, s, final);
+    const int bucket = s64_wide_bucket(a.Mp);
+    return bucket == 0 ? s64_wide_launches<5, RAGGED>(a, s, final) : bucket == 1 ? s64_wide_launches<9, RAGGED>(a, s, final) : s64_wide_launches<W64_NC2MAX, RAGGED>(a, s, final);
 }
 
 static int s64_launch_streaming(const Sk64Call& c, void* workspace, hipStream_t s) {
@@ -783,7 +814,9 @@ static int s64_launch_streaming(const Sk64Call& c, void* workspace, hipStream_t 
     const Wk64Args a = s64_wide_args(c, w);
     if (c.cnt0) if (int rc = s64_zero_Z(c, s)) return rc;
     if (int rc = c.cnt0 ? s64_wide_dispatch<true>(a, s, true) : s64_wide_dispatch<false>(a, s, true)) return rc;
-    return s64_merge_columns(c, w.sidx, w.sval, w.G, s);
+    if (int rc = s64_merge_columns(c, w.sidx, w.sval, w.G, s)) return rc;
+    s64_count(s64_streaming_index(w.Mp, c.cnt0 != nullptr, false));
+    return MDGAT_OK;
 }
 
 Sk64Stream sinkhorn_f64_stream_carve(void* base, int B, int N, int M) {
@@ -799,7 +832,9 @@ int sinkhorn_f64_stream_history(const Sk64Call& c, double* hist_a, int hist_lda,
     }
     Wk64Args a = s64_wide_args(c, s64_wide_carve(workspace, c.B, c.N, c.M));
     a.hist_a = hist_a; a.hist_b = hist_b; a.hist_lda = hist_lda;
-    return s64_wide_dispatch<false>(a, s, false);
+    if (int rc = s64_wide_dispatch<false>(a, s, false)) return rc;
+    s64_count(s64_streaming_index(a.Mp, false, true));
+    return MDGAT_OK;
 }
 
 // ---- the register-resident form's launch ----
@@ -838,7 +873,9 @@ static int s64_launch_resident(const Sk64Call& c, void* workspace, hipStream_t s
         hipLaunchKernelGGL((sinkhorn_f64_kernel<8, false>), dim3(groups * 8 * G), dim3(512), lds, s, a);
     }
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn_f64 launch")) return rc;
-    return s64_merge_columns(c, w.sidx, w.sval, G, s);
+    if (int rc = s64_merge_columns(c, w.sidx, w.sval, G, s)) return rc;
+    s64_count(c.cnt0 ? MDGAT_SINKHORN_F64_RESIDENT_RAGGED : MDGAT_SINKHORN_F64_RESIDENT);
+    return MDGAT_OK;
 }
 
 // The form is the caller's decision; what is checked here is that sinkhorn_f64_form gives it to a call like this one under some ragged

@@ -35,6 +35,11 @@ struct Sk64Call {
 enum class Sk64Form { unsupported, resident, streaming };
 Sk64Form sinkhorn_f64_form(int N, int M, bool ragged, int ragged_mode);
 inline bool sinkhorn_f64_supported(int N, int M) { return sinkhorn_f64_form(N, M, false, 0) != Sk64Form::unsupported; }
+// Which of the eleven forms a call runs - the two above with and without counts, the streaming one by its instantiation <5 | 9 | 17>, and
+// the history run below (mdgat_sinkhorn_f64_plan, include/mdgat_hip.h: the table and the arguments) - from the code the launchers
+// branch on, and how many calls have run in each in this process (mdgat_sinkhorn_f64_launches).  Host code only; no HIP call.
+int sinkhorn_f64_plan(int N, int M, int ragged, int ragged_mode, int form, int history, int* slabs, int* chunks);
+void sinkhorn_f64_launches(uint64_t counts[MDGAT_SINKHORN_F64_FORMS]);
 // the form's workspace, carved by the padded sizes (streaming: K is [B][N][Mp], 35.6 MB per pair at 2048); 0 for Sk64Form::unsupported
 size_t sinkhorn_f64_workspace_bytes(int B, int N, int M, Sk64Form form);
 

@@ -13,6 +13,7 @@ import math
 import numpy as np
 import torch
 
+import sinkhorn_f64_forms
 from oracle import mdgat_oracle as O
 
 MODES = {0: ('triplet_loss', False), 1: ('triplet_loss', True), 2: ('superglue', False), 3: ('superglue', True)}    # mdgat_extract_mode
@@ -167,14 +168,10 @@ def streaming_kernel(N, M):
 
 def f64_kernel(N, M, form: int = -1):
     """csrc/sinkhorn_f64.hip sinkhorn_f64_form (a uniform call) and the streaming form's NC2: ('resident', row slabs of 32) or ('streaming', NC2, slabs)."""
-    resident = N >= 1 and M >= 1 and M + 1 <= 576 and N <= 576
-    wide_ok = N >= 1 and M >= 1 and M + 1 <= 2176 and N + 1 <= 2176
-    if not resident and not wide_ok:
+    index, slabs, _ = sinkhorn_f64_forms.decide(N, M, form=form)      # (the one restatement of the decision, counts and history included)
+    if index < 0:
         return None
-    if not resident or form == 1:
-        nc2 = ((M + 1 + 127) & ~127) >> 7
-        return 'streaming', (5 if nc2 <= 5 else 9 if nc2 <= 9 else 17), (N + 31) // 32
-    return 'resident', (N + 31) // 32
+    return ('resident', slabs) if index == sinkhorn_f64_forms.RESIDENT else ('streaming', sinkhorn_f64_forms.NC2[index], slabs)
 
 
 def sk_wave(i):

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import sinkhorn_f64_forms as F  # noqa: E402
 from mdgat_matcher_amd import _lib, ops  # noqa: E402
 from oracle import mdgat_oracle as O  # noqa: E402
 
@@ -65,7 +66,10 @@ def _check_against_alone(name, s):
     _, alone = _alone(name)
     cnt = ([n for n, _ in counts], [m for _, m in counts])
     sd = s.to(DEV)
-    Z = ops.sinkhorn_f64(sd, alpha, iters, counts=cnt, **STREAM)
+    with F.watch() as w:
+        Z = ops.sinkhorn_f64(sd, alpha, iters, counts=cnt, **STREAM)
+    # the instantiation follows the slot (tests/sinkhorn_f64_forms.py: S <5, true>, T and U <17, true>)
+    assert w.ran() == {F.STREAM_SETS_ELSEWHERE[name][1]: 1}, (name, w.ran())
     for b, (n, m) in enumerate(counts):
         assert torch.equal(Z[b, :n + 1, :m + 1], alone[b][0][0]), (name, b)
         rest = Z[b].clone()

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from loss_ref import gt_batch
-from sinkhorn_grad_ref import VARIANT_CASES, max_rel, oracle_grad, reverse_dispatch, sinkhorn_grad
+import sinkhorn_f64_forms as F
+from sinkhorn_grad_ref import REVERSE_VARIANTS, VARIANT_CASES, max_rel, oracle_grad, reverse_dispatch, sinkhorn_grad
 
 pytestmark = pytest.mark.gpu
 
@@ -123,7 +124,10 @@ def test_fp64_reverse_variants(B, N, M, T):
     (the shape list and what it covers: sinkhorn_grad_ref.VARIANT_CASES, checked on the CPU by test_sinkhorn_grad_ref.py)."""
     print(f'M={M}: Mp, nc2, variant = {reverse_dispatch(M)}', end='; ')
     gen = torch.Generator().manual_seed(N * 7 + M * 131 + T)
-    _against_restatement(_uniform(B, N, M, 4.0, gen), 1.0, T, torch.randn(B, N + 1, M + 1, generator=gen, dtype=torch.float64))
+    with F.watch() as w:
+        _against_restatement(_uniform(B, N, M, 4.0, gen), 1.0, T, torch.randn(B, N + 1, M + 1, generator=gen, dtype=torch.float64))
+    # the history run of the instantiation the columns name (tests/sinkhorn_f64_forms.py), and no other call of the fp64 Sinkhorn
+    assert w.ran() == {F.HISTORY_5 + REVERSE_VARIANTS.index(reverse_dispatch(M)[2]): 1}, w.ran()
 
 
 # a score spread of +-100, and dustbin-heavy pairs (alpha above every score), in <9> (900 columns: nc2 8) and <17> (1500: nc2 12)

@@ -119,12 +119,14 @@ EXEMPT = {
     'mdgat_gemm_f64_plan': ('a plan', 'the fp64 GEMM launcher\'s choice as a pure function'),
     'mdgat_attention_f64_plan': ('a plan', 'the fp64 attention launcher\'s choice as a pure function'),
     'mdgat_layer_f64_plan': ('a plan', 'the fp64 layer-tail and encoder launchers\' choice as a pure function'),
+    'mdgat_sinkhorn_f64_plan': ('a plan', 'the fp64 Sinkhorn launchers\' choice as a pure function'),
     'mdgat_layer_launches': ('a counter', 'launches by instantiation, into a host array'),
     'mdgat_sinkhorn_launches': ('a counter', 'launches by instantiation, into a host array'),
     'mdgat_attention_launches': ('a counter', 'launches by instantiation, into a host array'),
     'mdgat_gemm_f64_launches': ('a counter', 'launches by instantiation, into a host array'),
     'mdgat_attention_f64_launches': ('a counter', 'launches by instantiation, into a host array'),
     'mdgat_layer_f64_launches': ('a counter', 'layer tails and encoders by form, into a host array'),
+    'mdgat_sinkhorn_f64_launches': ('a counter', 'calls of the fp64 Sinkhorn by form, into a host array'),
     'mdgat_set_lanes': ('a setter', 'how many streams a handle splits a large batch over'),
     'mdgat_set_layer_split_tiles': ('a setter', 'a launch parameter of the layer kernel'),
     'mdgat_set_f64_layer_fusion': ('a setter', 'which form the fp64 layer tail takes'),
