@@ -232,6 +232,22 @@ SIGNATURES = {
 _lib = None
 
 
+# ... and every symbol include/mdgat_hip_wide.h declares (the per-op ragged entries for slots of up to 2048 keypoints); a table of its own, as
+# the header is: tests/test_ragged_fp32_wide_refusals.py holds the two against each other and every entry to a case of
+# tests/test_gpu_prefilled_wide.py or a stated exemption, as tests/test_host.py and tests/test_prefilled_table.py do for SIGNATURES
+WIDE_SIGNATURES = {
+    'mdgat_set_ragged_fp32_slots': (C.c_int, [C.c_void_p, C.c_int]),
+    'mdgat_sinkhorn_ragged_wide_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'mdgat_sinkhorn_ragged_wide': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
+    'mdgat_sinkhorn_extract_ragged_wide': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_float, C.c_int, C.c_int, C.c_float] +
+                                           [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'mdgat_ragged_wide_launches': (None, [C.POINTER(C.c_uint64)]),
+    'mdgat_attention_ragged_wide': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
+
 def load():
     """Load the shared library (once).  Raises if it has not been built - there is no fallback."""
     global _lib
@@ -242,7 +258,7 @@ def load():
             f'{LIB_PATH} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
             f'or `make -C mdgat_matcher_amd/csrc`.  mdgat_matcher_amd has no CPU / PyTorch fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **WIDE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -73,6 +73,7 @@ struct mdgat_handle {
     unsigned match_token = 0;       // the running forward's token (a new one per mdgat_forward / mdgat_forward_frames call, never 0)
     // Two lanes (forward_batched): the second lane's stream and the events that fork it off the caller's stream and join it again
     int lanes = 2;                  // 1 or 2 (mdgat_set_lanes; default 2, MDGAT_FORWARD_LANES)
+    int ragged_fp32_slots = 0;      // mdgat_set_ragged_fp32_slots: 1: the fp32-class ragged plan takes slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS
     int ragged_sinkhorn = 0;        // mdgat_set_ragged_sinkhorn.  MDGAT_ARITH_FP64: which fp64 Sinkhorn an exact ragged batch runs: 0 resident only, 1 automatic,
                                     // 2 streaming.  MDGAT_ARITH_FP32: non-zero: the ragged forwards run the split form of the fp32 Sinkhorn (split32)
     hipStream_t lane_stream = nullptr;
@@ -280,7 +281,8 @@ struct Workspace {
 // sk64: a form of the fp64 Sinkhorn to hold beside the one a uniform call runs at this shape (sinkhorn_f64_form) - a ragged call's, which
 // mdgat_set_ragged_sinkhorn can put on the streaming form at sizes where the uniform forward runs the resident one
 // split32: room for the split form of the fp32 Sinkhorn, behind everything else
-Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form sk64 = Sk64Form::unsupported, bool split32 = false) {
+// wide32: ... sized for wide slots (mdgat_set_ragged_fp32_slots)
+Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form sk64 = Sk64Form::unsupported, bool split32 = false, bool wide32 = false) {
     const size_t R = (size_t)B * (N + M);
     Workspace w{};
     WsCarver c{static_cast<char*>(base)};
@@ -310,7 +312,7 @@ Workspace carve(void* base, int B, int N, int M, bool f64, bool loss, Sk64Form s
         if (f64) c.take(w.Z64, (size_t)B * (N + 1) * (M + 1));
     }
     if (split32) {
-        w.sksplit_bytes = sinkhorn_split_workspace_bytes(B, N, M);
+        w.sksplit_bytes = sinkhorn_split_workspace_bytes(B, N, M, wide32);
         c.take(w.sksplit, w.sksplit_bytes);
     }
     w.total = c.bytes;
@@ -458,7 +460,7 @@ static size_t workspace_bytes(const mdgat_handle* h, int B, int N, int M, bool l
     // mdgat_set_ragged_sinkhorn - beside the uniform call's, so the streaming form's K is there whenever a ragged call could need it)
     // (on an MDGAT_ARITH_FP32 handle that opted in, likewise: the scratch of the split form a ragged batch in these slots would run)
     const bool split32 = h && h->cfg.arithmetic == MDGAT_ARITH_FP32 && h->ragged_sinkhorn != 0;
-    const size_t whole = carve(nullptr, B, N, M, f64, loss, sinkhorn_f64_form(N, M, true, h ? h->ragged_sinkhorn : 0), split32).total;
+    const size_t whole = carve(nullptr, B, N, M, f64, loss, sinkhorn_f64_form(N, M, true, h ? h->ragged_sinkhorn : 0), split32, h && h->ragged_fp32_slots != 0).total;
     const LanePlan p = lane_plan(h ? h->lanes : 2, B, N, M, f64, loss);
     const size_t laned = p.lane_bytes * (size_t)p.lanes;
     return whole > laned ? whole : laned;
@@ -472,6 +474,15 @@ extern "C" int mdgat_set_ragged_sinkhorn(mdgat_handle* h, int mode) {
     if (!h || mode < 0 || mode > 2) { mdgat_set_error("mdgat_set_ragged_sinkhorn: mode must be 0 (resident), 1 (automatic) or 2 (streaming)"); return -1; }
     const int prev = h->ragged_sinkhorn;
     h->ragged_sinkhorn = mode;
+    return prev;
+}
+
+// the slots of the fp32-class ragged plan (mdgat_forward_ragged and every entry that runs its plan): 0 up to MDGAT_RAGGED_FP32_MAX_KEYPOINTS, today's
+// kernels and bits; 1 up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS - slots within 512 x 512 run what they run under 0.  Size the workspace afterwards.
+extern "C" int mdgat_set_ragged_fp32_slots(mdgat_handle* h, int mode) {
+    if (!h || mode < 0 || mode > 1) { mdgat_set_error("mdgat_set_ragged_fp32_slots: mode must be 0 (512 keypoints per frame) or 1 (wide: 2048)"); return -1; }
+    const int prev = h->ragged_fp32_slots;
+    h->ragged_fp32_slots = mode;
     return prev;
 }
 
@@ -490,6 +501,7 @@ struct Path {
     bool cluster32;   // the fp32 Sinkhorn's cluster kernel (N, M <= 2048): arg-maxes fused, Z only materialised when something reads it
     int cnt_min;      // a ragged batch (FwdIn::counts): the smallest keypoint count of any frame; 0 otherwise
     Sk64Form sk64;    // the form of the fp64 Sinkhorn this call runs if it has the fp64 tail (sinkhorn_f64_form; a ragged batch: by mdgat_set_ragged_sinkhorn)
+    bool wide32;      // a ragged batch on the fp32-class plan of a handle in mode 1 of mdgat_set_ragged_fp32_slots: the wide launchers, the wide split scratch
     bool split32;     // a ragged batch on an MDGAT_ARITH_FP32 handle that opted in (mdgat_set_ragged_sinkhorn non-zero): the fp32 Sinkhorn's split form
                       // wherever the slot has two slabs of rows or more (sinkhorn_plan decides), its scratch in the workspace
     LanePlan lanes;
@@ -538,7 +550,8 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
     p.lanes = (taps || in.counts) ? LanePlan{1, B, 1, 0} : lane_plan(h->lanes, B, N, M, f64, out.loss);
     p.sk64 = f64 ? sinkhorn_f64_form(N, M, (bool)in.counts, h->ragged_sinkhorn) : Sk64Form::unsupported;
     p.split32 = in.counts && !f64 && h->cfg.arithmetic == MDGAT_ARITH_FP32 && h->ragged_sinkhorn != 0;
-    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.sk64, p.split32).total;
+    p.wide32 = in.counts && h->ragged_fp32_slots != 0;
+    const size_t need = p.lanes.nslices > 1 ? p.lanes.lane_bytes * (size_t)p.lanes.lanes : carve(nullptr, B, N, M, f64, out.loss, p.sk64, p.split32, p.wide32).total;
     if (workspace_bytes < need) { mdgat_set_error("mdgat_forward: workspace %zu < %zu bytes", workspace_bytes, need); return MDGAT_ERR_BAD_ARG; }
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) { mdgat_set_error("mdgat_forward: workspace must be 256-byte aligned"); return MDGAT_ERR_BAD_ARG; }
     const int L2 = 2 * h->cfg.L;
@@ -583,8 +596,9 @@ static int plan_forward(mdgat_handle* h, int B, int N, int M, const FwdIn& in, c
         if (taps || out.loss) { mdgat_set_error("%s: taps and the loss are not supported on a ragged batch", who); return MDGAT_ERR_UNSUPPORTED; }
         if (in.rec0 && !in.bank) { mdgat_set_error("%s: fp32 arrays only (no frame records)", who); return MDGAT_ERR_UNSUPPORTED; }
         if (h->cfg.attention_mode == 1) { mdgat_set_error("%s: attention_mode = 1 (single-f16 products) takes no per-pair counts", who); return MDGAT_ERR_UNSUPPORTED; }
-        if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
-            mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        const int limit = p.wide32 ? MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS : MDGAT_RAGGED_FP32_MAX_KEYPOINTS;      // (mdgat_set_ragged_fp32_slots)
+        if (N > limit || M > limit) {
+            mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, N, M, limit);
             return MDGAT_ERR_UNSUPPORTED;
         }
         if (int rc = mdgat_check_ragged(who, B, N, M, in.counts, in.bank ? &in.bank : nullptr, h->cfg.topk, L2, &p.cnt_min)) return rc;
@@ -830,7 +844,7 @@ static int layers32(Fwd& f) {
     for (int i = f.p.first; i < L2; ++i) {
         const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
         const int kk = h->cfg.topk[i];
-        if (int rc = f.cnt0 ? launch_attention_ragged(f.B, f.N, f.M, f.cnt0, f.cnt1, cross, kk, f.q16, f.ws.msg, f.s)
+        if (int rc = f.cnt0 ? (f.p.wide32 ? launch_attention_ragged_wide : launch_attention_ragged)(f.B, f.N, f.M, f.cnt0, f.cnt1, cross, kk, f.q16, f.ws.msg, f.s, nullptr)
                             : launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
         LayerLaunch p{};
@@ -863,7 +877,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
     c.Z = Zout; c.Zfb = Zroom; c.cnt0 = f.cnt0; c.cnt1 = f.cnt1;      // (Zfb: where redone pairs go when the cluster kernel writes no Z)
     c.ws = ws.sk; c.ws_bytes = ws.sk_bytes; c.slots_cleared = sk_clear != 0; c.status = f.status; c.ex = &ex; c.stream = f.s;
     // (a ragged batch of a handle that opted in: the split form, each of its iterations a launch of the profile's Sinkhorn class)
-    c.split = f.p.split32; c.split_ws = ws.sksplit; c.split_ws_bytes = ws.sksplit_bytes;
+    c.wide = f.p.wide32; c.split = f.p.split32; c.split_ws = ws.sksplit; c.split_ws_bytes = ws.sksplit_bytes;
     c.launched = [](void* fwd) { static_cast<Fwd*>(fwd)->mark(MDGAT_PROF_SINKHORN); }; c.launched_ctx = &f;
     if (int rc = launch_sinkhorn(c)) return rc;
     f.mark(MDGAT_PROF_SINKHORN);
@@ -873,7 +887,7 @@ static int tail32(Fwd& f, const FwdOut& o) {
 // one slice of a call (checked by plan_forward) on one lane
 static int forward_impl(mdgat_handle* h, const Path& p, int B, int N, int M, const FwdIn& in, const FwdOut& o, const mdgat_taps* taps,
                         void* workspace, hipStream_t s, unsigned* status, int lane, int defer_alldust) {
-    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.sk64, p.split32);
+    const Workspace ws = carve(workspace, B, N, M, p.f64, o.loss, p.sk64, p.split32, p.wide32);
     Fwd f{h, p, B, N, M, B * (N + M), ws, mdgat_qkv16_carve(ws.qkv16, B, N, M), s, status, taps ? *taps : mdgat_taps{}, h->prof[lane], defer_alldust,
           in.counts.cnt0, in.counts.cnt1, p.cnt_min};
     f.mark(-1);
@@ -1153,17 +1167,24 @@ extern "C" int mdgat_profile(mdgat_handle* h, int enable, double* ms_out, long l
 // ---------------------------------------------------------------------------------- per-op entry points
 extern "C" size_t mdgat_sinkhorn_workspace_bytes(int B, int N, int M) { return sinkhorn_cluster_workspace_bytes(B, N, M); }
 
+static size_t sk_ragged_z_bytes(int B, int Np, int Mp) { return ((size_t)B * (Np + 1) * (Mp + 1) * sizeof(float) + 255) & ~(size_t)255; }
 extern "C" size_t mdgat_sinkhorn_ragged_workspace_bytes(int B, int Np, int Mp) {
     if (B <= 0 || Np <= 0 || Mp <= 0 || Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return 0;
-    return ((size_t)B * (Np + 1) * (Mp + 1) * sizeof(float) + 255) & ~(size_t)255;
+    return sk_ragged_z_bytes(B, Np, Mp);
+}
+// the wide entries' workspace: a Z of the slot's size, the split form's scratch (0 bytes for a slot of one slab) behind it
+extern "C" size_t mdgat_sinkhorn_ragged_wide_workspace_bytes(int B, int Np, int Mp) {
+    if (B <= 0 || Np <= 0 || Mp <= 0 || Np > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS) return 0;
+    return sk_ragged_z_bytes(B, Np, Mp) + sinkhorn_split_workspace_bytes(B, Np, Mp, true);
 }
 
 // the slot limit of the fp32 ragged entries, then the per-pair checks every ragged entry makes (ragged.hpp)
-static int sk_ragged_check(const char* who, int B, int Np, int Mp, int iters, const RaggedCounts& c) {
+static int sk_ragged_check(const char* who, int B, int Np, int Mp, int iters, const RaggedCounts& c, bool wide) {
     if (B < 0 || Np <= 0 || Mp <= 0 || iters < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d iters=%d", who, B, Np, Mp, iters); return MDGAT_ERR_BAD_ARG; }
     if (B == 0) return MDGAT_OK;
-    if (Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
-        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+    const int limit = wide ? MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS : MDGAT_RAGGED_FP32_MAX_KEYPOINTS;
+    if (Np > limit || Mp > limit) {
+        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, limit);
         return MDGAT_ERR_UNSUPPORTED;
     }
     return mdgat_check_ragged(who, B, Np, Mp, c, nullptr, nullptr, 0, nullptr);
@@ -1179,14 +1200,22 @@ static SkCall sk_op_call(int B, int N, int M, const float* scores, float bin_sco
 // ONE body for the four Sinkhorn entries.  counts: null for the uniform entries, which run the streaming kernel instead of the cluster kernel without (enough,
 // 256-byte aligned) workspace; a ragged batch always does, and its extraction scans Z: the caller's, or one produced into the workspace.  ex: as in the
 // forward's call (tail32) - the same launcher, the same SkExtract, the batch-wide rule applied inside the launch.
+// c.wide (the wide ragged entries): c.ws is then a workspace of mdgat_sinkhorn_ragged_wide_workspace_bytes - a Z, the split form's scratch behind it.
 static int sk_op(const char* who, SkCall c, const RaggedCounts* counts, const SkExtract* ex) {
     if (!c.scores || (ex ? sk_outputs_null(*ex) : !c.Z)) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
     if (ex) if (int rc = extract_check_mode(who, ex->mode)) return rc;
     c.ex = ex;
     if (counts) {
-        if (int rc = sk_ragged_check(who, c.B, c.N, c.M, c.iters, *counts)) return rc;
+        if (int rc = sk_ragged_check(who, c.B, c.N, c.M, c.iters, *counts, c.wide)) return rc;
         if (c.B == 0) return MDGAT_OK;
-        if (!c.Z && (!c.ws || c.ws_bytes < mdgat_sinkhorn_ragged_workspace_bytes(c.B, c.N, c.M) || (reinterpret_cast<uintptr_t>(c.ws) & 255))) {
+        if (c.wide) {
+            const size_t zbytes = sk_ragged_z_bytes(c.B, c.N, c.M), split_bytes = c.split ? sinkhorn_split_workspace_bytes(c.B, c.N, c.M, true) : 0;
+            if ((!c.Z || split_bytes) && (!c.ws || c.ws_bytes < mdgat_sinkhorn_ragged_wide_workspace_bytes(c.B, c.N, c.M) || (reinterpret_cast<uintptr_t>(c.ws) & 255))) {
+                mdgat_set_error("%s: the workspace (a Z where none is given, the split form's scratch) is too small or not 256-byte aligned", who);
+                return MDGAT_ERR_BAD_ARG;
+            }
+            if (split_bytes) { c.split_ws = static_cast<char*>(c.ws) + zbytes; c.split_ws_bytes = split_bytes; }
+        } else if (!c.Z && (!c.ws || c.ws_bytes < mdgat_sinkhorn_ragged_workspace_bytes(c.B, c.N, c.M) || (reinterpret_cast<uintptr_t>(c.ws) & 255))) {
             mdgat_set_error("%s: without Z the workspace holds it: too small or not 256-byte aligned", who);
             return MDGAT_ERR_BAD_ARG;
         }
@@ -1222,6 +1251,31 @@ extern "C" int mdgat_sinkhorn_extract_ragged(int B, int Np, int Mp, const int32_
     const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
     const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1};
     return sk_op("mdgat_sinkhorn_extract_ragged", sk_op_call(B, Np, Mp, scores, bin_score, iters, Z_or_null, workspace, workspace_bytes, stream), &counts, &ex);
+}
+
+// ---- the two above in wide slots (up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS), on the one-workgroup kernel or - split - the split form ----
+extern "C" int mdgat_sinkhorn_ragged_wide(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                          const int32_t* counts1_host, const float* scores, float bin_score, int iters, float* Z, int split,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    SkCall c = sk_op_call(B, Np, Mp, scores, bin_score, iters, Z, workspace, workspace_bytes, stream);
+    c.wide = true; c.split = split != 0;
+    return sk_op("mdgat_sinkhorn_ragged_wide", c, &counts, nullptr);
+}
+
+extern "C" int mdgat_sinkhorn_extract_ragged_wide(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                                  const int32_t* counts1_host, const float* scores, float bin_score, int iters, int mode,
+                                                  float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                                                  float* Z_or_null, int split, void* workspace, size_t workspace_bytes, void* stream) {
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    const SkExtract ex{mode, match_threshold, matches0, matches1, mscores0, mscores1};
+    SkCall c = sk_op_call(B, Np, Mp, scores, bin_score, iters, Z_or_null, workspace, workspace_bytes, stream);
+    c.wide = true; c.split = split != 0;
+    return sk_op("mdgat_sinkhorn_extract_ragged_wide", c, &counts, &ex);
+}
+
+extern "C" void mdgat_ragged_wide_launches(uint64_t counts[MDGAT_RAGGED_WIDE_COUNTERS]) {
+    if (counts) ragged_wide_launch_counts(counts);
 }
 
 extern "C" int mdgat_extract(int B, int N, int M, const float* Z, int mode, float match_threshold, int64_t* matches0,
@@ -1276,6 +1330,29 @@ extern "C" int mdgat_attention_ragged(int B, int Np, int Mp, const int32_t* coun
     const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, Np, Mp);
     if (int rc = launch_qkv_split(B, Np, Mp, qkv, q16, s)) return rc;      // (over the padded rows: the kernel reads none beyond a pair's counts)
     return launch_attention_ragged(B, Np, Mp, counts0, counts1, cross, topk, q16, msg, s, sel);
+}
+
+// ... in wide slots: up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS per frame
+extern "C" int mdgat_attention_ragged_wide(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
+                                           const int32_t* counts1_host, int cross, int topk, const float* qkv, float* msg, uint32_t* sel, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    const char* who = "mdgat_attention_ragged_wide";
+    if (!qkv || !msg || !workspace) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
+    if (B == 0) return MDGAT_OK;
+    if (Np > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS) {
+        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
+    if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, nullptr)) return rc;
+    if (workspace_bytes < mdgat_attention_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+        mdgat_set_error("%s: workspace too small or not 16-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, Np, Mp);
+    if (int rc = launch_qkv_split(B, Np, Mp, qkv, q16, s)) return rc;      // (over the padded rows: the kernels read none beyond a pair's counts)
+    return launch_attention_ragged_wide(B, Np, Mp, counts0, counts1, cross, topk, q16, msg, s, sel);
 }
 
 extern "C" int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles) {

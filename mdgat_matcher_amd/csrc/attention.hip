@@ -461,12 +461,12 @@ __device__ __forceinline__ void topk_break_ties(f32x16 (&S)[NBLK], float thr, in
 // Threads: 512 (two waves per SIMD, <= 256 registers) for NBLK <= 8, else 256 (one wave per SIMD).
 // RAGGED = per-pair keypoint counts in padded slots (AttnArgs::cnt0 / cnt1): the queries and keys of workgroup (b, side) are the pair's own,
 //         every offset and stride is the slots'; the V^T columns beyond the pair's keys are staged as zeros whatever the slot holds there, and
-//         the message rows beyond its queries are written 0.  What a row gets depends on its pair alone.
+//         the message rows beyond its queries are written 0.  What a row gets depends on its pair alone.  With LARGE (slots of more than 512
+//         keys, full attention) the window loop runs over the pair's own keys; every wave stays in the loop, whose barriers the workgroup shares.
 template <bool TOPK, int NBLK, bool LARGE, bool TAP = false, bool RAGGED = false>
 __global__ __launch_bounds__(NBLK <= 8 ? 512 : 256, NBLK <= 8 ? 2 : 1) void attention_kernel(AttnArgs a) {
     static_assert(TOPK || !TAP, "the selection tap belongs to the dynamic layers");
     static_assert(!(TOPK && LARGE), "dynamic attention needs the whole row in one chunk");
-    static_assert(!(RAGGED && LARGE), "ragged batches: slots of at most 512 keys");
     constexpr int NT = NBLK <= 8 ? 512 : 256;
     extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
     const int tid = threadIdx.x;
@@ -1068,7 +1068,13 @@ struct WideComm {
 // Dynamic attention for more than 512 keys per frame (up to 256 NW): NW waves share a 32-query tile, wave
 // kw of the tile keeps the logits of keys [256 kw, 256 kw + 256) in 128 registers.  Nothing is shared between
 // the waves except per-row scalars, so K and V^T fragments come straight from global memory (L2) instead of LDS.
-template <int NW, bool TAP = false>
+// RAGGED = per-pair keypoint counts in padded slots, as attention_kernel's: nq and nk are the pair's own, read once into scalars, everything else
+// (strides, Npad, PP, the tap pitch, the grid) the slots'.  A wave whose keys [256 kw, 256 kw + 256) lie beyond the pair's holds -inf only and
+// goes through every exchange with the neutral partial (maximum -inf, count 0, sums 0), as the waves beyond the frame of a uniform launch do;
+// `whole` is the pair's; the first probe follows the pair's own k / keys.  K rows beyond the pair's keys are outside their block's descriptor
+// and load as zeros; V^T columns beyond them may hold anything (they are another matter than the zero pads of a uniform batch) and are
+// selected away in the pair's last block, so that a probability of 0 never meets them.  Message rows beyond the pair's queries are written 0.
+template <int NW, bool TAP = false, bool RAGGED = false>
 __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a) {
     constexpr int NBLK = 8;
     constexpr int NG = 8 / NW;                // query tiles per workgroup pass
@@ -1090,11 +1096,13 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
     const int pass0 = slot % npg;
     const int head = unit & 3, side = (unit >> 2) & 1, b = unit >> 3;
     const int P = a.N + a.M;
-    const int nq = side ? a.M : a.N;
+    const int n0 = RAGGED ? __builtin_amdgcn_readfirstlane(a.cnt0[b]) : a.N, n1 = RAGGED ? __builtin_amdgcn_readfirstlane(a.cnt1[b]) : a.M;
+    const int nq = side ? n1 : n0;
     const int q_off = side ? a.N : 0;
     const int src = a.cross ? (1 - side) : side;
-    const int nk = src ? a.M : a.N;
+    const int nk = src ? n1 : n0;
     const int k_off = src ? a.N : 0;
+    const float zq = RAGGED ? normal_quantile_upper_dev(((float)a.topk - 0.5f) / (float)max(n0, n1)) : a.zq;      // (as the launcher's, of the pair's own sizes)
     const int nblk = (nk + 31) >> 5;
     const int krow = (l31 & ~12) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);   // bits 2 <-> 3
     const float NEG_INF = -__builtin_inff();
@@ -1180,7 +1188,7 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r) m = fmaxf(m, S[jb][r]);
         // (m goes in as this wave's part of the row maximum and comes back as the row's: it travels with the search's statistics)
-        const float thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, a.zq, comm, whole);
+        const float thr = topk_threshold<NBLK, false>(S, m, a.topk, nk, zq, comm, whole);
         // Exact ties at the k-th place (topk_break_ties; about one tile in 10^4).  The pass below counts what it keeps (softmax8); the
         // counts travel to LDS with the output partials, every wave sums them for the rows of the workgroup's query groups, and only
         // a tile that kept too much drops the surplus in the registers and runs the pass once more.  (Until round 6 a counting pass
@@ -1233,10 +1241,20 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
             {
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const f16x8 vh = vhn, vl = vln;
+                    f16x8 vh = vhn, vl = vln;
                     if (2 * jb + t + 1 < 2 * NBLK) vload(2 * jb + t + 1, vhn, vln);
                     __builtin_amdgcn_sched_barrier(0);
                     if (gb >= nblk) continue;
+                    if constexpr (RAGGED) {
+                        if (last_partial && gb == nblk - 1) {       // (wave-uniform) the slot's columns beyond the pair's keys: zeros
+                            const int left = nk - (gb * 32 + t * 16 + 8 * hi);
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                vh[j] = j < left ? vh[j] : (_Float16)0.f;
+                                vl[j] = j < left ? vl[j] : (_Float16)0.f;
+                            }
+                        }
+                    }
                     float p[8], s8[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) s8[j] = S[jb][8 * t + j];
@@ -1301,6 +1319,12 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
             }
         }
         __syncthreads();     // obuf is reused by the next pass
+    }
+    if constexpr (RAGGED) {
+        // this head's 32 columns of the slot's rows beyond the pair's queries, shared among the workgroups of the unit
+        const int nqs = side ? a.M : a.N;
+        float* out = a.msg + ((size_t)b * P + q_off + nq) * 128 + head * 32;
+        for (int idx = pass0 * 512 + tid; idx < (nqs - nq) * 32; idx += npg * 512) out[(size_t)(idx >> 5) * 128 + (idx & 31)] = 0.f;
     }
 }
 
@@ -1462,7 +1486,8 @@ AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
 // A ragged batch: pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M <= 512 (counts checked by the caller against topk).  The form
 // follows the slots alone - never a count, so a pair's launch geometry does not depend on its companions' sizes: attention_kernel's RAGGED
 // instantiation for the slots' 32-key blocks, a dynamic layer always a dynamic one (a pair whose frame has just k keys keeps them all inside
-// the kernel).  The stream, topk16, windowed and wide kernels take no counts.  Counted under the uniform sibling's form.
+// the kernel).  The stream and topk16 kernels take no counts; the windowed and wide ones serve slots beyond 512 (launch_attention_ragged_wide).
+// Counted under the uniform sibling's form.
 int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
                             uint32_t* sel) {
     if (B <= 0) return MDGAT_OK;
@@ -1501,6 +1526,53 @@ int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt
     }
     attention_count_launch(form);
     return mdgat_check_hip(hipGetLastError(), "attention launch (ragged)");
+}
+
+// The same in WIDE slots, up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS per frame.  Slots of at most 16 key blocks run launch_attention_ragged: what
+// they run without the switch.  Beyond, from the slots alone: full attention on the windowed kernel's RAGGED instantiation, a dynamic layer on
+// the wide kernel's - four waves per tile up to 32 key blocks, eight up to 64 - with the uniform launch's geometry for the slots.  Counted under
+// the uniform sibling's form and, apart, as a ragged-wide launch (ragged_wide_count_launch).
+int launch_attention_ragged_wide(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg,
+                                 hipStream_t s, uint32_t* sel) {
+    if (B <= 0) return MDGAT_OK;
+    const int nk_max = N > M ? N : M;
+    const int nblk = (nk_max + 31) / 32;
+    if (nblk <= 16) return launch_attention_ragged(B, N, M, cnt0, cnt1, cross, topk, qkv, msg, s, sel);
+    if (!cnt0 || !cnt1 || N <= 0 || M <= 0 || topk < 0 || nk_max > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS) {
+        mdgat_set_error("attention (ragged, wide): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", N, M, topk, MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    const bool dyn = topk > 0, tap = dyn && sel;
+    AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, nblk, 0, 0, cnt0, cnt1};
+    if (!dyn) {
+        // the windowed kernel: 256 queries per workgroup pass, a workgroup per pass of the larger slot (attention_plan), a window of 512 keys
+        const int qtiles = (nk_max + 255) / 256;
+        const size_t lds = ((size_t)512 * KROWH + (size_t)64 * (512 + 8)) * sizeof(_Float16);
+        const auto kern = attention_kernel<false, 8, true, false, true>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kern, dim3(qtiles, MDGAT_HEADS, B * 2), dim3(512), lds, s, a);
+        attention_count_launch(ATTN_FULL8_WINDOWED);
+        ragged_wide_count_launch(RAGGED_WIDE_ATTN_WINDOWED);
+        return mdgat_check_hip(hipGetLastError(), "attention launch (ragged, windowed)");
+    }
+    if (tap) {
+        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, 0, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
+        a.sel = sel;
+    }
+    // the wide kernels: a workgroup pass is 64 (four waves per tile) or 32 (eight) queries, one workgroup per pass of the larger slot (attention_plan)
+    const bool w4 = nblk <= 32;
+    const int per_pass = w4 ? 64 : 32;
+    a.grid_units = B * 2 * MDGAT_HEADS;
+    a.grid_split = (nk_max + per_pass - 1) / per_pass;
+    const size_t lds = (size_t)(1040 + 8 * 18 * 64 + 4 * 8 * 64) * sizeof(float);      // (launch_attention_topk_wide)
+    const dim3 grid(8 * a.grid_split * ((a.grid_units + 7) / 8));
+    if (w4 && !tap) hipLaunchKernelGGL((attention_topk_wide_kernel<4, false, true>), grid, dim3(512), lds, s, a);
+    else if (w4) hipLaunchKernelGGL((attention_topk_wide_kernel<4, true, true>), grid, dim3(512), lds, s, a);
+    else if (!tap) hipLaunchKernelGGL((attention_topk_wide_kernel<8, false, true>), grid, dim3(512), lds, s, a);
+    else hipLaunchKernelGGL((attention_topk_wide_kernel<8, true, true>), grid, dim3(512), lds, s, a);
+    attention_count_launch((w4 ? ATTN_WIDE4 : ATTN_WIDE8) + (tap ? ATTN_TAP : 0));
+    ragged_wide_count_launch((w4 ? RAGGED_WIDE_ATTN_WIDE4 : RAGGED_WIDE_ATTN_WIDE8) + (tap ? 1 : 0));
+    return mdgat_check_hip(hipGetLastError(), "attention launch (ragged, wide)");
 }
 
 int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode, uint32_t* sel) {

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <atomic>
 #include "../../include/mdgat_hip.h"
+#include "../../include/mdgat_hip_wide.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -174,6 +175,10 @@ int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv,
 // uniform siblings' forms; message rows (and tap masks) beyond a pair's counts are zero.
 int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
                             uint32_t* sel = nullptr);
+// ... in slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS: beyond 16 key blocks the RAGGED instantiations of the windowed kernel (full attention) and
+// of the wide kernels (a dynamic layer), again from the slots alone; counted under the uniform sibling's form and as a ragged-wide launch
+int launch_attention_ragged_wide(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
+                                 uint32_t* sel = nullptr);
 // Which instantiation launch_attention runs and its launch geometry (mdgat_attention_plan, include/mdgat_hip.h: the table of indices), and
 // how often each has been launched by this process (mdgat_attention_launches).  Host code only; the plan touches no HIP call.
 enum AttnForm {
@@ -258,10 +263,11 @@ struct SkCall {
     float *Z, *Zfb;                     // Z [B][N+1][M+1]: may be null with `ex` on the cluster kernel, which fuses the arg-maxes.  Zfb: lent for the pairs the
                                         // streaming kernel redoes when no Z is wanted (neither: the cluster launch is cooperative instead)
     const int *cnt0, *cnt1;             // both or neither (device int32 [B], checked by the caller): a ragged batch on the streaming kernel - pair b has cnt0[b] x
-                                        // cnt1[b] keypoints in slots of N x M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS.  Z is required: 0 outside a pair's own block
+                                        // cnt1[b] keypoints in slots of N x M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS (`wide`: _WIDE_MAX_).  Z is required: 0 outside a pair's own block
     void* ws; size_t ws_bytes;          // the cluster kernel's workspace; missing, short or not 256-byte aligned: the streaming kernel
     bool slots_cleared;                 // the first sinkhorn_slots_clear_bytes(B, N, M) bytes of ws are already zero on the stream (no memset launch)
     unsigned* status; const SkExtract* ex; hipStream_t stream;      // status: optional, a device pointer to MDGAT_STATUS_WORDS host-mapped words
+    bool wide;                          // a ragged batch only: the caller opted in to slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS (slots within 512 x 512 run what they run without)
     bool split;                         // a ragged batch only: the split form (one launch per iteration, a pair's rows over several workgroups) where the slot has
     void* split_ws; size_t split_ws_bytes;      // two slabs of 128 rows or more; then its scratch: 256-byte aligned, sinkhorn_split_workspace_bytes(B, N, M)
     void (*launched)(void*); void* launched_ctx;      // optional: called behind every launch of the split form's iterations (the forward's profile marks)
@@ -275,13 +281,22 @@ enum SkForm {
     SK_RAGGED_1, SK_RAGGED_2, SK_RAGGED_4, SK_RAGGED_8,                                           // ... its RAGGED twins
     SK_GATED,                                                                                     // a streaming kernel gated behind a cluster launch
     SK_EXTRACT,                                                                                   // extract_kernel
-    SK_COUNTERS = MDGAT_SINKHORN_COUNTERS
+    SK_COUNTERS = MDGAT_SINKHORN_COUNTERS,
+    SK_RAGGED_16 = SK_COUNTERS, SK_RAGGED_32                                                      // sinkhorn_kernel<16, 8, true>, <32, 8, true>: a wide ragged slot of more than 512 /
+};                                                                                                // 1024 columns; no index of mdgat_sinkhorn_launches: counted as RAGGED_WIDE_SK_16 / _32
+// the launches only a wide ragged slot reaches (mdgat_ragged_wide_launches, include/mdgat_hip_wide.h: the table of indices)
+enum RaggedWideCounter {
+    RAGGED_WIDE_SK_16 = 0, RAGGED_WIDE_SK_32, RAGGED_WIDE_SPLIT_ITERATION, RAGGED_WIDE_SPLIT_FINISH,      // sinkhorn.hip
+    RAGGED_WIDE_ATTN_WINDOWED, RAGGED_WIDE_ATTN_WIDE4 /* + 1 with the tap */, RAGGED_WIDE_ATTN_WIDE8 = RAGGED_WIDE_ATTN_WIDE4 + 2 /* likewise */,      // attention.hip
+    RAGGED_WIDE_COUNTERS = MDGAT_RAGGED_WIDE_COUNTERS
 };
+void ragged_wide_count_launch(int index);
+void ragged_wide_launch_counts(uint64_t counts[MDGAT_RAGGED_WIDE_COUNTERS]);
 enum SkPath { SK_PATH_NONE = -1, SK_PATH_CLUSTER = 0, SK_PATH_STREAMING = 1 };
 struct SkPlan {
     int path;           // SkPath; SK_PATH_NONE: nothing is launched (an empty batch), or rc says why not
     int scaling;        // SK_SCALING_* of a cluster launch, else -1
-    int stream;         // SK_STREAM_* / SK_RAGGED_*: launched on its own (streaming path) or gated behind the cluster launch; -1: none
+    int stream;         // SK_STREAM_* / SK_RAGGED_* (SK_RAGGED_16 / _32: a wide ragged slot): launched on its own (streaming path) or gated behind the cluster launch; -1: none
     int GR, GC;         // cluster: row slabs of 128 rows x column slabs of 512 columns, one workgroup each
     int ngroups;        // cluster: pairs in flight
     int xcd_map;        // cluster: the partners of a pair share blockIdx % 8, the grid padded to 8 groups per slot
@@ -291,11 +306,11 @@ struct SkPlan {
     int split;          // a ragged batch on the split form: row slabs per pair (grid = B * split per launch, `stream` names the NC); 0: not that form
 };
 // workspace: sinkhorn_workspace_usable; fallback_buffer: a Z, or one lent for redone pairs; ragged: a call with counts
-// split: the caller opted in to the split form (a ragged batch only)
-SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split = false);
+// split: the caller opted in to the split form (a ragged batch only); wide: ... to slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS (likewise)
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split = false, bool wide = false);
 void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]);
 size_t sinkhorn_cluster_workspace_bytes(int B, int N, int M);      // the cluster kernel's workspace (its one layout: sinkhorn.hip); 0: the shape is beyond that kernel
-size_t sinkhorn_split_workspace_bytes(int B, int N, int M);        // the split form's scratch; 0: the slot has one slab of rows (or is beyond the ragged kernels)
+size_t sinkhorn_split_workspace_bytes(int B, int N, int M, bool wide = false);      // the split form's scratch; 0: the slot has one slab of rows (or is beyond the ragged kernels; wide: SkCall::wide)
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M);            // ... the prefix of it that is zero when a launch starts
 bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes);      // ... whether a buffer is large enough for it and 256-byte aligned
 

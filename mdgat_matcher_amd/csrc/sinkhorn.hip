@@ -66,10 +66,65 @@ __device__ __forceinline__ float wave_lse2(const float* x, int n, float extra, i
     return m + lg2(s);
 }
 
+// sinkhorn_kernel's row pass of one iteration (its loop, as a function for the virtual waves below) as wave `vw` of `nw`: the rows vw, vw + nw, ...
+// of the pair - u_i from the row's log-sum-exp over the lane's NC columns (v in registers), then the same registers, with the fresh u_i, folded
+// into the lane's running (max, sum) of the COLUMN log-sum-exps - and the wave's column partials into pm / ps [vw][M].  A wave without rows
+// stores (NEG_BIG, 0).
+template <int NC>
+__device__ __forceinline__ void sk_row_pass(const float* S, int Ms, int N, int M, int vw, int nw, int lane, float bM, float lmu, float* u,
+                                            const float* v, float* pm, float* ps) {
+    // column potentials of this lane's columns
+    float vr[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int j = c * 64 + lane;
+        vr[c] = j < M ? v[j] : 0.f;
+    }
+    float cm[NC], cs[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { cm[c] = NEG_BIG; cs[c] = 0.f; }
+
+    for (int i = vw; i < N; i += nw) {
+        const float* row = S + (size_t)i * Ms;
+        float s[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int j = c * 64 + lane;
+            s[c] = j < M ? row[j] * MDGAT_LOG2E : NEG_BIG;
+        }
+        float m = bM;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) m = fmaxf(m, s[c] + vr[c]);
+        m = wave_max(m);
+        float e = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) e += ex2(s[c] + vr[c] - m);
+        e = wave_sum(e) + ex2(bM - m);
+        const float ui = lmu - (m + lg2(e));          // mdgat.py:283
+        if (lane == 0) u[i] = ui;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {                // fold into the column LSEs (mdgat.py:284)
+            const float w = s[c] + ui;
+            const float nm = fmaxf(cm[c], w);
+            cs[c] = cs[c] * ex2(cm[c] - nm) + ex2(w - nm);
+            cm[c] = nm;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int j = c * 64 + lane;
+        if (j < M) { pm[vw * M + j] = cm[c]; ps[vw * M + j] = cs[c]; }
+    }
+}
+
 // RAGGED: per-pair keypoint counts in padded slots (SkArgs::cnt0 / cnt1).  A pair then computes exactly what it computes alone through the
 // instantiation its own M selects: rows, columns, norm, mu, nu and the dustbins are its own, only the strides are the slots'; a lane's column
 // registers beyond the pair's M hold NEG_BIG as they do beyond M in a uniform launch - exp2 gives an exact 0, added last - so a wider NC
 // changes no bit.  The rest of the pair's Z slot is written 0.
+// The 8-wave RAGGED instantiations (NC = 16, 32: wide slots of more than 512 columns) also hold pairs of at most 512 columns, which alone run on 16
+// waves: wave w there folds rows w, w + 16, ... into its column partials, and the 16 partials merge in ascending w.  Such a pair gets the same
+// bits here from 16 VIRTUAL waves: physical wave w plays virtual wave w and then virtual wave w + 8, each over its own rows in ascending order
+// with 8 column registers, which hold a pair of this width (sk_row_pass).
 template <int NC, int NW, bool RAGGED = false>
 __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -87,10 +142,13 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
     const float* S = a.scores + (size_t)blockIdx.x * Ns * Ms;
     float* Z = a.Z + (size_t)blockIdx.x * (Ns + 1) * (Ms + 1);
 
+    constexpr bool VWAVES = RAGGED && NW == 8;
+    const bool two = VWAVES && M <= 512;                      // (workgroup-uniform) 16 virtual waves
+    const int nwv = two ? 16 : NW;
     float* u = smem;                 // [N+1]
     float* v = u + (N + 1);          // [M+1]
-    float* pm = v + (M + 1);         // [NW][M]
-    float* ps = pm + NW * M;         // [NW][M]
+    float* pm = v + (M + 1);         // [nwv][M]
+    float* ps = pm + nwv * M;        // [nwv][M]
 
     const float alpha = (a.alpha_dev ? *a.alpha_dev : a.alpha_host) * MDGAT_LOG2E;
     const float norm = -logf((float)(N + M));                 // mdgat.py:301
@@ -104,56 +162,78 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_kernel(SkArgs a) {
     __syncthreads();
 
     for (int it = 0; it < a.iters; ++it) {
-        // column potentials of this lane's columns
-        float vr[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int j = c * 64 + lane;
-            vr[c] = j < M ? v[j] : 0.f;
-        }
-        const float bM = alpha + v[M];   // dustbin-column term of every row
-        if (wave == NW - 1) {
-            // dustbin row: u_N = log_mu_N - LSE_j(alpha + v_j), j = 0..M
-            const float lse = alpha + wave_lse2(v, M, v[M], lane);
-            if (lane == 0) u[N] = lmuN - lse;
-        }
-        float cm[NC], cs[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { cm[c] = NEG_BIG; cs[c] = 0.f; }
-
-        for (int i = wave; i < N; i += NW) {
-            const float* row = S + (size_t)i * Ms;
-            float s[NC];
+        if (two) {
+            // a pair of at most 512 columns in a wide slot: the row pass as virtual wave `wave`, then as virtual wave `wave + 8`, of 16
+            const float bM = alpha + v[M];
+            if (wave == NW - 1) {
+                const float lse = alpha + wave_lse2(v, M, v[M], lane);
+                if (lane == 0) u[N] = lmuN - lse;
+            }
+            sk_row_pass<8>(S, Ms, N, M, wave, 16, lane, bM, lmu, u, v, pm, ps);
+            sk_row_pass<8>(S, Ms, N, M, wave + 8, 16, lane, bM, lmu, u, v, pm, ps);
+        } else {
+            // column potentials of this lane's columns
+            float vr[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const int j = c * 64 + lane;
-                s[c] = j < M ? row[j] * MDGAT_LOG2E : NEG_BIG;
+                vr[c] = j < M ? v[j] : 0.f;
             }
-            float m = bM;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) m = fmaxf(m, s[c] + vr[c]);
-            m = wave_max(m);
-            float e = 0.f;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) e += ex2(s[c] + vr[c] - m);
-            e = wave_sum(e) + ex2(bM - m);
-            const float ui = lmu - (m + lg2(e));          // mdgat.py:283
-            if (lane == 0) u[i] = ui;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {                // fold into the column LSEs (mdgat.py:284)
-                const float w = s[c] + ui;
-                const float nm = fmaxf(cm[c], w);
-                cs[c] = cs[c] * ex2(cm[c] - nm) + ex2(w - nm);
-                cm[c] = nm;
+            const float bM = alpha + v[M];   // dustbin-column term of every row
+            if (wave == NW - 1) {
+                // dustbin row: u_N = log_mu_N - LSE_j(alpha + v_j), j = 0..M
+                const float lse = alpha + wave_lse2(v, M, v[M], lane);
+                if (lane == 0) u[N] = lmuN - lse;
             }
-        }
+            float cm[NC], cs[NC];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int j = c * 64 + lane;
-            if (j < M) { pm[wave * M + j] = cm[c]; ps[wave * M + j] = cs[c]; }
+            for (int c = 0; c < NC; ++c) { cm[c] = NEG_BIG; cs[c] = 0.f; }
+
+            for (int i = wave; i < N; i += NW) {
+                const float* row = S + (size_t)i * Ms;
+                float s[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const int j = c * 64 + lane;
+                    s[c] = j < M ? row[j] * MDGAT_LOG2E : NEG_BIG;
+                }
+                float m = bM;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) m = fmaxf(m, s[c] + vr[c]);
+                m = wave_max(m);
+                float e = 0.f;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) e += ex2(s[c] + vr[c] - m);
+                e = wave_sum(e) + ex2(bM - m);
+                const float ui = lmu - (m + lg2(e));          // mdgat.py:283
+                if (lane == 0) u[i] = ui;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {                // fold into the column LSEs (mdgat.py:284)
+                    const float w = s[c] + ui;
+                    const float nm = fmaxf(cm[c], w);
+                    cs[c] = cs[c] * ex2(cm[c] - nm) + ex2(w - nm);
+                    cm[c] = nm;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int j = c * 64 + lane;
+                if (j < M) { pm[wave * M + j] = cm[c]; ps[wave * M + j] = cs[c]; }
+            }
         }
         __syncthreads();
         const float bN = alpha + u[N];   // dustbin-row term of every column
+        if (two) {      // the partials of the 16 virtual waves, in the same order and the same expressions
+            for (int j = tid; j < M; j += NW * 64) {
+                float m = bN;
+#pragma unroll
+                for (int w = 0; w < 16; ++w) m = fmaxf(m, pm[w * M + j]);
+                float e = ex2(bN - m);
+#pragma unroll
+                for (int w = 0; w < 16; ++w) e += ps[w * M + j] * ex2(pm[w * M + j] - m);
+                v[j] = lnu - (m + lg2(e));
+            }
+        } else
         for (int j = tid; j < M; j += NW * 64) {
             float m = bN;
 #pragma unroll
@@ -1106,7 +1186,14 @@ __global__ __launch_bounds__(256) void extract_alldust_fixup(const int64_t* m0, 
 // polls or adds atomically.  The arithmetic per element is sinkhorn_kernel's.  Between launches a pair's state lives in scratch, indexed
 // by the parity of `it`: one (max, sum) column partial per slab, and the row potentials u with u_N behind the pair's last row.
 // A launch reads only what the launch before it wrote: v = 0 at it = 0 comes from no memory.
-constexpr int SK_SPLIT_ROWS = 128, SK_SPLIT_GMAX = 4, SK_SPLIT_NW = 16;
+//
+// WIDE slots (SkCall::wide, a frame beyond 512 keypoints, up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS): the same kernels, instantiated for up to
+// SK_SPLIT_WIDE_GMAX = 16 slabs and, where the slot has more than 512 columns (NC = 16, 32), with 8 waves instead of 16 - sinkhorn_kernel's own
+// choice at those widths, for its reasons: a thread of 8 waves has 256 VGPRs for its four arrays of NC floats, and the workgroup's
+// (N + 1) + (M + 1) + 2 * NW * M floats of LDS are 144 KB at 2048 x 2048 where 16 waves would want 272 KB.  A wave then takes 16 rows of a slab
+// instead of 8; the order of every merge - waves ascending, then slabs ascending - is the narrow form's.  Slots within 512 x 512 keep the
+// GMAX = 4 instantiations: their code and bits do not move.
+constexpr int SK_SPLIT_ROWS = 128, SK_SPLIT_GMAX = 4, SK_SPLIT_NW = 16, SK_SPLIT_WIDE_GMAX = 16, SK_SPLIT_WIDE_NW = 8;
 struct SkSplitArgs {
     const float* scores;      // [B][N][M]
     const float* alpha_dev;
@@ -1124,7 +1211,7 @@ struct SkSplitArgs {
 // u[0 .. N] of iteration it - 1 from scratch, v[0 .. M - 1] as the merge, in ascending g, of the G column partials of iteration it - 1 with
 // the dustbin-row term - sinkhorn_kernel's merge of its per-wave partials; a slab without rows wrote (NEG_BIG, 0), which adds an exact 0
 // below the maximum - and v_M from that u.  it = 0: all zero.  Ends on a barrier.
-template <int NW>
+template <int NW, int GMAX>
 __device__ __forceinline__ void sk_split_potentials(const SkSplitArgs& a, int b, int it, int N, int M, float alpha, float lnu, float lnuM,
                                                     float* u, float* v) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1141,15 +1228,15 @@ __device__ __forceinline__ void sk_split_potentials(const SkSplitArgs& a, int b,
     for (int i = tid; i <= N; i += NW * 64) u[i] = up[i];
     const float bN = alpha + up[N];      // dustbin-row term of every column
     for (int j = tid; j < M; j += NW * 64) {
-        float2 p[SK_SPLIT_GMAX];
+        float2 p[GMAX];
 #pragma unroll
-        for (int g = 0; g < SK_SPLIT_GMAX; ++g) p[g] = g < a.G ? pp[(size_t)g * a.M + j] : float2{NEG_BIG, 0.f};
+        for (int g = 0; g < GMAX; ++g) p[g] = g < a.G ? pp[(size_t)g * a.M + j] : float2{NEG_BIG, 0.f};
         float m = bN;
 #pragma unroll
-        for (int g = 0; g < SK_SPLIT_GMAX; ++g) m = fmaxf(m, p[g].x);
+        for (int g = 0; g < GMAX; ++g) m = fmaxf(m, p[g].x);
         float e = ex2(bN - m);
 #pragma unroll
-        for (int g = 0; g < SK_SPLIT_GMAX; ++g) e += p[g].y * ex2(p[g].x - m);
+        for (int g = 0; g < GMAX; ++g) e += p[g].y * ex2(p[g].x - m);
         v[j] = lnu - (m + lg2(e));
     }
     __syncthreads();
@@ -1161,7 +1248,7 @@ __device__ __forceinline__ void sk_split_potentials(const SkSplitArgs& a, int b,
     __syncthreads();
 }
 
-template <int NC, int NW>
+template <int NC, int NW, int GMAX = SK_SPLIT_GMAX>
 __global__ __launch_bounds__(NW * 64) void sinkhorn_split_kernel(SkSplitArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Ns = a.N, Ms = a.M;
@@ -1192,7 +1279,7 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_split_kernel(SkSplitArgs a) 
     const float lnu = lmu;                                    // cols 0..M-1 (303)
     const float lnuM = (logf((float)N) + norm) * MDGAT_LOG2E; // dustbin column
 
-    sk_split_potentials<NW>(a, b, a.it, N, M, alpha, lnu, lnuM, u, v);
+    sk_split_potentials<NW, GMAX>(a, b, a.it, N, M, alpha, lnu, lnuM, u, v);
 
     // column potentials of this lane's columns
     float vr[NC];
@@ -1258,7 +1345,7 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_split_kernel(SkSplitArgs a) 
 // The finishing launch: the last u (scratch) and v (formed as above), then Z = couplings + u + v - norm (mdgat.py:285, 307) in natural-log
 // units over the pair's own block, the dustbins at its own counts, 0 over the rest of the slot.  Workgroup (b, g) writes the rows
 // [128 g, 128 g + 128) of the slot's N + 1, the last one to the slot's end.
-template <int NW>
+template <int NW, int GMAX = SK_SPLIT_GMAX>
 __global__ __launch_bounds__(NW * 64) void sinkhorn_split_finish_kernel(SkSplitArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Ns = a.N, Ms = a.M;
@@ -1274,7 +1361,7 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_split_finish_kernel(SkSplitA
     const float norm = -logf((float)(N + M));
     const float lnu = norm * MDGAT_LOG2E;
     const float lnuM = (logf((float)N) + norm) * MDGAT_LOG2E;
-    sk_split_potentials<NW>(a, b, a.iters, N, M, alpha, lnu, lnuM, u, v);
+    sk_split_potentials<NW, GMAX>(a, b, a.iters, N, M, alpha, lnu, lnuM, u, v);
     const float uN = u[N], vM = v[M];
     const int r0 = g * SK_SPLIT_ROWS, r1 = g == a.G - 1 ? Ns + 1 : r0 + SK_SPLIT_ROWS;
     for (int i = r0 + wave; i < r1; i += NW) {
@@ -1296,7 +1383,9 @@ __global__ __launch_bounds__(NW * 64) void sinkhorn_split_finish_kernel(SkSplitA
 
 template <int NC, int NW, bool RAGGED = false>
 int launch_sk(const SkArgs& a, int B, hipStream_t s) {
-    const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)NW * a.M) * sizeof(float);
+    // (the 8-wave RAGGED instantiations: a pair of at most 512 columns keeps the partials of 16 virtual waves, [16][512] at the most)
+    const size_t partials = RAGGED && NW == 8 && a.M < 1024 ? (size_t)16 * 512 : (size_t)NW * a.M;
+    const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * partials) * sizeof(float);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_kernel<NC, NW, RAGGED>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return mdgat_check_hip(e, "sinkhorn LDS attribute");
@@ -1350,16 +1439,18 @@ struct SkSplitLayout {
     size_t part, u, total;       // total 0: the split form does not apply (G < 2)
     bool usable(const void* ws, size_t ws_bytes) const { return total && ws && ws_bytes >= total && (reinterpret_cast<uintptr_t>(ws) & 255) == 0; }
 };
-static SkSplitLayout sk_split_layout(int B, int N, int M) {
+static int sk_ragged_limit(bool wide) { return wide ? MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS : MDGAT_RAGGED_FP32_MAX_KEYPOINTS; }
+static bool sk_wide_slot(int N, int M) { return N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS; }
+static SkSplitLayout sk_split_layout(int B, int N, int M, bool wide) {
     SkSplitLayout l{};
-    if (B <= 0 || N <= 0 || M <= 0 || N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) return l;
+    if (B <= 0 || N <= 0 || M <= 0 || N > sk_ragged_limit(wide) || M > sk_ragged_limit(wide)) return l;
     l.G = (N + SK_SPLIT_ROWS - 1) / SK_SPLIT_ROWS;
     if (l.G < 2) return l;
     l.u = ((size_t)B * 2 * l.G * M * sizeof(float2) + 255) & ~(size_t)255;
     l.total = l.u + (((size_t)B * 2 * (N + 1) * sizeof(float) + 255) & ~(size_t)255);
     return l;
 }
-size_t sinkhorn_split_workspace_bytes(int B, int N, int M) { return sk_split_layout(B, N, M).total; }
+size_t sinkhorn_split_workspace_bytes(int B, int N, int M, bool wide) { return sk_split_layout(B, N, M, wide).total; }
 size_t sinkhorn_slots_clear_bytes(int B, int N, int M) { return sk_layout(B, N, M).clear_bytes; }
 bool sinkhorn_workspace_usable(int B, int N, int M, const void* ws, size_t ws_bytes) { return sk_layout(B, N, M).usable(ws, ws_bytes); }
 
@@ -1369,21 +1460,28 @@ static void sinkhorn_count_launch(int index) { sinkhorn_launch_count[index].fetc
 void sinkhorn_launch_counts(uint64_t counts[MDGAT_SINKHORN_COUNTERS]) {
     for (int i = 0; i < SK_COUNTERS; ++i) counts[i] = sinkhorn_launch_count[i].load(std::memory_order_relaxed);
 }
+// ... and the launches that only a wide ragged slot reaches, attention.hip's among them (mdgat_ragged_wide_launches)
+static std::atomic<unsigned long long> ragged_wide_launch_count[RAGGED_WIDE_COUNTERS];
+void ragged_wide_count_launch(int index) { ragged_wide_launch_count[index].fetch_add(1, std::memory_order_relaxed); }
+void ragged_wide_launch_counts(uint64_t counts[MDGAT_RAGGED_WIDE_COUNTERS]) {
+    for (int i = 0; i < RAGGED_WIDE_COUNTERS; ++i) counts[i] = ragged_wide_launch_count[i].load(std::memory_order_relaxed);
+}
 
-SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split) {
+SkPlan sinkhorn_plan(int B, int N, int M, int num_cu, bool workspace, bool fallback_buffer, bool ragged, bool split, bool wide) {
     SkPlan p{SK_PATH_NONE, -1, -1, 0, 0, 0, 0, 0, 0, MDGAT_OK, 0};
     if (B <= 0 || N <= 0 || M <= 0) return p;
     // the one-workgroup-per-pair streaming kernel: any shape up to M = 2048, no workspace
     const int nc = M <= 64 ? 0 : M <= 128 ? 1 : M <= 256 ? 2 : M <= 512 ? 3 : (M <= 1024 && N <= 4096) ? 4 : (M <= 2048 && N <= 4096) ? 5 : -1;
     if (ragged) {
         // the RAGGED instantiation for the slot, picked from the padded sizes alone (launch_sinkhorn: a call with counts)
-        if (N > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || M > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
+        // (wide: the caller opted in to slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS; more than 512 columns select the NC = 16 and 32 twins)
+        if (N > sk_ragged_limit(wide) || M > sk_ragged_limit(wide)) { p.rc = MDGAT_ERR_UNSUPPORTED; return p; }
         p.path = SK_PATH_STREAMING;
-        p.stream = SK_RAGGED_1 + nc;
+        p.stream = nc <= 3 ? SK_RAGGED_1 + nc : SK_RAGGED_16 + (nc - 4);
         p.grid = B;
         // the split form where the caller opted in and the slot has more than one slab of rows: iters launches of B * G workgroups and a
         // finishing one, in the slot's NC; a slot of one slab keeps the one-workgroup kernel
-        if (const int G = sk_split_layout(B, N, M).G; split && G >= 2) { p.split = G; p.grid = B * G; }
+        if (const int G = sk_split_layout(B, N, M, wide).G; split && G >= 2) { p.split = G; p.grid = B * G; }
         return p;
     }
     if (!workspace || N > SK_CLUSTER_MAX || M > SK_CLUSTER_MAX) {
@@ -1480,6 +1578,11 @@ static int launch_streaming(const SkArgs& a, int B, int form, bool gated, hipStr
     static int (*const launch[])(const SkArgs&, int, hipStream_t) = {      // SK_STREAM_1 .. SK_STREAM_32, SK_RAGGED_1 .. SK_RAGGED_8
         launch_sk<1, 16>, launch_sk<2, 16>, launch_sk<4, 16>, launch_sk<8, 16>, launch_sk<16, 8>, launch_sk<32, 8>,
         launch_sk<1, 16, true>, launch_sk<2, 16, true>, launch_sk<4, 16, true>, launch_sk<8, 16, true>};
+    if (form == SK_RAGGED_16 || form == SK_RAGGED_32) {      // a wide ragged slot of more than 512 columns: counted apart (ragged_wide_launch_counts)
+        const int rc = form == SK_RAGGED_16 ? launch_sk<16, 8, true>(a, B, s) : launch_sk<32, 8, true>(a, B, s);
+        if (!rc) ragged_wide_count_launch(form == SK_RAGGED_16 ? RAGGED_WIDE_SK_16 : RAGGED_WIDE_SK_32);
+        return rc;
+    }
     if (form < SK_STREAM_1 || form > SK_RAGGED_8) { mdgat_set_error("sinkhorn: M=%d > 2048 unsupported", a.M); return MDGAT_ERR_UNSUPPORTED; }
     const int rc = launch[form - SK_STREAM_1](a, B, s);
     if (!rc) sinkhorn_count_launch(gated ? SK_GATED : form);
@@ -1533,29 +1636,43 @@ static int launch_scaling(const SkCall& c, const SkPlan& pl, const SkLayout& l) 
 }
 
 // the split form (SkPlan::split slabs per pair): one launch per iteration and the finishing one into Z, then extract_kernel on that Z
-template <int NC>
+template <int NC, int NW = SK_SPLIT_NW, int GMAX = SK_SPLIT_GMAX>
 static hipError_t launch_sk_split(const SkSplitArgs& a, int B, hipStream_t s, bool prepare) {
-    const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)SK_SPLIT_NW * a.M) * sizeof(float);
-    if (prepare) return hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_split_kernel<NC, SK_SPLIT_NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((sinkhorn_split_kernel<NC, SK_SPLIT_NW>), dim3(B * a.G), dim3(SK_SPLIT_NW * 64), lds, s, a);
+    const size_t lds = ((size_t)(a.N + 1) + (a.M + 1) + 2 * (size_t)NW * a.M) * sizeof(float);
+    if (prepare) return hipFuncSetAttribute(reinterpret_cast<const void*>(sinkhorn_split_kernel<NC, NW, GMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((sinkhorn_split_kernel<NC, NW, GMAX>), dim3(B * a.G), dim3(NW * 64), lds, s, a);
     return hipGetLastError();
 }
 static int launch_split(const SkCall& c, const SkPlan& pl) {
-    static hipError_t (*const launch[])(const SkSplitArgs&, int, hipStream_t, bool) = {launch_sk_split<1>, launch_sk_split<2>, launch_sk_split<4>, launch_sk_split<8>};
-    const SkSplitLayout l = sk_split_layout(c.B, c.N, c.M);
-    if (pl.stream < SK_RAGGED_1 || pl.stream > SK_RAGGED_8 || pl.split != l.G || pl.split > SK_SPLIT_GMAX) { mdgat_set_error("sinkhorn: no split form for slots of %d x %d", c.N, c.M); return MDGAT_ERR_UNSUPPORTED; }
+    // by the slot's NC: SK_RAGGED_1 .. SK_RAGGED_8, SK_RAGGED_16, SK_RAGGED_32; a wide slot (more than 512 rows or columns) on the instantiations for
+    // up to 16 slabs, 8 waves where NC >= 16
+    typedef hipError_t (*Launch)(const SkSplitArgs&, int, hipStream_t, bool);
+    static const Launch narrow[] = {launch_sk_split<1>, launch_sk_split<2>, launch_sk_split<4>, launch_sk_split<8>};
+    static const Launch wide[] = {launch_sk_split<1, SK_SPLIT_NW, SK_SPLIT_WIDE_GMAX>, launch_sk_split<2, SK_SPLIT_NW, SK_SPLIT_WIDE_GMAX>,
+                                  launch_sk_split<4, SK_SPLIT_NW, SK_SPLIT_WIDE_GMAX>, launch_sk_split<8, SK_SPLIT_NW, SK_SPLIT_WIDE_GMAX>,
+                                  launch_sk_split<16, SK_SPLIT_WIDE_NW, SK_SPLIT_WIDE_GMAX>, launch_sk_split<32, SK_SPLIT_WIDE_NW, SK_SPLIT_WIDE_GMAX>};
+    const bool wide_slot = c.wide && sk_wide_slot(c.N, c.M);
+    const SkSplitLayout l = sk_split_layout(c.B, c.N, c.M, c.wide);
+    const int nc = pl.stream >= SK_RAGGED_16 ? 4 + (pl.stream - SK_RAGGED_16) : pl.stream - SK_RAGGED_1;
+    if (pl.stream < SK_RAGGED_1 || nc > (wide_slot ? 5 : 3) || pl.split != l.G || pl.split > (wide_slot ? SK_SPLIT_WIDE_GMAX : SK_SPLIT_GMAX)) {
+        mdgat_set_error("sinkhorn: no split form for slots of %d x %d", c.N, c.M);
+        return MDGAT_ERR_UNSUPPORTED;
+    }
     if (!l.usable(c.split_ws, c.split_ws_bytes)) { mdgat_set_error("sinkhorn: the split form needs %zu bytes of 256-byte aligned scratch", l.total); return MDGAT_ERR_BAD_ARG; }
     SkSplitArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z, c.N, c.M, c.iters, c.cnt0, c.cnt1};
     a.part = reinterpret_cast<float2*>(static_cast<char*>(c.split_ws) + l.part); a.u = reinterpret_cast<float*>(static_cast<char*>(c.split_ws) + l.u); a.G = l.G;
-    const auto run = launch[pl.stream - SK_RAGGED_1];
+    const Launch run = wide_slot ? wide[nc] : narrow[nc];
     if (int rc = mdgat_check_hip(run(a, c.B, c.stream, true), "sinkhorn LDS attribute")) return rc;
     for (a.it = 0; a.it < c.iters; ++a.it) {
         if (int rc = mdgat_check_hip(run(a, c.B, c.stream, false), "sinkhorn split launch")) return rc;
+        if (wide_slot) ragged_wide_count_launch(RAGGED_WIDE_SPLIT_ITERATION);
         if (c.launched) c.launched(c.launched_ctx);
     }
     const size_t lds = ((size_t)(c.N + 1) + (c.M + 1)) * sizeof(float);
-    hipLaunchKernelGGL((sinkhorn_split_finish_kernel<SK_SPLIT_NW>), dim3(c.B * a.G), dim3(SK_SPLIT_NW * 64), lds, c.stream, a);
+    if (wide_slot) hipLaunchKernelGGL((sinkhorn_split_finish_kernel<SK_SPLIT_NW, SK_SPLIT_WIDE_GMAX>), dim3(c.B * a.G), dim3(SK_SPLIT_NW * 64), lds, c.stream, a);
+    else hipLaunchKernelGGL((sinkhorn_split_finish_kernel<SK_SPLIT_NW>), dim3(c.B * a.G), dim3(SK_SPLIT_NW * 64), lds, c.stream, a);
     if (int rc = mdgat_check_hip(hipGetLastError(), "sinkhorn split finishing launch")) return rc;
+    if (wide_slot) ragged_wide_count_launch(RAGGED_WIDE_SPLIT_FINISH);
     return c.ex ? launch_extract(c.B, c.N, c.M, c.Z, *c.ex, c.stream, c.cnt0, c.cnt1) : MDGAT_OK;
 }
 
@@ -1571,10 +1688,10 @@ int launch_sinkhorn(const SkCall& c) {
     if (N <= 0 || M <= 0 || c.iters < 0) { mdgat_set_error("sinkhorn: bad shape N=%d M=%d iters=%d", N, M, c.iters); return MDGAT_ERR_BAD_ARG; }
     const SkLayout l = sk_layout(B, N, M);
     const bool usable = !ragged && l.usable(c.ws, c.ws_bytes);      // (the cluster kernel takes no counts)
-    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, c.Z || c.Zfb, ragged, ragged && c.split);
+    const SkPlan p = sinkhorn_plan(B, N, M, usable ? mdgat_cu_count() : 0, usable, c.Z || c.Zfb, ragged, ragged && c.split, ragged && c.wide);
     if (usable) return launch_scaling(c, p, l);
     if (!c.Z) { mdgat_set_error("sinkhorn: the streaming kernel needs a Z buffer"); return MDGAT_ERR_BAD_ARG; }
-    if (ragged && p.rc) { mdgat_set_error("sinkhorn: ragged slots of %d x %d: at most %d keypoints per frame", N, M, MDGAT_RAGGED_FP32_MAX_KEYPOINTS); return p.rc; }
+    if (ragged && p.rc) { mdgat_set_error("sinkhorn: ragged slots of %d x %d: at most %d keypoints per frame", N, M, sk_ragged_limit(c.wide)); return p.rc; }
     if (p.split) return launch_split(c, p);
     SkArgs a{c.scores, c.alpha_dev, c.alpha_host, c.Z, N, M, c.iters};
     a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;

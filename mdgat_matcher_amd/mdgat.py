@@ -232,6 +232,14 @@ class MDGAT(nn.Module):
         self.ragged_sinkhorn_fp32 = str(self.config.get('ragged_sinkhorn_fp32') or os.environ.get('MDGAT_RAGGED_SINKHORN_FP32') or 'pair')
         if self.ragged_sinkhorn_fp32 not in ('pair', 'split'):
             raise ValueError(f"ragged_sinkhorn_fp32={self.ragged_sinkhorn_fp32!r}: expected 'pair' or 'split'")
+        # not a reference key: the slots of the fp32-class ragged forward (include/mdgat_hip_wide.h: mdgat_set_ragged_fp32_slots).  'narrow' (the
+        # default): frames of at most 512 keypoints, today's kernels and bits.  'wide': up to 2048 - slots within 512 x 512 run what they run
+        # under 'narrow', larger ones the ragged forms of the windowed and wide attention kernels and of the streaming Sinkhorn at 16 and 32
+        # columns per lane (ragged_sinkhorn_fp32 = 'split': the split form for up to 16 slabs).  An exact module ignores the key.
+        # MDGAT_RAGGED_SLOTS_FP32 in the environment replaces the default for modules whose config does not carry the key.
+        self.ragged_slots_fp32 = str(self.config.get('ragged_slots_fp32') or os.environ.get('MDGAT_RAGGED_SLOTS_FP32') or 'narrow')
+        if self.ragged_slots_fp32 not in ('narrow', 'wide'):
+            raise ValueError(f"ragged_slots_fp32={self.ragged_slots_fp32!r}: expected 'narrow' or 'wide'")
         f64_layers =self.config.get('f64_layers')
         self.f64_layers = None if f64_layers is None or int(f64_layers) < 0 else int(f64_layers)
         # 'sinkhorn_arithmetic' (optional; MDGAT_SINKHORN_ARITHMETIC in the environment): the exact mode's TAIL - every layer, final_proj,
@@ -441,6 +449,10 @@ class MDGAT(nn.Module):
                     # an MDGAT_ARITH_FP32 handle: its ragged forwards run the split form of the fp32 Sinkhorn (no other call reads the mode)
                     if lib.mdgat_set_ragged_sinkhorn(handle, 1) < 0:
                         raise RuntimeError('mdgat_set_ragged_sinkhorn: ' + _lib.last_error())
+                if not exact and getattr(self, 'ragged_slots_fp32', 'narrow') == 'wide':
+                    # the fp32-class ragged plan of this handle (an MDGAT_ARITH_FP32 one, or the fp64 one that runs the encoders alone)
+                    if lib.mdgat_set_ragged_fp32_slots(handle, 1) < 0:
+                        raise RuntimeError('mdgat_set_ragged_fp32_slots: ' + _lib.last_error())
                 if blob_device_tensor is not None:
                     n = blob_device_tensor.numel()
                     _lib.check(lib.mdgat_load_weights(handle, C.c_void_p(blob_device_tensor.data_ptr()), n, 1),
@@ -551,6 +563,7 @@ class MDGAT(nn.Module):
         }
 
     RAGGED_MAX_KEYPOINTS = 575      # what the register-resident fp64 Sinkhorn holds (csrc/sinkhorn_f64.hip)
+    RAGGED_FP32_WIDE_MAX_KEYPOINTS = 2048     # ... under config['ragged_slots_fp32'] = 'wide' (include/mdgat_hip_wide.h: MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS)
     RAGGED_FP32_MAX_KEYPOINTS = 512     # the slots of the fp32-class ragged forward (include/mdgat_hip.h: MDGAT_RAGGED_FP32_MAX_KEYPOINTS)
     RAGGED_WIDE_MAX_KEYPOINTS = 2048    # an exact module with config['ragged_sinkhorn'] = 'auto' or 'streaming' (MDGAT_RAGGED_WIDE_MAX_KEYPOINTS)
 
@@ -605,7 +618,8 @@ class MDGAT(nn.Module):
     def _ragged_counts_checked(self, h0, h1, Np, Mp):
         """the kernels' limits on the counts of a ragged batch in slots of Np x Mp"""
         kmax = max([int(k) for k in self._topk_schedule()] + [0])
-        limit = self.RAGGED_FP32_MAX_KEYPOINTS if self._ragged_fp32() else self.RAGGED_WIDE_MAX_KEYPOINTS if self._ragged_wide() else self.RAGGED_MAX_KEYPOINTS
+        fp32_limit = self.RAGGED_FP32_WIDE_MAX_KEYPOINTS if getattr(self, 'ragged_slots_fp32', 'narrow') == 'wide' else self.RAGGED_FP32_MAX_KEYPOINTS
+        limit = fp32_limit if self._ragged_fp32() else self.RAGGED_WIDE_MAX_KEYPOINTS if self._ragged_wide() else self.RAGGED_MAX_KEYPOINTS
         for b in range(int(h0.numel())):
             n, m = int(h0[b]), int(h1[b])
             if n > limit or m > limit:

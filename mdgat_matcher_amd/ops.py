@@ -35,7 +35,28 @@ def _match_outputs(B, N, M, device, want_Z=False):
             torch.empty((B, N + 1, M + 1), dtype=torch.float32, device=device) if want_Z else None)
 
 
-def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool = False, counts=None) -> torch.Tensor:
+RAGGED_WIDE_LAUNCHES = ('stream<16,8>,RAGGED', 'stream<32,8>,RAGGED', 'split iteration, wide', 'split finish, wide',
+                        'full<8>,windowed,RAGGED', 'wide<4>,RAGGED', 'wide<4>,TAP,RAGGED', 'wide<8>,RAGGED', 'wide<8>,TAP,RAGGED')
+
+
+def ragged_wide_launches() -> dict:
+    """``mdgat_ragged_wide_launches``: the launches only a wide ragged slot reaches, by name, counted by this process so far (never reset:
+    read them before and after a call and subtract)."""
+    buf = (C.c_uint64 * len(RAGGED_WIDE_LAUNCHES))()
+    _lib.load().mdgat_ragged_wide_launches(buf)
+    return dict(zip(RAGGED_WIDE_LAUNCHES, (int(n) for n in buf)))
+
+
+def _wide_args(wide, split, counts):
+    if (wide or split) and counts is None:
+        raise ValueError('wide / split select the wide ragged entries: they need counts')
+    if split and not wide:
+        raise ValueError('split=True is the wide ragged entries\': it needs wide=True')
+    return bool(wide), bool(split)
+
+
+def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool = False, counts=None, wide: bool = False,
+             split: bool = False) -> torch.Tensor:
     """log_optimal_transport (mdgat.py:288-308): scores [B, N, M] -> Z [B, N+1, M+1] (fp32).
 
     N, M <= 2048 run on the register-resident cluster kernel (128 x 512 tiles per workgroup; needs a small workspace,
@@ -44,7 +65,12 @@ def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool
     ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch in slots of N x M <= 512 - pair b is
     ``scores[b, :counts0[b], :counts1[b]]``, the rest of its slot is never read.  It runs on the streaming kernel:
     ``Z[b, :counts0[b]+1, :counts1[b]+1]`` has the bits of the pair run alone with ``streaming=True`` (its dustbins at row
-    ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0."""
+    ``counts0[b]`` / column ``counts1[b]``), the rest of the slot is 0.
+
+    ``wide=True`` (with counts): slots of up to 2048 x 2048 (``mdgat_sinkhorn_ragged_wide``) - the same contract, slots within 512 x 512 the
+    same kernels and bits.  ``split=True`` with it: the split form where the slot has more than 128 rows (a pair's rows over several
+    workgroups, one launch per iteration); it agrees with the default form to fp32 rounding, not bit for bit."""
+    wide, split = _wide_args(wide, split, counts)
     _need_cuda(scores)
     s = scores.to(torch.float32).contiguous()
     B, N, M = s.shape
@@ -53,20 +79,24 @@ def sinkhorn(scores: torch.Tensor, bin_score: float, iters: int, streaming: bool
     with torch.cuda.device(s.device):
         name, lead, _keep = _entry('mdgat_sinkhorn', counts, B, s.device)
         need = 0 if streaming or counts is not None else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
+        if wide:
+            name, need = name + '_wide', lib.mdgat_sinkhorn_ragged_wide_workspace_bytes(B, N, M) if split else 0
         _buf, ws_ptr, _ = _workspace(need, s.device) if need else (None, None, 0)
-        tail = () if counts is not None else (ws_ptr, need)
+        tail = (int(split), ws_ptr, need) if wide else () if counts is not None else (ws_ptr, need)
         _lib.check(getattr(lib, name)(B, N, M, *lead, s.data_ptr(), float(bin_score), int(iters), Z.data_ptr(), *tail, _stream(s)), name)
     return Z
 
 
 def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: int = _lib.EXTRACT_DUSTBIN, match_threshold: float = 0.2,
-                     want_Z: bool = False, streaming: bool = False, counts=None):
+                     want_Z: bool = False, streaming: bool = False, counts=None, wide: bool = False, split: bool = False):
     """fp32 Sinkhorn + match extraction as the forward runs them (launch_sinkhorn with an extraction request): (matches0, matches1,
     mscores0, mscores1[, Z]).  On the cluster kernel (N, M <= 2048) the arg-maxes are decided in its epilogue and Z is written only
     if wanted; ``streaming=True`` passes no workspace: the one-workgroup-per-pair kernel writes Z and the extraction kernel scans it.
 
     ``counts`` as in ``sinkhorn``: pair b's matches and scores are those of the pair run alone with ``streaming=True`` (no match: -1; the
-    rule of mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0."""
+    rule of mdgat.py:465-467 per pair); beyond its counts matches are -1 and scores 0.  ``wide``, ``split``: as in ``sinkhorn``
+    (``mdgat_sinkhorn_extract_ragged_wide``)."""
+    wide, split = _wide_args(wide, split, counts)
     _need_cuda(scores)
     s = scores.to(torch.float32).contiguous()
     B, N, M = s.shape
@@ -78,6 +108,9 @@ def sinkhorn_extract(scores: torch.Tensor, bin_score: float, iters: int, mode: i
             # the ragged entry scans the Z it is given, or - when none is wanted - one it produces into a workspace
             need = 0 if want_Z else lib.mdgat_sinkhorn_ragged_workspace_bytes(B, N, M)
             z_out, lent = want_Z, ()
+            if wide:        # (one workspace: a Z where none is wanted, the split form's scratch)
+                name, lent = name + '_wide', (int(split),)
+                need = lib.mdgat_sinkhorn_ragged_wide_workspace_bytes(B, N, M) if split or not want_Z else 0
         else:
             need = 0 if streaming else lib.mdgat_sinkhorn_workspace_bytes(B, N, M)
             z_out = want_Z or not need
@@ -489,7 +522,7 @@ def _selection_masks(sel, B, N, M, cross, topk, cnt, device):
     return mask0, mask1
 
 
-def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None):
+def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, return_selection: bool = False, counts=None, wide: bool = False):
     """attention / dynamic_attention (mdgat.py:190-210).  qkv [B, N+M, 3, 4, 32] -> message [B, N+M, 128]
     (with ``return_selection``: also the boolean masks of the keys a dynamic layer kept, see topk_sel_to_masks; full attention keeps
     every key of a pair: all True within its counts).
@@ -497,7 +530,10 @@ def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, ret
 
     ``counts`` (a ``pack_ragged`` dict or ``(counts0, counts1)``): a ragged batch - pair b has ``counts0[b]`` / ``counts1[b]`` keypoints in
     slots of N / M <= 512 rows; its rows are those of its own q/k/v rows alone, bit-identical wherever it stands in a batch of the same slots;
-    message rows and masks beyond its counts are zero / False, and what ``qkv`` holds there reaches no result."""
+    message rows and masks beyond its counts are zero / False, and what ``qkv`` holds there reaches no result.  ``wide=True`` (with counts):
+    slots of up to 2048 rows (``mdgat_attention_ragged_wide``) - the same contract; slots within 512 run the same kernels and give the same bits."""
+    if wide and counts is None:
+        raise ValueError('wide selects the wide ragged entry: it needs counts')
     _need_cuda(qkv)
     x = qkv.to(torch.float32).contiguous()
     B, P = x.shape[0], x.shape[1]
@@ -509,6 +545,8 @@ def attention(qkv: torch.Tensor, N: int, M: int, cross: bool, topk: int = 0, ret
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         sel = torch.empty(topk_sel_words(B, N, M), dtype=torch.int32, device=x.device) if return_selection and topk > 0 else None
         name, lead, cnt = _entry('mdgat_attention', counts, B, x.device)
+        if wide:
+            name += '_wide'
         _lib.check(getattr(lib, name if counts is not None else 'mdgat_attention_sel')(
             B, N, M, *lead, int(bool(cross)), int(topk), x.data_ptr(), msg.data_ptr(), sel.data_ptr() if sel is not None else None,
             ws.data_ptr(), need, _stream(x)), name)

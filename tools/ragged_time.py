@@ -26,7 +26,9 @@ Device-synchronised host clock; the median of --windows windows and their spread
 Ranges beyond the register-resident fp64 Sinkhorn (575 keypoints): ``--ragged_sinkhorn auto`` (or ``streaming``) builds the exact module
 with that config key, and the ranges ``--lo 512 --hi 1024`` and ``--lo 1024 --hi 2048`` then run the exact legs on the streaming fp64
 Sinkhorn with per-pair counts.  Its K workspace follows the SLOT (35.6 MB per pair at 2048; 16 pairs: 570 MB), so --pairs defaults to 16
-and 8 there, 64 below.  The fp32-class ragged forward holds 512 keypoints per frame: its legs are left out of larger ranges.
+and 8 there, 64 below.  The fp32-class ragged forward holds 512 keypoints per frame; for larger ranges - up to 2048 - its modules are built
+with config['ragged_slots_fp32'] = 'wide', and the default and the split Sinkhorn run side by side as below (the bank legs and the
+pooled descriptor's as well).
 
 ``--per_op``: instead of all the above, the streaming ragged per-op launch (``ops.sinkhorn_f64(..., counts=, form='streaming')``, 100
 iterations) on the counts (40, 1200), (1100, 40), (40, 33), (64, 64) in their slots of 1100 x 1200, against the uniform streaming launch
@@ -65,19 +67,20 @@ def main():
         a.pairs = 64 if a.hi <= MDGAT.RAGGED_MAX_KEYPOINTS else 16 if a.hi <= 1024 else 8
     if a.hi > MDGAT.RAGGED_MAX_KEYPOINTS and a.ragged_sinkhorn == 'resident':
         ap.error(f'counts up to {a.hi} are beyond the register-resident fp64 Sinkhorn ({MDGAT.RAGGED_MAX_KEYPOINTS}): --ragged_sinkhorn auto')
-    with_f32 = a.hi <= MDGAT.RAGGED_FP32_MAX_KEYPOINTS
+    with_f32 = a.hi <= MDGAT.RAGGED_FP32_WIDE_MAX_KEYPOINTS
+    wide = {'ragged_slots_fp32': 'wide'} if a.hi > MDGAT.RAGGED_FP32_MAX_KEYPOINTS else {}
     L = 9
     cfg = synth.default_config(L=L, sinkhorn_iterations=100)
     net = MDGAT({**cfg, 'ragged_sinkhorn': a.ragged_sinkhorn}).double()
     net.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net = net.eval().to(dev)
-    net32 = MDGAT({**cfg, 'ragged_arithmetic': 'module'})
+    net32 = MDGAT({**cfg, **wide, 'ragged_arithmetic': 'module'})
     net32.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net32 = net32.float().eval().to(dev)
-    net32s = MDGAT({**cfg, 'ragged_arithmetic': 'module', 'ragged_sinkhorn_fp32': 'split'})
+    net32s = MDGAT({**cfg, **wide, 'ragged_arithmetic': 'module', 'ragged_sinkhorn_fp32': 'split'})
     net32s.load_state_dict(synth.make_state_dict(L=L, seed=1))
     net32s = net32s.float().eval().to(dev)
-    net32g = MDGAT({**cfg, 'ragged_arithmetic': 'module', 'descriptor': 'FPFH_gloabal'})
+    net32g = MDGAT({**cfg, **wide, 'ragged_arithmetic': 'module', 'descriptor': 'FPFH_gloabal'})
     net32g.load_state_dict(synth.make_state_dict(L=L, seed=1, descriptor='FPFH_gloabal'))
     net32g = net32g.float().eval().to(dev)
     rs = np.random.RandomState(a.seed)
@@ -127,7 +130,7 @@ def main():
         legs = {k: v for k, v in legs.items() if not k.startswith('f32_')}
     if a.split_only:
         if not with_f32:
-            ap.error('--split_only: the fp32-class ragged forward holds 512 keypoints per frame')
+            ap.error('--split_only: the fp32-class ragged forward holds 2048 keypoints per frame')
         legs = {k: legs[k] for k in ('f32_b_forward_ragged', 'f32_b_split_forward_ragged', 'f32_d_match_frames_ragged', 'f32_d_split_match_frames_ragged')}
     times = {k: [] for k in legs}
     with torch.no_grad():
