@@ -14,6 +14,8 @@ and with G = dL/dO:
     dQ = s dS K,   dK = s dS^T Q,   dV = P^T G
 
 The selection is not differentiated (the reference gathers, softmaxes and scatters: autograd sends exactly 0 to the other logits).
+A row that keeps no key - no forward writes one, but the selection is an input of the backward - has P = 0 throughout: no message,
+dQ = 0, nothing sent to dK and dV, and a tolerance of 0.
 
 The error bound (``tolerances``), derived as head_grad_ref derives its own: a dot product of length K in fp64, in any order, with or
 without FMA, is off by at most K u sum|a_k b_k| to first order, u = 2^-53, and the formulas rerun on absolute values give the
@@ -48,6 +50,11 @@ CASES = (('full_self_n48',        1, 48, 48, False, 0),
 GOLDEN_FILES = tuple('attention_grad_' + c[0] for c in CASES)
 
 
+def _scale(dtype):
+    """1 / sqrt(32) in ``dtype`` (fp64: SCALE itself)."""
+    return SCALE if dtype == np.float64 else 1 / np.sqrt(np.dtype(dtype).type(32))
+
+
 def _sides(N, M, cross):
     """(query rows, source rows) of frame 0 and of frame 1."""
     f = (slice(0, N), slice(N, N + M))
@@ -60,26 +67,32 @@ def _heads(x):
 
 
 def _softmax(S, mask):
+    """Over the kept keys of each row, exactly 0 elsewhere.  A row that keeps no key has P = 0 throughout (no message, no gradient);
+    every other row goes through the same operations on the same values as if there were no such row."""
     if mask is not None:
         S = np.where(mask, S, -np.inf)
-    e = np.exp(S - S.max(axis=-1, keepdims=True))
-    return e / e.sum(axis=-1, keepdims=True)
+    mx = S.max(axis=-1, keepdims=True)
+    e = np.exp(S - np.where(np.isfinite(mx), mx, 0.0))          # (an empty row: exp(-inf - 0) = 0)
+    l = e.sum(axis=-1, keepdims=True)
+    return e / np.where(l > 0, l, 1.0)
 
 
-def _check(qkv, N, M):
-    qkv = np.asarray(qkv, dtype=np.float64)
+def _check(qkv, N, M, dtype=np.float64):
+    qkv = np.asarray(qkv, dtype=dtype)
     assert qkv.ndim == 5 and qkv.shape[1] == N + M and qkv.shape[2:] == (3, 4, 32), qkv.shape
     return qkv
 
 
-def probabilities(qkv, N, M, cross, masks=None):
+def logits(qkv, N, M, cross, dtype=np.float64):
+    """(S of frame 0's queries [B, 4, N, keys], S of frame 1's), in ``dtype``."""
+    qkv = _check(qkv, N, M, dtype)
+    return tuple(_scale(qkv.dtype) * (_heads(qkv[:, qs, 0]) @ np.swapaxes(_heads(qkv[:, ks, 1]), -1, -2)) for qs, ks in _sides(N, M, cross))
+
+
+def probabilities(qkv, N, M, cross, masks=None, dtype=np.float64):
     """(P of frame 0's queries [B, 4, N, keys], P of frame 1's)."""
-    qkv = _check(qkv, N, M)
-    out = []
-    for side, (qs, ks) in enumerate(_sides(N, M, cross)):
-        Q, K = _heads(qkv[:, qs, 0]), _heads(qkv[:, ks, 1])
-        out.append(_softmax(SCALE * (Q @ np.swapaxes(K, -1, -2)), None if masks is None else np.asarray(masks[side], dtype=bool)))
-    return tuple(out)
+    return tuple(_softmax(S, None if masks is None else np.asarray(masks[side], dtype=bool))
+                 for side, S in enumerate(logits(qkv, N, M, cross, dtype)))
 
 
 def forward(qkv, N, M, cross, masks=None):
@@ -98,6 +111,7 @@ def _backward(qkv, N, M, cross, dmsg, Ps, mode='grad', e_in=None, e_dmsg=None):
     propagation of the module docstring; ``e_in`` / ``e_dmsg`` (err only): absolute errors the inputs qkv / dmsg arrive with."""
     B = qkv.shape[0]
     out = np.zeros_like(qkv)
+    SCALE = _scale(qkv.dtype)
     for (qs, ks), P in zip(_sides(N, M, cross), Ps):
         Q, K, V = _heads(qkv[:, qs, 0]), _heads(qkv[:, ks, 1]), _heads(qkv[:, ks, 2])
         G = _heads(dmsg[:, qs].reshape(B, -1, 4, 32))
@@ -167,6 +181,184 @@ def topk_masks(qkv, N, M, cross, k):
             srt = np.take_along_axis(S, order, axis=-1)
             gap = min(gap, float((srt[..., k - 1] - srt[..., k]).min()))
     return tuple(masks), gap
+
+
+def backward_longdouble(qkv, N, M, cross, dmsg, masks=None):
+    """``backward``, every operation in np.longdouble (x87 extended where the platform has it): dqkv as longdouble."""
+    qkv = _check(qkv, N, M, np.longdouble)
+    dmsg = np.asarray(dmsg, dtype=np.longdouble)
+    assert dmsg.shape == (qkv.shape[0], N + M, 128), dmsg.shape
+    return _backward(qkv, N, M, cross, dmsg, probabilities(qkv, N, M, cross, masks, np.longdouble))
+
+
+def masks_to_words(masks, B, N, M, cross, pad=0):
+    """The inverse of ``ops.topk_sel_to_masks``: int32 words [B][4][N + M][W], W = ceil(max(N, M) / 32), bit j of word w = key
+    32 w + j of the row's source frame.  ``pad`` (0 or 1) is the value of every bit that addresses no key: the bits at or beyond the
+    source's size in its last used word, and every higher word of the row."""
+    W = (max(N, M) + 31) // 32
+    bits = np.full((B, 4, N + M, W * 32), bool(pad))
+    nk = (M, N) if cross else (N, M)
+    for side, rows in enumerate((slice(0, N), slice(N, N + M))):
+        m = np.asarray(masks[side], dtype=bool)
+        assert m.shape == (B, 4, rows.stop - rows.start, nk[side]), (m.shape, side)
+        bits[:, :, rows, :nk[side]] = m
+    words = (bits.reshape(B, 4, N + M, W, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=-1)
+    return words.astype(np.uint32).view(np.int32)
+
+
+LAZY_NEG, LAZY_TAU = -1e300, 8.0
+
+
+def lazy_trace(qkv, N, M, cross, masks=None):
+    """The decisions of the lazy softmax reference in walk 1 of ag_row_kernel, emulated on the fp64 logits (the decisions only, not the
+    kernel's arithmetic).  A wave is 16 consecutive queries of a 64-query tile; lane (query, g), g = 0 .. 3, owns the keys
+    16 jb + g + 4 r, r = 0 .. 3, of key block jb; keys past the frame and keys the row did not keep never count.  Every lane starts
+    from m = mthr = -1e300; in a block where ANY lane of the wave has its block maximum above its own mthr, EVERY lane of the wave
+    sets m = max(m, its block maximum) and mthr = m + 8, rescaling its sums by exp(old m - new m).  (The lanes of a last wave's
+    missing queries run too, as the kernel's do: on logits of 0 under the selection of the frame's last query.  They can trigger a
+    wave's update and are counted nowhere.)
+
+    Returns a dict of [2, 4] arrays (side, head), over all pairs: ``blocks`` the number of wave-blocks in which some lane that already
+    held a kept key rescaled by a factor below 1, ``factor`` the smallest such factor (1.0 if none), ``apart`` the largest distance
+    between the references of a row's quarters at the end (quarters that kept a key; 0.0 if no row has two)."""
+    out = {'blocks': np.zeros((2, 4), dtype=np.int64), 'factor': np.ones((2, 4)), 'apart': np.zeros((2, 4))}
+    for side, S in enumerate(logits(qkv, N, M, cross)):
+        B, _, nq, nk = S.shape
+        keep = np.ones(S.shape, dtype=bool) if masks is None else np.asarray(masks[side], dtype=bool)
+        nw, nblk = (nq + 15) // 16, (nk + 15) // 16
+        # [B, 4, wave, query of the wave, key block, r, g]: the missing queries of the last wave, the missing keys of the last block
+        Sp = np.zeros((B, 4, nw * 16, nblk * 16))
+        Kp = np.zeros(Sp.shape, dtype=bool)
+        Sp[:, :, :nq, :nk], Kp[:, :, :nq, :nk] = S, keep
+        Kp[:, :, nq:, :nk] = keep[:, :, nq - 1:nq]
+        real = (np.arange(nw * 16) < nq).reshape(nw, 16, 1)
+        lm_all = np.where(Kp, Sp, LAZY_NEG).reshape(B, 4, nw, 16, nblk, 4, 4).max(axis=5)      # [B, 4, wave, query, block, g]
+        m = np.full((B, 4, nw, 16, 4), LAZY_NEG)
+        mthr = m.copy()
+        has = np.zeros(m.shape, dtype=bool)
+        for jb in range(nblk):
+            lm = lm_all[..., jb, :]
+            fire = (lm > mthr).any(axis=(3, 4), keepdims=True)
+            mnew = np.where(fire, np.maximum(m, lm), m)
+            shrink = has & real & (mnew > m)
+            out['blocks'][side] += shrink.any(axis=(3, 4)).sum(axis=(0, 2))
+            fac = np.where(shrink, np.exp(np.where(shrink, m - mnew, 0.0)), 1.0)
+            out['factor'][side] = np.minimum(out['factor'][side], fac.min(axis=(0, 2, 3, 4)))
+            mthr = np.where(fire, mnew + LAZY_TAU, mthr)
+            m = mnew
+            has |= lm > LAZY_NEG
+        two = real[..., 0] & (has.sum(axis=-1) >= 2)
+        apart = np.where(has, m, -np.inf).max(axis=-1) - np.where(has, m, np.inf).min(axis=-1)
+        out['apart'][side] = np.where(two, apart, 0.0).max(axis=(0, 2, 3))
+    return out
+
+
+# ---- seeded inputs that reach what Gaussian inputs of unit scale do not: (qkv [B, N + M, 3, 4, 32], dmsg [B, N + M, 128]) ----
+def _unit_heads(rs):
+    u = rs.standard_normal((4, 32))
+    return u / np.linalg.norm(u, axis=-1, keepdims=True)
+
+
+def _frames(N, M):
+    return (slice(0, N), slice(N, N + M))
+
+
+def gauss(B, N, M, seed, scale):
+    """Standard normal; q and k times ``scale``: logits of standard deviation scale^2."""
+    rs = np.random.RandomState(seed)
+    qkv, dmsg = rs.standard_normal((B, N + M, 3, 4, 32)), rs.standard_normal((B, N + M, 128))
+    qkv[:, :, :2] *= scale
+    return qkv, dmsg
+
+
+def ramp(B, N, M, seed, peak=200.0):
+    """Noise 0.3 N(0, 1); the k of key j gets a t_j u_head, t rising linearly from -1 to 1 along the frame's keys, the q of query i
+    gets +- a c_i u_head (+ for even i, - for odd i, c_i in [0.5, 1]), u_head a unit vector per head, a = sqrt(peak sqrt(32)): the
+    logit of (i, j) is +- peak c_i t_j plus noise.  Even rows rise along the keys - the reference moves block after block - and odd
+    rows fall: the first block holds the mass and later terms run down toward exp(-2 peak)."""
+    rs = np.random.RandomState(seed)
+    qkv, dmsg = 0.3 * rs.standard_normal((B, N + M, 3, 4, 32)), rs.standard_normal((B, N + M, 128))
+    u, a = _unit_heads(rs), np.sqrt(peak * np.sqrt(32.0))
+    for fr in _frames(N, M):
+        n = fr.stop - fr.start
+        c = rs.uniform(0.5, 1.0, (B, n)) * np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
+        qkv[:, fr, 0] += a * c[:, :, None, None] * u
+        qkv[:, fr, 1] += a * np.linspace(-1.0, 1.0, n)[None, :, None, None] * u
+    return qkv, dmsg
+
+
+def _spiked(B, N, M, seed, peak, keys):
+    rs = np.random.RandomState(seed)
+    qkv, dmsg = 1.3 * rs.standard_normal((B, N + M, 3, 4, 32)), rs.standard_normal((B, N + M, 128))
+    u, a = _unit_heads(rs), np.sqrt(peak * np.sqrt(32.0))
+    qkv[:, :, 0] += a * u
+    for fr in _frames(N, M):
+        qkv[:, fr, 1][:, keys(fr.stop - fr.start)] += a * u
+    return qkv, dmsg
+
+
+def lastkey(B, N, M, seed, peak=150.0):
+    """1.3 N(0, 1), every q plus a u_head and only the LAST key of each frame plus a u_head (a = sqrt(peak sqrt(32))): the dominant
+    logit, about ``peak``, arrives in the final key block."""
+    return _spiked(B, N, M, seed, peak, lambda n: slice(n - 1, n))
+
+
+def quarter(B, N, M, seed, peak=120.0):
+    """As ``lastkey``, but the keys j = 2 (mod 4) of each frame get a u_head: one lane quarter of every row holds all the mass."""
+    return _spiked(B, N, M, seed, peak, lambda n: slice(2, n, 4))
+
+
+def alternate_rows(dmsg, e=20):
+    """dmsg with its rows scaled by 2^e (even rows) and 2^-e (odd rows)."""
+    return dmsg * np.where(np.arange(dmsg.shape[1]) % 2 == 0, 2.0 ** e, 2.0 ** -e)[None, :, None]
+
+
+def varied_masks(B, N, M, cross, seed):
+    """Row (row + head) % 6 = 0 .. 5 keeps 0, 1, 2, nk / 2, nk - 1, nk keys of its source's nk, drawn at random."""
+    rs = np.random.RandomState(seed)
+    masks = []
+    for nq, nk in zip((N, M), (M, N) if cross else (N, M)):
+        counts = np.array([0, 1, 2, nk // 2, nk - 1, nk])[(np.arange(nq)[None, :] + np.arange(4)[:, None]) % 6]
+        masks.append(np.argsort(rs.random_sample((B, 4, nq, nk)), axis=-1) < np.minimum(counts, nk)[None, :, :, None])
+    return tuple(masks)
+
+
+def last_block_masks(B, N, M, cross):
+    """Every row keeps the keys of its source's last block of 16 (keys >= 16 floor((nk - 1) / 16)) and no other."""
+    return tuple(np.broadcast_to(np.arange(nk) >= 16 * ((nk - 1) // 16), (B, 4, nq, nk)).copy()
+                 for nq, nk in zip((N, M), (M, N) if cross else (N, M)))
+
+
+def constant_masks(B, N, M, cross, value):
+    return tuple(np.full((B, 4, nq, nk), bool(value)) for nq, nk in zip((N, M), (M, N) if cross else (N, M)))
+
+
+FAMILIES = {'gauss_2m12': (gauss, {'scale': 2.0 ** -12}), 'gauss_1.3': (gauss, {'scale': 1.3}), 'gauss_4': (gauss, {'scale': 4.0}),
+            'gauss_6': (gauss, {'scale': 6.0}), 'ramp': (ramp, {}), 'lastkey': (lastkey, {}), 'quarter': (quarter, {})}
+HARD = ('gauss_4', 'gauss_6', 'ramp', 'lastkey', 'quarter')          # the reference of walk 1 must be seen to move
+TINY_FACTOR = ('gauss_6', 'ramp', 'lastkey')                         # ... by a factor below 1e-20 somewhere
+#             family,  B, N, M, cross, k
+LOGIT_CASES = tuple((f, B, N, M, cross, k) for f in ('gauss_2m12', 'gauss_4', 'gauss_6', 'ramp', 'lastkey', 'quarter')
+                    for (B, N, M, cross) in ((2, 49, 65, True), (2, 49, 65, False), (1, 130, 70, True)) for k in (0, 8, 17))
+#                 family,  B, N, M, cross
+SELECTION_CASES = tuple((f, 2, N, M, cross) for f in ('gauss_1.3', 'gauss_6') for (N, M, cross) in ((49, 65, True), (65, 49, False)))
+SELECTION_KINDS = ('varied', 'last_block', 'none', 'all')
+SINGLE_CASES = tuple(('gauss_1.3', 3, N, M, cross, k) for (N, M) in ((1, 1), (1, 70), (65, 1)) for cross in (False, True) for k in (0, 1))
+INVARIANCE_CASES = (('gauss_4', 2, 49, 65, True, 8), ('gauss_4', 2, 65, 49, False, 0))
+
+
+def family_inputs(family, B, N, M, cross):
+    """The seeded (qkv, dmsg) of a case: one seed per (family, shape, direction)."""
+    fn, kw = FAMILIES[family]
+    return fn(B, N, M, seed=1000 * sorted(FAMILIES).index(family) + 7 * N + 3 * M + B + int(cross), **kw)
+
+
+def selection_masks(kind, B, N, M, cross):
+    if kind == 'varied':
+        return varied_masks(B, N, M, cross, seed=N + 2 * M + int(cross))
+    if kind == 'last_block':
+        return last_block_masks(B, N, M, cross)
+    return constant_masks(B, N, M, cross, kind == 'all')
 
 
 def worst_fraction(got, want, tol):
