@@ -854,10 +854,16 @@ int mdgat_attention_ragged(int B, int Np, int Mp, const int32_t* counts0, const 
  * attention_kernel, the grid_split of the 16-query and wide kernels, the tile count of the streamed one.  *tiles (optional): the most
  * query tiles (wide kernels: passes) one workgroup walks, ceil(tiles of the larger frame / split).  Both 0 with -1.  A pure function of
  * its arguments: no device is needed or touched; launch_attention takes its branch and its split from the same code.
+ * mdgat_attention_ragged_plan: the same for a ragged batch in slots of Np x Mp (mdgat_attention_ragged; wide != 0: mdgat_attention_ragged_wide,
+ * include/mdgat_hip_wide.h; a layer of mdgat_forward_ragged).  The index is the uniform sibling's, the kernel its RAGGED instantiation: from
+ * the slots alone - never B or a count - one of 1, 2, 4 .. 6 and 11 .. 13, and beyond 512 keypoints (wide only) 3, 9, 10, 16 or 17; never the stream or
+ * topk16 kernels, which take no counts.  Any topk > 0 is a dynamic layer; the split and the tiles are the uniform launch's for the slots.
+ * -1: an empty batch, or the launcher refuses (topk < 0, a slot beyond 512 keypoints, with wide beyond 2048).
  * mdgat_attention_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
  * counters, never reset: read them before and after a call and subtract). */
 #define MDGAT_ATTENTION_FORMS 23
 int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles);
+int mdgat_attention_ragged_plan(int B, int Np, int Mp, int topk, int tap, int wide, int* split, int* tiles);
 void mdgat_attention_launches(uint64_t counts[MDGAT_ATTENTION_FORMS]);
 
 /* Measurement only (bench.py, roofline_qk): the Q K^T contraction of the streamed full-attention kernel in isolation -

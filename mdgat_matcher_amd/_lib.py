@@ -191,6 +191,7 @@ SIGNATURES = {
                                   C.c_size_t, C.c_void_p]),
     'mdgat_attention_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'mdgat_attention_plan': (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2),
+    'mdgat_attention_ragged_plan': (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2),
     'mdgat_attention_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_mfma_probe': (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_void_p]),
     'mdgat_mfma_f64_probe': (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.c_void_p]),

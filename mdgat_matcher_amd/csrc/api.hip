@@ -844,8 +844,10 @@ static int layers32(Fwd& f) {
     for (int i = f.p.first; i < L2; ++i) {
         const int cross = i & 1;   // names = ['self', 'cross'] * L (mdgat.py:352-353)
         const int kk = h->cfg.topk[i];
-        if (int rc = f.cnt0 ? (f.p.wide32 ? launch_attention_ragged_wide : launch_attention_ragged)(f.B, f.N, f.M, f.cnt0, f.cnt1, cross, kk, f.q16, f.ws.msg, f.s, nullptr)
-                            : launch_attention(f.B, f.N, f.M, cross, kk, f.q16, f.ws.msg, f.s, h->cfg.attention_mode, f.sel_tap(i))) return rc;
+        AttnCall c{f.B, f.N, f.M, cross, kk, h->cfg.attention_mode, f.q16, f.ws.msg};
+        c.sel = f.cnt0 ? nullptr : f.sel_tap(i);      // (a ragged forward taps no selection)
+        c.cnt0 = f.cnt0; c.cnt1 = f.cnt1; c.wide = f.p.wide32; c.stream = f.s;
+        if (int rc = launch_attention(c)) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_ATTENTION_TOPK : MDGAT_PROF_ATTENTION_FULL);
         LayerLaunch p{};
         p.msg = f.ws.msg; p.do_mlp = 1; p.mlp = h->w.layer32(i);
@@ -1290,73 +1292,67 @@ extern "C" size_t mdgat_attention_workspace_bytes(int B, int N, int M) {
     return mdgat_qkv16_halves(B, N, M) * sizeof(_Float16);
 }
 
+// ONE body for the four attention entries: the q | k | v split into the workspace, then the forward's launcher.  counts: null for the uniform entries;
+// a ragged batch has them on the device for the kernel, on the host for the checks made before the launch (wide: slots of up to
+// MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS per frame).
+static int attention_op(const char* who, int B, int N, int M, int cross, int topk, const float* qkv, float* msg, uint32_t* sel, void* workspace,
+                        size_t workspace_bytes, void* stream, const RaggedCounts* counts = nullptr, bool wide = false) {
+    if (!qkv || !msg || !workspace) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    AttnCall c{B, N, M, cross, topk};
+    c.msg = msg; c.sel = sel; c.wide = wide; c.stream = static_cast<hipStream_t>(stream);
+    if (counts) {
+        if (topk < 0 || B < 0 || N <= 0 || M <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, B, N, M, topk); return MDGAT_ERR_BAD_ARG; }
+        if (B == 0) return MDGAT_OK;
+        const int limit = wide ? MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS : MDGAT_RAGGED_FP32_MAX_KEYPOINTS;
+        if (N > limit || M > limit) {
+            mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, N, M, limit);
+            return MDGAT_ERR_UNSUPPORTED;
+        }
+        if (int rc = mdgat_check_ragged(who, B, N, M, *counts, nullptr, &topk, 1, nullptr)) return rc;
+        c.cnt0 = counts->cnt0; c.cnt1 = counts->cnt1;
+    } else if (topk < 0) { mdgat_set_error("%s: topk < 0", who); return MDGAT_ERR_BAD_ARG; }
+    if (workspace_bytes < mdgat_attention_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+        mdgat_set_error("%s: workspace too small or not 16-byte aligned", who);
+        return MDGAT_ERR_BAD_ARG;
+    }
+    c.qkv = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, N, M);
+    if (int rc = launch_qkv_split(B, N, M, qkv, c.qkv, c.stream)) return rc;      // (a ragged batch: over the padded rows - the kernels read none beyond a pair's counts)
+    return launch_attention(c);
+}
+
 extern "C" int mdgat_attention(int B, int N, int M, int cross, int topk, const float* qkv, float* msg, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    return mdgat_attention_sel(B, N, M, cross, topk, qkv, msg, nullptr, workspace, workspace_bytes, stream);
+    return attention_op("mdgat_attention", B, N, M, cross, topk, qkv, msg, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mdgat_attention_sel(int B, int N, int M, int cross, int topk, const float* qkv, float* msg, uint32_t* sel,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (!qkv || !msg || !workspace) { mdgat_set_error("mdgat_attention: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (topk < 0) { mdgat_set_error("mdgat_attention: topk < 0"); return MDGAT_ERR_BAD_ARG; }
-    if (workspace_bytes < mdgat_attention_workspace_bytes(B, N, M) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-        mdgat_set_error("mdgat_attention: workspace too small or not 16-byte aligned");
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, N, M);
-    if (int rc = launch_qkv_split(B, N, M, qkv, q16, s)) return rc;
-    return launch_attention(B, N, M, cross, topk, q16, msg, s, 0, sel);
+    return attention_op("mdgat_attention", B, N, M, cross, topk, qkv, msg, sel, workspace, workspace_bytes, stream);
 }
 
-// a ragged batch: the counts on the device for the kernel, on the host for the checks made before the launch
 extern "C" int mdgat_attention_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                       const int32_t* counts1_host, int cross, int topk, const float* qkv, float* msg, uint32_t* sel, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_attention_ragged";
-    if (!qkv || !msg || !workspace) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (Np > MDGAT_RAGGED_FP32_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
-        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, nullptr)) return rc;
-    if (workspace_bytes < mdgat_attention_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-        mdgat_set_error("%s: workspace too small or not 16-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, Np, Mp);
-    if (int rc = launch_qkv_split(B, Np, Mp, qkv, q16, s)) return rc;      // (over the padded rows: the kernel reads none beyond a pair's counts)
-    return launch_attention_ragged(B, Np, Mp, counts0, counts1, cross, topk, q16, msg, s, sel);
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    return attention_op("mdgat_attention_ragged", B, Np, Mp, cross, topk, qkv, msg, sel, workspace, workspace_bytes, stream, &counts);
 }
 
-// ... in wide slots: up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS per frame
 extern "C" int mdgat_attention_ragged_wide(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                            const int32_t* counts1_host, int cross, int topk, const float* qkv, float* msg, uint32_t* sel, void* workspace,
                                            size_t workspace_bytes, void* stream) {
-    const char* who = "mdgat_attention_ragged_wide";
-    if (!qkv || !msg || !workspace) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
-    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
-    if (B == 0) return MDGAT_OK;
-    if (Np > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS || Mp > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS) {
-        mdgat_set_error("%s: padded sizes %d x %d: fp32 ragged batches hold at most %d keypoints per frame", who, Np, Mp, MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, nullptr)) return rc;
-    if (workspace_bytes < mdgat_attention_workspace_bytes(B, Np, Mp) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-        mdgat_set_error("%s: workspace too small or not 16-byte aligned", who);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Qkv16 q16 = mdgat_qkv16_carve(static_cast<_Float16*>(workspace), B, Np, Mp);
-    if (int rc = launch_qkv_split(B, Np, Mp, qkv, q16, s)) return rc;      // (over the padded rows: the kernels read none beyond a pair's counts)
-    return launch_attention_ragged_wide(B, Np, Mp, counts0, counts1, cross, topk, q16, msg, s, sel);
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    return attention_op("mdgat_attention_ragged_wide", B, Np, Mp, cross, topk, qkv, msg, sel, workspace, workspace_bytes, stream, &counts, true);
 }
 
 extern "C" int mdgat_attention_plan(int B, int N, int M, int topk, int tap, int mode, int* split, int* tiles) {
     const AttnPlan p = topk < 0 ? AttnPlan{-1, 0, 0, MDGAT_ERR_BAD_ARG} : attention_plan(B, N, M, topk, tap != 0, mode);   // (topk < 0: mdgat_attention refuses)
+    if (split) *split = p.split;
+    if (tiles) *tiles = p.tiles;
+    return p.form;
+}
+
+extern "C" int mdgat_attention_ragged_plan(int B, int Np, int Mp, int topk, int tap, int wide, int* split, int* tiles) {
+    const AttnPlan p = attention_plan(B, Np, Mp, topk, tap != 0, 0, true, wide != 0);
     if (split) *split = p.split;
     if (tiles) *tiles = p.tiles;
     return p.form;

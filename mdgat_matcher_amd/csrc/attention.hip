@@ -1328,21 +1328,40 @@ __global__ __launch_bounds__(512, 2) void attention_topk_wide_kernel(AttnArgs a)
     }
 }
 
-static int launch_attention_topk_wide(const AttnArgs& a, int B, const AttnPlan& p, hipStream_t s) {
-    const size_t lds = (size_t)(1040 + 8 * 18 * 64 + 4 * 8 * 64) * sizeof(float);
-    AttnArgs w = a;
-    w.grid_units = B * 2 * MDGAT_HEADS;
-    w.grid_split = p.split;
-    const dim3 grid(8 * w.grid_split * ((w.grid_units + 7) / 8));
-    switch (p.form) {
-    case ATTN_WIDE4: hipLaunchKernelGGL(attention_topk_wide_kernel<4>, grid, dim3(512), lds, s, w); break;
-    case ATTN_WIDE4 + ATTN_TAP: hipLaunchKernelGGL((attention_topk_wide_kernel<4, true>), grid, dim3(512), lds, s, w); break;
-    case ATTN_WIDE8: hipLaunchKernelGGL(attention_topk_wide_kernel<8>, grid, dim3(512), lds, s, w); break;
-    default: hipLaunchKernelGGL((attention_topk_wide_kernel<8, true>), grid, dim3(512), lds, s, w); break;
+// The one map from a planned form to its instantiation: every form has a uniform one here but the stream forms (attention_stream.hip); the
+// general, windowed and wide kernels have a RAGGED twin, which takes counts.  Null: none - attention_plan plans no such launch.
+using AttnKernel = void (*)(AttnArgs);
+static AttnKernel attention_instantiation(int form, bool ragged) {
+    switch (form) {
+    case ATTN_FULL4: return ragged ? attention_kernel<false, 4, false, false, true> : attention_kernel<false, 4, false>;
+    case ATTN_FULL8: return ragged ? attention_kernel<false, 8, false, false, true> : attention_kernel<false, 8, false>;
+    case ATTN_FULL8_WINDOWED: return ragged ? attention_kernel<false, 8, true, false, true> : attention_kernel<false, 8, true>;
+    case ATTN_DYN4: return ragged ? attention_kernel<true, 4, false, false, true> : attention_kernel<true, 4, false>;
+    case ATTN_DYN8: return ragged ? attention_kernel<true, 8, false, false, true> : attention_kernel<true, 8, false>;
+    case ATTN_DYN16: return ragged ? attention_kernel<true, 16, false, false, true> : attention_kernel<true, 16, false>;
+    case ATTN_DYN4 + ATTN_TAP: return ragged ? attention_kernel<true, 4, false, true, true> : attention_kernel<true, 4, false, true>;
+    case ATTN_DYN8 + ATTN_TAP: return ragged ? attention_kernel<true, 8, false, true, true> : attention_kernel<true, 8, false, true>;
+    case ATTN_DYN16 + ATTN_TAP: return ragged ? attention_kernel<true, 16, false, true, true> : attention_kernel<true, 16, false, true>;
+    case ATTN_WIDE4: return ragged ? attention_topk_wide_kernel<4, false, true> : attention_topk_wide_kernel<4>;
+    case ATTN_WIDE8: return ragged ? attention_topk_wide_kernel<8, false, true> : attention_topk_wide_kernel<8>;
+    case ATTN_WIDE4 + ATTN_TAP: return ragged ? attention_topk_wide_kernel<4, true, true> : attention_topk_wide_kernel<4, true>;
+    case ATTN_WIDE8 + ATTN_TAP: return ragged ? attention_topk_wide_kernel<8, true, true> : attention_topk_wide_kernel<8, true>;
+    case ATTN_TOPK16_256: return ragged ? nullptr : attention_topk16_kernel<false, false, 256>;
+    case ATTN_TOPK16_512: return ragged ? nullptr : attention_topk16_kernel<false, false, 512>;
+    case ATTN_TOPK16_256 + ATTN_TAP: return ragged ? nullptr : attention_topk16_kernel<false, true, 256>;
+    case ATTN_TOPK16_512 + ATTN_TAP: return ragged ? nullptr : attention_topk16_kernel<false, true, 512>;
+    case ATTN_TOPK16_256_FAST: return ragged ? nullptr : attention_topk16_kernel<true, false, 256>;
+    case ATTN_TOPK16_512_FAST: return ragged ? nullptr : attention_topk16_kernel<true, false, 512>;
+    case ATTN_TOPK16_256_FAST + ATTN_FAST_TAP: return ragged ? nullptr : attention_topk16_kernel<true, true, 256>;
+    case ATTN_TOPK16_512_FAST + ATTN_FAST_TAP: return ragged ? nullptr : attention_topk16_kernel<true, true, 512>;
+    default: return nullptr;
     }
-    attention_count_launch(p.form);
-    return mdgat_check_hip(hipGetLastError(), "wide dynamic attention launch");
 }
+// the launcher's constants that live with the kernels: the LDS of attention_kernel for `keys` staged keys, of attention_topk16_kernel<.., NKEY>
+// (+ the tile counter) and of the wide kernels
+constexpr size_t attention_lds(int keys) { return ((size_t)keys * KROWH + (size_t)64 * (keys + 8)) * sizeof(_Float16); }
+constexpr size_t attention_topk16_lds(int nkey) { return ((size_t)2 * 4 * nkey * 8 + (size_t)64 * (nkey + 8)) * sizeof(_Float16) + 16; }
+constexpr size_t ATTENTION_WIDE_LDS = (size_t)(1040 + 8 * 18 * 64 + 4 * 8 * 64) * sizeof(float);
 
 // fp32 q/k/v [B][P][3][4][32] -> the split-f16 operand layouts above (per-op entry point and tests; the
 // forward's q/k/v projection writes these layouts directly from its epilogue)
@@ -1422,26 +1441,37 @@ extern "C" size_t mdgat_topk_sel_words(int B, int N, int M) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
     return (size_t)B * 4 * (N + M) * (((N > M ? N : M) + 31) / 32); }
 
-// ---- the launcher's choice as a pure function (mdgat_attention_plan; no HIP call), and the launches counted by it ----
+// ---- the launcher's choice as a pure function (mdgat_attention_plan, mdgat_attention_ragged_plan; no HIP call), and the launches counted by it ----
 static std::atomic<unsigned long long> attention_launch_count[ATTN_FORMS];
 void attention_count_launch(int form) { attention_launch_count[form].fetch_add(1, std::memory_order_relaxed); }
 void attention_launch_counts(uint64_t counts[MDGAT_ATTENTION_FORMS]) {
     for (int i = 0; i < ATTN_FORMS; ++i) counts[i] = attention_launch_count[i].load(std::memory_order_relaxed);
 }
 
-AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
-    if (B <= 0 || N <= 0 || M <= 0) return AttnPlan{-1, 0, 0, MDGAT_OK};
+// A ragged batch (pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M): the form and the geometry follow the slots alone - never a count, so
+// a pair's launch does not depend on its companions' sizes - and are the uniform launch's for the slots, but: the mode is ignored, a layer with
+// topk > 0 is always dynamic (a pair whose frame has just k keys keeps them all inside the kernel; k against the counts is the caller's check),
+// and the stream and topk16 kernels, which take no counts, are never chosen.  Slots beyond 16 key blocks need `wide`.
+AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode, bool ragged, bool wide) {
+    AttnPlan p{-1, 0, 0, MDGAT_OK};
+    if (B <= 0 || (!ragged && (N <= 0 || M <= 0))) return p;
     const int nk_max = N > M ? N : M, nk_min = N < M ? N : M;
-    // torch.topk raises when k exceeds the number of keys of either direction (mdgat.py:202)
-    if (topk > nk_min) return AttnPlan{-1, 0, 0, MDGAT_ERR_BAD_ARG};
-    // k == number of keys on both sides keeps every key: identical to full attention
-    const bool dyn = topk > 0 && !(topk == N && topk == M);
-    const bool fast = mode == 1;
+    // a ragged batch is refused by its slots; else torch.topk raises when k exceeds the number of keys of either direction (mdgat.py:202)
+    if (ragged ? N <= 0 || M <= 0 || topk < 0 || nk_max > (wide ? MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS : MDGAT_RAGGED_FP32_MAX_KEYPOINTS) : topk > nk_min) {
+        p.rc = MDGAT_ERR_BAD_ARG;
+        return p;
+    }
+    // uniform: k == number of keys on both sides keeps every key: identical to full attention
+    p.dyn = topk > 0 && (ragged || !(topk == N && topk == M));
+    const bool fast = !ragged && mode == 1;
     const int nblk = (nk_max + 31) / 32;
     const int units = B * 2 * MDGAT_HEADS;
-    if (!dyn && attention_stream_supported(N, M)) return AttnPlan{fast ? ATTN_STREAM_FAST : ATTN_STREAM, attention_stream_qtiles(N, M), 1, MDGAT_OK};
+    if (!ragged && !p.dyn && attention_stream_supported(N, M)) {
+        p.form = fast ? ATTN_STREAM_FAST : ATTN_STREAM; p.split = attention_stream_qtiles(N, M); p.tiles = 1;
+        return p;
+    }
     // attention_kernel: one workgroup per (pair, frame, head) loops over its query tiles (32 queries per wave); split the tiles over
-    // more workgroups only when there are too few (pair, frame, head) units to fill the chip twice
+    // more workgroups only when there are too few (pair, frame, head) units to fill the chip twice.  LDS: all keys, or a window of 512
     auto go = [&](int form, int threads) {
         const int qt = (threads / 64) * 32;
         const int qtiles = (nk_max + qt - 1) / qt;
@@ -1449,7 +1479,10 @@ AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
         if (qsplit > qtiles) qsplit = qtiles;
         if (qsplit < 1) qsplit = 1;
         if (nk_max > 512) qsplit = qtiles;     // windowed kernel: every pass re-stages its keys anyway
-        return AttnPlan{form, qsplit, (qtiles + qsplit - 1) / qsplit, MDGAT_OK};
+        p.form = form; p.split = qsplit; p.tiles = (qtiles + qsplit - 1) / qsplit;
+        p.threads = threads; p.lds = attention_lds(nblk > 16 ? 512 : nblk * 32); p.lds_attribute = true;
+        if (ragged && nk_max > 512) p.wide_counter = RAGGED_WIDE_ATTN_WINDOWED;
+        return p;
     };
     // exactly 512 (or 256) keys in both frames: one wave = 16 queries, the row in four lanes
     auto go16 = [&](int form, int nkey) {
@@ -1460,179 +1493,76 @@ AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode) {
         if (qsplit > qmax) qsplit = qmax;
         if (fast) form += ATTN_TOPK16_256_FAST - ATTN_TOPK16_256 + (tap ? ATTN_FAST_TAP : 0);
         else if (tap) form += ATTN_TAP;
-        return AttnPlan{form, qsplit, (nkey / 16 + qsplit - 1) / qsplit, MDGAT_OK};
+        p.form = form; p.split = qsplit; p.tiles = (nkey / 16 + qsplit - 1) / qsplit;
+        p.threads = 512; p.lds = attention_topk16_lds(nkey); p.lds_attribute = true; p.xcd_grid = true;
+        return p;
     };
-    if (!dyn) {
+    if (!p.dyn) {
         // chunks of 8 blocks (256 keys), two waves per SIMD
         if (nblk <= 4) return go(ATTN_FULL4, 512);
         if (nblk > 16) return go(ATTN_FULL8_WINDOWED, 512);
         return go(ATTN_FULL8, 512);
     }
     // the whole row in one chunk
-    if (N == 256 && M == 256) return go16(ATTN_TOPK16_256, 256);
-    if (tap && !(N == 512 && M == 512) && nblk <= 16)
-        return nblk <= 4 ? go(ATTN_DYN4 + ATTN_TAP, 512) : nblk <= 8 ? go(ATTN_DYN8 + ATTN_TAP, 512) : go(ATTN_DYN16 + ATTN_TAP, 256);
-    if (nblk <= 4) return go(ATTN_DYN4, 512);
-    if (nblk <= 8) return go(ATTN_DYN8, 512);
-    if (N == 512 && M == 512) return go16(ATTN_TOPK16_512, 512);
-    if (nblk <= 16) return go(ATTN_DYN16, 256);
-    if (nblk > 64) return AttnPlan{-1, 0, 0, MDGAT_ERR_UNSUPPORTED};
-    // wide kernels: a workgroup pass is 64 (four waves per tile) or 32 (eight) queries, one workgroup per pass of the larger frame
-    const int per_pass = nblk <= 32 ? 64 : 32;
-    const int npass = (nk_max + per_pass - 1) / per_pass;
-    return AttnPlan{(nblk <= 32 ? ATTN_WIDE4 : ATTN_WIDE8) + (tap ? ATTN_TAP : 0), npass, 1, MDGAT_OK};
-}
-
-// A ragged batch: pair b has cnt0[b] / cnt1[b] keypoints in slots of N / M <= 512 (counts checked by the caller against topk).  The form
-// follows the slots alone - never a count, so a pair's launch geometry does not depend on its companions' sizes: attention_kernel's RAGGED
-// instantiation for the slots' 32-key blocks, a dynamic layer always a dynamic one (a pair whose frame has just k keys keeps them all inside
-// the kernel).  The stream and topk16 kernels take no counts; the windowed and wide ones serve slots beyond 512 (launch_attention_ragged_wide).
-// Counted under the uniform sibling's form.
-int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
-                            uint32_t* sel) {
-    if (B <= 0) return MDGAT_OK;
-    const int nk_max = N > M ? N : M;
-    if (!cnt0 || !cnt1 || N <= 0 || M <= 0 || topk < 0 || nk_max > MDGAT_RAGGED_FP32_MAX_KEYPOINTS) {
-        mdgat_set_error("attention (ragged): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", N, M, topk, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
-        return MDGAT_ERR_BAD_ARG;
+    if (!ragged && N == 256 && M == 256) return go16(ATTN_TOPK16_256, 256);
+    if (!ragged && N == 512 && M == 512) return go16(ATTN_TOPK16_512, 512);
+    const int tapped = tap ? ATTN_TAP : 0;
+    if (nblk <= 4) return go(ATTN_DYN4 + tapped, 512);
+    if (nblk <= 8) return go(ATTN_DYN8 + tapped, 512);
+    if (nblk <= 16) return go(ATTN_DYN16 + tapped, 256);
+    if (nblk > 64) {
+        p.rc = MDGAT_ERR_UNSUPPORTED;
+        return p;
     }
-    const bool dyn = topk > 0, tap = dyn && sel;
-    const int nblk = (nk_max + 31) / 32;
-    const int form = !dyn ? (nblk <= 4 ? ATTN_FULL4 : ATTN_FULL8) : (nblk <= 4 ? ATTN_DYN4 : nblk <= 8 ? ATTN_DYN8 : ATTN_DYN16) + (tap ? ATTN_TAP : 0);
-    const int threads = dyn && nblk > 8 ? 256 : 512;
-    // the query tiles of a (pair, frame, head) over more workgroups only when there are too few units to fill the chip twice (attention_plan)
-    const int qt = (threads / 64) * 32, qtiles = (nk_max + qt - 1) / qt, units = B * 2 * MDGAT_HEADS;
-    int split = (512 + units - 1) / units;
-    split = split > qtiles ? qtiles : split;
-    AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, nblk, 0, 0, cnt0, cnt1};
-    if (sel && dyn) {
-        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, 0, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
-        a.sel = sel;
-    }
-    const size_t lds = ((size_t)nblk * 32 * KROWH + (size_t)64 * (nblk * 32 + 8)) * sizeof(_Float16);
-    auto go = [&](auto kern) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(split, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
-    };
-    switch (form) {
-    case ATTN_FULL4: go(attention_kernel<false, 4, false, false, true>); break;
-    case ATTN_FULL8: go(attention_kernel<false, 8, false, false, true>); break;
-    case ATTN_DYN4: go(attention_kernel<true, 4, false, false, true>); break;
-    case ATTN_DYN8: go(attention_kernel<true, 8, false, false, true>); break;
-    case ATTN_DYN16: go(attention_kernel<true, 16, false, false, true>); break;
-    case ATTN_DYN4 + ATTN_TAP: go(attention_kernel<true, 4, false, true, true>); break;
-    case ATTN_DYN8 + ATTN_TAP: go(attention_kernel<true, 8, false, true, true>); break;
-    default: go(attention_kernel<true, 16, false, true, true>); break;
-    }
-    attention_count_launch(form);
-    return mdgat_check_hip(hipGetLastError(), "attention launch (ragged)");
-}
-
-// The same in WIDE slots, up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS per frame.  Slots of at most 16 key blocks run launch_attention_ragged: what
-// they run without the switch.  Beyond, from the slots alone: full attention on the windowed kernel's RAGGED instantiation, a dynamic layer on
-// the wide kernel's - four waves per tile up to 32 key blocks, eight up to 64 - with the uniform launch's geometry for the slots.  Counted under
-// the uniform sibling's form and, apart, as a ragged-wide launch (ragged_wide_count_launch).
-int launch_attention_ragged_wide(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg,
-                                 hipStream_t s, uint32_t* sel) {
-    if (B <= 0) return MDGAT_OK;
-    const int nk_max = N > M ? N : M;
-    const int nblk = (nk_max + 31) / 32;
-    if (nblk <= 16) return launch_attention_ragged(B, N, M, cnt0, cnt1, cross, topk, qkv, msg, s, sel);
-    if (!cnt0 || !cnt1 || N <= 0 || M <= 0 || topk < 0 || nk_max > MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS) {
-        mdgat_set_error("attention (ragged, wide): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", N, M, topk, MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    const bool dyn = topk > 0, tap = dyn && sel;
-    AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, nblk, 0, 0, cnt0, cnt1};
-    if (!dyn) {
-        // the windowed kernel: 256 queries per workgroup pass, a workgroup per pass of the larger slot (attention_plan), a window of 512 keys
-        const int qtiles = (nk_max + 255) / 256;
-        const size_t lds = ((size_t)512 * KROWH + (size_t)64 * (512 + 8)) * sizeof(_Float16);
-        const auto kern = attention_kernel<false, 8, true, false, true>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(qtiles, MDGAT_HEADS, B * 2), dim3(512), lds, s, a);
-        attention_count_launch(ATTN_FULL8_WINDOWED);
-        ragged_wide_count_launch(RAGGED_WIDE_ATTN_WINDOWED);
-        return mdgat_check_hip(hipGetLastError(), "attention launch (ragged, windowed)");
-    }
-    if (tap) {
-        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, 0, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
-        a.sel = sel;
-    }
-    // the wide kernels: a workgroup pass is 64 (four waves per tile) or 32 (eight) queries, one workgroup per pass of the larger slot (attention_plan)
+    // wide kernels: a workgroup pass is 64 (four waves per tile, up to 32 key blocks) or 32 (eight) queries, one workgroup per pass of the larger frame
     const bool w4 = nblk <= 32;
     const int per_pass = w4 ? 64 : 32;
-    a.grid_units = B * 2 * MDGAT_HEADS;
-    a.grid_split = (nk_max + per_pass - 1) / per_pass;
-    const size_t lds = (size_t)(1040 + 8 * 18 * 64 + 4 * 8 * 64) * sizeof(float);      // (launch_attention_topk_wide)
-    const dim3 grid(8 * a.grid_split * ((a.grid_units + 7) / 8));
-    if (w4 && !tap) hipLaunchKernelGGL((attention_topk_wide_kernel<4, false, true>), grid, dim3(512), lds, s, a);
-    else if (w4) hipLaunchKernelGGL((attention_topk_wide_kernel<4, true, true>), grid, dim3(512), lds, s, a);
-    else if (!tap) hipLaunchKernelGGL((attention_topk_wide_kernel<8, false, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((attention_topk_wide_kernel<8, true, true>), grid, dim3(512), lds, s, a);
-    attention_count_launch((w4 ? ATTN_WIDE4 : ATTN_WIDE8) + (tap ? ATTN_TAP : 0));
-    ragged_wide_count_launch((w4 ? RAGGED_WIDE_ATTN_WIDE4 : RAGGED_WIDE_ATTN_WIDE8) + (tap ? 1 : 0));
-    return mdgat_check_hip(hipGetLastError(), "attention launch (ragged, wide)");
+    p.form = (w4 ? ATTN_WIDE4 : ATTN_WIDE8) + tapped; p.split = (nk_max + per_pass - 1) / per_pass; p.tiles = 1;
+    p.threads = 512; p.lds = ATTENTION_WIDE_LDS; p.xcd_grid = true;
+    if (ragged) p.wide_counter = (w4 ? RAGGED_WIDE_ATTN_WIDE4 : RAGGED_WIDE_ATTN_WIDE8) + (tap ? 1 : 0);
+    return p;
 }
 
-int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode, uint32_t* sel) {
-    if (B <= 0 || N <= 0 || M <= 0) return MDGAT_OK;
-    const int nk_max = N > M ? N : M;
-    const bool dyn = topk > 0 && !(topk == N && topk == M);
-    const AttnPlan p = attention_plan(B, N, M, topk, sel && dyn, mode);
+// The one launcher: the plan, the refusals, the tap's memset, the arguments, the instantiation, the launch, its counters.  A ragged launch is
+// counted under its uniform sibling's form and, where only a wide slot reaches it, apart as a ragged-wide launch (ragged_wide_count_launch).
+int launch_attention(const AttnCall& c) {
+    const bool ragged = c.cnt0 || c.cnt1;
+    const int nk_max = c.N > c.M ? c.N : c.M, nblk = (nk_max + 31) / 32, units = c.B * 2 * MDGAT_HEADS;
+    const AttnPlan p = attention_plan(c.B, c.N, c.M, c.topk, c.sel != nullptr, c.mode, ragged, c.wide);
+    if (p.form < 0 && p.rc == MDGAT_OK) return MDGAT_OK;
+    if (ragged && (p.rc || !c.cnt0 || !c.cnt1)) {
+        if (c.wide && nblk > 16)
+            mdgat_set_error("attention (ragged, wide): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", c.N, c.M, c.topk, MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS);
+        else mdgat_set_error("attention (ragged): bad shape N=%d M=%d topk=%d (slots of at most %d keypoints)", c.N, c.M, c.topk, MDGAT_RAGGED_FP32_MAX_KEYPOINTS);
+        return MDGAT_ERR_BAD_ARG;
+    }
     if (p.rc == MDGAT_ERR_BAD_ARG) {
-        mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", topk, N < M ? N : M);
+        mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", c.topk, c.N < c.M ? c.N : c.M);
         return p.rc;
     }
-    AttnArgs a{qkv.q16, qkv.k16, qkv.vt16, msg, N, M, qkv.Npad, qkv.PP, cross, topk, 0.f, nullptr, (nk_max + 31) / 32};
-    if (topk > 0) a.zq = normal_quantile_upper(((double)topk - 0.5) / (double)nk_max);
-    const int nkp = ((nk_max + 31) / 32) * 32;
-    const int wkeys = nkp > 512 ? 512 : nkp;      // keys the LDS window holds
-    const size_t lds = ((size_t)wkeys * KROWH + (size_t)64 * (wkeys + 8)) * sizeof(_Float16);
-    if (sel && topk > 0) {
-        // parity tap: the kept keys of every (pair, head, query) as a bit mask; k == number of keys keeps them all
-        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, dyn ? 0 : 0xff, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
-        if (dyn) a.sel = sel;
+    AttnArgs a{c.qkv.q16, c.qkv.k16, c.qkv.vt16, c.msg, c.N, c.M, c.qkv.Npad, c.qkv.PP, c.cross, c.topk, 0.f, nullptr, nblk, 0, 0, c.cnt0, c.cnt1};
+    // the first probe of the threshold search (a RAGGED instantiation computes it per pair on the device)
+    if (!ragged && c.topk > 0) a.zq = normal_quantile_upper(((double)c.topk - 0.5) / (double)nk_max);
+    if (c.sel && c.topk > 0) {
+        // parity tap: the kept keys of every (pair, head, query) as a bit mask; a uniform k == number of keys keeps them all
+        if (int rc = mdgat_check_hip(hipMemsetAsync(c.sel, p.dyn ? 0 : 0xff, mdgat_topk_sel_words(c.B, c.N, c.M) * sizeof(uint32_t), c.stream), "memset(top-k tap)")) return rc;
+        if (p.dyn) a.sel = c.sel;
     }
     if (p.rc == MDGAT_ERR_UNSUPPORTED) {
         mdgat_set_error("dynamic attention: %d keys per frame > 2048 supported", nk_max);
         return p.rc;
     }
-    if (p.form == ATTN_STREAM || p.form == ATTN_STREAM_FAST) return launch_attention_stream(B, N, M, cross, qkv, msg, s, mode);
-    auto go = [&](auto kern, int threads) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(p.split, MDGAT_HEADS, B * 2), dim3(threads), lds, s, a);
-    };
-    auto launch16 = [&](auto nkc) {
-        constexpr int NKEY = decltype(nkc)::value;
-        const size_t lds3 = ((size_t)2 * 4 * NKEY * 8 + (size_t)64 * (NKEY + 8)) * sizeof(_Float16) + 16;    // + the tile counter
-        AttnArgs w = a;
-        w.grid_split = p.split;
-        w.grid_units = B * 2 * MDGAT_HEADS;
-        auto run = [&](auto kern) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-            hipLaunchKernelGGL(kern, dim3(8 * p.split * ((w.grid_units + 7) / 8)), dim3(512), lds3, s, w);
-        };
-        if (a.sel) { if (mode == 1) run(attention_topk16_kernel<true, true, NKEY>); else run(attention_topk16_kernel<false, true, NKEY>); }
-        else if (mode == 1) run(attention_topk16_kernel<true, false, NKEY>);
-        else run(attention_topk16_kernel<false, false, NKEY>);
-    };
-    switch (p.form) {
-    case ATTN_FULL4: go(attention_kernel<false, 4, false>, 512); break;
-    case ATTN_FULL8: go(attention_kernel<false, 8, false>, 512); break;
-    case ATTN_FULL8_WINDOWED: go(attention_kernel<false, 8, true>, 512); break;
-    case ATTN_DYN4: go(attention_kernel<true, 4, false>, 512); break;
-    case ATTN_DYN8: go(attention_kernel<true, 8, false>, 512); break;
-    case ATTN_DYN16: go(attention_kernel<true, 16, false>, 256); break;
-    case ATTN_DYN4 + ATTN_TAP: go(attention_kernel<true, 4, false, true>, 512); break;
-    case ATTN_DYN8 + ATTN_TAP: go(attention_kernel<true, 8, false, true>, 512); break;
-    case ATTN_DYN16 + ATTN_TAP: go(attention_kernel<true, 16, false, true>, 256); break;
-    case ATTN_TOPK16_256: case ATTN_TOPK16_256 + ATTN_TAP: case ATTN_TOPK16_256_FAST: case ATTN_TOPK16_256_FAST + ATTN_FAST_TAP:
-        launch16(std::integral_constant<int, 256>{}); break;
-    case ATTN_TOPK16_512: case ATTN_TOPK16_512 + ATTN_TAP: case ATTN_TOPK16_512_FAST: case ATTN_TOPK16_512_FAST + ATTN_FAST_TAP:
-        launch16(std::integral_constant<int, 512>{}); break;
-    default: return launch_attention_topk_wide(a, B, p, s);
-    }
+    if (p.form == ATTN_STREAM || p.form == ATTN_STREAM_FAST) return launch_attention_stream(c.B, c.N, c.M, c.cross, c.qkv, c.msg, c.stream, c.mode);
+    const AttnKernel kern = attention_instantiation(p.form, ragged);
+    if (!kern) { mdgat_set_error("attention: no kernel of form %d for a %s batch", p.form, ragged ? "ragged" : "uniform"); return MDGAT_ERR_UNSUPPORTED; }
+    if (p.xcd_grid) { a.grid_split = p.split; a.grid_units = units; }
+    const dim3 grid = p.xcd_grid ? dim3(8 * p.split * ((units + 7) / 8)) : dim3(p.split, MDGAT_HEADS, c.B * 2);
+    if (p.lds_attribute) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    hipLaunchKernelGGL(kern, grid, dim3(p.threads), p.lds, c.stream, a);
     attention_count_launch(p.form);
-    return mdgat_check_hip(hipGetLastError(), "attention launch");
+    if (p.wide_counter >= 0) ragged_wide_count_launch(p.wide_counter);
+    return mdgat_check_hip(hipGetLastError(), !ragged ? (p.lds_attribute ? "attention launch" : "wide dynamic attention launch")
+                                              : p.wide_counter < 0 ? "attention launch (ragged)"
+                                              : p.dyn ? "attention launch (ragged, wide)" : "attention launch (ragged, windowed)");
 }
+

@@ -167,20 +167,21 @@ struct Qkv16 {
 size_t mdgat_qkv16_halves(int B, int N, int M);
 Qkv16 mdgat_qkv16_carve(_Float16* base, int B, int N, int M);
 int launch_qkv_split(int B, int N, int M, const float* qkv, const Qkv16& out, hipStream_t s);
-// mode: mdgat_attention_mode (1 = single-f16 products where implemented)
-// sel (parity tap, may be NULL): the kept keys of a dynamic layer as bit masks [B][4][P][W], W = ceil(max(N, M) / 32)
-int launch_attention(int B, int N, int M, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s, int mode = 0, uint32_t* sel = nullptr);
-// The same on a ragged batch: pair b has cnt0[b] / cnt1[b] keypoints (device int32 [B], checked by the caller against topk) in slots of
-// N / M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS.  The general kernel's ragged instantiations, chosen from the slots alone and counted under their
-// uniform siblings' forms; message rows (and tap masks) beyond a pair's counts are zero.
-int launch_attention_ragged(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
-                            uint32_t* sel = nullptr);
-// ... in slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS: beyond 16 key blocks the RAGGED instantiations of the windowed kernel (full attention) and
-// of the wide kernels (a dynamic layer), again from the slots alone; counted under the uniform sibling's form and as a ragged-wide launch
-int launch_attention_ragged_wide(int B, int N, int M, const int* cnt0, const int* cnt1, int cross, int topk, const Qkv16& qkv, float* msg, hipStream_t s,
-                                 uint32_t* sel = nullptr);
-// Which instantiation launch_attention runs and its launch geometry (mdgat_attention_plan, include/mdgat_hip.h: the table of indices), and
-// how often each has been launched by this process (mdgat_attention_launches).  Host code only; the plan touches no HIP call.
+// One fp32-class attention call (attention.hip).  Zero-initialise it and set what applies.
+struct AttnCall {
+    int B, N, M, cross, topk;
+    int mode;                           // mdgat_attention_mode (1 = single-f16 products where implemented); a ragged batch always runs the split-f16 kernels
+    Qkv16 qkv; float* msg;              // msg [B][N + M][128]
+    uint32_t* sel;                      // parity tap, may be null: the kept keys of a dynamic layer as bit masks [B][4][P][W], W = ceil(max(N, M) / 32)
+    const int *cnt0, *cnt1;             // both or neither (device int32 [B], checked by the caller against topk): a ragged batch - pair b has cnt0[b] / cnt1[b] keypoints
+                                        // in slots of N / M <= MDGAT_RAGGED_FP32_MAX_KEYPOINTS (`wide`: _WIDE_MAX_); message rows (and tap masks) beyond a pair's counts are zero
+    bool wide;                          // a ragged batch only: the caller opted in to slots of up to MDGAT_RAGGED_FP32_WIDE_MAX_KEYPOINTS (slots within 512 x 512 run what they run without)
+    hipStream_t stream;
+};
+int launch_attention(const AttnCall& c);
+// What launch_attention chooses (mdgat_attention_plan, mdgat_attention_ragged_plan; include/mdgat_hip.h: the table of indices) - the instantiation
+// and all of its launch but the pointers - and how often each has been launched by this process (mdgat_attention_launches).  Host code only; the plan
+// touches no HIP call.  A ragged call's form follows the slots alone, never a count or B, and is counted under its uniform sibling's index.
 enum AttnForm {
     ATTN_STREAM = 0, ATTN_FULL4, ATTN_FULL8, ATTN_FULL8_WINDOWED, ATTN_DYN4, ATTN_DYN8, ATTN_DYN16, ATTN_TOPK16_256, ATTN_TOPK16_512, ATTN_WIDE4,
     ATTN_WIDE8, ATTN_TAP = 7 /* + ATTN_DYN4 .. ATTN_WIDE8 */, ATTN_STREAM_FAST = 18, ATTN_TOPK16_256_FAST, ATTN_TOPK16_512_FAST,
@@ -190,8 +191,15 @@ struct AttnPlan {
     int form;           // AttnForm, or -1: no launch
     int split, tiles;   // workgroups per (pair, frame, head); the most query tiles one of them walks
     int rc;             // why not, where the launcher refuses (MDGAT_OK otherwise; the message is the launcher's)
+    bool dyn = false;           // the layer keeps its k largest logits (uniform: unless k keeps every key of both frames; ragged: whenever topk > 0)
+    int threads = 0;            // of a workgroup; the stream forms: launch_attention_stream's own, as their LDS
+    size_t lds = 0;             // dynamic LDS bytes
+    bool lds_attribute = false; // hipFuncSetAttribute(MaxDynamicSharedMemorySize) goes before the launch: every kernel but the wide ones
+    bool xcd_grid = false;      // the XCD-aware 1-D grid of the topk16 and wide kernels (8 * split * ceil(units / 8)); else the 3-D grid (split, heads, 2 B)
+    int wide_counter = -1;      // RaggedWideCounter of a launch only a wide ragged slot reaches
 };
-AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode);
+// tap: a selection buffer is passed; ragged: a call with counts; wide: AttnCall::wide (a ragged call only)
+AttnPlan attention_plan(int B, int N, int M, int topk, bool tap, int mode, bool ragged = false, bool wide = false);
 void attention_count_launch(int form);
 void attention_launch_counts(uint64_t counts[MDGAT_ATTENTION_FORMS]);
 // full attention as a stream of 64-key chunks (attention_stream.hip); frames with key counts that are multiples of 64

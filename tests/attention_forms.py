@@ -1,6 +1,6 @@
-"""The 23 instantiations launch_attention (csrc/attention.hip, csrc/attention_stream.hip) can reach, as the tests name them, and the two
-symbols that make the launcher's choice observable: mdgat_attention_plan (the choice and its launch geometry as a pure function; no
-device) and mdgat_attention_launches (launches so far by index).  The table of indices: include/mdgat_hip.h.
+"""The 23 instantiations launch_attention (csrc/attention.hip, csrc/attention_stream.hip) can reach, as the tests name them, and the
+symbols that make the launcher's choice observable: mdgat_attention_plan and, for a ragged batch, mdgat_attention_ragged_plan (the choice
+and its launch geometry as a pure function; no device) and mdgat_attention_launches (launches so far by index).  The table of indices: include/mdgat_hip.h.
 
 mode 0 (split-f16): 0 stream, 1-3 the full forms of attention_kernel, 4-10 the dynamic kernels, 11-17 their TAP twins (a selection buffer
 is passed); mode 1 (F16): 18-22 the FAST twins of the kernels that have one (stream, topk16 and its TAP twin)."""
@@ -36,6 +36,19 @@ def plan(B, N, M, topk=0, tap=False, mode=0):
     (pair, frame, head), and the most query tiles one of them walks."""
     split, tiles = C.c_int(-7), C.c_int(-7)
     form = _lib().mdgat_attention_plan(B, N, M, topk, int(tap), mode, C.byref(split), C.byref(tiles))
+    return form, split.value, tiles.value
+
+
+# the forms whose kernel has a RAGGED instantiation (a call with counts); WIDE_ONLY: those only a slot beyond 512 keypoints reaches
+RAGGED = ('full<4>', 'full<8>', 'full<8,windowed>', 'dyn<4>', 'dyn<8>', 'dyn<16>', 'wide<4>', 'wide<8>')
+RAGGED_WIDE_ONLY = ('full<8,windowed>', 'wide<4>', 'wide<8>')
+
+
+def ragged_plan(B, Np, Mp, topk=0, tap=False, wide=False):
+    """(form, split, tiles) launch_attention chooses for a ragged batch in slots of Np x Mp (mdgat_attention_ragged_plan): the index is the
+    uniform sibling's, the kernel its RAGGED instantiation."""
+    split, tiles = C.c_int(-7), C.c_int(-7)
+    form = _lib().mdgat_attention_ragged_plan(B, Np, Mp, topk, int(tap), int(wide), C.byref(split), C.byref(tiles))
     return form, split.value, tiles.value
 
 

@@ -116,6 +116,7 @@ EXEMPT = {
     'mdgat_layer_plan': ('a plan', 'the layer launcher\'s choice as a pure function'),
     'mdgat_sinkhorn_plan': ('a plan', 'the Sinkhorn launchers\' choice as a pure function; the workspace address is never dereferenced'),
     'mdgat_attention_plan': ('a plan', 'the attention launcher\'s choice as a pure function'),
+    'mdgat_attention_ragged_plan': ('a plan', 'the attention launcher\'s choice for a ragged batch as a pure function'),
     'mdgat_gemm_f64_plan': ('a plan', 'the fp64 GEMM launcher\'s choice as a pure function'),
     'mdgat_attention_f64_plan': ('a plan', 'the fp64 attention launcher\'s choice as a pure function'),
     'mdgat_layer_f64_plan': ('a plan', 'the fp64 layer-tail and encoder launchers\' choice as a pure function'),
