@@ -928,10 +928,16 @@ void mdgat_gemm_f64_launches(uint64_t counts[10]);
  * `form` as mdgat_set_f64_attention_form takes it (-1 by launch size, 0, 1), on a device of `cus` compute units.  topk == N == M is full
  * attention unless ragged.  A pure function of its arguments: no device is needed or touched.  Negative: no launch - -1 an empty one,
  * -2 / -3 what the launcher refuses (k above the smallest key count or bad counts / more than 2048 keys in a dynamic layer).
+ * mdgat_attention_f64_geometry: the same index, and the launch it stands for: the queries of a workgroup (16, 32, or 128 where a wave owns 32),
+ * the query tiles of a (pair, frame, head) = ceil(max(N, M) / queries), the grid = 8 * tiles * B workgroups of 256 threads (eight (frame, head) units per pair), and
+ * the launch's dynamic LDS bytes.  Each output may be null; all are 0 where nothing is launched.
  * mdgat_attention_f64_launches: counts[i] = launches of instantiation i by this process so far, on any device and stream (relaxed atomic
  * counters, never reset: read them before and after a call and subtract). */
+#define MDGAT_ATTENTION_F64_FORMS 7
 int mdgat_attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus);
-void mdgat_attention_f64_launches(uint64_t counts[7]);
+int mdgat_attention_f64_geometry(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus, int* queries, int* tiles,
+                                 int* workgroups, size_t* lds_bytes);
+void mdgat_attention_f64_launches(uint64_t counts[MDGAT_ATTENTION_F64_FORMS]);
 /* The same on a RAGGED batch: pair b has counts0[b] / counts1[b] keypoints in slots padded to Np / Mp (qkv [B][Np+Mp][384], frame 1 from row
  * Np on; msg and sel likewise, sel with the words of mdgat_topk_sel_words(B, Np, Mp)).  Queries and keys beyond a pair's counts take no part
  * and are never read; their message rows and selection words are zero.  A pair's rows are those of mdgat_attention_f64 on the pair alone -

@@ -200,6 +200,7 @@ SIGNATURES = {
     'mdgat_gemm_f64_plan': (C.c_int, [C.c_int] * 8),
     'mdgat_gemm_f64_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_attention_f64_plan': (C.c_int, [C.c_int] * 9),
+    'mdgat_attention_f64_geometry': (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_size_t)]),
     'mdgat_attention_f64_launches': (None, [C.POINTER(C.c_uint64)]),
     'mdgat_layer_f64_plan': (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int)] * 2),
     'mdgat_layer_f64_launches': (None, [C.POINTER(C.c_uint64)]),

@@ -740,10 +740,10 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
     // 32 + 64 + 128 + 64 + 128 = 416 of the 603 doubles per point there
     double* in4 = ws.hid64 + Rz * (256 - 37);
     double* in33 = in4 + Rz * 4;
-    if (int rc = in.bank ? launch_assemble_frames_ragged_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.bank.start0, in.bank.start1, f.cnt0, f.cnt1, in.normalize_fpfh, in4,
-                                                             in33, in.kp0_out, in.kp1_out, f.guard(), f.s)
-               : in.rec0 ? launch_assemble_frames_f64(f.B, f.N, f.M, in.rec0, in.rec1, in.normalize_fpfh, in4, in33, f.guard(), f.s)
-                         : launch_assemble_f64(f.B, f.N, f.M, in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in4, in33, f.guard(), f.s, f.cnt0, f.cnt1)) return rc;
+    AssembleF64 as{in.dk0, in.ds0, in.df0, in.dk1, in.ds1, in.df1, in.rec0, in.rec1, in.normalize_fpfh, f.cnt0, f.cnt1};
+    as.start0 = in.bank.start0; as.start1 = in.bank.start1; as.kp0 = in.kp0_out; as.kp1 = in.kp1_out;
+    as.in4 = in4; as.in33 = in33; as.B = f.B; as.N = f.N; as.M = f.M; as.guard = f.guard();
+    if (int rc = launch_assemble_f64(as, f.s)) return rc;
     f.mark(MDGAT_PROF_F64_OTHER);
     // KeypointEncoder (mdgat.py:184-188), DescriptorEncoder (152-155), their sum (392-393) as one product over [hd ; hk]
     if (f.h->pool64) {
@@ -774,7 +774,7 @@ static int head64(Fwd& f, const FwdIn& in, CoopGroup& coop) {
             f.mark(MDGAT_PROF_F64_GEMM);
         }
         const int kk = f.h->cfg.topk[i];
-        if (int rc = launch_attention_f64(f.B, f.N, f.M, i & 1, kk, ws.qkv64, ws.msg64, f.sel_tap(i), f.s, f.guard(), f.cnt0, f.cnt1, f.cnt_min)) return rc;
+        if (int rc = launch_attention_f64(AttnF64Call{f.B, f.N, f.M, i & 1, kk, ws.qkv64, ws.msg64, f.sel_tap(i), f.cnt0, f.cnt1, f.cnt_min, f.guard(), f.s})) return rc;
         f.mark(kk > 0 ? MDGAT_PROF_F64_ATTENTION_TOPK : MDGAT_PROF_F64_ATTENTION_FULL);
         // AttentionalPropagation + residual (mdgat.py:246-248, 274)
         if (f.p.fused64) {
@@ -1077,8 +1077,11 @@ extern "C" int mdgat_assemble_frames_f64_ragged(int B, int Np, int Mp, const int
     if (B < 0 || Np <= 0 || Mp <= 0 || rows0 < 0 || rows1 < 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d", who, B, Np, Mp); return MDGAT_ERR_BAD_ARG; }
     const RaggedStarts bank = ragged_starts(starts0, starts1, starts0_host, starts1_host, rows0, rows1);
     if (int rc = mdgat_check_ragged(who, B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, &bank, nullptr, 0, nullptr)) return rc;
-    return launch_assemble_frames_ragged_f64(B, Np, Mp, rec0, rec1, bank.start0, bank.start1, counts0, counts1, normalize_fpfh, in4, in33, kpts0_out, kpts1_out,
-                                             guard, static_cast<hipStream_t>(stream));
+    AssembleF64 as{};      // (the starts are not null - mdgat_check_ragged refuses that with a bank - so this is the launch of the bank kernel)
+    as.rec0 = rec0; as.rec1 = rec1; as.normalize = normalize_fpfh; as.cnt0 = counts0; as.cnt1 = counts1;
+    as.start0 = bank.start0; as.start1 = bank.start1; as.kp0 = kpts0_out; as.kp1 = kpts1_out;
+    as.in4 = in4; as.in33 = in33; as.B = B; as.N = Np; as.M = Mp; as.guard = guard;
+    return launch_assemble_f64(as, static_cast<hipStream_t>(stream));
 }
 
 // The loader's train-mode assembly of a chunk (ensure_kpts_num): the saliency filter and the pad / truncate to T in front of the same decode.
@@ -1500,10 +1503,20 @@ extern "C" void mdgat_gemm_f64_launches(uint64_t counts[10]) {
 }
 
 extern "C" int mdgat_attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus) {
-    return attention_f64_plan_index(B, N, M, topk, tap, ragged, cnt_min, form, cus);
+    return attention_f64_plan(B, N, M, topk, tap, ragged, cnt_min, form, cus).form;
 }
 
-extern "C" void mdgat_attention_f64_launches(uint64_t counts[7]) {
+extern "C" int mdgat_attention_f64_geometry(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus, int* queries, int* tiles,
+                                            int* workgroups, size_t* lds_bytes) {
+    const AttnF64Plan p = attention_f64_plan(B, N, M, topk, tap, ragged, cnt_min, form, cus);
+    if (queries) *queries = p.queries;
+    if (tiles) *tiles = p.tiles;
+    if (workgroups) *workgroups = p.workgroups;
+    if (lds_bytes) *lds_bytes = p.lds;
+    return p.form;
+}
+
+extern "C" void mdgat_attention_f64_launches(uint64_t counts[MDGAT_ATTENTION_F64_FORMS]) {
     if (counts) attention_f64_launch_counts(counts);
 }
 
@@ -1638,20 +1651,30 @@ extern "C" int mdgat_mlp_backward_f64(const mdgat_mlp_desc* d, const double* x0,
     return launch_mlp_backward_f64(*d, x0, x1, saved, dout, *grads, workspace, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
-    if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (topk < 0) { mdgat_set_error("mdgat_attention_f64: topk < 0"); return MDGAT_ERR_BAD_ARG; }
-    return launch_attention_f64(B, N, M, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream));
+// ONE body for the two fp64 attention entries, as attention_op is for the fp32-class ones.  counts: null for the uniform entry; a ragged batch
+// has them on the device for the kernel, on the host for the checks made before the launch.
+static int attention_f64_op(const char* who, AttnF64Call c, const RaggedCounts* counts) {
+    if (!c.qkv || !c.msg) { mdgat_set_error("%s: null pointer", who); return MDGAT_ERR_BAD_ARG; }
+    if (counts) {
+        if (c.topk < 0 || c.B < 0 || c.N <= 0 || c.M <= 0) { mdgat_set_error("%s: bad shape B=%d Np=%d Mp=%d topk=%d", who, c.B, c.N, c.M, c.topk); return MDGAT_ERR_BAD_ARG; }
+        if (int rc = mdgat_check_ragged(who, c.B, c.N, c.M, *counts, nullptr, &c.topk, 1, &c.cnt_min)) return rc;
+        c.cnt0 = counts->cnt0; c.cnt1 = counts->cnt1;
+    } else if (c.topk < 0) { mdgat_set_error("%s: topk < 0", who); return MDGAT_ERR_BAD_ARG; }
+    return launch_attention_f64(c);
 }
 
-// a ragged batch: the counts on the device for the kernel, on the host for the checks made before the launch
+extern "C" int mdgat_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
+    AttnF64Call c{B, N, M, cross, topk, qkv, msg, sel};
+    c.stream = static_cast<hipStream_t>(stream);
+    return attention_f64_op("mdgat_attention_f64", c, nullptr);
+}
+
 extern "C" int mdgat_attention_f64_ragged(int B, int Np, int Mp, const int32_t* counts0, const int32_t* counts1, const int32_t* counts0_host,
                                           const int32_t* counts1_host, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, void* stream) {
-    if (!qkv || !msg) { mdgat_set_error("mdgat_attention_f64_ragged: null pointer"); return MDGAT_ERR_BAD_ARG; }
-    if (topk < 0 || B < 0 || Np <= 0 || Mp <= 0) { mdgat_set_error("mdgat_attention_f64_ragged: bad shape B=%d Np=%d Mp=%d topk=%d", B, Np, Mp, topk); return MDGAT_ERR_BAD_ARG; }
-    int cmin = 0;
-    if (int rc = mdgat_check_ragged("mdgat_attention_f64_ragged", B, Np, Mp, RaggedCounts{counts0, counts1, counts0_host, counts1_host}, nullptr, &topk, 1, &cmin)) return rc;
-    return launch_attention_f64(B, Np, Mp, cross, topk, qkv, msg, sel, static_cast<hipStream_t>(stream), nullptr, counts0, counts1, cmin);
+    const RaggedCounts counts{counts0, counts1, counts0_host, counts1_host};
+    AttnF64Call c{B, Np, Mp, cross, topk, qkv, msg, sel};
+    c.stream = static_cast<hipStream_t>(stream);
+    return attention_f64_op("mdgat_attention_f64_ragged", c, &counts);
 }
 
 // ---- the backward of mdgat_attention_f64: csrc/attention_grad.hip ----

@@ -1001,125 +1001,107 @@ extern "C" int mdgat_set_f64_attention_form(int mode) {
     return prev;
 }
 
-// Which of attention_f64_kernel's seven instantiations a launch runs, as the index mdgat_attention_f64_plan returns and
-// mdgat_attention_f64_launches counts by (include/mdgat_hip.h): 0 full attention, 16 queries per workgroup; 1 full, 32 queries;
-// 2 dynamic, at most 512 keys (KEEP), with the selection tap; 3 the same without; 4 dynamic beyond 512 keys (recomputing) with the
-// tap; 5 without; 6 full, one wave per 32 queries.  Pure: no HIP call.  Negative: no launch - -1 nothing to do, -2 / -3 what the
-// launcher refuses as MDGAT_ERR_BAD_ARG / MDGAT_ERR_UNSUPPORTED.
-static std::atomic<unsigned long long> attention_f64_launch_count[7];
-int attention_f64_plan_index(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus) {
-    if (B <= 0 || N <= 0 || M <= 0 || cus <= 0) return -1;
-    if (ragged && (cnt_min < 1 || cnt_min > (N < M ? N : M))) return -2;
-    // (a ragged batch: the grid, the LDS and the choice of the kernel follow the padded sizes)
-    const int nk_max = N > M ? N : M, nk_min = ragged ? cnt_min : N < M ? N : M;
-    if (topk > nk_min) return -2;      // torch.topk raises (mdgat.py:202)
-    if (nk_max > 2048 && topk > 0) return -3;
-    const bool dyn = topk > 0 && (ragged || !(topk == N && topk == M));
+// What a launch of attention_f64_kernel is, but for its pointers (f64.hpp: AttnF64Plan; the forms as mdgat_attention_f64_plan returns and
+// mdgat_attention_f64_launches counts them, include/mdgat_hip.h).  Pure: no HIP call.
+static std::atomic<unsigned long long> attention_f64_launch_count[ATTN_F64_FORMS];
+AttnF64Plan attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus) {
+    AttnF64Plan p{-1, MDGAT_OK};
+    if (B <= 0 || N <= 0 || M <= 0 || cus <= 0) return p;
+    auto refuse = [&p](int why, int rc) { p.form = why; p.rc = rc; return p; };
+    if (ragged && (cnt_min < 1 || cnt_min > (N < M ? N : M))) { p.bad_counts = true; return refuse(-2, MDGAT_ERR_BAD_ARG); }
+    // (a ragged batch: the grid, the LDS and the choice of the kernel follow the padded sizes, the histograms' place the smallest count)
+    const int nk_max = p.nk_max = N > M ? N : M, nk_min = p.nk_min = ragged ? cnt_min : N < M ? N : M;
+    if (topk > nk_min) return refuse(-2, MDGAT_ERR_BAD_ARG);      // torch.topk raises (mdgat.py:202)
+    if (nk_max > 2048 && topk > 0) return refuse(-3, MDGAT_ERR_UNSUPPORTED);
+    p.dyn = topk > 0 && (ragged || !(topk == N && topk == M));
+    const int ugroups = (B * 2 * MDGAT_HEADS + 7) / 8;
     // full attention: 32 queries per workgroup (half the key traffic per query).  Dynamic attention: 16 - at most 512 keys the
     // fp64 logits stay in registers between the passes (KEEP), beyond that the rounding images of 32 rows would not fit the LDS
-    if (!dyn) {
+    if (!p.dyn) {
         // (fewer than two workgroups per CU with 32 queries each - a pair or two of 512 keypoints: 16 queries per workgroup, the
         // same arithmetic per row.  64 queries per workgroup - 234 registers, two waves per SIMD - lose: 236 -> 289 us at batch 32)
         // one wave per 32 queries (SOLO) from F64_SOLO_MIN_WG_PER_CU workgroups of four such waves per CU on; mdgat_set_f64_attention_form(1)
         // forces it at every size (tests: ragged frames, one pair), (0) never
-        const long ugroups = ((long)B * 2 * MDGAT_HEADS + 7) / 8;
         const long solo_wgs = 8L * ((nk_max + 127) / 128) * ugroups;
-        if (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)cus)) return 6;
-        return 8L * ((nk_max + 31) / 32) * ugroups < 2L * cus ? 0 : 1;
-    }
-    return (nk_max <= 512 ? 2 : 4) + (tap ? 0 : 1);
-}
-void attention_f64_launch_counts(uint64_t counts[7]) {
-    for (int i = 0; i < 7; ++i) counts[i] = attention_f64_launch_count[i].load(std::memory_order_relaxed);
-}
-
-int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard,
-                         const int* cnt0, const int* cnt1, int cnt_min) {
-    if (B <= 0 || N <= 0 || M <= 0) return MDGAT_OK;
-    const bool ragged = cnt0 != nullptr;
-    if (ragged && (!cnt1 || cnt_min < 1 || cnt_min > (N < M ? N : M))) { mdgat_set_error("attention (fp64): bad per-pair counts"); return MDGAT_ERR_BAD_ARG; }
-    // (a ragged batch: the grid, the LDS and the choice of the kernel follow the padded sizes, the histograms' place the smallest count)
-    const int nk_max = N > M ? N : M, nk_min = ragged ? cnt_min : N < M ? N : M;
-    if (topk > nk_min) {   // torch.topk raises (mdgat.py:202)
-        mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", topk, nk_min);
-        return MDGAT_ERR_BAD_ARG;
-    }
-    if (nk_max > 2048 && topk > 0) {
-        mdgat_set_error("dynamic attention (fp64): %d keys per frame > 2048 supported", nk_max);
-        return MDGAT_ERR_UNSUPPORTED;
-    }
-    const int plan = attention_f64_plan_index(B, N, M, topk, sel != nullptr, ragged, cnt_min, f64_attention_form(), mdgat_cu_count());
-    if (plan < 0 || plan > 6) { mdgat_set_error("attention (fp64): no kernel for this launch (plan %d)", plan); return MDGAT_ERR_BAD_ARG; }
-    const bool dyn = plan >= 2 && plan <= 5;
-    AttnF64Args a{};
-    a.cnt0 = cnt0; a.cnt1 = cnt1;
-    // (the kernel writes the rows of a pair's own queries only)
-    if (ragged) if (int rc = mdgat_check_hip(hipMemsetAsync(msg, 0, (size_t)B * (N + M) * 128 * sizeof(double), s), "memset(ragged attention message)")) return rc;
-    a.qkv = qkv; a.msg = msg; a.N = N; a.M = M; a.cross = cross; a.topk = dyn ? topk : 0;
-    a.zq = dyn ? f64_normal_quantile_upper(((double)topk - 0.5) / (double)nk_max) : 0.f;
-    a.selW = (nk_max + 31) / 32;
-    a.sel = nullptr;
-    a.units = B * 2 * MDGAT_HEADS;
-    a.guard = guard;
-    if (sel && topk > 0) {
-        if (int rc = mdgat_check_hip(hipMemsetAsync(sel, dyn ? 0 : 0xff, mdgat_topk_sel_words(B, N, M) * sizeof(uint32_t), s), "memset(top-k tap)")) return rc;
-        if (dyn) a.sel = sel;
-    }
-    const int ugroups = (a.units + 7) / 8;
+        if (form == 1 || (form != 0 && solo_wgs >= F64_SOLO_MIN_WG_PER_CU * (long)cus)) p.form = ATTN_F64_SOLO;
+        else p.form = 8L * ((nk_max + 31) / 32) * ugroups < 2L * cus ? ATTN_F64_FULL16 : ATTN_F64_FULL32;
+    } else p.form = (nk_max <= 512 ? ATTN_F64_KEEP_TAP : ATTN_F64_RECOMPUTE_TAP) + (tap ? 0 : 1);
+    const bool solo = p.form == ATTN_F64_SOLO;
+    p.queries = solo ? 128 : p.form == ATTN_F64_FULL32 ? 32 : 16;
+    p.tiles = (nk_max + p.queries - 1) / p.queries;
+    p.workgroups = 8 * p.tiles * ugroups;
+    p.hist_ints = p.dyn ? attn_hist_ints(nk_min, nk_max) : 0;
+    // (the one-wave-per-query-block form keeps only the exponential's table in LDS)
+    p.lds = solo ? 256 * sizeof(double) : attn_lds_bytes(p.queries, nk_max, p.dyn, p.hist_ints);
     // (the LDS opt-in once per instantiation and device, at the largest size the instantiation is ever launched with: a limit that
-    // followed each launch's key count raced between host threads with different keypoint counts, and cost a driver call per launch.
-    // `cap` = that largest key count; the tag gives every call site its own instantiation of this lambda, hence its own `done` mask.)
-    auto go = [&](auto kern, int QT, bool tk, int cap, auto tag) -> int {
-        (void)tag;
-        static std::atomic<unsigned long long> done{0};
-        a.hist_ints = tk ? attn_hist_ints(nk_min, nk_max) : 0;
-        const bool solo = QT > 32;        // (QT = the queries of a workgroup; the one-wave-per-query-block form keeps only the exponential's table in LDS)
-        const size_t lds = solo ? 256 * sizeof(double) : attn_lds_bytes(QT, nk_max, tk, a.hist_ints);
-        if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), solo ? lds : attn_lds_bytes(QT, cap, tk, tk ? (cap > 512 ? 4 * RS_HIST_INTS : 16 * RQ_HIST_INTS) : 0), done, "attention_f64 LDS")) return rc;
-        a.tiles = (nk_max + QT - 1) / QT;
-        hipLaunchKernelGGL(kern, dim3(8 * a.tiles * ugroups), dim3(256), lds, s, a);
-        attention_f64_launch_count[decltype(tag)::value].fetch_add(1, std::memory_order_relaxed);
-        return mdgat_check_hip(hipGetLastError(), "attention_f64 launch");
-    };
-    // (the choice: attention_f64_plan_index above)
-    switch (plan) {
-    case 6: return go(attention_f64_kernel<false, 2, false, false, true>, 128, false, 0, std::integral_constant<int, 6>());
-    case 0: return go(attention_f64_kernel<false, 1, false>, 16, false, 0, std::integral_constant<int, 0>());
-    case 1: return go(attention_f64_kernel<false, 2, false>, 32, false, 0, std::integral_constant<int, 1>());
-    case 2: return go(attention_f64_kernel<true, 1, true, true>, 16, true, 512, std::integral_constant<int, 2>());
-    case 3: return go(attention_f64_kernel<true, 1, false, true>, 16, true, 512, std::integral_constant<int, 3>());
-    case 4: return go(attention_f64_kernel<true, 1, true>, 16, true, 2048, std::integral_constant<int, 4>());
-    default: return go(attention_f64_kernel<true, 1, false>, 16, true, 2048, std::integral_constant<int, 5>());
+    // followed each launch's key count raced between host threads with different keypoint counts, and cost a driver call per launch)
+    p.lds_optin = !p.dyn ? p.lds : nk_max <= 512 ? attn_lds_bytes(16, 512, true, 16 * RQ_HIST_INTS) : attn_lds_bytes(16, 2048, true, 4 * RS_HIST_INTS);
+    return p;
+}
+void attention_f64_launch_counts(uint64_t counts[MDGAT_ATTENTION_F64_FORMS]) {
+    for (int i = 0; i < ATTN_F64_FORMS; ++i) counts[i] = attention_f64_launch_count[i].load(std::memory_order_relaxed);
+}
+
+using AttnF64Kernel = void (*)(AttnF64Args);
+static AttnF64Kernel attention_f64_instantiation(int form) {
+    switch (form) {
+    case ATTN_F64_FULL16: return attention_f64_kernel<false, 1, false>;
+    case ATTN_F64_FULL32: return attention_f64_kernel<false, 2, false>;
+    case ATTN_F64_KEEP_TAP: return attention_f64_kernel<true, 1, true, true>;
+    case ATTN_F64_KEEP: return attention_f64_kernel<true, 1, false, true>;
+    case ATTN_F64_RECOMPUTE_TAP: return attention_f64_kernel<true, 1, true>;
+    case ATTN_F64_RECOMPUTE: return attention_f64_kernel<true, 1, false>;
+    case ATTN_F64_SOLO: return attention_f64_kernel<false, 2, false, false, true>;
     }
+    return nullptr;
 }
 
-int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
-                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s, const int* cnt0,
-                        const int* cnt1) {
-    const size_t total = (size_t)B * (N + M) * 37;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(assemble_f64_kernel, dim3(blocks), dim3(256), 0, s, kpts0, sigma0, fpfh0, kpts1, sigma1, fpfh1, in4, in33, B, N, M, guard, cnt0, cnt1);
+// The one launcher: the plan, the refusals, the memsets, the arguments, the instantiation, its LDS opt-in, the launch, its counter.
+int launch_attention_f64(const AttnF64Call& c) {
+    if (c.B <= 0 || c.N <= 0 || c.M <= 0) return MDGAT_OK;
+    const bool ragged = c.cnt0 != nullptr;
+    const AttnF64Plan p = attention_f64_plan(c.B, c.N, c.M, c.topk, c.sel != nullptr, ragged, c.cnt_min, f64_attention_form(), mdgat_cu_count());
+    if (ragged && (!c.cnt1 || p.bad_counts)) { mdgat_set_error("attention (fp64): bad per-pair counts"); return MDGAT_ERR_BAD_ARG; }
+    if (p.form == -2) { mdgat_set_error("dynamic attention: k=%d exceeds the number of keys (%d)", c.topk, p.nk_min); return p.rc; }
+    if (p.form == -3) { mdgat_set_error("dynamic attention (fp64): %d keys per frame > 2048 supported", p.nk_max); return p.rc; }
+    const AttnF64Kernel kern = attention_f64_instantiation(p.form);
+    if (!kern) { mdgat_set_error("attention (fp64): no kernel for this launch (plan %d)", p.form); return MDGAT_ERR_BAD_ARG; }
+    // (the kernel writes the rows of a pair's own queries only)
+    if (ragged) if (int rc = mdgat_check_hip(hipMemsetAsync(c.msg, 0, (size_t)c.B * (c.N + c.M) * 128 * sizeof(double), c.stream), "memset(ragged attention message)")) return rc;
+    AttnF64Args a{};
+    if (c.sel && c.topk > 0) {      // a uniform k == N == M keeps every key
+        if (int rc = mdgat_check_hip(hipMemsetAsync(c.sel, p.dyn ? 0 : 0xff, mdgat_topk_sel_words(c.B, c.N, c.M) * sizeof(uint32_t), c.stream), "memset(top-k tap)")) return rc;
+        if (p.dyn) a.sel = c.sel;
+    }
+    a.qkv = c.qkv; a.msg = c.msg; a.N = c.N; a.M = c.M; a.cross = c.cross; a.topk = p.dyn ? c.topk : 0;
+    a.zq = p.dyn ? f64_normal_quantile_upper(((double)c.topk - 0.5) / (double)p.nk_max) : 0.f;
+    a.selW = (p.nk_max + 31) / 32;
+    a.units = c.B * 2 * MDGAT_HEADS; a.tiles = p.tiles; a.hist_ints = p.hist_ints;
+    a.guard = c.guard; a.cnt0 = c.cnt0; a.cnt1 = c.cnt1;
+    static std::atomic<unsigned long long> done[ATTN_F64_FORMS];      // mdgat_lds_optin's devices, per instantiation
+    if (int rc = mdgat_lds_optin(reinterpret_cast<const void*>(kern), p.lds_optin, done[p.form], "attention_f64 LDS")) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.workgroups), dim3(256), p.lds, c.stream, a);
+    attention_f64_launch_count[p.form].fetch_add(1, std::memory_order_relaxed);
+    return mdgat_check_hip(hipGetLastError(), "attention_f64 launch");
+}
+
+// The inference assemble launch, by the inputs that are set: a bank of records (the starts), records, or the six arrays.
+int launch_assemble_f64(const AssembleF64& a, hipStream_t s) {
+    const size_t rows = (size_t)a.B * (a.N + a.M), work = a.rec0 ? rows : rows * 37;
+    if (a.rec0 && !rows) return MDGAT_OK;
+    const dim3 grid((unsigned)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192));
+    if (a.start0) {
+        hipLaunchKernelGGL(assemble_frames_ragged_f64_kernel, grid, dim3(256), 0, s, a.rec0, a.rec1, a.start0, a.start1, a.cnt0, a.cnt1, a.normalize,
+                           a.in4, a.in33, a.kp0, a.kp1, a.B, a.N, a.M, a.guard);
+        return mdgat_check_hip(hipGetLastError(), "assemble_frames_ragged_f64 launch");
+    }
+    if (a.rec0) {
+        hipLaunchKernelGGL(assemble_frames_f64_kernel, grid, dim3(256), 0, s, a.rec0, a.rec1, a.normalize, a.in4, a.in33, a.B, a.N, a.M, a.guard);
+        return mdgat_check_hip(hipGetLastError(), "assemble_frames_f64 launch");
+    }
+    hipLaunchKernelGGL(assemble_f64_kernel, grid, dim3(256), 0, s, a.kpts0, a.sigma0, a.fpfh0, a.kpts1, a.sigma1, a.fpfh1, a.in4, a.in33, a.B, a.N, a.M,
+                       a.guard, a.cnt0, a.cnt1);
     return mdgat_check_hip(hipGetLastError(), "assemble_f64 launch");
-}
-
-int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const float* rec1, int normalize, double* in4, double* in33, unsigned* guard,
-                               hipStream_t s) {
-    const size_t rows = (size_t)B * (N + M);
-    if (!rows) return MDGAT_OK;
-    const int blocks = (int)((rows + 255) / 256 < 8192 ? (rows + 255) / 256 : 8192);
-    hipLaunchKernelGGL(assemble_frames_f64_kernel, dim3(blocks), dim3(256), 0, s, rec0, rec1, normalize, in4, in33, B, N, M, guard);
-    return mdgat_check_hip(hipGetLastError(), "assemble_frames_f64 launch");
-}
-
-int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
-                                      const int* cnt0, const int* cnt1, int normalize, double* in4, double* in33, float* kp0, float* kp1,
-                                      unsigned* guard, hipStream_t s) {
-    const size_t rows = (size_t)B * (N + M);
-    if (!rows) return MDGAT_OK;
-    const int blocks = (int)((rows + 255) / 256 < 8192 ? (rows + 255) / 256 : 8192);
-    hipLaunchKernelGGL(assemble_frames_ragged_f64_kernel, dim3(blocks), dim3(256), 0, s, rec0, rec1, start0, start1, cnt0, cnt1, normalize, in4, in33,
-                       kp0, kp1, B, N, M, guard);
-    return mdgat_check_hip(hipGetLastError(), "assemble_frames_ragged_f64 launch");
 }
 
 int launch_assemble_frames_train_f64(int B, int T, const float* rec0, const float* rec1, const long long* start0, const long long* start1,

@@ -46,31 +46,51 @@ struct AttnF64Args {
     const int* cnt0;       // optional (device int32 [B], both or neither): a ragged batch - pair b has cnt0[b] / cnt1[b] keypoints; N, M are then
     const int* cnt1;       // the padded sizes: strides, grid and LDS follow them, queries and keys the pair's own counts
 };
-// attention (topk == 0) / dynamic_attention (mdgat.py:190-210) on fp64 q / k / v; sel: optional tap of the kept keys
+// One fp64 attention call: attention (topk == 0) / dynamic_attention (mdgat.py:190-210) on fp64 q / k / v.  Zero-initialise it and set what applies.
+struct AttnF64Call {
+    int B, N, M, cross, topk;
+    const double* qkv; double* msg;     // AttnF64Args::qkv, ::msg
+    uint32_t* sel;                      // optional tap of the kept keys
+    // cnt0 / cnt1: a ragged batch in slots padded to N / M (cnt_min: the smallest count of either frame, known to the caller on the host, who
+    // has checked 1 <= cnt0[b] <= N, 1 <= cnt1[b] <= M).  A pair's message rows and selection words are those of the pair run alone wherever
+    // the same instantiation runs it; message rows and selection words beyond its counts are zero.
+    const int *cnt0, *cnt1; int cnt_min;
+    unsigned* guard;                    // as GemmF64Args::guard, for the message rows
+    hipStream_t stream;
+};
+int launch_attention_f64(const AttnF64Call& c);
 // mdgat_set_f64_attention_form / MDGAT_F64_ATTENTION_FORM: -1 full attention by launch size; 0 always the split-key form (results do not
 // depend on the batch a pair travels in); 1 the big-launch form at every size
 int f64_attention_form();
-// Which of attention_f64_kernel's seven instantiations launch_attention_f64 runs (mdgat_attention_f64_plan, include/mdgat_hip.h), and how
-// often each has been launched by this process (mdgat_attention_f64_launches).  Host code only; the first touches no HIP call.
-int attention_f64_plan_index(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus);
-void attention_f64_launch_counts(uint64_t counts[7]);
-// cnt0 / cnt1: a ragged batch in slots padded to N / M (cnt_min: the smallest count of either frame, known to the caller on the host, who
-// has checked 1 <= cnt0[b] <= N, 1 <= cnt1[b] <= M).  A pair's message rows and selection words are those of the pair run alone wherever
-// the same instantiation runs it; message rows and selection words beyond its counts are zero.
-int launch_attention_f64(int B, int N, int M, int cross, int topk, const double* qkv, double* msg, uint32_t* sel, hipStream_t s, unsigned* guard = nullptr,
-                         const int* cnt0 = nullptr, const int* cnt1 = nullptr, int cnt_min = 0);
-// in4 [R][4] = x y z saliency, in33 [R][33] = FPFH; rows pair-major, frame 0 then frame 1
-int launch_assemble_f64(int B, int N, int M, const double* kpts0, const double* sigma0, const double* fpfh0, const double* kpts1,
-                        const double* sigma1, const double* fpfh1, double* in4, double* in33, unsigned* guard, hipStream_t s,
-                        const int* cnt0 = nullptr, const int* cnt1 = nullptr);      // cnt: a ragged batch - rows beyond a pair's counts are written as zeros, unread
-// the same from raw float32 records [B][N][37] (load_data.py:146-165; FPFH normalised as numpy does it in float32, 290-292)
-int launch_assemble_frames_f64(int B, int N, int M, const float* rec0, const float* rec1, int normalize, double* in4, double* in33, unsigned* guard,
-                               hipStream_t s);
-// a ragged chunk out of a bank of records: frame f of pair b = the cnt[b] records from row start[b] of rec0 / rec1 [rows][37], in slots of
-// N + M rows per pair; rows beyond the counts are zeros, their records unread; kp0 [B][N][3] / kp1 [B][M][3] float32 keypoints (optional)
-int launch_assemble_frames_ragged_f64(int B, int N, int M, const float* rec0, const float* rec1, const long long* start0, const long long* start1,
-                                      const int* cnt0, const int* cnt1, int normalize, double* in4, double* in33, float* kp0, float* kp1,
-                                      unsigned* guard, hipStream_t s);
+// What launch_attention_f64 chooses (mdgat_attention_f64_plan, mdgat_attention_f64_geometry; include/mdgat_hip.h numbers the forms) - the
+// instantiation and all of its launch but the pointers - and how often each has been launched by this process (mdgat_attention_f64_launches).
+// Host code only; the plan touches no HIP call.
+enum AttnF64Form { ATTN_F64_FULL16 = 0, ATTN_F64_FULL32, ATTN_F64_KEEP_TAP, ATTN_F64_KEEP, ATTN_F64_RECOMPUTE_TAP, ATTN_F64_RECOMPUTE, ATTN_F64_SOLO, ATTN_F64_FORMS = MDGAT_ATTENTION_F64_FORMS };
+struct AttnF64Plan {
+    int form, rc;           // AttnF64Form and MDGAT_OK, or no launch: -1 nothing to do, -2 / -3 what the launcher refuses as rc (the message is its own)
+    bool bad_counts;        // of the two -2 refusals: cnt_min lies outside the slots (else: k above nk_min)
+    int nk_max, nk_min;     // the larger slot; the fewest keys a frame has (ragged: cnt_min)
+    bool dyn;               // the layer keeps its k largest logits (uniform: unless k == N == M keeps every key; ragged: whenever topk > 0)
+    int queries;            // of a workgroup: 16, 32, or 128 (solo: 32 per wave)
+    int tiles, workgroups;  // query tiles per (pair, frame, head); the XCD-aware 1-D grid, 8 * tiles * ceil(units / 8)
+    int hist_ints;          // AttnF64Args::hist_ints
+    size_t lds, lds_optin;  // dynamic LDS bytes of this launch; of the instantiation's largest launch, which it is opted in to once per device
+};
+// tap: a selection buffer is passed; ragged: a call with counts, the smallest cnt_min; form: f64_attention_form(); cus: the device's compute units
+AttnF64Plan attention_f64_plan(int B, int N, int M, int topk, int tap, int ragged, int cnt_min, int form, int cus);
+void attention_f64_launch_counts(uint64_t counts[MDGAT_ATTENTION_F64_FORMS]);
+// One inference assemble launch: in4 [R][4] = x y z saliency, in33 [R][33] = FPFH; rows pair-major, frame 0 then frame 1.  Zero-initialise
+// it and set what applies; the launcher picks the kernel by the inputs that are set.
+struct AssembleF64 {
+    const double *kpts0, *sigma0, *fpfh0, *kpts1, *sigma1, *fpfh1;      // the six arrays, or
+    const float *rec0, *rec1; int normalize;    // raw float32 records [B][N][37] / [B][M][37] (load_data.py:146-165; FPFH normalised as numpy does it in float32, 290-292)
+    const int *cnt0, *cnt1;             // optional (the arrays, or a bank): a ragged batch - rows beyond a pair's counts are written as zeros, unread
+    // a ragged chunk out of a bank of records: frame f of pair b = the cnt[b] records from row start[b] of rec0 / rec1 [rows][37], in slots of
+    // N + M rows per pair; their records beyond the counts unread; kp0 [B][N][3] / kp1 [B][M][3] float32 keypoints (optional)
+    const long long *start0, *start1; float *kp0, *kp1;
+    double *in4, *in33; int B, N, M; unsigned* guard;
+};
+int launch_assemble_f64(const AssembleF64& a, hipStream_t s);
 // the loader's train-mode assembly (ensure_kpts_num, load_data.py:180-211) of the same chunk: the records with saliency > min_saliency, the
 // first T of them or padded to T by the loader's prepend loop; in4 / in33 in slots of T + T rows per pair, kp0 / kp1 [B][T][3], source0 / 1
 // [B][T] (the record row within its frame behind each slot), salient0 / 1 [B] (records kept), status [B][2] (1: a frame kept none and was
@@ -79,7 +99,7 @@ int launch_assemble_frames_train_f64(int B, int T, const float* rec0, const floa
                                      const int* cnt0, const int* cnt1, float min_saliency, int normalize, double* in4, double* in33, float* kp0,
                                      float* kp1, int* source0, int* source1, int* salient0, int* salient1, unsigned* status, unsigned* guard,
                                      hipStream_t s);
-// guard (all five): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
+// guard (all three): host-mapped status word raised when a value is not finite (tested by its bits), or nullptr
 int launch_f64_to_f32(const double* in, float* out, size_t n, unsigned* guard, hipStream_t s);
 
 // ---- layer_f64.hip: the tail of a propagation layer (mlp.0 + ReLU, mlp.3 + residual, the next layer's q | k | v) as ONE launch ----

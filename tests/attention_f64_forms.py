@@ -1,6 +1,7 @@
-"""The seven instantiations of attention_f64_kernel (csrc/f64.hip) as the tests name them, and the two symbols that make the launcher's
-choice observable: mdgat_attention_f64_plan (the choice as a pure function; no device) and mdgat_attention_f64_launches (launches so far
-by index)."""
+"""The seven instantiations of attention_f64_kernel (csrc/f64.hip) as the tests name them, and the three symbols that make the launcher's
+plan (attention_f64_plan) observable: mdgat_attention_f64_plan (the choice as a pure function; no device), mdgat_attention_f64_geometry
+(the same with the launch it stands for: queries per workgroup, tiles, grid, LDS bytes) and mdgat_attention_f64_launches (launches so
+far by index)."""
 import ctypes as C
 
 import numpy as np
@@ -19,8 +20,15 @@ def plan(B, N, M, topk=0, tap=False, ragged=False, cnt_min=0, form=-1, cus=256):
     return _lib().mdgat_attention_f64_plan(B, N, M, topk, int(tap), int(ragged), cnt_min, form, cus)
 
 
+def geometry(B, N, M, topk=0, tap=False, ragged=False, cnt_min=0, form=-1, cus=256):
+    """(index, queries per workgroup, query tiles per unit, workgroups, LDS bytes) of that launch; the four are 0 where there is none"""
+    q, t, w, lds = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_size_t(1)
+    idx = _lib().mdgat_attention_f64_geometry(B, N, M, topk, int(tap), int(ragged), cnt_min, form, cus, C.byref(q), C.byref(t), C.byref(w), C.byref(lds))
+    return idx, q.value, t.value, w.value, lds.value
+
+
 def counts():
-    buf = (C.c_uint64 * 7)()
+    buf = (C.c_uint64 * len(NAMES))()      # MDGAT_ATTENTION_F64_FORMS
     _lib().mdgat_attention_f64_launches(buf)
     return np.array(list(buf), dtype=np.int64)
 

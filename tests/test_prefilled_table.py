@@ -119,6 +119,7 @@ EXEMPT = {
     'mdgat_attention_ragged_plan': ('a plan', 'the attention launcher\'s choice for a ragged batch as a pure function'),
     'mdgat_gemm_f64_plan': ('a plan', 'the fp64 GEMM launcher\'s choice as a pure function'),
     'mdgat_attention_f64_plan': ('a plan', 'the fp64 attention launcher\'s choice as a pure function'),
+    'mdgat_attention_f64_geometry': ('a plan', 'the fp64 attention launcher\'s launch geometry as a pure function, into host integers'),
     'mdgat_layer_f64_plan': ('a plan', 'the fp64 layer-tail and encoder launchers\' choice as a pure function'),
     'mdgat_sinkhorn_f64_plan': ('a plan', 'the fp64 Sinkhorn launchers\' choice as a pure function'),
     'mdgat_layer_launches': ('a counter', 'launches by instantiation, into a host array'),
